@@ -3,7 +3,18 @@
 bench.py -- rays/sec of the pixelNeRF volume-rendering hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--prec f16x3|f16] [--rays R]
-                    [--workload sn64|dtu] [--bcast tree|flat]
+                    [--workload sn64|dtu] [--bcast tree|flat] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given, and prints
+the result line (headline, `ms_per_step`, the committed-profile roofline of the timed launches, `comm` when distributed).
+Everything else the line can carry -- the f16 peer region, the live PMC passes, the CPU / eager baselines, the PSNR and
+fp32 cross-checks, latency / encode timings and the extra configurations -- runs only with --full (the --no-* switches
+still turn single sections of a --full run off).
+
+--dump-outputs DIR: after the timed steps, what the timed path returned to its caller in its last step, as float32 .npy
+files: DIR/rgb.npy (rays, 3) and DIR/depth.npy (rays,); with N ranks, rank 0's gathered result over all ranks.  The inputs
+(grid, weights, rays, noise keys) are seeded, so the same arguments give the same inputs on every run.  Above
+MAX_DUMP_RAYS rays a fixed, seeded sample of the rays is written, with its ray indices in DIR/ray_index.npy (float64).
 
 Headline workload (BASELINE.json configs[1], the configuration the metric is quoted on): sn64 NMR geometry, 64x64 target
 views, 1 source view, 64 coarse + 128 fine samples (112 importance + 16 depth), separate coarse / fine ResnetFC
@@ -16,20 +27,20 @@ PRECISION.  The reference computes in fp32 (nn.Linear, no autocast: src/model/re
 headline therefore runs `precision="f16x3"` -- the fp32-CLASS fused kernel (pnr_split.hip: every operand a (head, tail)
 pair of fp16, three f16 MFMAs per product, fp32 accumulation and tables; per-point |rgb| <= 2e-5 against the reference's
 goldens, tests/test_hip_split.py) -- and `dtype` says so.  The 16-bit-operand kernel (`precision="f16"`, PSNR >= 52 dB
-against the reference) is timed in a second region of the same length and reported as a PEER block `f16_path`
+against the reference) is timed (--full) in a second region of the same length and reported as a PEER block `f16_path`
 with its own roofline: faster, but narrower arithmetic than the reference, so it is not `value`.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU, RCCL): weak scaling -- every rank renders its own R rays; each
 timed step also contains the single feature-grid broadcast from rank 0 and the final gather of (rgb, depth) to rank 0
-(SURVEY.md 8e).  The same run then times BASELINE configs[3] in its strong-scaling form (`extra.strong_dtu`: ONE DTU
+(SURVEY.md 8e).  With --full the same run then times BASELINE configs[3] in its strong-scaling form (`extra.strong_dtu`: ONE DTU
 400x300 image, 3 source views, 176 MiB grid, its 120 000 rays sharded contiguously over the N ranks; step = grid broadcast
 + render + gather).  `--workload dtu` makes that form the headline instead (`scaling: "strong"`).
 
-The JSON line also carries
+The JSON line also carries (a plain run: `roofline` from the committed profile, and `comm`; the rest with --full)
   roofline     : the fused network kernel (>= 99 % of the work) against the dense f16 MFMA peak: algorithmic FLOP of the
                  launches in the timed region / their HIP-event time on the launch stream; executed_mfma_tflops counts the
                  MFMAs really issued (3 per product for f16x3, lin_z folded away); traffic = bytes per launch at the L2 <-> fabric
-                 interface, MEASURED IN THIS RUN by two rocprofv3 --pmc passes around a 2-step child of the same command (the
+                 interface, MEASURED IN THIS RUN (--full) by rocprofv3 --pmc passes around a 2-step child of the same command (the
                  committed PMC profile, stamped with the kernel-source hash, is the fallback and rides along for comparison);
   torch_eager_gpu_baseline : the same algorithm in eager PyTorch-ROCm fp32 on this GPU (oracle restatement), in the reference's
                  execution shape -- 50 000-ray batches, 50 000-point model calls (eval/eval.py:137,264; nerf.py:190-216) -- and,
@@ -66,6 +77,27 @@ DTYPE_NOTE = {"f16x3": "fp32-class: (head, tail) fp16 operand pairs, 3 f16 MFMAs
                        "per-point |rgb| <= 2e-5 vs the reference (the reference's own arithmetic class)",
               "f16": "fp16 MFMA operands, fp32 accumulate: narrower than the reference's fp32 (PSNR >= 52 dB bar)",
               "bf16": "bf16 MFMA operands (experiment flag)"}
+MAX_DUMP_RAYS = 1 << 21  # --dump-outputs: rgb + depth in float32 stay within 32 MiB
+
+
+def dump_outputs(dirname, rgb, depth):
+    """--dump-outputs: the (rays, 3) colours and (rays,) depths of the last timed step as float32 .npy files; above
+    MAX_DUMP_RAYS rays a fixed, seeded sample of the rays (sorted) and its ray indices."""
+    import numpy as np
+    rgb, depth = rgb.float().cpu().numpy(), depth.float().cpu().numpy()
+    arrays = {"rgb": rgb, "depth": depth}
+    if rgb.shape[0] > MAX_DUMP_RAYS:
+        idx = np.sort(np.random.RandomState(0).choice(rgb.shape[0], MAX_DUMP_RAYS, replace=False))
+        arrays = {"rgb": rgb[idx], "depth": depth[idx], "ray_index": idx.astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
+def gathered_outputs(bufs, sizes):
+    """rank 0's dist.gather buffers ((rgb | depth) rows, padded to the largest shard) -> (rgb, depth) over all ranks' rays"""
+    out = torch.cat([b[:n] for b, n in zip(bufs, sizes)])
+    return out[:, :3], out[:, 3]
 
 
 def build(dev, prec, scene_name="sn64"):
@@ -636,7 +668,8 @@ def self_launch(n):
 
 def timed_region(step, fence, steps, warmup):
     """W untimed warm-ups, then exactly K steps bracketed by fence() (synchronize [+ barrier + synchronize]); HIP events of the
-    network-kernel launches on their stream are collected over the same K steps.  -> (elapsed s, kernel ms, launches)"""
+    network-kernel launches on their stream are collected over the same K steps.
+    -> (elapsed s, kernel ms, launches, what the last timed step returned)"""
     from pixelnerf_amd import ops
     for _ in range(warmup):
         step()
@@ -644,12 +677,12 @@ def timed_region(step, fence, steps, warmup):
     ops.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     kern_ms, n_launch = ops.profile_read()
     ops.profile_enable(False)
-    return elapsed, kern_ms, n_launch
+    return elapsed, kern_ms, n_launch, last
 
 
 def strong_dtu(dev, prec, world, rank, steps, warmup, bcast, fence, dist_on=None, layout="nhwc"):
@@ -669,6 +702,7 @@ def strong_dtu(dev, prec, world, rank, steps, warmup, bcast, fence, dist_on=None
     renderer.ray_id_offset, renderer.ray_id_stride = lo, R  # the sharded image equals the unsharded one
     tb, tg = [0.0], [0.0]
     dist_on = world > 1 if dist_on is None else dist_on
+    sizes = [shard_bounds(R, r, world)[1] - shard_bounds(R, r, world)[0] for r in range(world)]
 
     def step():
         net._tables.clear()
@@ -679,10 +713,10 @@ def strong_dtu(dev, prec, world, rank, steps, warmup, bcast, fence, dist_on=None
             e1.record()
         with torch.no_grad():
             rgb, depth = render_par(rays[None])
+        bufs = None
         if dist_on:
             e2, e3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             out = torch.cat([rgb[0], depth[0].unsqueeze(-1)], dim=-1)  # 16 B/ray
-            sizes = [shard_bounds(R, r, world)[1] - shard_bounds(R, r, world)[0] for r in range(world)]
             if out.shape[0] < max(sizes):
                 out = torch.cat([out, out.new_zeros(max(sizes) - out.shape[0], 4)])
             bufs = [torch.empty_like(out) for _ in range(world)] if rank == 0 else None
@@ -690,17 +724,18 @@ def strong_dtu(dev, prec, world, rank, steps, warmup, bcast, fence, dist_on=None
             dist.gather(out, bufs, dst=0)
             e3.record()
             evs.append((e0, e1, e2, e3))
-        return rgb
+        return rgb[0], depth[0], bufs
 
     evs = []
     torch.manual_seed(4321)
-    elapsed, kern_ms, n_launch = timed_region(step, fence, steps, warmup)
+    elapsed, kern_ms, n_launch, (rgb, depth, bufs) = timed_region(step, fence, steps, warmup)
     for e0, e1, e2, e3 in evs[-steps:]:
         tb[0] += e0.elapsed_time(e1)
         tg[0] += e2.elapsed_time(e3)
     NS = scene["NS"]
     res = {"elapsed": elapsed, "kern_ms": kern_ms, "n_launch": n_launch, "R": R, "rays_this_rank": hi - lo, "NS": NS,
-           "bcast_ms": tb[0] / steps, "gather_ms": tg[0] / steps, "grid_bytes": int(scene["latent"].numel() * 4)}
+           "bcast_ms": tb[0] / steps, "gather_ms": tg[0] / steps, "grid_bytes": int(scene["latent"].numel() * 4),
+           "outputs": gathered_outputs(bufs, sizes) if bufs is not None else (rgb, depth)}
     del net, renderer
     torch.cuda.empty_cache()
     return res
@@ -734,6 +769,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed BASELINE configs 3/4/5 section (extra.configs)")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure `roofline.traffic` "
                     "in this run (profiling / A/B invocations; the committed profile is reported instead)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other section (peer region, live PMC passes, CPU / eager baselines, "
+                         "cross-checks, latency / encode, extra configurations); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's rgb / depth as float32 DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -800,6 +840,8 @@ def main():
         # ---- BASELINE configs[3] as the headline: one DTU image over N ranks
         st = strong_dtu(dev, args.prec, world, rank, args.steps, args.warmup, args.bcast, fence, dist_on, args.bcast_layout)
         elapsed = max_over_ranks(st["elapsed"])
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, *st["outputs"])
         if rank == 0:
             rays_per_s = st["R"] * args.steps / elapsed
             res = {"metric": "rays/sec (64 coarse + 128 fine samples) at matched PSNR vs reference",
@@ -839,6 +881,7 @@ def main():
             e1.record()
         with torch.no_grad():
             rgb, depth = render_par(rays[None])
+        bufs = None
         if dist_on:
             out = torch.cat([rgb[0], depth[0].unsqueeze(-1)], dim=-1)  # 16 B/ray
             bufs = [torch.empty_like(out) for _ in range(world)] if rank == 0 else None
@@ -847,12 +890,15 @@ def main():
             dist.gather(out, bufs, dst=0)
             e3.record()
             comm_ev.append((e0, e1, e2, e3))
-        return rgb
+        return rgb[0], depth[0], bufs
 
     torch.manual_seed(1234 + rank)
     net.precision = args.prec
-    elapsed, kern_ms, n_launch = timed_region(step, fence, args.steps, args.warmup)
+    elapsed, kern_ms, n_launch, (rgb, depth, bufs) = timed_region(step, fence, args.steps, args.warmup)
     elapsed = max_over_ranks(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *(gathered_outputs(bufs, [R] * world) if bufs is not None else (rgb, depth)))
+    del rgb, depth, bufs
     comm = None
     if dist_on:
         ev = comm_ev[-args.steps:]
@@ -862,11 +908,11 @@ def main():
                 "backend": args.backend, "ranks": world}
 
     peer = None
-    if world == 1 and not args.no_peer:
+    if args.full and world == 1 and not args.no_peer:
         peer_prec = "f16" if args.prec == "f16x3" else "f16x3"
         net.precision = peer_prec
         torch.manual_seed(1234 + rank)
-        pe, pk, pn = timed_region(step, fence, args.steps, args.warmup)
+        pe, pk, pn, _ = timed_region(step, fence, args.steps, args.warmup)
         net.precision = args.prec
         peer = (peer_prec, pe, pk, pn)
 
@@ -895,7 +941,7 @@ def main():
                 "what": "the same workload, same steps / warm-up, timed in a second region right after the headline: " + DTYPE_NOTE[pp],
                 "value": R * args.steps / pe, "unit": "rays/s", "ms_per_step": pe / args.steps * 1e3, "dtype": pp,
                 "roofline": roofline_block(pp, R, args.steps, pk, pn, NS, True, pe, default_shape)}
-    if world == 1 and rank == 0 and default_shape and not args.no_live_pmc:
+    if args.full and world == 1 and rank == 0 and default_shape and not args.no_live_pmc:
         # roofline.traffic measured in THIS run (outside the timed region): two counter passes around a 2-step child
         live, why, live_extras = measure_traffic_live(args.prec)
         rf = res["roofline"]
@@ -907,7 +953,7 @@ def main():
             rf.update(live_extras)  # shader clock during the kernel / MFMA-busy share of this box (third pass)
         else:
             rf["traffic_live_error"] = why
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # bounded CPU sample of the same workload; also yields the matched-PSNR figure.  torch's intra-op pool does not
         # scale to every core of a many-socket host on 512-wide GEMMs: pick the thread count that is FASTEST on a 64-ray
         # probe (fair to the CPU), then time the real sample with it.  `cores` reports the threads actually used.
@@ -963,7 +1009,7 @@ def main():
             "sample": "BASELINE configs[0]: sn64, 1 view, 32 coarse samples (no fine pass), ray_batch=4096 in ONE call on the CPU path, %.1f s" % dt1,
             "hip_same_call_ms": dtg * 1e3, "hip_same_call_rays_per_s": 4096 / dtg, "hip_precision": args.prec,
             "psnr_db_hip_vs_cpu": O.psnr(o1.coarse.rgb.cpu(), ref1["coarse"]["rgb"])}
-    if world == 1 and not args.no_latency:
+    if args.full and world == 1 and not args.no_latency:
         # single-image latency (one 4096-ray call through render_par, fold included) next to the saturated rate
         lat_ms = {}
         with torch.no_grad():
@@ -985,7 +1031,7 @@ def main():
             res["encode_ms"] = encode_timing(dev)
         except Exception as e:
             res["encode_ms"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-    if world == 1 and not args.no_f32_check:
+    if args.full and world == 1 and not args.no_f32_check:
         # full-size cross-check on the GPU, outside the timed region: all R rays of the step with the same noise through
         # the exact, unfused fp32-MFMA validation path (agrees with the reference to ~1e-6)
         from oracle import pnr_oracle as O
@@ -1010,7 +1056,7 @@ def main():
             res[peer[0] + "_path"]["psnr_db_full_size_vs_f32_hip"] = O.psnr(pfast.fine.rgb.cpu(), exact.fine.rgb.cpu())
         net.precision = args.prec
         res["f32_unfused_validation_path_rays_per_s"] = R / dt32
-    if world == 1 and not args.no_eager_baseline:
+    if args.full and world == 1 and not args.no_eager_baseline:
         # the comparison point north_star names, in the shape the reference runs it (50 000-ray calls, 50 000-point model
         # calls); the unchunked 16 384-ray form earlier rounds quoted stays next to it under its own key
         res["torch_eager_gpu_baseline"] = eager_gpu_baseline(scene, mlps, rays, dev, n=50000, eval_batch_size=50000)
@@ -1029,7 +1075,7 @@ def main():
             res[peer[0] + "_path"]["speedup_vs_torch_eager_gpu"] = res[peer[0] + "_path"]["value"] / res["torch_eager_gpu_baseline"]["value"]
     del net, renderer, render_par
     torch.cuda.empty_cache()
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extra = {}
         if world == 1:
             # BASELINE configs[2..4] on this one GPU, outside the timed region

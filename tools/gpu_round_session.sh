@@ -4,7 +4,7 @@
 #   bash tools/gpu_round_session.sh TAG      -> everything under gpurun_out/TAG/ ; copy what is to be judged into profiles/
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; TAG=${1:-round}; O=gpurun_out/$TAG; mkdir -p $O; R=$PWD; export TMPDIR=/tmp
 timeout 1700 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log; tail -3 $O/pytest.log
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - $O/bench.json <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r=d["roofline"]

@@ -3,7 +3,7 @@
 
     python tools/scale_report.py SCALE_r06.json                 # the driver's file: a list / dict of per-N bench lines
     python tools/scale_report.py n1.json n2.json n4.json n8.json  # or one file per run (the last `{...}` line of each is read)
-    python bench.py --gpus 1 | python tools/scale_report.py -     # or stdin
+    python bench.py --gpus 1 --full | python tools/scale_report.py -     # or stdin (--full: the line carries extra.*)
 
 Prints, per workload found (the weak-scaling sn64 headline `value`, and `extra.strong_dtu` = ONE 120 000-ray DTU image sharded over
 the ranks): rays/s, speed-up and efficiency against N = 1, the step / image time, and the rank-0 communication
