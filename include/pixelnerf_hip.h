@@ -75,7 +75,7 @@ int pnr_version(int *major, int *minor);
 /* ABI revision of THIS header: bumped whenever a struct layout or an entry point's argument list changes.  The
  * library returns the value it was compiled with; a binding must compare it with the header it was written against
  * before the first call (pixelnerf_amd/_lib.py does, and refuses a stale or foreign .so). */
-#define PNR_ABI_VERSION 8
+#define PNR_ABI_VERSION 9
 int pnr_abi_version(void);
 int pnr_device_info(int *num_cus, int *lds_bytes_per_block);
 
@@ -311,6 +311,38 @@ int pnr_depth_sample_backward(const PnrScene *scene /*host*/, const float *rays,
                               int K, const int *ranks, const float *n4, int Kfd, const float *depth_c, float depth_std,
                               const float *d_in42, const float *d_zlat, const float *dz_comp, float *contrib, void *stream);
 
+/* pnr_composite_backward plus d_far (R) (nullable) = dL/d(far) through the last delta far - z_{K-1} (nerf.py:181). */
+int pnr_composite_backward_far(const float *rays, const float *z, const float *rgbsigma, int R, int K,
+                               int white_bkgd, const float *d_rgb, const float *d_depth,
+                               const float *d_weights, float *d_rgbsigma, float *d_z, float *d_far,
+                               int pre_activation, void *stream);
+
+/* Gradients with respect to the rays and the source cameras of one network pass (torch autograd through
+ * src/render/nerf.py:98-249 and src/model/models.py:161-215): per (view, sample) the world-space gradient of the point
+ * p = o + z d through the positional code of R_v p, the projection of R_v p + t_v and the bilinear lookup, and of the
+ * view direction R_v d; summed in a fixed order (no atomics: bit-reproducible).
+ *   d_rays (R,8): d origin, d direction, d near, d far.  dL/dz of a sample (network term over all views + dz_comp) goes
+ *     to near / far through z = near (1-s) + far s (lindisp: 1/z linear in s; nerf.py:98-148); depth samples (ranks) only
+ *     where their clamp is active (nerf.py:157-160) -- unclamped ones belong to pnr_depth_sample_backward.  d_far (R)
+ *     of pnr_composite_backward_far is added to column 7.
+ *   d_poses (SB*NS,3,4): d of the world->camera [R | t] in the scene; d_focal (n_focal,2), d_c (n_c,2): d of the scene's
+ *     focal (fy negated as stored) and principal point, each summed over the rows it is broadcast to.
+ * Nullable: dz_comp, d_far, ranks (with n4, depth_c, Kfd), d_rays, d_poses, d_focal, d_c.
+ * workspace: pnr_camera_backward_workspace_bytes(R, K, rays_per_obj, NS) bytes. */
+size_t pnr_camera_backward_workspace_bytes(int R, int K, int rays_per_obj, int NS);
+/* The sampling part of that reduction alone, for renderers around an arbitrary model (points built by the caller):
+ * dz (R,K) = dL/d(sample positions) -> d_rays (R,8) with columns 0..5 zero, near / far as above (z = near (1-s) + far s,
+ * lindisp: 1/z linear in s, nerf.py:98-148; the depth samples at `ranks` only where their clamp is active,
+ * nerf.py:157-160), plus d_far (R) (nullable).  Nullable: ranks (with n4, depth_c, Kfd), d_far. */
+int pnr_sample_bounds_backward(const float *rays, const float *z, const float *dz, int R, int K, int lindisp,
+                               const int *ranks, const float *n4, int Kfd, const float *depth_c, float depth_std,
+                               const float *d_far, float *d_rays, void *stream);
+int pnr_camera_backward(const PnrScene *scene /*host*/, const float *rays, const float *z, int R, int rays_per_obj,
+                        int K, int lindisp, const float *d_in42, const float *d_zlat, const float *dz_comp,
+                        const float *d_far, const int *ranks, const float *n4, int Kfd, const float *depth_c,
+                        float depth_std, float *d_rays, float *d_poses, float *d_focal, float *d_c,
+                        void *workspace, void *stream);
+
 /* Fused data-gradient chain of one ResnetFC (reverse of src/model/resnetfc.py:132-184).
  * g_out (P,4) = dL/d(lin_out output) (pre sigmoid/relu), grad_scale = power of two the chain is
  * run at (16-bit range management; every dump is scaled by it).  NS = views per object. */
@@ -407,6 +439,11 @@ int pnr_render_forward(const PnrScene *scene /*host*/, const void *packed_coarse
  * poses (NV,4,4) camera-to-world -> rays (NV,H,W,8). */
 int pnr_gen_rays(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
                  float z_near, float z_far, float *rays, void *stream);
+/* Its backward (src/util/util.py:238-276 under torch autograd): d rays (NV,H,W,8) -> d camera-to-world [R | t]
+ * (NV,3,4): d t = sum of d origin, d R = sum of d direction (x) unprojected pixel direction; fixed-order sum per pose.
+ * The intrinsics are constants. */
+int pnr_gen_rays_backward(const float *d_rays, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                          float *d_poses, void *stream);
 
 /* ---- counter-based random draws (production mode; SURVEY.md 7 "hard parts", nerf.py:111,135,141,158) ------------
  * The reference draws its jitter / importance / depth-sample noise with four torch.rand launches per call.  The
@@ -569,14 +606,16 @@ typedef struct PnrSplitSaved {
 int pnr_eval_ray_samples_split_train(const PnrScene *scene /*host*/, const void *packed_split, const void *tables_f32,
                                      const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
                                      const PnrSplitSaved *saved /*host*/, void *stream);
-/* grad_scale = device [s, 1/s] from pnr_grad_scale(g_out); outputs as pnr_mlp_backward_f32 (d_zlat required, d_in nullable). */
+/* grad_scale = device [s, 1/s] from pnr_grad_scale(g_out); outputs as pnr_mlp_backward_f32 (d_zlat required, d_in and grads
+ * nullable: grads == NULL runs the data-gradient chain only, without the weight-gradient launches). */
 size_t pnr_mlp_backward_split_workspace_bytes(long long P, int NS);
 int pnr_mlp_backward_split(const PnrMlpWeights *w /*host*/, const PnrSplitSaved *saved /*host*/, const float *g_out, long long P,
                            int NS, const PnrMlpWeights *grads /*host*/, float *d_zlat, float *d_in /*nullable*/,
                            const float *grad_scale, void *workspace, size_t workspace_bytes, void *stream);
 /* All parameter gradients of one ResnetFC + d(interpolated latent) [+ d(lin_in operand)] from g_out (P,4) =
  * dL/d(lin_out output): `grads` holds device pointers of the 30 gradient tensors in PnrMlpWeights' layout (same shapes as
- * the parameters, overwritten); d_zlat (rows_v,512), d_in (rows_v,42) or NULL. */
+ * the parameters, overwritten) or NULL (data gradients only: pose refinement with a frozen network, src/model/models.py:161-215
+ * differentiated with respect to the inputs alone -- no weight-gradient launch); d_zlat (rows_v,512), d_in (rows_v,42) or NULL. */
 size_t pnr_mlp_backward_f32_workspace_bytes(long long P, int NS);
 /* split_gemm = 1 additionally takes grad_scale = device [s, 1/s] from pnr_grad_scale(g_out): the gradient chain runs at the
  * power-of-two scale s (fp16 range of the operand heads), results are un-scaled exactly on their way out. */

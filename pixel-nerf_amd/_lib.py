@@ -15,10 +15,10 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # experiment switch is compiled with -DPNR_VARIANT and reports a NEGATIVE ABI revision: load() refuses it unless the
 # process says PIXELNERF_ALLOW_VARIANT=1 (the A/B tools do) -- a stray -D can no longer yield a library that passes for the product
 LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelnerf_hip.so")
-SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_f32.hip", "pnr_encode.hip"]
+SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip"]
 HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_raysrc.h", "pnr_internal.h", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
-ABI_VERSION = 8  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
+ABI_VERSION = 9  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3
 PRECISIONS = {"f16": PREC_F16, "fp16": PREC_F16, "bf16": PREC_BF16, "f32": PREC_F32, "fp32": PREC_F32, "f16x3": PREC_F16X3}
 
@@ -132,6 +132,12 @@ PROTOTYPES = {
     "pnr_composite_backward": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "pnr_position_backward": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "pnr_depth_sample_backward": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _I, _I, _P, _P, _I, _P, _F, _P, _P, _P, _P, _P]),
+    "pnr_composite_backward_far": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "pnr_camera_backward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "pnr_camera_backward": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _F,
+                                 _P, _P, _P, _P, _P, _P]),
+    "pnr_gen_rays_backward": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _P, _P]),
+    "pnr_sample_bounds_backward": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _F, _P, _P, _P]),
     "pnr_mlp_backward": (_I, [_P, _I, ctypes.POINTER(PnrTrainDumps), _P, _F, _P, ctypes.c_longlong, _I,
                               ctypes.POINTER(PnrBackwardDumps), _P]),
     "pnr_weight_grad_workspace_bytes": (_SZ, []),

@@ -21,8 +21,9 @@ Gradients flow to every ResnetFC parameter of both networks and to `encoder.late
 the ResNet-34 through PyTorch autograd), including the reference's one position-gradient path:
 fine loss -> positions of the n_fine_depth samples (compositing deltas/depth, positional code,
 projection + bilinear lookup) -> sort permutation -> clamp -> coarse depth (nerf.py:157-160,292)
--> coarse network.  Coarse and importance samples carry no gradient in the reference either
-(rays are inputs, importance weights are detached, nerf.py:288).
+-> coarse network.  When the rays or the scene's cameras (net.poses / focal / c) require grad, every pass also asks for the
+network-input gradient and pnr_camera_backward turns it into d rays (origins, directions, near / far through the sampling maps)
+and d poses / focal / c (importance weights stay detached, nerf.py:288).
 """
 
 import torch
@@ -88,18 +89,19 @@ def _train_eval(net, scene, coarse, rays, z):
     return ops.eval_ray_samples_train(scene, net.packed(coarse, folded=False, training_pass=True), rays, z)
 
 
-def _pass_grads(net, mlp, dumps, g_out, scene_NS, want_d_in):
-    """-> (grads, d_zlat, d_in, releasable) of one pass at the network's precision"""
+def _pass_grads(net, mlp, dumps, g_out, scene_NS, want_d_in, want_grads=True):
+    """-> (grads, d_zlat, d_in, releasable) of one pass at the network's precision.  want_grads=False (no parameter of this
+    network needs a gradient): the data-gradient chain alone, no weight-gradient launch, grads None."""
     if isinstance(dumps, ops.SplitSaved):
-        grads, d_zlat, d_in = ops.mlp_backward_split(mlp.packed("f32"), dumps, g_out, want_d_in=want_d_in)
+        grads, d_zlat, d_in = ops.mlp_backward_split(mlp.packed("f32"), dumps, g_out, want_d_in=want_d_in, want_grads=want_grads)
         return grads, d_zlat, d_in, _NoRelease
     if net.precision in ("f32", "f16x3"):
-        grads, d_zlat, d_in = ops.mlp_backward_f32(mlp.packed("f32"), dumps, g_out, want_d_in=want_d_in)
+        grads, d_zlat, d_in = ops.mlp_backward_f32(mlp.packed("f32"), dumps, g_out, want_d_in=want_d_in, want_grads=want_grads)
         return grads, d_zlat, d_in, _NoRelease
-    return _mlp_grads(None, mlp.packed_bwd(net.precision), dumps, g_out, scene_NS, want_d_in=want_d_in)
+    return _mlp_grads(None, mlp.packed_bwd(net.precision), dumps, g_out, scene_NS, want_d_in=want_d_in, want_grads=want_grads)
 
 
-def _mlp_grads(mlp_state, packed_bwd, fwd, g_out, scene_NS, want_d_in=False):
+def _mlp_grads(mlp_state, packed_bwd, fwd, g_out, scene_NS, want_d_in=False, want_grads=True):
     """All parameter gradients of one ResnetFC + d(interpolated latent) [+ d(lin_in operand)] from
     one backward pass.  fwd: ops.TrainDumps of the forward; g_out (P,4) fp32 = dL/d(lin_out output)."""
     # run the 16-bit chain at a power-of-two scale that puts max|g| near 2^6 (exact to undo); the scale is picked
@@ -107,6 +109,8 @@ def _mlp_grads(mlp_state, packed_bwd, fwd, g_out, scene_NS, want_d_in=False):
     sc = ops.grad_scale(g_out)
     bd = ops.mlp_backward(packed_bwd, fwd, g_out, sc[0:1])
     inv_s = sc[1:2]
+    if not want_grads:  # data gradients only: the weight-gradient GEMMs are not launched
+        return None, bd.d_zlat, (bd.d_in if want_d_in else None), bd
 
     prec = packed_bwd.precision
     grads = {}
@@ -131,12 +135,13 @@ def _mlp_grads(mlp_state, packed_bwd, fwd, g_out, scene_NS, want_d_in=False):
 
 
 class _RenderFunction(torch.autograd.Function):
-    """inputs: cfg (python object), rays (R,8), latent (SB*NS,512,Hl,Wl), 30 coarse params,
-    30 fine params (or the coarse ones again when mlp_fine is None).
+    """inputs: cfg (python object), rays (R,8), latent (SB*NS,512,Hl,Wl), the scene's cameras (net.poses (SB*NS,3,4)
+    world->camera, net.focal, net.c -- the tensors ops.Scene points at), 30 coarse params, 30 fine params (or the coarse
+    ones again when mlp_fine is None).
     outputs: rgb_c, depth_c, weights_c[, rgb_f, depth_f, weights_f]."""
 
     @staticmethod
-    def forward(ctx, cfg, rays, latent, *params):
+    def forward(ctx, cfg, rays, latent, poses, focal, c, *params):
         # outputs the loss does not use (depths, weights) arrive in backward as None, not as zero tensors torch would
         # have to fill and the compositing backward would have to read
         ctx.set_materialize_grads(False)
@@ -163,6 +168,7 @@ class _RenderFunction(torch.autograd.Function):
             outs += [rgb_f, depth_f, w_f]
         ctx.cfg, ctx.rays, ctx.scene, ctx.passes = cfg, rays, scene, passes
         ctx.latent_shape = latent.shape
+        ctx.cam_shapes = (poses.shape, focal.shape, c.shape)
         ctx.n_params = len(params)
         return tuple(outs)
 
@@ -176,6 +182,9 @@ class _RenderFunction(torch.autograd.Function):
         net = cfg["net"]
         dev = rays.device
         need_latent = ctx.needs_input_grad[2]
+        need_rays, need_poses, need_focal, need_c = ctx.needs_input_grad[1], *ctx.needs_input_grad[3:6]
+        need_cam = need_rays or need_poses or need_focal or need_c
+        cam = [None, None, None, None]  # d rays, d poses, d focal, d c summed over the passes (fine, then coarse)
         # one zeroed grid gradient PER PASS, summed at the end: pnr_latent_scatter's LDS-slab form leaves at most two atomic adds
         # per element and call (its owner workgroups split the points at most two ways on a full-size batch), and two terms onto
         # zero commute -- the latent gradient, and with it the whole step, is then bit-reproducible.  Accumulating the fine and
@@ -189,6 +198,9 @@ class _RenderFunction(torch.autograd.Function):
         d_lat = torch.zeros((n_buf, ctx.latent_shape[0], ctx.latent_shape[2], ctx.latent_shape[3], ctx.latent_shape[1]),
                             dtype=torch.float32, device=dev) if need_latent else None
         shared = net.mlp_fine is None  # fine pass ran on the coarse network (models.py:242)
+        n_each = len(PARAM_NAMES)
+        # per network: does any of its parameters need a gradient (else its weight-gradient launches are skipped)
+        need_w = [any(ctx.needs_input_grad[6 + n_each * k:6 + n_each * (k + 1)]) for k in range(ctx.n_params // n_each)]
         gsum = [None, None]
         extra_depth = None  # dL/d(coarse depth) arriving through the fine pass's depth samples
         for i in reversed(range(len(ctx.passes))):  # fine first: it feeds a depth gradient to coarse
@@ -202,16 +214,19 @@ class _RenderFunction(torch.autograd.Function):
             pos = (not ps["coarse"]) and ps.get("ranks") is not None  # depth samples exist
             cb = ops.composite_backward(rays, ps["z"], ps["rgbs"], cfg["white_bkgd"], d_rgb.contiguous().float(),
                                         None if d_depth is None else d_depth.contiguous().float(),
-                                        None if d_w is None else d_w.contiguous().float(), want_dz=pos,
-                                        pre_activation=True)  # also through sigmoid / relu (models.py:260-265)
-            d_pre, dz = cb if pos else (cb, None)
+                                        None if d_w is None else d_w.contiguous().float(), want_dz=pos or need_cam,
+                                        pre_activation=True,  # also through sigmoid / relu (models.py:260-265)
+                                        want_dfar=need_rays)
+            d_far = cb[-1] if need_rays else None
+            d_pre, dz = (cb[0], cb[1]) if (pos or need_cam) else (cb, None)
             if ps.get("live") is not None:  # sigma noise: the compositing kernel saw relu(sigma) + n; relu' of the network's own sigma
                 d_pre[..., 3] *= ps["live"]
             g_out = d_pre.reshape(-1, 4)
             mlp = net.mlp_coarse if (ps["coarse"] or shared) else net.mlp_fine
-            grads, d_zlat, d_in, bd = _pass_grads(net, mlp, ps["dumps"], g_out, scene.NS, pos)
             slot = 0 if (ps["coarse"] or shared) else 1
-            gsum[slot] = grads if gsum[slot] is None else {k: gsum[slot][k] + v for k, v in grads.items()}
+            grads, d_zlat, d_in, bd = _pass_grads(net, mlp, ps["dumps"], g_out, scene.NS, pos or need_cam, want_grads=need_w[slot])
+            if grads is not None:
+                gsum[slot] = grads if gsum[slot] is None else {k: gsum[slot][k] + v for k, v in grads.items()}
             if need_latent:
                 ops.latent_scatter(scene, rays, ps["z"], d_zlat, d_lat[i if n_buf > 1 else 0])
             if pos:
@@ -219,13 +234,21 @@ class _RenderFunction(torch.autograd.Function):
                 # sorted positions, through the clamp z = max(min(depth + n*std, far), near)   (nerf.py:157-160,292)
                 extra_depth = ops.depth_sample_backward(scene, rays, ps["z"], ps["ranks"], ps["n4"], ps["depth_c"],
                                                         cfg["depth_std"], d_in, d_zlat, dz)
+            if need_cam:
+                # rays and cameras: every sample's world-space input gradient (pnr_camera_backward), fixed-order sums
+                part = ops.camera_backward(scene, rays, ps["z"], d_in, d_zlat, dz_comp=dz, d_far=d_far,
+                                           ranks=ps.get("ranks") if pos else None, n4=ps.get("n4") if pos else None,
+                                           depth_c=ps.get("depth_c") if pos else None, depth_std=cfg["depth_std"],
+                                           lindisp=cfg["lindisp"], want_rays=need_rays, want_poses=need_poses,
+                                           want_focal=need_focal, want_c=need_c)
+                cam = [p if a is None else (a if p is None else a + p) for a, p in zip(cam, part)]
             # every consumer of this pass's dumps is enqueued: the sets go back to the pool (same-stream reuse)
             bd.release()
             ps["dumps"].release()
             ps["dumps"] = None
         ctx.passes = None  # release the 16-bit operand dumps (~12 KB per point and view) as soon as they are used
-        out = [None, None, (d_lat[0] if d_lat.shape[0] == 1 else d_lat.sum(0)).permute(0, 3, 1, 2).contiguous() if need_latent else None]
-        n_each = len(PARAM_NAMES)
+        out = [None, cam[0], (d_lat[0] if d_lat.shape[0] == 1 else d_lat.sum(0)).permute(0, 3, 1, 2).contiguous() if need_latent else None]
+        out += [None if g is None else g.reshape(shp) for g, shp in zip(cam[1:], ctx.cam_shapes)]
         for slot in range(ctx.n_params // n_each):
             g = gsum[slot]
             out += [None if g is None else g[n] for n in PARAM_NAMES]
@@ -284,7 +307,7 @@ class _CompositeFunction(torch.autograd.Function):
     223-249): forward = pnr_composite, backward = pnr_composite_backward.  Gradients reach the model through `rgbsigma`
     (relu' of the raw sigma is applied inside, as nerf.py:228 applies the relu inside) and the sample positions `z`
     (through the deltas and depth = sum w z) -- the latter is what carries the fine loss back to the coarse depth
-    (nerf.py:157-160,292).  Rays are inputs, like on the fused path."""
+    (nerf.py:157-160,292) -- and, when the rays require grad, `far` through the last delta far - z_{K-1}."""
 
     @staticmethod
     def forward(ctx, rays, z, rgbsigma, white_bkgd):
@@ -301,12 +324,18 @@ class _CompositeFunction(torch.autograd.Function):
             return None, None, None, None
         if d_rgb is None:
             d_rgb = torch.zeros((rays.shape[0], 3), dtype=torch.float32, device=rays.device)
-        want_dz = ctx.needs_input_grad[1]
+        want_dz, want_far = ctx.needs_input_grad[1], ctx.needs_input_grad[0]
         res = ops.composite_backward(rays, z, rgbsigma, ctx.white_bkgd, d_rgb.contiguous().float(),
                                      None if d_depth is None else d_depth.contiguous().float(),
-                                     None if d_w is None else d_w.contiguous().float(), want_dz=want_dz, pre_activation=False)
-        d_rgbs, dz = res if want_dz else (res, None)
-        return None, dz, (d_rgbs if ctx.needs_input_grad[2] else None), None
+                                     None if d_w is None else d_w.contiguous().float(), want_dz=want_dz, pre_activation=False,
+                                     want_dfar=want_far)
+        res = res if isinstance(res, tuple) else (res,)
+        d_rgbs, dz = res[0], (res[1] if want_dz else None)
+        d_rays = None
+        if want_far:  # the last delta is far - z_{K-1} (nerf.py:181): column 7 of the rays
+            d_rays = torch.zeros_like(rays)
+            d_rays[:, 7] = res[-1]
+        return d_rays, dz, (d_rgbs if ctx.needs_input_grad[2] else None), None
 
 
 def composite_autograd(rays, z, rgbsigma, white_bkgd):
@@ -323,24 +352,62 @@ class _SampleFineFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays, weights_c, depth_c, z_coarse, u2, u3, n4, depth_std, lindisp):
         z_all, ranks = ops.sample_fine(rays, weights_c, depth_c, z_coarse, u2, u3, n4, depth_std, lindisp, want_ranks=True)
-        ctx.save_for_backward(rays, depth_c, n4, ranks)
-        ctx.depth_std = float(depth_std)
+        if ranks is None:  # no depth samples
+            ranks = torch.zeros((rays.shape[0], 0), dtype=torch.int32, device=rays.device)
+        ctx.save_for_backward(rays, depth_c, n4, ranks, z_all)
+        ctx.depth_std, ctx.lindisp = float(depth_std), bool(lindisp)
         ctx.mark_non_differentiable(ranks)
         return z_all, ranks
 
     @staticmethod
     def backward(ctx, dz_all, _):
-        rays, depth_c, n4, ranks = ctx.saved_tensors
+        rays, depth_c, n4, ranks, z_all = ctx.saved_tensors
         if dz_all is None:
             return (None,) * 9
-        zraw = depth_c.unsqueeze(1) + n4 * ctx.depth_std
-        live = (zraw < rays[:, 7:8]) & (zraw > rays[:, 6:7])  # inside the clamp: the gradient passes (nerf.py:160)
-        g = torch.gather(dz_all, 1, ranks.long()) * live.to(dz_all.dtype)
-        return None, None, g.sum(dim=1), None, None, None, None, None, None
+        dz_all = dz_all.contiguous().float()
+        d_depth = d_rays = None
+        has_depth = n4 is not None and ranks.shape[1] > 0
+        if has_depth and ctx.needs_input_grad[2]:
+            zraw = depth_c.unsqueeze(1) + n4 * ctx.depth_std
+            live = (zraw < rays[:, 7:8]) & (zraw > rays[:, 6:7])  # inside the clamp: the gradient passes (nerf.py:160)
+            g = torch.gather(dz_all, 1, ranks.long()) * live.to(dz_all.dtype)
+            d_depth = g.sum(dim=1)
+        if ctx.needs_input_grad[0]:
+            # near / far of every sample: the coarse and importance samples through z(s), the depth samples where clamped.
+            # (z_coarse gets none here: its own sample_coarse node carries the same samples of the coarse pass)
+            d_rays = ops.sample_bounds_backward(rays, z_all, dz_all, ctx.lindisp, ranks=ranks if has_depth else None,
+                                                n4=n4 if has_depth else None, depth_c=depth_c.detach() if has_depth else None,
+                                                depth_std=ctx.depth_std)
+        return d_rays, None, d_depth, None, None, None, None, None, None
+
+
+class _SampleCoarseFunction(torch.autograd.Function):
+    """ops.sample_coarse differentiable with respect to near / far (nerf.py:98-118: z = near (1-s) + far s, lindisp:
+    1/z linear in s) -- pnr_sample_bounds_backward."""
+
+    @staticmethod
+    def forward(ctx, rays, u1, lindisp):
+        z = ops.sample_coarse(rays, u1, lindisp)
+        ctx.save_for_backward(rays, z)
+        ctx.lindisp = bool(lindisp)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        rays, z = ctx.saved_tensors
+        if dz is None:
+            return None, None, None
+        return ops.sample_bounds_backward(rays, z, dz.contiguous().float(), ctx.lindisp), None, None
+
+
+def sample_coarse_autograd(rays, u1, lindisp):
+    """ops.sample_coarse, differentiable with respect to the rays' near / far."""
+    return _SampleCoarseFunction.apply(rays, u1, bool(lindisp))
 
 
 def sample_fine_autograd(rays, weights_c, depth_c, z_coarse, u2, u3, n4, depth_std, lindisp):
-    """ops.sample_fine, differentiable with respect to the coarse depth (only the n_fine_depth samples depend on it)."""
+    """ops.sample_fine, differentiable with respect to the coarse depth (only the n_fine_depth samples depend on it) and the
+    rays' near / far."""
     return _SampleFineFunction.apply(rays, weights_c, depth_c, z_coarse, u2, u3, n4, float(depth_std), bool(lindisp))[0]
 
 
@@ -412,7 +479,7 @@ def render_autograd(renderer, net, rays, noise, want_weights):
     sync = getattr(net, "_grad_sync", None)
     if sync is not None:  # multi-process training (dist.ShardedRenderWrapper): identity here, ONE gradient all-reduce in backward
         latent, params = sync(latent, params)
-    outs = _RenderFunction.apply(cfg, rays, latent, *params)
+    outs = _RenderFunction.apply(cfg, rays, latent, net.poses, net.focal, net.c, *params)
     res = {"coarse": {"rgb": outs[0], "depth": outs[1], "weights": outs[2]}}
     if Kf > 0:
         res["fine"] = {"rgb": outs[3], "depth": outs[4], "weights": outs[5]}

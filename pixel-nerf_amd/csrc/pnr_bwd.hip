@@ -912,7 +912,7 @@ __device__ __forceinline__ float wscan_add(float v, int lane) {
 template <int PASS>
 __device__ __forceinline__ float composite_bwd_pass(const float *zr, const float4 *cr, const float *dwr, int K, float far,
                                                     float3 drgb, float ddepth, float gwhite, int lane, float total,
-                                                    float4 *dout, float *dzout, bool preact) {
+                                                    float4 *dout, float *dzout, bool preact, float *dfar = nullptr) {
     float carry = 1.f, run = 0.f, acc = 0.f, ddelta_prev = 0.f;
     for (int c0 = 0; c0 < K; c0 += 64) {
         const int i = c0 + lane;
@@ -950,6 +950,7 @@ __device__ __forceinline__ float composite_bwd_pass(const float *zr, const float
                 }
                 dout[i] = go;
                 ddelta = dalpha * fmaxf(cs.w, 0.f) * ex;  // d alpha_i / d delta_i = relu(sigma) exp(-delta relu(sigma))
+                if (dfar && i == K - 1) *dfar = ddelta;    // the last delta is far - z_{K-1} (nerf.py:181)
             }
             if (dzout) {
                 // delta_i = z_{i+1} - z_i (last: far - z_i), depth = sum w z:
@@ -969,7 +970,8 @@ __device__ __forceinline__ float composite_bwd_pass(const float *zr, const float
 __global__ void __launch_bounds__(CW * 64)
 composite_bwd_kernel(const float *__restrict__ rays, const float *__restrict__ z, const float4 *__restrict__ rgbs, int R,
                      int K, int white_bkgd, const float *__restrict__ d_rgb, const float *__restrict__ d_depth,
-                     const float *__restrict__ d_w, float4 *__restrict__ d_rgbs, float *__restrict__ d_z, int preact) {
+                     const float *__restrict__ d_w, float4 *__restrict__ d_rgbs, float *__restrict__ d_z, int preact,
+                     float *__restrict__ d_far) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r = blockIdx.x * CW + wv;
     if (r >= R) return;
@@ -982,7 +984,7 @@ composite_bwd_kernel(const float *__restrict__ rays, const float *__restrict__ z
     const float *dwr = d_w ? d_w + (size_t)r * K : nullptr;
     const float total = composite_bwd_pass<0>(zr, cr, dwr, K, far, drgb, ddepth, gwhite, lane, 0.f, nullptr, nullptr, false);
     composite_bwd_pass<1>(zr, cr, dwr, K, far, drgb, ddepth, gwhite, lane, total, d_rgbs + (size_t)r * K,
-                          d_z ? d_z + (size_t)r * K : nullptr, preact != 0);
+                          d_z ? d_z + (size_t)r * K : nullptr, preact != 0, d_far ? d_far + r : nullptr);
 }
 
 // ---------------------------------------------------------------- latent scatter-add
@@ -1965,8 +1967,21 @@ extern "C" int pnr_composite_backward(const float *rays, const float *z, const f
     if (!rays || !z || !rgbsigma || !d_rgb || !d_rgbsigma) return pnr_fail(PNR_E_INVALID, "pnr_composite_backward: null argument");
     hipLaunchKernelGGL(composite_bwd_kernel, dim3((R + CW - 1) / CW), dim3(CW * 64), 0, (hipStream_t)stream, rays, z,
                        (const float4 *)rgbsigma, R, K, white_bkgd, d_rgb, d_depth, d_weights, (float4 *)d_rgbsigma, d_z,
-                       pre_activation);
+                       pre_activation, nullptr);
     return pnr_check_launch("pnr_composite_backward");
+}
+
+extern "C" int pnr_composite_backward_far(const float *rays, const float *z, const float *rgbsigma, int R, int K,
+                                          int white_bkgd, const float *d_rgb, const float *d_depth, const float *d_weights,
+                                          float *d_rgbsigma, float *d_z, float *d_far, int pre_activation, void *stream) {
+    if (R < 0 || K <= 0) return pnr_fail(PNR_E_INVALID, "pnr_composite_backward_far: bad sizes");
+    if (R == 0) return PNR_OK;
+    if (!rays || !z || !rgbsigma || !d_rgb || !d_rgbsigma)
+        return pnr_fail(PNR_E_INVALID, "pnr_composite_backward_far: null argument");
+    hipLaunchKernelGGL(composite_bwd_kernel, dim3((R + CW - 1) / CW), dim3(CW * 64), 0, (hipStream_t)stream, rays, z,
+                       (const float4 *)rgbsigma, R, K, white_bkgd, d_rgb, d_depth, d_weights, (float4 *)d_rgbsigma, d_z,
+                       pre_activation, d_far);
+    return pnr_check_launch("pnr_composite_backward_far");
 }
 
 extern "C" int pnr_position_backward(const PnrScene *s, const float *rays, const float *z, int R, int rays_per_obj, int K,

@@ -1,0 +1,365 @@
+// pnr_camera.hip -- gradients with respect to the rays and the cameras (training / pose refinement), gfx950.
+//
+//   camera_record_kernel  one wavefront per (view, sample): the world-space gradient of the sample point through the
+//                         positional code, the projection and the bilinear lookup (the same math as position_bwd_kernel),
+//                         kept whole instead of collapsed to dL/dz -- a ray record (8 floats) and a camera record (16).
+//   ray_reduce_kernel     thread per ray: the ray records summed over (sample, view) in a fixed order, dL/dz pushed through
+//                         the sampling maps to near / far (nerf.py:98-161), the last compositing delta added to far.
+//   cam_partial_kernel    per source view: the camera records of that view's object summed in fixed chunks (no atomics),
+//   cam_final_kernel      the chunks summed in order -> d poses (NV,3,4), d focal / d c (1 or SB rows).
+//   gen_rays_bwd_kernel   util.gen_rays backward: d rays (NV,H,W,8) -> d camera-to-world (NV,3,4), workgroup per pose.
+// Every sum has a fixed order: the gradients are bit-reproducible.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "pnr_common.h"
+#include "pnr_device.h"
+#include "pnr_layout.h"
+
+namespace pnr {
+namespace {
+
+constexpr int CAM_CW = 4;          // wavefronts per block of the record kernel
+constexpr int CAM_REC = 16;        // camera record: dR (9, row-major), dt (3), d(fx, fy), d(cx, cy)
+constexpr int RAY_REC = 8;         // ray record: gp (3), z gp + R^T g_vd (3), d . gp, 0
+constexpr int CAM_CHUNK = 2048;    // samples per partial sum of cam_partial_kernel
+constexpr int CAM_NT = 256;
+
+__device__ __forceinline__ float cam_wsum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+#pragma clang fp contract(fast)
+__global__ void __launch_bounds__(CAM_CW * 64)
+camera_record_kernel(const EvalParams q, const float *__restrict__ d_in42, const float *__restrict__ d_zlat,
+                     float *__restrict__ ray_rec, float *__restrict__ cam_rec) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long idx = (long long)blockIdx.x * CAM_CW + wv;  // view * P + point
+    if (idx >= q.P * q.NS) return;
+    const int view = (int)(idx / q.P);
+    const int g = (int)(idx - (long long)view * q.P);
+    const int r = g / q.K;
+    const float *ray = q.rays + (size_t)r * 8;
+    const float zz = q.z[g];
+    const float X = ray[0] + zz * ray[3], Y = ray[1] + zz * ray[4], Z = ray[2] + zz * ray[5];
+    const int obj = r / q.per_obj;
+    const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;
+    const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
+    const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
+    const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
+    const float xc0 = xr0 + pose[3], xc1 = xr1 + pose[7], xc2 = xr2 + pose[11];
+    const float *fo = q.focal + (q.n_focal > 1 ? obj * 2 : 0);
+    const float *cc = q.c + (q.n_c > 1 ? obj * 2 : 0);
+    const float u = -xc0 / xc2 * fo[0] + cc[0], v = -xc1 / xc2 * fo[1] + cc[1];
+    const float Wl = (float)q.Wl, Hl = (float)q.Hl;
+    const float sx = Wl / (Wl - 1.f) * 2.f / q.img_w, sy = Hl / (Hl - 1.f) * 2.f / q.img_h;
+    float ix = ((u * sx - 1.f + 1.f) / 2.f) * (Wl - 1.f), iy = ((v * sy - 1.f + 1.f) / 2.f) * (Hl - 1.f);
+    // grid_sample border padding: clip_coordinates_set_grad -> gradient 0 outside (0, size-1)
+    const bool gx_on = ix > 0.f && ix < Wl - 1.f, gy_on = iy > 0.f && iy < Hl - 1.f;
+    ix = fminf(Wl - 1.f, fmaxf(ix, 0.f));
+    iy = fminf(Hl - 1.f, fmaxf(iy, 0.f));
+    float six = 0.f, siy = 0.f;
+    if ((gx_on || gy_on) && ix == ix && iy == iy) {
+        const float ix0 = floorf(ix), iy0 = floorf(iy);
+        const int x0 = (int)ix0, y0 = (int)iy0;
+        const int x1 = min(x0 + 1, q.Wl - 1), y1 = min(y0 + 1, q.Hl - 1);
+        const float ax = ix - ix0, ay = iy - iy0;
+        const size_t rowbase = (size_t)(obj * q.NS + view) * (size_t)(q.Hl * q.Wl);
+        const float *nw = q.latent + (rowbase + (size_t)y0 * q.Wl + x0) * C_LAT + lane * 8;
+        const float *ne = q.latent + (rowbase + (size_t)y0 * q.Wl + x1) * C_LAT + lane * 8;
+        const float *sw = q.latent + (rowbase + (size_t)y1 * q.Wl + x0) * C_LAT + lane * 8;
+        const float *se = q.latent + (rowbase + (size_t)y1 * q.Wl + x1) * C_LAT + lane * 8;
+        const float *dz = d_zlat + (size_t)idx * C_LAT + lane * 8;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(nw + 4 * hh), b = *reinterpret_cast<const f32x4 *>(ne + 4 * hh);
+            const f32x4 c = *reinterpret_cast<const f32x4 *>(sw + 4 * hh), d = *reinterpret_cast<const f32x4 *>(se + 4 * hh);
+            const f32x4 gq = *reinterpret_cast<const f32x4 *>(dz + 4 * hh);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                six += gq[e] * ((1.f - ay) * (b[e] - a[e]) + ay * (d[e] - c[e]));
+                siy += gq[e] * ((1.f - ax) * (c[e] - a[e]) + ax * (d[e] - b[e]));
+            }
+        }
+    }
+    // positional code of xr (code.py:37-41): lane l < 18 differentiates band l / 3 of coordinate l % 3, lanes 18..20 the
+    // identity part
+    const float *gi = d_in42 + (size_t)idx * D_IN;
+    float gc0 = 0.f, gc1 = 0.f, gc2 = 0.f;
+    if (lane < 21) {
+        const float HALF_PI = 1.57079637050628662109375f;
+        const int k = lane / 3, c = lane - 3 * k;
+        const float xc = c == 0 ? xr0 : (c == 1 ? xr1 : xr2);
+        float term;
+        if (k < 6) {
+            const float f = 1.5f * (float)(1 << k), a = xc * f;
+            term = f * (cosf(a) * gi[3 + 6 * k + c] + cosf(__builtin_fmaf(xc, f, HALF_PI)) * gi[3 + 6 * k + 3 + c]);
+        } else {
+            term = gi[c];
+        }
+        gc0 = c == 0 ? term : 0.f; gc1 = c == 1 ? term : 0.f; gc2 = c == 2 ? term : 0.f;
+    }
+    gc0 = cam_wsum(gc0); gc1 = cam_wsum(gc1); gc2 = cam_wsum(gc2);
+    six = cam_wsum(six);
+    siy = cam_wsum(siy);
+    if (lane != 0) return;
+    const float du = gx_on ? six * (Wl - 1.f) * 0.5f * sx : 0.f;
+    const float dv = gy_on ? siy * (Hl - 1.f) * 0.5f * sy : 0.f;
+    // u = -xc0/xc2 fx + cx ; v = -xc1/xc2 fy + cy   (fy already negated in `focal`): g_cam = d/d xc
+    const float gm0 = -fo[0] / xc2 * du;
+    const float gm1 = -fo[1] / xc2 * dv;
+    const float gm2 = (xc0 * fo[0] * du + xc1 * fo[1] * dv) / (xc2 * xc2);
+    const float g0 = gm0 + gc0, g1 = gm1 + gc1, g2 = gm2 + gc2;  // d/d xr (xc = xr + t)
+    // view direction R d (models.py:188-196) enters the network as columns 39..41
+    const float v0 = gi[39], v1 = gi[40], v2 = gi[41];
+    const float d0 = ray[3], d1 = ray[4], d2 = ray[5];
+    // world gradient gp = R^T g ; direction: z gp + R^T g_vd
+    const float wx = pose[0] * g0 + pose[4] * g1 + pose[8] * g2;
+    const float wy = pose[1] * g0 + pose[5] * g1 + pose[9] * g2;
+    const float wz = pose[2] * g0 + pose[6] * g1 + pose[10] * g2;
+    const float vx = pose[0] * v0 + pose[4] * v1 + pose[8] * v2;
+    const float vy = pose[1] * v0 + pose[5] * v1 + pose[9] * v2;
+    const float vz = pose[2] * v0 + pose[6] * v1 + pose[10] * v2;
+    float4 *rr = reinterpret_cast<float4 *>(ray_rec + (size_t)idx * RAY_REC);
+    float4 *cr = reinterpret_cast<float4 *>(cam_rec + (size_t)idx * CAM_REC);
+    // a point on a source camera's plane (xc2 == 0) or a non-finite upstream gradient: the record is dropped, as
+    // position_bwd_kernel drops its dL/dz, instead of poisoning every sum it enters
+    if (!__builtin_isfinite(g0 + g1 + g2 + gm0 + gm1 + gm2 + v0 + v1 + v2 + du * xc0 / xc2 + dv * xc1 / xc2)) {
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        rr[0] = z4; rr[1] = z4; cr[0] = z4; cr[1] = z4; cr[2] = z4; cr[3] = z4;
+        return;
+    }
+    rr[0] = make_float4(wx, wy, wz, zz * wx + vx);
+    rr[1] = make_float4(zz * wy + vy, zz * wz + vz, d0 * wx + d1 * wy + d2 * wz, 0.f);
+    // dR = (g_code + g_cam) (x) p + g_vd (x) d, dt = g_cam
+    cr[0] = make_float4(g0 * X + v0 * d0, g0 * Y + v0 * d1, g0 * Z + v0 * d2, g1 * X + v1 * d0);
+    cr[1] = make_float4(g1 * Y + v1 * d1, g1 * Z + v1 * d2, g2 * X + v2 * d0, g2 * Y + v2 * d1);
+    cr[2] = make_float4(g2 * Z + v2 * d2, gm0, gm1, gm2);
+    cr[3] = make_float4(du * (-xc0 / xc2), dv * (-xc1 / xc2), du, dv);
+}
+
+// dz/d(near), dz/d(far) of a sample on the stratified / importance map z(s) = near (1 - s) + far s (lindisp: 1/z linear in s),
+// with s recovered from z (nerf.py:98-148)
+__device__ __forceinline__ void sample_bounds_grad(float z, float near, float far, bool lindisp, float &dn, float &df) {
+    if (!lindisp) {
+        const float s = (z - near) / (far - near);
+        dn = 1.f - s; df = s;
+    } else {
+        const float in = 1.f / near, ifa = 1.f / far;
+        const float s = (1.f / z - in) / (ifa - in);
+        const float z2 = z * z;
+        dn = z2 * (1.f - s) * in * in; df = z2 * s * ifa * ifa;
+    }
+}
+
+struct RayReduce {
+    const float *rays, *z;
+    const float *ray_rec;   // (NS, R*K, 8), or null with NS = 0 (sampling maps only)
+    const float *dz_comp;   // (R, K) nullable
+    const float *d_far;     // (R) nullable: dL/d(last delta)
+    const int *ranks;       // (R, Kfd) nullable: sorted positions of the depth samples
+    const float *n4, *depth_c;
+    float depth_std;
+    int Kfd, R, K, NS, lindisp;
+    const float *dz_extra;  // (R, K) nullable: dL/dz of the sample positions (sampling-only form)
+    float *d_rays;          // (R, 8) out
+};
+
+__global__ void __launch_bounds__(256) ray_reduce_kernel(const RayReduce a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.R) return;
+    const float near = a.rays[(size_t)r * 8 + 6], far = a.rays[(size_t)r * 8 + 7];
+    const long long P = (long long)a.R * a.K;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f, dnear = 0.f, dfar = a.d_far ? a.d_far[r] : 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const long long g = (long long)r * a.K + k;
+        float dz = (a.dz_comp ? a.dz_comp[g] : 0.f) + (a.dz_extra ? a.dz_extra[g] : 0.f);
+        for (int v = 0; v < a.NS; ++v) {
+            const float4 *rr = reinterpret_cast<const float4 *>(a.ray_rec + ((size_t)v * P + g) * RAY_REC);
+            const float4 p = rr[0], s = rr[1];
+            o0 += p.x; o1 += p.y; o2 += p.z;
+            e0 += p.w; e1 += s.x; e2 += s.y;
+            dz += s.z;
+        }
+        int jd = -1;
+        for (int j = 0; j < a.Kfd && a.ranks; ++j)
+            if (a.ranks[(size_t)r * a.Kfd + j] == k) jd = j;
+        if (jd >= 0) {
+            // depth sample z = max(min(depth + n std, far), near) (nerf.py:157-160): near / far only where the clamp is active;
+            // the unclamped ones go to the coarse depth (pnr_depth_sample_backward)
+            const float zraw = a.depth_c[r] + a.n4[(size_t)r * a.Kfd + jd] * a.depth_std;
+            if (zraw >= far) dfar += dz;
+            else if (zraw <= near) dnear += dz;
+        } else {
+            float dn, df;
+            sample_bounds_grad(a.z[g], near, far, a.lindisp != 0, dn, df);
+            dnear += dz * dn;
+            dfar += dz * df;
+        }
+    }
+    float4 *out = reinterpret_cast<float4 *>(a.d_rays + (size_t)r * 8);
+    out[0] = make_float4(o0, o1, o2, e0);
+    out[1] = make_float4(e1, e2, dnear, dfar);
+}
+
+// grid (chunks, SB*NS): block sums chunk `blockIdx.x` of the samples of source view row nv = obj * NS + view
+__global__ void __launch_bounds__(CAM_NT) cam_partial_kernel(const float *__restrict__ cam_rec, long long P, int NS,
+                                                             long long per_obj_pts, int nchunk, float *__restrict__ part) {
+    __shared__ float red[CAM_NT];
+    const int nv = blockIdx.y, obj = nv / NS, view = nv - obj * NS;
+    const int comp = threadIdx.x & (CAM_REC - 1), lane = threadIdx.x / CAM_REC;  // 16 sample lanes x 16 components
+    const long long lo = (long long)blockIdx.x * CAM_CHUNK;
+    const long long hi = min(lo + CAM_CHUNK, per_obj_pts);
+    const float *base = cam_rec + ((size_t)view * P + (size_t)obj * per_obj_pts) * CAM_REC;
+    float acc = 0.f;
+    for (long long i = lo + lane; i < hi; i += CAM_NT / CAM_REC) acc += base[(size_t)i * CAM_REC + comp];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (lane == 0) {
+        float s = 0.f;
+        for (int l = 0; l < CAM_NT / CAM_REC; ++l) s += red[l * CAM_REC + comp];
+        part[((size_t)nv * nchunk + blockIdx.x) * CAM_REC + comp] = s;
+    }
+}
+
+// one block: thread t < NV*12 -> d pose[nv][t%12]; then the intrinsics rows (1 = shared: summed over every object)
+__global__ void __launch_bounds__(CAM_NT) cam_final_kernel(const float *__restrict__ part, int SB, int NS, int nchunk,
+                                                           int n_focal, int n_c, float *__restrict__ d_poses,
+                                                           float *__restrict__ d_focal, float *__restrict__ d_c) {
+    const int NV = SB * NS;
+    for (int t = threadIdx.x; t < NV * 12 + 2 * n_focal + 2 * n_c; t += blockDim.x) {
+        if (t < NV * 12) {
+            const int nv = t / 12, e = t - nv * 12, i = e / 4, j = e - i * 4;
+            const int comp = j < 3 ? i * 3 + j : 9 + i;  // (3,4) layout: R columns 0..2, t column 3
+            if (!d_poses) continue;
+            float s = 0.f;
+            for (int ch = 0; ch < nchunk; ++ch) s += part[((size_t)nv * nchunk + ch) * CAM_REC + comp];
+            d_poses[t] = s;
+            continue;
+        }
+        int u = t - NV * 12;
+        const bool is_f = u < 2 * n_focal;
+        if (!is_f) u -= 2 * n_focal;
+        float *dst = is_f ? d_focal : d_c;
+        if (!dst) continue;
+        const int rows = is_f ? n_focal : n_c;
+        const int row = u / 2, comp = (is_f ? 12 : 14) + (u - row * 2);
+        const int o_lo = rows > 1 ? row : 0, o_hi = rows > 1 ? row + 1 : SB;
+        float s = 0.f;
+        for (int o = o_lo; o < o_hi; ++o)
+            for (int v = 0; v < NS; ++v)
+                for (int ch = 0; ch < nchunk; ++ch) s += part[((size_t)(o * NS + v) * nchunk + ch) * CAM_REC + comp];
+        dst[u] = s;
+    }
+}
+
+// util.gen_rays (util.py:238-276, ndc=False): rays = (t, R dir(px), near, far); workgroup per pose, fixed-order tree sum
+#pragma clang fp contract(off)  // the forward's direction, bit for bit (gen_rays_kernel)
+__global__ void __launch_bounds__(CAM_NT) gen_rays_bwd_kernel(const float *__restrict__ d_rays, int W, int H, float fx,
+                                                              float fy, float cx, float cy, float *__restrict__ d_poses) {
+    __shared__ float red[12][CAM_NT];
+    const int n = blockIdx.x;
+    float acc[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) acc[e] = 0.f;
+    const long long npx = (long long)W * H;
+    for (long long i = threadIdx.x; i < npx; i += CAM_NT) {
+        const int px = (int)(i % W), py = (int)(i / W);
+        const float X = ((float)px - cx) / fx, Y = ((float)py - cy) / fy;
+        float d0 = X, d1 = -Y, d2 = -1.f;
+        const float nrm = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+        d0 /= nrm; d1 /= nrm; d2 /= nrm;
+        const float *g = d_rays + ((size_t)n * npx + i) * 8;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            acc[a * 4 + 0] += g[3 + a] * d0;
+            acc[a * 4 + 1] += g[3 + a] * d1;
+            acc[a * 4 + 2] += g[3 + a] * d2;
+            acc[a * 4 + 3] += g[a];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 12; ++e) red[e][threadIdx.x] = acc[e];
+    __syncthreads();
+    for (int s = CAM_NT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+#pragma unroll
+            for (int e = 0; e < 12; ++e) red[e][threadIdx.x] += red[e][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 12) d_poses[(size_t)n * 12 + threadIdx.x] = red[threadIdx.x][0];
+}
+#pragma clang fp contract(fast)
+
+}  // namespace
+}  // namespace pnr
+
+using namespace pnr;
+
+extern "C" size_t pnr_camera_backward_workspace_bytes(int R, int K, int rays_per_obj, int NS) {
+    if (R <= 0 || K <= 0 || rays_per_obj <= 0 || NS <= 0) return 0;
+    const long long P = (long long)R * K, per_obj_pts = (long long)rays_per_obj * K;
+    const long long nchunk = (per_obj_pts + CAM_CHUNK - 1) / CAM_CHUNK;
+    const long long SB = R / rays_per_obj;
+    return (size_t)(P * NS * (RAY_REC + CAM_REC) + SB * NS * nchunk * CAM_REC) * sizeof(float);
+}
+
+extern "C" int pnr_camera_backward(const PnrScene *s, const float *rays, const float *z, int R, int rays_per_obj, int K,
+                                   int lindisp, const float *d_in42, const float *d_zlat, const float *dz_comp,
+                                   const float *d_far, const int *ranks, const float *n4, int Kfd, const float *depth_c,
+                                   float depth_std, float *d_rays, float *d_poses, float *d_focal, float *d_c,
+                                   void *workspace, void *stream) {
+    if (!s || !rays || !z || !d_in42 || !d_zlat || !workspace || R <= 0 || K <= 0 || rays_per_obj <= 0)
+        return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: bad argument");
+    if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: R != SB * rays_per_obj");
+    if (ranks && (!n4 || !depth_c || Kfd <= 0 || Kfd > K)) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: depth samples");
+    EvalParams q = {};
+    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
+    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
+    q.img_w = s->img_w; q.img_h = s->img_h;
+    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
+    const long long n = q.P * q.NS;
+    float *ray_rec = (float *)workspace;
+    float *cam_rec = ray_rec + n * RAY_REC;
+    const long long per_obj_pts = (long long)rays_per_obj * K;
+    const int nchunk = (int)((per_obj_pts + CAM_CHUNK - 1) / CAM_CHUNK);
+    float *part = cam_rec + n * CAM_REC;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(camera_record_kernel, dim3((unsigned)((n + CAM_CW - 1) / CAM_CW)), dim3(CAM_CW * 64), 0, st, q, d_in42,
+                       d_zlat, ray_rec, cam_rec);
+    if (d_rays) {
+        RayReduce a = {rays, z, ray_rec, dz_comp, d_far, ranks, n4, depth_c, depth_std, ranks ? Kfd : 0, R, K, s->NS,
+                       lindisp, nullptr, d_rays};
+        hipLaunchKernelGGL(ray_reduce_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, a);
+    }
+    if (d_poses || d_focal || d_c) {
+        hipLaunchKernelGGL(cam_partial_kernel, dim3((unsigned)nchunk, (unsigned)(s->SB * s->NS)), dim3(CAM_NT), 0, st, cam_rec,
+                           q.P, s->NS, per_obj_pts, nchunk, part);
+        hipLaunchKernelGGL(cam_final_kernel, dim3(1), dim3(CAM_NT), 0, st, part, s->SB, s->NS, nchunk, s->n_focal, s->n_c,
+                           d_poses, d_focal, d_c);
+    }
+    return pnr_check_launch("pnr_camera_backward");
+}
+
+extern "C" int pnr_gen_rays_backward(const float *d_rays, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                     float *d_poses, void *stream) {
+    if (!d_rays || !d_poses || NV <= 0 || W <= 0 || H <= 0) return pnr_fail(PNR_E_INVALID, "pnr_gen_rays_backward: bad argument");
+    hipLaunchKernelGGL(gen_rays_bwd_kernel, dim3((unsigned)NV), dim3(CAM_NT), 0, (hipStream_t)stream, d_rays, W, H, fx, fy, cx,
+                       cy, d_poses);
+    return pnr_check_launch("pnr_gen_rays_backward");
+}
+
+extern "C" int pnr_sample_bounds_backward(const float *rays, const float *z, const float *dz, int R, int K, int lindisp,
+                                          const int *ranks, const float *n4, int Kfd, const float *depth_c, float depth_std,
+                                          const float *d_far, float *d_rays, void *stream) {
+    if (!rays || !z || !dz || !d_rays || R < 0 || K <= 0) return pnr_fail(PNR_E_INVALID, "pnr_sample_bounds_backward: bad argument");
+    if (ranks && (!n4 || !depth_c || Kfd <= 0 || Kfd > K))
+        return pnr_fail(PNR_E_INVALID, "pnr_sample_bounds_backward: depth samples");
+    if (R == 0) return PNR_OK;
+    RayReduce a = {rays, z, nullptr, nullptr, d_far, ranks, n4, depth_c, depth_std, ranks ? Kfd : 0, R, K, 0, lindisp, dz, d_rays};
+    hipLaunchKernelGGL(ray_reduce_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return pnr_check_launch("pnr_sample_bounds_backward");
+}

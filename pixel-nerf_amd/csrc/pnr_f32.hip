@@ -698,6 +698,7 @@ static void lin_out_grad_f32(hipStream_t st, const float *g, const float *x5, lo
 
 static void wgrad(const Mm &c, const float *dY, int lddy, const float *X, int ldx, bool relu_x, long long M, int N, int Kd,
                   float *dW, float *db, float *part, bool in_unscaled = false) {
+    if (!dW) return;  // no weight gradient wanted (pnr_mlp_backward_f32 with grads == NULL)
     float *bpart = part + (size_t)WG_SPLIT * N * Kd;
     if (c.fast) {
         Gemm3 g = {};
@@ -890,7 +891,7 @@ extern "C" int pnr_mlp_backward_split(const PnrMlpWeights *w, const PnrSplitSave
                                       const PnrMlpWeights *grads, float *d_zlat, float *d_in, const float *grad_scale, void *workspace,
                                       size_t workspace_bytes, void *stream) {
     using namespace pnr;
-    if (!w || !g_out || !grads || !d_zlat || !workspace || !grad_scale || P <= 0 || NS <= 0)
+    if (!w || !g_out || !d_zlat || !workspace || !grad_scale || P <= 0 || NS <= 0)
         return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: bad argument");
     if (w->combine_max && NS > 1) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: combine_type \"max\" is an inference form (no backward)");
     if (!check_split_saved(sv)) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: null buffer in PnrSplitSaved");
@@ -913,6 +914,7 @@ extern "C" int pnr_mlp_backward_split(const PnrMlpWeights *w, const PnrSplitSave
     if (rc != PNR_OK) return rc;
     rc = mlp_backward_split_chain(packed, (const unsigned long long *)sv->masks, g_out, grad_scale, P, NS, g_fc1, g_fc0, g_x0, d_zlat, d_in, hs);
     if (rc != PNR_OK) return rc;
+    if (!grads) return pnr_check_launch("pnr_mlp_backward_split");  // data gradients only: no weight-gradient launches
     // all 14 wide weight gradients in one launch pair, straight from the (head | tail) images; the chain ran at scale s: 1/s on the way out
     PnrWeightGradJob jobs[14];
     int nj = 0;
@@ -943,8 +945,10 @@ extern "C" int pnr_mlp_backward_f32(const PnrMlpWeights *w, const PnrF32Saved *s
                                     const PnrMlpWeights *grads, float *d_zlat, float *d_in, int split_gemm, const float *grad_scale,
                                     void *workspace, size_t workspace_bytes, void *stream) {
     using namespace pnr;
-    if (!w || !g_out || !grads || !d_zlat || !workspace || P <= 0 || NS <= 0)
+    if (!w || !g_out || !d_zlat || !workspace || P <= 0 || NS <= 0)
         return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_f32: bad argument");
+    static const PnrMlpWeights no_grads = {};  // grads == NULL: every dW / db null, wgrad skips its launches
+    if (!grads) grads = &no_grads;
     if (w->combine_max && NS > 1) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_f32: combine_type \"max\" is an inference form (no backward)");
     if (split_gemm && !grad_scale)
         return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_f32: the split-operand form needs grad_scale = device [s, 1/s] (pnr_grad_scale)");

@@ -543,6 +543,55 @@ def gen_rays(poses, width, height, focal, z_near, z_far, c=None):
     return rays
 
 
+def sample_bounds_backward(rays, z, dz, lindisp=False, ranks=None, n4=None, depth_c=None, depth_std=0.01, d_far=None):
+    """dL/d rays (R,8) of sample positions z (R,K) drawn by sample_coarse / sample_fine (pnr_sample_bounds_backward): dz
+    through z = near (1-s) + far s (lindisp: 1/z linear in s) to near / far; the depth samples at `ranks` (ops.sample_fine
+    want_ranks) only where their clamp is active; d_far (R,) is added to far.  Columns 0..5 are zero (the caller builds the
+    points from the rays with differentiable ops)."""
+    _expect(rays, "rays", (None, 8))
+    R = rays.shape[0]
+    _expect(z, "z", (R, None))
+    K = z.shape[1]
+    _expect(dz, "dz", (R, K))
+    Kfd = 0
+    if ranks is not None:
+        _expect(ranks, "ranks", (R, None), torch.int32)
+        Kfd = ranks.shape[1]
+        if Kfd == 0:
+            ranks = None
+    lib = _lib.load()
+    rays, z, dz = _f32(rays, "rays", (R, 8)), _f32(z, "z", (R, K)), _f32(dz, "dz", (R, K))
+    if ranks is not None:
+        ranks = ranks.contiguous()
+        n4 = _f32(n4, "n4", (R, Kfd))
+        depth_c = _f32(depth_c, "depth_c", (R,))
+    d_far = None if d_far is None else _f32(d_far, "d_far", (R,))
+    d_rays = torch.empty((R, 8), dtype=torch.float32, device=rays.device)
+    with torch.cuda.device(rays.device):
+        _lib.check(lib.pnr_sample_bounds_backward(_p(rays), _p(z), _p(dz), R, K, int(bool(lindisp)), _p(ranks), _p(n4), Kfd,
+                                                  _p(depth_c), float(depth_std), _p(d_far), _p(d_rays), _stream()),
+                   "pnr_sample_bounds_backward")
+    return d_rays
+
+
+def gen_rays_backward(d_rays, width, height, focal, c=None):
+    """Backward of gen_rays with respect to the camera-to-world poses (the intrinsics are constants):
+    d_rays (NV,H,W,8) -> d poses (NV,4,4) (bottom row zero)."""
+    _expect(d_rays, "d_rays", (None, int(height), int(width), 8))
+    lib = _lib.load()
+    d_rays = _f32(d_rays, "d_rays", (None, int(height), int(width), 8))
+    NV = d_rays.shape[0]
+    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+    cx, cy = (width * 0.5, height * 0.5) if c is None else (float(c[0]), float(c[1]))
+    out = torch.zeros((NV, 4, 4), dtype=torch.float32, device=d_rays.device)
+    d34 = torch.empty((NV, 3, 4), dtype=torch.float32, device=d_rays.device)
+    with torch.cuda.device(d_rays.device):
+        _lib.check(lib.pnr_gen_rays_backward(_p(d_rays), NV, int(width), int(height), fx, fy, cx, cy, _p(d34), _stream()),
+                   "pnr_gen_rays_backward")
+    out[:, :3] = d34
+    return out
+
+
 def render_views(scene, packed_coarse, packed_fine, poses_c2w, width, height, focal, z_near, z_far, n_coarse, n_fine,
                  n_fine_depth, noise, c=None, depth_std=0.01, white_bkgd=False, lindisp=False, want_weights=False, tables=None,
                  seed=0):
@@ -1099,37 +1148,43 @@ def eval_ray_samples_split_train(scene, packed, tables, rays, z):
     return out, saved
 
 
-def mlp_backward_split(weights, saved, g_out, want_d_in=False):
+def mlp_backward_split(weights, saved, g_out, want_d_in=False, want_grads=True):
     """Backward of eval_ray_samples_split_train (pnr_mlp_backward_split): weights = PackedMLP of precision 'f32' (the raw
     nn.Linear tensors; the transposed streams are packed inside the call).  -> (grads, d_zlat, d_in | None) like mlp_backward_f32."""
     lib = _lib.load()
     P, NS = saved.P, saved.NS
     g_out = _f32(g_out, "g_out", (P, 4))
     dev = g_out.device
-    grads = {k: torch.empty(_MLP_SHAPES.get(k, (512, 512) if k.endswith("weight") else (512,)), dtype=torch.float32, device=dev)
-             for k in _MLP_KEYS}
-    gstruct, _keep = _weights_struct(grads)
+    grads, gref, _keep = None, None, None
+    if want_grads:  # (want_grads=False: grads == NULL, the data-gradient chain alone, grads returned as None)
+        grads = {k: torch.empty(_MLP_SHAPES.get(k, (512, 512) if k.endswith("weight") else (512,)), dtype=torch.float32, device=dev)
+                 for k in _MLP_KEYS}
+        gstruct, _keep = _weights_struct(grads)
+        gref = ctypes.byref(gstruct)
     d_zlat = torch.empty((NS * P, 512), dtype=torch.float32, device=dev)
     d_in = torch.empty((NS * P, 42), dtype=torch.float32, device=dev) if want_d_in else None
     sc = grad_scale(g_out)  # device [s, 1/s]: no host synchronisation
     nbytes = lib.pnr_mlp_backward_split_workspace_bytes(P, NS)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mlp_backward_split(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, ctypes.byref(gstruct),
+        _lib.check(lib.pnr_mlp_backward_split(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, gref,
                                               _p(d_zlat), _p(d_in), _p(sc), _p(ws), nbytes, _stream()), "pnr_mlp_backward_split")
     return grads, d_zlat, d_in
 
 
-def mlp_backward_f32(weights, saved, g_out, want_d_in=False):
+def mlp_backward_f32(weights, saved, g_out, want_d_in=False, want_grads=True):
     """-> ({reference state_dict key: fp32 gradient}, d_zlat (rows_v,512), d_in (rows_v,42) | None) of one ResnetFC: exact fp32
     MFMA products, or the split-operand (fp32-class) form when the forward ran with split=True."""
     lib = _lib.load()
     P, NS = saved.P, saved.NS
     g_out = _f32(g_out, "g_out", (P, 4))
     dev = g_out.device
-    grads = {k: torch.empty(_MLP_SHAPES.get(k, (512, 512) if k.endswith("weight") else (512,)), dtype=torch.float32, device=dev)
-             for k in _MLP_KEYS}
-    gstruct, _keep = _weights_struct(grads)
+    grads, gref, _keep = None, None, None
+    if want_grads:  # (want_grads=False: grads == NULL, the data-gradient chain alone, grads returned as None)
+        grads = {k: torch.empty(_MLP_SHAPES.get(k, (512, 512) if k.endswith("weight") else (512,)), dtype=torch.float32, device=dev)
+                 for k in _MLP_KEYS}
+        gstruct, _keep = _weights_struct(grads)
+        gref = ctypes.byref(gstruct)
     d_zlat = torch.empty((NS * P, 512), dtype=torch.float32, device=dev)
     d_in = torch.empty((NS * P, 42), dtype=torch.float32, device=dev) if want_d_in else None
     split = bool(getattr(saved, "split", False))
@@ -1137,15 +1192,15 @@ def mlp_backward_f32(weights, saved, g_out, want_d_in=False):
     nbytes = lib.pnr_mlp_backward_f32_workspace_bytes(P, NS)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mlp_backward_f32(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, ctypes.byref(gstruct),
+        _lib.check(lib.pnr_mlp_backward_f32(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, gref,
                                             _p(d_zlat), _p(d_in), int(split), _p(sc), _p(ws), nbytes, _stream()), "pnr_mlp_backward_f32")
     return grads, d_zlat, d_in
 
 
 def composite_backward(rays, z, rgbsigma, white_bkgd, d_rgb, d_depth=None, d_weights=None, want_dz=False,
-                       pre_activation=False):
+                       pre_activation=False, want_dfar=False):
     """-> dL/d(rgb sigma) per point (R,K,4) [after the output activations, or in front of them with
-    pre_activation=True] and optionally dL/dz (R,K)."""
+    pre_activation=True], optionally dL/dz (R,K) and (want_dfar) dL/d(far) (R,) through the last delta far - z_{K-1}."""
     lib = _lib.load()
     rays = _f32(rays, "rays", (None, 8))
     R = rays.shape[0]
@@ -1157,11 +1212,74 @@ def composite_backward(rays, z, rgbsigma, white_bkgd, d_rgb, d_depth=None, d_wei
     d_weights = None if d_weights is None else _f32(d_weights, "d_weights", (R, K))
     out = torch.empty((R, K, 4), dtype=torch.float32, device=rays.device)
     dz = torch.empty((R, K), dtype=torch.float32, device=rays.device) if want_dz else None
+    if want_dfar:
+        dfar = torch.empty((R,), dtype=torch.float32, device=rays.device)
+        with torch.cuda.device(rays.device):
+            _lib.check(lib.pnr_composite_backward_far(_p(rays), _p(z), _p(rgbsigma), R, K, int(bool(white_bkgd)), _p(d_rgb),
+                                                      _p(d_depth), _p(d_weights), _p(out), _p(dz), _p(dfar),
+                                                      int(bool(pre_activation)), _stream()), "pnr_composite_backward_far")
+        return (out, dz, dfar) if want_dz else (out, dfar)
     with torch.cuda.device(rays.device):
         _lib.check(lib.pnr_composite_backward(_p(rays), _p(z), _p(rgbsigma), R, K, int(bool(white_bkgd)), _p(d_rgb),
                                               _p(d_depth), _p(d_weights), _p(out), _p(dz), int(bool(pre_activation)),
                                               _stream()), "pnr_composite_backward")
     return (out, dz) if want_dz else out
+
+
+def _expect(t, name, shape, dtype=torch.float32):
+    """argument check of the camera-gradient entries, before any device work: ValueError on a wrong dtype or shape"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{name}: expected a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+
+
+def camera_backward(scene, rays, z, d_in42, d_zlat, dz_comp=None, d_far=None, ranks=None, n4=None, depth_c=None,
+                    depth_std=0.01, lindisp=False, want_rays=True, want_poses=True, want_focal=True, want_c=True):
+    """Gradients of one network pass with respect to the rays and the scene's cameras (pnr_camera_backward):
+    -> (d_rays (R,8), d_poses (SB*NS,3,4), d_focal (n_focal,2), d_c (n_c,2)), None for what is not wanted.
+    d_in42 / d_zlat: the pass's dL/d(lin_in operand) (NS*R*K,42) and dL/d(interpolated latent) (NS*R*K,512); dz_comp (R,K)
+    and d_far (R,) from composite_backward; ranks / n4 / depth_c: the fine pass's depth samples (their unclamped part
+    goes to the coarse depth through depth_sample_backward, not here)."""
+    _expect(rays, "rays", (None, 8))
+    R = rays.shape[0]
+    _expect(z, "z", (R, None))
+    K = z.shape[1]
+    rows = scene.NS * R * K
+    _expect(d_in42, "d_in42", (rows, 42))
+    _expect(d_zlat, "d_zlat", (rows, 512))
+    if ranks is not None:
+        _expect(ranks, "ranks", (R, None), torch.int32)
+    lib = _lib.load()
+    rays = _f32(rays, "rays", (None, 8))
+    z = _f32(z, "z", (R, None))
+    if R % scene.SB != 0:
+        raise ValueError("camera_backward: the rays must be SB equal groups (one per object)")
+    d_in42 = _f32(d_in42, "d_in42", (rows, 42))
+    d_zlat = _f32(d_zlat, "d_zlat", (rows, 512))
+    dz_comp = None if dz_comp is None else _f32(dz_comp, "dz_comp", (R, K))
+    d_far = None if d_far is None else _f32(d_far, "d_far", (R,))
+    Kfd = 0
+    if ranks is not None:
+        if ranks.dtype != torch.int32 or not ranks.is_contiguous() or ranks.dim() != 2 or ranks.shape[0] != R:
+            raise ValueError("ranks must be a contiguous (R, Kfd) int32 tensor (ops.sample_fine(..., want_ranks=True))")
+        Kfd = ranks.shape[1]
+        n4 = _f32(n4, "n4", (R, Kfd))
+        depth_c = _f32(depth_c, "depth_c", (R,))
+    dev = rays.device
+    per_obj = R // scene.SB
+    NV = scene.SB * scene.NS
+    d_rays = torch.empty((R, 8), dtype=torch.float32, device=dev) if want_rays else None
+    d_poses = torch.empty((NV, 3, 4), dtype=torch.float32, device=dev) if want_poses else None
+    d_focal = torch.empty((scene.focal.shape[0], 2), dtype=torch.float32, device=dev) if want_focal else None
+    d_c = torch.empty((scene.c.shape[0], 2), dtype=torch.float32, device=dev) if want_c else None
+    ws = torch.empty((lib.pnr_camera_backward_workspace_bytes(R, K, per_obj, scene.NS),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_camera_backward(scene.ref, _p(rays), _p(z), R, per_obj, K, int(bool(lindisp)), _p(d_in42), _p(d_zlat),
+                                           _p(dz_comp), _p(d_far), _p(ranks), _p(n4), Kfd, _p(depth_c), float(depth_std),
+                                           _p(d_rays), _p(d_poses), _p(d_focal), _p(d_c), _p(ws), _stream()),
+                   "pnr_camera_backward")
+    return d_rays, d_poses, d_focal, d_c
 
 
 def position_backward(scene, rays, z, d_in42, d_zlat, d_z):

@@ -74,6 +74,9 @@ class NeRFRenderer(torch.nn.Module):
     def sample_coarse(self, rays, _u=None):
         """nerf.py:98-118.  rays (B,8) -> (B,Kc)."""
         u = torch.rand(rays.shape[0], self.n_coarse, device=rays.device) if _u is None else _u
+        if torch.is_grad_enabled() and rays.requires_grad:  # near / far carry gradient (nerf.py:113-115)
+            from ..autograd import sample_coarse_autograd
+            return sample_coarse_autograd(rays, u, self.lindisp)
         return ops.sample_coarse(rays, u, self.lindisp)
 
     def sample_fine(self, rays, weights, _u2=None, _u3=None):
@@ -129,7 +132,7 @@ class NeRFRenderer(torch.nn.Module):
         if self.training and self.noise_std > 0.0:
             out = torch.cat([out[..., :3], out[..., 3:4] + torch.randn_like(out[..., 3:4]) * self.noise_std], -1)
         rgbs = out[..., :4].contiguous()
-        if torch.is_grad_enabled() and (rgbs.requires_grad or z_samp.requires_grad):
+        if torch.is_grad_enabled() and (rgbs.requires_grad or z_samp.requires_grad or rays.requires_grad):
             # training with an arbitrary model: the compositing kernels as an autograd node (pnr_composite /
             # pnr_composite_backward); gradients reach the model through its outputs and, for the depth samples of the fine
             # pass, through the sample positions (points above are torch ops on z_samp)
@@ -182,7 +185,9 @@ class NeRFRenderer(torch.nn.Module):
             needs_grad = torch.is_grad_enabled() and (
                 model.mlp_coarse.any_requires_grad()
                 or (model.mlp_fine is not None and model.mlp_fine.any_requires_grad())
-                or (model.encoder.latent.requires_grad and not model.stop_encoder_grad))
+                or (model.encoder.latent.requires_grad and not model.stop_encoder_grad)
+                or rays.requires_grad  # rays and cameras: pose estimation / refinement (autograd._RenderFunction)
+                or any(torch.is_tensor(t) and t.requires_grad for t in (model.poses, model.focal, model.c)))
             if self.training and self.noise_std > 0.0 and not needs_grad:
                 raise NotImplementedError("noise_std > 0 in train mode is implemented on the differentiable path (grad enabled); "
                                           "the reference adds the noise only while training (nerf.py:225-226)")
@@ -230,7 +235,7 @@ class NeRFRenderer(torch.nn.Module):
         outputs = DotMap(coarse=self._format(dict(rgb=rgbc, depth=depthc, weights=wc), SB, want_weights))
         if Kf > 0:
             n4 = noise.get("n4") if Kfd > 0 else None
-            if n4 is not None and torch.is_grad_enabled() and depthc.requires_grad:
+            if torch.is_grad_enabled() and ((n4 is not None and depthc.requires_grad) or rays.requires_grad):
                 # nerf.py:292: the coarse depth is not detached -- the depth samples carry the fine loss back to it
                 from ..autograd import sample_fine_autograd
                 z_all = sample_fine_autograd(rays, wc.detach(), depthc, z_coarse, noise.get("u2"), noise.get("u3"), n4,

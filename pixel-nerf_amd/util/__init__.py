@@ -83,6 +83,27 @@ def unproj_map(width, height, f, c=None, device="cpu"):
     return (d / torch.norm(d, dim=-1, keepdim=True)).to(device)
 
 
+class _GenRaysFunction(torch.autograd.Function):
+    """gen_rays on a HIP tensor, differentiable with respect to the camera-to-world poses (pnr_gen_rays /
+    pnr_gen_rays_backward); the intrinsics are constants."""
+
+    @staticmethod
+    def forward(ctx, poses, args):
+        from .. import ops
+        width, height, focal, z_near, z_far, c = args
+        ctx.args, ctx.rows = (width, height, focal, c), poses.shape[-2]
+        if ctx.rows == 3:  # (B,3,4) camera-to-world, as the reference accepts: the kernel reads 4x4 rows
+            poses = torch.cat((poses, poses.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(poses.shape[0], 1, 4)), dim=1)
+        return ops.gen_rays(poses.contiguous(), width, height, focal, z_near, z_far, c=c)
+
+    @staticmethod
+    def backward(ctx, d_rays):
+        from .. import ops
+        width, height, focal, c = ctx.args
+        g = ops.gen_rays_backward(d_rays.contiguous().float(), width, height, focal, c=c)
+        return g[:, :ctx.rows].contiguous(), None  # the poses' own shape
+
+
 def gen_rays(poses, width, height, focal, z_near, z_far, c=None, ndc=False):
     """src/util/util.py:238-276.  poses (B,4,4) camera-to-world -> rays (B,H,W,8).
     HIP tensors go through the gen_rays kernel (pnr_gen_rays); host tensors are input
@@ -96,6 +117,8 @@ def gen_rays(poses, width, height, focal, z_near, z_far, c=None, ndc=False):
         c = c.flatten().tolist()
     if poses.is_cuda:
         from .. import ops
+        if torch.is_grad_enabled() and poses.requires_grad:
+            return _GenRaysFunction.apply(poses, (width, height, focal, z_near, z_far, c))
         return ops.gen_rays(poses, width, height, focal, z_near, z_far, c=c)
     B = poses.shape[0]
     dirs = unproj_map(width, height, focal, c=c)[None].expand(B, -1, -1, -1)
