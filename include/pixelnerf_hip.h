@@ -28,6 +28,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the library is built with hidden default visibility: what this header declares is all it exports */
+#pragma GCC visibility push(default)
 
 #define PNR_OK 0
 #define PNR_E_INVALID (-1)   /* bad argument / unsupported shape          */
@@ -53,6 +55,9 @@ typedef struct PnrScene {
     int32_t Hl, Wl;           /* latent grid size                                           */
     int32_t n_focal, n_c;     /* 1 (broadcast) or SB (per object)            models.py:207-212 */
     float img_w, img_h;       /* net.image_shape = (W, H)                    models.py:116-117 */
+    void *mv_workspace;       /* NS > 1: pnr_mv_workspace_bytes() bytes of device scratch, caller-owned: the view sum of
+                                 every forward entry that takes this scene (eval, render, _split, _train); NS == 1: unused.
+                                 Launches that share one scene must be ordered on one stream. */
 } PnrScene;
 
 /* One ResnetFC (src/model/resnetfc.py:66-130) at the only shape the reference ships:
@@ -75,9 +80,13 @@ int pnr_version(int *major, int *minor);
 /* ABI revision of THIS header: bumped whenever a struct layout or an entry point's argument list changes.  The
  * library returns the value it was compiled with; a binding must compare it with the header it was written against
  * before the first call (pixelnerf_amd/_lib.py does, and refuses a stale or foreign .so). */
-#define PNR_ABI_VERSION 9
+#define PNR_ABI_VERSION 10
 int pnr_abi_version(void);
 int pnr_device_info(int *num_cus, int *lds_bytes_per_block);
+/* Bytes of the multi-view scratch (PnrScene.mv_workspace, PnrBackwardDumps.mv_workspace) on the CURRENT device: one tile of
+ * fp32 view-sum accumulators per workgroup, CUs x 96 x 512 x 4 (48 MiB on 256 CUs).  A multi-view call with a NULL
+ * workspace fails with PNR_E_INVALID. */
+size_t pnr_mv_workspace_bytes(void);
 
 /* 64-bit content fingerprint of the 30 parameter tensors, computed and (optionally) compared on the device with no host
  * synchronisation: ws = pnr_params_checksum_ws_bytes() of device scratch, first 8 bytes zero (left so); sum_out (device,
@@ -268,6 +277,7 @@ typedef struct PnrBackwardDumps {
                        (resnetfc.py:175-180 backward), unscaled; REQUIRED (pnr_mlp_backward rejects NULL)     */
     float *d_in;    /* (rows_v, 42) fp32: d(positional code | view direction) = dY W_in (resnetfc.py:147
                        backward), unscaled; NULL = not wanted                                            */
+    void *mv_workspace; /* NS > 1: pnr_mv_workspace_bytes() bytes of device scratch (required); NS == 1: unused */
 } PnrBackwardDumps;
 
 int pnr_eval_ray_samples_train(const PnrScene *scene /*host*/, const void *packed, int precision,
@@ -607,7 +617,8 @@ int pnr_eval_ray_samples_split_train(const PnrScene *scene /*host*/, const void 
                                      const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
                                      const PnrSplitSaved *saved /*host*/, void *stream);
 /* grad_scale = device [s, 1/s] from pnr_grad_scale(g_out); outputs as pnr_mlp_backward_f32 (d_zlat required, d_in and grads
- * nullable: grads == NULL runs the data-gradient chain only, without the weight-gradient launches). */
+ * nullable: grads == NULL runs the data-gradient chain only, without the weight-gradient launches).  With NS > 1 the workspace
+ * also holds the multi-view scratch. */
 size_t pnr_mlp_backward_split_workspace_bytes(long long P, int NS);
 int pnr_mlp_backward_split(const PnrMlpWeights *w /*host*/, const PnrSplitSaved *saved /*host*/, const float *g_out, long long P,
                            int NS, const PnrMlpWeights *grads /*host*/, float *d_zlat, float *d_in /*nullable*/,
@@ -636,6 +647,7 @@ int pnr_point_features_f32(const PnrScene *scene /*host*/, const float *xyz, con
 int pnr_profile_enable(int on);
 int pnr_profile_read(double *mlp_kernel_ms, int *mlp_launches);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelne
 SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip"]
 HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_raysrc.h", "pnr_internal.h", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
-ABI_VERSION = 9  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
+ABI_VERSION = 10  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3
 PRECISIONS = {"f16": PREC_F16, "fp16": PREC_F16, "bf16": PREC_BF16, "f32": PREC_F32, "fp32": PREC_F32, "f16x3": PREC_F16X3}
 
@@ -31,7 +31,7 @@ class PnrScene(ctypes.Structure):
         ("c", ctypes.c_void_p),
         ("SB", ctypes.c_int32), ("NS", ctypes.c_int32), ("Hl", ctypes.c_int32), ("Wl", ctypes.c_int32),
         ("n_focal", ctypes.c_int32), ("n_c", ctypes.c_int32),
-        ("img_w", ctypes.c_float), ("img_h", ctypes.c_float),
+        ("img_w", ctypes.c_float), ("img_h", ctypes.c_float), ("mv_workspace", ctypes.c_void_p),
     ]
 
 
@@ -59,7 +59,7 @@ class PnrTrainDumps(ctypes.Structure):
 
 class PnrBackwardDumps(ctypes.Structure):
     _fields_ = [("g_fc1", ctypes.c_void_p * 5), ("g_fc0", ctypes.c_void_p * 5), ("g_x0", ctypes.c_void_p),
-                ("d_zlat", ctypes.c_void_p), ("d_in", ctypes.c_void_p)]
+                ("d_zlat", ctypes.c_void_p), ("d_in", ctypes.c_void_p), ("mv_workspace", ctypes.c_void_p)]
 
 
 class PnrF32Saved(ctypes.Structure):
@@ -79,6 +79,7 @@ PROTOTYPES = {
     "pnr_version": (_I, [ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "pnr_abi_version": (_I, []),
     "pnr_device_info": (_I, [ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "pnr_mv_workspace_bytes": (_SZ, []),
     "pnr_params_checksum_ws_bytes": (_SZ, []),
     "pnr_params_checksum": (_I, [ctypes.POINTER(PnrMlpWeights), _P, _P, _P, _P, _P]),
     "pnr_packed_mlp_bytes": (_SZ, []),
@@ -173,10 +174,6 @@ PROTOTYPES = {
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }
-# test hook exported by the library but not part of the public header
-_EXTRA = {"pnr_debug_set_x_dump": (_I, [_P]),
-          "pnr_debug_phase_timing": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _I, _I, _P, _P]),
-          "pnr_debug_phase_timing_split": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P])}
 
 _lib = None
 
@@ -204,7 +201,9 @@ def build_library(force=False, verbose=False, jobs=None):
         return LIB_PATH
     from concurrent.futures import ThreadPoolExecutor
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
+    # hidden by default: the library exports what include/pixelnerf_hip.h declares (its `visibility push(default)`) and nothing else
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
+             "-Wno-unused-value"]
     objdir = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "build", "obj_prod")
     os.makedirs(objdir, exist_ok=True)
     newest_header = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS if os.path.exists(os.path.join(CSRC, h)))
@@ -283,7 +282,7 @@ def load():
     if abi != ABI_VERSION:
         raise PixelNerfHipError(f"{LIB_PATH} implements ABI revision {abi}, this binding was written against {ABI_VERSION} "
                                 "(include/pixelnerf_hip.h PNR_ABI_VERSION): rebuild it (__graft_entry__.build())")
-    for name, (res, args) in list(PROTOTYPES.items()) + list(_EXTRA.items()):
+    for name, (res, args) in PROTOTYPES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

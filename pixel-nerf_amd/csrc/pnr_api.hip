@@ -1,6 +1,7 @@
 // pnr_api.hip -- error plumbing and library facts for libpixelnerf_hip.so.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,14 +46,26 @@ extern "C" int pnr_abi_version(void) {
 
 extern "C" int pnr_device_info(int *num_cus, int *lds_bytes_per_block) {
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return pnr_check_hip(e, "hipGetDevice");
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, dev);
-    if (e != hipSuccess) return pnr_check_hip(e, "hipGetDeviceProperties");
-    if (num_cus) *num_cus = prop.multiProcessorCount;
+    if (num_cus) *num_cus = pnr::device_cus();
     if (lds_bytes_per_block) *lds_bytes_per_block = pnr::LDS_TOTAL;
     return PNR_OK;
+}
+
+// the multi-view kernels park one tile of fp32 view sums per workgroup; 96 points is the largest tile (the f16 training forward)
+extern "C" size_t pnr_mv_workspace_bytes(void) { return (size_t)pnr::device_cus() * 96 * pnr::D_HID * sizeof(float); }
+
+// a fact of the current device, queried once per device ordinal (0 = not asked yet: threads that race store the same value)
+static int per_device(std::atomic<int> *cache, int (*query)(int dev), int fallback) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fallback;
+    int n = cache[dev].load(std::memory_order_relaxed);
+    if (!n) {
+        n = query(dev);
+        cache[dev].store(n, std::memory_order_relaxed);
+    }
+    return n;
 }
 
 int pnr::device_xcd_count() {
@@ -61,15 +74,19 @@ int pnr::device_xcd_count() {
         const int n = std::atoi(ov);
         return n > 0 ? n : 0;
     }
-    static int cached[64];  // per device ordinal; 0 = not asked yet
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (!cached[dev]) {
+    static std::atomic<int> cache[64];
+    return per_device(cache, [](int dev) {
         int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess || n <= 0) n = 1;
-        cached[dev] = n;
-    }
-    return cached[dev];
+        return hipDeviceGetAttribute(&n, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && n > 0 ? n : 1;
+    }, 0);
+}
+
+int pnr::device_cus() {
+    static std::atomic<int> cache[64];
+    return per_device(cache, [](int dev) {
+        int n = 0;
+        return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    }, 256);
 }
 
 // ---- fp16-range guard of the fp32-class ("f16x3") kernels

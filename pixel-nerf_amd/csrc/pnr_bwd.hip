@@ -10,7 +10,7 @@
 //                         (operands of the weight-gradient GEMMs dW = dY^T X).
 //   dw_kernel             dW = dY^T X for all linears of a network in one launch (MFMA from the dumps
 //                         through transposing LDS reads), dw_reduce_kernel sums the row slices.
-//   dw_split_kernel       the same at split-operand (fp32-class) precision: (head | tail) f16 operand rows, three
+//   dw_split_wide_kernel  the same at split-operand (fp32-class) precision: (head | tail) f16 operand rows, three
 //                         MFMAs per product -- the weight gradients of the fused fp32-class training path.
 //   composite_bwd_kernel  backward of the alpha compositing (nerf.py:223-249), wavefront per ray.
 //                         also emits dL/dz through the deltas and depth = sum w z.
@@ -21,10 +21,7 @@
 //                         samples (nerf.py:292), for all points or for the depth samples only.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 
 #include "pnr_common.h"
@@ -504,152 +501,16 @@ dw_kernel(const DwJobs jobs, float *__restrict__ part, float *__restrict__ bpart
 // The same weight-gradient GEMM at split-operand (fp32-class) precision: both operands arrive as (head, tail) f16 row sets -- the
 // activation images of the fused split forward and the gradient images of the fused split chain, copied out of LDS as they lie
 // there; the tail array of an operand follows its head array -- and every fragment pair costs three MFMAs (head x head,
-// head x tail, tail x head; fp32 accumulate), the arithmetic of PNR_PREC_F16X3.  Same tiling, placement, slice reduction and
-// storage -> feature order mapping as dw_kernel; four operand slabs (dY / X, head / tail), double-buffered: 147 KiB of LDS, one
-// workgroup of 8 waves per CU -- the kernel is MFMA-bound (3 MFMAs per 2 fragment reads), which 2 waves per SIMD cover.
-__global__ void __launch_bounds__(512)
-dw_split_kernel(const DwJobs jobs, float *__restrict__ part, float *__restrict__ bpart) {
-    typedef Prec<PNR_PREC_F16> P;
-    typedef _Float16 T;
-    constexpr int SR = 32, LDB = 576;
-    extern __shared__ __attribute__((aligned(16))) char dws[];  // [buf][dY head, dY tail, X head, X tail][SR * LDB]
-    constexpr int SLAB = SR * LDB;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int lid = blockIdx.x, ngroups = gridDim.x >> 2, full = (ngroups >> 3) * 32;
-    int grp, tile4;
-    if (lid < full) { const int k = lid >> 3; grp = (k >> 2) * 8 + (lid & 7); tile4 = k & 3; }
-    else { const int rem = lid - full; grp = (full >> 2) + (rem >> 2); tile4 = rem & 3; }
-    const int job = grp / jobs.nsplit, slice = grp - job * jobs.nsplit;
-    const long long rows = jobs.rows[job];
-    const int nx = jobs.nx[job];
-    const T *dYh = reinterpret_cast<const T *>(jobs.dY[job]), *dYl = dYh + (size_t)rows * D_HID;
-    const T *Xh = reinterpret_cast<const T *>(jobs.X[job]), *Xl = Xh + (size_t)rows * nx;
-    long long per = (rows + jobs.nsplit - 1) / jobs.nsplit;
-    per = (per + SR - 1) / SR * SR;
-    const int o0 = (tile4 >> 1) * 256, k0 = (tile4 & 1) * 256;
-    if (k0 >= nx) return;  // narrow X (lin_in): only the first column tile exists
-    const long long r_begin = (long long)slice * per;
-    const long long r_end = r_begin + per < rows ? r_begin + per : rows;
-    const int wo = (w >> 1) * 64, wk = (w & 1) * 128;  // wave tile: 64 (o) x 128 (k) = 2 x 4 MFMA tiles
-    const int i = lane & 31, kh = lane >> 5;
-    f32x16 acc[2][4];
-    float bsum[2] = {0.f, 0.f};
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    u32x4 vyh[2], vyl[2], vxh[2], vxl[2];
-    auto load_slab = [&](long long r0) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int chunk = t + u * 512;  // consecutive lanes -> consecutive 16-byte chunks of a row
-            const int srow = chunk >> 5, scol = (chunk & 31) * 8;
-            vyh[u] = vyl[u] = vxh[u] = vxl[u] = u32x4{0, 0, 0, 0};
-            if (r0 + srow < r_end) {
-                const size_t oy = (size_t)(r0 + srow) * D_HID + o0 + scol;
-                vyh[u] = *reinterpret_cast<const u32x4 *>(dYh + oy);
-                vyl[u] = *reinterpret_cast<const u32x4 *>(dYl + oy);
-                if (k0 + scol < nx) {
-                    const size_t ox = (size_t)(r0 + srow) * nx + k0 + scol;
-                    vxh[u] = *reinterpret_cast<const u32x4 *>(Xh + ox);
-                    vxl[u] = *reinterpret_cast<const u32x4 *>(Xl + ox);
-                }
-            }
-        }
-    };
-    const int c16 = lane & 15;
-    const int frag_off = (8 * kh + (c16 >> 2)) * LDB + (16 * ((lane >> 4) & 1) + 4 * (c16 & 3)) * 2;
-    auto store_slab = [&](int buf) {
-        char *base = dws + buf * (4 * SLAB);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int chunk = t + u * 512;
-            const int off = (chunk >> 5) * LDB + (chunk & 31) * 16;
-            *reinterpret_cast<u32x4 *>(base + off) = vyh[u];
-            *reinterpret_cast<u32x4 *>(base + SLAB + off) = vyl[u];
-            *reinterpret_cast<u32x4 *>(base + 2 * SLAB + off) = vxh[u];
-            *reinterpret_cast<u32x4 *>(base + 3 * SLAB + off) = vxl[u];
-        }
-    };
-    if (r_begin < r_end) {
-        load_slab(r_begin);
-        store_slab(0);
-    }
-    __syncthreads();
-    int cur = 0;
-    for (long long r0 = r_begin; r0 < r_end; r0 += SR, cur ^= 1) {
-        const bool more = r0 + SR < r_end;
-        if (more) load_slab(r0 + SR);  // in flight under this slab's MFMAs
-        const char *sYh = dws + cur * (4 * SLAB), *sYl = sYh + SLAB, *sXh = sYh + 2 * SLAB, *sXl = sYh + 3 * SLAB;
-#pragma unroll
-        for (int ks = 0; ks < SR / 16; ++ks) {
-            P::T8 ah[2], al[2], bh[4], bl[4];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                ah[a] = tr_frag<P::T8, LDB>(sYh + ks * 16 * LDB + (wo + a * 32) * 2 + frag_off);
-                al[a] = tr_frag<P::T8, LDB>(sYl + ks * 16 * LDB + (wo + a * 32) * 2 + frag_off);
-            }
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                bh[b] = tr_frag<P::T8, LDB>(sXh + ks * 16 * LDB + (wk + b * 32) * 2 + frag_off);
-                bl[b] = tr_frag<P::T8, LDB>(sXl + ks * 16 * LDB + (wk + b * 32) * 2 + frag_off);
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = P::mfma(ah[a], bh[b], acc[a][b]);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = P::mfma(ah[a], bl[b], acc[a][b]);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = P::mfma(al[a], bh[b], acc[a][b]);
-            if ((tile4 & 1) == 0 && (w & 1) == 0) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) bsum[a] += (float)ah[a][e] + (float)al[a][e];
-            }
-            // the next slab's rows (requested at the top of this slab, one k-step = 48 MFMAs per SIMD ago) go into the OTHER
-            // buffer -- its readers passed the barrier of the previous slab -- between the two k-steps: the 8 LDS stores per
-            // thread ride under the second k-step's MFMAs instead of standing between the last MFMA and the barrier
-            // (same-box A/B against storing after the last MFMA: 907.4 / 908.0 vs 918.8 / 914.4 us per launch, -1 %;
-            // profiles/r05_train_step_notes.md)
-            if (ks == 0 && more) store_slab(cur ^ 1);
-        }
-        __syncthreads();
-    }
-    float *pz = part + ((size_t)job * jobs.nsplit + slice) * (D_HID * D_HID);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int orow = o0 + wo + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                pz[(size_t)orow * D_HID + k0 + wk + b * 32 + i] = acc[a][b][r];
-            }
-    if ((tile4 & 1) == 0 && (w & 1) == 0) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            float v = bsum[a] + __shfl_xor(bsum[a], 32, 64);
-            if (kh == 0) bpart[((size_t)job * jobs.nsplit + slice) * D_HID + o0 + wo + a * 32 + i] = v;
-        }
-    }
-}
-
-// dw_split_kernel as ONE wave per SIMD (round 6; the launcher's default): 4 waves of 128 (o) x 128 (k) = 4 x 4 MFMA tiles,
-// 256 accumulator registers per lane (the AGPR half of the 512-register file a 256-thread workgroup owns), 16 fragments per k-step
-// for 48 MFMAs (the 8-wave form: 12 for 24 -- a third less LDS traffic per MFMA), and room for TWO fragment sets: the fragments of
-// k-step j + 1 are read while the MFMAs of k-step j issue, the slab barrier sits BETWEEN the two k-steps of a slab (every LDS read
-// of a slab is issued before it, so the other buffer may be overwritten right behind it), and no k-step starts with an LDS burst of
-// all waves behind a barrier.  What the 8-wave form does there (ISA): 24 transposing reads at the top of every k-step, waited for,
-// then 24 MFMAs; after the barrier of every second k-step all 8 waves read at once -- 96 KiB through the 128 B/clk LDS pipe = 768
-// clocks against 1536 clocks of MFMAs per k-step and SIMD.
+// head x tail, tail x head; fp32 accumulate), the arithmetic of PNR_PREC_F16X3.  Same placement, slice reduction and storage ->
+// feature order mapping as dw_kernel; four operand slabs (dY / X, head / tail), double-buffered: 147 KiB of LDS.
+// ONE wave per SIMD (round 6): 4 waves of 128 (o) x 128 (k) = 4 x 4 MFMA tiles, 256 accumulator registers per lane (the AGPR half
+// of the 512-register file a 256-thread workgroup owns), 16 fragments per k-step for 48 MFMAs (the round-3..5 8-wave form: 12 for
+// 24 -- a third less LDS traffic per MFMA), and room for TWO fragment sets: the fragments of k-step j + 1 are read while the MFMAs
+// of k-step j issue, the slab barrier sits BETWEEN the two k-steps of a slab (every LDS read of a slab is issued before it, so the
+// other buffer may be overwritten right behind it), and no k-step starts with an LDS burst of all waves behind a barrier.  What
+// the 8-wave form did there (ISA): 24 transposing reads at the top of every k-step, waited for, then 24 MFMAs; after the barrier
+// of every second k-step all 8 waves read at once -- 96 KiB through the 128 B/clk LDS pipe = 768 clocks against 1536 clocks of
+// MFMAs per k-step and SIMD.  -12 % per launch, same partial sums bit for bit (profiles/r06_dw_split_notes.md).
 __global__ void __launch_bounds__(256)
 dw_split_wide_kernel(const DwJobs jobs, float *__restrict__ part, float *__restrict__ bpart) {
     typedef Prec<PNR_PREC_F16> P;
@@ -1645,17 +1506,6 @@ extern "C" int pnr_pack_mlp_bwd(const PnrMlpWeights *w, int precision, void *pac
     return pnr_check_launch("pnr_pack_mlp_bwd");
 }
 
-static int bwd_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 // scales[0] = 2^(6 - ceil(log2 max|g|)) (1 if g == 0), scales[1] = 1 / scales[0]; NaN if g holds a non-finite value
 __global__ void __launch_bounds__(1024) grad_scale_kernel(const float *__restrict__ g, long long n, float *__restrict__ scales) {
     __shared__ float red[1024];
@@ -1797,11 +1647,9 @@ extern "C" int pnr_mlp_backward(const void *packed_bwd, int precision, const Pnr
         if (!q.g_fc1[b] || !q.g_fc0[b]) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward: null dump");
     }
     const bool mv = NS > 1;
-    const int grid = q.ntiles < bwd_num_cus() ? q.ntiles : bwd_num_cus();
-    if (mv) {
-        q.mv_ws = mv_scratch((hipStream_t)stream, (size_t)bwd_num_cus() * 96 * D_HID * sizeof(float));
-        if (!q.mv_ws) return pnr_fail(PNR_E_HIP, "pnr_mlp_backward: cannot allocate the multi-view scratch (48 MiB)");
-    }
+    q.mv_ws = (float *)out->mv_workspace;
+    if (mv && !q.mv_ws) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward: NS > 1 needs PnrBackwardDumps.mv_workspace (pnr_mv_workspace_bytes())");
+    const int grid = q.ntiles < device_cus() ? q.ntiles : device_cus();
     void (*k)(const BwdParams);
     if (precision == PNR_PREC_F16) k = mv ? bwd_kernel<PNR_PREC_F16, true> : bwd_kernel<PNR_PREC_F16, false>;
     else if (precision == PNR_PREC_BF16) k = mv ? bwd_kernel<PNR_PREC_BF16, true> : bwd_kernel<PNR_PREC_BF16, false>;
@@ -1879,7 +1727,7 @@ static int dw_nsplit(int n_jobs, long long max_rows) {
     // 4 tiles x jobs x slices workgroups of 8 waves, one per CU at a time: pick the slice count whose workgroup total fills
     // whole rounds of the chip (14 jobs: 9 slices = 504 workgroups = 1.97 rounds; the former "at least 512" rule gave 10
     // slices = 560 = 2.19 rounds, i.e. a third round at 19 % occupancy); slices of at least 256 rows
-    const int cus = bwd_num_cus();
+    const int cus = device_cus();
     const int per = 4 * n_jobs;
     int best = 1;
     double best_eff = 0.0;
@@ -1889,10 +1737,6 @@ static int dw_nsplit(int n_jobs, long long max_rows) {
         const double eff = (double)blocks / (double)(rounds * cus);
         if (blocks >= cus && eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
         else if (blocks < cus) best = ns;  // fewer workgroups than CUs: more slices is always better
-    }
-    if (const char *e = getenv("PNR_DW_NSPLIT")) {  // experiment hook: force the slice count
-        const int v = atoi(e);
-        if (v >= 1 && v <= DW_MAX_SPLIT) best = v;
     }
     const long long cap = (max_rows + 255) / 256;
     if (best > cap) best = (int)cap;
@@ -1934,17 +1778,9 @@ extern "C" int pnr_weight_grad_batched(const PnrWeightGradJob *jobs, int n_jobs,
     else if (precision == PNR_PREC_F16X3) {
         // split-operand form: dY / X are (head | tail) f16 row sets, the tail array behind the head array
         constexpr int lds = 2 * 4 * 32 * 576;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dw_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(dw_split_kernel)");
-        // one wave per SIMD with 128 x 128 wave tiles (dw_split_wide_kernel) since round 6: -12 % per launch, same partial sums bit
-        // for bit (the bias sums differ in summation order); PNR_DW_FORM=8wave selects the round-3..5 kernel (profiles/r06_dw_split_notes.md)
-        static const bool wide = [] { const char *e = getenv("PNR_DW_FORM"); return !(e && !strcmp(e, "8wave")); }();
-        if (wide) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(dw_split_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(dw_split_wide_kernel)");
-            hipLaunchKernelGGL(dw_split_wide_kernel, grid, dim3(256), lds, st, J, part, bpart);
-        } else
-            hipLaunchKernelGGL(dw_split_kernel, grid, dim3(512), lds, st, J, part, bpart);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dw_split_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(dw_split_wide_kernel)");
+        hipLaunchKernelGGL(dw_split_wide_kernel, grid, dim3(256), lds, st, J, part, bpart);
     } else
         return pnr_fail(PNR_E_INVALID, "pnr_weight_grad_batched: unknown precision");
     hipLaunchKernelGGL(dw_reduce_kernel, dim3(D_HID * D_HID / 256, (unsigned)n_jobs), dim3(256), 0, st, J, part, bpart, out_scale, out_scale_dev);
@@ -1990,9 +1826,7 @@ extern "C" int pnr_position_backward(const PnrScene *s, const float *rays, const
         return pnr_fail(PNR_E_INVALID, "pnr_position_backward: bad argument");
     if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_position_backward: R != SB * rays_per_obj");
     EvalParams q = {};
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
     const long long n = q.P * q.NS;
     hipLaunchKernelGGL(position_bwd_kernel, dim3((unsigned)((n + CW - 1) / CW)), dim3(CW * 64), 0, (hipStream_t)stream, q,
@@ -2009,9 +1843,7 @@ extern "C" int pnr_depth_sample_backward(const PnrScene *s, const float *rays, c
         return pnr_fail(PNR_E_INVALID, "pnr_depth_sample_backward: bad argument");
     if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_depth_sample_backward: R != SB * rays_per_obj");
     EvalParams q = {};
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
     DepthSamples ds = {ranks, n4, depth_c, dz_comp, contrib, depth_std, Kfd};
     const long long n = (long long)R * Kfd * q.NS;
@@ -2032,7 +1864,7 @@ static bool slab_row(int texels, int cs, int &row) {
 }
 static void scatter_form(int texels, int images, int &cs, int &row) {
     cs = 0; row = 0;
-    const int cus = bwd_num_cus();
+    const int cus = device_cus();
     for (int c = 16; c >= 4; c >>= 1) {
         int r = 0;
         if (!slab_row(texels, c, r)) continue;
@@ -2058,10 +1890,7 @@ static size_t scatter_tiled_extra_bytes(int images, int ntiles, int NS, long lon
 }
 // Grids whose slab only fits 4 channels wide (2275 .. 5116 texels: the 64 x 64 grids of SRN-sized images) read the gradient rows in
 // 16-byte pieces; cut into tiles they read 64-byte pieces like the small grids (4 x 64 x 64: 165 -> see profiles/r06_scatter_notes.md).
-// PNR_SCATTER_TILED_MIN_TEXELS moves the crossover (experiment hook).
 static bool scatter_prefers_tiles(int cs, int texels) {
-    static const long long min_texels = [] { const char *e = getenv("PNR_SCATTER_TILED_MIN_TEXELS"); return e ? atoll(e) : -1LL; }();
-    if (min_texels >= 0) return texels >= min_texels;
     int r = 0;
     return cs == 4 && !slab_row(texels, 8, r);  // (one or two small images also get cs == 4 -- for the pair count; they stay slabs)
 }
@@ -2092,7 +1921,6 @@ extern "C" int pnr_latent_scatter_single_owner(const PnrScene *s, int R, int ray
     int cs, row;
     scatter_form(s->Hl * s->Wl, s->SB * s->NS, cs, row);
     const bool tiles_ok = scatter_tiled_ok((long long)rays_per_obj * K, tile_geom(s->Hl, s->Wl).ntiles);
-    if (getenv("PNR_SCATTER_FORM")) return 0;  // (experiment hook active: unknown form)
     return ((cs == 0 || scatter_prefers_tiles(cs, s->Hl * s->Wl)) && tiles_ok) ? 1 : 0;
 }
 
@@ -2102,35 +1930,23 @@ extern "C" int pnr_latent_scatter(const PnrScene *s, const float *rays, const fl
         return pnr_fail(PNR_E_INVALID, "pnr_latent_scatter: bad argument");
     if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_latent_scatter: R != SB * rays_per_obj");
     EvalParams q = {};
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
     const int texels = q.Hl * q.Wl;
     int cs, row;
     scatter_form(texels, q.SB * q.NS, cs, row);
     if (scatter_prefers_tiles(cs, texels) && scatter_tiled_ok((long long)rays_per_obj * K, tile_geom(q.Hl, q.Wl).ntiles)) cs = 0;
-    int force_psplit = 0;
-    if (const char *e = getenv("PNR_SCATTER_FORM")) {  // experiment hook "cs,psplit": force the slice width (16 / 8 / 4) and the point split
-        int fcs = 0, fps = 0;
-        int frow = 0;
-        if (cs && sscanf(e, "%d,%d", &fcs, &fps) >= 1 && (fcs == 16 || fcs == 8 || fcs == 4) && slab_row(texels, fcs, frow)) {
-            cs = fcs; row = frow;
-            force_psplit = fps;
-        }
-    }
     if (cs) {
         const size_t lds = (size_t)texels * row * 8;
         const long long pts = (long long)rays_per_obj * K;
         // one workgroup per (image, slice) takes all of the image's segments; they are split only when there are fewer
         // (image, slice) pairs than compute units (and never below ~one segment per thread: a segment is >= 1 sample)
         const int owners = q.SB * q.NS * (C_LAT / cs);
-        int psplit = (bwd_num_cus() + owners - 1) / owners;
+        int psplit = (device_cus() + owners - 1) / owners;
         const long long rounds = (pts + 4LL * OWNER_NT - 1) / (4LL * OWNER_NT);
         if (psplit > rounds) psplit = (int)rounds;
         if (psplit > 2) psplit = 2;  // (scatter_form: at most two adds per grid element)
         if (psplit < 1) psplit = 1;
-        if (force_psplit >= 1 && force_psplit <= 8) psplit = force_psplit;
         const int images = q.SB * q.NS;
         const size_t coords_bytes = (size_t)q.NS * q.P * sizeof(float2);
         const int sub_len = scatter_sub_len(pts);

@@ -317,9 +317,7 @@ extern "C" int pnr_camera_backward(const PnrScene *s, const float *rays, const f
     if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: R != SB * rays_per_obj");
     if (ranks && (!n4 || !depth_c || Kfd <= 0 || Kfd > K)) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: depth samples");
     EvalParams q = {};
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
     const long long n = q.P * q.NS;
     float *ray_rec = (float *)workspace;

@@ -62,7 +62,6 @@ struct EvalParams {
     int n_xcd;         // XCDs workgroups are dealt to round-robin (device_xcd_count(); 0 / 1: plain grid-stride tile order)
     float *out;        // (P,4)
     float *mv_ws;      // multi-view: per-workgroup scratch for the parked view sum (MT x 512 fp32 each)
-    float *dbg;        // optional debug dump of the final residual stream x (P,512), may be null
     unsigned long long *tim;  // phase-timing accumulators (TIMING instantiation only)
     // TRAIN instantiation: 16-bit row-major dumps of every linear layer's input operand
     // (rows = view*P + point for the per-view layers, point for the pooled ones)
@@ -81,6 +80,14 @@ struct EvalParams {
     // GUARD instantiation of the split-operand kernel: one word that collects "layer l saw a value beyond the fp16 range" bits
     unsigned int *sat_flag;
 };
+
+// the scene's fields of a launch, the multi-view scratch (PnrScene.mv_workspace) included
+inline void scene_params(EvalParams &q, const PnrScene &s) {
+    q.latent = s.latent_nhwc; q.poses = s.poses; q.focal = s.focal; q.c = s.c;
+    q.SB = s.SB; q.NS = s.NS; q.Hl = s.Hl; q.Wl = s.Wl; q.n_focal = s.n_focal; q.n_c = s.n_c;
+    q.img_w = s.img_w; q.img_h = s.img_h;
+    q.mv_ws = (float *)s.mv_workspace;
+}
 
 // Tile order of the fused evaluation kernels (eval_kernel, eval_split_kernel).  Workgroup b runs on XCD b % n_xcd (the
 // dispatcher deals workgroups to the XCDs round-robin -- relied on for speed only, never for a result): every XCD takes ONE

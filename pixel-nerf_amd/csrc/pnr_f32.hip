@@ -725,9 +725,7 @@ static int eval_f32(const PnrScene *s, const PnrMlpWeights *w, EvalParams q, boo
     if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: bad scene shape");
     if (q.P == 0) return PNR_OK;
     if (q.P > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: too many points");
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     const int NS = s->NS;
     long long chunk = (long long)(ws_bytes / sizeof(float) / floats_per_point(NS));
     if (chunk < 64) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: workspace too small");
@@ -788,9 +786,7 @@ static int eval_f32_train(const PnrScene *s, const PnrMlpWeights *w, EvalParams 
     if (!check_saved(sv, s->NS)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: null activation buffer in PnrF32Saved");
     if (q.P == 0) return PNR_OK;
     if (q.P * s->NS > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: too many points");
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     const int NS = s->NS;
     const int np = (int)q.P;
     const long long rows = (long long)np * NS;
@@ -842,7 +838,7 @@ extern "C" int pnr_eval_ray_samples_f32_train(const PnrScene *scene, const PnrMl
 // ---- fp32-class training, FUSED (round 3).  The training forward is the split-operand inference kernel (pnr_split.hip, TRAIN
 // instantiation: one launch, lin_z through the folded fp32 tables) that also copies the (head, tail) operand images of every
 // linear out of LDS and writes 1-bit relu masks; the backward is bwd_split_kernel (all 15 transposed products of a network in
-// one launch, gradient images copied out the same way) + ONE batched split-operand weight-gradient launch (dw_split_kernel,
+// one launch, gradient images copied out the same way) + ONE batched split-operand weight-gradient launch (dw_split_wide_kernel,
 // pnr_bwd.hip) straight from those images + lin_out's 4 x 512 gradient.  ~120 launches of the GEMM-per-layer form -> 8.
 static int check_split_saved(const PnrSplitSaved *sv) {
     if (!sv || !sv->in_op || !sv->zlat || !sv->x5 || !sv->masks) return 0;
@@ -863,9 +859,7 @@ extern "C" int pnr_eval_ray_samples_split_train(const PnrScene *scene, const voi
     EvalParams q = {};
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
     if (q.P * scene->NS > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: too many points");
-    q.latent = scene->latent_nhwc; q.poses = scene->poses; q.focal = scene->focal; q.c = scene->c;
-    q.SB = scene->SB; q.NS = scene->NS; q.Hl = scene->Hl; q.Wl = scene->Wl; q.n_focal = scene->n_focal; q.n_c = scene->n_c;
-    q.img_w = scene->img_w; q.img_h = scene->img_h;
+    scene_params(q, *scene);
     const int np = (int)q.P;
     const long long rows = (long long)np * scene->NS;
     // lin_in operand and interpolated latent as (head | tail) rows: operands of the lin_in / lin_z weight gradients
@@ -882,9 +876,10 @@ static size_t split_bwd_images_bytes(long long P, int NS) { return ((size_t)P * 
 extern "C" size_t pnr_mlp_backward_split_workspace_bytes(long long P, int NS) {
     if (P <= 0 || NS <= 0) return 0;
     // gradient images: g_fc1 / g_fc0 of blocks 0-2 and g_x0 at NS*P rows, of blocks 3-4 at P rows, 2 x 1024 B per row; the
-    // transposed (head, tail) streams; the slice partials of the batched weight-gradient launch and of lin_out's
+    // transposed (head, tail) streams; the slice partials of the batched weight-gradient launch and of lin_out's; several views:
+    // the chain's view-sum scratch
     return split_bwd_images_bytes(P, NS) + pnr::bwd_split_packed_bytes() + pnr_weight_grad_batched_workspace_bytes(14, P * NS) +
-           (size_t)pnr::WG_SPLIT * (pnr::D_HID * pnr::D_HID + pnr::D_HID) * sizeof(float);
+           (size_t)pnr::WG_SPLIT * (pnr::D_HID * pnr::D_HID + pnr::D_HID) * sizeof(float) + (NS > 1 ? pnr_mv_workspace_bytes() : 0);
 }
 
 extern "C" int pnr_mlp_backward_split(const PnrMlpWeights *w, const PnrSplitSaved *sv, const float *g_out, long long P, int NS,
@@ -909,10 +904,11 @@ extern "C" int pnr_mlp_backward_split(const PnrMlpWeights *w, const PnrSplitSave
     void *g_x0 = cur; cur += (size_t)rows * D_HID * 4;
     void *packed = cur; cur += bwd_split_packed_bytes();
     void *dw_ws = cur; cur += pnr_weight_grad_batched_workspace_bytes(14, rows);
-    float *part = (float *)cur;
+    float *part = (float *)cur; cur += (size_t)WG_SPLIT * (D_HID * D_HID + D_HID) * sizeof(float);
+    float *mv_ws = NS > 1 ? (float *)cur : nullptr;
     int rc = pack_bwd_split(w, packed, hs);
     if (rc != PNR_OK) return rc;
-    rc = mlp_backward_split_chain(packed, (const unsigned long long *)sv->masks, g_out, grad_scale, P, NS, g_fc1, g_fc0, g_x0, d_zlat, d_in, hs);
+    rc = mlp_backward_split_chain(packed, (const unsigned long long *)sv->masks, g_out, grad_scale, P, NS, g_fc1, g_fc0, g_x0, d_zlat, d_in, mv_ws, hs);
     if (rc != PNR_OK) return rc;
     if (!grads) return pnr_check_launch("pnr_mlp_backward_split");  // data gradients only: no weight-gradient launches
     // all 14 wide weight gradients in one launch pair, straight from the (head | tail) images; the chain ran at scale s: 1/s on the way out
@@ -1107,9 +1103,7 @@ extern "C" int pnr_point_features_f32(const PnrScene *s, const float *xyz, const
     EvalParams q = {};
     q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B; q.P = (long long)s->SB * B;
     if (q.P * s->NS > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_point_features_f32: too many points");
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     const long long rows = q.P * s->NS;
     hipLaunchKernelGGL(feat_f32_kernel<false>, dim3((unsigned)((rows + FW - 1) / FW)), dim3(FW * 64), 0, (hipStream_t)stream, q, 0LL,
                        (int)q.P, in42, zlat);

@@ -32,7 +32,8 @@ size_t bwd_split_packed_bytes();
 int pack_bwd_split(const PnrMlpWeights *w, void *packed, hipStream_t st);
 int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long long *masks, const float *g_out, const float *scale_dev,
                              long long P, int NS, void *const *g_fc1, void *const *g_fc0, void *g_x0, float *d_zlat /* (NS*P,512) */,
-                             float *d_in /* (NS*P,42), nullable */, hipStream_t st);
+                             float *d_in /* (NS*P,42), nullable */,
+                             float *mv_ws /* NS > 1: pnr_mv_workspace_bytes() */, hipStream_t st);
 
 // fp16-range guard of the fp32-class kernels (pnr_saturation_guard, pnr_api.hip): the flag word the next split-operand launch
 // of THIS host thread reports into (NULL = guard off), and which of the caller's two words that is (render entries set the
@@ -42,12 +43,10 @@ void saturation_guard_slot(int slot);
 
 // XCDs the dispatcher deals workgroups to round-robin on the current device (hipDeviceAttributeNumberOfXccs, i.e. of the
 // current compute-partition mode: 8 in SPX, 1 in CPX; PIXELNERF_XCD_COUNT=n overrides, 0 selects the plain grid-stride
-// tile order); cached per process.  Feeds EvalParams::n_xcd / tile_range() (pnr_device.h).  Defined in pnr_api.hip.
+// tile order), and its compute units; both cached per device.  n_xcd feeds EvalParams::n_xcd / tile_range() (pnr_device.h),
+// the CU count sizes the persistent grids and the multi-view scratch.  Defined in pnr_api.hip.
 int device_xcd_count();
-
-// per (device, stream) scratch for the parked view sum of multi-view launches (one tile of fp32 accumulators per workgroup),
-// allocated at the first multi-view launch on a stream and kept; NULL on allocation failure.  Defined in pnr_mlp.hip.
-float *mv_scratch(hipStream_t st, size_t bytes);
+int device_cus();
 
 // HIP events around one network-kernel launch, recorded on the launch's own stream while pnr_profile_enable(1) is
 // active (pnr_profile_read sums them): the live kernel-time figure of bench.py's roofline block.  Defined in pnr_mlp.hip.

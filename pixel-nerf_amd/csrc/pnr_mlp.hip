@@ -15,7 +15,6 @@
 // averaged before block 3 (util.combine_interleaved, util.py:461-471).
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <vector>
 
 #include "pnr_common.h"
@@ -389,17 +388,6 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_kernel(const EvalParams
             res_block<P, TIMING, TRAIN, FOLD, TL>(x, smem, b, false, R, NS, bias_lane, a_rd0, a_rd1, z_rd0, z_rd1, a_wr, tid, tim, tlast,
                                               q, dump_pooled, valid, wv, lane, mask_pooled, mask_layer, rows_left);
 
-        if (q.dbg) {
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt) {
-                    const long long g = (long long)tile * MT + jt * 32 + pl;
-                    if (g < q.P)
-                        for (int r = 0; r < 16; ++r) q.dbg[g * D_HID + feat_of(wv * IT + it, h, r)] = x[it][jt][r];
-                }
-        }
-
         // lin_out(relu(x)) (resnetfc.py:183): each wave contracts its own 64 features
         {
             f32x16 o[JT];
@@ -465,8 +453,6 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_kernel(const EvalParams
 static bool g_profile = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_events;
 
-static int num_cus();
-
 ProfileScope::ProfileScope(hipStream_t s) : st(s) {
     if (!g_profile) return;
     if (hipEventCreate(&e0) != hipSuccess) { e0 = nullptr; return; }
@@ -487,47 +473,9 @@ ProfileScope::~ProfileScope() {
 // of 96 against 3 of 64 -> 96).  Both forms give the same bits per point.
 static inline bool use_tile96(const EvalParams &q, bool mv) {
     if (!(q.tables && !mv && !q.d_z)) return false;  // multi-view: the 64-point tile
-    const long long ncu = num_cus();
+    const long long ncu = device_cus();
     const long long r96 = ((q.P + 95) / 96 + ncu - 1) / ncu, r64 = ((q.P + 63) / 64 + ncu - 1) / ncu;
     return r96 * 137 <= r64 * 100;
-}
-
-// per (device, stream) scratch of the multi-view instantiations (the split-operand kernel, and -DPNR_MV_PARK builds of this one): the parked view sum, one tile
-// of fp32 accumulators per workgroup (256 x 192 KiB = 48 MiB), allocated at the first multi-view launch on a stream.
-float *mv_scratch(hipStream_t st, size_t bytes) {
-    struct Slot { int dev; hipStream_t st; float *p; size_t bytes; };
-    static std::vector<Slot> slots;
-    static std::mutex mu;  // single-process multi-GPU training runs one autograd thread per device: the table is shared
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    // growing the table allocates: illegal inside a HIP-graph capture.  A capture runs on a stream of its own (torch.cuda.graph), which
-    // no warm-up call has ever seen: the launch being captured then BORROWS the largest scratch another stream of this device
-    // already owns (the warm-up's).  That is ordered correctly as long as the replayed graph and multi-view launches on that
-    // other stream do not run at the same time -- the one restriction of capturing a multi-view call.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    for (auto &sl : slots)
-        if (sl.dev == dev && sl.st == st) {
-            if (sl.bytes >= bytes) return sl.p;
-            if (capturing) break;
-            (void)hipFree(sl.p);
-            sl.p = nullptr; sl.bytes = 0;
-            if (hipMalloc(&sl.p, bytes) != hipSuccess) return nullptr;
-            sl.bytes = bytes;
-            return sl.p;
-        }
-    if (capturing) {
-        float *best = nullptr;
-        size_t best_bytes = 0;
-        for (auto &sl : slots)
-            if (sl.dev == dev && sl.bytes >= bytes && sl.bytes > best_bytes) { best = sl.p; best_bytes = sl.bytes; }
-        return best;  // nullptr: no multi-view launch has run on this device outside of a capture yet
-    }
-    Slot sl = {dev, st, nullptr, bytes};
-    if (hipMalloc(&sl.p, bytes) != hipSuccess) return nullptr;
-    slots.push_back(sl);
-    return sl.p;
 }
 
 template <int PREC, bool RAYS>
@@ -543,12 +491,7 @@ static int launch(EvalParams &q, bool mv, hipStream_t st) {
     else if (q.tables) k = mv ? eval_kernel<PREC, RAYS, true, false, false, true> : eval_kernel<PREC, RAYS, false, false, false, true>;
     const long long nt = (q.P + mt - 1) / mt;
     q.ntiles = (int)nt;
-    const int grid = (int)(nt < num_cus() ? nt : num_cus());
-    if (mv && RAYS && q.d_z)  // the training instantiation parks its view sum
-    {
-        q.mv_ws = mv_scratch(st, (size_t)num_cus() * 96 * D_HID * sizeof(float));
-        if (!q.mv_ws) return pnr_fail(PNR_E_HIP, "pnr_eval: cannot allocate the multi-view pooling scratch (48 MiB)");
-    }
+    const int grid = (int)(nt < device_cus() ? nt : device_cus());
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(eval_kernel)");
     {
@@ -557,17 +500,6 @@ static int launch(EvalParams &q, bool mv, hipStream_t st) {
         hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, q);
     }
     return pnr_check_launch("eval_kernel");
-}
-
-static int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
 }
 
 static int eval_common(const PnrScene *s, const void *packed, int precision, EvalParams &q, bool rays, hipStream_t st,
@@ -580,9 +512,7 @@ static int eval_common(const PnrScene *s, const void *packed, int precision, Eva
     if (!(s->n_focal == 1 || s->n_focal == s->SB) || !(s->n_c == 1 || s->n_c == s->SB))
         return pnr_fail(PNR_E_INVALID, "pnr_eval: focal / c must have 1 or SB rows");
     if (q.P == 0) return PNR_OK;
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.wstream = (const char *)packed;
     q.bias = (const float *)((const char *)packed + BIAS_OFFSET_BYTES);
     q.bout = (const float *)((const char *)packed + BOUT_OFFSET_BYTES);
@@ -591,6 +521,7 @@ static int eval_common(const PnrScene *s, const void *packed, int precision, Eva
     if ((long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT > 0xffffffffLL)
         return pnr_fail(PNR_E_INVALID, "pnr_eval: feature grid too large (SB*NS*Hl*Wl*512 must stay below 2^32 elements)");
     const bool mv = s->NS > 1;
+    if (mv && !q.mv_ws) return pnr_fail(PNR_E_INVALID, "pnr_eval: a multi-view scene needs PnrScene.mv_workspace (pnr_mv_workspace_bytes())");
     if (precision == PNR_PREC_F16) return rays ? launch<PNR_PREC_F16, true>(q, mv, st) : launch<PNR_PREC_F16, false>(q, mv, st);
     if (precision == PNR_PREC_BF16) return rays ? launch<PNR_PREC_BF16, true>(q, mv, st) : launch<PNR_PREC_BF16, false>(q, mv, st);
     return pnr_fail(PNR_E_INVALID, "pnr_eval: unknown precision");
@@ -598,18 +529,18 @@ static int eval_common(const PnrScene *s, const void *packed, int precision, Eva
 
 }  // namespace pnr
 
-// test/diagnostic hook (not in the public header): per-phase s_memtime totals of wave 0 of
-// workgroup 0 for one f16 single-view launch.  tim: NW*NPHASE device counters, zeroed by the caller.
+#ifdef PNR_VARIANT
+// diagnostic hook of variant builds (tools/gpu_phase_timing.py): per-phase s_memtime totals of wave 0 of workgroup 0 for one
+// f16 single-view launch.  tim: NW*NPHASE device counters, zeroed by the caller; rgbsigma (R,K,4) out.
 extern "C" int pnr_debug_phase_timing(const PnrScene *s, const void *packed, const void *tables, const float *rays,
-                                      const float *z, int R, int rays_per_obj, int K, unsigned long long *tim,
+                                      const float *z, int R, int rays_per_obj, int K, float *rgbsigma, unsigned long long *tim,
                                       void *stream) {
     using namespace pnr;
-    if (!s || !packed || !rays || !z || !tim || s->NS != 1) return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing: bad argument");
+    if (!s || !packed || !rays || !z || !rgbsigma || !tim || s->NS != 1)
+        return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing: bad argument");
     EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.tim = tim;
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = 1; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma; q.tim = tim;
+    scene_params(q, *s);
     q.wstream = (const char *)packed;
     q.bias = (const float *)((const char *)packed + BIAS_OFFSET_BYTES);
     q.bout = (const float *)((const char *)packed + BOUT_OFFSET_BYTES);
@@ -617,27 +548,16 @@ extern "C" int pnr_debug_phase_timing(const PnrScene *s, const void *packed, con
     q.ntiles = (int)((q.P + mt - 1) / mt);
     q.tables = (const char *)tables;  // non-null: folded stream
     q.table_stride = (long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT;
-    static float *scratch_out = nullptr;
-    static long long scratch_n = 0;
-    if (scratch_n < q.P) {
-        if (scratch_out) (void)hipFree(scratch_out);
-        if (hipMalloc(&scratch_out, (size_t)q.P * 16) != hipSuccess) return pnr_fail(PNR_E_HIP, "hipMalloc");
-        scratch_n = q.P;
-    }
-    q.out = scratch_out;
     auto k = tables ? eval_kernel<PNR_PREC_F16, true, false, true, false, true, 96> : eval_kernel<PNR_PREC_F16, true, false, true>;
     const int lds = tables ? Tile<96>::LDS_TOTAL : Tile<64>::LDS_TOTAL;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute");
-    const int grid = q.ntiles < num_cus() ? q.ntiles : num_cus();
+    const int grid = q.ntiles < device_cus() ? q.ntiles : device_cus();
     q.n_xcd = device_xcd_count();
     hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, (hipStream_t)stream, q);
     return pnr_check_launch("eval_kernel<timing>");
 }
-
-static float *g_dbg_ptr = nullptr;
-// test hook (not part of the public header): dump the final residual stream of the next launches
-extern "C" int pnr_debug_set_x_dump(float *ptr) { g_dbg_ptr = ptr; return PNR_OK; }
+#endif
 
 int pnr::eval_samples_src(const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
                           const float *z, int R, int rays_per_obj, int K, float *rgbsigma, hipStream_t stream) {
@@ -647,7 +567,7 @@ int pnr::eval_samples_src(const PnrScene *scene, const void *packed, const void 
     if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: R != SB * rays_per_obj");
     pnr::EvalParams q = {};
     q.rays = src.rays; q.cam = src; q.cam.rays = nullptr;
-    q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma; q.dbg = g_dbg_ptr;
+    q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
     return pnr::eval_common(scene, packed, precision, q, true, stream, tables);
 }
 
@@ -696,7 +616,7 @@ static int eval_points_impl(const PnrScene *scene, const void *packed, const voi
     if (B > 0 && (!xyz || !viewdirs)) return pnr_fail(PNR_E_INVALID, "pnr_eval_points: null xyz/viewdirs");
     pnr::EvalParams q = {};
     q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B > 0 ? B : 1;
-    q.P = scene ? (long long)scene->SB * B : 0; q.out = rgbsigma; q.dbg = g_dbg_ptr;
+    q.P = scene ? (long long)scene->SB * B : 0; q.out = rgbsigma;
     return pnr::eval_common(scene, packed, precision, q, false, (hipStream_t)stream, tables);
 }
 

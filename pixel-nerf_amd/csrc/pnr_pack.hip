@@ -3,8 +3,6 @@
 // transpose of the encoder feature grid.  gfx950.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "pnr_common.h"
 #include "pnr_device.h"  // EvalParams, project_point: the sparse fold marks rows with the forward kernels' own projection
 #include "pnr_internal.h"
@@ -752,9 +750,9 @@ extern "C" int pnr_fold_latent_f32(const PnrScene *s, const PnrMlpWeights *w, fl
         jobs.W[b] = w->lin_z_w[b]; jobs.bias[b] = w->lin_z_b[b];
     }
     // large grids: 256 x 256 tiles, double-buffered (fold_split_big_kernel); small ones keep the 128 x 128 kernel, whose 4-wave
-    // workgroups fill the chip at a few thousand texels (PNR_FOLD_BIG_MIN_TEXELS: the crossover, measured -- profiles/r06_fold_notes.md)
-    static const long long big_min = [] { const char *e = getenv("PNR_FOLD_BIG_MIN_TEXELS"); return e ? atoll(e) : 8192LL; }();
-    if (M >= big_min) {
+    // workgroups fill the chip at a few thousand texels (the crossover, measured -- profiles/r06_fold_notes.md)
+    constexpr long long FOLD_BIG_MIN_TEXELS = 8192;
+    if (M >= FOLD_BIG_MIN_TEXELS) {
         const int ngroups = (int)((M + FB_TM - 1) / FB_TM);
         const unsigned wgs = (unsigned)((ngroups + 7) / 8) * 8u * 6u;
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fold_split_big_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
@@ -804,9 +802,7 @@ extern "C" int pnr_fold_latent_f32_rows(const PnrScene *s, const PnrMlpWeights *
     hipError_t e = hipMemsetAsync(flags, 0, nb * FR_PER_WG, st);
     if (e != hipSuccess) return pnr_check_hip(e, "hipMemsetAsync(fold marks)");
     EvalParams q = {};
-    q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = P;
     const long long n = P * s->NS;
     hipLaunchKernelGGL(fold_mark_kernel, dim3((unsigned)((n + FM_NT - 1) / FM_NT)), dim3(FM_NT), 0, st, q, flags);

@@ -56,7 +56,7 @@ static_assert(NW == 8, "pnr_split.hip: the product build is 8 waves per workgrou
 // The fp32 table rows (2 KiB + 16 B pad per point) are looked up into the space of the two activation images
 // while those are free (tile start, and after fc_1 of blocks 0-1 has finished reading).
 template <int MT_> struct SplitTileT {
-    static_assert(MT_ == 64 || MT_ == 32, "64-point tiles (the 32-point form, view sum in registers, is kept for A/B: -DPNR_SPLIT_MV32)");
+    static_assert(MT_ == 64, "64-point tiles");
     static constexpr int MT = MT_, JT = MT_ / 32;
     static constexpr int A_HI = 0;
     static constexpr int A_LO = MT * ROW_ACT;             // 66,560 (64)
@@ -64,7 +64,7 @@ template <int MT_> struct SplitTileT {
     static constexpr int IN_LO_DELTA = MT * ROW_IN;        // tail image right behind it
     static constexpr int LDS_META = LDS_IN + 2 * MT * ROW_IN;
     static constexpr int LDS_OUT = LDS_META + MT * 32;
-    static constexpr int LDS_TOTAL = LDS_OUT + NW * MT * 16;  // 161,792 B (64) / 80,896 B (32)
+    static constexpr int LDS_TOTAL = LDS_OUT + NW * MT * 16;  // 161,792 B
     static constexpr int ROW_TAB = D_HID * 4 + 16;          // fp32 table row: 2064 B (129 16-B slots: conflict-free)
     static constexpr int LDS_Z = 0;                         // (geometry_item only needs LDS_IN / LDS_META)
     static_assert(MT * ROW_TAB <= LDS_IN, "table image must fit in the space of the two activation images");
@@ -490,13 +490,12 @@ __device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *
 // per-workgroup scratch (q.mv_ws, [slot][thread] layout: every lane re-reads only what it wrote itself, no synchronisation;
 // 128 KiB per workgroup, L2-resident) and read-modify-written once per view and tile -- 256 KiB of traffic against the 6.6 MB
 // of weights the same view streams.  (Round 2 ran multi-view scenes on 32-point tiles with the sum in registers: twice the
-// weight stream per point, 105-147 k rays/s; -DPNR_SPLIT_MV32 rebuilds that form.)  Fixed summation order
-// (view 0 + view 1) + ...: bit-identical to the in-register form.
-constexpr int SPLIT_MV_TILE = 64;
+// weight stream per point, 105-147 k rays/s.)  Fixed summation order (view 0 + view 1) + ...: bit-identical to the
+// in-register form.
 template <bool RAYS, bool MV, bool TIMING = false, bool TRAIN = false, bool GUARD = false>
 __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const EvalParams q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef SplitTileT<MV ? SPLIT_MV_TILE : 64> ST;
+    typedef SplitTileT<64> ST;
     constexpr int JT = ST::JT, MT = ST::MT;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1058,18 +1057,6 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) bwd_split_kernel(const BwdSp
     }
 }
 
-static int bwd_split_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, c = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) c = prop.multiProcessorCount;
-        n = c;
-    }
-    return n;
-}
-
-
 static int split_launch(const PnrScene *s, const void *packed, const void *tables, EvalParams &q, bool rays, hipStream_t st) {
     if (!s || !packed || !tables || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: null argument");
     if (s->SB <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: bad scene shape");
@@ -1080,30 +1067,21 @@ static int split_launch(const PnrScene *s, const void *packed, const void *table
     if (q.P > 0x7fffff80LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: too many points (P must stay below 2^31)");
     if ((long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT > 0xffffffffLL)
         return pnr_fail(PNR_E_INVALID, "pnr_eval_split: feature grid too large (SB*NS*Hl*Wl*512 must stay below 2^32 elements)");
-    q.latent = s->latent_nhwc; q.poses = s->poses; q.focal = s->focal; q.c = s->c;
-    q.SB = s->SB; q.NS = s->NS; q.Hl = s->Hl; q.Wl = s->Wl; q.n_focal = s->n_focal; q.n_c = s->n_c;
-    q.img_w = s->img_w; q.img_h = s->img_h;
+    scene_params(q, *s);
     q.wstream = (const char *)packed;
     q.bias = (const float *)((const char *)packed + BIAS_OFFSET_BYTES);
     q.bout = (const float *)((const char *)packed + BOUT_OFFSET_BYTES);
     q.tables = (const char *)tables;
     q.table_stride = (long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT;
     const bool mv = s->NS > 1;
-    int dev = 0, ncu = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        ncu = prop.multiProcessorCount;
+    if (mv && !q.mv_ws) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: a multi-view scene needs PnrScene.mv_workspace (pnr_mv_workspace_bytes())");
+    const int ncu = device_cus();
     // tile: 64 points (the two full operand images fill the LDS; the 96-point K-half-staged form of round 3 measured 15 % slower,
     // profiles/r03_split_kernel_ab.txt, and was removed with the other experiment code in round 4)
-    const int MT = mv ? SplitTileT<SPLIT_MV_TILE>::MT : SplitTileT<64>::MT;
-    const int lds = mv ? SplitTileT<SPLIT_MV_TILE>::LDS_TOTAL : SplitTileT<64>::LDS_TOTAL;
+    const int MT = SplitTileT<64>::MT, lds = SplitTileT<64>::LDS_TOTAL;
     const long long nt = (q.P + MT - 1) / MT;
     q.ntiles = (int)nt;
     const int grid = (int)(nt < ncu ? nt : ncu);
-    if (mv && SPLIT_MV_TILE == 64) {
-        q.mv_ws = mv_scratch(st, (size_t)ncu * 64 * D_HID * sizeof(float));
-        if (!q.mv_ws) return pnr_fail(PNR_E_HIP, "pnr_eval_split: cannot allocate the multi-view pooling scratch (32 MiB)");
-    }
     auto k = mv ? (rays ? eval_split_kernel<true, true> : eval_split_kernel<false, true>)
                 : (rays ? eval_split_kernel<true, false> : eval_split_kernel<false, false>);
     // fp16-range guard armed on this host thread (pnr_saturation_guard): the instantiations that follow the largest value
@@ -1118,10 +1096,12 @@ static int split_launch(const PnrScene *s, const void *packed, const void *table
         k = mv ? (guard ? eval_split_kernel<true, true, false, true, true> : eval_split_kernel<true, true, false, true>)
                : (guard ? eval_split_kernel<true, false, false, true, true> : eval_split_kernel<true, false, false, true>);
     }
+#ifdef PNR_VARIANT
     if (q.tim) {  // diagnostic instantiation (pnr_debug_phase_timing_split): single view, rays
         if (mv || !rays) return pnr_fail(PNR_E_INVALID, "phase timing: single-view ray launches only");
         k = eval_split_kernel<true, false, true>;
     }
+#endif
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(eval_split_kernel)");
     {
@@ -1144,7 +1124,7 @@ int pack_bwd_split(const PnrMlpWeights *w, void *packed, hipStream_t st) {
 
 int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long long *masks, const float *g_out, const float *scale_dev,
                              long long P, int NS, void *const *g_fc1, void *const *g_fc0, void *g_x0, float *d_zlat, float *d_in,
-                             hipStream_t st) {
+                             float *mv_ws, hipStream_t st) {
     if (!packed_bwd_split || !masks || !g_out || !scale_dev || !g_fc1 || !g_fc0 || !g_x0 || !d_zlat || P <= 0 || NS <= 0)
         return pnr_fail(PNR_E_INVALID, "mlp_backward_split_chain: bad argument");
     BwdSplitParams q = {};
@@ -1157,13 +1137,11 @@ int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long l
         q.g_fc1[b] = (char *)g_fc1[b]; q.g_fc0[b] = (char *)g_fc0[b];
     }
     q.g_x0 = (char *)g_x0; q.d_zlat = d_zlat; q.d_in = d_in;
-    const int cus = bwd_split_cus();
+    const int cus = device_cus();
     const int grid = (int)(nt < cus ? nt : cus);
     const bool mv = NS > 1;
-    if (mv) {
-        q.mv_ws = mv_scratch(st, (size_t)cus * 64 * D_HID * sizeof(float));
-        if (!q.mv_ws) return pnr_fail(PNR_E_HIP, "mlp_backward_split_chain: cannot allocate the multi-view scratch");
-    }
+    if (mv && !mv_ws) return pnr_fail(PNR_E_INVALID, "mlp_backward_split_chain: NS > 1 needs the multi-view scratch");
+    q.mv_ws = mv_ws;
     auto k = mv ? bwd_split_kernel<true> : bwd_split_kernel<false>;
     const int lds = SplitTileT<64>::LDS_TOTAL;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1192,7 +1170,6 @@ int pnr::eval_samples_split_train(const PnrScene *scene, const void *packed_spli
                                   const float *z, int R, int rays_per_obj, int K, float *rgbsigma, void *const *img_a, void *const *img_n,
                                   float *x5, void *masks, hipStream_t stream) {
     if (!rays || !z || !img_a || !img_n || !x5 || !masks) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null argument");
-    if (SPLIT_MV_TILE != 64) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: built with 32-point multi-view tiles");
     pnr::EvalParams q = {};
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
     for (int b = 0; b < 5; ++b) {
@@ -1212,7 +1189,9 @@ extern "C" int pnr_eval_ray_samples_split(const PnrScene *scene, const void *pac
     return pnr::eval_samples_split_src(scene, packed_split, tables_f32, src, z, R, rays_per_obj, K, rgbsigma, (hipStream_t)stream);
 }
 
-// test/diagnostic hook (not in the public header): per-phase cycle totals of every wave of workgroup 0, one single-view launch
+#ifdef PNR_VARIANT
+// diagnostic hook of variant builds (tools/gpu_phase_timing_split.py): per-phase cycle totals of every wave of workgroup 0, one
+// single-view launch
 extern "C" int pnr_debug_phase_timing_split(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *rays,
                                             const float *z, int R, int rays_per_obj, int K, float *rgbsigma, unsigned long long *tim,
                                             void *stream) {
@@ -1221,6 +1200,7 @@ extern "C" int pnr_debug_phase_timing_split(const PnrScene *scene, const void *p
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma; q.tim = tim;
     return pnr::split_launch(scene, packed_split, tables_f32, q, true, (hipStream_t)stream);
 }
+#endif
 
 extern "C" int pnr_eval_points_split(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *xyz,
                                      const float *viewdirs, int B, float *rgbsigma, void *stream) {

@@ -187,6 +187,15 @@ def _check_split_tables(tables):
         raise _lib.PixelNerfHipError("precision='f16x3' takes the fp32 tables of fold_latent(scene, state, 'f16x3')")
 
 
+def _mv_workspace(NS, device):
+    """the view-sum scratch of the multi-view kernels (pnr_mv_workspace_bytes() of `device`; None for one view): a torch tensor,
+    so that inside a graph capture it comes from the graph's pool like every other buffer"""
+    if NS <= 1:
+        return None
+    with torch.cuda.device(device):
+        return torch.empty(_lib.load().pnr_mv_workspace_bytes(), dtype=torch.uint8, device=device)
+
+
 class Scene:
     """Device-side encoded-scene state (what PixelNeRFNet.encode() leaves behind)."""
 
@@ -210,8 +219,10 @@ class Scene:
         s.SB, s.NS, s.Hl, s.Wl = self.SB, self.NS, Hl, Wl
         s.n_focal, s.n_c = self.focal.shape[0], self.c.shape[0]
         s.img_w, s.img_h = float(image_shape[0]), float(image_shape[1])
-        self.struct = s
         self.device = self.latent_nhwc.device
+        self.mv_workspace = _mv_workspace(self.NS, self.device)
+        s.mv_workspace = None if self.mv_workspace is None else self.mv_workspace.data_ptr()
+        self.struct = s
 
     @property
     def ref(self):
@@ -890,43 +901,6 @@ def profile_read():
     return ms.value, n.value
 
 
-def debug_set_x_dump(t):
-    """test hook: dump the residual stream before lin_out of subsequent launches into t (P,512)."""
-    _lib.check(_lib.load().pnr_debug_set_x_dump(_p(t)), "pnr_debug_set_x_dump")
-
-
-PHASES = ["sync_top", "geometry", "gather", "gemm_in_z0", "bar1", "write_x", "bar2", "gemm_fc0", "bar3", "write_net",
-          "bar4", "gemm_fc1_z", "lin_out", "bar_out", "final", "table", "own_bias", "own_prologue", "own_ksteps"]
-
-
-def debug_phase_timing(scene, packed, rays, z, tables=None):
-    """diagnostic: {phase: [s_memtime ticks of wave 0..7]} of workgroup 0, one f16 single-view launch."""
-    lib = _lib.load()
-    rays, z = _f32(rays, "rays", (None, 8)), _f32(z, "z")
-    tim = torch.zeros(8 * len(PHASES), dtype=torch.int64, device=rays.device)
-    _check_fold(packed, tables, "debug_phase_timing")
-    _lib.check(lib.pnr_debug_phase_timing(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), rays.shape[0],
-                                          max(rays.shape[0] // scene.SB, 1), z.shape[1], _p(tim), _stream()),
-               "pnr_debug_phase_timing")
-    torch.cuda.synchronize()
-    t = tim.cpu().reshape(8, len(PHASES))
-    return {p: t[:, i].tolist() for i, p in enumerate(PHASES)}  # per wave
-
-
-def debug_phase_timing_split(scene, packed, rays, z, tables):
-    """diagnostic: {phase: [cycles of wave 0..7]} of workgroup 0, one f16x3 single-view launch."""
-    lib = _lib.load()
-    rays, z = _f32(rays, "rays", (None, 8)), _f32(z, "z")
-    _check_split_tables(tables)
-    tim = torch.zeros(8 * len(PHASES), dtype=torch.int64, device=rays.device)
-    out = torch.empty((rays.shape[0], z.shape[1], 4), dtype=torch.float32, device=rays.device)
-    _lib.check(lib.pnr_debug_phase_timing_split(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), rays.shape[0],
-                                                max(rays.shape[0] // scene.SB, 1), z.shape[1], _p(out), _p(tim), _stream()),
-               "pnr_debug_phase_timing_split")
-    torch.cuda.synchronize()
-    t = tim.cpu().reshape(8, len(PHASES))
-    return {p: t[:, i].tolist() for i, p in enumerate(PHASES)}
-
 
 # ------------------------------------------------------------------ training support
 
@@ -1039,10 +1013,13 @@ class BackwardDumps:
         rows = fwd.d_z.shape[0]
         self.d_zlat = torch.empty((rows, 512), dtype=torch.float32, device=device)
         self.d_in = torch.empty((rows, 42), dtype=torch.float32, device=device)
-        self.nbytes = sum(t.numel() * t.element_size() for t in [self.g_x0, self.d_zlat, self.d_in] + self.g_fc1 + self.g_fc0)
+        self.mv_workspace = _mv_workspace(fwd.NS, device)
+        own = [self.g_x0, self.d_zlat, self.d_in] + self.g_fc1 + self.g_fc0 + ([] if self.mv_workspace is None else [self.mv_workspace])
+        self.nbytes = sum(t.numel() * t.element_size() for t in own)
         s = _lib.PnrBackwardDumps()
         s.g_x0 = self.g_x0.data_ptr()
         s.d_zlat, s.d_in = self.d_zlat.data_ptr(), self.d_in.data_ptr()
+        s.mv_workspace = None if self.mv_workspace is None else self.mv_workspace.data_ptr()
         for b in range(5):
             s.g_fc1[b], s.g_fc0[b] = self.g_fc1[b].data_ptr(), self.g_fc0[b].data_ptr()
         self.struct = s

@@ -1,8 +1,10 @@
-"""CPU tests: the C-ABI library builds for gfx950, loads, and exports every symbol that
+"""CPU tests: the C-ABI library builds for gfx950, loads, and exports exactly the functions that
 include/pixelnerf_hip.h declares (no compute calls: there is no GPU here)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -29,10 +31,24 @@ def test_library_exports_every_declared_symbol(lib, repo_root):
     assert sorted(_lib.PROTOTYPES) == names, "ctypes prototypes and header out of sync"
 
 
-def test_struct_layouts_match_header():
-    # PnrScene: 4 pointers, 6 int32, 2 floats; PnrMlpWeights: 30 pointers + the combine_max flag (padded to 8); dumps: 13 / 13 pointers (11 dY dumps + d_zlat + d_in)
-    assert ctypes.sizeof(_lib.PnrTrainDumps) == 14 * 8 and ctypes.sizeof(_lib.PnrBackwardDumps) == 13 * 8
-    assert ctypes.sizeof(_lib.PnrScene) == 4 * 8 + 6 * 4 + 2 * 4
+def test_library_exports_only_the_header_and_allocates_nothing(lib, repo_root):
+    """built with hidden visibility, the product library exports the header's functions and no other function of its own (no
+    debug entries, no C++ internals); it imports no device allocator: every buffer is the caller's (torch tensors)"""
+    if shutil.which("nm") is None:
+        pytest.skip("no nm")
+    nm = lambda *flags: subprocess.run(["nm", "-D", *flags, _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout.split("\n")
+    funcs = {f[2] for f in (line.split() for line in nm("--defined-only")) if len(f) == 3 and f[1] in "TWi"}
+    assert sorted(n for n in funcs if n.startswith("pnr_")) == header_functions(repo_root)
+    assert not [n for n in funcs if n.startswith("_Z")], "mangled functions exported"
+    imports = {line.split()[-1].split("@")[0] for line in nm("--undefined-only") if line.strip()}
+    assert not [n for n in imports if n.startswith(("hipMalloc", "hipFree", "hipHostMalloc"))]
+
+
+def test_struct_layouts_match_header_abi_rev10():
+    # PnrScene: 4 pointers, 6 int32, 2 floats, the multi-view scratch; PnrMlpWeights: 30 pointers + the combine_max flag (padded to 8);
+    # dumps: 14 / 14 pointers (backward: 11 dY dumps + d_zlat + d_in + the multi-view scratch)
+    assert ctypes.sizeof(_lib.PnrTrainDumps) == 14 * 8 and ctypes.sizeof(_lib.PnrBackwardDumps) == 14 * 8
+    assert ctypes.sizeof(_lib.PnrScene) == 4 * 8 + 6 * 4 + 2 * 4 + 8 == 72
     assert ctypes.sizeof(_lib.PnrMlpWeights) == 30 * 8 + 8
 
 
@@ -89,6 +105,9 @@ def test_host_only_entry_points(lib):
     assert lib.pnr_packed_mlp_bwd_bytes() == 8 * 424 * 2 * 1024
     assert lib.pnr_packed_mlp_split_bytes() == 2 * lib.pnr_packed_mlp_bytes()
     assert lib.pnr_weight_grad_workspace_bytes() == 32 * (512 * 512 + 512) * 4
+    mv = lib.pnr_mv_workspace_bytes()  # CUs x 96 x 512 fp32 (256 CUs when no device answers)
+    assert mv > 0 and mv % (96 * 512 * 4) == 0
+    assert lib.pnr_mlp_backward_split_workspace_bytes(1000, 2) - lib.pnr_mlp_backward_split_workspace_bytes(1000, 1) > mv
     perm = (ctypes.c_int32 * 512)()
     assert lib.pnr_storage_perm(perm) == 0 and sorted(perm) == list(range(512)) and perm[16] == 4 and perm[1] == 1
     r, kc, kf = 100, 64, 128
@@ -117,6 +136,17 @@ def test_argument_validation_without_gpu(lib):
     bd.g_x0 = 64
     assert lib.pnr_mlp_backward(64, 0, ctypes.byref(dumps), 64, 1.0, None, 10, 1, ctypes.byref(bd), None) == -1
     assert b"d_zlat is required" in lib.pnr_last_error()
+    # several views need the caller's multi-view scratch: the library never allocates one
+    bd.d_zlat = 64
+    assert lib.pnr_mlp_backward(64, 0, ctypes.byref(dumps), 64, 1.0, None, 10, 2, ctypes.byref(bd), None) == -1
+    assert b"mv_workspace" in lib.pnr_last_error()
+    mvs = _lib.PnrScene()
+    mvs.latent_nhwc, mvs.poses, mvs.focal, mvs.c = 64, 64, 64, 64
+    mvs.SB, mvs.NS, mvs.Hl, mvs.Wl, mvs.n_focal, mvs.n_c = 1, 2, 8, 8, 1, 1
+    assert lib.pnr_eval_ray_samples(ctypes.byref(mvs), 64, _lib.PREC_F16, 64, 64, 4, 4, 8, 64, None) == -1
+    assert b"mv_workspace" in lib.pnr_last_error()
+    assert lib.pnr_eval_ray_samples_split(ctypes.byref(mvs), 64, 64, 64, 64, 4, 4, 8, 64, None) == -1
+    assert b"mv_workspace" in lib.pnr_last_error()
     assert lib.pnr_grad_scale(None, 10, None, None) == -1
     assert lib.pnr_weight_grad(None, None, 10, 0, 1.0, 0, 0, None, None, None, None) == -1
     assert lib.pnr_position_backward(None, None, None, 1, 1, 1, None, None, None, None) == -1

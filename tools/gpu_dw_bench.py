@@ -2,14 +2,14 @@
 """pnr_weight_grad_batched at PNR_PREC_F16X3 on the training step's shape: 14 jobs (ten fc + three lin_z of 512 columns, lin_in of 64),
 rows = 32768 (coarse pass of config 5) and 49152 (fine pass); HIP events, us per call (dw kernel + reduction), max error of one job
 against fp64, a checksum of all outputs (equal across forms when the partial sums are formed in the same order).
-A/B: PNR_DW_FORM=8wave | (unset: the one-wave-per-SIMD kernel); variant libraries through PIXELNERF_HIP_LIB (profiles/r06_dw_split_notes.md)."""
+A/B: variant libraries through PIXELNERF_HIP_LIB (profiles/r06_dw_split_notes.md)."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pixelnerf_amd import ops, _lib
 dev = torch.device("cuda:0")
-tag = os.environ.get("PNR_DW_FORM", "wide") + ":" + os.path.basename(os.environ.get("PIXELNERF_HIP_LIB", "product"))
+tag = os.path.basename(os.environ.get("PIXELNERF_HIP_LIB", "product"))
 for rows in [int(a) for a in sys.argv[1:]] or [32768, 49152]:
     g = torch.Generator(device=dev).manual_seed(rows)
     def pair(cols, scale):

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Per-phase cycle breakdown of the fp32-class fused kernel (eval_split_kernel, 64-point tiles), all waves of workgroup 0."""
+"""Per-phase cycle breakdown of the fp32-class fused kernel (eval_split_kernel, 64-point tiles), all waves of workgroup 0.
+The phases need a variant library (tools/gpu_phase_timing.py says how); --no-phases times the product kernel alone."""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pixelnerf_amd import ops
 from testdata import synthetic
+from gpu_phase_timing import phase_timing
 
 dev = torch.device("cuda:0")
 MT = 64
@@ -28,7 +30,7 @@ print(f"f16x3 sn64 R={R} K={K}: {dt*1e3:.2f} ms  {R*K/dt/1e6:.2f} Mpts/s  {R*K*6
       f"{3*0.771*R*K*6.863e6/dt/1e12:.1f} executed")
 if "--no-phases" not in sys.argv:
     for it in range(2):
-        t = ops.debug_phase_timing_split(sc, pk, rays, z, tab)
+        t = phase_timing("pnr_debug_phase_timing_split", sc, pk, rays, z, tab)
     ntile = ((R * K + MT - 1) // MT + 255) // 256
     tot = [sum(v[w] for v in t.values()) for w in range(8)]
     print(f"tile {MT} pts; tiles by WG0: {ntile}; per-tile cycles per wave: " + " ".join(f"{x/ntile:8.0f}" for x in tot))
