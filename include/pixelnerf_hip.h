@@ -71,6 +71,11 @@ typedef struct PnrMlpWeights {
     const float *lin_out_w, *lin_out_b;     /* (4,512), (4)     */
     int32_t combine_max;                    /* pooling over the source views (util.combine_interleaved, util.py:461-471):
                                                0 = "average" (every shipped config), 1 = "max" (inference entries only) */
+    int32_t stream_scale_log2;              /* ABI rev 11.  s in [0, 30], honoured by pnr_pack_mlp_split only: the PNR_PREC_F16X3
+                                               inference kernels carry the hidden stream (x and the block-internal net of
+                                               resnetfc.py:66-88, 147-184) at 2^-s of its value -- see "stream scale" below.
+                                               0 = off.  Every other pack entry and every training entry refuses a non-zero
+                                               value (PNR_E_INVALID); the exact fp32 inference entries ignore it. */
 } PnrMlpWeights;
 
 const char *pnr_last_error(void);
@@ -80,7 +85,7 @@ int pnr_version(int *major, int *minor);
 /* ABI revision of THIS header: bumped whenever a struct layout or an entry point's argument list changes.  The
  * library returns the value it was compiled with; a binding must compare it with the header it was written against
  * before the first call (pixelnerf_amd/_lib.py does, and refuses a stale or foreign .so). */
-#define PNR_ABI_VERSION 10
+#define PNR_ABI_VERSION 11
 int pnr_abi_version(void);
 int pnr_device_info(int *num_cus, int *lds_bytes_per_block);
 /* Bytes of the multi-view scratch (PnrScene.mv_workspace, PnrBackwardDumps.mv_workspace) on the CURRENT device: one tile of
@@ -511,6 +516,38 @@ int pnr_render_views(const PnrScene *scene /*host*/, const void *packed_coarse, 
  * pixelnerf_amd copies it to pinned memory and looks at it on the next call, like the parameter check).
  * The guard never changes a result. */
 int pnr_saturation_guard(unsigned int *flags_dev);
+
+/* ---- stream scale and range probe of the fp32-class ("f16x3") kernels (ABI rev 11) ----------------
+ * ReLU is positively homogeneous, so the hidden stream of a ResnetFC (src/model/resnetfc.py:147-184: x, and
+ * net / dx inside every block, resnetfc.py:66-88) can be carried at c = 2^-s of its value and undone exactly in
+ * front of lin_out's bias (resnetfc.py:183, src/model/models.py:258-265).  A network packed with
+ * PnrMlpWeights.stream_scale_log2 = s > 0 (pnr_pack_mlp_split) runs the scaled instantiation in every
+ * PNR_PREC_F16X3 inference entry (pnr_eval_points_split, pnr_eval_ray_samples_split, pnr_render_forward_folded /
+ * _seeded, pnr_render_views; single- and multi-view, the merge path of a NULL fine network included).  All four
+ * scale sites are fp32 and exact -- nothing that is stored as fp16 is shifted:
+ *   x *= c          after lin_in + table 0 (lin_in's bias included)         resnetfc.py:147, 175-180 (b = 0)
+ *   x += c * t      tables 1 and 2 (one FMA; the tables in memory are unscaled) resnetfc.py:175-180 (b = 1, 2)
+ *   c * bias        blocks[b].fc_0 / fc_1 biases, at pack time               resnetfc.py:81-82
+ *   sum * 2^(s-t)   the lin_out partial sum, BEFORE lin_out's bias           resnetfc.py:183
+ * t: lin_out's weights are packed LIFTED by 2^t (the largest t in [0, 30] with max |W_out| 2^t <= 2^14; exact, in fp32, in
+ * front of the head/tail split).  A network with a large hidden stream has a correspondingly small lin_out, whose fp16 tails
+ * -- at 1e-6 even its heads -- are subnormal; the lift moves them up into the normal range.  The hidden weights are untouched.
+ * A blob packed with s = 0 runs the unscaled instantiations: the same bits as revision 10.
+ * What a scale does NOT cure: guard bit 12 (grid values / lin_z weights themselves beyond 65504).
+ * pnr_eval_ray_samples_split_train takes no PnrMlpWeights: it must be given a blob packed at s = 0 (its callers
+ * pack through a struct the other training entries check).
+ *
+ * pnr_range_probe(amax) arms the range probe for the CALLING HOST THREAD (NULL disarms), slotted like the guard:
+ * every split-operand inference launch runs a calibration instantiation that follows the fp32 values entering
+ * the (head, tail) split with v_max3_f32 and, at the end of each workgroup, does one atomic max per layer on the
+ * bit pattern of the non-negative float.  amax: DEVICE array of 2 x 12 floats (slot 0: coarse-network launches
+ * and the direct entries, slot 1: fine-network launches), zeroed by the caller:
+ *   words 0..10  largest value that entered the operand image of layer l (the numbering of the guard's bits 0..10),
+ *                in TRUE units (the kernel multiplies by 2^s)
+ *   word 11      non-zero if a network output was NaN / inf (the guard's bit 11)
+ * Downstream of a saturated layer the probe under-reports (the products used clamped heads): calibrate
+ * iteratively.  A calibration tool, not a timed path.  The guard, when armed too, keeps reporting. */
+int pnr_range_probe(float *amax_dev);
 
 /* ---- SpatialEncoder.index as a stand-alone operator ------------------------------------------
  * src/model/encoder.py:80-109 (SpatialEncoder.index): F.grid_sample(latent, uv[:, :, None], mode "bilinear",

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelne
 SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip"]
 HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_raysrc.h", "pnr_internal.h", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
-ABI_VERSION = 10  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
+ABI_VERSION = 11  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3
 PRECISIONS = {"f16": PREC_F16, "fp16": PREC_F16, "bf16": PREC_BF16, "f32": PREC_F32, "fp32": PREC_F32, "f16x3": PREC_F16X3}
 
@@ -42,7 +42,7 @@ class PnrMlpWeights(ctypes.Structure):
         ("fc0_w", ctypes.c_void_p * 5), ("fc0_b", ctypes.c_void_p * 5),
         ("fc1_w", ctypes.c_void_p * 5), ("fc1_b", ctypes.c_void_p * 5),
         ("lin_out_w", ctypes.c_void_p), ("lin_out_b", ctypes.c_void_p),
-        ("combine_max", ctypes.c_int32),
+        ("combine_max", ctypes.c_int32), ("stream_scale_log2", ctypes.c_int32),
     ]
 
 
@@ -99,6 +99,7 @@ PROTOTYPES = {
     "pnr_pyramid_to_latent": (_I, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                    ctypes.POINTER(ctypes.c_int), _I, _I, _P, _P, _P]),
     "pnr_saturation_guard": (_I, [_P]),
+    "pnr_range_probe": (_I, [_P]),
     "pnr_grid_index": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "pnr_grid_index_backward": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P, _P]),
     "pnr_positional_encoding": (_I, [_P, ctypes.c_longlong, _I, _I, _P, _P, _I, _P, _P]),

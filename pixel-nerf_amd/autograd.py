@@ -444,8 +444,19 @@ def linear_autograd(x, weight, bias=None, relu_in=False, residual=None, precisio
     return _LinearFunction.apply(x, weight, bias, residual, bool(relu_in), precision)
 
 
+def _refuse_stream_scale(net):
+    """the differentiable paths run the network unscaled: a net that renders at a stream scale cannot be trained through"""
+    scales = [int(getattr(m, "stream_scale", 0) or 0) for m in (net.mlp_coarse, net.mlp_fine) if m is not None]
+    if any(scales) and net._effective_precision() == "f16x3":
+        raise NotImplementedError(f"training through a network with a non-zero stream scale {tuple(scales)} is not implemented: the "
+                                  "scale is an inference form of precision 'f16x3' (the operand dumps, the backward chain and the "
+                                  "bias gradients would each need their own factor).  Set net.stream_scale = 0 to train, or "
+                                  "precision='f32'.")
+
+
 def points_autograd(net, xyz, viewdirs, coarse):
     """net(xyz, viewdirs) with autograd: (SB,B,3) x 2 -> (SB,B,4)."""
+    _refuse_stream_scale(net)
     if xyz.requires_grad or viewdirs.requires_grad:
         raise NotImplementedError("gradients with respect to the query points / view directions are not implemented "
                                   "(the renderer path does not need them: rays are inputs)")
@@ -462,6 +473,7 @@ def points_autograd(net, xyz, viewdirs, coarse):
 def render_autograd(renderer, net, rays, noise, want_weights):
     """Differentiable twin of the one-call inference path; returns {coarse:{...}, fine:{...}} of
     flat tensors like ops.render_forward."""
+    _refuse_stream_scale(net)
     Kf = renderer.n_fine if renderer.using_fine else 0
     cfg = dict(net=net, noise=noise, n_coarse=renderer.n_coarse, n_fine=Kf,
                n_fine_depth=min(renderer.n_fine_depth, Kf), depth_std=renderer.depth_std,

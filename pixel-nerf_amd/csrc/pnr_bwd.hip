@@ -1495,6 +1495,7 @@ extern "C" size_t pnr_packed_mlp_bwd_bytes(void) { return BPACKED_BYTES; }
 
 extern "C" int pnr_pack_mlp_bwd(const PnrMlpWeights *w, int precision, void *packed_bwd, void *stream) {
     if (!w || !packed_bwd) return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_bwd: null argument");
+    if (w->stream_scale_log2 != 0) return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_bwd: training at a stream scale (stream_scale_log2 != 0) is not supported");
     const size_t n = BWSTREAM_ELEMS_PER_WAVE / 8 * NW;  // one thread per 8 elements
     const unsigned blocks = (unsigned)((n + 255) / 256);
     if (precision == PNR_PREC_F16)

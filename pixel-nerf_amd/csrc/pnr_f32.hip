@@ -830,6 +830,7 @@ extern "C" int pnr_eval_ray_samples_f32_train(const PnrScene *scene, const PnrMl
                                               void *stream) {
     if (R <= 0 || K <= 0 || rays_per_obj <= 0 || !rays || !z) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: bad argument");
     if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: R != SB * rays_per_obj");
+    if (w && w->stream_scale_log2 != 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: training at a stream scale (stream_scale_log2 != 0) is not supported");
     pnr::EvalParams q = {};
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
     return pnr::eval_f32_train(scene, w, q, saved, (hipStream_t)stream, split_gemm != 0);
@@ -888,6 +889,7 @@ extern "C" int pnr_mlp_backward_split(const PnrMlpWeights *w, const PnrSplitSave
     using namespace pnr;
     if (!w || !g_out || !d_zlat || !workspace || !grad_scale || P <= 0 || NS <= 0)
         return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: bad argument");
+    if (w->stream_scale_log2 != 0) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: training at a stream scale (stream_scale_log2 != 0) is not supported");
     if (w->combine_max && NS > 1) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: combine_type \"max\" is an inference form (no backward)");
     if (!check_split_saved(sv)) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: null buffer in PnrSplitSaved");
     if (workspace_bytes < pnr_mlp_backward_split_workspace_bytes(P, NS)) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_split: workspace too small");
@@ -943,6 +945,7 @@ extern "C" int pnr_mlp_backward_f32(const PnrMlpWeights *w, const PnrF32Saved *s
     using namespace pnr;
     if (!w || !g_out || !d_zlat || !workspace || P <= 0 || NS <= 0)
         return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_f32: bad argument");
+    if (w->stream_scale_log2 != 0) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_f32: training at a stream scale (stream_scale_log2 != 0) is not supported");
     static const PnrMlpWeights no_grads = {};  // grads == NULL: every dW / db null, wgrad skips its launches
     if (!grads) grads = &no_grads;
     if (w->combine_max && NS > 1) return pnr_fail(PNR_E_INVALID, "pnr_mlp_backward_f32: combine_type \"max\" is an inference form (no backward)");

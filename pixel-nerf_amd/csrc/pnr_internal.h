@@ -40,6 +40,12 @@ int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long l
 // slot: 0 = coarse-network launch, 1 = fine-network launch).
 unsigned int *saturation_guard_word();
 void saturation_guard_slot(int slot);
+// range probe (pnr_range_probe): the 12 words of the armed slot (the guard's slot), or NULL = probe off
+float *range_probe_words();
+constexpr int PROBE_WORDS = 12;
+// stream scale of the split-operand blob packed at this address (0: none noted); pnr_pack_mlp_split notes it.  pnr_api.hip.
+int note_stream_scale(const void *packed, int s);
+int stream_scale_of(const void *packed);
 
 // XCDs the dispatcher deals workgroups to round-robin on the current device (hipDeviceAttributeNumberOfXccs, i.e. of the
 // current compute-partition mode: 8 in SPX, 1 in CPX; PIXELNERF_XCD_COUNT=n overrides, 0 selects the plain grid-stride

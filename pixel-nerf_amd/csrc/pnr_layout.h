@@ -96,6 +96,9 @@ constexpr size_t BIAS_BYTES = (size_t)NBIAS * NW * BIAS_FLOATS_PER_WAVE * 4;
 constexpr size_t BOUT_OFFSET_BYTES = BIAS_OFFSET_BYTES + BIAS_BYTES;
 constexpr size_t PACKED_BYTES = BOUT_OFFSET_BYTES + 32;  // lin_out bias (4 floats) | network flags word (+ pad)
 constexpr int BOUT_FLAGS_INDEX = 4;  // 32-bit word behind lin_out's bias: bit 0 = combine_type "max" (util.py:467-468)
+constexpr int BOUT_SCALE_INDEX = 5;  // next word: stream scale s (PnrMlpWeights.stream_scale_log2; split-operand blobs, else 0)
+constexpr int BOUT_LIFT_INDEX = 6;   // s > 0: lin_out's weights are packed times 2^t (pnr_pack.hip, lin_out_lift), this is t; word 7: zero
+constexpr int STREAM_SCALE_MAX = 30;
 
 // hidden feature held by D-register r of half h in feature tile T (global tile index 0..15)
 __host__ __device__ constexpr int feat_of(int T, int h, int r) {

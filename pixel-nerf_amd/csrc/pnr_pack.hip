@@ -42,6 +42,25 @@ __device__ inline GemmSrc gemm_source(const PnrMlpWeights &p, int g) {
     }
 }
 
+// Stream scale (p.stream_scale_log2 > 0, split-operand blobs): lin_out's weights are packed LIFTED by 2^t, t = the largest
+// value in [0, 30] with max |W_out| * 2^t <= 2^14, and the kernel multiplies lin_out's partial sum by 2^(s - t) instead of 2^s.
+// A network whose hidden stream is large has a correspondingly small lin_out (its outputs are O(1)): at |w| ~ 1e-6 the f16 tail
+// of w is gone and the head itself is subnormal (4 bits), which no scaling of the STREAM repairs.  Lifting is a power of two
+// applied in fp32 in front of the (head, tail) split: exact, and it only moves operand bits UP, out of the subnormals.  Every
+// thread that packs a lin_out fragment (256 of them) finds the maximum of the 2048 weights itself; pack_bias_kernel stores t.
+__device__ inline int lin_out_lift(const float *w) {
+    float m = 0.f;
+    for (int i = 0; i < D_OUT * D_HID / 4; ++i) {
+        const f32x4 a = reinterpret_cast<const f32x4_param *>(w)[i];
+        m = fmaxf(m, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
+    }
+    if (!(m > 0.f) || !(m < __builtin_huge_valf())) return 0;
+    int e;
+    frexpf(m, &e);  // m <= 2^e
+    const int t = 14 - e;
+    return t < 0 ? 0 : (t > 30 ? 30 : t);
+}
+
 // FOLD: the stream without the three lin_z GEMMs (they are folded into per-texel tables, pnr_fold_latent)
 // LO: the f16 TAIL of the weight, f16(w - f16(w)), for the split-operand kernel (pnr_split.hip)
 // One thread = one lane's 8-element fragment slice (a 16-byte store; the index arithmetic is paid once per 8 elements).
@@ -113,6 +132,11 @@ __global__ void pack_weights_kernel(PnrMlpWeights p, T *__restrict__ out, T *__r
             const float *row = src.w + i * D_HID + feat_of(wv * IT + (q >> 1), h, 8 * (q & 1));
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[e] = row[e]; v[4 + e] = row[8 + e]; }
+            if (p.stream_scale_log2 > 0) {  // (split-operand blobs only: every other pack entry refuses the field)
+                const float lift = __uint_as_float((uint32_t)(127 + lin_out_lift(src.w)) << 23);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] *= lift;
+            }
         }
     }
     __attribute__((aligned(16))) T o[8];
@@ -126,11 +150,19 @@ __global__ void pack_weights_kernel(PnrMlpWeights p, T *__restrict__ out, T *__r
     }
 }
 
+// Stream scale (split-operand blobs, p.stream_scale_log2 = s > 0): the block biases enter a stream carried at c = 2^-s, so
+// slots 1.. hold c * bias (fp32, exact); slot 0 is added in front of the kernel's x *= c and stays.  s rides in the tail.
 template <bool FOLD>
 __global__ void pack_bias_kernel(PnrMlpWeights p, float *__restrict__ bias, float *__restrict__ bout) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < D_OUT) bout[idx] = p.lin_out_b[idx];
-    if (idx == 0) reinterpret_cast<int *>(bout)[BOUT_FLAGS_INDEX] = p.combine_max ? 1 : 0;
+    if (idx == 0) {
+        int *tail = reinterpret_cast<int *>(bout);
+        tail[BOUT_FLAGS_INDEX] = p.combine_max ? 1 : 0;
+        tail[BOUT_SCALE_INDEX] = p.stream_scale_log2;
+        tail[BOUT_LIFT_INDEX] = p.stream_scale_log2 > 0 ? lin_out_lift(p.lin_out_w) : 0;
+        tail[7] = 0;
+    }
     if (idx >= NBIAS * NW * BIAS_FLOATS_PER_WAVE) return;
     const int r = idx & 15, h = (idx >> 4) & 1, it = (idx >> 5) % IT;
     const int wv = (idx / BIAS_FLOATS_PER_WAVE) % NW;
@@ -150,6 +182,7 @@ __global__ void pack_bias_kernel(PnrMlpWeights p, float *__restrict__ bias, floa
         case B_FC0_4: v = p.fc0_b[4][f]; break;
         case B_FC1_4: v = p.fc1_b[4][f]; break;
     }
+    if (slot != B_IN_Z0 && p.stream_scale_log2 > 0) v *= __uint_as_float((uint32_t)(127 - p.stream_scale_log2) << 23);
     bias[idx] = v;
 }
 
@@ -822,6 +855,9 @@ extern "C" int pnr_fold_latent_f32_rows(const PnrScene *s, const PnrMlpWeights *
 extern "C" int pnr_pack_mlp_split(const PnrMlpWeights *w, void *packed, void *stream) {
     using namespace pnr;
     if (!w || !packed) return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_split: null argument");
+    if (w->stream_scale_log2 < 0 || w->stream_scale_log2 > STREAM_SCALE_MAX)
+        return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_split: stream_scale_log2 must be in [0, 30]");
+    if (int rc = note_stream_scale(packed, w->stream_scale_log2)) return rc;  // the host picks the kernel form by the blob's address
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)RS_TOTAL_F * IT * (FRAG_ELEMS / 8) * NW;  // one thread per 8 elements
     const int threads = 256;
@@ -832,6 +868,12 @@ extern "C" int pnr_pack_mlp_split(const PnrMlpWeights *w, void *packed, void *st
     const int nb = NBIAS * NW * BIAS_FLOATS_PER_WAVE;
     hipLaunchKernelGGL(pack_bias_kernel<true>, dim3((nb + threads - 1) / threads), dim3(threads), 0, st, *w,
                        (float *)((char *)packed + BIAS_OFFSET_BYTES), (float *)((char *)packed + BOUT_OFFSET_BYTES));
+    // what no kernel writes is zeroed, so that equal parameters give equal blobs: the ring steps of the three folded lin_z GEMMs
+    // (the blob is sized for the unfolded stream) in both halves, and the tail half's bias table and 32-byte tail
+    const size_t used = (size_t)RS_TOTAL_F * IT * 1024 * NW;
+    hipError_t e = hipMemsetAsync((char *)packed + used, 0, BIAS_OFFSET_BYTES - used, st);
+    if (e == hipSuccess) e = hipMemsetAsync((char *)packed + PACKED_BYTES + used, 0, PACKED_BYTES - used, st);
+    if (e != hipSuccess) return pnr_check_hip(e, "pnr_pack_mlp_split: hipMemsetAsync");
     return pnr_check_launch("pnr_pack_mlp_split");
 }
 
@@ -841,6 +883,8 @@ template <bool FOLD>
 static int pack_mlp_impl(const PnrMlpWeights *w, int precision, void *packed, void *stream) {
     using namespace pnr;
     if (!w || !packed) return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp: null argument");
+    if (w->stream_scale_log2 != 0)
+        return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp: a stream scale (stream_scale_log2 != 0) exists for the f16x3 stream only (pnr_pack_mlp_split)");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)(FOLD ? RS_TOTAL_F : RS_TOTAL) * IT * (FRAG_ELEMS / 8) * NW;  // one thread per 8 elements
     const int threads = 256;

@@ -21,7 +21,7 @@
 // are B fragments as they are), while the same fragments go to the operand images for the other waves: stage_own / gemm_split_rot.
 //
 // Kernels of this file:
-//   eval_split_kernel<RAYS, MV, TIMING, TRAIN, GUARD>   the fused network.  GUARD = the fp16-range guard (pnr_saturation_guard): the
+//   eval_split_kernel<RAYS, MV, TIMING, TRAIN, GUARD, SC>   the fused network (SC: the stream-scale / range-probe forms, below).  GUARD = the fp16-range guard (pnr_saturation_guard): the
 //                                                same bits, plus one flag bit per layer whose operand image received a value >= 65504.
 //                                                TRAIN = the fp32-class TRAINING forward: the same launch also
 //                                                copies every wide linear's (head, tail) operand image out of LDS (relu(x) /
@@ -468,9 +468,9 @@ __device__ __forceinline__ void gather_table_f32(const EvalParams &q, char *smem
     }
 }
 
-// x += this lane's slots of the fp32 table rows
-template <typename ST, int JT>
-__device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *smem, int pl, int h, int wv) {
+// x += this lane's slots of the fp32 table rows (SCALED: x += c * t, one FMA: the stream is carried at c = 2^-s, the tables are not)
+template <typename ST, bool SCALED = false, int JT>
+__device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *smem, int pl, int h, int wv, [[maybe_unused]] float c = 1.f) {
 #pragma unroll
     for (int it = 0; it < IT; ++it)
 #pragma unroll
@@ -480,7 +480,10 @@ __device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *
             for (int k = 0; k < 4; ++k) {
                 const f32x4 t = *reinterpret_cast<const f32x4 *>(row + 16 * k);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) x[it][jt][4 * k + e] += t[e];
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (SCALED) x[it][jt][4 * k + e] = __builtin_fmaf(c, t[e], x[it][jt][4 * k + e]);
+                    else x[it][jt][4 * k + e] += t[e];
+                }
             }
         }
 }
@@ -492,10 +495,36 @@ __device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *
 // of weights the same view streams.  (Round 2 ran multi-view scenes on 32-point tiles with the sum in registers: twice the
 // weight stream per point, 105-147 k rays/s.)  Fixed summation order (view 0 + view 1) + ...: bit-identical to the
 // in-register form.
-template <bool RAYS, bool MV, bool TIMING = false, bool TRAIN = false, bool GUARD = false>
+//
+// SC: the stream scale (PnrMlpWeights.stream_scale_log2 = s, word BOUT_SCALE_INDEX of the blob's tail).  SC = 0 is the kernel as
+// it always was (blobs packed at s = 0: the same instructions).  SC = 1 carries x and net at c = 2^-s:
+//   x *= c behind lin_in + table 0 | x += c t for tables 1, 2 | block biases arrive as c b (pack_bias_kernel) |
+//   the lin_out partial sum times 2^(s - t) in front of lin_out's bias (t: the lift lin_out's weights were packed with, pnr_pack.hip)
+// -- four fp32 sites, all exact; nothing stored as fp16 is shifted, the hidden weights are untouched, view pooling (mean and
+// max) is homogeneous.  SC = 2: the same with the range probe (pnr_range_probe): the fp32 values about to enter split8 -- the
+// accumulator tiles a stage_own / lin_out is about to split -- are followed with v_max3_f32 in FRONT of the stage (relu'd: the
+// running maximum starts at 0), the round-5 form of the guard; it says how far beyond the range a value went, which saturated
+// heads cannot.  Per-layer maxima are collected in 12 LDS words behind the tile map (non-negative floats order like their bit
+// patterns: ds_max_u32), one global atomic max per layer and workgroup at the end, in true units (times 2^s).  The stages
+// themselves are the guarded scaled kernel's, instruction for instruction: the probe keeps the guard's bits and its result.
+template <bool RAYS, bool MV, bool TIMING = false, bool TRAIN = false, bool GUARD = false, int SC = 0>
 __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const EvalParams q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef SplitTileT<64> ST;
+    constexpr bool PROBE = SC == 2;
+    static_assert(!(SC && (TRAIN || TIMING || !GUARD)), "the stream scale is an inference form, instantiated with the guard on");
+    [[maybe_unused]] float sc_c = 1.f, sc_inv = 1.f, sc_out = 1.f;
+    if constexpr (SC != 0) {
+        const int s = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(q.bout)[BOUT_SCALE_INDEX]);
+        const int t = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int *>(q.bout)[BOUT_LIFT_INDEX]);
+        sc_c = __builtin_bit_cast(float, (uint32_t)(127 - s) << 23);
+        sc_inv = __builtin_bit_cast(float, (uint32_t)(127 + s) << 23);
+        sc_out = __builtin_bit_cast(float, (uint32_t)(127 + s - t) << 23);  // s, t in [0, 30]
+    }
+    [[maybe_unused]] uint32_t *probe_lds = reinterpret_cast<uint32_t *>(smem + ST::LDS_TOTAL);
+    if constexpr (PROBE) {
+        if (threadIdx.x < PROBE_WORDS) probe_lds[threadIdx.x] = 0u;  // (published by the tile loop's first barrier)
+    }
     constexpr int JT = ST::JT, MT = ST::MT;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -582,6 +611,22 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             amax = 0u;
         }
     };
+    // PROBE: the largest relu'd value of the accumulator tiles a stage is about to split -> LDS word `layer`.  One LDS max per
+    // lane, straight-line (an atomicMax() becomes a branch + a wave-reduction loop); the file has no static LDS, so the dynamic
+    // block starts at LDS address 0.  NaNs are skipped (fmaxf); an inf arrives as inf.
+    [[maybe_unused]] auto probe_note = [&](const f32x16 (&a)[IT][JT], int layer) {
+        if constexpr (PROBE) {
+            float m = 0.f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it)
+#pragma unroll
+                for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) m = fmaxf(fmaxf(m, a[it][jt][r]), a[it][jt][r + 1]);
+            const uint32_t ad = ST::LDS_TOTAL + 4u * (uint32_t)layer;
+            asm volatile("ds_max_u32 %0, %1" : : "v"(ad), "v"(m) : "memory");
+        }
+    };
     [[maybe_unused]] auto own_mark = [&](int ph) { PNR_T(ph); };
     // one residual block on x (resnetfc.py:66-88); lookup: lin_z[b+1] via table b+1 behind it.
     // Every 512-wide linear = stage_own (split epilogue + this wave's own K block, from registers) | barrier | gemm_split_rot
@@ -594,6 +639,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             add_bias<true>(net, bias_lane, 1 + 2 * b);
             if constexpr (TIMING) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the bias has ARRIVED when the stage's clock starts (diagnostic: also drains the ring)
             own_mark(PH_OWN_BIAS);
+            probe_note(x, 2 * b);
             stage_own<ST, JT, GUARD>(net, x, smem, a_wr, R, NS, &amax, own_mark);                  // fc_0, own block
             sat_note(2 * b);
             PNR_T(PH_WRITE_X);
@@ -607,6 +653,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             PNR_T(PH_BAR3);
             add_bias<false>(x, bias_lane, 2 + 2 * b);
             own_mark(PH_OWN_BIAS);
+            probe_note(net, 2 * b + 1);
             stage_own<ST, JT, GUARD>(x, net, smem, a_wr, R, NS, &amax, own_mark);                  // fc_1, own block
             sat_note(2 * b + 1);
             PNR_T(PH_WRITE_NET);
@@ -620,7 +667,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             __syncthreads();
             gather_table_f32<2, ST>(q, smem, wv, lane, b + 1);
             __syncthreads();
-            add_from_table<ST>(x, smem, pl, h, wv);
+            add_from_table<ST, SC != 0>(x, smem, pl, h, wv, sc_c);
             PNR_T(PH_TABLE);
         }
     };
@@ -648,6 +695,12 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             gemm_split(x, smem, in_rd0, 32 * ROW_IN, ST::IN_LO_DELTA, KS_IN / 4, R, NS);  // lin_in   resnetfc.py:147
             __syncthreads();  // table rows of every wave are in place
             add_from_table<ST>(x, smem, pl, h, wv);                                           // lin_z[0] via table 0
+            if constexpr (SC != 0) {  // from here on the stream is c x
+#pragma unroll
+                for (int it = 0; it < IT; ++it)
+#pragma unroll
+                    for (int jt = 0; jt < JT; ++jt) x[it][jt] *= sc_c;
+            }
             PNR_T(PH_GEMM_IN_Z0);
             if constexpr (TRAIN) {
                 tr_rows_pooled = (long long)tile * MT;
@@ -693,6 +746,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
         }
 
         // lin_out(relu(x)): each wave contracts its own 64 features (the wave's accumulators are the B operand)
+        probe_note(x, 10);
         {
             f32x16 o[JT];
 #pragma unroll
@@ -738,9 +792,17 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
         PNR_T(PH_BAR_OUT);
         if (tid < MT) {
             const long long g = (long long)tile * MT + tid;
-            f32x4 s = *reinterpret_cast<const f32x4 *>(q.bout);
+            f32x4 s;
+            if constexpr (SC != 0) {  // the partials are at scale c 2^t: undone in front of lin_out's bias
+                s = *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + tid * 16);
 #pragma unroll
-            for (int w = 0; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + (w * MT + tid) * 16);
+                for (int w = 1; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + (w * MT + tid) * 16);
+                s = s * sc_out + *reinterpret_cast<const f32x4 *>(q.bout);
+            } else {
+                s = *reinterpret_cast<const f32x4 *>(q.bout);
+#pragma unroll
+                for (int w = 0; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + (w * MT + tid) * 16);
+            }
             // models.py:260-265: rgb = sigmoid(out[:3]), sigma = relu(out[3])
             f32x4 res = {1.f / (1.f + expf(-s[0])), 1.f / (1.f + expf(-s[1])), 1.f / (1.f + expf(-s[2])), fmaxf(s[3], 0.f)};
             if (g < q.P) {
@@ -755,6 +817,15 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
     }
     if constexpr (GUARD) {
         if (sat_bits && q.sat_flag) atomicOr(q.sat_flag, sat_bits);
+    }
+    if constexpr (PROBE) {
+        if (sat_bits & (1u << 11)) probe_lds[11] = 0x3F800000u;  // (every writer stores the same word)
+        __syncthreads();
+        if (tid < PROBE_WORDS) {
+            const uint32_t m = probe_lds[tid];
+            const float v = tid < 11 ? __builtin_bit_cast(float, m) * sc_inv : __builtin_bit_cast(float, m);  // true units
+            if (m) atomicMax(q.probe + tid, __builtin_bit_cast(uint32_t, v));
+        }
     }
 }
 
@@ -1091,23 +1162,39 @@ static int split_launch(const PnrScene *s, const void *packed, const void *table
     if (guard)
         k = mv ? (rays ? eval_split_kernel<true, true, false, false, true> : eval_split_kernel<false, true, false, false, true>)
                : (rays ? eval_split_kernel<true, false, false, false, true> : eval_split_kernel<false, false, false, false, true>);
+    // stream scale (blobs packed at s > 0, noted by pnr_pack_mlp_split) and the range probe (armed on this host thread, any s)
+    const int scale = stream_scale_of(packed);
+    float *probe = range_probe_words();
+    q.probe = reinterpret_cast<unsigned int *>(probe);
+    int lds_extra = 0;
+    if (probe && !q.f_x5) {
+        k = mv ? (rays ? eval_split_kernel<true, true, false, false, true, 2> : eval_split_kernel<false, true, false, false, true, 2>)
+               : (rays ? eval_split_kernel<true, false, false, false, true, 2> : eval_split_kernel<false, false, false, false, true, 2>);
+        lds_extra = 64;  // the probe's 12 words behind the tile map
+    } else if (scale) {
+        k = mv ? (rays ? eval_split_kernel<true, true, false, false, true, 1> : eval_split_kernel<false, true, false, false, true, 1>)
+               : (rays ? eval_split_kernel<true, false, false, false, true, 1> : eval_split_kernel<false, false, false, false, true, 1>);
+    }
     if (q.f_x5) {  // training forward: the same kernel + fp32 rows of what the backward keeps
+        if (scale) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: training at a stream scale is not supported (pack the blob with stream_scale_log2 = 0)");
         if (!rays) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: the training instantiation takes ray samples on 64-point tiles");
         k = mv ? (guard ? eval_split_kernel<true, true, false, true, true> : eval_split_kernel<true, true, false, true>)
                : (guard ? eval_split_kernel<true, false, false, true, true> : eval_split_kernel<true, false, false, true>);
     }
 #ifdef PNR_VARIANT
     if (q.tim) {  // diagnostic instantiation (pnr_debug_phase_timing_split): single view, rays
+        if (scale || probe) return pnr_fail(PNR_E_INVALID, "phase timing: unscaled blobs, probe disarmed");
         if (mv || !rays) return pnr_fail(PNR_E_INVALID, "phase timing: single-view ray launches only");
         k = eval_split_kernel<true, false, true>;
     }
 #endif
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    static_assert(SplitTileT<64>::LDS_TOTAL + 64 <= 160 * 1024 && PROBE_WORDS * 4 <= 64, "room for the probe's words");
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds + lds_extra);
     if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(eval_split_kernel)");
     {
         q.n_xcd = device_xcd_count();
         ProfileScope prof(st);  // HIP events around the launch on ITS stream when pnr_profile_enable(1) is active
-        hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, q);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds + lds_extra, st, q);
     }
     return pnr_check_launch("eval_split_kernel");
 }

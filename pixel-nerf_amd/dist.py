@@ -206,6 +206,9 @@ class ShardedRenderWrapper(torch.nn.Module):
 
     def forward(self, rays, want_weights=False):
         net = getattr(self.wrapped, "net", None)
+        if net is not None:  # an integer stream scale passes through; an automatic one would differ from rank to rank
+            from .render.nerf import _check_scale_resolved
+            _check_scale_resolved(net, "ShardedRenderWrapper")
         training = (net is not None and torch.is_grad_enabled()
                     and (any(p.requires_grad for p in net.parameters())
                          or (torch.is_tensor(getattr(getattr(net, "encoder", None), "latent", None)) and net.encoder.latent.requires_grad)))

@@ -23,7 +23,7 @@ from .model_util import make_encoder, make_mlp
 
 
 class PixelNeRFNet(torch.nn.Module):
-    def __init__(self, conf, stop_encoder_grad=False, precision="f16x3", fold=True):
+    def __init__(self, conf, stop_encoder_grad=False, precision="f16x3", fold=True, stream_scale=0):
         """:param conf PyHocon-like config subtree 'model' (util.Conf or a real ConfigTree)
         :param precision arithmetic of the 512-wide linears:
         'f16x3' (default) -- fp32-CLASS on the f16 matrix cores: every operand a (head, tail) fp16 pair, 3 MFMAs per product, fp32
@@ -36,7 +36,11 @@ class PixelNeRFNet(torch.nn.Module):
         'bf16' -- experiment flag only: 8-bit significands are not enough for surface-like densities (33 dB on the
         adversarial fixtures); not a supported product precision.
         :param fold inference applies lin_z[b] to the encoded grid once per scene (per-texel tables) instead of
-        once per sample -- the same function by linearity, 22-28 % fewer FLOPs per sample (ops.fold_latent)."""
+        once per sample -- the same function by linearity, 22-28 % fewer FLOPs per sample (ops.fold_latent).
+        :param stream_scale precision 'f16x3' inference, for checkpoints whose hidden activations leave the fp16 range (the
+        guard's warning): 0 (default, today's behaviour), an integer s in [0, 30] -- both networks carry their hidden stream at
+        2**-s --, or "auto" -- the first inference call after the weights or the scene changed waits for the guard's verdict and
+        calibrates on its own rays if needed (see `stream_scale` / calibrate_stream_scale below).  Not part of state_dict()."""
         super().__init__()
         self.encoder = make_encoder(conf["encoder"])
         self.use_encoder = conf.get_bool("use_encoder", True)
@@ -83,6 +87,105 @@ class PixelNeRFNet(torch.nn.Module):
         self._tables = {}
         self._sparse_tables = {}  # training_tables(): persistent buffers of the row-wise fold
         self._grad_sync = None  # set for the duration of a call by dist.ShardedRenderWrapper (gradient all-reduce across ranks)
+        self._stream_auto = None  # None: fixed scales | "pending": "auto", not resolved yet | "resolved": "auto", scales chosen
+        self.stream_scale = stream_scale
+
+    # ---- stream scale of precision 'f16x3' (include/pixelnerf_hip.h "stream scale"; ops.pack_mlp).  Stored per network on the
+    # ResnetFCs (ResnetFC.stream_scale, part of the key of their packed() cache), never in state_dict().
+    def _mlps(self):
+        return [m for m in (self.mlp_coarse, self.mlp_fine) if m is not None]
+
+    @property
+    def stream_scale(self):
+        """"auto" while an automatic scale is unresolved, else (s_coarse, s_fine) -- s_fine repeats s_coarse when mlp_fine is None.
+        Settable: 0 | int (both networks) | (s_coarse, s_fine) | "auto"."""
+        if self.__dict__.get("_stream_auto") == "pending":
+            return "auto"
+        sc = int(getattr(self.mlp_coarse, "stream_scale", 0))
+        return (sc, sc if self.mlp_fine is None else int(getattr(self.mlp_fine, "stream_scale", 0)))
+
+    @stream_scale.setter
+    def stream_scale(self, value):
+        if isinstance(value, str):
+            if value != "auto":
+                raise ValueError(f"stream_scale: expected 0, an integer in [0, {ops.STREAM_SCALE_MAX}], a pair of them or 'auto', got {value!r}")
+            pair, auto = (0, 0), "pending"
+        elif isinstance(value, (tuple, list)):
+            if len(value) != 2:
+                raise ValueError("stream_scale: a pair is (s_coarse, s_fine)")
+            pair, auto = (ops.check_stream_scale(value[0]), ops.check_stream_scale(value[1])), None
+        else:
+            pair, auto = (ops.check_stream_scale(value),) * 2, None
+        self.mlp_coarse.stream_scale = pair[0]
+        if self.mlp_fine is not None:
+            self.mlp_fine.stream_scale = pair[1]
+        self.__dict__["_stream_auto"] = auto
+
+    def stream_scale_resolved(self):
+        """False only for an "auto" that no inference call / calibrate_stream_scale has resolved yet"""
+        return self.__dict__.get("_stream_auto") != "pending"
+
+    def calibrate_stream_scale(self, rays=None, xyz=None, viewdirs=None, renderer=None, _restart=True):
+        """Choose the stream scale of both networks on a batch of the ENCODED scene: either `rays` (SB,B,8) with the
+        `renderer` (NeRFRenderer) they will be rendered with, or points `xyz` + `viewdirs` (SB,B,3).  The batch is rendered
+        under the range probe (ops.range_probe_*), every network takes the smallest s that brings the largest of its 11 probed
+        maxima to <= 16384 (ops.stream_scale_for), the networks are re-packed and probed again -- downstream of a saturated layer
+        a probe under-reports, so the scales only grow from pass to pass.  Stops when a probe at the chosen scales stays at or below
+        16384 with finite outputs (the guard's eleven layer bits are implied: it fires at 65488), or after 6 passes with an
+        error that prints the maxima.  One host synchronisation per pass; not during stream capture.  -> (s_coarse, s_fine)."""
+        import math
+        if self._effective_precision() != "f16x3":
+            raise ValueError("calibrate_stream_scale: the stream scale belongs to precision 'f16x3' (precision='f32' needs none)")
+        self._check_supported()
+        if (rays is None) == (xyz is None) or (rays is not None and renderer is None) or (xyz is not None and viewdirs is None):
+            raise ValueError("calibrate_stream_scale: pass rays= and renderer=, or xyz= and viewdirs=")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("calibrate_stream_scale synchronises with the host: call it outside stream capture")
+        dev = self.encoder.latent.device
+        mlps = self._mlps()
+        if _restart:
+            for m in mlps:
+                m.stream_scale = 0
+        self.__dict__["_calibrating"] = True
+        log = []
+        try:
+            for _ in range(6):
+                ops.range_probe_arm(dev)
+                try:
+                    with torch.no_grad():
+                        if rays is not None:
+                            renderer(self, rays)
+                        else:
+                            self._forward_points(xyz, True, viewdirs)
+                            if self.mlp_fine is not None:
+                                self._forward_points(xyz, False, viewdirs)
+                finally:
+                    ops.range_probe_disarm(dev)
+                words = ops.range_probe_read(dev)  # the pass's one synchronisation
+                self.__dict__["_probe_passes"] = self.__dict__.get("_probe_passes", 0) + 1
+                log.append((tuple(m.stream_scale for m in mlps), words[: len(mlps)]))
+                settled = True
+                for m, w in zip(mlps, words):
+                    amax = max(w[:11])
+                    if not all(math.isfinite(v) for v in w[:11]):
+                        raise RuntimeError(f"calibrate_stream_scale: a probed maximum is not finite -- no stream scale cures that: {w[:11]}")
+                    need = ops.stream_scale_for(amax)
+                    if need > m.stream_scale:
+                        m.stream_scale, settled = need, False
+                    elif w[11] != 0.0:
+                        settled = False  # a non-finite output at a scale the maxima fit: look again, then give up below
+                if settled:
+                    self.__dict__["_probe_log"] = log
+                    if self.__dict__.get("_stream_auto") == "pending":
+                        self.__dict__["_stream_auto"] = "resolved"
+                    return self.stream_scale
+        finally:
+            self.__dict__["_calibrating"] = False
+            # the guard rode along: verdicts of the calibration's own (saturated) passes are not findings.  Everything on the
+            # stream is done after the probe read, so this wait returns at once.
+            ops.saturation_guard_poll(dev, wait=True, owner=id(self))
+        raise RuntimeError("calibrate_stream_scale: no scale settled in 6 passes; (scales, probed maxima per network) of every pass: "
+                           + "; ".join(f"{sc}: {[[float('%.4g' % v) for v in w] for w in ws]}" for sc, ws in log))
 
     def __getstate__(self):
         # copies / pickles (copy.deepcopy for EMA or replica nets, torch.save(net)) carry parameters, buffers and encode() state;
@@ -246,7 +349,10 @@ class PixelNeRFNet(torch.nn.Module):
         import os
         if torch.cuda.is_current_stream_capturing():
             return False  # (no Event.query() during a capture either: pending verdicts are reported by the next eager call)
-        self._guard_report()
+        if self.__dict__.get("_calibrating"):  # verdicts of a calibration's own (saturated) passes are not findings
+            ops.saturation_guard_poll(self.encoder.latent.device, owner=id(self))
+        else:
+            self._guard_report()
         if self._effective_precision() != "f16x3":
             return False
         mode = os.environ.get("PIXELNERF_SATURATION_GUARD", "auto")
@@ -254,7 +360,7 @@ class PixelNeRFNet(torch.nn.Module):
             return False
         mlps = [m for m in (self.mlp_coarse, self.mlp_fine) if m is not None]
         lat = self.encoder.latent
-        key = (tuple(m._fingerprint() for m in mlps), lat.data_ptr(), lat._version, tuple(lat.shape))
+        key = self._guard_keyval()
         n = self.__dict__.get("_guard_calls", 0)
         self.__dict__["_guard_calls"] = n + 1
         # (training: the weights change every step -- the key would fire every time; every 16th call instead)
@@ -262,9 +368,41 @@ class PixelNeRFNet(torch.nn.Module):
                or (not training and (mode != "sample" or key != self.__dict__.get("_guard_key"))))
         if not due:
             return False
+        # stream_scale="auto": the first inference call on new weights / a new scene WAITS for its verdict (_auto_resolve)
+        self.__dict__["_auto_first"] = (not training and self.__dict__.get("_stream_auto") is not None
+                                        and not self.__dict__.get("_calibrating") and key != self.__dict__.get("_guard_key"))
         self.__dict__["_guard_key"] = key
         ops.saturation_guard_arm(lat.device, owner=id(self))
         return True
+
+    def _guard_keyval(self):
+        mlps = self._mlps()
+        lat = self.encoder.latent
+        key = (tuple(m._fingerprint() for m in mlps), lat.data_ptr(), lat._version, tuple(lat.shape))
+        scales = tuple(int(getattr(m, "stream_scale", 0)) for m in mlps)
+        return key + (scales,) if any(scales) else key
+
+    def _auto_resolve(self, **batch):
+        """stream_scale="auto", after the guarded FIRST call on new weights / a new scene (_guard_begin): wait for its verdict
+        (the one host synchronisation of the automatic mode); saturated layers -> calibrate on that call's own batch.
+        -> True when the caller must render the call again (its first result was out of class and is not to be delivered)."""
+        if not self.__dict__.pop("_auto_first", False):
+            return False
+        dev = self.encoder.latent.device
+        got = ops.saturation_guard_poll(dev, wait=True, owner=id(self))
+        self.__dict__["_auto_syncs"] = self.__dict__.get("_auto_syncs", 0) + 1
+        bits = (0, 0) if got is None else got
+        other = (bits[0] & ~0x7FF, bits[1] & ~0x7FF)  # non-finite outputs, the fold's range bit: no scale cures those
+        redo = False
+        if (bits[0] | bits[1]) & 0x7FF:
+            self.calibrate_stream_scale(_restart=False, **batch)
+            self.__dict__["_guard_key"] = self._guard_keyval()  # the re-render is this same first call, not a new one
+            other = (other[0] & ~0x800, other[1] & ~0x800)  # (a non-finite output of the saturated pass is not a finding)
+            redo = True
+        self.__dict__["_stream_auto"] = "resolved"
+        if other[0] or other[1]:
+            self._guard_warn(other)
+        return redo
 
     def _guard_end(self):
         ops.saturation_guard_disarm(self.encoder.latent.device, owner=id(self))
@@ -275,12 +413,32 @@ class PixelNeRFNet(torch.nn.Module):
             return None
         got = ops.saturation_guard_poll(lat.device, wait=wait, owner=id(self))
         if got is not None and (got[0] or got[1]):
-            parts = [f"{name} network: {ops.describe_saturation(b)}" for name, b in (("coarse", got[0]), ("fine", got[1])) if b]
-            warnings.warn("pixelnerf_amd (precision 'f16x3'): hidden activations reached the fp16 range limit of 65504 -- "
-                          + "; ".join(parts) + ".  Operand heads saturate there, so these renders are NOT within the fp32-class "
-                          "tolerance of the reference; use make_model(conf, precision='f32') (exact, slower) for this checkpoint.",
-                          RuntimeWarning, stacklevel=3)
+            raised = None
+            if self.__dict__.get("_stream_auto") is not None and (got[0] | got[1]) & 0x7FF:
+                # automatic mode, a LATER batch saturated on its own: its render is out (it was out of class), the following
+                # calls run two more bits down -- and the next one is a "first" call again (the scales are part of the guard key)
+                raised = []
+                for m, b in zip((self.mlp_coarse, self.mlp_fine), got):
+                    if m is not None and b & 0x7FF:
+                        m.stream_scale = min(int(m.stream_scale) + 2, ops.STREAM_SCALE_MAX)
+                        raised.append(m.stream_scale)
+            self._guard_warn(got, raised)
         return got
+
+    def _guard_warn(self, got, raised=None):
+        parts = [f"{name} network: {ops.describe_saturation(b)}" for name, b in (("coarse", got[0]), ("fine", got[1])) if b]
+        curable = (got[0] | got[1]) & 0x7FF
+        if raised is not None:
+            tail = (f"  stream_scale='auto': that EARLIER render was out of class; the stream scale was raised to {self.stream_scale} "
+                    "for the following calls.")
+        elif curable:
+            tail = ("  Use make_model(conf, precision='f16x3', stream_scale='auto') (or net.calibrate_stream_scale) to carry the "
+                    "hidden stream at a power-of-two scale, or precision='f32' (exact, slower) for this checkpoint.")
+        else:
+            tail = "  Use make_model(conf, precision='f32') (exact, slower) for this checkpoint."
+        warnings.warn("pixelnerf_amd (precision 'f16x3'): hidden activations reached the fp16 range limit of 65504 -- "
+                      + "; ".join(parts) + ".  Operand heads saturate there, so these renders are NOT within the fp32-class "
+                      "tolerance of the reference." + tail, RuntimeWarning, stacklevel=4)
 
     def __del__(self):
         try:
@@ -367,16 +525,23 @@ class PixelNeRFNet(torch.nn.Module):
                                           "GEMMs) or 'f32' (exact fp32 validation path)")
             from .. import autograd
             return autograd.points_autograd(self, xyz, viewdirs.reshape(SB, B, 3), coarse)
-        pk = self.packed(coarse)
-        tab = self.tables(coarse)
-        guarded = self._guard_begin()
-        try:
-            if guarded:
-                ops.saturation_guard_slot(xyz.device, 0 if (coarse or self.mlp_fine is None) else 1)
-            return ops.eval_points(sc, pk, xyz.float(), viewdirs.reshape(SB, B, 3).float(), tables=tab)
-        finally:
-            if guarded:
-                self._guard_end()
+        slot = 0 if (coarse or self.mlp_fine is None) else 1
+        for _ in range(2):  # (twice only for stream_scale="auto" when the first call on new weights saturated: _auto_resolve)
+            pk = self.packed(coarse)
+            tab = self.tables(coarse)
+            guarded = self._guard_begin()
+            try:
+                if guarded:
+                    ops.saturation_guard_slot(xyz.device, slot)
+                if self.__dict__.get("_calibrating"):
+                    ops.range_probe_slot(xyz.device, slot)
+                out = ops.eval_points(sc, pk, xyz.float(), viewdirs.reshape(SB, B, 3).float(), tables=tab)
+            finally:
+                if guarded:
+                    self._guard_end()
+            if not (guarded and self._auto_resolve(xyz=xyz, viewdirs=viewdirs)):
+                break
+        return out
 
     # ------------------------------------------------------------------ checkpoints
     # file layout of the reference's trainer (src/model/models.py:268-316): <checkpoints_path>/<name>/pixel_nerf_{latest,init}

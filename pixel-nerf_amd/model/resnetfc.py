@@ -110,6 +110,9 @@ class ResnetFC(nn.Module):
             if use_spade:
                 self.scale_z = per_block()
         self.activation = nn.Softplus(beta=beta) if beta > 0 else nn.ReLU()
+        # "f16x3" inference carries the hidden stream at 2 ** -stream_scale (ops.pack_mlp; PixelNeRFNet.stream_scale sets it).
+        # A plain attribute: not part of state_dict(), the reference's checkpoints load unchanged.
+        self.stream_scale = 0
         self.composed_precision = "f16x3"  # arithmetic of the per-Linear operators of a non-shipped shape ('f16x3' | 'f32')
         self._packed = {}
 
@@ -260,8 +263,18 @@ class ResnetFC(nn.Module):
             raise NotImplementedError(
                 "fused HIP network supports d_in=42, d_latent=512, d_hidden=512, n_blocks=5, "
                 "combine_layer=3, combine_type average | max (conf/default_mv.conf); got a different ResnetFC")
-        return self._cached((precision, bool(folded)), precision,
-                            lambda out: ops.pack_mlp(None, precision, folded=folded, weights=self._wstruct(), out=out), training_pass)
+        scale = ops.check_stream_scale(self.__dict__.get("stream_scale", 0), "ResnetFC.stream_scale") if precision == "f16x3" else 0
+        if scale and training_pass:
+            raise NotImplementedError("training at a stream scale is not implemented (ResnetFC.stream_scale = %d): the scale is an "
+                                      "inference form of precision 'f16x3'; set stream_scale = 0 to train" % scale)
+        return self._cached(self._packed_key(precision, folded, scale), precision,
+                            lambda out: ops.pack_mlp(None, precision, folded=folded, weights=self._wstruct(), out=out, stream_scale=scale),
+                            training_pass)
+
+    @staticmethod
+    def _packed_key(precision, folded, scale=0):
+        """key of packed()'s cache: a stream scale is part of it (an unscaled stream keeps its historical key)"""
+        return (precision, bool(folded)) + ((scale,) if scale else ())
 
     def _cached(self, key, precision, build, training_pass=False):
         """entry = [fingerprint, stream, content fingerprint recorded?, times served from the cache].

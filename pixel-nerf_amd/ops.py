@@ -43,9 +43,10 @@ class PackedMLP:
     """A ResnetFC's parameters repacked into the fused kernel's fragment stream.
     precision "f32" (exact validation path) keeps the raw nn.Linear tensors instead."""
 
-    def __init__(self, buf, precision, weights=None, folded=False):
+    def __init__(self, buf, precision, weights=None, folded=False, stream_scale=0):
         self.buf = buf
         self.precision = precision
+        self.stream_scale = stream_scale  # "f16x3" only: the hidden stream is carried at 2^-stream_scale (pack_mlp)
         self.weights = weights  # f32 only: (PnrMlpWeights, {key: tensor} keeping the storage alive)
         self.folded = folded    # stream without the lin_z GEMMs: must be used with fold_latent() tables
 
@@ -95,8 +96,40 @@ def _weights_struct(state, combine_max=False):
     return w, keep
 
 
-def pack_mlp(state, precision="f16", backward=False, folded=False, weights=None, out=None, combine_max=False):
-    """state: {reference ResnetFC state_dict key: float32 HIP tensor}
+STREAM_SCALE_MAX = 30
+
+
+def check_stream_scale(s, what="stream_scale"):
+    """an integer in [0, 30] (bools and floats are refused: 2 ** -s is what the kernel applies)"""
+    if isinstance(s, bool) or not isinstance(s, int):
+        raise TypeError(f"{what}: expected an integer in [0, {STREAM_SCALE_MAX}], got {s!r}")
+    if not 0 <= s <= STREAM_SCALE_MAX:
+        raise ValueError(f"{what}: expected an integer in [0, {STREAM_SCALE_MAX}], got {s}")
+    return s
+
+
+def stream_scale_for(amax):
+    """The smallest s >= 0 with amax * 2**-s <= 16384: two bits of headroom under the fp16 limit of 65504 for ray batches a
+    calibration did not see.  Host arithmetic only.  amax: the largest hidden value a range probe reported (true units)."""
+    import math
+    amax = float(amax)
+    if not math.isfinite(amax):
+        raise ValueError(f"stream_scale_for: the probed maximum is not finite ({amax}): no stream scale cures that")
+    if amax < 0:
+        raise ValueError(f"stream_scale_for: a maximum of relu'd values cannot be negative ({amax})")
+    s = 0
+    while math.ldexp(amax, -s) > 16384.0:
+        s += 1
+    if s > STREAM_SCALE_MAX:
+        raise ValueError(f"stream_scale_for: {amax:g} needs a scale of {s} bits (the limit is {STREAM_SCALE_MAX})")
+    return s
+
+
+def pack_mlp(state, precision="f16", backward=False, folded=False, weights=None, out=None, combine_max=False, stream_scale=0):
+    """stream_scale: "f16x3" only -- carry the hidden stream at 2**-stream_scale of its value (include/pixelnerf_hip.h,
+    "stream scale"): for networks whose hidden activations leave the fp16 range.  0 = off (the same blob as without it).
+    Every other precision, and backward=True, refuses a non-zero value.
+    state: {reference ResnetFC state_dict key: float32 HIP tensor}
     (src/model/resnetfc.py:66-130: lin_in, lin_out, blocks.N.fc_0/fc_1, lin_z.N).
     backward=True packs the transposed streams of the data-gradient chain instead;
     folded=True packs the inference stream without the lin_z GEMMs (use with fold_latent).
@@ -105,6 +138,14 @@ def pack_mlp(state, precision="f16", backward=False, folded=False, weights=None,
     lib = _lib.load()
     prec = _lib.PRECISIONS[precision] if isinstance(precision, str) else int(precision)
     w, keep = weights if weights is not None else _weights_struct(state, combine_max)
+    stream_scale = check_stream_scale(stream_scale)
+    if stream_scale:
+        if prec == _lib.PREC_F32:
+            stream_scale = 0  # the exact path needs no scale
+        else:
+            # (a copy: `weights` may be a cached struct that other precisions pack from)
+            w = _lib.PnrMlpWeights.from_buffer_copy(w)
+            w.stream_scale_log2 = stream_scale
     if prec == _lib.PREC_F32:
         if backward:
             raise _lib.PixelNerfHipError("precision='f32' has no backward path")
@@ -117,7 +158,7 @@ def pack_mlp(state, precision="f16", backward=False, folded=False, weights=None,
         buf = torch.empty(lib.pnr_packed_mlp_split_bytes(), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.pnr_pack_mlp_split(ctypes.byref(w), _p(buf), _stream()), "pnr_pack_mlp_split")
-        return PackedMLP(buf, prec, folded=True)
+        return PackedMLP(buf, prec, folded=True, stream_scale=stream_scale)
     if backward and folded:
         raise ValueError("the backward streams have no folded form")
     nbytes = lib.pnr_packed_mlp_bwd_bytes() if backward else lib.pnr_packed_mlp_bytes()
@@ -810,6 +851,47 @@ def saturation_guard_poll(device, wait=False, owner=None):
 
 def describe_saturation(bits):
     return ", ".join(SAT_LAYER_NAMES[i] for i in range(len(SAT_LAYER_NAMES)) if bits >> i & 1)
+
+
+# ---------------------------------------------------------------- range probe of the same kernels (calibration of a stream scale)
+# include/pixelnerf_hip.h, pnr_range_probe: while armed, the split-operand inference kernels run a calibration instantiation
+# that reports, per network slot, the largest value that entered each of the 11 operand images (true units) + a non-finite mark.
+_PROBE = {}
+PROBE_WORDS = 12
+
+
+def _probe_buf(device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    buf = _PROBE.get(idx)
+    if buf is None:
+        buf = torch.zeros(2 * PROBE_WORDS, dtype=torch.float32, device=torch.device("cuda", idx))
+        _PROBE[idx] = buf
+    return buf
+
+
+def range_probe_arm(device):
+    """arm the probe for the launches this host thread makes next on `device` (until range_probe_disarm); zeroes the maxima"""
+    buf = _probe_buf(device)
+    with torch.cuda.device(buf.device):
+        buf.zero_()
+    _lib.check(_lib.load().pnr_range_probe(_p(buf)), "pnr_range_probe")
+
+
+def range_probe_slot(device, slot):
+    """while armed: direct network launches (pnr_eval_*_split) report into slot 0 (coarse network) or 1 (fine network); the
+    render entries pick the slot themselves"""
+    buf = _probe_buf(device)
+    _lib.check(_lib.load().pnr_range_probe(ctypes.c_void_p(buf.data_ptr() + 4 * PROBE_WORDS * (1 if slot else 0))), "pnr_range_probe")
+
+
+def range_probe_disarm(device=None):
+    _lib.check(_lib.load().pnr_range_probe(None), "pnr_range_probe")
+
+
+def range_probe_read(device):
+    """-> ([11 maxima + non-finite mark] of the coarse slot, the same of the fine slot) as Python floats.  Synchronises."""
+    w = _probe_buf(device).tolist()
+    return w[:PROBE_WORDS], w[PROBE_WORDS:]
 
 
 def pyramid_to_latent(stages, want_nchw=True):

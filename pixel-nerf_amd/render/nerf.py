@@ -206,24 +206,38 @@ class NeRFRenderer(torch.nn.Module):
                 # mlp_fine is None (eval/eval.py:140): pass no fine network, so the fine pass re-uses the coarse pass's
                 # outputs at the shared sample positions instead of evaluating them again
                 own_fine = Kf > 0 and getattr(model, "mlp_fine", None) is not None
-                pk_c, pk_f = model.packed(True), (model.packed(False) if own_fine else None)  # before tables(): see PixelNeRFNet.tables
-                guarded = model._guard_begin()  # fp16-range guard of the fp32-class kernels: first call on new weights / scene
-                try:
-                    tc = model.tables(True)   # (a fold that happens now is guarded too: grid values / lin_z weights)
-                    if guarded:
-                        ops.saturation_guard_slot(rays.device, 1)
-                    tf = model.tables(False) if (own_fine and tc is not None) else None
-                    if guarded:
-                        ops.saturation_guard_slot(rays.device, 0)
-                    res = ops.render_forward(model.scene(), pk_c, pk_f,
-                                             rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
-                                             white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights,
-                                             tables=None if tc is None else (tc, tf),
-                                             seed=self._next_seed(rays.device) if seeded else 0,
-                                             ray_id_offset=self.ray_id_offset, ray_id_stride=self.ray_id_stride)
-                finally:
-                    if guarded:
-                        model._guard_end()
+                seed = self._next_seed(rays.device) if seeded else 0
+                for _ in range(2):  # (twice only for stream_scale="auto" when the first call on new weights saturated)
+                    pk_c, pk_f = model.packed(True), (model.packed(False) if own_fine else None)  # before tables(): see PixelNeRFNet.tables
+                    guarded = model._guard_begin()  # fp16-range guard of the fp32-class kernels: first call on new weights / scene
+                    try:
+                        tc = model.tables(True)   # (a fold that happens now is guarded too: grid values / lin_z weights)
+                        if guarded:
+                            ops.saturation_guard_slot(rays.device, 1)
+                        tf = model.tables(False) if (own_fine and tc is not None) else None
+                        if guarded:
+                            ops.saturation_guard_slot(rays.device, 0)
+                        res = ops.render_forward(model.scene(), pk_c, pk_f,
+                                                 rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
+                                                 white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights,
+                                                 tables=None if tc is None else (tc, tf),
+                                                 seed=seed,
+                                                 ray_id_offset=self.ray_id_offset, ray_id_stride=self.ray_id_stride)
+                    finally:
+                        if guarded:
+                            model._guard_end()
+                    if not (guarded and getattr(model, "__dict__", {}).get("_auto_first")):
+                        break
+                    # the automatic stream scale calibrates on THIS call's rays and draws (same seed / noise), then renders it again
+                    keep = self._seed_override
+                    try:
+                        if seeded:
+                            self._seed_override = seed
+                        redo = model._auto_resolve(rays=rays.reshape(SB, -1, 8), renderer=_FixedNoise(self, _noise if not seeded else None, noise))
+                    finally:
+                        self._seed_override = keep
+                    if not redo:
+                        break
             outputs = DotMap(coarse=self._format(res["coarse"], SB, want_weights))
             if Kf > 0:
                 outputs.fine = self._format(res["fine"], SB, want_weights)
@@ -310,6 +324,25 @@ class NeRFRenderer(torch.nn.Module):
         return wrapped
 
 
+class _FixedNoise:
+    """renderer(model, rays) with the noise tensors of one particular call (calibration of an automatic stream scale on that
+    call's own samples; seeded draws repeat through the renderer's seed override instead)"""
+
+    def __init__(self, renderer, given, drawn):
+        self.renderer, self.noise = renderer, (given if given is not None else drawn)
+
+    def __call__(self, model, rays):
+        return self.renderer.forward(model, rays, _noise=self.noise)
+
+
+def _check_scale_resolved(net, what):
+    """sharded renders equal the single-GPU image bit for bit only if every rank / device runs the same stream scale"""
+    if hasattr(net, "stream_scale_resolved") and not net.stream_scale_resolved():
+        raise RuntimeError(f"{what}: stream_scale='auto' is unresolved -- every rank / device must render at the SAME scale, and an "
+                           "automatic one is chosen from the rays a rank happens to see.  Call net.calibrate_stream_scale(rays=..., "
+                           "renderer=...) on the same batch on every rank first (or set an integer net.stream_scale).")
+
+
 class _MultiDeviceRenderWrapper(torch.nn.Module):
     """Single-process counterpart of the reference's DataParallel(_RenderWrapper, gpus, dim=1) (nerf.py:367-371): rays
     are split on dim 1 across the listed devices, every device renders its slice with its own replica of the
@@ -370,6 +403,7 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         rep.image_shape = src.image_shape.to(dev, non_blocking=True)
         rep.num_objs, rep.num_views_per_obj, rep.mlp_fine = src.num_objs, src.num_views_per_obj, (rep.mlp_fine if src.mlp_fine is not None else None)
         rep.precision, rep.fold, rep.stop_encoder_grad = src.precision, src.fold, src.stop_encoder_grad
+        rep.stream_scale = src.stream_scale  # (resolved: forward checks) an integer pair, the same on every device
         for k in ("n_coarse", "n_fine", "n_fine_depth", "using_fine", "white_bkgd", "lindisp", "depth_std", "noise_std"):
             setattr(rend, k, getattr(self.renderer, k))
         rend.train(self.renderer.training)
@@ -380,6 +414,7 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         from ..autograd import PARAM_NAMES
         from ..dist import shard_bounds
         src = self.net
+        _check_scale_resolved(src, "bind_parallel (several devices)")
         lat = src.encoder.latent
         training = torch.is_grad_enabled() and (any(p.requires_grad for p in src.parameters())
                                                 or (torch.is_tensor(lat) and lat.requires_grad and not src.stop_encoder_grad))
