@@ -78,6 +78,15 @@ typedef struct PnrMlpWeights {
                                                value (PNR_E_INVALID); the exact fp32 inference entries ignore it. */
 } PnrMlpWeights;
 
+/* What a launch of ONE split-operand (PNR_PREC_F16X3) network takes beyond its blob and tables (ABI rev 12; host struct).  A NULL
+ * pointer = every field zero = the plain launch.  The library keeps none of this between calls: a launch is a function of its
+ * arguments.  See "fp16-range guard" and "stream scale and range probe" below. */
+typedef struct PnrSplitAux {
+    int32_t stream_scale_log2;  /* the s this network's blob was packed with (PnrMlpWeights.stream_scale_log2), in [0, 30] */
+    unsigned int *sat_flag;     /* device, ONE 32-bit word, nullable: the fp16-range guard ORs this network's bits into it */
+    float *range_probe;         /* device, 12 floats, nullable: the range probe's words of this network                    */
+} PnrSplitAux;
+
 const char *pnr_last_error(void);
 
 /* Library / device facts (host out-params may be NULL). */
@@ -85,7 +94,7 @@ int pnr_version(int *major, int *minor);
 /* ABI revision of THIS header: bumped whenever a struct layout or an entry point's argument list changes.  The
  * library returns the value it was compiled with; a binding must compare it with the header it was written against
  * before the first call (pixelnerf_amd/_lib.py does, and refuses a stale or foreign .so). */
-#define PNR_ABI_VERSION 11
+#define PNR_ABI_VERSION 12
 int pnr_abi_version(void);
 int pnr_device_info(int *num_cus, int *lds_bytes_per_block);
 /* Bytes of the multi-view scratch (PnrScene.mv_workspace, PnrBackwardDumps.mv_workspace) on the CURRENT device: one tile of
@@ -136,6 +145,7 @@ int pnr_render_forward_folded(const PnrScene *scene /*host*/, const void *packed
                               int lindisp, const float *u1, const float *u2, const float *u3,
                               const float *n4, float *rgb_c, float *depth_c, float *weights_c,
                               float *rgb_f, float *depth_f, float *weights_f, void *workspace,
+                              const PnrSplitAux *aux_coarse /*host, nullable*/, const PnrSplitAux *aux_fine /*host, nullable*/,
                               void *stream);
 
 /* ---- fp32-class accuracy on the f16 matrix cores (PNR_PREC_F16X3): same spans as the folded entries above
@@ -148,7 +158,8 @@ int pnr_render_forward_folded(const PnrScene *scene /*host*/, const void *packed
 size_t pnr_packed_mlp_split_bytes(void);
 int pnr_pack_mlp_split(const PnrMlpWeights *w /*host*/, void *packed_split, void *stream);
 size_t pnr_folded_tables_f32_bytes(const PnrScene *scene /*host*/);
-int pnr_fold_latent_f32(const PnrScene *scene /*host*/, const PnrMlpWeights *w /*host*/, float *tables_f32, void *stream);
+int pnr_fold_latent_f32(const PnrScene *scene /*host*/, const PnrMlpWeights *w /*host*/, float *tables_f32,
+                        unsigned int *sat_flag /*nullable: guard bit 12*/, void *stream);
 /* The same tables for the texels ONE training pass reads (ABI rev 8).  A training step re-folds lin_z every pass -- the
  * weights moved -- and on a large grid most texels are not near any ray of the pass (DTU, 128 rays x 3 views: 37-43 k of
  * 90 k).  rays (R,8), z (R,K) = the pass's samples: every (view, point) is projected with the forward kernels' own code, its
@@ -160,12 +171,13 @@ int pnr_fold_latent_f32(const PnrScene *scene /*host*/, const PnrMlpWeights *w /
 size_t pnr_fold_latent_f32_rows_workspace_bytes(const PnrScene *scene /*host*/);
 int pnr_fold_latent_f32_rows(const PnrScene *scene /*host*/, const PnrMlpWeights *w /*host*/, const float *rays, const float *z,
                              int R, int rays_per_obj, int K, float *tables_f32, void *workspace, size_t workspace_bytes,
-                             void *stream);
+                             unsigned int *sat_flag /*nullable: guard bit 12*/, void *stream);
 int pnr_eval_ray_samples_split(const PnrScene *scene /*host*/, const void *packed_split, const void *tables_f32,
                                const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
-                               void *stream);
+                               const PnrSplitAux *aux /*host, nullable*/, void *stream);
 int pnr_eval_points_split(const PnrScene *scene /*host*/, const void *packed_split, const void *tables_f32,
-                          const float *xyz, const float *viewdirs, int B, float *rgbsigma, void *stream);
+                          const float *xyz, const float *viewdirs, int B, float *rgbsigma,
+                          const PnrSplitAux *aux /*host, nullable*/, void *stream);
 
 /* encoder.latent NCHW -> NHWC (layout change for the lookup in src/model/encoder.py:80-109). */
 int pnr_nchw_to_nhwc(const float *in, float *out, int N, int C, int H, int W, void *stream);
@@ -478,7 +490,9 @@ int pnr_render_forward_seeded(const PnrScene *scene /*host*/, const void *packed
                               const float *rays, int R, int rays_per_obj, int Kc, int Kf, int Kfd, float depth_std,
                               int white_bkgd, int lindisp, unsigned long long seed, long long ray_id_offset,
                               int ray_id_stride, float *rgb_c, float *depth_c, float *weights_c, float *rgb_f,
-                              float *depth_f, float *weights_f, void *workspace, void *stream);
+                              float *depth_f, float *weights_f, void *workspace,
+                              const PnrSplitAux *aux_coarse /*host, nullable*/, const PnrSplitAux *aux_fine /*host, nullable*/,
+                              void *stream);
 
 /* ---- next-row helpers (continued): render whole target views ----------
  * util.gen_rays + NeRFRenderer.forward in ONE call (what eval/eval.py:247-279 and eval/gen_video.py do per
@@ -495,36 +509,40 @@ int pnr_render_views(const PnrScene *scene /*host*/, const void *packed_coarse, 
                      float z_near, float z_far, int Kc, int Kf, int Kfd, float depth_std, int white_bkgd,
                      int lindisp, const float *u1, const float *u2, const float *u3, const float *n4,
                      unsigned long long seed, float *rgb_c, float *depth_c, float *weights_c, float *rgb_f,
-                     float *depth_f, float *weights_f, void *workspace, void *stream);
+                     float *depth_f, float *weights_f, void *workspace,
+                     const PnrSplitAux *aux_coarse /*host, nullable*/, const PnrSplitAux *aux_fine /*host, nullable*/, void *stream);
 
 /* ---- fp16-range guard of the fp32-class ("f16x3") kernels ---------------------------------------
  * The split-operand kernels carry every operand as an fp16 (head, tail) pair: values up to 65504 are
  * represented to ~2^-22, beyond that the head SATURATES (MODE.FP16_OVFL) and the result silently leaves
  * the reference's arithmetic class (src/model/resnetfc.py:132-184 computes in fp32, whatever the
  * magnitude).  Random-init networks stay four orders of magnitude below the limit; a checkpoint need not.
- * pnr_saturation_guard(flags) arms the guard for the CALLING HOST THREAD: until it is called again with
- * NULL, every launch of a split-operand network kernel on that thread runs the instantiation that
- * follows the largest operand head produced (one v_pk_maximum3_f16 per four values in the split epilogue,
- * 1.15 % of the kernel; a head of 65504 means a value >= 65488) and ORs into flags[0] (coarse-network launches and the direct pnr_eval_*_split
- * entries) / flags[1] (fine-network launches of pnr_render_*):
+ * A launch whose PnrSplitAux.sat_flag is non-NULL runs the instantiation that follows the largest operand
+ * head produced (one v_pk_maximum3_f16 per four values in the split epilogue, 1.15 % of the kernel; a head
+ * of 65504 means a value >= 65488) and ORs into that ONE word:
  *   bit 2b    a value >= 65504 in relu(x) entering blocks[b].fc_0        (b = 0..4)
  *   bit 2b+1  a value >= 65504 in relu(net) entering blocks[b].fc_1
  *   bit 10    a value >= 65504 in the stream in front of lin_out
  *   bit 11    a non-finite network output
- *   bit 12    (pnr_fold_latent_f32, called while armed) a feature-grid value or lin_z weight beyond the fp16 range
- * flags: DEVICE array of two 32-bit words, zeroed by the caller, read back by the caller (asynchronously:
- * pixelnerf_amd copies it to pinned memory and looks at it on the next call, like the parameter check).
- * The guard never changes a result. */
-int pnr_saturation_guard(unsigned int *flags_dev);
+ *   bit 12    (pnr_fold_latent_f32 / _rows, through their own sat_flag argument) a feature-grid value or lin_z weight
+ *             beyond the fp16 range
+ * The word is per network: the render entries take one struct for the coarse and one for the fine network, and a
+ * caller that wants the two apart passes two words (pixelnerf_amd: word 0 coarse, word 1 fine).  With packed_fine == NULL
+ * (the merge path) both launches of the coarse network use aux_coarse.  The word is zeroed by the caller and read back by
+ * the caller (asynchronously: pixelnerf_amd copies it to pinned memory and looks at it on the next call, like the
+ * parameter check).  The guard never changes a result.  pnr_eval_ray_samples_split_train reports the same bits. */
 
-/* ---- stream scale and range probe of the fp32-class ("f16x3") kernels (ABI rev 11) ----------------
+/* ---- stream scale and range probe of the fp32-class ("f16x3") kernels ----------------------------
  * ReLU is positively homogeneous, so the hidden stream of a ResnetFC (src/model/resnetfc.py:147-184: x, and
  * net / dx inside every block, resnetfc.py:66-88) can be carried at c = 2^-s of its value and undone exactly in
  * front of lin_out's bias (resnetfc.py:183, src/model/models.py:258-265).  A network packed with
- * PnrMlpWeights.stream_scale_log2 = s > 0 (pnr_pack_mlp_split) runs the scaled instantiation in every
- * PNR_PREC_F16X3 inference entry (pnr_eval_points_split, pnr_eval_ray_samples_split, pnr_render_forward_folded /
- * _seeded, pnr_render_views; single- and multi-view, the merge path of a NULL fine network included).  All four
- * scale sites are fp32 and exact -- nothing that is stored as fp16 is shifted:
+ * PnrMlpWeights.stream_scale_log2 = s > 0 (pnr_pack_mlp_split) must be LAUNCHED with PnrSplitAux.stream_scale_log2 = s:
+ * that selects the scaled instantiation in every PNR_PREC_F16X3 inference entry (pnr_eval_points_split,
+ * pnr_eval_ray_samples_split, pnr_render_forward_folded / _seeded, pnr_render_views; single- and multi-view, the merge
+ * path of a NULL fine network included).  A blob is position-independent bytes -- it may be copied, moved to another
+ * device or restored from a file -- and the library remembers nothing about it: the caller passes the s it packed with.
+ * A launch at another s than the blob's computes with biases packed for the wrong scale, and nothing reports it.  All
+ * four scale sites are fp32 and exact -- nothing that is stored as fp16 is shifted:
  *   x *= c          after lin_in + table 0 (lin_in's bias included)         resnetfc.py:147, 175-180 (b = 0)
  *   x += c * t      tables 1 and 2 (one FMA; the tables in memory are unscaled) resnetfc.py:175-180 (b = 1, 2)
  *   c * bias        blocks[b].fc_0 / fc_1 biases, at pack time               resnetfc.py:81-82
@@ -532,22 +550,21 @@ int pnr_saturation_guard(unsigned int *flags_dev);
  * t: lin_out's weights are packed LIFTED by 2^t (the largest t in [0, 30] with max |W_out| 2^t <= 2^14; exact, in fp32, in
  * front of the head/tail split).  A network with a large hidden stream has a correspondingly small lin_out, whose fp16 tails
  * -- at 1e-6 even its heads -- are subnormal; the lift moves them up into the normal range.  The hidden weights are untouched.
- * A blob packed with s = 0 runs the unscaled instantiations: the same bits as revision 10.
+ * A blob packed with s = 0 and launched with s = 0 (or a NULL struct) runs the unscaled instantiations: the bits of revision 10.
  * What a scale does NOT cure: guard bit 12 (grid values / lin_z weights themselves beyond 65504).
- * pnr_eval_ray_samples_split_train takes no PnrMlpWeights: it must be given a blob packed at s = 0 (its callers
- * pack through a struct the other training entries check).
+ * Every entry refuses an s outside [0, 30]; pnr_eval_ray_samples_split_train refuses s != 0 (no training at a stream scale);
+ * the render entries refuse a struct with any field set at a precision other than PNR_PREC_F16X3 (all PNR_E_INVALID, before
+ * any device work).
  *
- * pnr_range_probe(amax) arms the range probe for the CALLING HOST THREAD (NULL disarms), slotted like the guard:
- * every split-operand inference launch runs a calibration instantiation that follows the fp32 values entering
- * the (head, tail) split with v_max3_f32 and, at the end of each workgroup, does one atomic max per layer on the
- * bit pattern of the non-negative float.  amax: DEVICE array of 2 x 12 floats (slot 0: coarse-network launches
- * and the direct entries, slot 1: fine-network launches), zeroed by the caller:
+ * A launch whose PnrSplitAux.range_probe is non-NULL runs a calibration instantiation (at any s) that follows the fp32 values
+ * entering the (head, tail) split with v_max3_f32 and, at the end of each workgroup, does one atomic max per layer on the
+ * bit pattern of the non-negative float.  range_probe: DEVICE array of 12 floats per network, zeroed by the caller:
  *   words 0..10  largest value that entered the operand image of layer l (the numbering of the guard's bits 0..10),
  *                in TRUE units (the kernel multiplies by 2^s)
  *   word 11      non-zero if a network output was NaN / inf (the guard's bit 11)
  * Downstream of a saturated layer the probe under-reports (the products used clamped heads): calibrate
- * iteratively.  A calibration tool, not a timed path.  The guard, when armed too, keeps reporting. */
-int pnr_range_probe(float *amax_dev);
+ * iteratively.  A calibration tool, not a timed path.  The guard, when given its word too, keeps reporting.
+ * pnr_eval_ray_samples_split_train has no probe form and ignores the pointer. */
 
 /* ---- SpatialEncoder.index as a stand-alone operator ------------------------------------------
  * src/model/encoder.py:80-109 (SpatialEncoder.index): F.grid_sample(latent, uv[:, :, None], mode "bilinear",
@@ -652,7 +669,7 @@ typedef struct PnrSplitSaved {
 } PnrSplitSaved;
 int pnr_eval_ray_samples_split_train(const PnrScene *scene /*host*/, const void *packed_split, const void *tables_f32,
                                      const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
-                                     const PnrSplitSaved *saved /*host*/, void *stream);
+                                     const PnrSplitSaved *saved /*host*/, const PnrSplitAux *aux /*host, nullable*/, void *stream);
 /* grad_scale = device [s, 1/s] from pnr_grad_scale(g_out); outputs as pnr_mlp_backward_f32 (d_zlat required, d_in and grads
  * nullable: grads == NULL runs the data-gradient chain only, without the weight-gradient launches).  With NS > 1 the workspace
  * also holds the multi-view scratch. */

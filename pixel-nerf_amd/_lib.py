@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelne
 SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip"]
 HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_raysrc.h", "pnr_internal.h", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
-ABI_VERSION = 11  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
+ABI_VERSION = 12  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3
 PRECISIONS = {"f16": PREC_F16, "fp16": PREC_F16, "bf16": PREC_BF16, "f32": PREC_F32, "fp32": PREC_F32, "f16x3": PREC_F16X3}
 
@@ -44,6 +44,10 @@ class PnrMlpWeights(ctypes.Structure):
         ("lin_out_w", ctypes.c_void_p), ("lin_out_b", ctypes.c_void_p),
         ("combine_max", ctypes.c_int32), ("stream_scale_log2", ctypes.c_int32),
     ]
+
+
+class PnrSplitAux(ctypes.Structure):
+    _fields_ = [("stream_scale_log2", ctypes.c_int32), ("sat_flag", ctypes.c_void_p), ("range_probe", ctypes.c_void_p)]
 
 
 class PnrWeightGradJob(ctypes.Structure):
@@ -74,6 +78,7 @@ class PnrSplitSaved(ctypes.Structure):
 
 # every symbol include/pixelnerf_hip.h declares: name -> (restype, argtypes)
 _I, _F, _P, _SZ = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+_AUX = ctypes.POINTER(PnrSplitAux)
 PROTOTYPES = {
     "pnr_last_error": (ctypes.c_char_p, []),
     "pnr_version": (_I, [ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -91,15 +96,13 @@ PROTOTYPES = {
     "pnr_eval_points": (_I, [ctypes.POINTER(PnrScene), _P, _I, _P, _P, _I, _P, _P]),
     "pnr_render_views_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "pnr_render_views": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _I, _I, _F,
-                              _I, _I, _P, _P, _P, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P]),
+                              _I, _I, _P, _P, _P, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _AUX, _AUX, _P]),
     "pnr_philox_noise": (_I, [ctypes.c_ulonglong, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pnr_philox_raw": (_I, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "pnr_render_forward_seeded": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I,
-                                       ctypes.c_ulonglong, ctypes.c_longlong, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+                                       ctypes.c_ulonglong, ctypes.c_longlong, _I, _P, _P, _P, _P, _P, _P, _P, _AUX, _AUX, _P]),
     "pnr_pyramid_to_latent": (_I, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                    ctypes.POINTER(ctypes.c_int), _I, _I, _P, _P, _P]),
-    "pnr_saturation_guard": (_I, [_P]),
-    "pnr_range_probe": (_I, [_P]),
     "pnr_grid_index": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "pnr_grid_index_backward": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P, _P]),
     "pnr_positional_encoding": (_I, [_P, ctypes.c_longlong, _I, _I, _P, _P, _I, _P, _P]),
@@ -119,13 +122,13 @@ PROTOTYPES = {
     "pnr_eval_ray_samples_folded": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
     "pnr_eval_points_folded": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _P, _P, _I, _P, _P]),
     "pnr_render_forward_folded": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I,
-                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _AUX, _AUX, _P]),
     "pnr_packed_mlp_split_bytes": (_SZ, []),
     "pnr_pack_mlp_split": (_I, [ctypes.POINTER(PnrMlpWeights), _P, _P]),
     "pnr_folded_tables_f32_bytes": (_SZ, [ctypes.POINTER(PnrScene)]),
-    "pnr_fold_latent_f32": (_I, [ctypes.POINTER(PnrScene), ctypes.POINTER(PnrMlpWeights), _P, _P]),
-    "pnr_eval_ray_samples_split": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _I, _I, _P, _P]),
-    "pnr_eval_points_split": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _P, _P]),
+    "pnr_fold_latent_f32": (_I, [ctypes.POINTER(PnrScene), ctypes.POINTER(PnrMlpWeights), _P, _P, _P]),
+    "pnr_eval_ray_samples_split": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _I, _I, _P, _AUX, _P]),
+    "pnr_eval_points_split": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _P, _AUX, _P]),
     "pnr_eval_ray_samples_train": (_I, [ctypes.POINTER(PnrScene), _P, _I, _P, _P, _I, _I, _I, _P,
                                         ctypes.POINTER(PnrTrainDumps), _P]),
     "pnr_storage_perm": (_I, [ctypes.POINTER(ctypes.c_int32)]),
@@ -153,7 +156,7 @@ PROTOTYPES = {
     "pnr_linear_backward_workspace_bytes": (_SZ, [_I, _I]),
     "pnr_linear_backward": (_I, [_P, _P, _P, ctypes.c_longlong, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _I, _P]),
     "pnr_fold_latent_f32_rows_workspace_bytes": (_SZ, [ctypes.POINTER(PnrScene)]),
-    "pnr_fold_latent_f32_rows": (_I, [ctypes.POINTER(PnrScene), ctypes.POINTER(PnrMlpWeights), _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "pnr_fold_latent_f32_rows": (_I, [ctypes.POINTER(PnrScene), ctypes.POINTER(PnrMlpWeights), _P, _P, _I, _I, _I, _P, _P, _SZ, _P, _P]),
     "pnr_latent_scatter_workspace_bytes": (_SZ, [ctypes.POINTER(PnrScene), _I, _I, _I]),
     "pnr_latent_scatter_single_owner": (_I, [ctypes.POINTER(PnrScene), _I, _I, _I]),
     "pnr_latent_scatter": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
@@ -162,7 +165,7 @@ PROTOTYPES = {
     "pnr_render_forward": (_I, [ctypes.POINTER(PnrScene), _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I,
                                 _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pnr_gen_rays": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P]),
-    "pnr_eval_ray_samples_split_train": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _I, _I, _P, ctypes.POINTER(PnrSplitSaved), _P]),
+    "pnr_eval_ray_samples_split_train": (_I, [ctypes.POINTER(PnrScene), _P, _P, _P, _P, _I, _I, _I, _P, ctypes.POINTER(PnrSplitSaved), _AUX, _P]),
     "pnr_eval_ray_samples_f32_train": (_I, [ctypes.POINTER(PnrScene), ctypes.POINTER(PnrMlpWeights), _P, _P, _I, _I, _I, _P,
                                             ctypes.POINTER(PnrF32Saved), _I, _P]),
     "pnr_mlp_backward_f32_workspace_bytes": (_SZ, [ctypes.c_longlong, _I]),

@@ -5,7 +5,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 
 #include "pnr_common.h"
 #include "pnr_internal.h"
@@ -88,65 +87,4 @@ int pnr::device_cus() {
         int n = 0;
         return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
     }, 256);
-}
-
-// ---- fp16-range guard of the fp32-class ("f16x3") kernels
-static thread_local unsigned int *g_sat_flags = nullptr;
-static thread_local int g_sat_slot = 0;
-
-unsigned int *pnr::saturation_guard_word() { return g_sat_flags ? g_sat_flags + g_sat_slot : nullptr; }
-void pnr::saturation_guard_slot(int slot) { g_sat_slot = slot == 1 ? 1 : 0; }
-
-extern "C" int pnr_saturation_guard(unsigned int *flags_dev) {
-    g_sat_flags = flags_dev;
-    g_sat_slot = 0;
-    return PNR_OK;
-}
-
-// ---- range probe of the same kernels: armed per host thread, slotted with the guard (saturation_guard_slot)
-static thread_local float *g_probe = nullptr;
-
-float *pnr::range_probe_words() { return g_probe ? g_probe + g_sat_slot * pnr::PROBE_WORDS : nullptr; }
-
-extern "C" int pnr_range_probe(float *amax_dev) {
-    g_probe = amax_dev;
-    g_sat_slot = 0;
-    return PNR_OK;
-}
-
-// ---- which split-operand blobs were packed at a stream scale.  The scale lives in the blob's tail (device memory); the host
-// picks the kernel instantiation, so pnr_pack_mlp_split notes the ADDRESS it packed at s > 0 here (and forgets it when the same
-// address is packed at 0).  A fixed table, no allocation; blobs at s = 0 -- every blob before revision 11 -- never enter it and
-// their launches pay one relaxed load.
-namespace {
-struct ScaledBlob { const void *p; int s; };
-constexpr int kMaxScaled = 256;
-ScaledBlob g_scaled[kMaxScaled];
-std::atomic<int> g_n_scaled{0};
-std::mutex g_scaled_mu;
-}  // namespace
-
-int pnr::note_stream_scale(const void *packed, int s) {
-    std::lock_guard<std::mutex> lock(g_scaled_mu);
-    int n = g_n_scaled.load(std::memory_order_relaxed);
-    for (int i = 0; i < n; ++i)
-        if (g_scaled[i].p == packed) {
-            if (s > 0) g_scaled[i].s = s;
-            else { g_scaled[i] = g_scaled[n - 1]; g_n_scaled.store(n - 1, std::memory_order_release); }
-            return PNR_OK;
-        }
-    if (s <= 0) return PNR_OK;
-    if (n == kMaxScaled) return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_split: more than 256 live blobs packed at a stream scale");
-    g_scaled[n] = {packed, s};
-    g_n_scaled.store(n + 1, std::memory_order_release);
-    return PNR_OK;
-}
-
-int pnr::stream_scale_of(const void *packed) {
-    if (g_n_scaled.load(std::memory_order_acquire) == 0) return 0;
-    std::lock_guard<std::mutex> lock(g_scaled_mu);
-    const int n = g_n_scaled.load(std::memory_order_relaxed);
-    for (int i = 0; i < n; ++i)
-        if (g_scaled[i].p == packed) return g_scaled[i].s;
-    return 0;
 }

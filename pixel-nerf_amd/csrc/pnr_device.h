@@ -79,7 +79,7 @@ struct EvalParams {
     float *f_x5;
     // GUARD instantiation of the split-operand kernel: one word that collects "layer l saw a value beyond the fp16 range" bits
     unsigned int *sat_flag;
-    // PROBE instantiation (pnr_range_probe): 12 words, per-layer maxima of the values entering the operand images + a non-finite mark
+    // PROBE instantiation (PnrSplitAux.range_probe): 12 words, per-layer maxima of the values entering the operand images + a non-finite mark
     unsigned int *probe;
 };
 

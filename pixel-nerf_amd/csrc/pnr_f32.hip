@@ -850,8 +850,12 @@ static int check_split_saved(const PnrSplitSaved *sv) {
 
 extern "C" int pnr_eval_ray_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32,
                                                 const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
-                                                const PnrSplitSaved *saved, void *stream) {
+                                                const PnrSplitSaved *saved, const PnrSplitAux *aux, void *stream) {
     using namespace pnr;
+    if (int rc = check_split_aux(aux, PNR_PREC_F16X3, "pnr_eval_ray_samples_split_train")) return rc;
+    if (aux && aux->stream_scale_log2 != 0)
+        return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: training at a stream scale is not supported "
+                                       "(PnrSplitAux.stream_scale_log2 must be 0: pack the blob with stream_scale_log2 = 0)");
     if (R <= 0 || K <= 0 || rays_per_obj <= 0 || !rays || !z || !scene || !packed_split || !tables_f32 || !rgbsigma)
         return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: bad argument");
     if ((long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: R != SB * rays_per_obj");
@@ -869,7 +873,7 @@ extern "C" int pnr_eval_ray_samples_split_train(const PnrScene *scene, const voi
     int rc = pnr_check_launch("pnr_eval_ray_samples_split_train (features)");
     if (rc != PNR_OK) return rc;
     return eval_samples_split_train(scene, packed_split, tables_f32, rays, z, R, rays_per_obj, K, rgbsigma, saved->a, saved->n,
-                                    saved->x5, saved->masks, (hipStream_t)stream);
+                                    saved->x5, saved->masks, aux, (hipStream_t)stream);
 }
 
 static size_t split_bwd_images_bytes(long long P, int NS) { return ((size_t)P * NS * 7 + (size_t)P * 4) * pnr::D_HID * 4; }

@@ -10,10 +10,11 @@ namespace pnr {
 // fused network on (ray, z) samples with the rays taken from `src` (explicit array or camera): dispatches on
 // `precision` (F16 / BF16 kernels of pnr_mlp.hip, F16X3 split-operand kernel of pnr_split.hip); tables == NULL selects
 // the unfolded stream.
+// aux: what a split-operand launch takes beyond that (stream scale, guard word, probe words; nullable, F16X3 only).
 int eval_samples_src(const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
-                     const float *z, int R, int rays_per_obj, int K, float *rgbsigma, hipStream_t stream);
+                     const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux, hipStream_t stream);
 int eval_samples_split_src(const PnrScene *scene, const void *packed_split, const void *tables_f32, const RaySrc &src,
-                           const float *z, int R, int rays_per_obj, int K, float *rgbsigma, hipStream_t stream);
+                           const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux, hipStream_t stream);
 
 // training forward of the fp32-class path: the split-operand kernel + what the backward keeps -- the (head | tail) 16-bit operand
 // images of every 512-wide linear in storage order (img_a[b]: relu(x) entering blocks[b].fc_0, img_n[b]: relu(net) entering fc_1;
@@ -21,7 +22,7 @@ int eval_samples_split_src(const PnrScene *scene, const void *packed_split, cons
 // the relu bit masks (pnr_train_masks_bytes).  Defined in pnr_split.hip.
 int eval_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *rays,
                              const float *z, int R, int rays_per_obj, int K, float *rgbsigma, void *const *img_a, void *const *img_n,
-                             float *x5, void *masks, hipStream_t stream);
+                             float *x5, void *masks, const PnrSplitAux *aux, hipStream_t stream);
 
 // fused data-gradient chain of the fp32-class training path (bwd_split_kernel, pnr_split.hip): transposed (head, tail) weight
 // streams packed from the raw parameters, relu masks of the TRAIN forward, g_out (P,4) unscaled + device [s, 1/s]; every layer's
@@ -35,17 +36,10 @@ int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long l
                              float *d_in /* (NS*P,42), nullable */,
                              float *mv_ws /* NS > 1: pnr_mv_workspace_bytes() */, hipStream_t st);
 
-// fp16-range guard of the fp32-class kernels (pnr_saturation_guard, pnr_api.hip): the flag word the next split-operand launch
-// of THIS host thread reports into (NULL = guard off), and which of the caller's two words that is (render entries set the
-// slot: 0 = coarse-network launch, 1 = fine-network launch).
-unsigned int *saturation_guard_word();
-void saturation_guard_slot(int slot);
-// range probe (pnr_range_probe): the 12 words of the armed slot (the guard's slot), or NULL = probe off
-float *range_probe_words();
-constexpr int PROBE_WORDS = 12;
-// stream scale of the split-operand blob packed at this address (0: none noted); pnr_pack_mlp_split notes it.  pnr_api.hip.
-int note_stream_scale(const void *packed, int s);
-int stream_scale_of(const void *packed);
+// PnrSplitAux of an entry (nullable): PNR_OK, or PNR_E_INVALID when stream_scale_log2 is outside [0, 30] or -- for a precision
+// other than PNR_PREC_F16X3 -- when any field is set.  No HIP call.  Defined in pnr_split.hip.
+int check_split_aux(const PnrSplitAux *aux, int precision, const char *entry);
+constexpr int PROBE_WORDS = 12;  // floats of PnrSplitAux.range_probe
 
 // XCDs the dispatcher deals workgroups to round-robin on the current device (hipDeviceAttributeNumberOfXccs, i.e. of the
 // current compute-partition mode: 8 in SPX, 1 in CPX; PIXELNERF_XCD_COUNT=n overrides, 0 selects the plain grid-stride

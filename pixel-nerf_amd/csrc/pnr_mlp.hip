@@ -560,8 +560,8 @@ extern "C" int pnr_debug_phase_timing(const PnrScene *s, const void *packed, con
 #endif
 
 int pnr::eval_samples_src(const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
-                          const float *z, int R, int rays_per_obj, int K, float *rgbsigma, hipStream_t stream) {
-    if (precision == PNR_PREC_F16X3) return eval_samples_split_src(scene, packed, tables, src, z, R, rays_per_obj, K, rgbsigma, stream);
+                          const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux, hipStream_t stream) {
+    if (precision == PNR_PREC_F16X3) return eval_samples_split_src(scene, packed, tables, src, z, R, rays_per_obj, K, rgbsigma, aux, stream);
     if (R < 0 || K <= 0 || rays_per_obj <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: bad sizes");
     if (R > 0 && ((!src.rays && !src.poses) || !z)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: null rays/z");
     if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: R != SB * rays_per_obj");
@@ -576,7 +576,7 @@ static int eval_ray_samples_impl(const PnrScene *scene, const void *packed, cons
                                  void *stream) {
     pnr::RaySrc src = {};
     src.rays = rays;
-    return pnr::eval_samples_src(scene, packed, tables, precision, src, z, R, rays_per_obj, K, rgbsigma, (hipStream_t)stream);
+    return pnr::eval_samples_src(scene, packed, tables, precision, src, z, R, rays_per_obj, K, rgbsigma, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pnr_eval_ray_samples(const PnrScene *scene, const void *packed, int precision, const float *rays,

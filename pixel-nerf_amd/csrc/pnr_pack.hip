@@ -261,7 +261,7 @@ fold_kernel(const float *__restrict__ grid, const FoldJobs jobs, T *__restrict__
 // inference (2.5 ms per network for the DTU grid, on EVERY rank of a sharded render) and per STEP in training (the grid is a
 // trained tensor: 0.27 ms of the 6.3 ms fp32-class step).  128 texels x 128 features per 256-thread workgroup (4 waves of
 // 64 x 64 = 2 x 2 MFMA tiles), K chunks of 32; [row][k] f16 images with 80-byte rows (conflict-free 16-byte fragment reads).
-// sat: when non-null, bit 12 is raised if a grid value or a lin_z weight is beyond the fp16 range (pnr_saturation_guard).
+// sat: when non-null, bit 12 is raised if a grid value or a lin_z weight is beyond the fp16 range (the fp16-range guard).
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 constexpr int FS_TM = 128, FS_TN = 128, FS_K = 32, FS_ROW = FS_K + 8;  // halves per LDS row (32 used)
@@ -771,7 +771,7 @@ extern "C" int pnr_fold_latent(const PnrScene *s, const PnrMlpWeights *w, int pr
 // fp32 tables for the split-operand kernel: same layout as the 16-bit tables, 4 bytes per entry
 extern "C" size_t pnr_folded_tables_f32_bytes(const PnrScene *s) { return 2 * pnr_folded_tables_bytes(s); }
 
-extern "C" int pnr_fold_latent_f32(const PnrScene *s, const PnrMlpWeights *w, float *tables, void *stream) {
+extern "C" int pnr_fold_latent_f32(const PnrScene *s, const PnrMlpWeights *w, float *tables, unsigned int *sat_flag, void *stream) {
     using namespace pnr;
     if (!s || !w || !tables || !s->latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32: null argument");
     if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32: bad scene shape");
@@ -791,11 +791,11 @@ extern "C" int pnr_fold_latent_f32(const PnrScene *s, const PnrMlpWeights *w, fl
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fold_split_big_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
         if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(fold_split_big_kernel)");
         hipLaunchKernelGGL(fold_split_big_kernel<false>, dim3(wgs), dim3(512), FB_LDS, (hipStream_t)stream, s->latent_nhwc, jobs, tables, M, ngroups,
-                           saturation_guard_word(), (const int *)nullptr, (const int *)nullptr);
+                           sat_flag, (const int *)nullptr, (const int *)nullptr);
         return pnr_check_launch("pnr_fold_latent_f32");
     }
     dim3 sgrid((unsigned)((M + FS_TM - 1) / FS_TM), D_HID / FS_TN, COMBINE_LAYER);
-    hipLaunchKernelGGL(fold_split_kernel, sgrid, dim3(256), 0, (hipStream_t)stream, s->latent_nhwc, jobs, tables, M, saturation_guard_word());
+    hipLaunchKernelGGL(fold_split_kernel, sgrid, dim3(256), 0, (hipStream_t)stream, s->latent_nhwc, jobs, tables, M, sat_flag);
     return pnr_check_launch("pnr_fold_latent_f32");
 }
 
@@ -810,7 +810,7 @@ extern "C" size_t pnr_fold_latent_f32_rows_workspace_bytes(const PnrScene *s) {
 }
 
 extern "C" int pnr_fold_latent_f32_rows(const PnrScene *s, const PnrMlpWeights *w, const float *rays, const float *z, int R, int rays_per_obj,
-                                        int K, float *tables, void *workspace, size_t workspace_bytes, void *stream) {
+                                        int K, float *tables, void *workspace, size_t workspace_bytes, unsigned int *sat_flag, void *stream) {
     using namespace pnr;
     if (!s || !w || !tables || !s->latent_nhwc || !rays || !z) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: null argument");
     if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2 || R <= 0 || K <= 0 || rays_per_obj <= 0)
@@ -847,7 +847,7 @@ extern "C" int pnr_fold_latent_f32_rows(const PnrScene *s, const PnrMlpWeights *
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(fold_split_big_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(fold_split_big_kernel<sparse>)");
     hipLaunchKernelGGL(fold_split_big_kernel<true>, dim3(wgs), dim3(512), FB_LDS, st, s->latent_nhwc, jobs, tables, M, ngroups,
-                       saturation_guard_word(), (const int *)rows, (const int *)nrows);
+                       sat_flag, (const int *)rows, (const int *)nrows);
     return pnr_check_launch("pnr_fold_latent_f32_rows");
 }
 
@@ -857,7 +857,6 @@ extern "C" int pnr_pack_mlp_split(const PnrMlpWeights *w, void *packed, void *st
     if (!w || !packed) return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_split: null argument");
     if (w->stream_scale_log2 < 0 || w->stream_scale_log2 > STREAM_SCALE_MAX)
         return pnr_fail(PNR_E_INVALID, "pnr_pack_mlp_split: stream_scale_log2 must be in [0, 30]");
-    if (int rc = note_stream_scale(packed, w->stream_scale_log2)) return rc;  // the host picks the kernel form by the blob's address
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)RS_TOTAL_F * IT * (FRAG_ELEMS / 8) * NW;  // one thread per 8 elements
     const int threads = 256;

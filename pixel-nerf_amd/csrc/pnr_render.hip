@@ -370,7 +370,11 @@ extern "C" size_t pnr_render_workspace_bytes(int R, int Kc, int Kf) {
 static int render_impl(const PnrScene *scene, const void *packed_coarse, const void *tables_coarse, const void *packed_fine,
                        const void *tables_fine, int precision, const RaySrc &rs, const NoiseSrc &ns, int R, int rays_per_obj,
                        int Kc, int Kf, int Kfd, float depth_std, int white_bkgd, int lindisp, float *rgb_c, float *depth_c,
-                       float *weights_c, float *rgb_f, float *depth_f, float *weights_f, void *workspace, void *stream) {
+                       float *weights_c, float *rgb_f, float *depth_f, float *weights_f, void *workspace,
+                       const PnrSplitAux *aux_coarse, const PnrSplitAux *aux_fine, void *stream) {
+    int rc;
+    if ((rc = check_split_aux(aux_coarse, precision, "pnr_render_forward")) || (rc = check_split_aux(aux_fine, precision, "pnr_render_forward")))
+        return rc;
     if (R < 0 || Kc <= 0 || Kf < 0 || Kfd < 0 || Kfd > Kf)
         return pnr_fail(PNR_E_INVALID, "pnr_render_forward: bad sample counts");
     if (R == 0) return PNR_OK;
@@ -392,25 +396,20 @@ static int render_impl(const PnrScene *scene, const void *packed_coarse, const v
     float *rgbs_new = ws; ws += align64(r * (kt - kc) * 4);
     int32_t *ranks = (int32_t *)ws;
     if (weights_c) w_c = weights_c;  // write straight into the caller's buffer
-    int rc;
     if ((rc = sample_coarse_src(rs, ns, R, Kc, lindisp, z_c, stream))) return rc;
-    saturation_guard_slot(0);  // (fp16-range guard, when armed: the coarse network reports into word 0, a fine network into word 1)
-    if ((rc = eval_samples_src(scene, packed_coarse, tables_coarse, precision, rs, z_c, R, rays_per_obj, Kc, rgbs_c, st))) return rc;
+    if ((rc = eval_samples_src(scene, packed_coarse, tables_coarse, precision, rs, z_c, R, rays_per_obj, Kc, rgbs_c, aux_coarse, st))) return rc;
     if ((rc = composite_src(rs, z_c, rgbs_c, R, Kc, white_bkgd, w_c, rgb_c, depth_c, stream))) return rc;
     if (Kf > 0) {
         if (packed_fine) {
             if ((rc = sample_fine_src(rs, w_c, depth_c, z_c, ns, R, Kc, Kf - Kfd, Kfd, depth_std, lindisp, z_f, nullptr, nullptr,
                                       nullptr, stream))) return rc;
-            saturation_guard_slot(1);
-            rc = eval_samples_src(scene, packed_fine, tables_fine, precision, rs, z_f, R, rays_per_obj, Kc + Kf, rgbs_f, st);
-            saturation_guard_slot(0);
-            if (rc) return rc;
+            if ((rc = eval_samples_src(scene, packed_fine, tables_fine, precision, rs, z_f, R, rays_per_obj, Kc + Kf, rgbs_f, aux_fine, st))) return rc;
         } else {
             // mlp_fine is None (models.py:242, eval/eval.py:140): the fine pass runs the coarse network on the merged
             // samples, Kc of which it has just evaluated -- evaluate the Kf new ones only and merge in sorted order
             if ((rc = sample_fine_src(rs, w_c, depth_c, z_c, ns, R, Kc, Kf - Kfd, Kfd, depth_std, lindisp, z_f, nullptr, z_new,
                                       ranks, stream))) return rc;
-            if ((rc = eval_samples_src(scene, packed_coarse, tables_coarse, precision, rs, z_new, R, rays_per_obj, Kf, rgbs_new, st))) return rc;
+            if ((rc = eval_samples_src(scene, packed_coarse, tables_coarse, precision, rs, z_new, R, rays_per_obj, Kf, rgbs_new, aux_coarse, st))) return rc;
             const long long n = (long long)R * (Kc + Kf);
             hipLaunchKernelGGL(merge_rgbsigma_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                (const float4 *)rgbs_c, (const float4 *)rgbs_new, ranks, R, Kc, Kf, (float4 *)rgbs_f);
@@ -429,7 +428,7 @@ extern "C" int pnr_render_forward(const PnrScene *scene, const void *packed_coar
     if (R > 0 && !u1) return pnr_fail(PNR_E_INVALID, "pnr_render_forward: null u1 (pnr_render_forward_seeded draws in-kernel)");
     return render_impl(scene, packed_coarse, nullptr, packed_fine, nullptr, precision, explicit_rays(rays),
                        explicit_noise(u1, u2, u3, n4), R, rays_per_obj, Kc, Kf, Kfd, depth_std, white_bkgd, lindisp, rgb_c, depth_c,
-                       weights_c, rgb_f, depth_f, weights_f, workspace, stream);
+                       weights_c, rgb_f, depth_f, weights_f, workspace, nullptr, nullptr, stream);
 }
 
 extern "C" int pnr_render_forward_folded(const PnrScene *scene, const void *packed_coarse, const void *tables_coarse,
@@ -437,13 +436,14 @@ extern "C" int pnr_render_forward_folded(const PnrScene *scene, const void *pack
                                          int R, int rays_per_obj, int Kc, int Kf, int Kfd, float depth_std, int white_bkgd,
                                          int lindisp, const float *u1, const float *u2, const float *u3, const float *n4,
                                          float *rgb_c, float *depth_c, float *weights_c, float *rgb_f, float *depth_f,
-                                         float *weights_f, void *workspace, void *stream) {
+                                         float *weights_f, void *workspace, const PnrSplitAux *aux_coarse, const PnrSplitAux *aux_fine,
+                                         void *stream) {
     if (!tables_coarse || (packed_fine && !tables_fine))
         return pnr_fail(PNR_E_INVALID, "pnr_render_forward_folded: every folded network needs its tables");
     if (R > 0 && !u1) return pnr_fail(PNR_E_INVALID, "pnr_render_forward_folded: null u1 (pnr_render_forward_seeded draws in-kernel)");
     return render_impl(scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, explicit_rays(rays),
                        explicit_noise(u1, u2, u3, n4), R, rays_per_obj, Kc, Kf, Kfd, depth_std, white_bkgd, lindisp, rgb_c, depth_c,
-                       weights_c, rgb_f, depth_f, weights_f, workspace, stream);
+                       weights_c, rgb_f, depth_f, weights_f, workspace, aux_coarse, aux_fine, stream);
 }
 
 extern "C" int pnr_render_forward_seeded(const PnrScene *scene, const void *packed_coarse, const void *tables_coarse,
@@ -451,12 +451,13 @@ extern "C" int pnr_render_forward_seeded(const PnrScene *scene, const void *pack
                                          int R, int rays_per_obj, int Kc, int Kf, int Kfd, float depth_std, int white_bkgd,
                                          int lindisp, unsigned long long seed, long long ray_id_offset, int ray_id_stride,
                                          float *rgb_c, float *depth_c, float *weights_c, float *rgb_f, float *depth_f,
-                                         float *weights_f, void *workspace, void *stream) {
+                                         float *weights_f, void *workspace, const PnrSplitAux *aux_coarse, const PnrSplitAux *aux_fine,
+                                         void *stream) {
     if ((tables_coarse == nullptr) != (tables_fine == nullptr) && packed_fine)
         return pnr_fail(PNR_E_INVALID, "pnr_render_forward_seeded: both networks folded or neither");
     return render_impl(scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, explicit_rays(rays),
                        seeded_noise(seed, ray_id_offset, ray_id_stride, rays_per_obj), R, rays_per_obj, Kc, Kf, Kfd, depth_std,
-                       white_bkgd, lindisp, rgb_c, depth_c, weights_c, rgb_f, depth_f, weights_f, workspace, stream);
+                       white_bkgd, lindisp, rgb_c, depth_c, weights_c, rgb_f, depth_f, weights_f, workspace, aux_coarse, aux_fine, stream);
 }
 
 // util.gen_rays + NeRFRenderer.forward for whole target views (eval/eval.py:247-279): the rays are never materialised
@@ -472,7 +473,8 @@ extern "C" int pnr_render_views(const PnrScene *scene, const void *packed_coarse
                                 int W, int H, float fx, float fy, float cx, float cy, float z_near, float z_far, int Kc, int Kf,
                                 int Kfd, float depth_std, int white_bkgd, int lindisp, const float *u1, const float *u2,
                                 const float *u3, const float *n4, unsigned long long seed, float *rgb_c, float *depth_c,
-                                float *weights_c, float *rgb_f, float *depth_f, float *weights_f, void *workspace, void *stream) {
+                                float *weights_c, float *rgb_f, float *depth_f, float *weights_f, void *workspace,
+                                const PnrSplitAux *aux_coarse, const PnrSplitAux *aux_fine, void *stream) {
     if (!scene || NV < 0 || W <= 0 || H <= 0) return pnr_fail(PNR_E_INVALID, "pnr_render_views: bad sizes");
     if (NV == 0) return PNR_OK;
     if (!poses_c2w) return pnr_fail(PNR_E_INVALID, "pnr_render_views: null poses");
@@ -486,5 +488,6 @@ extern "C" int pnr_render_views(const PnrScene *scene, const void *packed_coarse
     const int per_obj = (int)(R / scene->SB);
     const NoiseSrc ns = (u1 || u2 || u3 || n4) ? explicit_noise(u1, u2, u3, n4) : seeded_noise(seed, 0, per_obj, per_obj);
     return render_impl(scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, rs, ns, (int)R, per_obj, Kc, Kf, Kfd,
-                       depth_std, white_bkgd, lindisp, rgb_c, depth_c, weights_c, rgb_f, depth_f, weights_f, workspace, stream);
+                       depth_std, white_bkgd, lindisp, rgb_c, depth_c, weights_c, rgb_f, depth_f, weights_f, workspace, aux_coarse, aux_fine,
+                       stream);
 }

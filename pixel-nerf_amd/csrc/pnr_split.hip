@@ -21,7 +21,7 @@
 // are B fragments as they are), while the same fragments go to the operand images for the other waves: stage_own / gemm_split_rot.
 //
 // Kernels of this file:
-//   eval_split_kernel<RAYS, MV, TIMING, TRAIN, GUARD, SC>   the fused network (SC: the stream-scale / range-probe forms, below).  GUARD = the fp16-range guard (pnr_saturation_guard): the
+//   eval_split_kernel<RAYS, MV, TIMING, TRAIN, GUARD, SC>   the fused network (SC: the stream-scale / range-probe forms, below).  GUARD = the fp16-range guard (PnrSplitAux.sat_flag): the
 //                                                same bits, plus one flag bit per layer whose operand image received a value >= 65504.
 //                                                TRAIN = the fp32-class TRAINING forward: the same launch also
 //                                                copies every wide linear's (head, tail) operand image out of LDS (relu(x) /
@@ -176,7 +176,7 @@ __device__ __forceinline__ void gemm_split(f32x16 (&acc)[IT][JT], const char *sm
 // register, times -1, plus v; result rounded once to f16) -- the same bits as convert-back + subtract + convert
 // (v - head is exact in fp32), 5 VALU operations per pair instead of 8.
 // GUARD: `amax` (a packed f16 pair) follows the largest HEAD produced, one v_pk_maximum3_f16 per FOUR values (gfx950; the
-// IEEE-2019 maximum: a NaN head sticks): the fp16-range guard of pnr_saturation_guard().  Half the VALU cost of following the
+// IEEE-2019 maximum: a NaN head sticks): the fp16-range guard (PnrSplitAux.sat_flag).  Half the VALU cost of following the
 // fp32 inputs with v_max3_f32 (round 5), which is what lets the guard run on every inference call (round 6).  Heads are >= 0
 // behind the relu, so no magnitudes are needed; a head of 65504 means v >= 65488 (round to nearest): the guard fires 16 below
 // the exact saturation point.
@@ -501,7 +501,7 @@ __device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *
 //   x *= c behind lin_in + table 0 | x += c t for tables 1, 2 | block biases arrive as c b (pack_bias_kernel) |
 //   the lin_out partial sum times 2^(s - t) in front of lin_out's bias (t: the lift lin_out's weights were packed with, pnr_pack.hip)
 // -- four fp32 sites, all exact; nothing stored as fp16 is shifted, the hidden weights are untouched, view pooling (mean and
-// max) is homogeneous.  SC = 2: the same with the range probe (pnr_range_probe): the fp32 values about to enter split8 -- the
+// max) is homogeneous.  SC = 2: the same with the range probe (PnrSplitAux.range_probe): the fp32 values about to enter split8 -- the
 // accumulator tiles a stage_own / lin_out is about to split -- are followed with v_max3_f32 in FRONT of the stage (relu'd: the
 // running maximum starts at 0), the round-5 form of the guard; it says how far beyond the range a value went, which saturated
 // heads cannot.  Per-layer maxima are collected in 12 LDS words behind the tile map (non-negative floats order like their bit
@@ -600,7 +600,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
         dump_image<MT>(smem, ST::A_HI, head + (size_t)rows * (D_HID * 2), tr_rows_left, wv, lane);
         dump_image<MT>(smem, ST::A_LO, head + total + (size_t)rows * (D_HID * 2), tr_rows_left, wv, lane);
     };
-    // fp16-range guard (GUARD instantiation, pnr_saturation_guard): bit l of sat_bits = "a head of 65504 (the largest fp16: heads
+    // fp16-range guard (GUARD instantiation, PnrSplitAux.sat_flag): bit l of sat_bits = "a head of 65504 (the largest fp16: heads
     // saturate there; i.e. a value >= 65488) went into the operand image of layer l" (2b: relu(x) entering blocks[b].fc_0, 2b+1: relu(net) entering
     // fc_1, 10: the stream in front of lin_out), bit 11 = a non-finite network output
     [[maybe_unused]] uint32_t sat_bits = 0;
@@ -1128,7 +1128,46 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) bwd_split_kernel(const BwdSp
     }
 }
 
-static int split_launch(const PnrScene *s, const void *packed, const void *tables, EvalParams &q, bool rays, hipStream_t st) {
+// The instantiation of eval_split_kernel for one launch.  form: 0 = plain, 1 = stream scale, 2 = range probe (at any scale).
+// The scaled and probe forms exist as the guard-capable instantiation only (it reports when EvalParams::sat_flag is set); the
+// training instantiation takes ray samples at form 0.  nullptr: no such instantiation.
+using SplitKernel = void (*)(EvalParams);
+template <bool RAYS, bool MV>
+static SplitKernel split_kernel_of(bool train, bool guard, int form) {
+    if (train) {
+        if constexpr (RAYS)
+            if (form == 0) return guard ? eval_split_kernel<true, MV, false, true, true> : eval_split_kernel<true, MV, false, true>;
+        return nullptr;
+    }
+    switch (form) {
+    case 0: return guard ? eval_split_kernel<RAYS, MV, false, false, true> : eval_split_kernel<RAYS, MV>;
+    case 1: return eval_split_kernel<RAYS, MV, false, false, true, 1>;
+    case 2: return eval_split_kernel<RAYS, MV, false, false, true, 2>;
+    }
+    return nullptr;
+}
+static SplitKernel split_kernel(bool rays, bool mv, bool train, bool guard, int form) {
+    return mv ? (rays ? split_kernel_of<true, true>(train, guard, form) : split_kernel_of<false, true>(train, guard, form))
+              : (rays ? split_kernel_of<true, false>(train, guard, form) : split_kernel_of<false, false>(train, guard, form));
+}
+
+int check_split_aux(const PnrSplitAux *aux, int precision, const char *entry) {
+    if (!aux) return PNR_OK;
+    char msg[256];
+    if (aux->stream_scale_log2 < 0 || aux->stream_scale_log2 > STREAM_SCALE_MAX) {
+        std::snprintf(msg, sizeof(msg), "%s: PnrSplitAux.stream_scale_log2 must be in [0, 30]", entry);
+        return pnr_fail(PNR_E_INVALID, msg);
+    }
+    if (precision != PNR_PREC_F16X3 && (aux->stream_scale_log2 || aux->sat_flag || aux->range_probe)) {
+        std::snprintf(msg, sizeof(msg), "%s: PnrSplitAux (stream_scale_log2, sat_flag, range_probe) belongs to PNR_PREC_F16X3 only", entry);
+        return pnr_fail(PNR_E_INVALID, msg);
+    }
+    return PNR_OK;
+}
+
+// aux: checked by the entry (check_split_aux)
+static int split_launch(const PnrScene *s, const void *packed, const void *tables, EvalParams &q, bool rays, const PnrSplitAux *aux,
+                        hipStream_t st) {
     if (!s || !packed || !tables || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: null argument");
     if (s->SB <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: bad scene shape");
     if (s->NS <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: NS must be positive");
@@ -1153,37 +1192,18 @@ static int split_launch(const PnrScene *s, const void *packed, const void *table
     const long long nt = (q.P + MT - 1) / MT;
     q.ntiles = (int)nt;
     const int grid = (int)(nt < ncu ? nt : ncu);
-    auto k = mv ? (rays ? eval_split_kernel<true, true> : eval_split_kernel<false, true>)
-                : (rays ? eval_split_kernel<true, false> : eval_split_kernel<false, false>);
-    // fp16-range guard armed on this host thread (pnr_saturation_guard): the instantiations that follow the largest value
-    // entering every operand image; word `slot` of the caller's flag array (0: a coarse-network launch, 1: a fine-network one)
-    unsigned int *guard = saturation_guard_word();
-    q.sat_flag = guard;
-    if (guard)
-        k = mv ? (rays ? eval_split_kernel<true, true, false, false, true> : eval_split_kernel<false, true, false, false, true>)
-               : (rays ? eval_split_kernel<true, false, false, false, true> : eval_split_kernel<false, false, false, false, true>);
-    // stream scale (blobs packed at s > 0, noted by pnr_pack_mlp_split) and the range probe (armed on this host thread, any s)
-    const int scale = stream_scale_of(packed);
-    float *probe = range_probe_words();
-    q.probe = reinterpret_cast<unsigned int *>(probe);
-    int lds_extra = 0;
-    if (probe && !q.f_x5) {
-        k = mv ? (rays ? eval_split_kernel<true, true, false, false, true, 2> : eval_split_kernel<false, true, false, false, true, 2>)
-               : (rays ? eval_split_kernel<true, false, false, false, true, 2> : eval_split_kernel<false, false, false, false, true, 2>);
-        lds_extra = 64;  // the probe's 12 words behind the tile map
-    } else if (scale) {
-        k = mv ? (rays ? eval_split_kernel<true, true, false, false, true, 1> : eval_split_kernel<false, true, false, false, true, 1>)
-               : (rays ? eval_split_kernel<true, false, false, false, true, 1> : eval_split_kernel<false, false, false, false, true, 1>);
-    }
-    if (q.f_x5) {  // training forward: the same kernel + fp32 rows of what the backward keeps
-        if (scale) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: training at a stream scale is not supported (pack the blob with stream_scale_log2 = 0)");
-        if (!rays) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: the training instantiation takes ray samples on 64-point tiles");
-        k = mv ? (guard ? eval_split_kernel<true, true, false, true, true> : eval_split_kernel<true, true, false, true>)
-               : (guard ? eval_split_kernel<true, false, false, true, true> : eval_split_kernel<true, false, false, true>);
-    }
+    // guard word, stream scale and probe words of this network: the caller's (PnrSplitAux).  The training forward (q.f_x5: the
+    // same kernel + what the backward keeps) has no scaled form (its entry refuses a scale) and no probe form (the pointer is unused).
+    const bool train = q.f_x5 != nullptr;
+    q.sat_flag = aux ? aux->sat_flag : nullptr;
+    q.probe = aux ? reinterpret_cast<unsigned int *>(aux->range_probe) : nullptr;
+    const int form = q.probe && !train ? 2 : aux && aux->stream_scale_log2 ? 1 : 0;
+    SplitKernel k = split_kernel(rays, mv, train, q.sat_flag != nullptr, form);
+    if (!k) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: the training instantiation takes ray samples at stream scale 0");
+    const int lds_extra = form == 2 ? 64 : 0;  // the probe's 12 words behind the tile map
 #ifdef PNR_VARIANT
     if (q.tim) {  // diagnostic instantiation (pnr_debug_phase_timing_split): single view, rays
-        if (scale || probe) return pnr_fail(PNR_E_INVALID, "phase timing: unscaled blobs, probe disarmed");
+        if (form) return pnr_fail(PNR_E_INVALID, "phase timing: unscaled blobs, no probe");
         if (mv || !rays) return pnr_fail(PNR_E_INVALID, "phase timing: single-view ray launches only");
         k = eval_split_kernel<true, false, true>;
     }
@@ -1242,20 +1262,21 @@ int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long l
 extern "C" size_t pnr_packed_mlp_split_bytes(void) { return 2 * pnr::PACKED_BYTES; }
 
 int pnr::eval_samples_split_src(const PnrScene *scene, const void *packed_split, const void *tables_f32, const RaySrc &src,
-                                const float *z, int R, int rays_per_obj, int K, float *rgbsigma, hipStream_t stream) {
+                                const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux,
+                                hipStream_t stream) {
     if (R < 0 || K <= 0 || rays_per_obj <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split: bad sizes");
     if (R > 0 && ((!src.rays && !src.poses) || !z)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split: null rays/z");
     if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split: R != SB * rays_per_obj");
     pnr::EvalParams q = {};
     q.rays = src.rays; q.cam = src; q.cam.rays = nullptr;
     q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
-    return pnr::split_launch(scene, packed_split, tables_f32, q, true, stream);
+    return pnr::split_launch(scene, packed_split, tables_f32, q, true, aux, stream);
 }
 
 // training forward of the fp32-class path (pnr_f32.hip, pnr_eval_ray_samples_split_train): outputs + what the backward keeps
 int pnr::eval_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *rays,
                                   const float *z, int R, int rays_per_obj, int K, float *rgbsigma, void *const *img_a, void *const *img_n,
-                                  float *x5, void *masks, hipStream_t stream) {
+                                  float *x5, void *masks, const PnrSplitAux *aux, hipStream_t stream) {
     if (!rays || !z || !img_a || !img_n || !x5 || !masks) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null argument");
     pnr::EvalParams q = {};
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
@@ -1265,15 +1286,16 @@ int pnr::eval_samples_split_train(const PnrScene *scene, const void *packed_spli
     }
     q.f_x5 = x5;
     q.d_mask = (unsigned long long *)masks;
-    return pnr::split_launch(scene, packed_split, tables_f32, q, true, stream);
+    return pnr::split_launch(scene, packed_split, tables_f32, q, true, aux, stream);
 }
 
 extern "C" int pnr_eval_ray_samples_split(const PnrScene *scene, const void *packed_split, const void *tables_f32,
                                           const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
-                                          void *stream) {
+                                          const PnrSplitAux *aux, void *stream) {
+    if (int rc = pnr::check_split_aux(aux, PNR_PREC_F16X3, "pnr_eval_ray_samples_split")) return rc;
     pnr::RaySrc src = {};
     src.rays = rays;
-    return pnr::eval_samples_split_src(scene, packed_split, tables_f32, src, z, R, rays_per_obj, K, rgbsigma, (hipStream_t)stream);
+    return pnr::eval_samples_split_src(scene, packed_split, tables_f32, src, z, R, rays_per_obj, K, rgbsigma, aux, (hipStream_t)stream);
 }
 
 #ifdef PNR_VARIANT
@@ -1285,16 +1307,17 @@ extern "C" int pnr_debug_phase_timing_split(const PnrScene *scene, const void *p
     if (!tim || !rays || !z) return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing_split: null argument");
     pnr::EvalParams q = {};
     q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma; q.tim = tim;
-    return pnr::split_launch(scene, packed_split, tables_f32, q, true, (hipStream_t)stream);
+    return pnr::split_launch(scene, packed_split, tables_f32, q, true, nullptr, (hipStream_t)stream);
 }
 #endif
 
 extern "C" int pnr_eval_points_split(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *xyz,
-                                     const float *viewdirs, int B, float *rgbsigma, void *stream) {
+                                     const float *viewdirs, int B, float *rgbsigma, const PnrSplitAux *aux, void *stream) {
+    if (int rc = pnr::check_split_aux(aux, PNR_PREC_F16X3, "pnr_eval_points_split")) return rc;
     if (B < 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_split: bad sizes");
     if (B > 0 && (!xyz || !viewdirs)) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_split: null xyz/viewdirs");
     pnr::EvalParams q = {};
     q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B > 0 ? B : 1;
     q.P = scene ? (long long)scene->SB * B : 0; q.out = rgbsigma;
-    return pnr::split_launch(scene, packed_split, tables_f32, q, false, (hipStream_t)stream);
+    return pnr::split_launch(scene, packed_split, tables_f32, q, false, aux, (hipStream_t)stream);
 }

@@ -296,9 +296,10 @@ class PixelNeRFNet(torch.nn.Module):
         mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
         return mlp.packed(self._effective_precision(), folded=self._folding() if folded is None else folded, training_pass=training_pass)
 
-    def tables(self, coarse=True):
+    def tables(self, coarse=True, guard_slot=None):
         """lin_z folded into the current scene's grid for the coarse / fine network (None when fold is off);
-        rebuilt when encode() or the network's parameters change."""
+        rebuilt when encode() or the network's parameters change.  guard_slot: the word of an armed fp16-range guard a fold that
+        happens now reports into (ops.fold_latent; None = the guard's current slot)."""
         if not self._folding():
             return None
         mlp = self.mlp_coarse if (coarse or self.mlp_fine is None) else self.mlp_fine
@@ -309,7 +310,7 @@ class PixelNeRFNet(torch.nn.Module):
         slot = "coarse" if mlp is self.mlp_coarse else "fine"
         hit = self._tables.get(slot)
         if hit is None or hit[0] != key:
-            self._tables[slot] = (key, ops.fold_latent(sc, dict(mlp.state_dict()), self._effective_precision()), sc)
+            self._tables[slot] = (key, ops.fold_latent(sc, dict(mlp.state_dict()), self._effective_precision(), slot=guard_slot), sc)
         return self._tables[slot][1]
 
     def training_tables(self, coarse, rays, z, scene=None):

@@ -175,9 +175,11 @@ def pack_mlp(state, precision="f16", backward=False, folded=False, weights=None,
     return out if reuse else PackedMLP(buf, prec, folded=folded)
 
 
-def fold_latent(scene, state, precision="f16"):
+def fold_latent(scene, state, precision="f16", slot=None):
     """Per-texel tables T_b = W_z[b] . grid + b_z[b] (b = 0..2) of one network for one encoded scene:
-    (3, SB*NS, Hl, Wl, 512) 16-bit, hidden features in storage order.  Re-run when the grid or lin_z change."""
+    (3, SB*NS, Hl, Wl, 512) 16-bit, hidden features in storage order.  Re-run when the grid or lin_z change.
+    slot: 'f16x3' under an armed fp16-range guard -- the word bit 12 goes to (0 = coarse network, 1 = fine; None = the
+    guard's current slot, saturation_guard_slot)."""
     lib = _lib.load()
     prec = _lib.PRECISIONS[precision] if isinstance(precision, str) else int(precision)
     if prec == _lib.PREC_F32:
@@ -188,7 +190,8 @@ def fold_latent(scene, state, precision="f16"):
         tables = torch.empty((3, NV, Hl, Wl, 512), dtype=torch.float32, device=scene.device)
         assert tables.numel() * 4 == lib.pnr_folded_tables_f32_bytes(scene.ref)
         with torch.cuda.device(scene.device):
-            _lib.check(lib.pnr_fold_latent_f32(scene.ref, ctypes.byref(w), _p(tables), _stream()), "pnr_fold_latent_f32")
+            _lib.check(lib.pnr_fold_latent_f32(scene.ref, ctypes.byref(w), _p(tables), _sat_word(scene.device, slot), _stream()),
+                       "pnr_fold_latent_f32")
         return tables
     dt = torch.float16 if prec == _lib.PREC_F16 else torch.bfloat16
     tables = torch.empty((3, NV, Hl, Wl, 512), dtype=dt, device=scene.device)
@@ -214,7 +217,7 @@ def fold_latent_rows(scene, state, rays, z, tables):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=scene.device)
     with torch.cuda.device(scene.device):
         _lib.check(lib.pnr_fold_latent_f32_rows(scene.ref, ctypes.byref(w), _p(rays), _p(z), R, max(R // scene.SB, 1), z.shape[1], _p(tables),
-                                                _p(ws), nbytes, _stream()), "pnr_fold_latent_f32_rows")
+                                                _p(ws), nbytes, _sat_word(scene.device), _stream()), "pnr_fold_latent_f32_rows")
     return tables
 
 
@@ -346,7 +349,8 @@ def eval_ray_samples(scene, packed, rays, z, tables=None):
         _check_split_tables(tables)
         with torch.cuda.device(rays.device):
             _lib.check(lib.pnr_eval_ray_samples_split(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), R,
-                                                      max(R // scene.SB, 1), K, _p(out), _stream()), "pnr_eval_ray_samples_split")
+                                                      max(R // scene.SB, 1), K, _p(out), _split_aux(packed, rays.device), _stream()),
+                       "pnr_eval_ray_samples_split")
         return out
     with torch.cuda.device(rays.device):
         if tables is not None:
@@ -413,8 +417,8 @@ def eval_points(scene, packed, xyz, viewdirs, tables=None):
     if packed.precision == _lib.PREC_F16X3:
         _check_split_tables(tables)
         with torch.cuda.device(xyz.device):
-            _lib.check(lib.pnr_eval_points_split(scene.ref, packed.ptr, _p(tables), _p(xyz), _p(viewdirs), B, _p(out), _stream()),
-                       "pnr_eval_points_split")
+            _lib.check(lib.pnr_eval_points_split(scene.ref, packed.ptr, _p(tables), _p(xyz), _p(viewdirs), B, _p(out),
+                                                 _split_aux(packed, xyz.device), _stream()), "pnr_eval_points_split")
         return out
     with torch.cuda.device(xyz.device):
         if tables is not None:
@@ -559,12 +563,13 @@ def render_forward(scene, packed_coarse, packed_fine, rays, n_coarse, n_fine, n_
     if packed_fine is not None:
         _check_fold(packed_fine, tf, "render_forward")
     pf = packed_fine.ptr if packed_fine is not None else None
+    aux = _split_aux(packed_coarse, dev, 0), _split_aux(packed_fine, dev, 1)
     with torch.cuda.device(dev):
         if noise is None:
             _lib.check(lib.pnr_render_forward_seeded(
                 scene.ref, packed_coarse.ptr, _p(tc), pf, _p(tf), packed_coarse.precision, _p(rays), R, per_obj, Kc, Kf, Kfd,
                 float(depth_std), int(bool(white_bkgd)), int(bool(lindisp)), int(seed) & (2 ** 64 - 1), int(ray_id_offset),
-                int(ray_id_stride), _p(c[0]), _p(c[1]), _p(c[2]), _p(f[0]), _p(f[1]), _p(f[2]), _p(ws), _stream()),
+                int(ray_id_stride), _p(c[0]), _p(c[1]), _p(c[2]), _p(f[0]), _p(f[1]), _p(f[2]), _p(ws), aux[0], aux[1], _stream()),
                 "pnr_render_forward_seeded")
         else:
             u1, u2, u3, n4 = _explicit_noise(noise, R, Kc, Kf, Kfd)
@@ -572,7 +577,8 @@ def render_forward(scene, packed_coarse, packed_fine, rays, n_coarse, n_fine, n_
                 _lib.check(lib.pnr_render_forward_folded(
                     scene.ref, packed_coarse.ptr, _p(tc), pf, _p(tf), packed_coarse.precision, _p(rays), R, per_obj, Kc, Kf, Kfd,
                     float(depth_std), int(bool(white_bkgd)), int(bool(lindisp)), _p(u1), _p(u2), _p(u3), _p(n4),
-                    _p(c[0]), _p(c[1]), _p(c[2]), _p(f[0]), _p(f[1]), _p(f[2]), _p(ws), _stream()), "pnr_render_forward_folded")
+                    _p(c[0]), _p(c[1]), _p(c[2]), _p(f[0]), _p(f[1]), _p(f[2]), _p(ws), aux[0], aux[1], _stream()),
+                    "pnr_render_forward_folded")
             else:
                 _lib.check(lib.pnr_render_forward(
                     scene.ref, packed_coarse.ptr, pf, packed_coarse.precision, _p(rays), R, per_obj, Kc, Kf, Kfd,
@@ -680,12 +686,13 @@ def render_views(scene, packed_coarse, packed_fine, poses_c2w, width, height, fo
         u1, u2, u3, n4 = _explicit_noise(noise, R, Kc, Kf, Kfd)
     co, fo = _render_outputs(R, Kc, Kf, want_weights, dev)
     ws = torch.empty(max(lib.pnr_render_views_workspace_bytes(NV, W, H, Kc, Kf), 16), dtype=torch.uint8, device=dev)
+    aux = _split_aux(packed_coarse, dev, 0), _split_aux(packed_fine, dev, 1)
     with torch.cuda.device(dev):
         _lib.check(lib.pnr_render_views(
             scene.ref, packed_coarse.ptr, _p(tc), packed_fine.ptr if packed_fine is not None else None, _p(tf),
             packed_coarse.precision, _p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), Kc, Kf, Kfd,
             float(depth_std), int(bool(white_bkgd)), int(bool(lindisp)), _p(u1), _p(u2), _p(u3), _p(n4), int(seed) & (2 ** 64 - 1),
-            _p(co[0]), _p(co[1]), _p(co[2]), _p(fo[0]), _p(fo[1]), _p(fo[2]), _p(ws), _stream()), "pnr_render_views")
+            _p(co[0]), _p(co[1]), _p(co[2]), _p(fo[0]), _p(fo[1]), _p(fo[2]), _p(ws), aux[0], aux[1], _stream()), "pnr_render_views")
     return _render_result(co, fo, Kf, want_weights)
 
 
@@ -755,25 +762,30 @@ def grid_index_backward(latent_nhwc, uv, g_out, want_latent=True, want_uv=True):
 
 
 # ---------------------------------------------------------------- fp16-range guard of the fp32-class kernels
-# include/pixelnerf_hip.h, pnr_saturation_guard: while armed, the split-operand network kernels note every layer whose operand
-# image received a value >= 65504 (fp16 heads saturate there: the result leaves the reference's fp32 arithmetic class) or whose
-# output is not finite.  The flag words travel to pinned host memory with an asynchronous copy and are looked at on a later
+# include/pixelnerf_hip.h, PnrSplitAux.sat_flag: a split-operand network launch that is given a flag word notes every layer whose
+# operand image received a value >= 65504 (fp16 heads saturate there: the result leaves the reference's fp32 arithmetic class) or
+# whose output is not finite.  "Armed" and the slot are state of THIS module (the package starts no threads); the library is told
+# per launch (_split_aux).  The flag words travel to pinned host memory with an asynchronous copy and are looked at on a later
 # call -- no host synchronisation, like the parameter content check of ResnetFC.
 _SAT = {}
 SAT_LAYER_NAMES = ([f"relu(x) entering blocks.{b}.fc_0" if i == 0 else f"relu(net) entering blocks.{b}.fc_1" for b in range(5) for i in (0, 1)]
                    + ["the stream in front of lin_out", "a non-finite network output", "the feature grid / lin_z weights of the per-texel fold"])
 
 
+def _device_index(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
 def _sat_state(device, owner=None):
     """flag words + pinned host copies, per (device, owner): two networks on one device do not read each other's verdicts.
     pending: [(event, pinned words)] of guarded calls whose flag copy is still on its way; carry: bits of copies that arrived
     but were not handed to a poll yet.  A guarded call never overwrites the words of an earlier one."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = _device_index(device)
     key = (idx, owner)
     st = _SAT.get(key)
     if st is None:
         st = dict(flags=torch.zeros(2, dtype=torch.int32, device=torch.device("cuda", idx)),
-                  pool=[], pending=[], carry=[0, 0], seen=False, armed=False)
+                  pool=[], pending=[], carry=[0, 0], seen=False, armed=False, slot=0)
         _SAT[key] = st
     return st
 
@@ -801,20 +813,42 @@ def saturation_guard_release(owner):
         _SAT.pop(key, None)
 
 
+def _sat_armed(device):
+    idx = _device_index(device)
+    return next((v for (d, o), v in _SAT.items() if d == idx and v["armed"]), None)
+
+
+def _sat_word(device, slot=None):
+    """address of flag word `slot` (None = the current slot) of the guard armed on `device`, or None when none is"""
+    st = _sat_armed(device)
+    return None if st is None else st["flags"].data_ptr() + 4 * (st["slot"] if slot is None else slot)
+
+
+def _split_aux(packed, device, slot=None):
+    """-> the PnrSplitAux argument of one network's launch: the scale `packed` was packed at, flag word `slot` of the guard armed
+    on `device` and the probe words of that slot (None = the current slots: the direct entries; the render entries say 0 for the
+    coarse and 1 for the fine network).  None (a NULL pointer) for a missing network and every precision but 'f16x3'."""
+    if packed is None or packed.precision != _lib.PREC_F16X3:
+        return None
+    aux = _lib.PnrSplitAux(stream_scale_log2=packed.stream_scale, sat_flag=_sat_word(device, slot))
+    probe = _PROBE.get(_device_index(device))
+    if probe is not None and probe["armed"]:
+        aux.range_probe = probe["buf"].data_ptr() + 4 * PROBE_WORDS * (probe["slot"] if slot is None else slot)
+    return ctypes.byref(aux)
+
+
 def saturation_guard_arm(device, owner=None):
-    """arm the guard for the launches this host thread makes next on `device` (until saturation_guard_disarm)"""
+    """arm the guard for the launches made next on `device` (until saturation_guard_disarm), slot 0"""
     st = _sat_state(device, owner)
-    _lib.check(_lib.load().pnr_saturation_guard(_p(st["flags"])), "pnr_saturation_guard")
-    st["armed"] = True
+    st["armed"], st["slot"] = True, 0
 
 
 def saturation_guard_slot(device, slot, owner=None):
-    """while armed: direct network launches (pnr_eval_*_split*) report into word `slot` (0 = coarse network, 1 = fine network);
-    the render entries pick the word themselves"""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    st = next((v for (d, o), v in _SAT.items() if d == idx and v["armed"]), None) if owner is None else _sat_state(device, owner)
+    """while armed: direct network launches (eval_ray_samples, eval_points, eval_ray_samples_split_train) and the folds report into
+    word `slot` (0 = coarse network, 1 = fine network); the render entries pick the word themselves"""
+    st = _sat_armed(device) if owner is None else _sat_state(device, owner)
     if st is not None and st["armed"]:
-        _lib.check(_lib.load().pnr_saturation_guard(ctypes.c_void_p(st["flags"].data_ptr() + 4 * (1 if slot else 0))), "pnr_saturation_guard")
+        st["slot"] = 1 if slot else 0
 
 
 def saturation_guard_disarm(device, owner=None):
@@ -822,7 +856,6 @@ def saturation_guard_disarm(device, owner=None):
     call gets its own pinned words: under PIXELNERF_SATURATION_GUARD=always the previous call's copy is usually still in flight
     when the next one ends, and re-using one buffer lost its bits."""
     st = _sat_state(device, owner)
-    _lib.check(_lib.load().pnr_saturation_guard(None), "pnr_saturation_guard")
     if st["armed"]:
         st["armed"] = False
         if len(st["pending"]) >= 8:  # bounded: fold the oldest copies in (blocks only when the GPU is 8 guarded calls behind)
@@ -854,43 +887,43 @@ def describe_saturation(bits):
 
 
 # ---------------------------------------------------------------- range probe of the same kernels (calibration of a stream scale)
-# include/pixelnerf_hip.h, pnr_range_probe: while armed, the split-operand inference kernels run a calibration instantiation
-# that reports, per network slot, the largest value that entered each of the 11 operand images (true units) + a non-finite mark.
+# include/pixelnerf_hip.h, PnrSplitAux.range_probe: a split-operand inference launch that is given probe words runs a calibration
+# instantiation that reports the largest value that entered each of the 11 operand images (true units) + a non-finite mark.  One
+# entry per device: 2 x 12 words (slot 0 coarse network, slot 1 fine), "armed" and the slot of the direct entries.
 _PROBE = {}
 PROBE_WORDS = 12
 
 
-def _probe_buf(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    buf = _PROBE.get(idx)
-    if buf is None:
-        buf = torch.zeros(2 * PROBE_WORDS, dtype=torch.float32, device=torch.device("cuda", idx))
-        _PROBE[idx] = buf
-    return buf
+def _probe_state(device):
+    idx = _device_index(device)
+    st = _PROBE.get(idx)
+    if st is None:
+        st = _PROBE[idx] = dict(buf=torch.zeros(2 * PROBE_WORDS, dtype=torch.float32, device=torch.device("cuda", idx)), armed=False, slot=0)
+    return st
 
 
 def range_probe_arm(device):
-    """arm the probe for the launches this host thread makes next on `device` (until range_probe_disarm); zeroes the maxima"""
-    buf = _probe_buf(device)
-    with torch.cuda.device(buf.device):
-        buf.zero_()
-    _lib.check(_lib.load().pnr_range_probe(_p(buf)), "pnr_range_probe")
+    """arm the probe for the launches made next on `device` (until range_probe_disarm), slot 0; zeroes the maxima"""
+    st = _probe_state(device)
+    with torch.cuda.device(st["buf"].device):
+        st["buf"].zero_()
+    st["armed"], st["slot"] = True, 0
 
 
 def range_probe_slot(device, slot):
-    """while armed: direct network launches (pnr_eval_*_split) report into slot 0 (coarse network) or 1 (fine network); the
-    render entries pick the slot themselves"""
-    buf = _probe_buf(device)
-    _lib.check(_lib.load().pnr_range_probe(ctypes.c_void_p(buf.data_ptr() + 4 * PROBE_WORDS * (1 if slot else 0))), "pnr_range_probe")
+    """while armed: direct network launches (eval_ray_samples, eval_points) report into slot 0 (coarse network) or 1 (fine
+    network); the render entries pick the slot themselves"""
+    _probe_state(device)["slot"] = 1 if slot else 0
 
 
 def range_probe_disarm(device=None):
-    _lib.check(_lib.load().pnr_range_probe(None), "pnr_range_probe")
+    for st in _PROBE.values():
+        st["armed"] = False
 
 
 def range_probe_read(device):
     """-> ([11 maxima + non-finite mark] of the coarse slot, the same of the fine slot) as Python floats.  Synchronises."""
-    w = _probe_buf(device).tolist()
+    w = _probe_state(device)["buf"].tolist()
     return w[:PROBE_WORDS], w[PROBE_WORDS:]
 
 
@@ -1203,7 +1236,8 @@ def eval_ray_samples_split_train(scene, packed, tables, rays, z):
     out = torch.empty((R, K, 4), dtype=torch.float32, device=rays.device)
     with torch.cuda.device(rays.device):
         _lib.check(lib.pnr_eval_ray_samples_split_train(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), R, max(R // scene.SB, 1), K,
-                                                        _p(out), ctypes.byref(saved.struct), _stream()), "pnr_eval_ray_samples_split_train")
+                                                        _p(out), ctypes.byref(saved.struct), _split_aux(packed, rays.device), _stream()),
+                       "pnr_eval_ray_samples_split_train")
     return out, saved
 
 

@@ -211,12 +211,9 @@ class NeRFRenderer(torch.nn.Module):
                     pk_c, pk_f = model.packed(True), (model.packed(False) if own_fine else None)  # before tables(): see PixelNeRFNet.tables
                     guarded = model._guard_begin()  # fp16-range guard of the fp32-class kernels: first call on new weights / scene
                     try:
-                        tc = model.tables(True)   # (a fold that happens now is guarded too: grid values / lin_z weights)
-                        if guarded:
-                            ops.saturation_guard_slot(rays.device, 1)
-                        tf = model.tables(False) if (own_fine and tc is not None) else None
-                        if guarded:
-                            ops.saturation_guard_slot(rays.device, 0)
+                        # (a fold that happens now is guarded too -- grid values / lin_z weights: word 0 coarse, word 1 fine)
+                        tc = model.tables(True, guard_slot=0)
+                        tf = model.tables(False, guard_slot=1) if (own_fine and tc is not None) else None
                         res = ops.render_forward(model.scene(), pk_c, pk_f,
                                                  rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
                                                  white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights,

@@ -209,7 +209,7 @@ def test_split_operands_saturate_instead_of_overflowing(ops, dev):
     assert torch.isfinite(out).all()
 
 
-# ---------------------------------------------------------------- fp16-range guard (pnr_saturation_guard)
+# ---------------------------------------------------------------- fp16-range guard (PnrSplitAux.sat_flag)
 def _guarded_eval(ops, dev, state, name="sn64", coarse_slot=0, fold_under_guard=False):
     s, _ = scene_for(name)
     sc = dscene(ops, dev, name)

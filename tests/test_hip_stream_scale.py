@@ -1,6 +1,6 @@
 """
 GPU tests (-m gpu) of the power-of-two stream scale of precision "f16x3" (include/pixelnerf_hip.h "stream scale";
-pnr_split.hip, the SC forms of eval_split_kernel) and of its range probe (pnr_range_probe).
+pnr_split.hip, the SC forms of eval_split_kernel) and of its range probe (PnrSplitAux.range_probe).
 
 Fixture: the homogeneous blow-up of test_stream_scale_host.py -- the hidden stream is A times the base network's, the outputs
 are the base network's.  Every comparison is against the CPU oracle at the SAME (blown-up) weights, held to the fp32-class bars
@@ -126,11 +126,13 @@ def test_scale_zero_is_the_unscaled_blob_and_the_unscaled_bits(ops, dev, name):
     tab = ops.fold_latent(sc, state, "f16x3")
     xyz, vd = (t.to(dev) for t in points(dev, name))
     assert torch.equal(ops.eval_points(sc, a, xyz, vd, tables=tab), ops.eval_points(sc, b, xyz, vd, tables=tab))
-    # a blob address that once held a scaled stream and is packed at 0 again runs unscaled again
+    # the bytes plus the s passed with the launch decide, nothing else: a buffer that held a scaled stream, packed at 0 again by
+    # the caller and declared so (PackedMLP.stream_scale is what ops hands to the launch), is the unscaled blob and runs unscaled
     c = ops.pack_mlp(state, "f16x3", stream_scale=5)
     lib = ops._lib.load()
     w, keep = ops._weights_struct(state)
     ops._lib.check(lib.pnr_pack_mlp_split(ctypes.byref(w), ops._p(c.buf), ops._stream()), "pnr_pack_mlp_split")
+    c.stream_scale = 0
     assert torch.equal(c.buf, a.buf)
     assert torch.equal(ops.eval_points(sc, c, xyz, vd, tables=tab), ops.eval_points(sc, a, xyz, vd, tables=tab))
 
@@ -365,7 +367,7 @@ def test_training_and_sharding_refuse_what_they_cannot_do(ops, dev):
         net(xyz, coarse=True, viewdirs=vd)
     net.stream_scale = 0  # ... and trains again at scale 0
     assert net(xyz, coarse=True, viewdirs=vd).requires_grad
-    # the training forward takes a blob, not the weight struct: a blob packed at a scale is refused by its address
+    # the training forward takes a blob and the s it was packed with (PnrSplitAux.stream_scale_log2): any s != 0 is refused
     sc = dscene(ops, dev, "sn64")
     state = {k: v.to(dev) for k, v in mlp_params(11).items()}
     pk, tab = ops.pack_mlp(state, "f16x3", stream_scale=3), ops.fold_latent(sc, state, "f16x3")
@@ -393,6 +395,62 @@ def test_training_and_sharding_refuse_what_they_cannot_do(ops, dev):
         torch.manual_seed(3)
         rgb1, depth1 = rend.bind_parallel(net, gpus=None, simple_output=True)(rays.to(dev))
     assert torch.equal(rgb, rgb1) and torch.equal(depth, depth1)  # the same scale on every replica: sharded = whole, bit for bit
+
+
+# ---------------------------------------------------------------- 6b. a blob is plain bytes; the library keeps no table of them
+def _scaled_fixture(ops, dev, s):
+    """sn64_64_128 with the coarse network blown up by 1.5 * 2^s: (scene, state, tables, rays (R,8), noise, render kwargs)"""
+    g, scene, meta, mc, mf, rays, noise = golden_setup("sn64_64_128")
+    sc = dscene(ops, dev, str(g["scene"]))
+    state = {k: v.to(dev) for k, v in blow_up(mlp_params(11), 1.5 * 2.0 ** s).items()}
+    r = rays.reshape(-1, 8).contiguous().to(dev)
+    nz = {k: v.to(dev).reshape(r.shape[0], -1).contiguous() for k, v in noise.items()}
+    kw = dict(depth_std=float(g["depth_std"]), white_bkgd=bool(g["white_bkgd"]), lindisp=bool(g["lindisp"]))
+    return sc, state, ops.fold_latent(sc, state, "f16x3"), r, nz, (int(g["n_coarse"]), int(g["n_fine"]), int(g["n_fine_depth"])), kw
+
+
+def test_a_copied_blob_runs_at_the_scale_its_owner_declares(ops, dev):
+    """a scaled blob is position-independent bytes: a clone (a copy to another device, a blob restored from a file) launched with
+    the s it was packed at gives the original's bits, also after the original is freed.  (Before ABI revision 12 the library
+    chose the kernel form by the ADDRESS pnr_pack_mlp_split had seen: the copy ran unscaled on biases packed at 2^-s.)"""
+    s = 6
+    sc, state, tab, r, nz, (Kc, Kf, Kfd), kw = _scaled_fixture(ops, dev, s)
+    xyz, vd = (t.to(dev) for t in points(dev, "sn64"))
+    pk = ops.pack_mlp(state, "f16x3", stream_scale=s)
+    copy = ops.PackedMLP(pk.buf.clone(), pk.precision, folded=True, stream_scale=s)
+    assert copy.buf.data_ptr() != pk.buf.data_ptr()
+    pts = ops.eval_points(sc, pk, xyz, vd, tables=tab)
+    img = ops.render_forward(sc, pk, None, r, Kc, Kf, Kfd, nz, tables=(tab, None), **kw)
+    assert torch.equal(ops.eval_points(sc, copy, xyz, vd, tables=tab), pts)
+    got = ops.render_forward(sc, copy, None, r, Kc, Kf, Kfd, nz, tables=(tab, None), **kw)
+    for p in ("coarse", "fine"):
+        assert torch.equal(got[p]["rgb"], img[p]["rgb"]) and torch.equal(got[p]["depth"], img[p]["depth"]), p
+    wrong = ops.PackedMLP(copy.buf, pk.precision, folded=True, stream_scale=0)  # (the declared s is what selects the form)
+    assert not torch.equal(ops.eval_points(sc, wrong, xyz, vd, tables=tab), pts)
+    del pk
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    assert torch.equal(ops.eval_points(sc, copy, xyz, vd, tables=tab), pts)
+    got = ops.render_forward(sc, copy, None, r, Kc, Kf, Kfd, nz, tables=(tab, None), **kw)
+    assert torch.equal(got["fine"]["rgb"], img["fine"]["rgb"]) and torch.equal(got["coarse"]["rgb"], img["coarse"]["rgb"])
+
+
+def test_three_hundred_live_scaled_blobs_pack_and_render(ops, dev):
+    """packing at a scale records nothing: 300 blobs at s = 3, all alive (300 distinct addresses, ~14 MB each), all pack, and the
+    last renders the bits of the first.  300 = the 256 entries of the address table revision 11 kept, plus a margin: there every
+    re-calibration / checkpoint reload of a process added an entry, and the 257th pack failed."""
+    s = 3
+    sc, state, tab, r, nz, (Kc, Kf, Kfd), kw = _scaled_fixture(ops, dev, s)
+    blobs = [ops.pack_mlp(state, "f16x3", stream_scale=s) for _ in range(300)]
+    assert len({b.buf.data_ptr() for b in blobs}) == 300 and all(b.stream_scale == s for b in blobs)
+    first = ops.render_forward(sc, blobs[0], None, r, Kc, Kf, Kfd, nz, tables=(tab, None), **kw)
+    last = ops.render_forward(sc, blobs[-1], None, r, Kc, Kf, Kfd, nz, tables=(tab, None), **kw)
+    assert torch.equal(blobs[0].buf, blobs[-1].buf)
+    for p in ("coarse", "fine"):
+        assert torch.isfinite(last[p]["rgb"]).all()
+        assert torch.equal(first[p]["rgb"], last[p]["rgb"]) and torch.equal(first[p]["depth"], last[p]["depth"]), p
+    del blobs
+    torch.cuda.empty_cache()
 
 
 # ---------------------------------------------------------------- 7. chunked = whole at s > 0

@@ -11,7 +11,7 @@ THROUGH THE HIP PATH ITSELF at the default precision, and then, at those weights
     and S3-like geometry (2 source views, pooled), 64 + 128 samples;
   * the config-5 gradient check is repeated: all 61 gradient tensors of the fused fp32-class training step against torch
     autograd through the oracle on the CPU, <= 1e-3 relative per tensor;
-  * the fp16-range guard (pnr_saturation_guard) must stay silent: trained-like activations are inside the fp32-class contract.
+  * the fp16-range guard (PnrSplitAux.sat_flag) must stay silent: trained-like activations are inside the fp32-class contract.
 """
 import numpy as np
 import pytest

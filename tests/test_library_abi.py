@@ -50,6 +50,7 @@ def test_struct_layouts_match_header_abi_rev10():
     assert ctypes.sizeof(_lib.PnrTrainDumps) == 14 * 8 and ctypes.sizeof(_lib.PnrBackwardDumps) == 14 * 8
     assert ctypes.sizeof(_lib.PnrScene) == 4 * 8 + 6 * 4 + 2 * 4 + 8 == 72
     assert ctypes.sizeof(_lib.PnrMlpWeights) == 30 * 8 + 8
+    assert ctypes.sizeof(_lib.PnrSplitAux) == 8 + 2 * 8  # (rev 12) the scale, padded to 8, + the guard word's and the probe's address
 
 
 def test_struct_layouts_against_the_header_compiled_by_gcc(repo_root, tmp_path):
@@ -61,7 +62,7 @@ def test_struct_layouts_against_the_header_compiled_by_gcc(repo_root, tmp_path):
         pytest.skip("no gcc")
     structs = {"PnrScene": _lib.PnrScene, "PnrMlpWeights": _lib.PnrMlpWeights, "PnrTrainDumps": _lib.PnrTrainDumps,
                "PnrBackwardDumps": _lib.PnrBackwardDumps, "PnrF32Saved": _lib.PnrF32Saved, "PnrSplitSaved": _lib.PnrSplitSaved,
-               "PnrWeightGradJob": _lib.PnrWeightGradJob}
+               "PnrWeightGradJob": _lib.PnrWeightGradJob, "PnrSplitAux": _lib.PnrSplitAux}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pixelnerf_hip.h"', 'int main(void) {']
     for name, cls in structs.items():
         lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
@@ -145,7 +146,7 @@ def test_argument_validation_without_gpu(lib):
     mvs.SB, mvs.NS, mvs.Hl, mvs.Wl, mvs.n_focal, mvs.n_c = 1, 2, 8, 8, 1, 1
     assert lib.pnr_eval_ray_samples(ctypes.byref(mvs), 64, _lib.PREC_F16, 64, 64, 4, 4, 8, 64, None) == -1
     assert b"mv_workspace" in lib.pnr_last_error()
-    assert lib.pnr_eval_ray_samples_split(ctypes.byref(mvs), 64, 64, 64, 64, 4, 4, 8, 64, None) == -1
+    assert lib.pnr_eval_ray_samples_split(ctypes.byref(mvs), 64, 64, 64, 64, 4, 4, 8, 64, None, None) == -1
     assert b"mv_workspace" in lib.pnr_last_error()
     assert lib.pnr_grad_scale(None, 10, None, None) == -1
     assert lib.pnr_weight_grad(None, None, 10, 0, 1.0, 0, 0, None, None, None, None) == -1
@@ -157,7 +158,7 @@ def test_argument_validation_without_gpu(lib):
     nb = (M + 4095) // 4096
     assert lib.pnr_fold_latent_f32_rows_workspace_bytes(ctypes.byref(sc)) == nb * 4096 + (nb + 4 + M) * 4
     assert lib.pnr_fold_latent_f32_rows_workspace_bytes(None) == 0
-    assert lib.pnr_fold_latent_f32_rows(None, None, None, None, 4, 2, 8, None, None, 0, None) == -1
+    assert lib.pnr_fold_latent_f32_rows(None, None, None, None, 4, 2, 8, None, None, 0, None, None) == -1
     assert b"null argument" in lib.pnr_last_error()
     assert lib.pnr_latent_scatter_single_owner(None, 4, 2, 8) == 0
     assert lib.pnr_latent_scatter_single_owner(ctypes.byref(sc), 256, 128, 96) == 1   # DTU-sized grid: owner tiles

@@ -67,34 +67,39 @@ def test_blow_up_fixture_leaves_the_outputs_alone_and_the_fp16_range_far_behind(
     assert float(h1.abs().max()) > 4 * FP16_MAX
 
 
-def test_abi_revision_11_declares_and_exports_the_probe_and_the_scale_field(repo_root, tmp_path):
+def test_abi_revision_12_declares_the_launch_struct_and_the_scale_field(repo_root, tmp_path):
     src = open(os.path.join(repo_root, "include", "pixelnerf_hip.h")).read()
-    assert int(re.search(r"#define\s+PNR_ABI_VERSION\s+(\d+)", src).group(1)) == 11 == _lib.ABI_VERSION
+    assert int(re.search(r"#define\s+PNR_ABI_VERSION\s+(\d+)", src).group(1)) == 12 == _lib.ABI_VERSION
     code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    assert re.search(r"\bint\s+pnr_range_probe\s*\(\s*float\s*\*", code)
     assert re.search(r"int32_t\s+stream_scale_log2\s*;", code)
-    assert "pnr_range_probe" in _lib.PROTOTYPES
+    assert re.search(r"typedef\s+struct\s+PnrSplitAux\s*\{[^}]*\}\s*PnrSplitAux\s*;", code)
     _lib.build_library()
     lib = _lib.load()
-    assert lib.pnr_abi_version() == 11 and hasattr(lib, "pnr_range_probe")
-    assert lib.pnr_range_probe(None) == 0  # disarming needs no device
-    # the struct as gcc lays the header out against the ctypes mirror
+    assert lib.pnr_abi_version() == 12
+    # guard, probe and scale are arguments of the launch (PnrSplitAux): the entries that armed them per host thread are gone
+    for gone in ("pnr_saturation_guard", "pnr_range_probe"):
+        assert gone not in code and gone not in _lib.PROTOTYPES and not hasattr(lib, gone)
+    # the structs as gcc lays the header out against the ctypes mirrors
     assert [f for f, _ in _lib.PnrMlpWeights._fields_][-2:] == ["combine_max", "stream_scale_log2"]
+    assert [f for f, _ in _lib.PnrSplitAux._fields_] == ["stream_scale_log2", "sat_flag", "range_probe"]
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pixelnerf_hip.h"', 'int main(void) {',
-             '  printf("size %zu\\n", sizeof(PnrMlpWeights));']
-    for fname, _ in _lib.PnrMlpWeights._fields_:
-        lines.append(f'  printf("{fname} %zu\\n", offsetof(PnrMlpWeights, {fname}));')
+    structs = {"PnrMlpWeights": _lib.PnrMlpWeights, "PnrSplitAux": _lib.PnrSplitAux}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pixelnerf_hip.h"', 'int main(void) {']
+    for name, cls in structs.items():
+        lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
+        for fname, _ in cls._fields_:
+            lines.append(f'  printf("{name}.{fname} %zu\\n", offsetof({name}, {fname}));')
     lines += ['  return 0;', '}']
     c = tmp_path / "layout.c"
     c.write_text("\n".join(lines))
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-std=c99", "-I", os.path.join(repo_root, "include"), str(c), "-o", str(exe)], check=True)
     got = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got["size"]) == ctypes.sizeof(_lib.PnrMlpWeights)
-    for fname, _ in _lib.PnrMlpWeights._fields_:
-        assert int(got[fname]) == getattr(_lib.PnrMlpWeights, fname).offset, fname
+    for name, cls in structs.items():
+        assert int(got[name]) == ctypes.sizeof(cls), name
+        for fname, _ in cls._fields_:
+            assert int(got[f"{name}.{fname}"]) == getattr(cls, fname).offset, f"{name}.{fname}"
 
 
 def test_entries_without_a_scaled_form_refuse_the_field_on_the_host():
@@ -121,6 +126,70 @@ def test_entries_without_a_scaled_form_refuse_the_field_on_the_host():
     for bad in (-1, 31):
         w.stream_scale_log2 = bad
         assert lib.pnr_pack_mlp_split(ref, 64, None) == -1 and b"[0, 30]" in lib.pnr_last_error()
+
+
+def _split_aux_calls(lib, sc, sv):
+    """every entry that takes a PnrSplitAux, with well-formed sizes and dummy (never dereferenced) device addresses:
+    name -> (call(aux_pointer), is a render entry)"""
+    render_tail = (64, 4, 4, 8, 16, 4, 0.01, 0, 0)  # rays, R, rays_per_obj, Kc, Kf, Kfd, depth_std, white_bkgd, lindisp
+    outs = (64, 64, 64, 64, 64, 64, 64)             # rgb_c .. weights_f, workspace
+    return {
+        "pnr_eval_ray_samples_split": (lambda a: lib.pnr_eval_ray_samples_split(sc, 64, 64, 64, 64, 4, 4, 8, 64, a, None), False),
+        "pnr_eval_points_split": (lambda a: lib.pnr_eval_points_split(sc, 64, 64, 64, 64, 4, 64, a, None), False),
+        "pnr_eval_ray_samples_split_train": (lambda a: lib.pnr_eval_ray_samples_split_train(sc, 64, 64, 64, 64, 4, 4, 8, 64, sv, a, None), False),
+        "pnr_render_forward_folded": (lambda a, p=_lib.PREC_F16X3, f=None: lib.pnr_render_forward_folded(
+            sc, 64, 64, 64, 64, p, *render_tail, 64, 64, 64, 64, *outs, a, f, None), True),
+        "pnr_render_forward_seeded": (lambda a, p=_lib.PREC_F16X3, f=None: lib.pnr_render_forward_seeded(
+            sc, 64, 64, 64, 64, p, *render_tail, 7, 0, 0, *outs, a, f, None), True),
+        "pnr_render_views": (lambda a, p=_lib.PREC_F16X3, f=None: lib.pnr_render_views(
+            sc, 64, 64, 64, 64, p, 64, 1, 2, 2, 1.0, 1.0, 1.0, 1.0, 0.5, 2.0, 8, 16, 4, 0.01, 0, 0, None, None, None, None, 7,
+            *outs, a, f, None), True),
+    }
+
+
+def test_entries_refuse_a_bad_launch_struct_on_the_host():
+    """PnrSplitAux is checked before any HIP call: a scale outside [0, 30] (every entry, coarse and fine struct), any scale on the
+    training entry, and a struct with a field set at a 16-bit precision (render entries) are PNR_E_INVALID, the message names the
+    field.  (On a machine without a GPU a HIP call would fail with PNR_E_HIP = -2 instead.)"""
+    _lib.build_library()
+    lib = _lib.load()
+    scene = _lib.PnrScene()
+    scene.latent_nhwc, scene.poses, scene.focal, scene.c = 64, 64, 64, 64
+    scene.SB, scene.NS, scene.Hl, scene.Wl, scene.n_focal, scene.n_c = 1, 1, 8, 8, 1, 1
+    saved = _lib.PnrSplitSaved()
+    calls = _split_aux_calls(lib, ctypes.byref(scene), ctypes.byref(saved))
+    assert sorted(calls) == sorted(n for n, (_, args) in _lib.PROTOTYPES.items() if _lib._AUX in args)
+    for name, (call, render) in calls.items():
+        for bad in (-1, 31):
+            aux = _lib.PnrSplitAux(stream_scale_log2=bad)
+            assert call(ctypes.byref(aux)) == -1, name
+            assert b"stream_scale_log2" in lib.pnr_last_error() and b"[0, 30]" in lib.pnr_last_error(), name
+            if render:
+                assert call(None, f=ctypes.byref(aux)) == -1, name
+                assert b"stream_scale_log2" in lib.pnr_last_error(), name
+        if render:
+            for prec in (_lib.PREC_F16, _lib.PREC_BF16):
+                for field in ("stream_scale_log2", "sat_flag", "range_probe"):
+                    aux = _lib.PnrSplitAux(**{field: 64 if field != "stream_scale_log2" else 3})
+                    for kw in (dict(a=ctypes.byref(aux)), dict(a=None, f=ctypes.byref(aux))):
+                        assert call(p=prec, **kw) == -1, (name, prec, field)
+                        assert field.encode() in lib.pnr_last_error() and b"PNR_PREC_F16X3" in lib.pnr_last_error(), (name, prec, field)
+    aux = _lib.PnrSplitAux(stream_scale_log2=3)
+    assert calls["pnr_eval_ray_samples_split_train"][0](ctypes.byref(aux)) == -1
+    assert b"stream scale" in lib.pnr_last_error() and b"stream_scale_log2" in lib.pnr_last_error()
+
+
+def test_the_library_keeps_no_launch_state(repo_root):
+    """what a launch does is a function of its arguments: the only thread-local of the library is the errno-style message behind
+    pnr_last_error, and nothing is guarded by a mutex (a text check, kept to these two words)"""
+    csrc = os.path.join(repo_root, "pixel-nerf_amd", "csrc")
+    hits = []
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h")):
+            for line in open(os.path.join(csrc, fn)):
+                if "thread_local" in line or "std::mutex" in line:
+                    hits.append((fn, line.strip()))
+    assert hits == [("pnr_api.hip", 'static thread_local char g_err[512] = "";')]
 
 
 def _model(**kw):
