@@ -616,6 +616,29 @@ int pnr_eval_epilogue(const float *rgb, const float *depth, int n_views, int pix
                       float z_near, float z_far, const float *gt_rgb, unsigned char *rgb_u8,
                       float *rgb_clamped, float *depth_norm, double *sq_err_sum, void *stream);
 
+/* eval/eval.py:321-326 (the structural-similarity call between the clamp and the PSNR; also
+ * eval/calc_metrics.py:186-191): per-view mean SSIM with a uniform win_size x win_size window,
+ * the second number of the reference's `final psnr ... ssim ...` line, on device.
+ * pred, gt: (n_views, H, W, channels) fp32, channel-interleaved (pnr_eval_epilogue's layout with
+ * pixels = H*W).  Per channel, in fp64 throughout: over every window that lies fully inside the
+ * image (NP = win_size^2 pixels) the window means ux, uy, uxx, uyy, uxy of x, y, x^2, y^2, x*y;
+ *   vx = cn (uxx - ux^2), vy = cn (uyy - uy^2), vxy = cn (uxy - ux uy), cn = NP / (NP - 1);
+ *   C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ *   S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2));
+ * ssim[v] = mean of S over the (H-win_size+1)(W-win_size+1) windows and the channels.  (A filter
+ * with reflected borders cropped by (win_size-1)/2 -- the usual formulation -- is the same number.)
+ * Reduction in a fixed order, no floating-point atomics: every workgroup (one 16x16 tile of window
+ * positions of one channel of one view) writes ONE fp64 partial into `workspace`, a second pass
+ * adds a view's partials in an order that depends on (H, W, channels) only -- bit-identical from
+ * run to run, and a view's value does not depend on how many views share the call.
+ * win_size odd, in [3, 15], <= min(H, W); channels in [1, 4]; data_range > 0; workspace: device
+ * memory of at least pnr_ssim_workspace_bytes (the caller's; the library allocates nothing);
+ * ssim: device, (n_views) fp64.  n_views == 0 is a no-op. */
+size_t pnr_ssim_workspace_bytes(int n_views, int H, int W, int channels);
+int pnr_ssim(const float *pred, const float *gt, int n_views, int H, int W, int channels,
+             int win_size, double data_range, void *workspace, size_t workspace_bytes,
+             double *ssim, void *stream);
+
 /* ---- next-row helpers: training-ray selection on device ---------------
  * train/train.py:143-182 with util.bbox_sample (src/util/util.py:220-235): for each of SB objects
  * pick B pixels among its NV views and emit their rays and ground-truth colours (image*0.5+0.5)

@@ -109,6 +109,8 @@ PROTOTYPES = {
     "pnr_positional_encoding_backward": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _P, _P, _I, _P, _P]),
     "pnr_sample_training_rays": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     "pnr_eval_epilogue": (_I, [_P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "pnr_ssim_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "pnr_ssim": (_I, [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _P, _SZ, _P, _P]),
     "pnr_resnetfc_forward_f32_workspace_bytes": (_SZ, [ctypes.c_longlong, _I]),
     "pnr_resnetfc_forward_f32": (_I, [ctypes.POINTER(PnrMlpWeights), _P, ctypes.c_longlong, _I, _I, _P, _P, _SZ, _P]),
     "pnr_train_masks_bytes": (_SZ, [ctypes.c_longlong, _I]),

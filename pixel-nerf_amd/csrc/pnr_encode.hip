@@ -289,6 +289,90 @@ eval_epilogue_kernel(const float *__restrict__ rgb, const float *__restrict__ de
     }
 }
 
+// eval/eval.py:321-326 (structural similarity, uniform win x win window, sample covariance, data_range given): a workgroup owns
+// a SSIM_T x SSIM_T tile of window positions (top-left corners) of ONE channel of one view.  The tile of both images plus a
+// win-1 halo goes to LDS as fp64; row sums of x, y, xx, yy, xy over `win` columns, then column sums over `win` rows (separable
+// box filter); S per window; the tile's sum of S is reduced by a fixed tree into ONE fp64 partial.  Windows that would leave
+// the image contribute nothing.  All arithmetic after the load is fp64, without FMA contraction (x == y must give S == 1).
+constexpr int SSIM_T = 16, SSIM_MAX_WIN = 15, SSIM_IN = SSIM_T + SSIM_MAX_WIN - 1;
+
+__global__ void __launch_bounds__(SSIM_T * SSIM_T)
+ssim_tile_kernel(const float *__restrict__ pred, const float *__restrict__ gt, int H, int W, int C, int win, int tiles_x,
+                 int tiles_per_view, double c1, double c2, double *__restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ double sx[SSIM_IN * SSIM_IN], sy[SSIM_IN * SSIM_IN];
+    __shared__ double row[5][SSIM_IN * SSIM_T];
+    __shared__ double part[SSIM_T * SSIM_T];
+    const int t = threadIdx.x;
+    const int tile = blockIdx.x % tiles_per_view;
+    const int vc = blockIdx.x / tiles_per_view;  // view * C + channel
+    const int v = vc / C, c = vc - v * C;
+    const int y0 = (tile / tiles_x) * SSIM_T, x0 = (tile % tiles_x) * SSIM_T;
+    const int in = SSIM_T + win - 1;           // tile edge with halo
+    const int rows = min(in, H - y0), cols = min(in, W - x0);  // (what of it lies inside the image)
+    const size_t base = (size_t)v * H * W;
+    for (int i = t; i < in * in; i += SSIM_T * SSIM_T) {
+        const int r = i / in, q = i - r * in;
+        double a = 0.0, b = 0.0;
+        if (r < rows && q < cols) {
+            const size_t at = (base + (size_t)(y0 + r) * W + (x0 + q)) * C + c;
+            a = (double)pred[at];
+            b = (double)gt[at];
+        }
+        sx[r * SSIM_IN + q] = a;
+        sy[r * SSIM_IN + q] = b;
+    }
+    __syncthreads();
+    for (int i = t; i < in * SSIM_T; i += SSIM_T * SSIM_T) {  // row r, window column q: sums over columns q .. q+win-1
+        const int r = i / SSIM_T, q = i - r * SSIM_T;
+        double ax = 0.0, ay = 0.0, axx = 0.0, ayy = 0.0, axy = 0.0;
+        for (int k = 0; k < win; ++k) {
+            const double a = sx[r * SSIM_IN + q + k], b = sy[r * SSIM_IN + q + k];
+            ax += a; ay += b; axx += a * a; ayy += b * b; axy += a * b;
+        }
+        row[0][i] = ax; row[1][i] = ay; row[2][i] = axx; row[3][i] = ayy; row[4][i] = axy;
+    }
+    __syncthreads();
+    const int wy = t / SSIM_T, wx = t - wy * SSIM_T;
+    double s = 0.0;
+    if (y0 + wy + win <= H && x0 + wx + win <= W) {
+        double ax = 0.0, ay = 0.0, axx = 0.0, ayy = 0.0, axy = 0.0;
+        for (int k = 0; k < win; ++k) {
+            const int i = (wy + k) * SSIM_T + wx;
+            ax += row[0][i]; ay += row[1][i]; axx += row[2][i]; ayy += row[3][i]; axy += row[4][i];
+        }
+        const double np = (double)(win * win), cn = np / (np - 1.0);
+        const double ux = ax / np, uy = ay / np, uxx = axx / np, uyy = ayy / np, uxy = axy / np;
+        const double vx = cn * (uxx - ux * ux), vy = cn * (uyy - uy * uy), vxy = cn * (uxy - ux * uy);
+        s = ((2.0 * ux * uy + c1) * (2.0 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2));
+    }
+    part[t] = s;
+    __syncthreads();
+    for (int h = SSIM_T * SSIM_T / 2; h > 0; h >>= 1) {
+        if (t < h) part[t] += part[t + h];
+        __syncthreads();
+    }
+    if (t == 0) partial[blockIdx.x] = part[0];
+}
+
+// second, ordered pass: one workgroup per view over that view's C * tiles partials -- thread t adds every 256th in ascending
+// order, then the fixed tree.  The order depends on (H, W, C) only: a view's value does not depend on the launch it shares.
+__global__ void __launch_bounds__(256)
+ssim_reduce_kernel(const double *__restrict__ partial, int per_view, double count, double *__restrict__ ssim) {
+#pragma clang fp contract(off)
+    __shared__ double part[256];
+    const int v = blockIdx.x, t = threadIdx.x;
+    double acc = 0.0;
+    for (int i = t; i < per_view; i += 256) acc += partial[(size_t)v * per_view + i];
+    part[t] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) part[t] += part[t + h];
+        __syncthreads();
+    }
+    if (t == 0) ssim[v] = part[0] / count;
+}
+
 // train/train.py:143-182 + util.bbox_sample (util.py:220-235): one thread per selected pixel; the ray is
 // built from (pose, intrinsics, pixel) exactly as gen_rays_kernel does, the colour is images*0.5+0.5.
 __global__ void sample_training_rays_kernel(const float *__restrict__ poses, const float *__restrict__ images,
@@ -508,6 +592,40 @@ extern "C" int pnr_eval_epilogue(const float *rgb, const float *depth, int n_vie
     hipLaunchKernelGGL(pnr::eval_epilogue_kernel, dim3(n_views), dim3(256), 0, (hipStream_t)stream, rgb, depth, pixels_per_view,
                        z_near, z_far, gt_rgb, rgb_u8, rgb_clamped, depth_norm, sq_err_sum);
     return pnr_check_launch("pnr_eval_epilogue");
+}
+
+static long long ssim_tiles(int H, int W) {
+    return (long long)((H + pnr::SSIM_T - 1) / pnr::SSIM_T) * ((W + pnr::SSIM_T - 1) / pnr::SSIM_T);
+}
+
+extern "C" size_t pnr_ssim_workspace_bytes(int n_views, int H, int W, int channels) {
+    if (n_views <= 0 || H <= 0 || W <= 0 || channels <= 0) return 0;
+    return (size_t)n_views * (size_t)channels * (size_t)ssim_tiles(H, W) * sizeof(double);
+}
+
+extern "C" int pnr_ssim(const float *pred, const float *gt, int n_views, int H, int W, int channels, int win_size,
+                        double data_range, void *workspace, size_t workspace_bytes, double *ssim, void *stream) {
+    if (n_views < 0 || H <= 0 || W <= 0) return pnr_fail(PNR_E_INVALID, "pnr_ssim: bad sizes (n_views, H, W)");
+    if (channels < 1 || channels > 4) return pnr_fail(PNR_E_INVALID, "pnr_ssim: channels must be in [1, 4]");
+    if (win_size < 3 || win_size > pnr::SSIM_MAX_WIN || win_size % 2 == 0)
+        return pnr_fail(PNR_E_INVALID, "pnr_ssim: win_size must be odd and in [3, 15]");
+    if (win_size > H || win_size > W) return pnr_fail(PNR_E_INVALID, "pnr_ssim: win_size must not exceed min(H, W)");
+    if (!(data_range > 0.0)) return pnr_fail(PNR_E_INVALID, "pnr_ssim: data_range must be positive");
+    if (n_views == 0) return PNR_OK;
+    if (!pred) return pnr_fail(PNR_E_INVALID, "pnr_ssim: pred is null");
+    if (!gt) return pnr_fail(PNR_E_INVALID, "pnr_ssim: gt is null");
+    if (!ssim) return pnr_fail(PNR_E_INVALID, "pnr_ssim: ssim is null");
+    if (!workspace || workspace_bytes < pnr_ssim_workspace_bytes(n_views, H, W, channels))
+        return pnr_fail(PNR_E_INVALID, "pnr_ssim: workspace too small (pnr_ssim_workspace_bytes)");
+    const long long tiles = ssim_tiles(H, W), blocks = tiles * channels * n_views;
+    if (blocks > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_ssim: n_views x channels x tiles exceeds the grid limit");
+    const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+    const double count = (double)(H - win_size + 1) * (double)(W - win_size + 1) * (double)channels;
+    hipLaunchKernelGGL(pnr::ssim_tile_kernel, dim3((unsigned)blocks), dim3(pnr::SSIM_T * pnr::SSIM_T), 0, (hipStream_t)stream, pred,
+                       gt, H, W, channels, win_size, (W + pnr::SSIM_T - 1) / pnr::SSIM_T, (int)tiles, c1, c2, (double *)workspace);
+    hipLaunchKernelGGL(pnr::ssim_reduce_kernel, dim3(n_views), dim3(256), 0, (hipStream_t)stream, (const double *)workspace,
+                       (int)(tiles * channels), count, ssim);
+    return pnr_check_launch("pnr_ssim");
 }
 
 extern "C" int pnr_positional_encoding(const float *x, long long N, int d_in, int num_freqs, const float *freqs2, const float *phases2,

@@ -204,6 +204,10 @@ class ShardedRenderWrapper(torch.nn.Module):
             return last["rgb"], last["depth"]
         return res
 
+    def render_views(self, *args, **kwargs):
+        raise NotImplementedError("render_views is a single-process entry: shard the rays of the views with forward(rays), or "
+                                  "call render_views on the unsharded bind_parallel(net)")
+
     def forward(self, rays, want_weights=False):
         net = getattr(self.wrapped, "net", None)
         if net is not None:  # an integer stream scale passes through; an automatic one would differ from rank to rank

@@ -980,12 +980,37 @@ def sample_training_rays(poses, images, focal, z_near, z_far, ids, c=None, bboxe
     return rays, gt
 
 
-def eval_epilogue(rgb, depth=None, z_near=0.0, z_far=1.0, gt_rgb=None, want_u8=True):
+def ssim(pred, gt, win_size=7, data_range=1.0):
+    """eval/eval.py:321-326 on device (pnr_ssim): mean structural similarity per view with a uniform win_size x win_size
+    window and the sample covariance, fp64, reduced in a fixed order.  pred, gt (NV,H,W,C) or (H,W,C) fp32 HIP tensors,
+    C in [1, 4] -> (NV,) float64 (one element for a single image)."""
+    lib = _lib.load()
+    if isinstance(pred, torch.Tensor) and pred.dim() == 3:
+        pred = pred.unsqueeze(0)
+    if isinstance(gt, torch.Tensor) and gt.dim() == 3:
+        gt = gt.unsqueeze(0)
+    pred = _f32(pred, "pred", (None, None, None, None))
+    NV, H, W, C = pred.shape
+    gt = _f32(gt, "gt", (NV, H, W, C))
+    dev = pred.device
+    out = torch.empty((NV,), dtype=torch.float64, device=dev)
+    nbytes = lib.pnr_ssim_workspace_bytes(NV, H, W, C)
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_ssim(_p(pred), _p(gt), NV, H, W, C, int(win_size), float(data_range), _p(ws), ws.numel() * 8, _p(out),
+                                _stream()), "pnr_ssim")
+    return out
+
+
+def eval_epilogue(rgb, depth=None, z_near=0.0, z_far=1.0, gt_rgb=None, want_u8=True, image_shape=None):
     """eval/eval.py:283-290,327-329 on device.  rgb (NV,P,3) [+ depth (NV,P)] [+ gt_rgb (NV,P,3) in [0,1]] ->
-    dict(rgb (clamped), rgb_u8, depth_norm, sse (NV,) float64, psnr (NV,) float64)."""
+    dict(rgb (clamped), rgb_u8, depth_norm, sse (NV,) float64, psnr (NV,) float64).  image_shape=(H, W) with gt_rgb adds
+    "ssim" (NV,) float64 of the CLAMPED prediction (eval.py:288-290 clamps before it compares, :321-326; ops.ssim)."""
     lib = _lib.load()
     rgb = _f32(rgb, "rgb", (None, None, 3))
     NV, P = rgb.shape[:2]
+    if image_shape is not None and (len(image_shape) != 2 or int(image_shape[0]) * int(image_shape[1]) != P):
+        raise ValueError(f"image_shape: expected (H, W) with H*W = {P} pixels per view, got {tuple(image_shape)}")
     dev = rgb.device
     depth = None if depth is None else _f32(depth, "depth", (NV, P))
     gt = None if gt_rgb is None else _f32(gt_rgb, "gt_rgb", (NV, P, 3))
@@ -1003,6 +1028,9 @@ def eval_epilogue(rgb, depth=None, z_near=0.0, z_far=1.0, gt_rgb=None, want_u8=T
     if sse is not None:
         out["sse"] = sse
         out["psnr"] = -10.0 * torch.log10(sse / (3 * P))
+        if image_shape is not None:
+            H, W = int(image_shape[0]), int(image_shape[1])
+            out["ssim"] = ssim(out["rgb"].reshape(NV, H, W, 3), gt.reshape(NV, H, W, 3))
     return out
 
 

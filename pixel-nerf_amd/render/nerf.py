@@ -43,6 +43,15 @@ class _RenderWrapper(torch.nn.Module):
             return outputs.coarse.rgb, outputs.coarse.depth
         return outputs.toDict()
 
+    def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, views_per_call=None,
+                     _noise=None):
+        """Images of the target views from their cameras, with depth normalisation and, given ground truth, PSNR and SSIM per
+        view, all on the device (NeRFRenderer.render_views; the loop of eval/eval.py:247-331 as one call).  Inference only:
+        runs under torch.no_grad()."""
+        with torch.profiler.record_function("render_par"):
+            return self.renderer.render_views(self.net, poses_c2w, W, H, focal, z_near, z_far, c=c, gt_rgb=gt_rgb, want_u8=want_u8,
+                                              views_per_call=views_per_call, _noise=_noise)
+
 
 class NeRFRenderer(torch.nn.Module):
     """NeRF renderer; parameters as src/render/nerf.py:45-96."""
@@ -162,17 +171,24 @@ class NeRFRenderer(torch.nn.Module):
         with torch.profiler.record_function("renderer_forward"):  # the reference's scope name (nerf.py:264)
             return self._forward(model, rays, want_weights, _noise)
 
-    def _forward(self, model, rays, want_weights, _noise):
+    def _apply_sched(self):
         if self.sched is not None and self.last_sched.item() > 0:
             self.n_coarse = self.sched[1][self.last_sched.item() - 1]
             self.n_fine = self.sched[2][self.last_sched.item() - 1]
+
+    @staticmethod
+    def _is_fused(model):
+        # pixelnerf_amd.PixelNeRFNet in the shipped configuration: the fused kernels.  Any other model -- including a PixelNeRFNet
+        # configured outside what the fused kernels implement (composed forward) -- is a callable to the reference's control flow.
+        return hasattr(model, "scene") and hasattr(model, "packed") and (not hasattr(model, "fused_supported") or model.fused_supported())
+
+    def _forward(self, model, rays, want_weights, _noise):
+        self._apply_sched()
         assert len(rays.shape) == 3
         SB = rays.shape[0]
         rays = rays.reshape(-1, 8).float().contiguous()
         R = rays.shape[0]
-        # pixelnerf_amd.PixelNeRFNet in the shipped configuration: the fused kernels.  Any other model -- including a PixelNeRFNet
-        # configured outside what the fused kernels implement (composed forward) -- is a callable to the reference's control flow.
-        fused = hasattr(model, "scene") and hasattr(model, "packed") and (not hasattr(model, "fused_supported") or model.fused_supported())
+        fused = self._is_fused(model)
         # (inside a HIP-graph capture the generator's offset cannot be read on the host: torch's own graph-safe draws are used)
         seeded = (_noise is None and fused and self.rng == "philox" and not (self.training and torch.is_grad_enabled())
                   and not (rays.is_cuda and torch.cuda.is_current_stream_capturing()))
@@ -203,38 +219,10 @@ class NeRFRenderer(torch.nn.Module):
                     if guarded:
                         model._guard_end()
             else:
-                # mlp_fine is None (eval/eval.py:140): pass no fine network, so the fine pass re-uses the coarse pass's
-                # outputs at the shared sample positions instead of evaluating them again
-                own_fine = Kf > 0 and getattr(model, "mlp_fine", None) is not None
                 seed = self._next_seed(rays.device) if seeded else 0
-                for _ in range(2):  # (twice only for stream_scale="auto" when the first call on new weights saturated)
-                    pk_c, pk_f = model.packed(True), (model.packed(False) if own_fine else None)  # before tables(): see PixelNeRFNet.tables
-                    guarded = model._guard_begin()  # fp16-range guard of the fp32-class kernels: first call on new weights / scene
-                    try:
-                        # (a fold that happens now is guarded too -- grid values / lin_z weights: word 0 coarse, word 1 fine)
-                        tc = model.tables(True, guard_slot=0)
-                        tf = model.tables(False, guard_slot=1) if (own_fine and tc is not None) else None
-                        res = ops.render_forward(model.scene(), pk_c, pk_f,
-                                                 rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
-                                                 white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights,
-                                                 tables=None if tc is None else (tc, tf),
-                                                 seed=seed,
-                                                 ray_id_offset=self.ray_id_offset, ray_id_stride=self.ray_id_stride)
-                    finally:
-                        if guarded:
-                            model._guard_end()
-                    if not (guarded and getattr(model, "__dict__", {}).get("_auto_first")):
-                        break
-                    # the automatic stream scale calibrates on THIS call's rays and draws (same seed / noise), then renders it again
-                    keep = self._seed_override
-                    try:
-                        if seeded:
-                            self._seed_override = seed
-                        redo = model._auto_resolve(rays=rays.reshape(SB, -1, 8), renderer=_FixedNoise(self, _noise if not seeded else None, noise))
-                    finally:
-                        self._seed_override = keep
-                    if not redo:
-                        break
+                res = self._fused_inference(model, Kf, seed, seeded, _noise, noise,
+                                            self._rays_launch(model, rays, Kf, Kfd, noise, want_weights),
+                                            lambda: rays.reshape(SB, -1, 8))
             outputs = DotMap(coarse=self._format(res["coarse"], SB, want_weights))
             if Kf > 0:
                 outputs.fine = self._format(res["fine"], SB, want_weights)
@@ -257,6 +245,156 @@ class NeRFRenderer(torch.nn.Module):
             wf, rgbf, depthf = self.composite(model, rays, z_all, coarse=False, sb=SB)
             outputs.fine = self._format(dict(rgb=rgbf, depth=depthf, weights=wf), SB, want_weights)
         return outputs
+
+    def _rays_launch(self, model, rays, Kf, Kfd, noise, want_weights):
+        """the launch of _fused_inference for rays (R,8): the seeded / folded one-call renderer"""
+        def launch(pk_c, pk_f, tables, seed):
+            return ops.render_forward(model.scene(), pk_c, pk_f, rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
+                                      white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights, tables=tables,
+                                      seed=seed, ray_id_offset=self.ray_id_offset, ray_id_stride=self.ray_id_stride)
+        return launch
+
+    def _fused_inference(self, model, Kf, seed, seeded, given_noise, noise, launch, calib_rays):
+        """The inference (no autograd) call of a fused PixelNeRFNet, shared by forward (rays) and render_views (cameras):
+        `launch(packed_coarse, packed_fine|None, tables|None, seed)` is the one C call, everything around it is here -- packed
+        streams before tables, the fp16-range guard around fold and launch, the second pass of stream_scale="auto" (which
+        calibrates on `calib_rays()` (SB,B,8), the rays of this call, with this call's draws)."""
+        # mlp_fine is None (eval/eval.py:140): pass no fine network, so the fine pass re-uses the coarse pass's
+        # outputs at the shared sample positions instead of evaluating them again
+        own_fine = Kf > 0 and getattr(model, "mlp_fine", None) is not None
+        for _ in range(2):  # (twice only for stream_scale="auto" when the first call on new weights saturated)
+            pk_c, pk_f = model.packed(True), (model.packed(False) if own_fine else None)  # before tables(): see PixelNeRFNet.tables
+            guarded = model._guard_begin()  # fp16-range guard of the fp32-class kernels: first call on new weights / scene
+            try:
+                # (a fold that happens now is guarded too -- grid values / lin_z weights: word 0 coarse, word 1 fine)
+                tc = model.tables(True, guard_slot=0)
+                tf = model.tables(False, guard_slot=1) if (own_fine and tc is not None) else None
+                res = launch(pk_c, pk_f, None if tc is None else (tc, tf), seed)
+            finally:
+                if guarded:
+                    model._guard_end()
+            if not (guarded and getattr(model, "__dict__", {}).get("_auto_first")):
+                break
+            # the automatic stream scale calibrates on THIS call's rays and draws (same seed / noise), then renders it again
+            keep = self._seed_override
+            try:
+                if seeded:
+                    self._seed_override = seed
+                redo = model._auto_resolve(rays=calib_rays(), renderer=_FixedNoise(self, given_noise if not seeded else None, noise))
+            finally:
+                self._seed_override = keep
+            if not redo:
+                break
+        return res
+
+    # ---- cameras -> images ----
+    def render_views(self, model, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False,
+                     views_per_call=None, _noise=None):
+        """Every pixel of the target views from their cameras, with the evaluation epilogue on the device: what
+        eval/eval.py:247-331 does per object (util.gen_rays, render_par over ray batches, clamp, depth normalisation, PSNR and
+        SSIM per view) as one call.  An INFERENCE entry: it runs under torch.no_grad() whatever the caller's mode.
+        :param poses_c2w (SB,NVt,4,4) camera-to-world of the target views ((NVt,4,4) when the net encoded one object)
+        :param focal scalar or (fx, fy); c (cx, cy) or None = the image centre (util.gen_rays)
+        :param gt_rgb (SB,NVt,H,W,3) in [0,1]: adds psnr and ssim
+        :param views_per_call k: render k views per object at a time (bounds the workspace); the same bits as one call
+        :return DotMap: rgb (SB,NVt,H,W,3) and depth (SB,NVt,H,W) -- the fine pass's (the coarse pass's when using_fine is false),
+        unclamped, as `simple_output` returns them; depth_norm = (depth - z_near) / (z_far - z_near); rgb_u8 with want_u8;
+        psnr, ssim (SB,NVt) float64 of clamp(rgb, 0, 1) against gt_rgb.  All on the device, no host synchronisation beyond what
+        forward has on the first call with new weights.
+        Under the same torch.manual_seed the image equals, bit for bit, forward over util.gen_rays of the same cameras; a fused
+        PixelNeRFNet renders without a ray array (ops.render_views), anything else goes through util.gen_rays + forward."""
+        with torch.no_grad(), torch.profiler.record_function("renderer_render_views"):
+            return self._render_views(model, poses_c2w, int(W), int(H), focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise)
+
+    def _render_views(self, model, poses, W, H, focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise):
+        from .. import util
+        self._apply_sched()
+        if poses.dim() == 3:
+            if int(getattr(model, "num_objs", 1) or 1) != 1:
+                raise ValueError("render_views: (NVt,4,4) poses need a net that encoded ONE object; pass (SB,NVt,4,4)")
+            poses = poses.unsqueeze(0)
+        if poses.dim() != 4 or tuple(poses.shape[2:]) != (4, 4):
+            raise ValueError(f"render_views: poses_c2w must be (SB,NVt,4,4), got {tuple(poses.shape)}")
+        SB, NVt = poses.shape[:2]
+        if views_per_call is not None and int(views_per_call) < 1:
+            raise ValueError("render_views: views_per_call must be a positive number of views")
+        if torch.is_tensor(focal):
+            focal = focal.flatten().tolist()
+            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
+        if torch.is_tensor(c):
+            c = c.flatten().tolist()
+        flat = poses.reshape(-1, 4, 4).float().contiguous()
+        HW = H * W
+        R, dev = SB * NVt * HW, flat.device
+        Kf = self.n_fine if self.using_fine else 0
+        Kfd = min(self.n_fine_depth, Kf)
+        fast = (self._is_fused(model) and flat.is_cuda and model._effective_precision() != "f32"
+                and not torch.cuda.is_current_stream_capturing() and not (self.training and self.noise_std > 0.0))
+        if not fast:
+            # a generic model callable, a composed-path PixelNeRFNet, the exact fp32 path, a capture in progress: the rays, then forward
+            rays = util.gen_rays(flat, W, H, focal, z_near, z_far, c).reshape(SB, -1, 8)
+            out = self.forward(model, rays, _noise=_noise)
+            last = out.fine if self.using_fine else out.coarse
+            rgb, depth = last.rgb, last.depth
+        else:
+            model._check_supported()
+            seeded = _noise is None and self.rng == "philox"
+            noise = _noise if (_noise is not None or seeded) else self._draw_noise(R, dev)
+            seed = self._next_seed(dev) if seeded else 0  # ONE key per call: the generator advances as for one forward over all rays
+            k = NVt if views_per_call is None else min(int(views_per_call), NVt)
+            if k == NVt:
+                def launch(pk_c, pk_f, tables, seed):
+                    return ops.render_views(model.scene(), pk_c, pk_f, flat, W, H, focal, z_near, z_far, self.n_coarse, Kf, Kfd,
+                                            noise, c=c, depth_std=self.depth_std, white_bkgd=self.white_bkgd, lindisp=self.lindisp,
+                                            tables=tables, seed=seed)
+                res = self._fused_inference(model, Kf, seed, seeded, _noise, noise, launch,
+                                            lambda: ops.gen_rays(flat, W, H, focal, z_near, z_far, c).reshape(SB, -1, 8))
+                last = res["fine"] if Kf > 0 else res["coarse"]
+                rgb, depth = last["rgb"], last["depth"]
+            else:
+                rgb, depth = self._render_view_groups(model, poses, k, W, H, focal, z_near, z_far, c, Kf, Kfd, seed, seeded, _noise, noise)
+        ret = DotMap(rgb=rgb.reshape(SB, NVt, H, W, 3), depth=depth.reshape(SB, NVt, H, W))
+        gt = None
+        if gt_rgb is not None:
+            if tuple(gt_rgb.shape) != (SB, NVt, H, W, 3) and (SB != 1 or tuple(gt_rgb.shape) != (NVt, H, W, 3)):
+                raise ValueError(f"render_views: gt_rgb must be (SB,NVt,H,W,3) = {(SB, NVt, H, W, 3)}, got {tuple(gt_rgb.shape)}")
+            gt = gt_rgb.reshape(SB * NVt, HW, 3).float()
+        ep = ops.eval_epilogue(rgb.reshape(SB * NVt, HW, 3), depth.reshape(SB * NVt, HW), z_near, z_far, gt_rgb=gt, want_u8=want_u8,
+                               image_shape=(H, W) if gt is not None else None)
+        ret.depth_norm = ep["depth_norm"].reshape(SB, NVt, H, W)
+        if want_u8:
+            ret.rgb_u8 = ep["rgb_u8"].reshape(SB, NVt, H, W, 3)
+        if gt is not None:
+            ret.psnr, ret.ssim = ep["psnr"].reshape(SB, NVt), ep["ssim"].reshape(SB, NVt)
+        return ret
+
+    def _render_view_groups(self, model, poses, k, W, H, focal, z_near, z_far, c, Kf, Kfd, seed, seeded, given_noise, noise):
+        """render_views, k views per object at a time.  pnr_render_views numbers its rays from 0, so a group goes through its
+        rays and the ray-batch entry, placed inside the whole (NVt,H,W) ray set of its object by ray_id_offset / ray_id_stride
+        (include/pixelnerf_hip.h, "counter-based random draws"); explicit noise is cut to the group's rows.  Same bits as one call."""
+        SB, NVt = poses.shape[:2]
+        HW = H * W
+        dev = poses.device
+        rgb = torch.empty((SB, NVt * HW, 3), dtype=torch.float32, device=dev)
+        depth = torch.empty((SB, NVt * HW), dtype=torch.float32, device=dev)
+        keep = (self.ray_id_offset, self.ray_id_stride)
+        try:
+            for v0 in range(0, NVt, k):
+                v1 = min(v0 + k, NVt)
+                rays = ops.gen_rays(poses[:, v0:v1].reshape(-1, 4, 4).float().contiguous(), W, H, focal, z_near, z_far, c).reshape(-1, 8)
+                part = noise if noise is None else {
+                    n: t.reshape(SB, NVt * HW, t.shape[-1])[:, v0 * HW:v1 * HW].reshape(-1, t.shape[-1]) for n, t in noise.items()}
+                # (the renderer's own placement fields: a calibration pass of stream_scale="auto" renders through forward)
+                self.ray_id_offset, self.ray_id_stride = keep[0] + v0 * HW, NVt * HW
+                res = self._fused_inference(model, Kf, seed, seeded, None if given_noise is None else part, part,
+                                            self._rays_launch(model, rays, Kf, Kfd, part, False),
+                                            lambda: rays.reshape(SB, -1, 8))
+                last = res["fine"] if Kf > 0 else res["coarse"]
+                rgb[:, v0 * HW:v1 * HW] = last["rgb"].reshape(SB, -1, 3)
+                depth[:, v0 * HW:v1 * HW] = last["depth"].reshape(SB, -1)
+        finally:
+            self.ray_id_offset, self.ray_id_stride = keep
+        return rgb, depth
 
     def _next_seed(self, device):
         """64-bit Philox key of this call, from the ray device's torch generator: (seed, Philox offset) mixed by a
@@ -406,6 +544,10 @@ class _MultiDeviceRenderWrapper(torch.nn.Module):
         rend.train(self.renderer.training)
         rep.train(src.training)
         return rep, rend
+
+    def render_views(self, *args, **kwargs):
+        raise NotImplementedError("render_views is a single-device entry: render with forward(rays) across several devices, or "
+                                  "bind_parallel(net) without a device list")
 
     def forward(self, rays, want_weights=False):
         from ..autograd import PARAM_NAMES

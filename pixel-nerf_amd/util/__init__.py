@@ -35,6 +35,15 @@ def psnr(pred, target):
     return -10 * math.log10(mse)
 
 
+def ssim(pred, target, win_size=7, data_range=1.0):
+    """The structural similarity the reference's evaluation reports next to util.psnr (eval/eval.py:321-326: uniform 7 x 7
+    window, data range 1, mean over the channels), on the device (ops.ssim / pnr_ssim, fp64).  A single image pair (H,W,3)
+    gives a 0-d float64 tensor, a batch (N,H,W,3) gives (N,); the values stay on the device (`float(...)` to read one)."""
+    from .. import ops
+    out = ops.ssim(pred.float(), target.float(), win_size=win_size, data_range=data_range)
+    return out[0] if pred.dim() == 3 else out
+
+
 def get_cuda(gpu_id):
     """src/util/util.py:193-199."""
     return torch.device("cuda:%d" % gpu_id) if torch.cuda.is_available() else torch.device("cpu")
