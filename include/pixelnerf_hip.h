@@ -607,6 +607,18 @@ int pnr_pyramid_to_latent(const float *const *stages, const int *channels, const
                           const int *widths, int n_stages, int NV, float *latent_nhwc,
                           float *latent_nchw, void *stream);
 
+/* Backward of the above: src/model/encoder.py:150-163 under autograd (upsample_bilinear2d backward of
+ * every stage + the cat's channel slicing).  d_latent is the gradient of the grid, channel-last
+ * (NV, H0, W0, sum channels) -- the layout pnr_latent_scatter produces -- or, with d_latent_is_nchw != 0,
+ * (NV, sum channels, H0, W0).  d_stages: HOST array of n_stages device pointers, d_stages[s] is
+ * (NV, channels[s], heights[s], widths[s]) NCHW fp32; EVERY element is written (the caller does not zero
+ * it, nothing is accumulated).  A texel gathers h * w * g over the output pixels whose forward read it,
+ * with the forward's fp32 indices and weights, in a fixed order and without atomics: two calls give the
+ * same bits.  Accepts exactly what pnr_pyramid_to_latent accepts (d_latent 16-byte aligned). */
+int pnr_pyramid_to_latent_backward(const float *d_latent, int d_latent_is_nchw, float *const *d_stages,
+                                   const int *channels, const int *heights, const int *widths,
+                                   int n_stages, int NV, void *stream);
+
 /* ---- next-row helpers: eval epilogue on device ----------------------
  * eval/eval.py:283-290,327-329 and util.psnr (src/util/util.py:474-481): rgb (n_views,pixels,3) ->
  * clamp to [0,1] [-> uint8 = trunc(x*255)]; depth -> (d - z_near)/(z_far - z_near); per-view sum

@@ -11,6 +11,7 @@ backward : HIP kernels only (no library GEMM, no torch matmul) --
              pnr_weight_grad_batched  dW = dY^T X, db = sum dY    from the 16-bit dumps (MFMA, fp32 acc), one launch
              pnr_lin_out_grad         lin_out's 4 x 512 weight gradient
              pnr_position_backward    d(network inputs)           -> d(sample positions z)
+             pnr_pyramid_to_latent_backward  d(feature grid), channel-last as the scatter wrote it -> d(ResNet stage outputs)
 At the default precision "f16x3" (fp32-class) the network calls are replaced by their split-operand forms, fused the same way:
              pnr_eval_ray_samples_split_train   the fp32-class inference kernel in its training instantiation (operand images
                                                 + relu masks kept, lin_z through the folded fp32 tables)
@@ -247,7 +248,13 @@ class _RenderFunction(torch.autograd.Function):
             ps["dumps"].release()
             ps["dumps"] = None
         ctx.passes = None  # release the 16-bit operand dumps (~12 KB per point and view) as soon as they are used
-        out = [None, cam[0], (d_lat[0] if d_lat.shape[0] == 1 else d_lat.sum(0)).permute(0, 3, 1, 2).contiguous() if need_latent else None]
+        g_lat = None
+        if need_latent:
+            # the reference's NCHW shape; the channel-last MEMORY stays when the latent's own node reads it that way
+            g_lat = (d_lat[0] if d_lat.shape[0] == 1 else d_lat.sum(0)).permute(0, 3, 1, 2)
+            if not cfg.get("latent_grad_channel_last", False):
+                g_lat = g_lat.contiguous()
+        out = [None, cam[0], g_lat]
         out += [None if g is None else g.reshape(shp) for g, shp in zip(cam[1:], ctx.cam_shapes)]
         for slot in range(ctx.n_params // n_each):
             g = gsum[slot]
@@ -295,7 +302,9 @@ class _PointsFunction(torch.autograd.Function):
             n, c, hl, wl = ctx.latent_shape
             d_lat = torch.zeros((n, hl, wl, c), dtype=torch.float32, device=g.device)
             ops.latent_scatter(ctx.scene, ctx.rays, ctx.z, d_zlat, d_lat)
-            d_lat = d_lat.permute(0, 3, 1, 2).contiguous()
+            d_lat = d_lat.permute(0, 3, 1, 2)
+            if not ctx.cfg.get("latent_grad_channel_last", False):
+                d_lat = d_lat.contiguous()
         bd.release()
         ctx.dumps.release()
         ctx.dumps = None
@@ -444,6 +453,42 @@ def linear_autograd(x, weight, bias=None, relu_in=False, residual=None, precisio
     return _LinearFunction.apply(x, weight, bias, residual, bool(relu_in), precision)
 
 
+class _PyramidFunction(torch.autograd.Function):
+    """Encoder output formatting (src/model/encoder.py:150-163) as ONE autograd node: forward = pnr_pyramid_to_latent
+    (the reference's NCHW `latent` + the channel-last grid the fused kernels read, not differentiable on its own), backward =
+    pnr_pyramid_to_latent_backward.  A gradient that arrives as channel-last memory (what the render backward hands over
+    for a latent made here) goes to the kernel as it is; anything else is made contiguous and read as NCHW."""
+
+    @staticmethod
+    def forward(ctx, *levels):
+        nhwc, nchw = ops.pyramid_to_latent(levels, want_nchw=True)
+        ctx.shapes = [tuple(t.shape) for t in levels]
+        ctx.mark_non_differentiable(nhwc)
+        return nchw, nhwc
+
+    @staticmethod
+    def backward(ctx, g, _):
+        if g is None:
+            return (None,) * len(ctx.shapes)
+        g = g.float()
+        if g.permute(0, 2, 3, 1).is_contiguous():
+            grads = ops.pyramid_to_latent_backward(g.permute(0, 2, 3, 1), ctx.shapes, nchw=False)
+        else:
+            grads = ops.pyramid_to_latent_backward(g.contiguous(), ctx.shapes, nchw=True)
+        return tuple(d if need else None for d, need in zip(grads, ctx.needs_input_grad))
+
+
+def pyramid_to_latent_autograd(levels):
+    """-> (latent (NV,sum C,H0,W0) with the HIP backward behind it, latent_nhwc (NV,H0,W0,sum C) detached)."""
+    return _PyramidFunction.apply(*levels)
+
+
+def _channel_last_grad(net, latent):
+    """may the grid gradient of this call stay channel-last memory?  Only for the latent the encoder's own HIP node made."""
+    enc = getattr(net, "encoder", None)
+    return bool(enc is not None and hasattr(enc, "latent_takes_channel_last_grad") and enc.latent_takes_channel_last_grad(latent))
+
+
 def _refuse_stream_scale(net):
     """the differentiable paths run the network unscaled: a net that renders at a stream scale cannot be trained through"""
     scales = [int(getattr(m, "stream_scale", 0) or 0) for m in (net.mlp_coarse, net.mlp_fine) if m is not None]
@@ -465,7 +510,7 @@ def points_autograd(net, xyz, viewdirs, coarse):
     if net.stop_encoder_grad:
         latent = latent.detach()
     mlp = net.mlp_coarse if (coarse or net.mlp_fine is None) else net.mlp_fine
-    out = _PointsFunction.apply(dict(net=net, coarse=coarse), xyz.reshape(-1, 3).float().contiguous(),
+    out = _PointsFunction.apply(dict(net=net, coarse=coarse, latent_grad_channel_last=_channel_last_grad(net, latent)), xyz.reshape(-1, 3).float().contiguous(),
                                 viewdirs.reshape(-1, 3).float().contiguous(), latent, *mlp.ordered_params(PARAM_NAMES))
     return out.reshape(SB, B, 4)
 
@@ -489,6 +534,7 @@ def render_autograd(renderer, net, rays, noise, want_weights):
     for m in mlps:
         params += m.ordered_params(PARAM_NAMES)
     sync = getattr(net, "_grad_sync", None)
+    cfg["latent_grad_channel_last"] = sync is None and _channel_last_grad(net, latent)  # (the all-reduce buckets take NCHW)
     if sync is not None:  # multi-process training (dist.ShardedRenderWrapper): identity here, ONE gradient all-reduce in backward
         latent, params = sync(latent, params)
     outs = _RenderFunction.apply(cfg, rays, latent, net.poses, net.focal, net.c, *params)

@@ -19,6 +19,8 @@
 // with lanes along the pixels (128-byte runs of a channel plane).
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+
 #include "pnr_common.h"
 
 namespace pnr {
@@ -223,6 +225,139 @@ pyramid_to_latent_kernel(const Pyramid p, int H0, int W0, float *__restrict__ nh
         }
     }
 }
+
+// ---------------------------------------------------------------- backward of the encoder output formatting
+// src/model/encoder.py:150-163 under autograd (upsample_bilinear2d backward per stage + the cat's slicing), in GATHER form: a
+// stage texel (n, c, ys, xs) is the sum of h * w * g over the output pixels whose forward read it.  No atomics, fixed loop
+// order (rows outer, columns inner, ascending): two calls give the same bits.  The contributors of a source row / column are
+// a contiguous range of output rows / columns because the forward's source index i0(dst) is non-decreasing in dst; the range
+// comes from an estimate (s / scale) corrected with the forward's own fp32 expression, so that a pixel feeds exactly the
+// texels the forward read, also where rounding puts i0 one off the real-number answer.
+#pragma clang fp contract(off)
+// the forward's taps of one output coordinate (above: src = scale * dst, i0 = min((int)src, in-1), i1 = i0 + (i0 < in-1),
+// l1 = src - i0, l0 = 1 - l1) and what of them lands on source index s: l0, l1, or l0 + l1 where i0 == i1 == in-1 == s
+__device__ __forceinline__ int axis_i0(float scale, int dst, int in) { return min((int)(scale * (float)dst), in - 1); }
+__device__ __forceinline__ float axis_weight(float scale, int dst, int in, int s) {
+    const float src = scale * (float)dst;
+    const int i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    const float l1 = src - (float)i0, l0 = 1.f - l1;
+    return (i0 == s ? l0 : 0.f) + (i1 == s ? l1 : 0.f);
+}
+// [lo, hi] = the output coordinates with i0 in {s-1, s} (empty: lo > hi).  scale == 0 (in == 1 or out == 1): i0 == 0 everywhere.
+__device__ __forceinline__ void axis_range(float scale, int in, int out, int s, int &lo, int &hi) {
+    const float top = (float)(out - 1);
+    int l = scale > 0.f ? (int)fminf(fmaxf((float)(s - 1) / scale, 0.f), top) : 0;
+    while (l > 0 && axis_i0(scale, l - 1, in) >= s - 1) --l;
+    while (l < out && axis_i0(scale, l, in) < s - 1) ++l;
+    int h = scale > 0.f ? (int)fminf((float)(s + 1) / scale, top) : out - 1;
+    while (h + 1 < out && axis_i0(scale, h + 1, in) <= s) ++h;
+    while (h >= 0 && axis_i0(scale, h, in) > s) --h;
+    lo = l; hi = h;
+}
+
+struct StageGrad {  // one stage of the pyramid and where its channels sit in the grid gradient
+    float *dst;     // (NV, Cs, Hs, Ws)
+    int cb, Cs, Hs, Ws, same;
+    float sy, sx;
+};
+
+constexpr int PB_TEX = 32;  // source texels of one row per workgroup: the stage stores are 128-byte runs of a channel plane
+
+// Channel-last gradient (NV,H0,W0,Ctot), the layout pnr_latent_scatter writes.  One workgroup = PB_TEX texels of ONE source row
+// x 4*LQ channels.  LQ lanes lie along the channels, 16 bytes each (LQ = 64 for a stage of 256 k channels: a wave instruction
+// reads 1 KiB of one pixel's row, as the forward writes it; 32 / 16 for 128 k / 64 k channels: 512 / 256-byte pieces of 2 / 4
+// pixels); a thread keeps PB_TEX * LQ / 256 texels in registers and walks the output rows (uniform) and its texels' columns.
+// The sums turn to NCHW through an LDS tile [channel][texel + 1]: the read side (lanes along the texels) is conflict-free, the
+// write side 2-way (lanes q and q + 8 of a 32-lane half share a bank: 4 * 33 * 8 = 0 mod 32) -- 4 LDS writes per ~100 loads.
+// Bound: not HBM.  The algorithmic bytes are |d_latent| + sum |d_stages|, but every output row is read for both source rows it
+// feeds and every column for both source columns (the column re-read hits the L1 of the same workgroup, the row re-read the
+// L2): like the forward's first form the kernel lives on the CU's vector-memory return path, 16 bytes per lane and load with
+// ~12 VALU operations of weight arithmetic between two loads.  A "same" stage is a channel-slice copy with a layout change.
+template <int LQ>
+__global__ void __launch_bounds__(256)
+pyramid_backward_kernel(const float *__restrict__ g, int H0, int W0, int Ctot, const StageGrad st) {
+    constexpr int CC = 4 * LQ, TG = 256 / LQ, NT = PB_TEX / TG;
+    __shared__ float tile[CC][PB_TEX + 1];
+    const int t = threadIdx.x, q = t % LQ, tg = t / LQ;
+    const int n = blockIdx.y;
+    const int tiles_x = (st.Ws + PB_TEX - 1) / PB_TEX, chunks = st.Cs / CC;
+    int b = blockIdx.x;  // uniform: (source row, channel chunk, texel tile)
+    const int xt = b % tiles_x; b /= tiles_x;
+    const int ck = b % chunks, ys = b / chunks;
+    const int xs0 = xt * PB_TEX, c0 = ck * CC;
+    int ylo = ys, yhi = ys;
+    if (!st.same) axis_range(st.sy, st.Hs, H0, ys, ylo, yhi);
+    int lo[NT], hi[NT];
+    f32x4_t acc[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        const int xs = xs0 + tg + k * TG;
+        acc[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        lo[k] = 1; hi[k] = 0;
+        if (xs < st.Ws) {
+            if (st.same) lo[k] = hi[k] = xs;
+            else axis_range(st.sx, st.Ws, W0, xs, lo[k], hi[k]);
+        }
+    }
+    // 64-bit view and row bases; a column's offset x * Ctot stays 64-bit too (W0 * Ctot is not bounded by the stage limit)
+    const float *gv = g + (size_t)n * H0 * W0 * Ctot + (st.cb + c0 + q * 4);
+    for (int y = ylo; y <= yhi; ++y) {
+        const float hy = st.same ? 1.f : axis_weight(st.sy, y, st.Hs, ys);  // uniform
+        const float *row = gv + (size_t)y * W0 * Ctot;
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            const int xs = xs0 + tg + k * TG;
+            for (int x = lo[k]; x <= hi[k]; ++x) {
+                const float w = st.same ? 1.f : hy * axis_weight(st.sx, x, st.Ws, xs);
+                const f32x4_t v = *reinterpret_cast<const f32x4_t *>(row + (size_t)x * Ctot);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[k][e] = __builtin_fmaf(w, v[e], acc[k][e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NT; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tile[q * 4 + e][tg + k * TG] = acc[k][e];
+    __syncthreads();
+    const int tx = t % PB_TEX, cg = t / PB_TEX;
+    if (xs0 + tx < st.Ws) {
+        const size_t plane = (size_t)st.Hs * st.Ws;
+        float *d = st.dst + ((size_t)n * st.Cs + c0 + cg) * plane + (size_t)ys * st.Ws + xs0 + tx;
+        for (int c = cg; c < CC; c += 256 / PB_TEX, d += (256 / PB_TEX) * plane) *d = tile[c][tx];
+    }
+}
+
+// NCHW gradient (NV,Ctot,H0,W0) -- what torch hands over when the consumer of `latent` was not the HIP renderer; not the hot
+// path.  Lanes along the source texels of one row, one wave per channel: reads and stores walk a channel plane.
+__global__ void __launch_bounds__(256)
+pyramid_backward_nchw_kernel(const float *__restrict__ g, int H0, int W0, int Ctot, const StageGrad st) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int n = blockIdx.y;
+    const int tiles_x = (st.Ws + 63) / 64;
+    int b = blockIdx.x;
+    const int xt = b % tiles_x; b /= tiles_x;
+    const int ys = b % st.Hs, c = (b / st.Hs) * 4 + wv;
+    const int xs = xt * 64 + lane;
+    if (xs >= st.Ws) return;
+    int ylo = ys, yhi = ys, xlo = xs, xhi = xs;
+    if (!st.same) {
+        axis_range(st.sy, st.Hs, H0, ys, ylo, yhi);
+        axis_range(st.sx, st.Ws, W0, xs, xlo, xhi);
+    }
+    const float *plane = g + ((size_t)n * Ctot + st.cb + c) * H0 * W0;
+    float acc = 0.f;
+    for (int y = ylo; y <= yhi; ++y) {
+        const float hy = st.same ? 1.f : axis_weight(st.sy, y, st.Hs, ys);
+        const float *row = plane + (size_t)y * W0;
+        for (int x = xlo; x <= xhi; ++x) {
+            const float w = st.same ? 1.f : hy * axis_weight(st.sx, x, st.Ws, xs);
+            acc = __builtin_fmaf(w, row[x], acc);
+        }
+    }
+    st.dst[(((size_t)n * st.Cs + c) * st.Hs + ys) * st.Ws + xs] = acc;
+}
+#pragma clang fp contract(fast)
 
 // PositionalEncoding.forward, src/model/code.py:30-42, for callers that use the module on its own (the fused kernels form the
 // code of their 3-vectors in registers, pnr_device.h):  out[n] = [x[n]] ++ sin(phases[j] + x[n][d] * freqs[j]) with j = 0 .. 2F-1
@@ -656,28 +791,29 @@ extern "C" int pnr_positional_encoding_backward(const float *x, const float *g_o
     return pnr_check_launch("pnr_positional_encoding_backward");
 }
 
-extern "C" int pnr_pyramid_to_latent(const float *const *stages, const int *channels, const int *heights, const int *widths,
-                                     int n_stages, int NV, float *latent_nhwc, float *latent_nchw, void *stream) {
-    if (n_stages < 1 || n_stages > pnr::MAX_STAGES) return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: 1..5 stages");
-    if (!stages || !channels || !heights || !widths || !latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: null argument");
-    if (NV < 0) return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: bad sizes");
-    pnr::Pyramid p = {};
+// What pnr_pyramid_to_latent and its backward accept (one rule for both: whatever the forward takes has a backward)
+// -> nullptr, or the reason.  Past the NV == 0 return it fills the forward's launch geometry: p, the run length P, the LDS bytes.
+static const char *pyramid_check(const void *const *stages, const int *channels, const int *heights, const int *widths, int n_stages,
+                                 int NV, const void *grid, pnr::Pyramid &p, int &P, size_t &lds) {
+    if (n_stages < 1 || n_stages > pnr::MAX_STAGES) return "1..5 stages";
+    if (!stages || !channels || !heights || !widths || !grid) return "null argument";
+    if (NV < 0) return "bad sizes";
+    p = {};
     p.n = n_stages;
     int c = 0;
     for (int s = 0; s < n_stages; ++s) {
         if (!stages[s] || channels[s] <= 0 || channels[s] % pnr::FT_C != 0 || heights[s] <= 0 || widths[s] <= 0)
-            return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: stage channels must be positive multiples of 64, sizes positive");
-        if ((long long)channels[s] * heights[s] * widths[s] >= (1LL << 29))
-            return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: a stage of one view must stay below 2 GiB");
-        p.src[s] = stages[s]; p.c_begin[s] = c; p.H[s] = heights[s]; p.W[s] = widths[s];
+            return "stage channels must be positive multiples of 64, sizes positive";
+        if ((long long)channels[s] * heights[s] * widths[s] >= (1LL << 29)) return "a stage of one view must stay below 2 GiB";
+        p.src[s] = (const float *)stages[s]; p.c_begin[s] = c; p.H[s] = heights[s]; p.W[s] = widths[s];
         c += channels[s];
     }
     p.c_begin[n_stages] = c;
-    if (NV == 0) return PNR_OK;
+    if (NV == 0) return nullptr;
     const int H0 = heights[0], W0 = widths[0];
     // pixels per workgroup: the longest run whose source windows leave room for >= 3 workgroups per CU (else the shortest)
-    int P = 32;
-    size_t lds = 0;
+    P = 32;
+    lds = 0;
     auto layout = [&](int run) {
         int off = 0;
         for (int s = 0; s < n_stages; ++s) {
@@ -696,18 +832,65 @@ extern "C" int pnr_pyramid_to_latent(const float *const *stages, const int *chan
         lds = layout(P);
         if (lds <= 48 * 1024 || P == 8) break;
     }
-    if (lds > 160 * 1024) return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: source windows do not fit the LDS (too many channels)");
+    if (lds > 160 * 1024) return "source windows do not fit the LDS (too many channels)";
     for (int s = 0; s < n_stages; ++s)
-        if (p.nxw[s] > 256) return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: a stage more than 32x wider than stage 0 is not supported");
+        if (p.nxw[s] > 256) return "a stage more than 32x wider than stage 0 is not supported";
+    if (H0 > 65535 || NV > 65535) return "grid too large";
+    return nullptr;
+}
+
+static int pyramid_fail(const char *who, const char *why) {
+    char msg[192];
+    std::snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    return pnr_fail(PNR_E_INVALID, msg);
+}
+
+extern "C" int pnr_pyramid_to_latent(const float *const *stages, const int *channels, const int *heights, const int *widths,
+                                     int n_stages, int NV, float *latent_nhwc, float *latent_nchw, void *stream) {
+    pnr::Pyramid p;
+    int P = 0;
+    size_t lds = 0;
+    if (const char *why = pyramid_check((const void *const *)stages, channels, heights, widths, n_stages, NV, latent_nhwc, p, P, lds))
+        return pyramid_fail("pnr_pyramid_to_latent", why);
+    if (NV == 0) return PNR_OK;
+    const int H0 = heights[0], W0 = widths[0];
     auto k = P == 32 ? pnr::pyramid_to_latent_kernel<32> : (P == 16 ? pnr::pyramid_to_latent_kernel<16> : pnr::pyramid_to_latent_kernel<8>);
     if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit (not reached by the shipped encoder shapes)
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(pyramid_to_latent_kernel)");
     }
     const int tiles_x = (W0 + P - 1) / P;
-    if (H0 > 65535 || NV > 65535) return pnr_fail(PNR_E_INVALID, "pnr_pyramid_to_latent: grid too large");
     hipLaunchKernelGGL(k, dim3(tiles_x, H0, NV), dim3(256), lds, (hipStream_t)stream, p, H0, W0, latent_nhwc, latent_nchw);
     return pnr_check_launch("pnr_pyramid_to_latent");
+}
+
+extern "C" int pnr_pyramid_to_latent_backward(const float *d_latent, int d_latent_is_nchw, float *const *d_stages, const int *channels,
+                                              const int *heights, const int *widths, int n_stages, int NV, void *stream) {
+    pnr::Pyramid p;
+    int P = 0;
+    size_t lds = 0;
+    if (const char *why = pyramid_check((const void *const *)d_stages, channels, heights, widths, n_stages, NV, d_latent, p, P, lds))
+        return pyramid_fail("pnr_pyramid_to_latent_backward", why);
+    if (NV == 0) return PNR_OK;
+    if (((size_t)d_latent & 15) != 0) return pyramid_fail("pnr_pyramid_to_latent_backward", "d_latent must be 16-byte aligned");
+    const int H0 = heights[0], W0 = widths[0], Ctot = p.c_begin[n_stages];
+    for (int s = 0; s < n_stages; ++s) {  // one launch per stage: all geometry is kernel arguments (scalar registers)
+        pnr::StageGrad st;
+        st.dst = d_stages[s]; st.cb = p.c_begin[s]; st.Cs = channels[s]; st.Hs = heights[s]; st.Ws = widths[s];
+        st.same = p.same[s]; st.sy = p.sy[s]; st.sx = p.sx[s];
+        // the flattened grids stay below 2^31: Cs Hs Ws < 2^29 and every tile holds at least one texel of >= 4 channels
+        if (d_latent_is_nchw) {
+            const long long blocks = (long long)(st.Cs / 4) * st.Hs * ((st.Ws + 63) / 64);
+            hipLaunchKernelGGL(pnr::pyramid_backward_nchw_kernel, dim3((unsigned)blocks, NV), dim3(256), 0, (hipStream_t)stream, d_latent,
+                               H0, W0, Ctot, st);
+        } else {
+            const int LQ = st.Cs % 256 == 0 ? 64 : (st.Cs % 128 == 0 ? 32 : 16);
+            const long long blocks = (long long)(st.Cs / (4 * LQ)) * st.Hs * ((st.Ws + pnr::PB_TEX - 1) / pnr::PB_TEX);
+            auto k = LQ == 64 ? pnr::pyramid_backward_kernel<64> : (LQ == 32 ? pnr::pyramid_backward_kernel<32> : pnr::pyramid_backward_kernel<16>);
+            hipLaunchKernelGGL(k, dim3((unsigned)blocks, NV), dim3(256), 0, (hipStream_t)stream, d_latent, H0, W0, Ctot, st);
+        }
+    }
+    return pnr_check_launch("pnr_pyramid_to_latent_backward");
 }
 
 extern "C" int pnr_grid_index(const float *latent_nhwc, int NV, int Hl, int Wl, int C, const float *uv, long long N, float *out,

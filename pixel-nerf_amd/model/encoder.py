@@ -9,12 +9,13 @@ each resampled to the first stage's resolution, concatenated along the channels.
 channel-last copy of `latent` made by `latent_nhwc()`; called on its own it is a HIP operator too (`pnr_grid_index` +
 backward, csrc/pnr_encode.hip), like `PositionalEncoding`."""
 import warnings
+import weakref
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import ops
+from .. import autograd, ops
 
 
 class _BasicBlock(nn.Module):
@@ -100,6 +101,7 @@ class SpatialEncoder(nn.Module):
         self.register_buffer("latent", torch.empty(1, 1, 1, 1), persistent=False)
         self.register_buffer("latent_scaling", torch.empty(2, dtype=torch.float32), persistent=False)
         self._nhwc = None
+        self._hip_latent = None
         if pretrained:
             import os
             path = os.environ.get("PIXELNERF_RESNET_WEIGHTS")
@@ -123,13 +125,18 @@ class SpatialEncoder(nn.Module):
     # (`__getstate__`, which copy.deepcopy and pickle both go through: a CUDAGraph is a process-local handle).
     use_graph = True
     MAX_GRAPHS = 4
-    _TRANSIENT = ("_graphs", "latents", "_nhwc", "_scaling_cache")  # per-process caches: rebuilt on demand, never part of a copy / checkpoint
+    # With grad enabled the formatting pass is the same HIP operator, wrapped in an autograd node whose backward is
+    # pnr_pyramid_to_latent_backward (deterministic gather, takes the renderer's channel-last grid gradient as it is).
+    # False restores torch's interpolate + cat under autograd (A/B timing, comparison tests).
+    hip_format_backward = True
+    _TRANSIENT = ("_graphs", "latents", "_nhwc", "_scaling_cache", "_hip_latent")  # per-process caches: rebuilt on demand, never part of a copy / checkpoint
 
     def __getstate__(self):
         state = self.__dict__.copy()
         for k in self._TRANSIENT:
             state.pop(k, None)
         state["_nhwc"] = None
+        state["_hip_latent"] = None
         return state
 
     def _apply(self, fn, *args, **kwargs):
@@ -212,14 +219,23 @@ class SpatialEncoder(nn.Module):
     def _forward_eager(self, x, scaling=True):
         levels = self._stages(self._resize_input(x).to(device=self.latent.device))
         self.latents = levels
-        fused_ok = (not torch.is_grad_enabled() and x.is_cuda and levels[0].dtype == torch.float32
+        grad = torch.is_grad_enabled()
+        fused_ok = ((not grad or self.hip_format_backward) and x.is_cuda and levels[0].dtype == torch.float32
                     and self.upsample_interp == "bilinear" and all(t.shape[1] % 64 == 0 for t in levels))
+        self._hip_latent = None
         if fused_ok:
-            # inference: one HIP pass writes the NHWC grid the fused kernel reads AND the reference's NCHW tensor
-            nhwc, self.latent = ops.pyramid_to_latent(levels, want_nchw=True)
-            self._nhwc = ((self.latent.data_ptr(), self.latent._version, tuple(self.latent.shape)), nhwc)
+            # one HIP pass writes the NHWC grid the fused kernel reads AND the reference's NCHW tensor; when a level
+            # carries a gradient the pass is an autograd node (backward: pnr_pyramid_to_latent_backward)
+            if grad and any(t.requires_grad for t in levels):
+                self.latent, nhwc = autograd.pyramid_to_latent_autograd(levels)
+            else:
+                nhwc, self.latent = ops.pyramid_to_latent(levels, want_nchw=True)
+            key = (self.latent.data_ptr(), self.latent._version, tuple(self.latent.shape))
+            self._nhwc = (key, nhwc)
+            if self.latent.grad_fn is not None:
+                self._hip_latent = (key, weakref.ref(self.latent))
         else:
-            # training (autograd must see the resampling) or a non-default interpolation: torch's own resampling of every
+            # hip_format_backward off, or a non-default interpolation / shape: torch's own resampling of every
             # level to the first level's size.  The reference asks for align_corners=True whatever the mode (its test for
             # "nearest" can never match, encoder.py:152), which only the interpolating modes accept -- same here.
             size = levels[0].shape[-2:]
@@ -249,6 +265,13 @@ class SpatialEncoder(nn.Module):
         if self._nhwc is None or self._nhwc[0] != key:
             self._nhwc = (key, ops.nchw_to_nhwc(lat.detach().float()))
         return self._nhwc[1]
+
+    def latent_takes_channel_last_grad(self, lat):
+        """True when `lat` is the tensor the last encode produced through the HIP formatting node: its backward reads a
+        channel-last grid gradient as it is, so the renderer need not transpose it (autograd._RenderFunction.backward)."""
+        rec = self._hip_latent
+        return (rec is not None and rec[1]() is lat and lat.is_cuda
+                and rec[0] == (lat.data_ptr(), lat._version, tuple(lat.shape)))
 
     def index(self, uv, cam_z=None, image_size=(), z_bounds=None):
         """Pixel-aligned features at image points (encoder.py:80-109), for callers that use the encoder on its own (the

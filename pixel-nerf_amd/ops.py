@@ -952,6 +952,32 @@ def pyramid_to_latent(stages, want_nchw=True):
     return nhwc, nchw
 
 
+def pyramid_to_latent_backward(d_latent, stage_shapes, nchw=False):
+    """Backward of `pyramid_to_latent` (src/model/encoder.py:150-163 under autograd).  d_latent: the grid's gradient,
+    (NV,H0,W0,sum C) channel-last, or with nchw=True (NV,sum C,H0,W0); stage_shapes: the (NV,C_s,H_s,W_s) of every stage.
+    -> list of float32 stage gradients of those shapes (every element written; deterministic)."""
+    lib = _lib.load()
+    shapes = [tuple(int(v) for v in shp) for shp in stage_shapes]
+    if not shapes or any(len(shp) != 4 for shp in shapes):
+        raise ValueError("stage_shapes: a non-empty list of (NV, C, H, W)")
+    n = len(shapes)
+    NV, _, H0, W0 = shapes[0]
+    if any(shp[0] != NV for shp in shapes):
+        raise ValueError("all stages must have the same batch size")
+    Ctot = sum(shp[1] for shp in shapes)
+    d_latent = _f32(d_latent, "d_latent", (NV, Ctot, H0, W0) if nchw else (NV, H0, W0, Ctot))
+    dev = d_latent.device
+    outs = [torch.empty(shp, dtype=torch.float32, device=dev) for shp in shapes]
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
+    ch = (ctypes.c_int * n)(*[shp[1] for shp in shapes])
+    hs = (ctypes.c_int * n)(*[shp[2] for shp in shapes])
+    wd = (ctypes.c_int * n)(*[shp[3] for shp in shapes])
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_pyramid_to_latent_backward(_p(d_latent), 1 if nchw else 0, ptrs, ch, hs, wd, n, NV, _stream()),
+                   "pnr_pyramid_to_latent_backward")
+    return outs
+
+
 def sample_training_rays(poses, images, focal, z_near, z_far, ids, c=None, bboxes=None, ux=None, uy=None):
     """train/train.py:143-182 on device.  poses (SB,NV,4,4), images (SB,NV,3,H,W) in [-1,1], focal (SB,2),
     c (SB,2)|None; ids (SB,B) int64: view ids (with bboxes (SB,NV,4) + ux, uy (SB,B)) or flat pixel indices.
