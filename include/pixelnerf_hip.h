@@ -730,6 +730,54 @@ int pnr_mlp_backward_f32(const PnrMlpWeights *w /*host*/, const PnrF32Saved *sav
 int pnr_point_features_f32(const PnrScene *scene /*host*/, const float *xyz, const float *viewdirs, int B,
                            float *in42, float *zlat, void *stream);
 
+/* ---- mesh extraction (src/util/recon.py; the grid of src/util/util.py:93-110) ----------------
+ * src/util/recon.py:43,54 with src/util/util.py:93-110: rows first .. first+count of
+ * util.gen_grid((c1x,c2x,nx), (c1y,c2y,ny), (c1z,c2z,nz), ij_indexing=True) -- x the slowest
+ * axis -- with every coordinate np.linspace(lo, hi, n, dtype=float32)'s value (numpy's fp64
+ * expression restated: i * ((hi-lo)/(n-1)) + lo, the last point = hi, cast to float32).
+ * c1, c2 (doubles), reso: HOST arrays of 3.  xyz (count,3) device.  viewdirs (count,3) device or
+ * NULL: the reference's "fake" direction -p/|p| (recon.py:54) in fp32.  Deviation: a point of
+ * norm 0 gets (0,0,0), not the reference's 0/0 = NaN. */
+int pnr_gen_grid_points(const double *c1 /*host*/, const double *c2 /*host*/, const int *reso /*host*/,
+                        long long first, long long count, float *xyz, float *viewdirs /*nullable*/,
+                        void *stream);
+
+/* src/util/recon.py:68-78 (where the reference calls PyMCubes on the host): marching cubes on a
+ * density grid, on device.  field (nx,ny,nz) fp32, C-contiguous (sigmas.view(*reso)).
+ *   inside   : a corner is inside iff its value is finite and > iso (== iso is outside; a
+ *              non-finite value is outside and counted in n_nonfinite).
+ *   vertices : an indexed mesh, one vertex per grid edge whose ends differ, shared by the cells
+ *              around the edge; ordered by owning grid point (the edge's lower end, linear index
+ *              (i ny + j) nz + k), then axis x, y, z.  From the lower end a to the upper end b:
+ *              t = (iso - f_a) / (f_b - f_a) in fp32, computed once per edge (no cracks from
+ *              rounding); a non-finite end cannot be interpolated through: the vertex sits on the
+ *              finite end (t = 0 or 1).  Index space: (i,j,k) + t e_axis; output: index * scale + c1
+ *              (separately rounded fp32).
+ *   triangles: cells in ascending linear order, within a cell the case table's order; winding
+ *              such that (v1 - v0) x (v2 - v0) points from inside to outside.
+ *   tables   : corner c = dx + 2 dy + 4 dz (bit c of the case index = inside); edge e = 4 axis + r
+ *              joins the corner whose other two coordinates, in axis order, are (r & 1, r >> 1)
+ *              with its neighbour along axis.  On every cube face the patch boundary depends on the
+ *              face's four flags alone; on an ambiguous face each inside corner is cut off on its
+ *              own.  pnr_marching_cubes_tables (host): edge_mask[256] (bit e: edge e carries a
+ *              vertex), tri[256*16] (up to five triangles as edge ids, -1 terminated).
+ * pnr_marching_cubes_count classifies, takes the exclusive prefix sums (a hand-written integer
+ * scan: block sums, a scan of the block sums, the add -- no atomics, the same bytes every run)
+ * into `workspace` (device, 8-byte aligned, pnr_marching_cubes_workspace_bytes; the caller's) and
+ * leaves counts_dev = [n_vertices, n_triangles, n_nonfinite] (3 ints, device; the last two
+ * saturate at INT_MAX).  The library does not synchronise: the caller reads the counts, allocates
+ * vertices (n_vertices,3) fp32 and triangles (n_triangles,3) int32 and calls
+ * pnr_marching_cubes_emit with the SAME field, sizes, iso and workspace.  c1, scale: HOST arrays
+ * of 3 floats.  PNR_E_INVALID for n < 2 on any axis and for 3 nx ny nz >= 2^31 (edge ids are
+ * int32); the workspace size of such a grid is 0. */
+size_t pnr_marching_cubes_workspace_bytes(int nx, int ny, int nz);
+int pnr_marching_cubes_count(const float *field, int nx, int ny, int nz, float iso, void *workspace,
+                             int *counts_dev, void *stream);
+int pnr_marching_cubes_emit(const float *field, int nx, int ny, int nz, float iso,
+                            const float *c1 /*host*/, const float *scale /*host*/,
+                            const void *workspace, float *vertices, int *triangles, void *stream);
+int pnr_marching_cubes_tables(int *edge_mask /*host, 256*/, int *tri /*host, 256*16*/);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

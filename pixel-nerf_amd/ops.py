@@ -1028,6 +1028,69 @@ def ssim(pred, gt, win_size=7, data_range=1.0):
     return out
 
 
+def gen_grid_points(c1, c2, reso, first=0, count=None, device="cuda", viewdirs=True):
+    """src/util/recon.py:43,54 on device (pnr_gen_grid_points): rows first .. first+count of
+    util.gen_grid(*zip(c1, c2, reso), ij_indexing=True) -- bit for bit numpy's float32 linspace values, x the slowest axis --
+    and, with viewdirs, the reference's "fake" directions -p/|p| (a point of norm 0 gets (0,0,0) where the reference has NaN).
+    -> (xyz (count,3), viewdirs (count,3) | None) fp32 on `device`."""
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.PixelNerfHipError(f"gen_grid_points: device must be a HIP device (got {dev}); pixelnerf_amd has no CPU path")
+    if len(c1) != 3 or len(c2) != 3 or len(reso) != 3:
+        raise ValueError("gen_grid_points: c1, c2, reso must have 3 entries each")
+    reso = [int(r) for r in reso]
+    total = reso[0] * reso[1] * reso[2]
+    count = total - int(first) if count is None else int(count)
+    xyz = torch.empty((max(count, 0), 3), dtype=torch.float32, device=dev)
+    vd = torch.empty_like(xyz) if viewdirs else None
+    lo, hi = (ctypes.c_double * 3)(*[float(v) for v in c1]), (ctypes.c_double * 3)(*[float(v) for v in c2])
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_gen_grid_points(lo, hi, (ctypes.c_int * 3)(*reso), int(first), count, _p(xyz), _p(vd), _stream()),
+                   "pnr_gen_grid_points")
+    return xyz, vd
+
+
+def marching_cubes_tables():
+    """the case tables the marching-cubes kernels use (pnr_marching_cubes_tables; conventions in include/pixelnerf_hip.h):
+    -> (edge_mask (256,) int32, tri (256,16) int32, -1 terminated) numpy arrays"""
+    import numpy as np
+    lib = _lib.load()
+    em, tri = (ctypes.c_int * 256)(), (ctypes.c_int * 4096)()
+    _lib.check(lib.pnr_marching_cubes_tables(em, tri), "pnr_marching_cubes_tables")
+    return np.array(em, dtype=np.int32), np.array(tri, dtype=np.int32).reshape(256, 16)
+
+
+def marching_cubes(field, iso, c1=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0), check_finite=True, return_counts=False):
+    """src/util/recon.py:71 on device (pnr_marching_cubes_count + pnr_marching_cubes_emit; semantics in include/pixelnerf_hip.h).
+    field (nx,ny,nz) fp32 HIP tensor; a corner is inside iff finite and > iso.  -> vertices (nv,3) fp32 = index * scale + c1,
+    triangles (nt,3) int32, on the field's device; the same bytes on every call.  One host synchronisation: reading the three
+    counts.  Non-finite field values count as outside; with check_finite they raise ValueError instead.
+    return_counts adds the tuple (n_vertices, n_triangles, n_nonfinite)."""
+    lib = _lib.load()
+    field = _f32(field, "field", (None, None, None))
+    nx, ny, nz = field.shape
+    dev = field.device
+    nbytes = lib.pnr_marching_cubes_workspace_bytes(nx, ny, nz)
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=dev)
+    counts = torch.empty((3,), dtype=torch.int32, device=dev)
+    lo, sc = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in scale])
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_marching_cubes_count(_p(field), nx, ny, nz, float(iso), _p(ws), _p(counts), _stream()),
+                   "pnr_marching_cubes_count")
+        nv, nt, nonfinite = counts.tolist()  # the one host synchronisation
+        if nonfinite and check_finite:
+            raise ValueError(f"marching_cubes: the field holds {nonfinite} non-finite value(s)")
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        if nv > 0:  # (no vertex, no triangle: nothing to write; the library refuses null outputs)
+            _lib.check(lib.pnr_marching_cubes_emit(_p(field), nx, ny, nz, float(iso), lo, sc, _p(ws), _p(vertices), _p(triangles),
+                                                   _stream()), "pnr_marching_cubes_emit")
+    if return_counts:
+        return vertices, triangles, (nv, nt, nonfinite)
+    return vertices, triangles
+
+
 def eval_epilogue(rgb, depth=None, z_near=0.0, z_far=1.0, gt_rgb=None, want_u8=True, image_shape=None):
     """eval/eval.py:283-290,327-329 on device.  rgb (NV,P,3) [+ depth (NV,P)] [+ gt_rgb (NV,P,3) in [0,1]] ->
     dict(rgb (clamped), rgb_u8, depth_norm, sse (NV,) float64, psnr (NV,) float64).  image_shape=(H, W) with gt_rgb adds

@@ -44,6 +44,16 @@ def ssim(pred, target, win_size=7, data_range=1.0):
     return out[0] if pred.dim() == 3 else out
 
 
+def gen_grid(*args, ij_indexing=False):
+    """src/util/util.py:93-110 (host): the len(args)-dimensional grid of points, each arg (lo, hi, sz) giving
+    np.linspace(lo, hi, sz, dtype=float32) along its axis -> (prod sz, len(args)) float32.  The device counterpart of the
+    three-axis, ij-indexed case is ops.gen_grid_points (bit-identical values, any sub-range of the rows)."""
+    import numpy as np
+    axes = [np.linspace(lo, hi, sz, dtype=np.float32) for lo, hi, sz in args]
+    grid = np.meshgrid(*axes, indexing="ij" if ij_indexing else "xy")
+    return torch.from_numpy(np.ascontiguousarray(np.stack(grid).reshape(len(args), -1).T))
+
+
 def get_cuda(gpu_id):
     """src/util/util.py:193-199."""
     return torch.device("cuda:%d" % gpu_id) if torch.cuda.is_available() else torch.device("cpu")
