@@ -745,28 +745,6 @@ __global__ void dw_reduce_kernel(const DwJobs jobs, const float *__restrict__ pa
 // ---------------------------------------------------------------- compositing backward
 constexpr int CW = 4;  // wavefronts per block
 
-template <typename T> __device__ __forceinline__ T wsum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wscan_mul(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v *= t;
-    }
-    return v;
-}
-__device__ __forceinline__ float wscan_add(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // w_i = a_i T_i, T_i = prod_{j<i} (1 - a_j + 1e-10), a_i = 1 - exp(-delta_i relu(sigma_i))
 // g_i = dL/dw_i = d_rgb.c_i + d_depth z_i + d_w_i - [white] sum(d_rgb)
 // dL/da_i = g_i T_i - (sum_{j>i} g_j w_j) / (1 - a_i + 1e-10)
@@ -788,7 +766,7 @@ __device__ __forceinline__ float composite_bwd_pass(const float *zr, const float
             alpha = 1.f - ex;
         }
         const float tf = valid ? (1.f - alpha + 1e-10f) : 1.f;
-        const float incl = wscan_mul(tf, lane);
+        const float incl = wave_scan_mul(tf, lane);
         float excl = __shfl_up(incl, 1, 64);
         if (lane == 0) excl = 1.f;
         const float T = carry * excl;
@@ -799,7 +777,7 @@ __device__ __forceinline__ float composite_bwd_pass(const float *zr, const float
         if (PASS == 0) {
             acc += gw;
         } else {
-            const float pre = wscan_add(gw, lane) + run;   // sum_{j<=i} g_j w_j
+            const float pre = wave_scan_add(gw, lane) + run;   // sum_{j<=i} g_j w_j
             const float suffix = total - pre;              // sum_{j>i}
             float ddelta = 0.f;
             if (valid) {
@@ -825,7 +803,7 @@ __device__ __forceinline__ float composite_bwd_pass(const float *zr, const float
         }
         carry = carry * __shfl(incl, 63, 64);
     }
-    return PASS == 0 ? wsum(acc) : 0.f;
+    return PASS == 0 ? wave_sum(acc) : 0.f;
 }
 
 __global__ void __launch_bounds__(CW * 64)
@@ -874,16 +852,8 @@ latent_scatter_kernel(const EvalParams q, const float *__restrict__ d_zlat, floa
         const long long gl = g0 + j;
         if (gl >= q.P) break;
         const int g = (int)gl;
-        const int r = g / q.K;
-        const float *ray = q.rays + (size_t)r * 8;
-        const float zz = q.z[g];
-        const float X = ray[0] + zz * ray[3], Y = ray[1] + zz * ray[4], Z = ray[2] + zz * ray[5];
-        const int obj = r / q.per_obj;
-        const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;
-        const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
-        const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
-        const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
-        const Proj pr = project_point(q, pose, obj, view, xr0, xr1, xr2, true);
+        const SamplePoint sp = sample_point(q, g, view);
+        const Proj pr = project_point(q, sp.pose, sp.obj, view, sp.xr0, sp.xr1, sp.xr2, true);
         const float *src = d_zlat + ((size_t)view * q.P + g) * C_LAT + lane * 8;
         const f32x4 a = *reinterpret_cast<const f32x4 *>(src), b = *reinterpret_cast<const f32x4 *>(src + 4);
 #pragma unroll
@@ -937,8 +907,8 @@ latent_scatter_kernel(const EvalParams q, const float *__restrict__ d_zlat, floa
 //   * the L1: a lane read its 32 bytes of a 2 KiB gradient row as two dwordx4 -- 16 waves x 64 lines in flight against
 //     256 lines of cache, each line fetched twice for a quarter of its bytes.
 // Here the merge is done BEFORE lanes are assigned:
-//   * scatter_segments_kernel projects every (view, point) ONCE -- the clamped grid position (ix, iy) of project_point,
-//     8 bytes per point -- and cuts every ray into SEGMENTS: consecutive samples that share the cell (floor ix, floor iy),
+//   * scatter_segments_kernel projects every (view, point) ONCE -- the clamped grid position (ix, iy) of grid_coords
+//     (pnr_geom.h), 8 bytes per point -- and cuts every ray into SEGMENTS: consecutive samples that share the cell (floor ix, floor iy),
 //     i.e. all four corners, at most SEG_B of them; per image a sorted list of segment starts (ballot + scan compaction,
 //     SEG_NSUB workgroups per image);
 //   * latent_scatter_owner_kernel: lane = (segment, 4 channels); the CS / 4 lanes of a segment read adjacent 16-byte pieces of a
@@ -955,8 +925,6 @@ latent_scatter_kernel(const EvalParams q, const float *__restrict__ d_zlat, floa
 constexpr int SLAB_MAX_BYTES = 160 * 1024;  // whole LDS
 constexpr int OWNER_NT = 1024;
 constexpr int SEG_NT = 1024;
-constexpr int SEG_B = 4;  // longest segment = samples per trip of the owner kernel (divides 64: a wave boundary is a cut)
-
 constexpr int SEG_NSUB = 16;  // sub-ranges of an object's samples, one workgroup of scatter_segments_kernel each
 
 #pragma clang fp contract(off)
@@ -976,36 +944,20 @@ scatter_segments_kernel(const EvalParams q, float2 *__restrict__ coords, int *__
     const size_t row0 = (size_t)view * q.P + (size_t)obj * pts;
     int *list = segs + (size_t)blockIdx.x * sub_len;
     const float *pose = q.poses + (size_t)img * 12;
-    const float *fo = q.focal + (q.n_focal > 1 ? obj * 2 : 0);
-    const float *cc = q.c + (q.n_c > 1 ? obj * 2 : 0);
-    const float Wl = (float)q.Wl, Hl = (float)q.Hl;
-    const float lsx = Wl / (Wl - 1.f) * 2.f, lsy = Hl / (Hl - 1.f) * 2.f;
     if (t == 0) carry = 0;
     __syncthreads();
     for (int base = s_begin; base < s_end; base += SEG_NT) {
         const int s = base + t;
         int cell = -1;
         if (s < s_end) {
-            const int g = obj * pts + s;
-            const int r = g / q.K;
-            const float *ray = q.rays + (size_t)r * 8;
-            const float zz = q.z[g];
-            const float X = ray[0] + zz * ray[3], Y = ray[1] + zz * ray[4], Z = ray[2] + zz * ray[5];
-            // project_point's op order (pnr_device.h)
-            const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
-            const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
-            const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
-            const float xc0 = xr0 + pose[3], xc1 = xr1 + pose[7], xc2 = xr2 + pose[11];
-            float u = -xc0 / xc2; u = u * fo[0]; u = u + cc[0];
-            float v = -xc1 / xc2; v = v * fo[1]; v = v + cc[1];
-            const float gx = u * (lsx / q.img_w) - 1.f, gy = v * (lsy / q.img_h) - 1.f;
-            float ix = ((gx + 1.f) / 2.f) * (Wl - 1.f), iy = ((gy + 1.f) / 2.f) * (Hl - 1.f);
-            ix = fminf(Wl - 1.f, fmaxf(ix, 0.f));
-            iy = fminf(Hl - 1.f, fmaxf(iy, 0.f));
-            if (!(ix == ix)) ix = 0.f;  // NaN (point on the camera plane): as project_point
-            if (!(iy == iy)) iy = 0.f;
-            coords[row0 + s] = make_float2(ix, iy);
-            cell = (int)floorf(iy) * q.Wl + (int)floorf(ix);
+            // the pose is the workgroup's (uniform), the rest is the forward's chain (pnr_geom.h)
+            const RayPoint rp = ray_point(q, obj * pts + s);
+            const float3 xr = rotate_point(pose, rp.X, rp.Y, rp.Z);
+            float2 p = grid_coords(q, pose, obj, xr.x, xr.y, xr.z);
+            if (!(p.x == p.x)) p.x = 0.f;  // NaN (point on the camera plane): as project_point
+            if (!(p.y == p.y)) p.y = 0.f;
+            coords[row0 + s] = p;
+            cell = (int)floorf(p.y) * q.Wl + (int)floorf(p.x);
         }
         // segment start: first sample of a ray, a cell that differs from the previous sample's, or every SEG_B-th sample (a
         // segment is ONE trip of the owner kernel's loads: a ray that leaves the image clamps to one border cell for dozens of
@@ -1041,12 +993,8 @@ latent_scatter_owner_kernel(const EvalParams q, const float *__restrict__ d_zlat
     constexpr int GRP = 32 / CS;       // slices that share a 128-byte line of a d_zlat / d_latent row
     const int t = threadIdx.x;
     const int texels = q.Hl * q.Wl, nslices = C_LAT / CS;
-    // XCD-aware placement (as in dw_kernel): the slices that share 128-byte lines form a group that lands on ONE XCD
-    // (consecutive per-XCD slots), so a line is fetched into one L2 once
-    const int lid = blockIdx.x, ngroups = gridDim.x / GRP, full = (ngroups >> 3) * (8 * GRP);
     int grp, sub;
-    if (lid < full) { const int k = lid >> 3; grp = (k / GRP) * 8 + (lid & 7); sub = k % GRP; }
-    else { const int rem = lid - full; grp = full / GRP + rem / GRP; sub = rem % GRP; }
+    xcd_group_slot(blockIdx.x, gridDim.x / GRP, GRP, grp, sub);
     const int cs = (grp % (nslices / GRP)) * GRP + sub;
     const int pslice = (grp / (nslices / GRP)) % psplit;
     const int img = grp / ((nslices / GRP) * psplit);  // img = obj * NS + view
@@ -1114,29 +1062,9 @@ latent_scatter_owner_kernel(const EvalParams q, const float *__restrict__ d_zlat
         float2 posn[SEG_B];
         f32x4 vn[SEG_B];
         if (i + STRIDE < i_end) load_batch(s0n, s1n, posn, vn);
-        const float ix0 = floorf(pos[0].x), iy0 = floorf(pos[0].y);  // the segment's cell
-        const float ix1 = ix0 + 1.f, iy1 = iy0 + 1.f;
-        const int x0 = (int)ix0, y0 = (int)iy0;
-        const bool x_in = x0 + 1 <= Wl - 1, y_in = y0 + 1 <= Hl - 1;  // out-of-range corner has weight 0 (project_point)
         f32x4 acc[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto accumulate = [&](const float2 (&ps)[SEG_B], const f32x4 (&vs)[SEG_B]) {
-#pragma unroll
-            for (int b = 0; b < SEG_B; ++b) {
-                // corner weights of project_point from (ix, iy); slots beyond the segment carry zero gradients
-                const float2 p = ps[b];
-                float w[4] = {(ix1 - p.x) * (iy1 - p.y), (p.x - ix0) * (iy1 - p.y), (ix1 - p.x) * (p.y - iy0), (p.x - ix0) * (p.y - iy0)};
-                if (!x_in) { w[1] = 0.f; w[3] = 0.f; }
-                if (!y_in) { w[2] = 0.f; w[3] = 0.f; }
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] += w[c] * vs[b][e];
-            }
-        };
-        accumulate(pos, v);  // s1 - s0 <= SEG_B: scatter_segments_kernel cuts there
-        const int x1 = min(x0 + 1, Wl - 1), y1 = min(y0 + 1, Hl - 1);
+        const Corners k = segment_corner_sums(pos, v, Wl, Hl, acc);  // s1 - s0 <= SEG_B: scatter_segments_kernel cuts there
+        const int x0 = k.x0, y0 = k.y0, x1 = k.x1(), y1 = k.y1();
         const int tex[4] = {y0 * Wl + x0, y0 * Wl + x1, y1 * Wl + x0, y1 * Wl + x1};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -1263,11 +1191,8 @@ latent_scatter_tiled_kernel(const EvalParams q, const float *__restrict__ d_zlat
     extern __shared__ double dslab[];  // [32 x 32 texels][TILE_ROW]
     constexpr int LPS = TILE_CS / 4, NSL = C_LAT / TILE_CS, GRP = 32 / TILE_CS;
     const int t = threadIdx.x;
-    // XCD-aware placement as in the slab kernel: the slices that share 128-byte lines get consecutive slots of ONE XCD
-    const int lid = blockIdx.x, ngroups = gridDim.x / GRP, full = (ngroups >> 3) * (8 * GRP);
     int grp, sub;
-    if (lid < full) { const int k = lid >> 3; grp = (k / GRP) * 8 + (lid & 7); sub = k % GRP; }
-    else { const int rem = lid - full; grp = full / GRP + rem / GRP; sub = rem % GRP; }
+    xcd_group_slot(blockIdx.x, gridDim.x / GRP, GRP, grp, sub);
     const int cs = (grp % (NSL / GRP)) * GRP + sub;
     const int it = grp / (NSL / GRP);  // (image, tile)
     const int img = it / tg.ntiles, tile = it % tg.ntiles;
@@ -1297,25 +1222,9 @@ latent_scatter_tiled_kernel(const EvalParams q, const float *__restrict__ d_zlat
                 v[b] = reinterpret_cast<const f32x4 *>(grad + (size_t)(s0 + b) * C_LAT)[part];
             }
         }
-        const float ix0 = floorf(pos[0].x), iy0 = floorf(pos[0].y);  // the segment's cell
-        const float ix1 = ix0 + 1.f, iy1 = iy0 + 1.f;
-        const int x0 = (int)ix0, y0 = (int)iy0;
-        const bool x_in = x0 + 1 <= Wl - 1, y_in = y0 + 1 <= Hl - 1;  // out-of-range corner has weight 0 (project_point)
         f32x4 acc[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int b = 0; b < SEG_B; ++b) {
-            const float2 p = pos[b];  // slots beyond the segment carry zero gradients
-            float w[4] = {(ix1 - p.x) * (iy1 - p.y), (p.x - ix0) * (iy1 - p.y), (ix1 - p.x) * (p.y - iy0), (p.x - ix0) * (p.y - iy0)};
-            if (!x_in) { w[1] = 0.f; w[3] = 0.f; }
-            if (!y_in) { w[2] = 0.f; w[3] = 0.f; }
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[c][e] += w[c] * v[b][e];
-        }
-        const int x1 = min(x0 + 1, Wl - 1), y1 = min(y0 + 1, Hl - 1);
+        const Corners k = segment_corner_sums(pos, v, Wl, Hl, acc);
+        const int x0 = k.x0, y0 = k.y0, x1 = k.x1(), y1 = k.y1();
         const int cx[4] = {x0, x1, x0, x1}, cy[4] = {y0, y0, y1, y1};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -1390,89 +1299,22 @@ position_bwd_kernel(const EvalParams q, const float *__restrict__ d_in42, const 
         g = (int)(widx % q.P);
     }
     const long long idx = (long long)view * q.P + g;
-    const int r = g / q.K;
-    const float *ray = q.rays + (size_t)r * 8;
-    const float zz = q.z[g];
-    const float X = ray[0] + zz * ray[3], Y = ray[1] + zz * ray[4], Z = ray[2] + zz * ray[5];
-    const int obj = r / q.per_obj;
-    const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;
-    const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
-    const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
-    const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
-    const float xc0 = xr0 + pose[3], xc1 = xr1 + pose[7], xc2 = xr2 + pose[11];
-    const float *fo = q.focal + (q.n_focal > 1 ? obj * 2 : 0);
-    const float *cc = q.c + (q.n_c > 1 ? obj * 2 : 0);
-    const float u = -xc0 / xc2 * fo[0] + cc[0], v = -xc1 / xc2 * fo[1] + cc[1];
-    const float Wl = (float)q.Wl, Hl = (float)q.Hl;
-    const float sx = Wl / (Wl - 1.f) * 2.f / q.img_w, sy = Hl / (Hl - 1.f) * 2.f / q.img_h;
-    float ix = ((u * sx - 1.f + 1.f) / 2.f) * (Wl - 1.f), iy = ((v * sy - 1.f + 1.f) / 2.f) * (Hl - 1.f);
-    // grid_sample border padding: clip_coordinates_set_grad -> gradient 0 outside (0, size-1)
-    const bool gx_on = ix > 0.f && ix < Wl - 1.f, gy_on = iy > 0.f && iy < Hl - 1.f;
-    ix = fminf(Wl - 1.f, fmaxf(ix, 0.f));
-    iy = fminf(Hl - 1.f, fmaxf(iy, 0.f));
-    float six = 0.f, siy = 0.f;
-    if ((gx_on || gy_on) && ix == ix && iy == iy) {
-        const float ix0 = floorf(ix), iy0 = floorf(iy);
-        const int x0 = (int)ix0, y0 = (int)iy0;
-        const int x1 = min(x0 + 1, q.Wl - 1), y1 = min(y0 + 1, q.Hl - 1);
-        const float ax = ix - ix0, ay = iy - iy0;  // fractional parts
-        const size_t rowbase = (size_t)(obj * q.NS + view) * (size_t)(q.Hl * q.Wl);
-        const float *nw = q.latent + (rowbase + (size_t)y0 * q.Wl + x0) * C_LAT + lane * 8;
-        const float *ne = q.latent + (rowbase + (size_t)y0 * q.Wl + x1) * C_LAT + lane * 8;
-        const float *sw = q.latent + (rowbase + (size_t)y1 * q.Wl + x0) * C_LAT + lane * 8;
-        const float *se = q.latent + (rowbase + (size_t)y1 * q.Wl + x1) * C_LAT + lane * 8;
-        const float *dz = d_zlat + (size_t)idx * C_LAT + lane * 8;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {  // 16-byte loads: 10 in flight per lane
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(nw + 4 * hh), b = *reinterpret_cast<const f32x4 *>(ne + 4 * hh);
-            const f32x4 c = *reinterpret_cast<const f32x4 *>(sw + 4 * hh), d = *reinterpret_cast<const f32x4 *>(se + 4 * hh);
-            const f32x4 gq = *reinterpret_cast<const f32x4 *>(dz + 4 * hh);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                six += gq[e] * ((1.f - ay) * (b[e] - a[e]) + ay * (d[e] - c[e]));   // d zlat / d ix
-                siy += gq[e] * ((1.f - ax) * (c[e] - a[e]) + ax * (d[e] - b[e]));   // d zlat / d iy
-            }
-        }
-    }
-    // positional code: [x, sin(f_k x), sin(f_k x + pi/2)] , f_k = 1.5 * 2^k  (code.py:37-41).  Lane l < 18 differentiates
-    // band k = l / 3 of coordinate c = l % 3; lanes 18..20 carry the identity part; summed per coordinate below
-    float gc0 = 0.f, gc1 = 0.f, gc2 = 0.f;
-    {
-        const float *gi = d_in42 + (size_t)idx * D_IN;
-        const float HALF_PI = 1.57079637050628662109375f;
-        if (lane < 21) {
-            const int k = lane / 3, c = lane - 3 * k;
-            const float xc = c == 0 ? xr0 : (c == 1 ? xr1 : xr2);
-            float term;
-            if (k < 6) {
-                const float f = 1.5f * (float)(1 << k), a = xc * f;
-                term = f * (cosf(a) * gi[3 + 6 * k + c] + cosf(__builtin_fmaf(xc, f, HALF_PI)) * gi[3 + 6 * k + 3 + c]);
-            } else {
-                term = gi[c];
-            }
-            gc0 = c == 0 ? term : 0.f; gc1 = c == 1 ? term : 0.f; gc2 = c == 2 ? term : 0.f;
-        }
-    }
-    gc0 = wsum(gc0); gc1 = wsum(gc1); gc2 = wsum(gc2);
-    six = wsum(six);
-    siy = wsum(siy);
+    const SamplePoint sp = sample_point_fused(q, g, view);
+    const PointGrad pg = point_grad(q, sp, view, idx, d_in42, d_zlat, lane);
     if (lane == 0) {
-        const float du = gx_on ? six * (Wl - 1.f) * 0.5f * sx : 0.f;
-        const float dv = gy_on ? siy * (Hl - 1.f) * 0.5f * sy : 0.f;
-        // u = -xc0/xc2 fx + cx ; v = -xc1/xc2 fy + cy   (fy already negated in `focal`)
-        float g0 = -fo[0] / xc2 * du;
-        float g1 = -fo[1] / xc2 * dv;
-        float g2 = (xc0 * fo[0] * du + xc1 * fo[1] * dv) / (xc2 * xc2);
-        g0 += gc0; g1 += gc1; g2 += gc2;
+        const float g0 = pg.g0, g1 = pg.g1, g2 = pg.g2;
+        const float *pose = sp.pose;
         // x_world gradient = R^T g ; dz = ray_dir . that
         const float wx = pose[0] * g0 + pose[4] * g1 + pose[8] * g2;
         const float wy = pose[1] * g0 + pose[5] * g1 + pose[9] * g2;
         const float wz = pose[2] * g0 + pose[6] * g1 + pose[10] * g2;
-        float val = ray[3] * wx + ray[4] * wy + ray[5] * wz;
+        float val = sp.dx * wx + sp.dy * wy + sp.dz * wz;
         if (!ds.ranks) {
             if (val == val) atomicAdd(d_z + g, val);
         } else {
             if (view == 0 && ds.dz_comp) val += ds.dz_comp[g];
+            const int r = sp.r;
+            const float *ray = q.rays + (size_t)r * 8;
             const float zraw = ds.depth_c[r] + ds.n4[(size_t)r * ds.Kfd + jd] * ds.depth_std;
             const bool live = zraw < ray[7] && zraw > ray[6];  // inside the clamp: gradient passes (nerf.py:157-160)
             ds.contrib[widx] = (live && val == val) ? val : 0.f;

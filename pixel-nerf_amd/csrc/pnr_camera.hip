@@ -1,8 +1,9 @@
 // pnr_camera.hip -- gradients with respect to the rays and the cameras (training / pose refinement), gfx950.
 //
 //   camera_record_kernel  one wavefront per (view, sample): the world-space gradient of the sample point through the
-//                         positional code, the projection and the bilinear lookup (the same math as position_bwd_kernel),
-//                         kept whole instead of collapsed to dL/dz -- a ray record (8 floats) and a camera record (16).
+//                         positional code, the projection and the bilinear lookup (point_grad in pnr_geom.h, which
+//                         position_bwd_kernel calls too), kept whole instead of collapsed to dL/dz -- a ray record
+//                         (8 floats) and a camera record (16).
 //   ray_reduce_kernel     thread per ray: the ray records summed over (sample, view) in a fixed order, dL/dz pushed through
 //                         the sampling maps to near / far (nerf.py:98-161), the last compositing delta added to far.
 //   cam_partial_kernel    per source view: the camera records of that view's object summed in fixed chunks (no atomics),
@@ -26,12 +27,6 @@ constexpr int RAY_REC = 8;         // ray record: gp (3), z gp + R^T g_vd (3), d
 constexpr int CAM_CHUNK = 2048;    // samples per partial sum of cam_partial_kernel
 constexpr int CAM_NT = 256;
 
-__device__ __forceinline__ float cam_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 #pragma clang fp contract(fast)
 __global__ void __launch_bounds__(CAM_CW * 64)
 camera_record_kernel(const EvalParams q, const float *__restrict__ d_in42, const float *__restrict__ d_zlat,
@@ -41,81 +36,15 @@ camera_record_kernel(const EvalParams q, const float *__restrict__ d_in42, const
     if (idx >= q.P * q.NS) return;
     const int view = (int)(idx / q.P);
     const int g = (int)(idx - (long long)view * q.P);
-    const int r = g / q.K;
-    const float *ray = q.rays + (size_t)r * 8;
-    const float zz = q.z[g];
-    const float X = ray[0] + zz * ray[3], Y = ray[1] + zz * ray[4], Z = ray[2] + zz * ray[5];
-    const int obj = r / q.per_obj;
-    const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;
-    const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
-    const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
-    const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
-    const float xc0 = xr0 + pose[3], xc1 = xr1 + pose[7], xc2 = xr2 + pose[11];
-    const float *fo = q.focal + (q.n_focal > 1 ? obj * 2 : 0);
-    const float *cc = q.c + (q.n_c > 1 ? obj * 2 : 0);
-    const float u = -xc0 / xc2 * fo[0] + cc[0], v = -xc1 / xc2 * fo[1] + cc[1];
-    const float Wl = (float)q.Wl, Hl = (float)q.Hl;
-    const float sx = Wl / (Wl - 1.f) * 2.f / q.img_w, sy = Hl / (Hl - 1.f) * 2.f / q.img_h;
-    float ix = ((u * sx - 1.f + 1.f) / 2.f) * (Wl - 1.f), iy = ((v * sy - 1.f + 1.f) / 2.f) * (Hl - 1.f);
-    // grid_sample border padding: clip_coordinates_set_grad -> gradient 0 outside (0, size-1)
-    const bool gx_on = ix > 0.f && ix < Wl - 1.f, gy_on = iy > 0.f && iy < Hl - 1.f;
-    ix = fminf(Wl - 1.f, fmaxf(ix, 0.f));
-    iy = fminf(Hl - 1.f, fmaxf(iy, 0.f));
-    float six = 0.f, siy = 0.f;
-    if ((gx_on || gy_on) && ix == ix && iy == iy) {
-        const float ix0 = floorf(ix), iy0 = floorf(iy);
-        const int x0 = (int)ix0, y0 = (int)iy0;
-        const int x1 = min(x0 + 1, q.Wl - 1), y1 = min(y0 + 1, q.Hl - 1);
-        const float ax = ix - ix0, ay = iy - iy0;
-        const size_t rowbase = (size_t)(obj * q.NS + view) * (size_t)(q.Hl * q.Wl);
-        const float *nw = q.latent + (rowbase + (size_t)y0 * q.Wl + x0) * C_LAT + lane * 8;
-        const float *ne = q.latent + (rowbase + (size_t)y0 * q.Wl + x1) * C_LAT + lane * 8;
-        const float *sw = q.latent + (rowbase + (size_t)y1 * q.Wl + x0) * C_LAT + lane * 8;
-        const float *se = q.latent + (rowbase + (size_t)y1 * q.Wl + x1) * C_LAT + lane * 8;
-        const float *dz = d_zlat + (size_t)idx * C_LAT + lane * 8;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(nw + 4 * hh), b = *reinterpret_cast<const f32x4 *>(ne + 4 * hh);
-            const f32x4 c = *reinterpret_cast<const f32x4 *>(sw + 4 * hh), d = *reinterpret_cast<const f32x4 *>(se + 4 * hh);
-            const f32x4 gq = *reinterpret_cast<const f32x4 *>(dz + 4 * hh);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                six += gq[e] * ((1.f - ay) * (b[e] - a[e]) + ay * (d[e] - c[e]));
-                siy += gq[e] * ((1.f - ax) * (c[e] - a[e]) + ax * (d[e] - b[e]));
-            }
-        }
-    }
-    // positional code of xr (code.py:37-41): lane l < 18 differentiates band l / 3 of coordinate l % 3, lanes 18..20 the
-    // identity part
-    const float *gi = d_in42 + (size_t)idx * D_IN;
-    float gc0 = 0.f, gc1 = 0.f, gc2 = 0.f;
-    if (lane < 21) {
-        const float HALF_PI = 1.57079637050628662109375f;
-        const int k = lane / 3, c = lane - 3 * k;
-        const float xc = c == 0 ? xr0 : (c == 1 ? xr1 : xr2);
-        float term;
-        if (k < 6) {
-            const float f = 1.5f * (float)(1 << k), a = xc * f;
-            term = f * (cosf(a) * gi[3 + 6 * k + c] + cosf(__builtin_fmaf(xc, f, HALF_PI)) * gi[3 + 6 * k + 3 + c]);
-        } else {
-            term = gi[c];
-        }
-        gc0 = c == 0 ? term : 0.f; gc1 = c == 1 ? term : 0.f; gc2 = c == 2 ? term : 0.f;
-    }
-    gc0 = cam_wsum(gc0); gc1 = cam_wsum(gc1); gc2 = cam_wsum(gc2);
-    six = cam_wsum(six);
-    siy = cam_wsum(siy);
+    const SamplePoint sp = sample_point_fused(q, g, view);
+    const PointGrad pg = point_grad(q, sp, view, idx, d_in42, d_zlat, lane);
     if (lane != 0) return;
-    const float du = gx_on ? six * (Wl - 1.f) * 0.5f * sx : 0.f;
-    const float dv = gy_on ? siy * (Hl - 1.f) * 0.5f * sy : 0.f;
-    // u = -xc0/xc2 fx + cx ; v = -xc1/xc2 fy + cy   (fy already negated in `focal`): g_cam = d/d xc
-    const float gm0 = -fo[0] / xc2 * du;
-    const float gm1 = -fo[1] / xc2 * dv;
-    const float gm2 = (xc0 * fo[0] * du + xc1 * fo[1] * dv) / (xc2 * xc2);
-    const float g0 = gm0 + gc0, g1 = gm1 + gc1, g2 = gm2 + gc2;  // d/d xr (xc = xr + t)
+    const float *pose = sp.pose, *gi = d_in42 + (size_t)idx * D_IN;
+    const float X = sp.X, Y = sp.Y, Z = sp.Z, zz = sp.zz, xc0 = pg.xc0, xc1 = pg.xc1, xc2 = pg.xc2;
+    const float du = pg.du, dv = pg.dv, gm0 = pg.gm0, gm1 = pg.gm1, gm2 = pg.gm2, g0 = pg.g0, g1 = pg.g1, g2 = pg.g2;
     // view direction R d (models.py:188-196) enters the network as columns 39..41
     const float v0 = gi[39], v1 = gi[40], v2 = gi[41];
-    const float d0 = ray[3], d1 = ray[4], d2 = ray[5];
+    const float d0 = sp.dx, d1 = sp.dy, d2 = sp.dz;
     // world gradient gp = R^T g ; direction: z gp + R^T g_vd
     const float wx = pose[0] * g0 + pose[4] * g1 + pose[8] * g2;
     const float wy = pose[1] * g0 + pose[5] * g1 + pose[9] * g2;

@@ -370,11 +370,16 @@ __device__ __forceinline__ void add_bias(f32x16 (&acc)[IT][JT_], const float *bi
 }
 
 
+}  // namespace pnr
+
+#include "pnr_geom.h"  // sample geometry (needs EvalParams): rotate_point, grid_coords, bilinear_corners, ...
+
+namespace pnr {
+
 // ---------------------------------------------------------------- projection + bilinear setup
-// Camera-space point and pinhole projection (models.py:165,206-212), SpatialEncoder.index
-// scaling (encoder.py:96-99,161-163) and grid_sample(bilinear, border, align_corners=True)
-// corner offsets / weights, in the reference's fp32 op order (no FMA contraction).
-// xr = R x (rotated point); off[] are element offsets into the NHWC grid.
+// grid_coords + bilinear_corners (pnr_geom.h) as the fused kernels consume them: element offsets into the NHWC grid and
+// weights of the four corners.  xr = R x (rotated point).  A NaN coordinate (point on the camera plane) and an invalid point
+// (padding of the last tile) read texel 0, the latter with weight 0.
 struct Proj {
     uint32_t off[4];  // nw, ne, sw, se
     float w[4];
@@ -382,40 +387,26 @@ struct Proj {
 #pragma clang fp contract(off)
 __device__ __forceinline__ Proj project_point(const EvalParams &q, const float *pose, int obj, int view, float xr0,
                                               float xr1, float xr2, bool valid) {
-    const float xc0 = xr0 + pose[3], xc1 = xr1 + pose[7], xc2 = xr2 + pose[11];
-    const float *fo = q.focal + (q.n_focal > 1 ? obj * 2 : 0);
-    const float *cc = q.c + (q.n_c > 1 ? obj * 2 : 0);
-    float u = -xc0 / xc2; u = u * fo[0]; u = u + cc[0];
-    float v = -xc1 / xc2; v = v * fo[1]; v = v + cc[1];
-    const float Wl = (float)q.Wl, Hl = (float)q.Hl;
-    const float lsx = Wl / (Wl - 1.f) * 2.f, lsy = Hl / (Hl - 1.f) * 2.f;
-    const float gx = u * (lsx / q.img_w) - 1.f, gy = v * (lsy / q.img_h) - 1.f;
-    float ix = ((gx + 1.f) / 2.f) * (Wl - 1.f), iy = ((gy + 1.f) / 2.f) * (Hl - 1.f);
-    ix = fminf(Wl - 1.f, fmaxf(ix, 0.f));
-    iy = fminf(Hl - 1.f, fmaxf(iy, 0.f));
-    if (!(ix == ix) || !valid) ix = 0.f;  // NaN (point on the camera plane): keep reads in bounds
-    if (!(iy == iy) || !valid) iy = 0.f;
-    const float ix0 = floorf(ix), iy0 = floorf(iy);
-    const float ix1 = ix0 + 1.f, iy1 = iy0 + 1.f;
-    float w_nw = (ix1 - ix) * (iy1 - iy), w_ne = (ix - ix0) * (iy1 - iy);
-    float w_sw = (ix1 - ix) * (iy - iy0), w_se = (ix - ix0) * (iy - iy0);
-    const int x0 = (int)ix0, y0 = (int)iy0;
-    const int x1 = min(x0 + 1, q.Wl - 1), y1 = min(y0 + 1, q.Hl - 1);  // out-of-range corner has weight 0
-    if (x0 + 1 > q.Wl - 1) { w_ne = 0.f; w_se = 0.f; }
-    if (y0 + 1 > q.Hl - 1) { w_sw = 0.f; w_se = 0.f; }
-    if (!valid) { w_nw = w_ne = w_sw = w_se = 0.f; }
-    const uint32_t rowbase = (uint32_t)(obj * q.NS + view) * (uint32_t)(q.Hl * q.Wl);
+    const float2 p = grid_coords(q, pose, obj, xr0, xr1, xr2);
+    // NaN, padding: texel 0 keeps the reads in bounds
+    const float ix = pick((p.x == p.x) & valid, p.x, 0.f), iy = pick((p.y == p.y) & valid, p.y, 0.f);
+    const Corners k = bilinear_corners(ix, iy, q.Wl, q.Hl);
     Proj pr;
+    float w_nw = k.w[0], w_ne = k.w[1], w_sw = k.w[2], w_se = k.w[3];
+    if (!valid) { w_nw = w_ne = w_sw = w_se = 0.f; }
+    pr.w[0] = w_nw; pr.w[1] = w_ne; pr.w[2] = w_sw; pr.w[3] = w_se;
+    const int x0 = k.x0, y0 = k.y0, y1 = k.y1(), x1 = k.x1();
+    const uint32_t rowbase = (uint32_t)(obj * q.NS + view) * (uint32_t)(q.Hl * q.Wl);
     pr.off[0] = (rowbase + y0 * q.Wl + x0) * C_LAT; pr.off[1] = (rowbase + y0 * q.Wl + x1) * C_LAT;
     pr.off[2] = (rowbase + y1 * q.Wl + x0) * C_LAT; pr.off[3] = (rowbase + y1 * q.Wl + x1) * C_LAT;
-    pr.w[0] = w_nw; pr.w[1] = w_ne; pr.w[2] = w_sw; pr.w[3] = w_se;
     return pr;
 }
 #pragma clang fp contract(fast)
 
 // ---------------------------------------------------------------- feature phase (geometry)
-// Thread (p = tid&63, sub = tid>>6).  Follows the reference op order without FMA contraction
-// so that fp32 intermediates round like the PyTorch eager path.
+// Thread (p = tid&63, sub = tid>>6).  The reference's op order without FMA contraction (pnr_geom.h).  It loads the point itself
+// -- explicit rays, rays regenerated from the camera, or xyz + view directions, zero-filled beyond the last point -- and takes
+// the rotation and the projection from the shared helpers.
 #pragma clang fp contract(off)
 template <typename P, bool RAYS, typename TL>
 __device__ __forceinline__ void geometry_item(const EvalParams &q, char *smem, int tile, int view, int p, int sub) {
@@ -446,10 +437,8 @@ __device__ __forceinline__ void geometry_item(const EvalParams &q, char *smem, i
         }
     }
     const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;  // row = obj*NS + view
-    // xyz_rot = R x (models.py:162-164)
-    const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
-    const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
-    const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
+    const float3 xr = rotate_point(pose, X, Y, Z);  // xyz_rot = R x (models.py:162-164)
+    const float xr0 = xr.x, xr1 = xr.y, xr2 = xr.z;
     T *in_row = reinterpret_cast<T *>(smem + LDS_IN + p * ROW_IN);
     // split-operand form (pnr_split.hip): value = hi + lo, two 16-bit images IN_LO_DELTA bytes apart
     auto put = [&](int i, float v) {
@@ -469,11 +458,9 @@ __device__ __forceinline__ void geometry_item(const EvalParams &q, char *smem, i
     };
     if (sub == 0) {
         // identity part of the code, rotated view direction (models.py:188-196), zero pad
-        const float dv0 = pose[0] * dx + pose[1] * dy + pose[2] * dz;
-        const float dv1 = pose[4] * dx + pose[5] * dy + pose[6] * dz;
-        const float dv2 = pose[8] * dx + pose[9] * dy + pose[10] * dz;
+        const float3 dv = rotate_point(pose, dx, dy, dz);
         put2(0, valid ? xr0 : 0.f, valid ? xr1 : 0.f); put(2, valid ? xr2 : 0.f);
-        put(39, dv0); put2(40, dv1, dv2);
+        put(39, dv.x); put2(40, dv.y, dv.z);
         // camera-space point, pinhole projection, bilinear corner setup
         const Proj pr = project_point(q, pose, obj, view, xr0, xr1, xr2, valid);
         uint32_t *mo = reinterpret_cast<uint32_t *>(smem + LDS_META + p * 32);

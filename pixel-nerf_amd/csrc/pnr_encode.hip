@@ -22,6 +22,7 @@
 #include <cstdio>
 
 #include "pnr_common.h"
+#include "pnr_device.h"  // bilinear_corners, wave_sum (pnr_geom.h)
 
 namespace pnr {
 
@@ -555,7 +556,7 @@ __global__ void sample_training_rays_kernel(const float *__restrict__ poses, con
 // corner = one contiguous row); a workgroup owns 64 points of one view: per 64-channel chunk every wave blends the four
 // corner rows of its 16 points with lanes along the channels (256-byte coalesced reads) into an LDS tile, which then leaves
 // with lanes along the points (256-byte runs of one channel's output row) -- the reference's (NV,C,N) layout without a
-// strided store.  Corner arithmetic in ATen's op order (no FMA contraction); a NaN coordinate reads texel 0 like
+// strided store.  Corner arithmetic in ATen's op order (bilinear_corners, pnr_geom.h); a NaN coordinate reads texel 0 like
 // project_point (pnr_device.h) and the fused kernels do.
 struct IndexCorner {
     int off[4];   // texel index (y * Wl + x) of nw, ne, sw, se
@@ -574,14 +575,10 @@ __device__ __forceinline__ IndexCorner index_corner(float gx, float gy, int Wl_,
     iy = fminf(Hl - 1.f, fmaxf(iy, 0.f));
     if (!(ix == ix)) { ix = 0.f; c.x_on = 0; }
     if (!(iy == iy)) { iy = 0.f; c.y_on = 0; }
-    const float ix0 = floorf(ix), iy0 = floorf(iy);
-    const float ix1 = ix0 + 1.f, iy1 = iy0 + 1.f;
-    c.w[0] = (ix1 - ix) * (iy1 - iy); c.w[1] = (ix - ix0) * (iy1 - iy);
-    c.w[2] = (ix1 - ix) * (iy - iy0); c.w[3] = (ix - ix0) * (iy - iy0);
-    const int x0 = (int)ix0, y0 = (int)iy0;
-    const int x1 = min(x0 + 1, Wl_ - 1), y1 = min(y0 + 1, Hl_ - 1);  // an out-of-range corner carries weight 0
-    if (x0 + 1 > Wl_ - 1) { c.w[1] = 0.f; c.w[3] = 0.f; }
-    if (y0 + 1 > Hl_ - 1) { c.w[2] = 0.f; c.w[3] = 0.f; }
+    const Corners k = bilinear_corners(ix, iy, Wl_, Hl_);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c.w[i] = k.w[i];
+    const int x0 = k.x0, y0 = k.y0, x1 = k.x1(), y1 = k.y1();
     c.off[0] = y0 * Wl_ + x0; c.off[1] = y0 * Wl_ + x1; c.off[2] = y1 * Wl_ + x0; c.off[3] = y1 * Wl_ + x1;
     c.ix = ix; c.iy = iy;
     return c;
@@ -687,9 +684,7 @@ grid_index_bwd_kernel(const float *__restrict__ grid, int Hl, int Wl, int C, con
     if (d_uv) {
 #pragma unroll
         for (int i = 0; i < GI_P / 4; ++i) {
-            float sx = ax[i], sy = ay[i];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o, 64); sy += __shfl_xor(sy, o, 64); }
+            const float sx = wave_sum(ax[i]), sy = wave_sum(ay[i]);
             const int p = wv * (GI_P / 4) + i;
             if (lane == 0 && n0 + p < N) {
                 const IndexCorner &k = corner[p];

@@ -47,20 +47,17 @@ feat_f32_kernel(const EvalParams q, long long p0, int np, float *__restrict__ in
     float X, Y, Z, dx, dy, dz;
     int obj;
     if (RAYS) {
-        const int r = g / q.K;
-        const float *ray = q.rays + (size_t)r * 8;
-        const float zz = q.z[g];
-        dx = ray[3]; dy = ray[4]; dz = ray[5];
-        X = ray[0] + zz * dx; Y = ray[1] + zz * dy; Z = ray[2] + zz * dz;
-        obj = r / q.per_obj;
+        const RayPoint rp = ray_point(q, g);
+        X = rp.X; Y = rp.Y; Z = rp.Z; dx = rp.dx; dy = rp.dy; dz = rp.dz;
+        obj = rp.r / q.per_obj;
     } else {
         X = q.xyz[(size_t)g * 3 + 0]; Y = q.xyz[(size_t)g * 3 + 1]; Z = q.xyz[(size_t)g * 3 + 2];
         dx = q.viewdirs[(size_t)g * 3 + 0]; dy = q.viewdirs[(size_t)g * 3 + 1]; dz = q.viewdirs[(size_t)g * 3 + 2];
         obj = g / q.per_obj;
     }
     const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;
-    const float xr[3] = {pose[0] * X + pose[1] * Y + pose[2] * Z, pose[4] * X + pose[5] * Y + pose[6] * Z,
-                         pose[8] * X + pose[9] * Y + pose[10] * Z};
+    const float3 xr3 = rotate_point(pose, X, Y, Z);
+    const float xr[3] = {xr3.x, xr3.y, xr3.z};
     // lin_in operand: [x(3), sin(f_k x)(3), sin(f_k x + pi/2)(3) ... , R d (3), 0-pad]
     float v = 0.f;
     if (lane < 3) {

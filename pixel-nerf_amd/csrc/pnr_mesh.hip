@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "pnr_common.h"
+#include "pnr_wave.h"
 
 namespace pnr {
 
@@ -58,15 +59,6 @@ static McWorkspace mc_carve(void *workspace, long long N) {
 __device__ __forceinline__ bool mc_finite(float f) { return fabsf(f) <= 3.402823466e+38f; }
 __device__ __forceinline__ bool mc_inside(float f, float iso) { return mc_finite(f) && f > iso; }
 
-__device__ __forceinline__ u64 wave_scan_u64(u64 v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // classification + the scan's first level: per grid point the owned edges that carry a vertex and the case of the cell whose
 // lowest corner it is; exclusive offsets within the block of MC_BLOCK points, the block's totals to bsum / bnf
 __global__ void __launch_bounds__(MC_THREADS)
@@ -109,10 +101,8 @@ mc_classify_kernel(const float *__restrict__ field, int nx, int ny, int nz, floa
         tsum += cnt[it];
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u64 incl = wave_scan_u64(tsum, lane);
-    unsigned nfw = nf;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nfw += __shfl_xor(nfw, o, 64);
+    const u64 incl = wave_scan_add(tsum, lane);
+    const unsigned nfw = wave_sum(nf);
     if (lane == 63) wave_tot[wv] = incl;
     if (lane == 0) wave_nf[wv] = nfw;
     __syncthreads();
@@ -145,9 +135,8 @@ mc_scan_blocks_kernel(McWorkspace ws, long long nb, int *__restrict__ counts) {
         const long long b = c0 + threadIdx.x;
         const u64 v = b < nb ? ws.bsum[b] : 0;
         u64 nf = b < nb ? (u64)ws.bnf[b] : 0;
-        const u64 incl = wave_scan_u64(v, lane);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o, 64);
+        const u64 incl = wave_scan_add(v, lane);
+        nf = wave_sum(nf);
         if (lane == 63) wave_tot[wv] = incl;
         if (lane == 0) wave_nf[wv] = nf;
         __syncthreads();

@@ -559,10 +559,10 @@ fold_split_big_kernel(const float *__restrict__ grid, const FoldJobs jobs, float
 // ---- which texels does a training pass read?  (pnr_fold_latent_f32_rows)
 // A training step re-folds lin_z every pass (the weights moved), and on a large grid most of that work is for texels no ray of the
 // pass comes near: 128 rays x 64 / 96 samples x 3 views of a DTU step touch 37-43 k of the 90 k texels (4 objects: ~150 of 360 k).
-// fold_mark_kernel projects every (view, point) with the forward kernels' own code -- geometry_item's rotation and project_point
-// (pnr_device.h), the same operations in the same order without contraction: the same bits, hence the same four corner rows -- and
-// raises a byte per corner texel; fold_rows_count_kernel / fold_rows_compact_kernel turn the bytes into the ascending list of
-// marked rows (4096 texels per workgroup; a workgroup sums the counts of the ones before it).
+// fold_mark_kernel projects every (view, point) with the forward kernels' own code -- sample_point (pnr_geom.h) and project_point
+// (pnr_device.h): the same bits, hence the same four corner rows -- and raises a byte per corner texel; fold_rows_count_kernel /
+// fold_rows_compact_kernel turn the bytes into the ascending list of marked rows (4096 texels per workgroup; a workgroup sums the
+// counts of the ones before it).
 constexpr int FM_NT = 256, FR_NT = 1024, FR_PER_WG = 4 * FR_NT;
 #pragma clang fp contract(off)
 __global__ void __launch_bounds__(FM_NT) fold_mark_kernel(const EvalParams q, unsigned char *__restrict__ flags) {
@@ -571,17 +571,8 @@ __global__ void __launch_bounds__(FM_NT) fold_mark_kernel(const EvalParams q, un
     if (idx < q.NS) flags[(size_t)idx * q.Hl * q.Wl] = 1;
     if (idx >= q.P * q.NS) return;
     const int view = (int)(idx / q.P), g = (int)(idx % q.P);
-    const int r = g / q.K;
-    const float *ray = q.rays + (size_t)r * 8;
-    const float ox = ray[0], oy = ray[1], oz = ray[2], dx = ray[3], dy = ray[4], dz = ray[5];
-    const float zz = q.z[g];
-    const float X = ox + zz * dx, Y = oy + zz * dy, Z = oz + zz * dz;
-    const int obj = r / q.per_obj;
-    const float *pose = q.poses + (size_t)(obj * q.NS + view) * 12;
-    const float xr0 = pose[0] * X + pose[1] * Y + pose[2] * Z;
-    const float xr1 = pose[4] * X + pose[5] * Y + pose[6] * Z;
-    const float xr2 = pose[8] * X + pose[9] * Y + pose[10] * Z;
-    const Proj pr = project_point(q, pose, obj, view, xr0, xr1, xr2, true);
+    const SamplePoint sp = sample_point(q, g, view);
+    const Proj pr = project_point(q, sp.pose, sp.obj, view, sp.xr0, sp.xr1, sp.xr2, true);
 #pragma unroll
     for (int c = 0; c < 4; ++c) flags[pr.off[c] / (uint32_t)C_LAT] = 1;
 }
@@ -592,9 +583,7 @@ __device__ __forceinline__ int popcount_bytes(uint32_t v) { return __popc(v & 0x
 __global__ void __launch_bounds__(FR_NT) fold_rows_count_kernel(const uint32_t *__restrict__ flags4, int *__restrict__ block_counts) {
     __shared__ int part[FR_NT / 64];
     const int t = threadIdx.x;
-    int c = popcount_bytes(flags4[(size_t)blockIdx.x * FR_NT + t]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    const int c = wave_sum(popcount_bytes(flags4[(size_t)blockIdx.x * FR_NT + t]));
     if ((t & 63) == 0) part[t >> 6] = c;
     __syncthreads();
     if (t == 0) {
@@ -612,8 +601,7 @@ __global__ void __launch_bounds__(FR_NT) fold_rows_compact_kernel(const uint32_t
     // rows marked in the workgroups before this one
     int before = 0;
     for (int i = t; i < b; i += FR_NT) before += block_counts[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+    before = wave_sum(before);
     if ((t & 63) == 0) part[t >> 6] = before;
     __syncthreads();
     if (t == 0) {
@@ -625,12 +613,7 @@ __global__ void __launch_bounds__(FR_NT) fold_rows_compact_kernel(const uint32_t
     __syncthreads();
     const uint32_t v = flags4[(size_t)b * FR_NT + t] & 0x01010101u;
     const int c = __popc(v);
-    int incl = c;  // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(incl, o, 64);
-        if ((t & 63) >= o) incl += up;
-    }
+    const int incl = wave_scan_add(c, t & 63);
     if ((t & 63) == 63) part[t >> 6] = incl;
     __syncthreads();
     int off = base_s + incl - c;
@@ -695,8 +678,7 @@ params_checksum_kernel(PnrMlpWeights p, unsigned long long *ws, unsigned long lo
         acc += (unsigned long long)x[u][0] * w + (unsigned long long)x[u][1] * (w + 2ull) + (unsigned long long)x[u][2] * (w + 4ull) +
                (unsigned long long)x[u][3] * (w + 6ull);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     __shared__ unsigned long long part[4];
     __shared__ bool last;
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
@@ -713,8 +695,7 @@ params_checksum_kernel(PnrMlpWeights p, unsigned long long *ws, unsigned long lo
         __threadfence();
         unsigned long long t = 0ull;
         for (int i = threadIdx.x; i < CK_BLOCKS; i += 256) t += ws[1 + i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        t = wave_sum(t);
         __syncthreads();
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
         __syncthreads();

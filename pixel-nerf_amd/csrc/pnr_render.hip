@@ -7,6 +7,7 @@
 #include "pnr_common.h"
 #include "pnr_internal.h"
 #include "pnr_raysrc.h"
+#include "pnr_wave.h"
 
 namespace pnr {
 
@@ -43,30 +44,6 @@ __global__ void sample_coarse_kernel(const RaySrc rs, const NoiseSrc ns, int R, 
     float t = linspace_at(1.f - step, Kc, i);
     t = t + noise_u1(ns, r, i, Kc) * step;
     z[idx] = z_from_t(near, far, t, lindisp);
-}
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// inclusive scans across the 64 lanes of a wavefront
-__device__ __forceinline__ double wave_scan_add(double v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_scan_mul(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v *= t;
-    }
-    return v;
 }
 
 // NeRFRenderer.sample_fine (nerf.py:120-148) + sample_fine_depth (:150-161) + cat/sort (:294-295)

@@ -189,3 +189,71 @@ def test_rowwise_fold_argument_validation():
         ops.fold_latent_rows(sc, state, rays, z, torch.zeros(3, 4, 72, 80, 256, device=dev))
     with pytest.raises(_lib.PixelNerfHipError):
         ops.fold_latent_rows(sc, state, rays[:-1], z[:-1], torch.zeros(3, 4, 72, 80, 512, device=dev))  # R != SB * rays_per_obj
+
+
+def _corner_rows_reference(s, rays, z, Hl, Wl):
+    """The rows (image * Hl * Wl + y * Wl + x, image = obj * NS + view) of the four corner texels of every (view, sample), in
+    torch on the host with the reference's op order, every operation rounded on its own as oracle/pnr_oracle.py
+    (pixelnerf_forward + index_latent) does: models.py:162-165,206-212, encoder.py:96-99,161-163, grid_sample(bilinear, border,
+    align_corners=True).  Also returns the smallest distance of an unclamped grid coordinate to a texel boundary."""
+    NS, SB = s["NS"], s["SB"]
+    per_obj = rays.shape[0] // SB
+    K = z.shape[1]
+    p = rays[:, None, 0:3] + z[:, :, None] * rays[:, None, 3:6]  # (R, K, 3), nerf.py:185
+    W, H = float(s["image_shape"][0]), float(s["image_shape"][1])
+    lsx, lsy = Wl / (Wl - 1.0) * 2.0, Hl / (Hl - 1.0) * 2.0
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    rows, margin = [], 1.0
+    for obj in range(SB):
+        X, Y, Z = (p[obj * per_obj:(obj + 1) * per_obj, :, i].reshape(-1) for i in range(3))
+        for view in range(NS):
+            img = obj * NS + view
+            P = s["poses"][img]
+            xc = [P[r, 0] * X + P[r, 1] * Y + P[r, 2] * Z + P[r, 3] for r in range(3)]
+            fo = s["focal"][obj if s["focal"].shape[0] > 1 else 0]
+            cc = s["c"][obj if s["c"].shape[0] > 1 else 0]
+            u = -xc[0] / xc[2] * fo[0] + cc[0]
+            v = -xc[1] / xc[2] * fo[1] + cc[1]
+            gx = u * (f32(lsx) / f32(W)) - 1.0
+            gy = v * (f32(lsy) / f32(H)) - 1.0
+            ix = torch.clamp(((gx + 1.0) / 2.0) * (Wl - 1.0), 0, Wl - 1)
+            iy = torch.clamp(((gy + 1.0) / 2.0) * (Hl - 1.0), 0, Hl - 1)
+            assert not torch.isnan(ix).any() and not torch.isnan(iy).any()
+            for c, n in ((ix, Wl), (iy, Hl)):
+                free = (c > 0) & (c < n - 1)
+                if free.any():
+                    margin = min(margin, float((c[free] - torch.round(c[free])).abs().min()))
+            x0, y0 = torch.floor(ix).long(), torch.floor(iy).long()
+            x1, y1 = torch.clamp(x0 + 1, max=Wl - 1), torch.clamp(y0 + 1, max=Hl - 1)
+            for yy in (y0, y1):
+                for xx in (x0, x1):
+                    rows.append(img * Hl * Wl + yy * Wl + xx)
+    return torch.unique(torch.cat(rows)), margin
+
+
+def test_marked_rows_are_exactly_the_corner_texels_the_forward_reads():
+    """fold_mark_kernel takes the projection from the helpers the forward kernels use (pnr_geom.h): the rows it marks are the
+    four corner texels of every (view, sample) -- recomputed here on the host in the reference's unfused op order -- plus texel
+    (0, 0) of each view of object 0 (the padding points of the last tile), and nothing else.  16 x 16 grid, 2 objects x 2 views,
+    24 rays x 10 samples per object; with these seeds no unclamped coordinate lies within 1e-4 of a texel boundary (asserted),
+    so the expected set does not hang on the last bit."""
+    from pixelnerf_amd import ops
+    dev = torch.device("cuda:0")
+    sc, s, meta = _scene(dev, "mv_mini")
+    Hl, Wl = s["latent"].shape[2], s["latent"].shape[3]
+    assert (Hl, Wl, s["NS"]) == (16, 16, 2)
+    rays = synthetic.target_rays(meta, n_rays=24).reshape(-1, 8)
+    K = 10
+    t = torch.sort(torch.rand(rays.shape[0], K, generator=torch.Generator().manual_seed(24)), dim=1)[0]  # margin 1.1e-3
+    z = rays[:, 6:7] + (rays[:, 7:8] - rays[:, 6:7]) * t
+    want, margin = _corner_rows_reference(s, rays, z, Hl, Wl)
+    assert margin > 1e-4, margin
+    want = torch.unique(torch.cat([want, torch.arange(s["NS"]) * Hl * Wl]))
+    state = {k: v.to(dev) for k, v in mlp_params(11).items()}
+    dense = ops.fold_latent(sc, state, "f16x3")
+    M = dense.shape[1] * dense.shape[2] * dense.shape[3]
+    buf = torch.full_like(dense, float("nan"))
+    ops.fold_latent_rows(sc, state, rays.to(dev), z.to(dev), buf)
+    got = torch.nonzero(~torch.isnan(buf.reshape(3, M, 512)[0, :, 0])).reshape(-1).cpu()
+    assert 0 < want.numel() < M
+    assert torch.equal(got, want), (got.numel(), want.numel())
