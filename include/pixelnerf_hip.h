@@ -778,6 +778,54 @@ int pnr_marching_cubes_emit(const float *field, int nx, int ny, int nz, float is
                             const void *workspace, float *vertices, int *triangles, void *stream);
 int pnr_marching_cubes_tables(int *edge_mask /*host, 256*/, int *tri /*host, 256*16*/);
 
+/* ---- occupancy-grid ray culling (inference; nothing in the reference corresponds: it renders every ray) --------
+ * A density grid of one encoded object -- sigma at the points of util.gen_grid (src/util/util.py:93-110), the grid
+ * src/util/recon.py:43-66 evaluates -- becomes a bitfield of occupied CELLS; rays are classified against it and only
+ * those that can hit something are rendered.  A ray that passes through empty cells alone composites to the value
+ * src/render/nerf.py:178-182,223-249 yields when every sigma is zero: weights 0, depth 0, rgb 0 (1 on every channel
+ * with white_bkgd, nerf.py:244-247) -- what the caller fills in for the rays these entries cull.
+ *
+ * Geometry.  A field (nx,ny,nz) has (nx-1)(ny-1)(nz-1) cells.  Cell (i,j,k) has linear index
+ * (i (ny-1) + j)(nz-1) + k; its bit is bit (index & 31) of word (index >> 5).  Per axis it spans
+ * [c1 + i h, c1 + (i+1) h] with h = (c2 - c1) / (n - 1): the TRUE spacing of util.gen_grid (util.py:93-110), where the
+ * densities were sampled -- not the (c2 - c1) / reso of src/util/recon.py:74.  c1, c2: HOST arrays of 3 floats, c1 < c2.
+ *
+ * pnr_occupancy_bytes: 4 x the number of 32-bit words of the bitfield; 0 for an invalid grid (n < 2 on an axis, or
+ * 2^31 cells and more). */
+size_t pnr_occupancy_bytes(int nx, int ny, int nz);
+/* field (nx,ny,nz) fp32, C-contiguous (the sigmas of recon.py:66 viewed as the grid) -> bits.
+ *   raw-occupied : a cell any of whose 8 corners is > threshold or is not finite (== threshold is empty).  NaN / +-inf
+ *                  count as OCCUPIED: culling must err towards rendering.  This is deliberately the opposite of the mesher
+ *                  above, where a non-finite corner is outside (recon.py:68-78).
+ *   occupied     : a cell with a raw-occupied cell within Chebyshev distance `dilate` (0..4).
+ * Every word of `bits` is written in full by ONE thread (no atomics: two calls give the same bytes); the unused high bits
+ * of the last word are zero.  n_occupied_dev (device int, nullable): the number of occupied cells = the popcount of the
+ * result, summed in a fixed order by a second, single-workgroup launch that needs no scratch (so there is no workspace
+ * argument; pnr_ssim's partial sums need one).  PNR_E_INVALID: n < 2 on an axis, 2^31 cells or more, dilate outside
+ * [0, 4], a NaN threshold, a null field / bits. */
+int pnr_occupancy_build(const float *field, int nx, int ny, int nz, float threshold, int dilate, uint32_t *bits,
+                        int *n_occupied_dev /*nullable*/, void *stream);
+/* rays (R,8) [origin, direction, near, far] (the rows of util.gen_rays, util.py:238-276) against the bitfield: for the
+ * segment o + t d, t in [near, far], over the occupied cells it passes through,
+ *   hit[r] = 1 iff there is one, and then t_bounds[r] = (max(near, t_enter - pad), min(far, t_exit + pad)) with t_enter
+ *            the smallest entry parameter and t_exit the largest exit parameter over those cells (both within
+ *            [near, far]: an origin inside an occupied cell gives t_enter = near);
+ *   hit[r] = 0 and t_bounds[r] = (near, far) otherwise.
+ * Conservative on what it cannot classify: a ray with a non-finite component, a zero direction or near >= far gets
+ * hit = 1 and unchanged bounds.  Zero direction components, origins inside the box or on a cell plane are ordinary.
+ * One thread per ray: the segment is clipped to the box, then a 3-D DDA (Amanatides & Woo) walks its cells -- all of
+ * them, the last occupied one is needed too -- at most (nx-1)+(ny-1)+(nz-1) of them.  Planes and parameters are
+ * separately rounded fp32 operations, t = ((c1 + i h) - o) / d, never accumulated.  pad >= 0, finite. */
+int pnr_occupancy_clip_rays(const float *rays, long long R, const uint32_t *bits, int nx, int ny, int nz,
+                            const float *c1 /*host*/, const float *c2 /*host*/, float pad, float *t_bounds /*(R,2)*/,
+                            int32_t *hit /*(R)*/, void *stream);
+/* pnr_philox_noise for an arbitrary list of rays (nerf.py:111,135,141,158): row r of u1 (R,Kc), u2, u3 (R,Kimp), n4 (R,Kfd)
+ * holds exactly the values the seeded entries draw for GLOBAL ray id ray_ids[r] (device, R int64; ids may repeat, be
+ * unordered and exceed 2^31) -- what the renderer feeds the explicit-noise entries with when it renders the rays that
+ * survived culling, so that a kept pixel has the bits of the dense render. */
+int pnr_philox_noise_ids(unsigned long long seed, const long long *ray_ids, int R, int Kc, int Kimp, int Kfd, float *u1,
+                         float *u2, float *u3, float *n4, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

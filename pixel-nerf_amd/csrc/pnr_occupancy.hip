@@ -1,0 +1,228 @@
+// pnr_occupancy.hip -- occupancy-grid ray culling for gfx950 (inference).  The reference renders every ray it is given; for the
+// object-centric workloads (eval/eval.py, eval/gen_video.py) most rays look through empty space.  A density grid of the encoded
+// object -- sigma at the points of util.gen_grid, src/util/util.py:93-110, as src/util/recon.py:43-66 evaluates it -- becomes a
+// bitfield of occupied cells (occupancy_build_kernel), rays are classified against it with a 3-D DDA (occupancy_clip_kernel), and the
+// caller renders the survivors only; a culled ray gets what src/render/nerf.py:178-182,223-249 composites from sigma == 0.
+// Geometry and semantics: include/pixelnerf_hip.h.  One owner thread per output word / ray, no atomics: the same bytes every run.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+
+#include "pnr_common.h"
+#include "pnr_wave.h"
+
+namespace pnr {
+
+constexpr int OCC_THREADS = 256;         // consecutive words / consecutive ray ids per wave: the rays of an image row are coherent
+constexpr int OCC_COUNT_THREADS = 1024;  // the single workgroup that counts the occupied cells
+constexpr int OCC_MAX_DILATE = 4;
+
+typedef unsigned long long u64;
+
+// a grid point makes its cells occupied iff its value is above the threshold or not finite (NaN, +-inf): culling errs towards
+// rendering -- the opposite of pnr_mesh.hip's mc_inside, on purpose
+__device__ __forceinline__ bool occ_point(float f, float thr) { return !(fabsf(f) <= 3.402823466e+38f) || f > thr; }
+
+// One thread per 32-bit word = 32 consecutive cells (k fastest), cut into runs that stay inside one (i,j) row of cells.  A cell
+// (i,j,k) is occupied iff a raw-occupied cell lies within Chebyshev distance d, i.e. iff any grid POINT of the box
+// [max(0,i-d), min(nx-2,i+d)+1] x (same in j) x (same in k) passes occ_point.  Per run the (i,j) extent of that box is shared: the
+// "any point of the (i,j) extent" flag of every k column goes into one 64-bit mask (a run has <= 32 cells, so <= 32 + 2d + 2 <= 42
+// columns), and a cell's bit is a window of that mask.
+__global__ void __launch_bounds__(OCC_THREADS)
+occupancy_build_kernel(const float *__restrict__ field, int nx, int ny, int nz, float thr, int d, long long n_cells, long long n_words,
+                       uint32_t *__restrict__ bits) {
+    const long long w = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    if (w >= n_words) return;
+    const int cy = ny - 1, cz = nz - 1;
+    long long cell = w * 32;
+    const long long end = cell + 32 < n_cells ? cell + 32 : n_cells;
+    uint32_t word = 0;
+    while (cell < end) {
+        const int k0 = (int)(cell % cz), j = (int)((cell / cz) % cy), i = (int)(cell / ((long long)cz * cy));
+        const int len = (int)((end - cell) < (long long)(cz - k0) ? (end - cell) : (long long)(cz - k0));
+        const int ilo = i - d > 0 ? i - d : 0, ihi = (i + d < nx - 2 ? i + d : nx - 2) + 1;
+        const int jlo = j - d > 0 ? j - d : 0, jhi = (j + d < ny - 2 ? j + d : ny - 2) + 1;
+        const int klo = k0 - d > 0 ? k0 - d : 0, khi = (k0 + len - 1 + d < nz - 2 ? k0 + len - 1 + d : nz - 2) + 1;
+        u64 col = 0;
+        for (int ii = ilo; ii <= ihi; ++ii)
+            for (int jj = jlo; jj <= jhi; ++jj) {
+                const float *row = field + ((size_t)ii * ny + jj) * nz;
+                for (int kk = klo; kk <= khi; ++kk) col |= (u64)occ_point(row[kk], thr) << (kk - klo);
+            }
+        const int bit0 = (int)(cell - w * 32);
+        for (int c = 0; c < len; ++c) {
+            const int k = k0 + c;
+            const int a = (k - d > 0 ? k - d : 0) - klo, b = (k + d < nz - 2 ? k + d : nz - 2) + 1 - klo;  // b - a + 1 <= 2d + 2 <= 10
+            const u64 window = ((2ull << (b - a)) - 1ull) << a;
+            word |= (uint32_t)((col & window) != 0) << (bit0 + c);
+        }
+        cell += len;
+    }
+    bits[w] = word;
+}
+
+// popcount of the bitfield by ONE workgroup: thread t adds words t, t + 1024, ...; the 16 wave sums are added in wave order
+__global__ void __launch_bounds__(OCC_COUNT_THREADS)
+occupancy_count_kernel(const uint32_t *__restrict__ bits, long long n_words, int *__restrict__ n_occupied) {
+    __shared__ unsigned wave_tot[OCC_COUNT_THREADS / 64];
+    unsigned n = 0;
+    for (long long w = threadIdx.x; w < n_words; w += OCC_COUNT_THREADS) n += (unsigned)__popc(bits[w]);
+    n = wave_sum(n);
+    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned tot = 0;
+        for (int v = 0; v < OCC_COUNT_THREADS / 64; ++v) tot += wave_tot[v];
+        *n_occupied = (int)tot;  // < 2^31 cells
+    }
+}
+
+struct OccGrid {
+    float c1[3], c2[3], h[3];  // h = (c2 - c1) / (n - 1): util.gen_grid's spacing (util.py:93-110)
+    int n[3];                  // grid POINTS per axis; cells: n - 1
+};
+
+#pragma clang fp contract(off)  // planes, differences and quotients are separately rounded: the header states them so
+
+// plane i of axis a: c1 + i h, the last one c2 itself (as np.linspace ends on `stop`)
+__device__ __forceinline__ float occ_plane(const OccGrid &g, int a, int i) { return i >= g.n[a] - 1 ? g.c2[a] : g.c1[a] + (float)i * g.h[a]; }
+
+__device__ __forceinline__ bool occ_finite(float f) { return fabsf(f) <= 3.402823466e+38f; }
+
+__global__ void __launch_bounds__(OCC_THREADS)
+occupancy_clip_kernel(const float *__restrict__ rays, long long R, const uint32_t *__restrict__ bits, const OccGrid g, float pad,
+                      float *__restrict__ t_bounds, int32_t *__restrict__ hit) {
+    const long long r = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    if (r >= R) return;
+    const float *p = rays + (size_t)r * 8;
+    const float o[3] = {p[0], p[1], p[2]}, dir[3] = {p[3], p[4], p[5]};
+    const float near = p[6], far = p[7];
+    float *tb = t_bounds + (size_t)r * 2;
+    tb[0] = near;
+    tb[1] = far;
+    bool ok = occ_finite(near) && occ_finite(far) && near < far && (dir[0] != 0.f || dir[1] != 0.f || dir[2] != 0.f);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok = ok && occ_finite(o[a]) && occ_finite(dir[a]);
+    if (!ok) { hit[r] = 1; return; }  // not classifiable: render it, bounds unchanged
+
+    // the segment inside the box [c1, c2] (slab test)
+    float t0 = near, t1 = far;
+    bool outside = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (dir[a] == 0.f) {
+            outside = outside || o[a] < g.c1[a] || o[a] > g.c2[a];
+        } else {
+            const float ta = (g.c1[a] - o[a]) / dir[a], tc = (g.c2[a] - o[a]) / dir[a];
+            t0 = fmaxf(t0, fminf(ta, tc));
+            t1 = fminf(t1, fmaxf(ta, tc));
+        }
+    }
+    if (t0 != t0 || t1 != t1) { hit[r] = 1; return; }  // (overflowed differences: not classifiable either)
+    if (outside || !(t0 < t1)) { hit[r] = 0; return; }
+
+    // the cell of the segment's first point, the DDA's state per axis: step, parameter of the next plane
+    int idx[3], step[3];
+    float tnext[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float x = o[a] + t0 * dir[a];
+        const float c = floorf((x - g.c1[a]) / g.h[a]);
+        idx[a] = (int)fminf(fmaxf(c, 0.f), (float)(g.n[a] - 2));
+        step[a] = dir[a] > 0.f ? 1 : -1;
+        tnext[a] = dir[a] == 0.f ? INFINITY : (occ_plane(g, a, idx[a] + (dir[a] > 0.f ? 1 : 0)) - o[a]) / dir[a];
+    }
+    const int cy = g.n[1] - 1, cz = g.n[2] - 1;
+    const int max_cells = (g.n[0] - 1) + cy + cz;
+    float t = t0, t_enter = 0.f, t_exit = 0.f;
+    bool any = false;
+    for (int s = 0; s < max_cells; ++s) {
+        const float tout = fminf(fminf(tnext[0], tnext[1]), tnext[2]);
+        const long long cell = ((long long)idx[0] * cy + idx[1]) * cz + idx[2];
+        if (bits[cell >> 5] >> (cell & 31) & 1u) {
+            if (!any) t_enter = t;
+            any = true;
+            t_exit = fmaxf(t, fminf(tout, t1));
+        }
+        if (!(tout < t1)) break;
+        // the axis whose plane comes first (ties: x, then y -- the cell in between is visited with zero length); selects, not
+        // indexing by a run-time axis, keep the three-element arrays in registers
+        const bool sx = tnext[0] <= tnext[1] && tnext[0] <= tnext[2], sy = !sx && tnext[1] <= tnext[2];
+        const int ni = sx ? idx[0] + step[0] : sy ? idx[1] + step[1] : idx[2] + step[2];
+        if (ni < 0 || ni > (sx ? g.n[0] : sy ? g.n[1] : g.n[2]) - 2) break;  // left the box
+        t = fmaxf(t, tout);
+        if (sx) { idx[0] = ni; tnext[0] = (occ_plane(g, 0, ni + (step[0] > 0 ? 1 : 0)) - o[0]) / dir[0]; }
+        else if (sy) { idx[1] = ni; tnext[1] = (occ_plane(g, 1, ni + (step[1] > 0 ? 1 : 0)) - o[1]) / dir[1]; }
+        else { idx[2] = ni; tnext[2] = (occ_plane(g, 2, ni + (step[2] > 0 ? 1 : 0)) - o[2]) / dir[2]; }
+    }
+    hit[r] = any ? 1 : 0;
+    if (any) {
+        tb[0] = fmaxf(near, t_enter - pad);
+        tb[1] = fminf(far, t_exit + pad);
+    }
+}
+#pragma clang fp contract(fast)
+
+static const char *occ_bad_dims(int nx, int ny, int nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return "every axis needs at least 2 grid points";
+    if ((long long)(nx - 1) * (ny - 1) * (nz - 1) >= (1LL << 31)) return "the grid must have fewer than 2^31 cells";
+    return nullptr;
+}
+
+static int occ_fail(const char *entry, const char *why) {
+    char msg[200];
+    std::snprintf(msg, sizeof msg, "%s: %s", entry, why);
+    return pnr_fail(PNR_E_INVALID, msg);  // (copies the text)
+}
+
+}  // namespace pnr
+
+extern "C" size_t pnr_occupancy_bytes(int nx, int ny, int nz) {
+    if (pnr::occ_bad_dims(nx, ny, nz)) return 0;
+    const long long cells = (long long)(nx - 1) * (ny - 1) * (nz - 1);
+    return (size_t)((cells + 31) / 32) * 4;
+}
+
+extern "C" int pnr_occupancy_build(const float *field, int nx, int ny, int nz, float threshold, int dilate, uint32_t *bits,
+                                   int *n_occupied_dev, void *stream) {
+    if (const char *why = pnr::occ_bad_dims(nx, ny, nz)) return pnr::occ_fail("pnr_occupancy_build", why);
+    if (dilate < 0 || dilate > pnr::OCC_MAX_DILATE) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_build: dilate must be in [0, 4]");
+    if (threshold != threshold) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_build: threshold is NaN");
+    if (!field) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_build: field is null");
+    if (!bits) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_build: bits is null");
+    const long long cells = (long long)(nx - 1) * (ny - 1) * (nz - 1), words = (cells + 31) / 32;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pnr::occupancy_build_kernel, dim3((unsigned)((words + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS)),
+                       dim3(pnr::OCC_THREADS), 0, st, field, nx, ny, nz, threshold, dilate, cells, words, bits);
+    if (n_occupied_dev)
+        hipLaunchKernelGGL(pnr::occupancy_count_kernel, dim3(1), dim3(pnr::OCC_COUNT_THREADS), 0, st, bits, words, n_occupied_dev);
+    return pnr_check_launch("pnr_occupancy_build");
+}
+
+extern "C" int pnr_occupancy_clip_rays(const float *rays, long long R, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
+                                       const float *c2, float pad, float *t_bounds, int32_t *hit, void *stream) {
+    if (const char *why = pnr::occ_bad_dims(nx, ny, nz)) return pnr::occ_fail("pnr_occupancy_clip_rays", why);
+    if (R < 0) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: bad sizes");
+    if (!c1 || !c2) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: c1 / c2 is null (host arrays of 3 floats)");
+    if (!(pad >= 0.f) || !std::isfinite(pad)) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: pad must be finite and >= 0");
+    pnr::OccGrid g;
+    const int n[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(c1[a]) || !std::isfinite(c2[a]) || !(c1[a] < c2[a]))
+            return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: c1 / c2 must be finite with c1 < c2 on every axis");
+        g.c1[a] = c1[a];
+        g.c2[a] = c2[a];
+        g.n[a] = n[a];
+        g.h[a] = (float)(((double)c2[a] - (double)c1[a]) / (double)(n[a] - 1));
+        if (!(g.h[a] > 0.f) || !std::isfinite(g.h[a])) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: the cell size (c2 - c1) / (n - 1) is not a positive fp32 number");
+    }
+    if (R == 0) return PNR_OK;
+    if (!rays || !bits || !t_bounds || !hit) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: null argument");
+    const long long blocks = (R + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS;
+    if (blocks > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: R exceeds the launch limit");
+    hipLaunchKernelGGL(pnr::occupancy_clip_kernel, dim3((unsigned)blocks), dim3(pnr::OCC_THREADS), 0, (hipStream_t)stream, rays, R, bits, g,
+                       pad, t_bounds, hit);
+    return pnr_check_launch("pnr_occupancy_clip_rays");
+}

@@ -4,6 +4,8 @@
 // and are bandwidth/latency-trivial next to the fused network.
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "pnr_common.h"
 #include "pnr_internal.h"
 #include "pnr_raysrc.h"
@@ -216,6 +218,29 @@ __global__ void philox_fill_kernel(const NoiseSrc ns, int R, int Kc, int Kimp, i
     n4[r * Kfd + i] = gen_normal(ns, r, i);
 }
 
+// the same for a LIST of global ray ids (culled renders: the rays that survived keep the draws of their place in the whole ray
+// set): a thread-local source whose row 0 has the id ray_ids[r] -- gen_uniform / gen_normal themselves are the sampling kernels'
+__global__ void philox_fill_ids_kernel(uint32_t seed_lo, uint32_t seed_hi, const long long *__restrict__ ray_ids, int R, int Kc, int Kimp,
+                                       int Kfd, float *__restrict__ u1, float *__restrict__ u2, float *__restrict__ u3,
+                                       float *__restrict__ n4) {
+    const int per = Kc + 2 * Kimp + Kfd;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)R * per) return;
+    const long long r = idx / per;
+    int i = (int)(idx % per);
+    NoiseSrc ns = {};
+    ns.seed_lo = seed_lo; ns.seed_hi = seed_hi;
+    ns.id_offset = ray_ids[r];
+    ns.id_stride = 1; ns.per_obj = INT_MAX;  // ray_id(ns, 0) = id_offset
+    if (i < Kc) { u1[r * Kc + i] = gen_uniform(ns, DRAW_U1, 0, i); return; }
+    i -= Kc;
+    if (i < Kimp) { u2[r * Kimp + i] = gen_uniform(ns, DRAW_U2, 0, i); return; }
+    i -= Kimp;
+    if (i < Kimp) { u3[r * Kimp + i] = gen_uniform(ns, DRAW_U3, 0, i); return; }
+    i -= Kimp;
+    n4[r * Kfd + i] = gen_normal(ns, 0, i);
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -321,6 +346,20 @@ extern "C" int pnr_philox_noise(unsigned long long seed, long long id_offset, in
     hipLaunchKernelGGL(philox_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        seeded_noise(seed, id_offset, id_stride, rays_per_obj), R, Kc, Kimp, Kfd, u1, u2, u3, n4);
     return pnr_check_launch("pnr_philox_noise");
+}
+
+extern "C" int pnr_philox_noise_ids(unsigned long long seed, const long long *ray_ids, int R, int Kc, int Kimp, int Kfd, float *u1,
+                                    float *u2, float *u3, float *n4, void *stream) {
+    if (R < 0 || Kc < 0 || Kimp < 0 || Kfd < 0) return pnr_fail(PNR_E_INVALID, "pnr_philox_noise_ids: bad sizes");
+    const long long n = (long long)R * ((long long)Kc + 2LL * Kimp + Kfd);
+    if (n == 0) return PNR_OK;  // no rays (every ray culled) or nothing to draw
+    if ((Kc > 0 && !u1) || (Kimp > 0 && (!u2 || !u3)) || (Kfd > 0 && !n4)) return pnr_fail(PNR_E_INVALID, "pnr_philox_noise_ids: null output");
+    if (!ray_ids) return pnr_fail(PNR_E_INVALID, "pnr_philox_noise_ids: ray_ids is null");
+    if ((long long)Kc + 2LL * Kimp + Kfd > 0x7fffffffLL || (n + 255) / 256 > 0x7fffffffLL)
+        return pnr_fail(PNR_E_INVALID, "pnr_philox_noise_ids: too many values for one launch");
+    hipLaunchKernelGGL(philox_fill_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), ray_ids, R, Kc, Kimp, Kfd, u1, u2, u3, n4);
+    return pnr_check_launch("pnr_philox_noise_ids");
 }
 
 extern "C" int pnr_philox_raw(const uint32_t *counter4 /*host*/, const uint32_t *key2 /*host*/, uint32_t *out4 /*host*/) {

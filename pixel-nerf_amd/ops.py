@@ -1091,6 +1091,83 @@ def marching_cubes(field, iso, c1=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0), check_
     return vertices, triangles
 
 
+def occupancy_build(field, threshold, dilate=1):
+    """A density grid as a bitfield of occupied cells (pnr_occupancy_build; geometry and semantics in include/pixelnerf_hip.h).
+    field (nx,ny,nz) fp32 HIP tensor -- sigma at the points of ops.gen_grid_points.  A cell is occupied iff a cell with a corner
+    > threshold (or a non-finite corner: culling errs towards rendering) lies within Chebyshev distance `dilate` (0..4).
+    -> (bits ((cells + 31) // 32,) int32 words -- cell (i,j,k) is bit (index & 31) of word (index >> 5), index = (i (ny-1) + j)(nz-1) + k
+    -- and n_occupied, a 0-d int32 tensor, both on the field's device; no host synchronisation, the same bytes on every call)."""
+    lib = _lib.load()
+    field = _f32(field, "field", (None, None, None))
+    nx, ny, nz = field.shape
+    nbytes = lib.pnr_occupancy_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError(f"occupancy_build: a grid needs at least 2 points per axis and fewer than 2^31 cells, got {(nx, ny, nz)}")
+    if not 0 <= int(dilate) <= 4:
+        raise ValueError(f"occupancy_build: dilate must be in [0, 4], got {dilate}")
+    bits = torch.empty((nbytes // 4,), dtype=torch.int32, device=field.device)
+    count = torch.empty((), dtype=torch.int32, device=field.device)
+    with torch.cuda.device(field.device):
+        _lib.check(lib.pnr_occupancy_build(_p(field), nx, ny, nz, float(threshold), int(dilate), _p(bits), _p(count), _stream()),
+                   "pnr_occupancy_build")
+    return bits, count
+
+
+def occupancy_clip_rays(rays, bits, reso, c1, c2, pad=0.0):
+    """Rays against an occupancy bitfield (pnr_occupancy_clip_rays): rays (R,8) fp32 HIP tensor, bits from occupancy_build of a
+    field with `reso` = (nx,ny,nz) points spanning [c1, c2].  -> (t_bounds (R,2) fp32, hit (R,) int32): hit = 1 iff the segment
+    t in [near, far] passes through an occupied cell, t_bounds = (max(near, t_enter - pad), min(far, t_exit + pad)) over those
+    cells; a miss keeps (near, far).  A ray that cannot be classified (non-finite, zero direction, near >= far) counts as hit."""
+    lib = _lib.load()
+    rays = _f32(rays, "rays", (None, 8))
+    if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
+        raise ValueError("occupancy_clip_rays: c1, c2, reso must have 3 entries each")
+    nx, ny, nz = (int(r) for r in reso)
+    nbytes = lib.pnr_occupancy_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError(f"occupancy_clip_rays: a grid needs at least 2 points per axis and fewer than 2^31 cells, got {(nx, ny, nz)}")
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or bits.dim() != 1 or bits.numel() != nbytes // 4:
+        raise ValueError(f"occupancy_clip_rays: bits must be the ({nbytes // 4},) int32 tensor of occupancy_build for reso {(nx, ny, nz)}")
+    if bits.device != rays.device:
+        raise ValueError(f"occupancy_clip_rays: bits live on {bits.device}, the rays on {rays.device}")
+    R, dev = rays.shape[0], rays.device
+    t_bounds = torch.empty((R, 2), dtype=torch.float32, device=dev)
+    hit = torch.empty((R,), dtype=torch.int32, device=dev)
+    lo, hi = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in c2])
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_occupancy_clip_rays(_p(rays), R, _p(bits.contiguous()), nx, ny, nz, lo, hi, float(pad), _p(t_bounds), _p(hit),
+                                               _stream()), "pnr_occupancy_clip_rays")
+    return t_bounds, hit
+
+
+def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):
+    """philox_noise for a list of GLOBAL ray ids (pnr_philox_noise_ids): ray_ids (R,) int64 HIP tensor -- any order, repeats
+    allowed, beyond 2^31 too -- -> the dict philox_noise returns, row r holding what the seeded renderer entries draw for ray
+    ray_ids[r].  How a culled render keeps the dense render's draws for the rays it keeps."""
+    lib = _lib.load()
+    if not isinstance(ray_ids, torch.Tensor):
+        raise TypeError("ray_ids: expected a torch.Tensor")
+    if not ray_ids.is_cuda:
+        raise _lib.PixelNerfHipError(f"ray_ids: tensor must live on a HIP device (got {ray_ids.device}); pixelnerf_amd has no CPU path")
+    if ray_ids.dtype != torch.int64 or ray_ids.dim() != 1:
+        raise TypeError(f"ray_ids: expected a 1-d int64 tensor, got {ray_ids.dtype} {tuple(ray_ids.shape)}")
+    ray_ids = ray_ids.contiguous()
+    R, device = ray_ids.shape[0], ray_ids.device
+    Kc, Kf, Kfd = int(n_coarse), int(n_fine), int(n_fine_depth)
+    Kimp = max(Kf - Kfd, 0) if Kf > 0 else 0
+    Kfd = Kfd if Kf > 0 else 0
+    out = {"u1": torch.empty((R, Kc), dtype=torch.float32, device=device)}
+    if Kimp > 0:
+        out["u2"] = torch.empty((R, Kimp), dtype=torch.float32, device=device)
+        out["u3"] = torch.empty((R, Kimp), dtype=torch.float32, device=device)
+    if Kfd > 0:
+        out["n4"] = torch.empty((R, Kfd), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.pnr_philox_noise_ids(int(seed) & (2 ** 64 - 1), _p(ray_ids), R, Kc, Kimp, Kfd, _p(out["u1"]), _p(out.get("u2")),
+                                            _p(out.get("u3")), _p(out.get("n4")), _stream()), "pnr_philox_noise_ids")
+    return out
+
+
 def eval_epilogue(rgb, depth=None, z_near=0.0, z_far=1.0, gt_rgb=None, want_u8=True, image_shape=None):
     """eval/eval.py:283-290,327-329 on device.  rgb (NV,P,3) [+ depth (NV,P)] [+ gt_rgb (NV,P,3) in [0,1]] ->
     dict(rgb (clamped), rgb_u8, depth_norm, sse (NV,) float64, psnr (NV,) float64).  image_shape=(H, W) with gt_rgb adds

@@ -32,11 +32,12 @@ class _RenderWrapper(torch.nn.Module):
         self.renderer = renderer
         self.simple_output = simple_output
 
-    def forward(self, rays, want_weights=False):
+    def forward(self, rays, want_weights=False, occupancy=None, tighten=False):
         if rays.shape[0] == 0:
             return (torch.zeros(0, 3, device=rays.device), torch.zeros(0, device=rays.device))
         with torch.profiler.record_function("render_par"):
-            outputs = self.renderer(self.net, rays, want_weights=want_weights and not self.simple_output)
+            outputs = self.renderer(self.net, rays, want_weights=want_weights and not self.simple_output, occupancy=occupancy,
+                                    tighten=tighten)
         if self.simple_output:
             if self.renderer.using_fine:
                 return outputs.fine.rgb, outputs.fine.depth
@@ -44,13 +45,13 @@ class _RenderWrapper(torch.nn.Module):
         return outputs.toDict()
 
     def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, views_per_call=None,
-                     _noise=None):
+                     _noise=None, occupancy=None, tighten=False):
         """Images of the target views from their cameras, with depth normalisation and, given ground truth, PSNR and SSIM per
         view, all on the device (NeRFRenderer.render_views; the loop of eval/eval.py:247-331 as one call).  Inference only:
         runs under torch.no_grad()."""
         with torch.profiler.record_function("render_par"):
             return self.renderer.render_views(self.net, poses_c2w, W, H, focal, z_near, z_far, c=c, gt_rgb=gt_rgb, want_u8=want_u8,
-                                              views_per_call=views_per_call, _noise=_noise)
+                                              views_per_call=views_per_call, _noise=_noise, occupancy=occupancy, tighten=tighten)
 
 
 class NeRFRenderer(torch.nn.Module):
@@ -163,12 +164,30 @@ class NeRFRenderer(torch.nn.Module):
                 noise["n4"] = torch.randn(R, self.n_fine_depth, device=dev)
         return noise
 
-    def forward(self, model, rays, want_weights=False, _noise=None):
+    def forward(self, model, rays, want_weights=False, _noise=None, occupancy=None, tighten=False):
         """src/render/nerf.py:251-303.
         :param model nerf model: (SB,B,3) points [+ viewdirs] -> (SB,B,4) rgb sigma
         :param rays [origins(3), directions(3), near, far] (SB,B,8)
+        :param occupancy a util.occupancy.OccupancyGrid of the ONE encoded object (inference only): only the rays that pass through
+        an occupied cell are rendered, the others are filled with what the compositing yields for sigma == 0 (nerf.py:223-249: rgb 0,
+        or 1 with white_bkgd; depth 0; weights 0).  With rng="philox" a rendered ray has exactly the bits of the call without
+        `occupancy` (it keeps the draws of its global ray id); with rng="torch" or a generic model callable the draws are made for
+        the rendered rays only, so the image is a different sample of the same distribution.  None: the call of the reference.
+        :param tighten with `occupancy`: sample every rendered ray between its first and last occupied cell instead of [near, far]
+        (the same number of samples over a shorter range: denser, so the image then differs from the dense render everywhere)
         :return DotMap {coarse:{rgb (SB,B,3), depth (SB,B)[, weights (SB,B,K)]}, fine:{...}}"""
         with torch.profiler.record_function("renderer_forward"):  # the reference's scope name (nerf.py:264)
+            if occupancy is not None:
+                assert len(rays.shape) == 3
+                self._apply_sched()
+                flat = rays.reshape(-1, 8).float().contiguous()
+                self._check_culled_call(model, flat, rays.shape[0])
+                res = self._render_culled(model, flat, self.ray_id_offset, occupancy, tighten, want_weights, _noise,
+                                          self._culled_seed(model, flat.device, _noise))[0]
+                outputs = DotMap(coarse=self._format(res["coarse"], 1, want_weights))
+                if "fine" in res:
+                    outputs.fine = self._format(res["fine"], 1, want_weights)
+                return outputs
             return self._forward(model, rays, want_weights, _noise)
 
     def _apply_sched(self):
@@ -198,12 +217,7 @@ class NeRFRenderer(torch.nn.Module):
 
         if fused:  # pixelnerf_amd.PixelNeRFNet: one C call
             model._check_supported()
-            needs_grad = torch.is_grad_enabled() and (
-                model.mlp_coarse.any_requires_grad()
-                or (model.mlp_fine is not None and model.mlp_fine.any_requires_grad())
-                or (model.encoder.latent.requires_grad and not model.stop_encoder_grad)
-                or rays.requires_grad  # rays and cameras: pose estimation / refinement (autograd._RenderFunction)
-                or any(torch.is_tensor(t) and t.requires_grad for t in (model.poses, model.focal, model.c)))
+            needs_grad = self._fused_needs_grad(model, rays)
             if self.training and self.noise_std > 0.0 and not needs_grad:
                 raise NotImplementedError("noise_std > 0 in train mode is implemented on the differentiable path (grad enabled); "
                                           "the reference adds the noise only while training (nerf.py:225-226)")
@@ -245,6 +259,83 @@ class NeRFRenderer(torch.nn.Module):
             wf, rgbf, depthf = self.composite(model, rays, z_all, coarse=False, sb=SB)
             outputs.fine = self._format(dict(rgb=rgbf, depth=depthf, weights=wf), SB, want_weights)
         return outputs
+
+    @staticmethod
+    def _fused_needs_grad(model, rays):
+        """whether a call on a fused PixelNeRFNet takes the differentiable path"""
+        return torch.is_grad_enabled() and (
+            model.mlp_coarse.any_requires_grad()
+            or (model.mlp_fine is not None and model.mlp_fine.any_requires_grad())
+            or (model.encoder.latent.requires_grad and not model.stop_encoder_grad)
+            or rays.requires_grad  # rays and cameras: pose estimation / refinement (autograd._RenderFunction)
+            or any(torch.is_tensor(t) and t.requires_grad for t in (model.poses, model.focal, model.c)))
+
+    # ---- occupancy-grid culling (inference): render the rays that can hit something, fill in the rest ----
+    def _check_culled_call(self, model, rays, SB):
+        """the refusals of a call with `occupancy`; rays: the call's differentiable input (the rays, or the cameras of render_views)"""
+        if SB != 1 or int(getattr(model, "num_objs", 1) or 1) != 1:
+            raise ValueError(f"occupancy: an OccupancyGrid describes ONE object, the call has {max(SB, int(getattr(model, 'num_objs', 1) or 1))}; "
+                             "encode one object and pass its rays as (1,B,8)")
+        if self._is_fused(model):
+            needs_grad = self._fused_needs_grad(model, rays)
+        else:
+            params = list(model.parameters()) if hasattr(model, "parameters") else []
+            needs_grad = torch.is_grad_enabled() and (rays.requires_grad or any(p.requires_grad for p in params))
+        if needs_grad:
+            raise NotImplementedError("occupancy: culling is an inference feature -- this call would take the differentiable path "
+                                      "(parameters, feature grid, rays or cameras require grad); call it under torch.no_grad()")
+        if rays.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("occupancy: the number of rays that survive is read on the host to size the launch, which a "
+                                      "HIP-graph capture cannot contain; capture the call without `occupancy`")
+
+    def _culled_seed(self, model, dev, given_noise):
+        """the ONE Philox key of a culled call, taken exactly where the dense call takes its own (the generator advances the same
+        way); None: the draws are torch's (rng="torch", a generic model callable, explicit noise)"""
+        seeded = (given_noise is None and self._is_fused(model) and self.rng == "philox"
+                  and not (self.training and torch.is_grad_enabled()))
+        return self._next_seed(dev) if seeded else None
+
+    def _background(self, R, K, want_weights, dev):
+        """what nerf.py:223-249 composites from sigma == 0 on every sample: T = 1 throughout, all weights 0"""
+        out = {"rgb": torch.full((R, 3), 1.0 if self.white_bkgd else 0.0, dtype=torch.float32, device=dev),
+               "depth": torch.zeros((R,), dtype=torch.float32, device=dev)}
+        if want_weights:
+            out["weights"] = torch.zeros((R, K), dtype=torch.float32, device=dev)
+        return out
+
+    def _render_culled(self, model, rays, first_id, occupancy, tighten, want_weights, given_noise, seed):
+        """The shared body of forward(occupancy=) and render_views(occupancy=): rays (R,8) of ONE object whose row r has the global
+        ray id first_id + r.  Clip against the grid, gather the rays that hit, render them through the ordinary forward with the
+        draws of their global ids (seed; given_noise is cut to the hit rows), scatter into outputs pre-filled with the empty-ray
+        value.  One host synchronisation: the number of hit rays.
+        -> ({"coarse": {...}[, "fine": {...}]} flat tensors, hit (R,) bool, the number of hit rays)"""
+        R, dev = rays.shape[0], rays.device
+        Kc = self.n_coarse
+        Kf = self.n_fine if self.using_fine else 0
+        Kfd = min(self.n_fine_depth, Kf)
+        res = {"coarse": self._background(R, Kc, want_weights, dev)}
+        if Kf > 0:
+            res["fine"] = self._background(R, Kc + Kf, want_weights, dev)
+        t_bounds, hit = occupancy.clip_rays(rays)
+        hit = hit != 0
+        idx = torch.nonzero(hit).flatten()  # ascending; its length reaches the host here
+        if idx.numel() == 0:
+            return res, hit, 0  # nothing can be hit: no network launch
+        sub = rays.index_select(0, idx)
+        if tighten:
+            sub[:, 6:8] = t_bounds.index_select(0, idx)
+        if given_noise is not None:
+            noise = {k: v.index_select(0, idx) for k, v in given_noise.items()}
+        elif seed is not None:
+            noise = ops.philox_noise_ids(idx + int(first_id), Kc, Kf, Kfd, seed)
+        else:
+            noise = None  # torch draws, for the rendered rays only
+        out = self._forward(model, sub.unsqueeze(0), want_weights, noise)
+        for name, full in res.items():
+            part = out[name]
+            for key, t in full.items():
+                t.index_copy_(0, idx, part[key].reshape(idx.numel(), *t.shape[1:]))
+        return res, hit, idx.numel()
 
     def _rays_launch(self, model, rays, Kf, Kfd, noise, want_weights):
         """the launch of _fused_inference for rays (R,8): the seeded / folded one-call renderer"""
@@ -289,7 +380,7 @@ class NeRFRenderer(torch.nn.Module):
 
     # ---- cameras -> images ----
     def render_views(self, model, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False,
-                     views_per_call=None, _noise=None):
+                     views_per_call=None, _noise=None, occupancy=None, tighten=False):
         """Every pixel of the target views from their cameras, with the evaluation epilogue on the device: what
         eval/eval.py:247-331 does per object (util.gen_rays, render_par over ray batches, clamp, depth normalisation, PSNR and
         SSIM per view) as one call.  An INFERENCE entry: it runs under torch.no_grad() whatever the caller's mode.
@@ -302,11 +393,20 @@ class NeRFRenderer(torch.nn.Module):
         psnr, ssim (SB,NVt) float64 of clamp(rgb, 0, 1) against gt_rgb.  All on the device, no host synchronisation beyond what
         forward has on the first call with new weights.
         Under the same torch.manual_seed the image equals, bit for bit, forward over util.gen_rays of the same cameras; a fused
-        PixelNeRFNet renders without a ray array (ops.render_views), anything else goes through util.gen_rays + forward."""
+        PixelNeRFNet renders without a ray array (ops.render_views), anything else goes through util.gen_rays + forward.
+        :param occupancy a util.occupancy.OccupancyGrid of the ONE encoded object: the rays are materialised (per group of
+        views_per_call views), clipped against the grid, and only those that pass through an occupied cell are rendered -- see
+        forward.  The return value then also has `hit` (SB,NVt,H,W) bool, the pixels that were rendered, and `n_hit`, their number
+        (a host int); every other pixel holds the background (rgb 0, or 1 with white_bkgd; depth 0), and the epilogue (depth_norm,
+        rgb_u8, psnr, ssim) runs on the full image as always.  With rng="philox" the pixels of `hit` have the bits of the call
+        without `occupancy` under the same torch.manual_seed.  One host synchronisation per group of views.
+        :param tighten with `occupancy`: sample the rendered rays between their first and last occupied cell (see forward)"""
         with torch.no_grad(), torch.profiler.record_function("renderer_render_views"):
-            return self._render_views(model, poses_c2w, int(W), int(H), focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise)
+            return self._render_views(model, poses_c2w, int(W), int(H), focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise,
+                                      occupancy, tighten)
 
-    def _render_views(self, model, poses, W, H, focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise):
+    def _render_views(self, model, poses, W, H, focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise, occupancy=None,
+                      tighten=False):
         from .. import util
         self._apply_sched()
         if poses.dim() == 3:
@@ -330,7 +430,10 @@ class NeRFRenderer(torch.nn.Module):
         Kfd = min(self.n_fine_depth, Kf)
         fast = (self._is_fused(model) and flat.is_cuda and model._effective_precision() != "f32"
                 and not torch.cuda.is_current_stream_capturing() and not (self.training and self.noise_std > 0.0))
-        if not fast:
+        hit = None
+        if occupancy is not None:
+            rgb, depth, hit = self._render_views_culled(model, poses, W, H, focal, z_near, z_far, c, views_per_call, _noise, occupancy, tighten)
+        elif not fast:
             # a generic model callable, a composed-path PixelNeRFNet, the exact fp32 path, a capture in progress: the rays, then forward
             rays = util.gen_rays(flat, W, H, focal, z_near, z_far, c).reshape(SB, -1, 8)
             out = self.forward(model, rays, _noise=_noise)
@@ -354,6 +457,8 @@ class NeRFRenderer(torch.nn.Module):
             else:
                 rgb, depth = self._render_view_groups(model, poses, k, W, H, focal, z_near, z_far, c, Kf, Kfd, seed, seeded, _noise, noise)
         ret = DotMap(rgb=rgb.reshape(SB, NVt, H, W, 3), depth=depth.reshape(SB, NVt, H, W))
+        if hit is not None:
+            ret.hit, ret.n_hit = hit[0].reshape(SB, NVt, H, W), hit[1]
         gt = None
         if gt_rgb is not None:
             if tuple(gt_rgb.shape) != (SB, NVt, H, W, 3) and (SB != 1 or tuple(gt_rgb.shape) != (NVt, H, W, 3)):
@@ -367,6 +472,27 @@ class NeRFRenderer(torch.nn.Module):
         if gt is not None:
             ret.psnr, ret.ssim = ep["psnr"].reshape(SB, NVt), ep["ssim"].reshape(SB, NVt)
         return ret
+
+    def _render_views_culled(self, model, poses, W, H, focal, z_near, z_far, c, views_per_call, given_noise, occupancy, tighten):
+        """render_views(occupancy=): the rays of every group of views (all views without views_per_call) through _render_culled,
+        under ONE key; ray id = pixel index in the (NVt,H,W) order.  -> (rgb (R,3), depth (R,), (hit (R,) bool, n_hit))"""
+        SB, NVt = poses.shape[:2]
+        HW = H * W
+        flat = poses.reshape(-1, 4, 4).float().contiguous()
+        self._check_culled_call(model, flat, SB)
+        seed = self._culled_seed(model, flat.device, given_noise)
+        k = NVt if views_per_call is None else min(int(views_per_call), NVt)
+        parts, n_hit = [], 0
+        for v0 in range(0, NVt, k):
+            v1 = min(v0 + k, NVt)
+            rays = ops.gen_rays(flat[v0:v1].contiguous(), W, H, focal, z_near, z_far, c).reshape(-1, 8)
+            part = given_noise if given_noise is None else {n: t[v0 * HW:v1 * HW] for n, t in given_noise.items()}
+            res, hit, n = self._render_culled(model, rays, v0 * HW, occupancy, tighten, False, part, seed)
+            last = res["fine"] if "fine" in res else res["coarse"]
+            parts.append((last["rgb"], last["depth"], hit))
+            n_hit += n
+        rgb, depth, hit = (torch.cat([p[i] for p in parts]) if len(parts) > 1 else parts[0][i] for i in range(3))
+        return rgb, depth, (hit, n_hit)
 
     def _render_view_groups(self, model, poses, k, W, H, focal, z_near, z_far, c, Kf, Kfd, seed, seeded, given_noise, noise):
         """render_views, k views per object at a time.  pnr_render_views numbers its rays from 0, so a group goes through its

@@ -8,6 +8,7 @@ import torch
 
 from .conf import Conf  # noqa: F401
 from .dotmap import DotMap  # noqa: F401
+from .occupancy import OccupancyGrid  # noqa: F401
 
 
 def repeat_interleave(input, repeats, dim=0):

@@ -18,6 +18,49 @@ import numpy as np
 import torch
 
 
+def density_grid(occu_net, c1, c2, reso, coarse=True, sigma_idx=3, eval_batch_size=100000, device=None, what="density_grid"):
+    """
+    The density of an encoded object on the grid of src/util/recon.py:43-66, on the device: what marching_cubes meshes and what
+    util.occupancy.OccupancyGrid.from_model turns into an occupancy bitfield.  The points come from ops.gen_grid_points (with the
+    reference's fake view directions, and its warning, when the network uses view directions), every chunk of eval_batch_size
+    points goes through `occu_net(xyz (1,N,3), coarse=, viewdirs=)`; runs under torch.no_grad() in eval mode, the network's
+    train / eval flag is restored.
+    :param coarse which network: True / False, or a tuple of them -> the element-wise MAXIMUM over those passes
+    :return (sigmas (prod reso,) float32 on the device -- `.view(*reso)` is the grid, x the slowest axis --, reso as a list of ints)
+    """
+    from .. import ops
+    use_viewdirs = bool(getattr(occu_net, "use_viewdirs", False))
+    if use_viewdirs:
+        warnings.warn("Running marching cubes with fake view dirs (pointing to origin), output may be invalid")
+    if int(getattr(occu_net, "num_objs", 1) or 1) > 1:
+        raise ValueError(f"{what}: the network encoded {int(occu_net.num_objs)} objects; encode one object")
+    reso = [int(r) for r in reso]
+    if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
+        raise ValueError(f"{what}: c1, c2, reso must have 3 entries each")
+    if device is None:
+        device = next(occu_net.parameters()).device
+    device = torch.device(device)
+    passes = tuple(coarse) if isinstance(coarse, (tuple, list)) else (coarse,)
+    total = reso[0] * reso[1] * reso[2]
+    is_train = bool(getattr(occu_net, "training", False))
+    if hasattr(occu_net, "eval"):
+        occu_net.eval()
+    try:
+        with torch.no_grad():
+            sigmas = torch.empty((total,), dtype=torch.float32, device=device)
+            for first in range(0, total, int(eval_batch_size)):
+                count = min(int(eval_batch_size), total - first)
+                pnts, vd = ops.gen_grid_points(c1, c2, reso, first, count, device=device, viewdirs=use_viewdirs)
+                for n, which in enumerate(passes):
+                    outputs = occu_net(pnts[None], coarse=which, viewdirs=vd[None] if use_viewdirs else None)
+                    sigma = outputs.reshape(count, -1)[:, sigma_idx]
+                    sigmas[first:first + count] = sigma if n == 0 else torch.maximum(sigmas[first:first + count], sigma)
+    finally:
+        if is_train:
+            occu_net.train()
+    return sigmas, reso
+
+
 def marching_cubes(
     occu_net,
     c1=[-1, -1, -1],
@@ -50,35 +93,11 @@ def marching_cubes(
     :return vertices (V,3) float64, triangles (T,3) int32 (numpy, like the reference)
     """
     from .. import ops
-    use_viewdirs = bool(getattr(occu_net, "use_viewdirs", False))
-    if use_viewdirs:
-        warnings.warn("Running marching cubes with fake view dirs (pointing to origin), output may be invalid")
-    if int(getattr(occu_net, "num_objs", 1) or 1) > 1:
-        raise ValueError(f"marching_cubes: the network encoded {int(occu_net.num_objs)} objects; encode one object")
-    reso = [int(r) for r in reso]
-    if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
-        raise ValueError("marching_cubes: c1, c2, reso must have 3 entries each")
-    if device is None:
-        device = next(occu_net.parameters()).device
-    device = torch.device(device)
-    total = reso[0] * reso[1] * reso[2]
-    is_train = bool(getattr(occu_net, "training", False))
-    if hasattr(occu_net, "eval"):
-        occu_net.eval()
-    try:
-        with torch.no_grad():
-            sigmas = torch.empty((total,), dtype=torch.float32, device=device)
-            for first in range(0, total, int(eval_batch_size)):
-                count = min(int(eval_batch_size), total - first)
-                pnts, vd = ops.gen_grid_points(c1, c2, reso, first, count, device=device, viewdirs=use_viewdirs)
-                outputs = occu_net(pnts[None], coarse=coarse, viewdirs=vd[None] if use_viewdirs else None)
-                sigmas[first:first + count] = outputs.reshape(count, -1)[:, sigma_idx]
-            lo, hi = np.array(c1, dtype=np.float64), np.array(c2, dtype=np.float64)
-            scale = (hi - lo) / (np.array(reso) - 1 if align_to_grid else np.array(reso))
-            vertices, triangles = ops.marching_cubes(sigmas.view(*reso), float(isosurface), c1=lo, scale=scale)
-    finally:
-        if is_train:
-            occu_net.train()
+    sigmas, reso = density_grid(occu_net, c1, c2, reso, coarse=coarse, sigma_idx=sigma_idx, eval_batch_size=eval_batch_size,
+                                device=device, what="marching_cubes")
+    lo, hi = np.array(c1, dtype=np.float64), np.array(c2, dtype=np.float64)
+    scale = (hi - lo) / (np.array(reso) - 1 if align_to_grid else np.array(reso))
+    vertices, triangles = ops.marching_cubes(sigmas.view(*reso), float(isosurface), c1=lo, scale=scale)
     if as_tensors:
         return vertices, triangles
     return vertices.cpu().numpy().astype(np.float64), triangles.cpu().numpy()
