@@ -826,6 +826,47 @@ int pnr_occupancy_clip_rays(const float *rays, long long R, const uint32_t *bits
 int pnr_philox_noise_ids(unsigned long long seed, const long long *ray_ids, int R, int Kc, int Kimp, int Kfd, float *u1,
                          float *u2, float *u3, float *n4, void *stream);
 
+/* ---- per-sample skipping against the same bitfield (inference): the network runs on the samples in occupied cells only.
+ * The staged entries (pnr_sample_coarse, pnr_eval_ray_samples*, pnr_composite, pnr_sample_fine) launch the kernels of the
+ * one-call renderer and a sample's world point is o + z d in separately rounded operations, so the one-sample "ray"
+ * (rays[r], z[r,k]) is the same point as sample k of ray r in the dense call.  mark -> compact ->
+ * pnr_eval_ray_samples*(rays_c, z_c, R = M, K = 1) -> expand -> pnr_composite is the dense pass with rgb sigma = 0 at every
+ * sample the grid calls empty: bit for bit where a point's output does not depend on its place in the launch (the 16-bit
+ * kernel, the exact fp32 path).  The split-operand kernel's last places depend on whether the point's place in the launch is
+ * even or odd: there a caller keeps whole pairs (2j, 2j+1) of the dense launch in the list and drops the partner's output.
+ *
+ * pnr_occupancy_mark_samples: rays (R,8), z (R,K) -> keep (R,K) bytes, one thread per sample (consecutive samples of a
+ * ray in consecutive lanes), no atomics.  The point is P[a] = o[a] + z d[a]: one multiply and one add, each rounded (the
+ * operations of the network kernels' own sample point).  keep = 1 iff c1[a] <= P[a] <= c2[a] on all three axes AND the
+ * bit of the point's cell is set; the cell is clamp(floorf((P[a] - c1[a]) / h[a]), 0, n[a] - 2) per axis, with the h of
+ * pnr_occupancy_clip_rays (the fp32 rounding of the fp64 quotient (c2 - c1) / (n - 1)) -- the cell that entry assigns to
+ * a point; a point on the c2 face belongs to the last cell.  A point outside the box is EMPTY (keep = 0), as a ray that
+ * misses the box is culled.  A sample whose z, or any origin or direction component of whose ray, is not finite gets
+ * keep = 1: culling errs towards rendering.  near and far (columns 6, 7) are not read.  c1, c2: HOST arrays, c1 < c2.
+ * PNR_E_INVALID: R < 0, K < 1, R K >= 2^31, a bad grid (as pnr_occupancy_clip_rays), a null pointer.  R = 0: no-op. */
+int pnr_occupancy_mark_samples(const float *rays, const float *z, int R, int K, const uint32_t *bits, int nx, int ny,
+                               int nz, const float *c1 /*host*/, const float *c2 /*host*/, uint8_t *keep /*(R,K)*/,
+                               void *stream);
+/* Stable compaction of the marked samples.  With g_0 < g_1 < ... < g_{M-1} the sample ids (r K + k) whose keep != 0:
+ *   index[m] = g_m,  rays_c[m] = rays[g_m / K] (all 8 floats, near and far included),  z_c[m] = z[g_m],  *count_dev = M.
+ * index, rays_c (.,8) and z_c need room for M rows (R K always suffices); rows >= M are NOT written.  Three ordinary
+ * launches in stream order -- per-workgroup totals (wave ballot + popcount), an exclusive scan of the totals by ONE
+ * workgroup, the scatter -- and no workgroup waits on another; no atomics, so two calls give the same bytes.  Ray rows
+ * move as two 16-byte accesses: rays and rays_c must be 16-byte aligned.  workspace: caller-owned device memory of
+ * pnr_compact_samples_workspace_bytes(R K) bytes (4 per workgroup of 256 samples; 0 for N <= 0 or N >= 2^31), overwritten.
+ * PNR_E_INVALID: R < 0, K < 1, R K >= 2^31, a null or misaligned pointer, a workspace that is too small.
+ * R = 0: no-op (nothing is written, *count_dev included). */
+size_t pnr_compact_samples_workspace_bytes(long long N);
+int pnr_compact_samples(const uint8_t *keep, const float *rays, const float *z, int R, int K, int32_t *index,
+                        float *rays_c, float *z_c, int *count_dev, void *workspace, size_t workspace_bytes, void *stream);
+/* The inverse placement: rgbsigma (N,4) = rgbsigma_c[m] at row index[m] (m < M), (0,0,0,0) at every other row.  EVERY
+ * element of rgbsigma is written (a zero fill, then the scatter, in stream order).  index: M distinct rows in [0, N), as
+ * pnr_compact_samples writes them (an entry outside [0, N) is skipped, never written through).  M = 0 is valid (index and
+ * rgbsigma_c may then be null) and gives all zeros.  Rows move as 16-byte accesses: rgbsigma and rgbsigma_c must be
+ * 16-byte aligned.  PNR_E_INVALID: M < 0, N < 0, M > N, N >= 2^31, a null or misaligned pointer.  N = 0: no-op. */
+int pnr_expand_rgbsigma(const int32_t *index, const float *rgbsigma_c /*(M,4)*/, int M, long long N,
+                        float *rgbsigma /*(N,4)*/, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

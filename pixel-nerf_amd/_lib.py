@@ -189,6 +189,10 @@ PROTOTYPES = {
     "pnr_occupancy_build": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P]),
     "pnr_occupancy_clip_rays": (_I, [_P, ctypes.c_longlong, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _P, _P, _P]),
     "pnr_philox_noise_ids": (_I, [ctypes.c_ulonglong, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "pnr_occupancy_mark_samples": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _P, _P]),
+    "pnr_compact_samples_workspace_bytes": (_SZ, [ctypes.c_longlong]),
+    "pnr_compact_samples": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "pnr_expand_rgbsigma": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _P]),
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }
@@ -300,8 +304,13 @@ def load():
     if abi != ABI_VERSION:
         raise PixelNerfHipError(f"{LIB_PATH} implements ABI revision {abi}, this binding was written against {ABI_VERSION} "
                                 "(include/pixelnerf_hip.h PNR_ABI_VERSION): rebuild it (__graft_entry__.build())")
+    # (entries are also ADDED within a revision: a library of this revision built before one was does not export it)
+    missing = [name for name in PROTOTYPES if not hasattr(lib, name)]
+    if missing:
+        raise PixelNerfHipError(f"{LIB_PATH} reports ABI revision {abi} but does not export {', '.join(missing)}: it was built from "
+                                "an older include/pixelnerf_hip.h; rebuild it (__graft_entry__.build())")
     for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError here = header/library mismatch
+        fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     _lib = lib

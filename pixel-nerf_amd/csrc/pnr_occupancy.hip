@@ -3,7 +3,9 @@
 // object -- sigma at the points of util.gen_grid, src/util/util.py:93-110, as src/util/recon.py:43-66 evaluates it -- becomes a
 // bitfield of occupied cells (occupancy_build_kernel), rays are classified against it with a 3-D DDA (occupancy_clip_kernel), and the
 // caller renders the survivors only; a culled ray gets what src/render/nerf.py:178-182,223-249 composites from sigma == 0.
-// Geometry and semantics: include/pixelnerf_hip.h.  One owner thread per output word / ray, no atomics: the same bytes every run.
+// The rays that remain can also skip the network on their samples in empty cells: occupancy_mark_kernel classifies every sample,
+// compact_* gathers the kept ones into a list of one-sample rays, expand_* puts the network's answers back between zeros.
+// Geometry and semantics: include/pixelnerf_hip.h.  One owner thread per output word / ray / sample, no atomics: the same bytes every run.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -163,7 +165,112 @@ occupancy_clip_kernel(const float *__restrict__ rays, long long R, const uint32_
         tb[1] = fminf(far, t_exit + pad);
     }
 }
+
+// ---- per-sample skipping: mark the samples in occupied cells, compact them, put the network's answers back ----
+// One thread per sample, consecutive samples of a ray in consecutive lanes: the z reads are coalesced, the ray row is a broadcast.
+// The point is ray_point's (pnr_geom.h): o + z d, the product and the sum rounded separately (contraction is off here).
+__global__ void __launch_bounds__(OCC_THREADS)
+occupancy_mark_kernel(const float *__restrict__ rays, const float *__restrict__ z, int K, int N, const uint32_t *__restrict__ bits,
+                      const OccGrid g, uint8_t *__restrict__ keep) {
+    const long long t = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    if (t >= N) return;
+    const int s = (int)t;
+    const float *p = rays + (size_t)(s / K) * 8;
+    const float zz = z[s];
+    bool finite = occ_finite(zz), inside = true;
+    int idx[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float o = p[a], d = p[3 + a];
+        finite = finite && occ_finite(o) && occ_finite(d);
+        const float x = o + zz * d;
+        inside = inside && x >= g.c1[a] && x <= g.c2[a];
+        const float c = floorf((x - g.c1[a]) / g.h[a]);
+        idx[a] = (int)fminf(fmaxf(c, 0.f), (float)(g.n[a] - 2));  // (fmaxf drops a NaN: always a cell of the grid)
+    }
+    const long long cell = ((long long)idx[0] * (g.n[1] - 1) + idx[1]) * (g.n[2] - 1) + idx[2];
+    const bool occupied = inside && (bits[cell >> 5] >> (cell & 31) & 1u);
+    keep[s] = (uint8_t)(!finite || occupied);  // not classifiable: evaluate it
+}
 #pragma clang fp contract(fast)
+
+// Compaction, three launches in stream order.  A workgroup owns OCC_THREADS consecutive samples; no workgroup waits on another.
+// (1) kept samples per workgroup: one ballot per wave, the 4 wave counts added in wave order.
+__global__ void __launch_bounds__(OCC_THREADS)
+compact_count_kernel(const uint8_t *__restrict__ keep, int N, int *__restrict__ totals) {
+    __shared__ int wave_tot[OCC_THREADS / 64];
+    const long long s = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    const u64 m = __ballot(s < N && keep[s < N ? s : 0] != 0);
+    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int v = 0; v < OCC_THREADS / 64; ++v) tot += wave_tot[v];
+        totals[blockIdx.x] = tot;
+    }
+}
+
+// (2) exclusive scan of the totals, in place, by ONE workgroup that walks them OCC_THREADS at a time with a running carry; the grand
+// total is M
+__global__ void __launch_bounds__(OCC_THREADS)
+compact_scan_kernel(int *__restrict__ totals, int n_groups, int *__restrict__ count) {
+    __shared__ int wave_tot[OCC_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;  // (the same value in every thread)
+    for (int base = 0; base < n_groups; base += OCC_THREADS) {
+        const int i = base + threadIdx.x;
+        const int v = i < n_groups ? totals[i] : 0;
+        const int incl = wave_scan_add(v, lane);
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        int off = carry, all = 0;
+        for (int u = 0; u < OCC_THREADS / 64; ++u) {
+            if (u < wave) off += wave_tot[u];
+            all += wave_tot[u];
+        }
+        if (i < n_groups) totals[i] = off + incl - v;
+        carry += all;
+        __syncthreads();  // wave_tot is rewritten by the next round
+    }
+    if (threadIdx.x == 0) *count = carry;  // < 2^31 samples
+}
+
+// (3) the scatter: rank inside the wave from the ballot, the waves before it from LDS, the workgroups before it from the scan
+__global__ void __launch_bounds__(OCC_THREADS)
+compact_scatter_kernel(const uint8_t *__restrict__ keep, const float *__restrict__ rays, const float *__restrict__ z, int K, int N,
+                       const int *__restrict__ offsets, int32_t *__restrict__ index, float *__restrict__ rays_c, float *__restrict__ z_c) {
+    __shared__ int wave_tot[OCC_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long s = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    const bool k = s < N && keep[s < N ? s : 0] != 0;
+    const u64 m = __ballot(k);
+    if (lane == 0) wave_tot[wave] = __popcll(m);
+    __syncthreads();
+    if (!k) return;
+    int at = offsets[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int u = 0; u < wave; ++u) at += wave_tot[u];
+    index[at] = (int32_t)s;
+    z_c[at] = z[s];
+    const float4 *row = reinterpret_cast<const float4 *>(rays) + (size_t)(s / K) * 2;
+    float4 *out = reinterpret_cast<float4 *>(rays_c) + (size_t)at * 2;
+    out[0] = row[0];
+    out[1] = row[1];
+}
+
+__global__ void __launch_bounds__(OCC_THREADS)
+expand_zero_kernel(float4 *__restrict__ rgbsigma, long long N) {
+    const long long s = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    if (s < N) rgbsigma[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__global__ void __launch_bounds__(OCC_THREADS)
+expand_scatter_kernel(const int32_t *__restrict__ index, const float4 *__restrict__ rgbsigma_c, int M, long long N,
+                      float4 *__restrict__ rgbsigma) {
+    const long long m = (long long)blockIdx.x * OCC_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const long long s = index[m];
+    if (s >= 0 && s < N) rgbsigma[s] = rgbsigma_c[m];  // (a row outside the output is the caller's error: skipped)
+}
 
 static const char *occ_bad_dims(int nx, int ny, int nz) {
     if (nx < 2 || ny < 2 || nz < 2) return "every axis needs at least 2 grid points";
@@ -176,6 +283,23 @@ static int occ_fail(const char *entry, const char *why) {
     std::snprintf(msg, sizeof msg, "%s: %s", entry, why);
     return pnr_fail(PNR_E_INVALID, msg);  // (copies the text)
 }
+
+// the grid of the clip and the mark entry: c1 / c2 checked, h = (c2 - c1) / (n - 1) rounded once from fp64; nullptr when it is usable
+static const char *occ_grid(int nx, int ny, int nz, const float *c1, const float *c2, OccGrid &g) {
+    if (!c1 || !c2) return "c1 / c2 is null (host arrays of 3 floats)";
+    const int n[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(c1[a]) || !std::isfinite(c2[a]) || !(c1[a] < c2[a])) return "c1 / c2 must be finite with c1 < c2 on every axis";
+        g.c1[a] = c1[a];
+        g.c2[a] = c2[a];
+        g.n[a] = n[a];
+        g.h[a] = (float)(((double)c2[a] - (double)c1[a]) / (double)(n[a] - 1));
+        if (!(g.h[a] > 0.f) || !std::isfinite(g.h[a])) return "the cell size (c2 - c1) / (n - 1) is not a positive fp32 number";
+    }
+    return nullptr;
+}
+
+static bool occ_misaligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 }  // namespace pnr
 
@@ -205,19 +329,9 @@ extern "C" int pnr_occupancy_clip_rays(const float *rays, long long R, const uin
                                        const float *c2, float pad, float *t_bounds, int32_t *hit, void *stream) {
     if (const char *why = pnr::occ_bad_dims(nx, ny, nz)) return pnr::occ_fail("pnr_occupancy_clip_rays", why);
     if (R < 0) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: bad sizes");
-    if (!c1 || !c2) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: c1 / c2 is null (host arrays of 3 floats)");
     if (!(pad >= 0.f) || !std::isfinite(pad)) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: pad must be finite and >= 0");
     pnr::OccGrid g;
-    const int n[3] = {nx, ny, nz};
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(c1[a]) || !std::isfinite(c2[a]) || !(c1[a] < c2[a]))
-            return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: c1 / c2 must be finite with c1 < c2 on every axis");
-        g.c1[a] = c1[a];
-        g.c2[a] = c2[a];
-        g.n[a] = n[a];
-        g.h[a] = (float)(((double)c2[a] - (double)c1[a]) / (double)(n[a] - 1));
-        if (!(g.h[a] > 0.f) || !std::isfinite(g.h[a])) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: the cell size (c2 - c1) / (n - 1) is not a positive fp32 number");
-    }
+    if (const char *why = pnr::occ_grid(nx, ny, nz, c1, c2, g)) return pnr::occ_fail("pnr_occupancy_clip_rays", why);
     if (R == 0) return PNR_OK;
     if (!rays || !bits || !t_bounds || !hit) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_clip_rays: null argument");
     const long long blocks = (R + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS;
@@ -225,4 +339,62 @@ extern "C" int pnr_occupancy_clip_rays(const float *rays, long long R, const uin
     hipLaunchKernelGGL(pnr::occupancy_clip_kernel, dim3((unsigned)blocks), dim3(pnr::OCC_THREADS), 0, (hipStream_t)stream, rays, R, bits, g,
                        pad, t_bounds, hit);
     return pnr_check_launch("pnr_occupancy_clip_rays");
+}
+
+extern "C" int pnr_occupancy_mark_samples(const float *rays, const float *z, int R, int K, const uint32_t *bits, int nx, int ny, int nz,
+                                          const float *c1, const float *c2, uint8_t *keep, void *stream) {
+    if (const char *why = pnr::occ_bad_dims(nx, ny, nz)) return pnr::occ_fail("pnr_occupancy_mark_samples", why);
+    if (R < 0 || K < 1) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_mark_samples: bad sizes");
+    if ((long long)R * K >= (1LL << 31)) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_mark_samples: R * K must be below 2^31");
+    pnr::OccGrid g;
+    if (const char *why = pnr::occ_grid(nx, ny, nz, c1, c2, g)) return pnr::occ_fail("pnr_occupancy_mark_samples", why);
+    if (R == 0) return PNR_OK;
+    if (!rays || !z || !bits || !keep) return pnr_fail(PNR_E_INVALID, "pnr_occupancy_mark_samples: null argument");
+    const int N = R * K;
+    hipLaunchKernelGGL(pnr::occupancy_mark_kernel, dim3((unsigned)(((long long)N + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS)),
+                       dim3(pnr::OCC_THREADS), 0, (hipStream_t)stream, rays, z, K, N, bits, g, keep);
+    return pnr_check_launch("pnr_occupancy_mark_samples");
+}
+
+extern "C" size_t pnr_compact_samples_workspace_bytes(long long N) {
+    if (N <= 0 || N >= (1LL << 31)) return 0;
+    return (size_t)((N + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS) * sizeof(int);
+}
+
+extern "C" int pnr_compact_samples(const uint8_t *keep, const float *rays, const float *z, int R, int K, int32_t *index, float *rays_c,
+                                   float *z_c, int *count_dev, void *workspace, size_t workspace_bytes, void *stream) {
+    if (R < 0 || K < 1) return pnr_fail(PNR_E_INVALID, "pnr_compact_samples: bad sizes");
+    if ((long long)R * K >= (1LL << 31)) return pnr_fail(PNR_E_INVALID, "pnr_compact_samples: R * K must be below 2^31");
+    if (R == 0) return PNR_OK;
+    if (!keep || !rays || !z || !index || !rays_c || !z_c || !count_dev || !workspace)
+        return pnr_fail(PNR_E_INVALID, "pnr_compact_samples: null argument");
+    if (pnr::occ_misaligned16(rays) || pnr::occ_misaligned16(rays_c))
+        return pnr_fail(PNR_E_INVALID, "pnr_compact_samples: rays and rays_c must be 16-byte aligned");
+    const int N = R * K;
+    if (workspace_bytes < pnr_compact_samples_workspace_bytes(N) || (reinterpret_cast<uintptr_t>(workspace) & 3u))
+        return pnr_fail(PNR_E_INVALID, "pnr_compact_samples: workspace smaller than pnr_compact_samples_workspace_bytes(R * K), or not 4-byte aligned");
+    const int groups = (int)(((long long)N + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS);
+    int *totals = static_cast<int *>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pnr::compact_count_kernel, dim3((unsigned)groups), dim3(pnr::OCC_THREADS), 0, st, keep, N, totals);
+    hipLaunchKernelGGL(pnr::compact_scan_kernel, dim3(1), dim3(pnr::OCC_THREADS), 0, st, totals, groups, count_dev);
+    hipLaunchKernelGGL(pnr::compact_scatter_kernel, dim3((unsigned)groups), dim3(pnr::OCC_THREADS), 0, st, keep, rays, z, K, N,
+                       (const int *)totals, index, rays_c, z_c);
+    return pnr_check_launch("pnr_compact_samples");
+}
+
+extern "C" int pnr_expand_rgbsigma(const int32_t *index, const float *rgbsigma_c, int M, long long N, float *rgbsigma, void *stream) {
+    if (M < 0 || N < 0 || (long long)M > N) return pnr_fail(PNR_E_INVALID, "pnr_expand_rgbsigma: bad sizes (0 <= M <= N)");
+    if (N >= (1LL << 31)) return pnr_fail(PNR_E_INVALID, "pnr_expand_rgbsigma: N must be below 2^31");
+    if (N == 0) return PNR_OK;
+    if (!rgbsigma || (M > 0 && (!index || !rgbsigma_c))) return pnr_fail(PNR_E_INVALID, "pnr_expand_rgbsigma: null argument");
+    if (pnr::occ_misaligned16(rgbsigma) || (M > 0 && pnr::occ_misaligned16(rgbsigma_c)))
+        return pnr_fail(PNR_E_INVALID, "pnr_expand_rgbsigma: rgbsigma and rgbsigma_c must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pnr::expand_zero_kernel, dim3((unsigned)((N + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS)), dim3(pnr::OCC_THREADS), 0, st,
+                       reinterpret_cast<float4 *>(rgbsigma), N);
+    if (M > 0)
+        hipLaunchKernelGGL(pnr::expand_scatter_kernel, dim3((unsigned)((M + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS)), dim3(pnr::OCC_THREADS), 0,
+                           st, index, reinterpret_cast<const float4 *>(rgbsigma_c), M, N, reinterpret_cast<float4 *>(rgbsigma));
+    return pnr_check_launch("pnr_expand_rgbsigma");
 }

@@ -1140,6 +1140,91 @@ def occupancy_clip_rays(rays, bits, reso, c1, c2, pad=0.0):
     return t_bounds, hit
 
 
+def _check_grid_args(what, bits, reso, c1, c2, device):
+    """-> (nx, ny, nz) of an occupancy bitfield checked against its geometry (occupancy_clip_rays / occupancy_mark_samples)"""
+    lib = _lib.load()
+    if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
+        raise ValueError(f"{what}: c1, c2, reso must have 3 entries each")
+    nx, ny, nz = (int(r) for r in reso)
+    nbytes = lib.pnr_occupancy_bytes(nx, ny, nz)
+    if nbytes == 0:
+        raise ValueError(f"{what}: a grid needs at least 2 points per axis and fewer than 2^31 cells, got {(nx, ny, nz)}")
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or bits.dim() != 1 or bits.numel() != nbytes // 4:
+        raise ValueError(f"{what}: bits must be the ({nbytes // 4},) int32 tensor of occupancy_build for reso {(nx, ny, nz)}")
+    if bits.device != device:
+        raise ValueError(f"{what}: bits live on {bits.device}, the rays on {device}")
+    return nx, ny, nz
+
+
+def occupancy_mark_samples(rays, z, bits, reso, c1, c2):
+    """Samples against an occupancy bitfield (pnr_occupancy_mark_samples): rays (R,8), z (R,K) fp32 HIP tensors -> keep (R,K) uint8,
+    1 iff the point o + z d (separately rounded product and sum, the network kernels' own sample point) lies in the box [c1, c2]
+    and in an occupied cell; a point outside the box is empty; a sample with a non-finite z, origin or direction component is
+    kept.  No host synchronisation."""
+    lib = _lib.load()
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    z = _f32(z, "z", (R, None))
+    K = z.shape[1]
+    nx, ny, nz = _check_grid_args("occupancy_mark_samples", bits, reso, c1, c2, dev)
+    if K < 1 or R * K >= 2 ** 31:
+        raise ValueError(f"occupancy_mark_samples: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+    keep = torch.empty((R, K), dtype=torch.uint8, device=dev)
+    lo, hi = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in c2])
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_occupancy_mark_samples(_p(rays), _p(z), R, K, _p(bits.contiguous()), nx, ny, nz, lo, hi, _p(keep), _stream()),
+                   "pnr_occupancy_mark_samples")
+    return keep
+
+
+def compact_samples(keep, rays, z):
+    """Stable compaction of the marked samples (pnr_compact_samples): keep (R,K) uint8, rays (R,8), z (R,K) ->
+    (index (M,) int32 -- the ascending ids r K + k of the samples with keep != 0 --, rays_c (M,8) = rays[index // K], z_c (M,) =
+    z.flatten()[index], M as a Python int).  The tensors are sized to M: the count is read on the host, the ONE synchronisation
+    of a pass (they are the leading rows of R K-row allocations, which the kernels leave untouched beyond M)."""
+    lib = _lib.load()
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    z = _f32(z, "z", (R, None))
+    K = z.shape[1]
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or tuple(keep.shape) != (R, K) or keep.device != dev:
+        raise ValueError(f"compact_samples: keep must be the ({R},{K}) uint8 tensor of occupancy_mark_samples on {dev}")
+    if K < 1 or R * K >= 2 ** 31:
+        raise ValueError(f"compact_samples: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+    N = R * K
+    index = torch.empty((N,), dtype=torch.int32, device=dev)
+    rays_c = torch.empty((N, 8), dtype=torch.float32, device=dev)
+    z_c = torch.empty((N,), dtype=torch.float32, device=dev)
+    if N == 0:
+        return index, rays_c, z_c, 0
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    nbytes = lib.pnr_compact_samples_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_compact_samples(_p(keep.contiguous()), _p(rays), _p(z), R, K, _p(index), _p(rays_c), _p(z_c), _p(count), _p(ws),
+                                           nbytes, _stream()), "pnr_compact_samples")
+    M = int(count)  # the host synchronisation
+    return index[:M], rays_c[:M], z_c[:M], M
+
+
+def expand_rgbsigma(index, rgbsigma_c, N):
+    """The inverse placement (pnr_expand_rgbsigma): index (M,) int32 of compact_samples, rgbsigma_c (M,4) (None when M = 0) ->
+    rgbsigma (N,4): row index[m] = rgbsigma_c[m], every other row (0,0,0,0).  Every element is written."""
+    lib = _lib.load()
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or not index.is_cuda:
+        raise TypeError("expand_rgbsigma: index must be the 1-d int32 HIP tensor of compact_samples")
+    M, dev, N = index.shape[0], index.device, int(N)
+    if M > 0:
+        rgbsigma_c = _f32(rgbsigma_c, "rgbsigma_c", (M, 4))
+    if not M <= N < 2 ** 31:
+        raise ValueError(f"expand_rgbsigma: needs M <= N < 2^31, got M = {M}, N = {N}")
+    out = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_expand_rgbsigma(_p(index.contiguous()) if M else None, _p(rgbsigma_c) if M else None, M, N, _p(out), _stream()),
+                   "pnr_expand_rgbsigma")
+    return out
+
+
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):
     """philox_noise for a list of GLOBAL ray ids (pnr_philox_noise_ids): ray_ids (R,) int64 HIP tensor -- any order, repeats
     allowed, beyond 2^31 too -- -> the dict philox_noise returns, row r holding what the seeded renderer entries draw for ray

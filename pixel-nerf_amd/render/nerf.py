@@ -32,12 +32,12 @@ class _RenderWrapper(torch.nn.Module):
         self.renderer = renderer
         self.simple_output = simple_output
 
-    def forward(self, rays, want_weights=False, occupancy=None, tighten=False):
+    def forward(self, rays, want_weights=False, occupancy=None, tighten=False, skip_empty=False):
         if rays.shape[0] == 0:
             return (torch.zeros(0, 3, device=rays.device), torch.zeros(0, device=rays.device))
         with torch.profiler.record_function("render_par"):
             outputs = self.renderer(self.net, rays, want_weights=want_weights and not self.simple_output, occupancy=occupancy,
-                                    tighten=tighten)
+                                    tighten=tighten, skip_empty=skip_empty)
         if self.simple_output:
             if self.renderer.using_fine:
                 return outputs.fine.rgb, outputs.fine.depth
@@ -45,13 +45,14 @@ class _RenderWrapper(torch.nn.Module):
         return outputs.toDict()
 
     def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, views_per_call=None,
-                     _noise=None, occupancy=None, tighten=False):
+                     _noise=None, occupancy=None, tighten=False, skip_empty=False):
         """Images of the target views from their cameras, with depth normalisation and, given ground truth, PSNR and SSIM per
         view, all on the device (NeRFRenderer.render_views; the loop of eval/eval.py:247-331 as one call).  Inference only:
         runs under torch.no_grad()."""
         with torch.profiler.record_function("render_par"):
             return self.renderer.render_views(self.net, poses_c2w, W, H, focal, z_near, z_far, c=c, gt_rgb=gt_rgb, want_u8=want_u8,
-                                              views_per_call=views_per_call, _noise=_noise, occupancy=occupancy, tighten=tighten)
+                                              views_per_call=views_per_call, _noise=_noise, occupancy=occupancy, tighten=tighten,
+                                              skip_empty=skip_empty)
 
 
 class NeRFRenderer(torch.nn.Module):
@@ -66,6 +67,7 @@ class NeRFRenderer(torch.nn.Module):
         self._seed_override = None  # set by the multi-device wrapper: every shard of one call uses the same key
         self.ray_id_offset = 0  # placement of this call's rays inside a larger ray set (set by sharding wrappers)
         self.ray_id_stride = 0
+        self.last_skip_stats = None  # of the last call with skip_empty=True: {"coarse": (kept, total), "fine": (kept, total)} samples
         self.n_coarse, self.n_fine, self.n_fine_depth = n_coarse, n_fine, n_fine_depth
         self.noise_std, self.depth_std = noise_std, depth_std
         self.eval_batch_size = eval_batch_size
@@ -164,7 +166,7 @@ class NeRFRenderer(torch.nn.Module):
                 noise["n4"] = torch.randn(R, self.n_fine_depth, device=dev)
         return noise
 
-    def forward(self, model, rays, want_weights=False, _noise=None, occupancy=None, tighten=False):
+    def forward(self, model, rays, want_weights=False, _noise=None, occupancy=None, tighten=False, skip_empty=False):
         """src/render/nerf.py:251-303.
         :param model nerf model: (SB,B,3) points [+ viewdirs] -> (SB,B,4) rgb sigma
         :param rays [origins(3), directions(3), near, far] (SB,B,8)
@@ -175,15 +177,21 @@ class NeRFRenderer(torch.nn.Module):
         the rendered rays only, so the image is a different sample of the same distribution.  None: the call of the reference.
         :param tighten with `occupancy`: sample every rendered ray between its first and last occupied cell instead of [near, far]
         (the same number of samples over a shorter range: denser, so the image then differs from the dense render everywhere)
+        :param skip_empty with `occupancy` and a fused PixelNeRFNet: the rendered rays run the network only on the samples that
+        lie in an occupied cell; every other sample gets rgb sigma = 0.  The result is the dense render of those rays with sigma
+        forced to 0 in the cells the grid calls empty (so its quality is the grid's: reso, threshold, dilate) -- bit for bit at every
+        precision -- at two host synchronisations more per call (the kept samples of the coarse and of the fine pass).  `last_skip_stats` then holds
+        {"coarse": (kept, total), "fine": (kept, total)} samples.
         :return DotMap {coarse:{rgb (SB,B,3), depth (SB,B)[, weights (SB,B,K)]}, fine:{...}}"""
+        self._check_skip_args(skip_empty, occupancy)
         with torch.profiler.record_function("renderer_forward"):  # the reference's scope name (nerf.py:264)
             if occupancy is not None:
                 assert len(rays.shape) == 3
                 self._apply_sched()
                 flat = rays.reshape(-1, 8).float().contiguous()
-                self._check_culled_call(model, flat, rays.shape[0])
+                self._check_culled_call(model, flat, rays.shape[0], skip_empty)
                 res = self._render_culled(model, flat, self.ray_id_offset, occupancy, tighten, want_weights, _noise,
-                                          self._culled_seed(model, flat.device, _noise))[0]
+                                          self._culled_seed(model, flat.device, _noise), skip_empty)[0]
                 outputs = DotMap(coarse=self._format(res["coarse"], 1, want_weights))
                 if "fine" in res:
                     outputs.fine = self._format(res["fine"], 1, want_weights)
@@ -271,7 +279,12 @@ class NeRFRenderer(torch.nn.Module):
             or any(torch.is_tensor(t) and t.requires_grad for t in (model.poses, model.focal, model.c)))
 
     # ---- occupancy-grid culling (inference): render the rays that can hit something, fill in the rest ----
-    def _check_culled_call(self, model, rays, SB):
+    @staticmethod
+    def _check_skip_args(skip_empty, occupancy):
+        if skip_empty and occupancy is None:
+            raise ValueError("skip_empty=True needs `occupancy`: the OccupancyGrid that says which cells are empty")
+
+    def _check_culled_call(self, model, rays, SB, skip_empty=False):
         """the refusals of a call with `occupancy`; rays: the call's differentiable input (the rays, or the cameras of render_views)"""
         if SB != 1 or int(getattr(model, "num_objs", 1) or 1) != 1:
             raise ValueError(f"occupancy: an OccupancyGrid describes ONE object, the call has {max(SB, int(getattr(model, 'num_objs', 1) or 1))}; "
@@ -287,6 +300,14 @@ class NeRFRenderer(torch.nn.Module):
         if rays.is_cuda and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("occupancy: the number of rays that survive is read on the host to size the launch, which a "
                                       "HIP-graph capture cannot contain; capture the call without `occupancy`")
+        if skip_empty:
+            if not self._is_fused(model):
+                raise NotImplementedError("skip_empty: the samples in empty cells are skipped by the staged HIP pass of a fused PixelNeRFNet; "
+                                          "a generic model callable and a PixelNeRFNet on the composed (non-fused) path are not "
+                                          "implemented -- call without skip_empty")
+            if self.training and self.noise_std > 0.0:
+                raise NotImplementedError("skip_empty: noise_std > 0 in train mode is implemented on the differentiable path only")
+            self.last_skip_stats = {"coarse": (0, 0), "fine": (0, 0)}
 
     def _culled_seed(self, model, dev, given_noise):
         """the ONE Philox key of a culled call, taken exactly where the dense call takes its own (the generator advances the same
@@ -303,11 +324,12 @@ class NeRFRenderer(torch.nn.Module):
             out["weights"] = torch.zeros((R, K), dtype=torch.float32, device=dev)
         return out
 
-    def _render_culled(self, model, rays, first_id, occupancy, tighten, want_weights, given_noise, seed):
+    def _render_culled(self, model, rays, first_id, occupancy, tighten, want_weights, given_noise, seed, skip_empty=False):
         """The shared body of forward(occupancy=) and render_views(occupancy=): rays (R,8) of ONE object whose row r has the global
         ray id first_id + r.  Clip against the grid, gather the rays that hit, render them through the ordinary forward with the
         draws of their global ids (seed; given_noise is cut to the hit rows), scatter into outputs pre-filled with the empty-ray
-        value.  One host synchronisation: the number of hit rays.
+        value.  One host synchronisation: the number of hit rays.  skip_empty: the hit rays go through the staged pass of
+        _skip_launch instead (two more synchronisations); its sample counts are ADDED to last_skip_stats.
         -> ({"coarse": {...}[, "fine": {...}]} flat tensors, hit (R,) bool, the number of hit rays)"""
         R, dev = rays.shape[0], rays.device
         Kc = self.n_coarse
@@ -330,7 +352,16 @@ class NeRFRenderer(torch.nn.Module):
             noise = ops.philox_noise_ids(idx + int(first_id), Kc, Kf, Kfd, seed)
         else:
             noise = None  # torch draws, for the rendered rays only
-        out = self._forward(model, sub.unsqueeze(0), want_weights, noise)
+        if skip_empty:
+            model._check_supported()
+            if noise is None:
+                noise = self._draw_noise(sub.shape[0], dev)
+            launch = self._skip_launch(model, sub, Kf, Kfd, noise, want_weights, occupancy)
+            out = self._fused_inference(model, Kf, 0, False, noise, noise, launch, lambda: sub.unsqueeze(0))
+            self.last_skip_stats = {name: (kept + launch.stats[name][0], total + launch.stats[name][1])
+                                    for name, (kept, total) in self.last_skip_stats.items()}
+        else:
+            out = self._forward(model, sub.unsqueeze(0), want_weights, noise)
         for name, full in res.items():
             part = out[name]
             for key, t in full.items():
@@ -343,6 +374,61 @@ class NeRFRenderer(torch.nn.Module):
             return ops.render_forward(model.scene(), pk_c, pk_f, rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
                                       white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights, tables=tables,
                                       seed=seed, ray_id_offset=self.ray_id_offset, ray_id_stride=self.ray_id_stride)
+        return launch
+
+    def _skip_launch(self, model, rays, Kf, Kfd, noise, want_weights, occupancy):
+        """the launch of _fused_inference for skip_empty: the stages of the one-call renderer as separate C calls, the network on
+        the compacted list of the samples in occupied cells (one-sample rays: their world point is o + z d rounded as in a dense
+        launch, and eval_kernel / the fp32 path give a point the same bits wherever it stands in the launch), zeros elsewhere.
+        "f16x3": eval_split_kernel blends the fp32 table rows of an even and of an odd point of the launch with differently
+        ordered roundings (its lookup handles two points per step; the compiler contracted w0 v0 + w1 v1 into an FMA onto the
+        first product for one of them and onto the second for the other), so there a point's last places depend on the PARITY of
+        its place -- and on nothing else.  The compacted list therefore carries whole pairs (2j, 2j+1) of the dense launch, a
+        kept sample's empty partner included: every kept sample stands at a place of its own parity, and the partner's output
+        is dropped again.  At most one more point per end of a run of kept samples."""
+        R, dev = rays.shape[0], rays.device
+        pairs = model._effective_precision() == "f16x3"
+
+        def network(packed, tables, z, slot, name):
+            N = z.numel()
+            keep = occupancy.mark_samples(rays, z)
+            run = keep  # the samples the network runs on
+            if pairs:
+                flat = keep.reshape(-1)
+                p = flat[:N - N % 2].view(-1, 2)
+                run = torch.cat([(p | p.flip(1)).reshape(-1), flat[N - N % 2:]]).view_as(keep)
+                n_kept = (keep != 0).sum()
+            index, rays_c, z_c, M = ops.compact_samples(run, rays, z)  # (the pass's host synchronisation)
+            part = None
+            if M > 0:
+                ops.saturation_guard_slot(dev, slot)  # (when the fp16-range guard is armed for this call: word 0 coarse, 1 fine)
+                part = ops.eval_ray_samples(model.scene(), packed, rays_c, z_c.unsqueeze(1), tables).reshape(M, 4)
+            rgbsigma = ops.expand_rgbsigma(index, part, N).reshape(R, z.shape[1], 4)
+            if pairs:
+                rgbsigma = torch.where(keep.unsqueeze(-1) != 0, rgbsigma, torch.zeros((), device=dev))
+                M = int(n_kept) if M > 0 else 0  # (already on its way: the stream was drained for the count above)
+            launch.stats[name] = (M, N)
+            return rgbsigma
+
+        def launch(pk_c, pk_f, tables, seed):
+            tc, tf = tables if tables is not None else (None, None)
+            launch.stats = {"coarse": (0, 0), "fine": (0, 0)}  # (kept, total) samples of THIS round (stream_scale="auto" may render twice)
+            z_c = ops.sample_coarse(rays, noise["u1"], self.lindisp)
+            w_c, rgb_c, depth_c = ops.composite(rays, z_c, network(pk_c, tc, z_c, 0, "coarse"), self.white_bkgd, True)
+            ret = {"coarse": {"rgb": rgb_c, "depth": depth_c}}
+            if want_weights:
+                ret["coarse"]["weights"] = w_c
+            if Kf > 0:
+                z_f = ops.sample_fine(rays, w_c, depth_c, z_c, noise.get("u2") if Kf > Kfd else None, noise.get("u3") if Kf > Kfd else None,
+                                      noise.get("n4") if Kfd > 0 else None, self.depth_std, self.lindisp)
+                # mlp_fine is None: the coarse network on every kept sample of the fine pass (the one-call renderer merges the
+                # coarse pass's outputs instead -- the same bits)
+                fine = (pk_f, tf, 1) if pk_f is not None else (pk_c, tc, 0)
+                w_f, rgb_f, depth_f = ops.composite(rays, z_f, network(fine[0], fine[1], z_f, fine[2], "fine"), self.white_bkgd, want_weights)
+                ret["fine"] = {"rgb": rgb_f, "depth": depth_f}
+                if want_weights:
+                    ret["fine"]["weights"] = w_f
+            return ret
         return launch
 
     def _fused_inference(self, model, Kf, seed, seeded, given_noise, noise, launch, calib_rays):
@@ -380,7 +466,7 @@ class NeRFRenderer(torch.nn.Module):
 
     # ---- cameras -> images ----
     def render_views(self, model, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False,
-                     views_per_call=None, _noise=None, occupancy=None, tighten=False):
+                     views_per_call=None, _noise=None, occupancy=None, tighten=False, skip_empty=False):
         """Every pixel of the target views from their cameras, with the evaluation epilogue on the device: what
         eval/eval.py:247-331 does per object (util.gen_rays, render_par over ray batches, clamp, depth normalisation, PSNR and
         SSIM per view) as one call.  An INFERENCE entry: it runs under torch.no_grad() whatever the caller's mode.
@@ -400,13 +486,16 @@ class NeRFRenderer(torch.nn.Module):
         (a host int); every other pixel holds the background (rgb 0, or 1 with white_bkgd; depth 0), and the epilogue (depth_norm,
         rgb_u8, psnr, ssim) runs on the full image as always.  With rng="philox" the pixels of `hit` have the bits of the call
         without `occupancy` under the same torch.manual_seed.  One host synchronisation per group of views.
-        :param tighten with `occupancy`: sample the rendered rays between their first and last occupied cell (see forward)"""
+        :param tighten with `occupancy`: sample the rendered rays between their first and last occupied cell (see forward)
+        :param skip_empty with `occupancy`: run the network only on the samples in occupied cells (see forward); `last_skip_stats`
+        sums over the groups of views.  Two more host synchronisations per group of views."""
+        self._check_skip_args(skip_empty, occupancy)
         with torch.no_grad(), torch.profiler.record_function("renderer_render_views"):
             return self._render_views(model, poses_c2w, int(W), int(H), focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise,
-                                      occupancy, tighten)
+                                      occupancy, tighten, skip_empty)
 
     def _render_views(self, model, poses, W, H, focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise, occupancy=None,
-                      tighten=False):
+                      tighten=False, skip_empty=False):
         from .. import util
         self._apply_sched()
         if poses.dim() == 3:
@@ -432,7 +521,8 @@ class NeRFRenderer(torch.nn.Module):
                 and not torch.cuda.is_current_stream_capturing() and not (self.training and self.noise_std > 0.0))
         hit = None
         if occupancy is not None:
-            rgb, depth, hit = self._render_views_culled(model, poses, W, H, focal, z_near, z_far, c, views_per_call, _noise, occupancy, tighten)
+            rgb, depth, hit = self._render_views_culled(model, poses, W, H, focal, z_near, z_far, c, views_per_call, _noise, occupancy, tighten,
+                                                        skip_empty)
         elif not fast:
             # a generic model callable, a composed-path PixelNeRFNet, the exact fp32 path, a capture in progress: the rays, then forward
             rays = util.gen_rays(flat, W, H, focal, z_near, z_far, c).reshape(SB, -1, 8)
@@ -473,13 +563,14 @@ class NeRFRenderer(torch.nn.Module):
             ret.psnr, ret.ssim = ep["psnr"].reshape(SB, NVt), ep["ssim"].reshape(SB, NVt)
         return ret
 
-    def _render_views_culled(self, model, poses, W, H, focal, z_near, z_far, c, views_per_call, given_noise, occupancy, tighten):
+    def _render_views_culled(self, model, poses, W, H, focal, z_near, z_far, c, views_per_call, given_noise, occupancy, tighten,
+                             skip_empty=False):
         """render_views(occupancy=): the rays of every group of views (all views without views_per_call) through _render_culled,
         under ONE key; ray id = pixel index in the (NVt,H,W) order.  -> (rgb (R,3), depth (R,), (hit (R,) bool, n_hit))"""
         SB, NVt = poses.shape[:2]
         HW = H * W
         flat = poses.reshape(-1, 4, 4).float().contiguous()
-        self._check_culled_call(model, flat, SB)
+        self._check_culled_call(model, flat, SB, skip_empty)
         seed = self._culled_seed(model, flat.device, given_noise)
         k = NVt if views_per_call is None else min(int(views_per_call), NVt)
         parts, n_hit = [], 0
@@ -487,7 +578,7 @@ class NeRFRenderer(torch.nn.Module):
             v1 = min(v0 + k, NVt)
             rays = ops.gen_rays(flat[v0:v1].contiguous(), W, H, focal, z_near, z_far, c).reshape(-1, 8)
             part = given_noise if given_noise is None else {n: t[v0 * HW:v1 * HW] for n, t in given_noise.items()}
-            res, hit, n = self._render_culled(model, rays, v0 * HW, occupancy, tighten, False, part, seed)
+            res, hit, n = self._render_culled(model, rays, v0 * HW, occupancy, tighten, False, part, seed, skip_empty)
             last = res["fine"] if "fine" in res else res["coarse"]
             parts.append((last["rgb"], last["depth"], hit))
             n_hit += n

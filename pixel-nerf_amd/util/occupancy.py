@@ -56,6 +56,12 @@ class OccupancyGrid:
         t_bounds, hit = ops.occupancy_clip_rays(rays.reshape(-1, 8).float(), self.bits, self.reso, self.c1, self.c2, pad)
         return t_bounds.reshape(*lead, 2), hit.reshape(lead)
 
+    def mark_samples(self, rays, z):
+        """rays (R,8), z (R,K) on the grid's device -> keep (R,K) uint8: 1 iff the sample o + z d lies in an occupied cell of the
+        grid (outside the box: 0; not classifiable: 1); ops.occupancy_mark_samples"""
+        from .. import ops
+        return ops.occupancy_mark_samples(rays, z, self.bits, self.reso, self.c1, self.c2)
+
     @property
     def n_cells(self):
         return (self.reso[0] - 1) * (self.reso[1] - 1) * (self.reso[2] - 1)

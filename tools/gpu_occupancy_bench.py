@@ -10,6 +10,10 @@ Grids: OccupancyGrid.from_model at 128^3 over [-1,1]^3, dilate 1, with the refer
 threshold and with a tenth of it; and a FULL grid (every cell occupied), whose culled render does all the dense render's work plus
 the culling machinery -- its excess over the dense render is the overhead at a 100 % hit fraction.
 
+The `sparse` row is the culled call with skip_empty=True: the network runs only on the samples in occupied cells (kept share per
+pass from NeRFRenderer.last_skip_stats; psnr_all_sparse against the dense image of the same seed), and skip_machinery_ms is mark +
+compact + expand alone on the hit rays, once at the coarse and once at the fine pass's shape (stratified stand-in positions).
+
 Timing: dense and culled calls ALTERNATE in one process after warm-up, every call between two device events ended by a device
 synchronise; median and min of REPS.  Reported per grid: hit fraction, ms per call dense / culled / culled with tighten, the
 expectation dense x hit fraction + clip + gather/scatter, PSNR of the culled image against the dense one over all pixels and over
@@ -150,20 +154,26 @@ def main():
     out["grids"] = {}
     for name, occ in grids.items():
         culled, tight = render(occupancy=occ), render(occupancy=occ, tighten=True)
+        sparse = render(occupancy=occ, skip_empty=True)
+        skip = dict(rend.last_skip_stats)
         hit = culled.hit
         g = {"occupied_fraction": round(occ.occupied_fraction, 5), "hit_fraction": round(culled.n_hit / hit.numel(), 5),
              "kept_pixels_bit_equal": bool(torch.equal(culled.rgb[hit], dense_img.rgb[hit])),
              "psnr_all": psnr(culled.rgb, dense_img.rgb), "psnr_missed": psnr(culled.rgb, dense_img.rgb, ~hit),
              "psnr_all_tighten": psnr(tight.rgb, dense_img.rgb), "psnr_missed_tighten": psnr(tight.rgb, dense_img.rgb, ~hit),
-             "max_abs_missed": float((culled.rgb - dense_img.rgb)[~hit].abs().max()) if bool((~hit).any()) else None}
+             "max_abs_missed": float((culled.rgb - dense_img.rgb)[~hit].abs().max()) if bool((~hit).any()) else None,
+             "psnr_all_sparse": psnr(sparse.rgb, dense_img.rgb), "psnr_sparse_vs_culled": psnr(sparse.rgb, culled.rgb),
+             "kept_share_coarse": round(skip["coarse"][0] / max(skip["coarse"][1], 1), 5),
+             "kept_share_fine": round(skip["fine"][0] / max(skip["fine"][1], 1), 5), "kept_samples": [skip["coarse"], skip["fine"]]}
         if not args.trace_only:
-            td, tc, tt = [], [], []
-            for i in range(REPS + WARMUP):  # dense / culled / tightened alternate
+            td, tc, tt, tsp = [], [], [], []
+            for i in range(REPS + WARMUP):  # dense / culled / tightened / sparse alternate
                 a = timed(render)[0]
                 b = timed(lambda: render(occupancy=occ))[0]
                 c = timed(lambda: render(occupancy=occ, tighten=True))[0]
+                d = timed(lambda: render(occupancy=occ, skip_empty=True))[0]
                 if i >= WARMUP:
-                    td.append(a), tc.append(b), tt.append(c)
+                    td.append(a), tc.append(b), tt.append(c), tsp.append(d)
             # gather / scatter of the hit rows alone: index_select of the rays + index_copy_ of rgb and depth (+ the noise tensors' draw)
             idx = torch.nonzero(hit.reshape(-1)).flatten()
             full_rgb, full_d = torch.ones((rays.shape[0], 3), device=dev), torch.zeros((rays.shape[0],), device=dev)
@@ -176,7 +186,19 @@ def main():
                 full_rgb.index_copy_(0, idx, part_rgb)
                 full_d.index_copy_(0, idx, part_d)
             tp = [timed(plumbing)[0] for _ in range(REPS + WARMUP)][WARMUP:]
-            g.update(dense_ms=stats(td), culled_ms=stats(tc), tighten_ms=stats(tt), gather_noise_scatter_ms=stats(tp))
+            # mark + compact + expand alone (each pass's host read of the count included), on the hit rays at both passes' shapes
+            sub = rays.index_select(0, idx)
+            z_pass = [ops.sample_coarse(sub, torch.rand((idx.numel(), k), device=dev)) for k in (KC, KC + KF)] if idx.numel() else []
+
+            def machinery():
+                for z in z_pass:
+                    index, _, _, m = ops.compact_samples(occ.mark_samples(sub, z), sub, z)
+                    ops.expand_rgbsigma(index, torch.zeros((m, 4), device=dev) if m else None, z.numel())
+            tm = [timed(machinery)[0] for _ in range(REPS + WARMUP)][WARMUP:]
+            g.update(dense_ms=stats(td), culled_ms=stats(tc), tighten_ms=stats(tt), sparse_ms=stats(tsp), gather_noise_scatter_ms=stats(tp),
+                     skip_machinery_ms=stats(tm))
+            g["speedup_sparse_vs_dense"] = round(g["dense_ms"][0] / g["sparse_ms"][0], 3)
+            g["speedup_sparse_vs_culled"] = round(g["culled_ms"][0] / g["sparse_ms"][0], 3)
             expect = g["dense_ms"][0] * g["hit_fraction"] + out["clip_rays_ms"][0] + out["gen_rays_ms"][0] + g["gather_noise_scatter_ms"][0]
             g["expected_ms"] = round(expect, 3)
             g["overhead_ms"] = round(g["culled_ms"][0] - expect, 3)
