@@ -778,6 +778,43 @@ int pnr_marching_cubes_emit(const float *field, int nx, int ny, int nz, float is
                             const void *workspace, float *vertices, int *triangles, void *stream);
 int pnr_marching_cubes_tables(int *edge_mask /*host, 256*/, int *tri /*host, 256*16*/);
 
+/* ---- finishing a mesh: floater removal and vertex normals (added within ABI rev 12: no struct or argument list changed; ---
+ * nothing in the reference corresponds: src/util/recon.py:68-106 meshes whatever the grid holds, writes bare vertices) ---
+ * pnr_grid_components: the connected components of the inside voxels of a density grid.  field (nx,ny,nz) fp32,
+ * C-contiguous, x the slowest axis (sigmas.view(*reso)).
+ *   inside  : a voxel is inside iff its value is finite and > threshold -- the mesher's rule above: == threshold and
+ *             NaN / +-inf are outside.
+ *   joined  : 6-connectivity, the grid edges.  pnr_marching_cubes_* puts a vertex exactly on the edges whose ends differ
+ *             under this rule, so two voxels are in one component iff the mesher joins them without a surface between.
+ *   labels  : (nx,ny,nz) int32.  -1 outside; inside, the SMALLEST linear index (i ny + j) nz + k among the voxels of the
+ *             voxel's component.  That makes the answer unique: the same bytes on every run, whatever the scheduling.
+ *   sizes   : nullable; int32, one entry per voxel, written in full: the component's voxel count at the entry of its
+ *             smallest index, 0 everywhere else (integer atomic adds, which commute exactly).
+ *   counts_dev : nullable; 2 ints, device: [n_inside, n_components].
+ * A lock-free union-find over `labels` in three launches in stream order (init, union, flatten; the two invariants that
+ * bound every loop are stated in csrc/pnr_meshfinish.hip); no workspace, no workgroup waits on another.
+ * PNR_E_INVALID: n < 1 on an axis (so a grid always has a voxel), nx ny nz >= 2^31, a NaN threshold (+-inf are
+ * ordinary: nothing / every finite value is inside), a null field / labels. */
+int pnr_grid_components(const float *field, int nx, int ny, int nz, float threshold, int *labels,
+                        int *sizes /*nullable*/, int *counts_dev /*nullable, 2 ints*/, void *stream);
+/* pnr_grid_normals: the field's gradient at mesh vertices, as unit normals; one thread per vertex, no atomics: the same
+ * bytes on every run.  vertices (V,3) in world coordinates, as pnr_marching_cubes_emit wrote them with the same c1 and
+ * scale (HOST arrays of 3 floats); normals (V,3).
+ *   index coordinates : p = (v - c1) / scale per axis, clamped to [0, n - 1]; the cell is floor(p), clamped to n - 2;
+ *                       the position in the cell is t = p - cell.
+ *   grid gradient     : per axis the central difference (f[i+1] - f[i-1]) / 2, at the border the one-sided difference
+ *                       f[1] - f[0] / f[n-1] - f[n-2].
+ *   at the vertex     : the trilinear blend of the cell's eight grid-point gradients, a + t (b - a) along x, then y, then
+ *                       z; component a is then divided by scale[a] (world units: the grid may be anisotropic, and
+ *                       recon.marching_cubes(align_to_grid=False) deliberately uses the reference's (c2 - c1) / reso).
+ *   normal            : -g / |g| -- from inside (high sigma) to outside, the direction the mesher's winding gives
+ *                       (v1 - v0) x (v2 - v0); (0,0,0) where g is zero or not finite.
+ * Separately rounded fp32 operations (no contraction); the norm and the final quotient go through fp64.
+ * PNR_E_INVALID: n < 2 on an axis, nx ny nz >= 2^31, a zero or non-finite scale, a non-finite c1, V < 0, a null
+ * pointer with V > 0.  V = 0: no-op. */
+int pnr_grid_normals(const float *field, int nx, int ny, int nz, const float *c1 /*host*/, const float *scale /*host*/,
+                     const float *vertices, long long V, float *normals, void *stream);
+
 /* ---- occupancy-grid ray culling (inference; nothing in the reference corresponds: it renders every ray) --------
  * A density grid of one encoded object -- sigma at the points of util.gen_grid (src/util/util.py:93-110), the grid
  * src/util/recon.py:43-66 evaluates -- becomes a bitfield of occupied CELLS; rays are classified against it and only

@@ -1091,6 +1091,48 @@ def marching_cubes(field, iso, c1=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0), check_
     return vertices, triangles
 
 
+def grid_components(field, threshold, want_sizes=True):
+    """The connected components of a density grid's inside voxels (pnr_grid_components; semantics in include/pixelnerf_hip.h).
+    field (nx,ny,nz) fp32 HIP tensor; a voxel is inside iff finite and > threshold (the mesher's rule), joined along the grid
+    edges (6-connectivity).  -> (labels (nx,ny,nz) int32: -1 outside, else the smallest linear index (i ny + j) nz + k of the
+    voxel's component; sizes (nx ny nz,) int32: the component's voxel count at that index, 0 elsewhere -- None without want_sizes;
+    counts (2,) int32 = [n_inside, n_components]), all on the field's device; no host synchronisation, the same bytes on every call."""
+    lib = _lib.load()
+    field = _f32(field, "field", (None, None, None))
+    nx, ny, nz = field.shape
+    if min(nx, ny, nz) < 1 or nx * ny * nz >= 2 ** 31:
+        raise ValueError(f"grid_components: a grid needs at least 1 point per axis and fewer than 2^31 points, got {(nx, ny, nz)}")
+    dev = field.device
+    labels = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+    sizes = torch.empty((nx * ny * nz,), dtype=torch.int32, device=dev) if want_sizes else None
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_grid_components(_p(field), nx, ny, nz, float(threshold), _p(labels), _p(sizes), _p(counts), _stream()),
+                   "pnr_grid_components")
+    return labels, sizes, counts
+
+
+def grid_normals(field, vertices, c1, scale):
+    """Unit normals at mesh vertices from the gradient of the grid the mesh was cut from (pnr_grid_normals; the formula in
+    include/pixelnerf_hip.h).  field (nx,ny,nz) fp32 HIP tensor, vertices (V,3) fp32 in world coordinates as ops.marching_cubes
+    wrote them with the same c1 and scale.  -> (V,3) float32 on the field's device: -grad / |grad| (from inside to outside, the
+    side the mesher's triangles face), (0,0,0) where the gradient is zero or not finite; the same bytes on every call."""
+    lib = _lib.load()
+    field = _f32(field, "field", (None, None, None))
+    vertices = _f32(vertices, "vertices", (None, 3))
+    if vertices.device != field.device:
+        raise ValueError(f"grid_normals: the vertices live on {vertices.device}, the field on {field.device}")
+    if len(c1) != 3 or len(scale) != 3:
+        raise ValueError("grid_normals: c1, scale must have 3 entries each")
+    nx, ny, nz = field.shape
+    normals = torch.empty_like(vertices)
+    lo, sc = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in scale])
+    with torch.cuda.device(field.device):
+        _lib.check(lib.pnr_grid_normals(_p(field), nx, ny, nz, lo, sc, _p(vertices), vertices.shape[0], _p(normals), _stream()),
+                   "pnr_grid_normals")
+    return normals
+
+
 def occupancy_build(field, threshold, dilate=1):
     """A density grid as a bitfield of occupied cells (pnr_occupancy_build; geometry and semantics in include/pixelnerf_hip.h).
     field (nx,ny,nz) fp32 HIP tensor -- sigma at the points of ops.gen_grid_points.  A cell is occupied iff a cell with a corner

@@ -14,7 +14,8 @@ import torch
 class OccupancyGrid:
     """bits: (ceil(cells / 32),) int32 words on the device (cell (i,j,k) = bit (index & 31) of word (index >> 5), index =
     (i (ny-1) + j)(nz-1) + k); reso: grid POINTS per axis (cells: reso - 1); c1, c2: corners of the grid; threshold, dilate: what
-    the bits were built with; n_occupied: 0-d int32 device tensor (`occupied_fraction` reads it: one host synchronisation)."""
+    the bits were built with; n_occupied: 0-d int32 device tensor (`occupied_fraction` reads it: one host synchronisation);
+    info: None, or util.recon.remove_floaters' dict when the grid was built with keep_largest / min_voxels."""
 
     def __init__(self, bits, reso, c1, c2, threshold, dilate, n_occupied):
         reso, c1, c2, words = _check_geometry(reso, c1, c2, dilate)
@@ -22,30 +23,43 @@ class OccupancyGrid:
             raise ValueError(f"OccupancyGrid: bits must be the ({words},) int32 tensor of ops.occupancy_build for reso {reso}")
         self.bits, self.reso, self.c1, self.c2 = bits, reso, c1, c2
         self.threshold, self.dilate, self.n_occupied = float(threshold), int(dilate), n_occupied
+        self.info = None
 
     @classmethod
-    def from_density(cls, field, c1, c2, threshold, dilate=1):
+    def from_density(cls, field, c1, c2, threshold, dilate=1, keep_largest=None, min_voxels=None):
         """field (nx,ny,nz) fp32 HIP tensor: sigma at the points of ops.gen_grid_points(c1, c2, (nx,ny,nz)).  A cell is occupied
-        iff a cell with a corner > threshold (or a non-finite corner) lies within Chebyshev distance `dilate`."""
+        iff a cell with a corner > threshold (or a non-finite corner) lies within Chebyshev distance `dilate`.
+        keep_largest / min_voxels (both None: off) ask for "the object only": the connected components of the grid POINTS
+        > threshold are taken BEFORE dilation (util.recon.remove_floaters: a component is kept iff it has at least min_voxels
+        points AND is among the keep_largest biggest), the points of a dropped component are set to `threshold`, then the build
+        above runs; `info` carries remove_floaters' counts.  Non-finite points are outside for the labelling and are left
+        untouched: the build still counts them as occupied, culling keeps erring towards rendering.  This CHANGES THE IMAGE
+        wherever the dropped haze was visible -- that is the point of asking for it; without the two arguments a culled render
+        stays exact where kept."""
         from .. import ops
+        from . import recon
         if not isinstance(field, torch.Tensor) or field.dim() != 3:
             raise ValueError("OccupancyGrid.from_density: field must be a (nx,ny,nz) tensor")
         _check_geometry(field.shape, c1, c2, dilate)  # (before any device work)
+        field, info = recon.remove_floaters(field, threshold, keep_largest=keep_largest, min_voxels=min_voxels)
         bits, count = ops.occupancy_build(field, threshold, dilate)
-        return cls(bits, field.shape, c1, c2, threshold, dilate, count)
+        grid = cls(bits, field.shape, c1, c2, threshold, dilate, count)
+        grid.info = info
+        return grid
 
     @classmethod
-    def from_model(cls, net, c1, c2, reso, threshold, dilate=1, eval_batch_size=100000):
+    def from_model(cls, net, c1, c2, reso, threshold, dilate=1, eval_batch_size=100000, keep_largest=None, min_voxels=None):
         """The grid of an encoded object from its networks: the field is the element-wise MAXIMUM of the coarse and the fine
         network's sigma (the coarse pass decides where the fine samples go, the fine pass decides the pixel; the coarse network's
         alone when net.mlp_fine is None), evaluated exactly as util.recon.marching_cubes evaluates its field (recon.density_grid:
         fake view directions with their warning, (1,N,3) calls, ONE encoded object, train / eval flag restored).
-        threshold: a sigma, e.g. the reference's iso-level 50 (src/util/recon.py:17) or a fraction of it."""
+        threshold: a sigma, e.g. the reference's iso-level 50 (src/util/recon.py:17) or a fraction of it.
+        keep_largest / min_voxels: as from_density (drops the haze's components; changes the image where it was visible)."""
         from . import recon
         passes = (True, False) if getattr(net, "mlp_fine", None) is not None else (True,)
         sigmas, reso = recon.density_grid(net, c1, c2, reso, coarse=passes, eval_batch_size=eval_batch_size,
                                           what="OccupancyGrid.from_model")
-        return cls.from_density(sigmas.view(*reso), c1, c2, threshold, dilate)
+        return cls.from_density(sigmas.view(*reso), c1, c2, threshold, dilate, keep_largest=keep_largest, min_voxels=min_voxels)
 
     def clip_rays(self, rays, pad=0.0):
         """rays (...,8) on the grid's device -> (t_bounds (...,2) fp32, hit (...) int32); ops.occupancy_clip_rays"""
