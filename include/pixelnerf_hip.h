@@ -360,7 +360,9 @@ size_t pnr_camera_backward_workspace_bytes(int R, int K, int rays_per_obj, int N
 /* The sampling part of that reduction alone, for renderers around an arbitrary model (points built by the caller):
  * dz (R,K) = dL/d(sample positions) -> d_rays (R,8) with columns 0..5 zero, near / far as above (z = near (1-s) + far s,
  * lindisp: 1/z linear in s, nerf.py:98-148; the depth samples at `ranks` only where their clamp is active,
- * nerf.py:157-160), plus d_far (R) (nullable).  Nullable: ranks (with n4, depth_c, Kfd), d_far. */
+ * nerf.py:157-160), plus d_far (R) (nullable).  A ray with near == far has every z equal to both, so s cannot be recovered
+ * from z: each sample's dz goes half to near and half to far (d near + d far = sum dz, exact for both maps; the same in
+ * pnr_camera_backward).  Nullable: ranks (with n4, depth_c, Kfd), d_far. */
 int pnr_sample_bounds_backward(const float *rays, const float *z, const float *dz, int R, int K, int lindisp,
                                const int *ranks, const float *n4, int Kfd, const float *depth_c, float depth_std,
                                const float *d_far, float *d_rays, void *stream);

@@ -12,8 +12,9 @@
 //                         through transposing LDS reads), dw_reduce_kernel sums the row slices.
 //   dw_split_wide_kernel  the same at split-operand (fp32-class) precision: (head | tail) f16 operand rows, three
 //                         MFMAs per product -- the weight gradients of the fused fp32-class training path.
-//   composite_bwd_kernel  backward of the alpha compositing (nerf.py:223-249), wavefront per ray.
-//                         also emits dL/dz through the deltas and depth = sum w z.
+//   composite_bwd_kernel  backward of the alpha compositing (nerf.py:223-249), wavefront per ray: the suffix sums by a
+//                         reverse scan of affine maps (no division, no difference of sums).
+//                         also emits dL/dz through the deltas and depth = sum w z, and dL/dfar through the last delta.
 //   latent_scatter_*      d(interpolated latent) -> d(feature grid): bilinear scatter-add (small grids: an fp64
 //                         slab in LDS per (image, channel slice) fed per ray segment; large: global atomics).
 //   position_bwd_kernel   dL/dz through the network inputs (positional code, projection, bilinear
@@ -745,65 +746,38 @@ __global__ void dw_reduce_kernel(const DwJobs jobs, const float *__restrict__ pa
 // ---------------------------------------------------------------- compositing backward
 constexpr int CW = 4;  // wavefronts per block
 
-// w_i = a_i T_i, T_i = prod_{j<i} (1 - a_j + 1e-10), a_i = 1 - exp(-delta_i relu(sigma_i))
+// w_i = a_i T_i, T_i = prod_{j<i} tf_j, tf_j = 1 - a_j + 1e-10, a_i = 1 - exp(-delta_i relu(sigma_i))
 // g_i = dL/dw_i = d_rgb.c_i + d_depth z_i + d_w_i - [white] sum(d_rgb)
-// dL/da_i = g_i T_i - (sum_{j>i} g_j w_j) / (1 - a_i + 1e-10)
-template <int PASS>
-__device__ __forceinline__ float composite_bwd_pass(const float *zr, const float4 *cr, const float *dwr, int K, float far,
-                                                    float3 drgb, float ddepth, float gwhite, int lane, float total,
-                                                    float4 *dout, float *dzout, bool preact, float *dfar = nullptr) {
-    float carry = 1.f, run = 0.f, acc = 0.f, ddelta_prev = 0.f;
-    for (int c0 = 0; c0 < K; c0 += 64) {
-        const int i = c0 + lane;
-        const bool valid = i < K;
-        float zi = 0.f, alpha = 0.f, delta = 0.f, ex = 1.f;
-        float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (valid) {
-            zi = zr[i];
-            delta = ((i + 1 < K) ? zr[i + 1] : far) - zi;
-            cs = cr[i];
-            ex = expf(-delta * fmaxf(cs.w, 0.f));
-            alpha = 1.f - ex;
-        }
-        const float tf = valid ? (1.f - alpha + 1e-10f) : 1.f;
-        const float incl = wave_scan_mul(tf, lane);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 1.f;
-        const float T = carry * excl;
-        const float w = alpha * T;
-        float g = 0.f;
-        if (valid) g = drgb.x * cs.x + drgb.y * cs.y + drgb.z * cs.z + ddepth * zi + (dwr ? dwr[i] : 0.f) - gwhite;
-        const float gw = valid ? g * w : 0.f;
-        if (PASS == 0) {
-            acc += gw;
-        } else {
-            const float pre = wave_scan_add(gw, lane) + run;   // sum_{j<=i} g_j w_j
-            const float suffix = total - pre;              // sum_{j>i}
-            float ddelta = 0.f;
-            if (valid) {
-                const float dalpha = g * T - suffix / tf;
-                const float dsigma = cs.w > 0.f ? dalpha * delta * ex : 0.f;
-                float4 go = make_float4(w * drgb.x, w * drgb.y, w * drgb.z, dsigma);
-                if (preact) {  // through rgb = sigmoid(.), sigma = relu(.) (models.py:260-263): relu' already applied
-                    go.x *= cs.x * (1.f - cs.x); go.y *= cs.y * (1.f - cs.y); go.z *= cs.z * (1.f - cs.z);
-                }
-                dout[i] = go;
-                ddelta = dalpha * fmaxf(cs.w, 0.f) * ex;  // d alpha_i / d delta_i = relu(sigma) exp(-delta relu(sigma))
-                if (dfar && i == K - 1) *dfar = ddelta;    // the last delta is far - z_{K-1} (nerf.py:181)
-            }
-            if (dzout) {
-                // delta_i = z_{i+1} - z_i (last: far - z_i), depth = sum w z:
-                //   dL/dz_i = w_i d_depth - ddelta_i + ddelta_{i-1}
-                float up = __shfl_up(ddelta, 1, 64);
-                if (lane == 0) up = ddelta_prev;
-                if (valid) dzout[i] = w * ddepth - ddelta + up;
-                ddelta_prev = __shfl(ddelta, 63, 64);
-            }
-            run = __shfl(pre, 63, 64);
-        }
-        carry = carry * __shfl(incl, 63, 64);
+// dL/da_i = T_i (g_i - S_i),  S_i = sum_{j>i} g_j a_j prod_{i<k<j} tf_k = g_{i+1} a_{i+1} + tf_{i+1} S_{i+1}
+// (= g_i T_i - (sum_{j>i} g_j w_j) / tf_i, with the suffix summed directly: formed as total - prefix and divided by tf_i, its
+// rounding is divided by a tiny tf_i on a nearly opaque sample and comes back times sigma_i exp(..) in dL/dz.)
+// The 64-sample chunks are walked from the last to the first: per chunk a reverse wave scan of the maps S -> g_j a_j + tf_j S
+// (wave_rscan_affine), S carried across chunks; T_i from the forward product scan, as composite_kernel forms it.
+struct CompSample {
+    float zi, delta, ex, alpha, tf;
+    float4 cs;
+    bool valid;
+};
+
+__device__ __forceinline__ CompSample composite_sample(const float *zr, const float4 *cr, int K, float far, int i) {
+    CompSample s;
+    s.valid = i < K;
+    s.zi = 0.f; s.delta = 0.f; s.ex = 1.f; s.alpha = 0.f;
+    s.cs = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (s.valid) {
+        s.zi = zr[i];
+        s.delta = ((i + 1 < K) ? zr[i + 1] : far) - s.zi;
+        s.cs = cr[i];
+        s.ex = expf(-s.delta * fmaxf(s.cs.w, 0.f));
+        s.alpha = 1.f - s.ex;
     }
-    return PASS == 0 ? wave_sum(acc) : 0.f;
+    s.tf = s.valid ? (1.f - s.alpha + 1e-10f) : 1.f;
+    return s;
+}
+
+// prod of tf over chunk c (every lane)
+__device__ __forceinline__ float composite_chunk_product(const float *zr, const float4 *cr, int K, float far, int c, int lane) {
+    return __shfl(wave_scan_mul(composite_sample(zr, cr, K, far, c * 64 + lane).tf, lane), 63, 64);
 }
 
 __global__ void __launch_bounds__(CW * 64)
@@ -821,9 +795,61 @@ composite_bwd_kernel(const float *__restrict__ rays, const float *__restrict__ z
     const float *zr = z + (size_t)r * K;
     const float4 *cr = rgbs + (size_t)r * K;
     const float *dwr = d_w ? d_w + (size_t)r * K : nullptr;
-    const float total = composite_bwd_pass<0>(zr, cr, dwr, K, far, drgb, ddepth, gwhite, lane, 0.f, nullptr, nullptr, false);
-    composite_bwd_pass<1>(zr, cr, dwr, K, far, drgb, ddepth, gwhite, lane, total, d_rgbs + (size_t)r * K,
-                          d_z ? d_z + (size_t)r * K : nullptr, preact != 0, d_far ? d_far + r : nullptr);
+    float4 *dout = d_rgbs + (size_t)r * K;
+    float *dzout = d_z ? d_z + (size_t)r * K : nullptr;
+    const int nc = (K + 63) >> 6;
+
+    // T at the head of chunk c, for c < 64 in lane c of `heads` (nothing to do for K <= 64); the chunks beyond 4096 samples
+    // rebuild theirs from chunk 63's
+    float heads = 1.f, carry = 1.f;
+    for (int c = 1; c < nc && c < 64; ++c) {
+        carry *= composite_chunk_product(zr, cr, K, far, c - 1, lane);
+        if (lane == c) heads = carry;
+    }
+
+    float S_in = 0.f;  // S of the chunk's last sample
+    float pend = 0.f;  // w d_depth - ddelta of the first sample of the chunk walked before: waits for ddelta of its left neighbour
+    for (int c = nc - 1; c >= 0; --c) {
+        const int c0 = c * 64, i = c0 + lane;
+        carry = __shfl(heads, c < 64 ? c : 63, 64);
+        for (int cc = 63; cc < c; ++cc) carry *= composite_chunk_product(zr, cr, K, far, cc, lane);
+        const CompSample s = composite_sample(zr, cr, K, far, i);
+        const float4 cs = s.cs;
+        const float incl = wave_scan_mul(s.tf, lane);
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.f;
+        const float T = carry * excl;
+        const float w = s.alpha * T;
+        float g = 0.f;
+        if (s.valid) g = drgb.x * cs.x + drgb.y * cs.y + drgb.z * cs.z + ddepth * s.zi + (dwr ? dwr[i] : 0.f) - gwhite;
+        float m = s.tf, b = g * s.alpha;  // past the end: (1, 0), the identity
+        wave_rscan_affine(m, b, lane);
+        const float mn = __shfl_down(m, 1, 64), bn = __shfl_down(b, 1, 64);
+        const float S = lane == 63 ? S_in : bn + mn * S_in;
+        S_in = __shfl(b + m * S_in, 0, 64);  // S of sample c0 - 1
+        float ddelta = 0.f;
+        if (s.valid) {
+            const float dalpha = T * (g - S);
+            const float dsigma = cs.w > 0.f ? dalpha * s.delta * s.ex : 0.f;
+            float4 go = make_float4(w * drgb.x, w * drgb.y, w * drgb.z, dsigma);
+            if (preact) {  // through rgb = sigmoid(.), sigma = relu(.) (models.py:260-263): relu' already applied
+                go.x *= cs.x * (1.f - cs.x); go.y *= cs.y * (1.f - cs.y); go.z *= cs.z * (1.f - cs.z);
+            }
+            dout[i] = go;
+            ddelta = dalpha * fmaxf(cs.w, 0.f) * s.ex;  // d alpha_i / d delta_i = relu(sigma) exp(-delta relu(sigma))
+            if (d_far && i == K - 1) d_far[r] = ddelta;   // the last delta is far - z_{K-1} (nerf.py:181)
+        }
+        if (dzout) {
+            // delta_i = z_{i+1} - z_i (last: far - z_i), depth = sum w z:
+            //   dL/dz_i = w_i d_depth - ddelta_i + ddelta_{i-1}
+            // the left neighbour of lane 0 is in the chunk walked next: its share is written from there (lane 63)
+            const float up = __shfl_up(ddelta, 1, 64);
+            const float own = w * ddepth - ddelta;
+            if (s.valid && (lane > 0 || c0 == 0)) dzout[i] = lane > 0 ? own + up : own;
+            if (lane == 63 && c0 + 64 < K) dzout[c0 + 64] = pend + ddelta;
+            pend = __shfl(own, 0, 64);
+        }
+    }
 }
 
 // ---------------------------------------------------------------- latent scatter-add

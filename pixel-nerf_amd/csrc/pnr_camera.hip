@@ -71,8 +71,13 @@ camera_record_kernel(const EvalParams q, const float *__restrict__ d_in42, const
 }
 
 // dz/d(near), dz/d(far) of a sample on the stratified / importance map z(s) = near (1 - s) + far s (lindisp: 1/z linear in s),
-// with s recovered from z (nerf.py:98-148)
+// with s recovered from z (nerf.py:98-148).  far == near: every z equals both and s cannot be recovered (0/0); dn + df = 1
+// holds for both maps there, so the sample's gradient goes half to near and half to far -- their sum is exact.
 __device__ __forceinline__ void sample_bounds_grad(float z, float near, float far, bool lindisp, float &dn, float &df) {
+    if (far == near) {
+        dn = 0.5f; df = 0.5f;
+        return;
+    }
     if (!lindisp) {
         const float s = (z - near) / (far - near);
         dn = 1.f - s; df = s;

@@ -29,4 +29,18 @@ __device__ __forceinline__ float wave_scan_mul(float v, int lane) {
     return v;
 }
 
+// reverse inclusive scan of affine maps f_l(S) = b_l + m_l S under composition: lane l ends with (m, b) of
+// f_l o f_{l+1} o ... o f_63 (f_63 applied first).  (m1, b1) o (m2, b2) = (m1 m2, b1 + m1 b2) is associative, so the
+// suffix recurrence S_{l-1} = b_l + m_l S_l becomes S_{l-1} = b + m S_63 with no division and no subtraction of sums.
+__device__ __forceinline__ void wave_rscan_affine(float &m, float &b, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float mt = __shfl_down(m, o, 64), bt = __shfl_down(b, o, 64);
+        if (lane + o < 64) {
+            b += m * bt;
+            m *= mt;
+        }
+    }
+}
+
 }  // namespace pnr

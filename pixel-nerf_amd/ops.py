@@ -605,7 +605,8 @@ def sample_bounds_backward(rays, z, dz, lindisp=False, ranks=None, n4=None, dept
     """dL/d rays (R,8) of sample positions z (R,K) drawn by sample_coarse / sample_fine (pnr_sample_bounds_backward): dz
     through z = near (1-s) + far s (lindisp: 1/z linear in s) to near / far; the depth samples at `ranks` (ops.sample_fine
     want_ranks) only where their clamp is active; d_far (R,) is added to far.  Columns 0..5 are zero (the caller builds the
-    points from the rays with differentiable ops)."""
+    points from the rays with differentiable ops).  On a ray with near == far, s cannot be recovered from z: each sample's dz
+    goes half to near and half to far (their sum, sum_k dz_k, is exact for both maps)."""
     _expect(rays, "rays", (None, 8))
     R = rays.shape[0]
     _expect(z, "z", (R, None))
