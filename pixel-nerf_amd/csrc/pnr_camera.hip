@@ -16,6 +16,7 @@
 
 #include "pnr_common.h"
 #include "pnr_device.h"
+#include "pnr_entry.h"
 #include "pnr_layout.h"
 
 namespace pnr {
@@ -246,13 +247,10 @@ extern "C" int pnr_camera_backward(const PnrScene *s, const float *rays, const f
                                    const float *d_far, const int *ranks, const float *n4, int Kfd, const float *depth_c,
                                    float depth_std, float *d_rays, float *d_poses, float *d_focal, float *d_c,
                                    void *workspace, void *stream) {
-    if (!s || !rays || !z || !d_in42 || !d_zlat || !workspace || R <= 0 || K <= 0 || rays_per_obj <= 0)
-        return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: bad argument");
-    if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: R != SB * rays_per_obj");
+    EvalParams q = {};  // (camera_record_kernel holds a point index in an int)
+    if (int rc = ray_samples(q, "pnr_camera_backward", s, rays, z, R, rays_per_obj, K, false, {0, INDEX_I32, 0})) return rc;
+    if (!d_in42 || !d_zlat || !workspace) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: bad argument");
     if (ranks && (!n4 || !depth_c || Kfd <= 0 || Kfd > K)) return pnr_fail(PNR_E_INVALID, "pnr_camera_backward: depth samples");
-    EvalParams q = {};
-    scene_params(q, *s);
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
     const long long n = q.P * q.NS;
     float *ray_rec = (float *)workspace;
     float *cam_rec = ray_rec + n * RAY_REC;

@@ -1,5 +1,5 @@
 // pnr_device.h -- device-side building blocks shared by the forward (pnr_mlp.hip) and backward
-// (pnr_bwd.hip) fused network kernels: MFMA traits, 16-bit packing, the weight prefetch ring,
+// (pnr_bwd.hip, pnr_scatter.hip) fused network kernels: MFMA traits, 16-bit packing, the weight prefetch ring,
 // the tile GEMM, activation-image writes.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -83,13 +83,9 @@ struct EvalParams {
     unsigned int *probe;
 };
 
-// the scene's fields of a launch, the multi-view scratch (PnrScene.mv_workspace) included
-inline void scene_params(EvalParams &q, const PnrScene &s) {
-    q.latent = s.latent_nhwc; q.poses = s.poses; q.focal = s.focal; q.c = s.c;
-    q.SB = s.SB; q.NS = s.NS; q.Hl = s.Hl; q.Wl = s.Wl; q.n_focal = s.n_focal; q.n_c = s.n_c;
-    q.img_w = s.img_w; q.img_h = s.img_h;
-    q.mv_ws = (float *)s.mv_workspace;
-}
+// (filled by the entry builders of pnr_entry.h: ray_samples / points / set_packed)
+
+constexpr int CW = 4;  // wavefronts per block of the wave-per-ray / wave-per-sample kernels (compositing and position backward, latent scatter)
 
 // Tile order of the fused evaluation kernels (eval_kernel, eval_split_kernel).  Workgroup b runs on XCD b % n_xcd (the
 // dispatcher deals workgroups to the XCDs round-robin -- relied on for speed only, never for a result): every XCD takes ONE

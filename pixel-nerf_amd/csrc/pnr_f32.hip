@@ -25,6 +25,7 @@
 
 #include "pnr_common.h"
 #include "pnr_device.h"
+#include "pnr_entry.h"
 #include "pnr_internal.h"
 #include "pnr_layout.h"
 
@@ -716,14 +717,11 @@ static void wgrad(const Mm &c, const float *dY, int lddy, const float *X, int ld
 // floats of workspace per point of a chunk
 static size_t floats_per_point(int NS) { return (size_t)NS * (D_IN_PAD + C_LAT + D_HID + D_HID) + D_HID + D_HID + 4; }
 
-static int eval_f32(const PnrScene *s, const PnrMlpWeights *w, EvalParams q, bool rays, float *ws, size_t ws_bytes,
-                    hipStream_t st) {
-    if (!s || !w || !ws || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: null argument");
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: bad scene shape");
+// q: from ray_samples() / points() (pnr_entry.h: scene, sizes and limits checked)
+static int eval_f32(const PnrMlpWeights *w, EvalParams q, bool rays, float *ws, size_t ws_bytes, hipStream_t st) {
+    if (!w || !ws || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: null argument");
     if (q.P == 0) return PNR_OK;
-    if (q.P > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: too many points");
-    scene_params(q, *s);
-    const int NS = s->NS;
+    const int NS = q.NS;
     long long chunk = (long long)(ws_bytes / sizeof(float) / floats_per_point(NS));
     if (chunk < 64) return pnr_fail(PNR_E_INVALID, "pnr_eval_f32: workspace too small");
     if (chunk >= q.P) chunk = q.P;
@@ -775,16 +773,13 @@ static int check_saved(const PnrF32Saved *sv, int NS) {
     return NS == 1 || sv->pool_in != nullptr;
 }
 
-static int eval_f32_train(const PnrScene *s, const PnrMlpWeights *w, EvalParams q, const PnrF32Saved *sv, hipStream_t stream, bool fast) {
+// q: from ray_samples() (pnr_entry.h: scene, sizes and limits checked)
+static int eval_f32_train(const PnrMlpWeights *w, EvalParams q, const PnrF32Saved *sv, hipStream_t stream, bool fast) {
     const Mm st = {stream, fast, nullptr, nullptr};
-    if (!s || !w || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: null argument");
-    if (w->combine_max && s->NS > 1) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: combine_type \"max\" is an inference form (no backward)");
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: bad scene shape");
-    if (!check_saved(sv, s->NS)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: null activation buffer in PnrF32Saved");
-    if (q.P == 0) return PNR_OK;
-    if (q.P * s->NS > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: too many points");
-    scene_params(q, *s);
-    const int NS = s->NS;
+    if (!w || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: null argument");
+    if (w->combine_max && q.NS > 1) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: combine_type \"max\" is an inference form (no backward)");
+    if (!check_saved(sv, q.NS)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: null activation buffer in PnrF32Saved");
+    const int NS = q.NS;
     const int np = (int)q.P;
     const long long rows = (long long)np * NS;
     hipLaunchKernelGGL(feat_f32_kernel<true>, dim3((unsigned)((rows + FW - 1) / FW)), dim3(FW * 64), 0, stream, q, 0LL, np, sv->in42, sv->zlat);
@@ -825,12 +820,11 @@ static void block_bwd_f32(const Mm &st, const PnrMlpWeights *w, const PnrMlpWeig
 extern "C" int pnr_eval_ray_samples_f32_train(const PnrScene *scene, const PnrMlpWeights *w, const float *rays, const float *z, int R,
                                               int rays_per_obj, int K, float *rgbsigma, const PnrF32Saved *saved, int split_gemm,
                                               void *stream) {
-    if (R <= 0 || K <= 0 || rays_per_obj <= 0 || !rays || !z) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: bad argument");
-    if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: R != SB * rays_per_obj");
     if (w && w->stream_scale_log2 != 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32_train: training at a stream scale (stream_scale_log2 != 0) is not supported");
     pnr::EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
-    return pnr::eval_f32_train(scene, w, q, saved, (hipStream_t)stream, split_gemm != 0);
+    if (int rc = pnr::ray_samples(q, "pnr_eval_ray_samples_f32_train", scene, rays, z, R, rays_per_obj, K, false, {0, 0, pnr::POINTS_F32})) return rc;
+    q.out = rgbsigma;
+    return pnr::eval_f32_train(w, q, saved, (hipStream_t)stream, split_gemm != 0);
 }
 
 // ---- fp32-class training, FUSED (round 3).  The training forward is the split-operand inference kernel (pnr_split.hip, TRAIN
@@ -853,15 +847,15 @@ extern "C" int pnr_eval_ray_samples_split_train(const PnrScene *scene, const voi
     if (aux && aux->stream_scale_log2 != 0)
         return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: training at a stream scale is not supported "
                                        "(PnrSplitAux.stream_scale_log2 must be 0: pack the blob with stream_scale_log2 = 0)");
-    if (R <= 0 || K <= 0 || rays_per_obj <= 0 || !rays || !z || !scene || !packed_split || !tables_f32 || !rgbsigma)
-        return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: bad argument");
-    if ((long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: R != SB * rays_per_obj");
-    if (scene->SB <= 0 || scene->NS <= 0 || scene->Hl < 2 || scene->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: bad scene shape");
-    if (!check_split_saved(saved)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null buffer in PnrSplitSaved");
+    // everything is checked before the feature launch: the limits of both kernels (feat_f32_kernel's rows, eval_split_kernel's
+    // points and grid) and the multi-view scratch the second launch needs
     EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K;
-    if (q.P * scene->NS > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: too many points");
-    scene_params(q, *scene);
+    if (int rc = ray_samples(q, "pnr_eval_ray_samples_split_train", scene, rays, z, R, rays_per_obj, K, false, {GRID_U32, POINTS_TILED, POINTS_F32}))
+        return rc;
+    if (!packed_split || !tables_f32 || !rgbsigma) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: bad argument");
+    if (!check_split_saved(saved)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null buffer in PnrSplitSaved");
+    if (scene->NS > 1 && !scene->mv_workspace)
+        return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: a multi-view scene needs PnrScene.mv_workspace (pnr_mv_workspace_bytes())");
     const int np = (int)q.P;
     const long long rows = (long long)np * scene->NS;
     // lin_in operand and interpolated latent as (head | tail) rows: operands of the lin_in / lin_z weight gradients
@@ -869,8 +863,8 @@ extern "C" int pnr_eval_ray_samples_split_train(const PnrScene *scene, const voi
                        np, (float *)saved->in_op, (float *)saved->zlat);
     int rc = pnr_check_launch("pnr_eval_ray_samples_split_train (features)");
     if (rc != PNR_OK) return rc;
-    return eval_samples_split_train(scene, packed_split, tables_f32, rays, z, R, rays_per_obj, K, rgbsigma, saved->a, saved->n,
-                                    saved->x5, saved->masks, aux, (hipStream_t)stream);
+    return eval_samples_split_train(scene, packed_split, tables_f32, q, rgbsigma, saved->a, saved->n, saved->x5, saved->masks, aux,
+                                    (hipStream_t)stream);
 }
 
 static size_t split_bwd_images_bytes(long long P, int NS) { return ((size_t)P * NS * 7 + (size_t)P * 4) * pnr::D_HID * 4; }
@@ -1077,22 +1071,18 @@ extern "C" size_t pnr_eval_f32_workspace_bytes(int NS, long long chunk_points) {
 extern "C" int pnr_eval_ray_samples_f32(const PnrScene *scene, const PnrMlpWeights *w, const float *rays, const float *z, int R,
                                         int rays_per_obj, int K, float *rgbsigma, void *workspace, size_t workspace_bytes,
                                         void *stream) {
-    if (R < 0 || K <= 0 || rays_per_obj <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32: bad sizes");
-    if (R > 0 && (!rays || !z)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32: null rays/z");
-    if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_f32: R != SB * rays_per_obj");
     pnr::EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
-    return pnr::eval_f32(scene, w, q, true, (float *)workspace, workspace_bytes, (hipStream_t)stream);
+    if (int rc = pnr::ray_samples(q, "pnr_eval_ray_samples_f32", scene, rays, z, R, rays_per_obj, K, true, {0, pnr::POINTS_F32, 0})) return rc;
+    q.out = rgbsigma;
+    return pnr::eval_f32(w, q, true, (float *)workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pnr_eval_points_f32(const PnrScene *scene, const PnrMlpWeights *w, const float *xyz, const float *viewdirs, int B,
                                    float *rgbsigma, void *workspace, size_t workspace_bytes, void *stream) {
-    if (B < 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_f32: bad sizes");
-    if (B > 0 && (!xyz || !viewdirs)) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_f32: null xyz/viewdirs");
     pnr::EvalParams q = {};
-    q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B > 0 ? B : 1;
-    q.P = scene ? (long long)scene->SB * B : 0; q.out = rgbsigma;
-    return pnr::eval_f32(scene, w, q, false, (float *)workspace, workspace_bytes, (hipStream_t)stream);
+    if (int rc = pnr::points(q, "pnr_eval_points_f32", scene, xyz, viewdirs, B, {0, pnr::POINTS_F32, 0})) return rc;
+    q.out = rgbsigma;
+    return pnr::eval_f32(w, q, false, (float *)workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // The feature phase alone (SURVEY rows R7 + R8 in isolation): lin_in operand rows [code(39) | R d (3) | 0-pad] and the
@@ -1100,14 +1090,10 @@ extern "C" int pnr_eval_points_f32(const PnrScene *scene, const PnrMlpWeights *w
 extern "C" int pnr_point_features_f32(const PnrScene *s, const float *xyz, const float *viewdirs, int B, float *in42,
                                       float *zlat, void *stream) {
     using namespace pnr;
-    if (!s || B < 0 || !in42 || !zlat) return pnr_fail(PNR_E_INVALID, "pnr_point_features_f32: bad argument");
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_point_features_f32: bad scene shape");
-    if (B == 0) return PNR_OK;
-    if (!xyz || !viewdirs) return pnr_fail(PNR_E_INVALID, "pnr_point_features_f32: null xyz/viewdirs");
     EvalParams q = {};
-    q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B; q.P = (long long)s->SB * B;
-    if (q.P * s->NS > 0x7fffffc0LL) return pnr_fail(PNR_E_INVALID, "pnr_point_features_f32: too many points");
-    scene_params(q, *s);
+    if (int rc = points(q, "pnr_point_features_f32", s, xyz, viewdirs, B, {0, 0, POINTS_F32})) return rc;
+    if (!in42 || !zlat) return pnr_fail(PNR_E_INVALID, "pnr_point_features_f32: bad argument");
+    if (B == 0) return PNR_OK;
     const long long rows = q.P * s->NS;
     hipLaunchKernelGGL(feat_f32_kernel<false>, dim3((unsigned)((rows + FW - 1) / FW)), dim3(FW * 64), 0, (hipStream_t)stream, q, 0LL,
                        (int)q.P, in42, zlat);

@@ -7,22 +7,24 @@
 
 namespace pnr {
 
+struct EvalParams;  // pnr_device.h
+
 // fused network on (ray, z) samples with the rays taken from `src` (explicit array or camera): dispatches on
 // `precision` (F16 / BF16 kernels of pnr_mlp.hip, F16X3 split-operand kernel of pnr_split.hip); tables == NULL selects
-// the unfolded stream.
+// the unfolded stream.  entry: exported name of the calling entry (prefix of its messages).
 // aux: what a split-operand launch takes beyond that (stream scale, guard word, probe words; nullable, F16X3 only).
-int eval_samples_src(const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
+int eval_samples_src(const char *entry, const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
                      const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux, hipStream_t stream);
-int eval_samples_split_src(const PnrScene *scene, const void *packed_split, const void *tables_f32, const RaySrc &src,
+int eval_samples_split_src(const char *entry, const PnrScene *scene, const void *packed_split, const void *tables_f32, const RaySrc &src,
                            const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux, hipStream_t stream);
 
 // training forward of the fp32-class path: the split-operand kernel + what the backward keeps -- the (head | tail) 16-bit operand
 // images of every 512-wide linear in storage order (img_a[b]: relu(x) entering blocks[b].fc_0, img_n[b]: relu(net) entering fc_1;
 // b < 3: NS*P rows [view][point], else P rows; 2 x rows x 1024 bytes each), the stream in front of lin_out as fp32 rows (x5) and
-// the relu bit masks (pnr_train_masks_bytes).  Defined in pnr_split.hip.
-int eval_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *rays,
-                             const float *z, int R, int rays_per_obj, int K, float *rgbsigma, void *const *img_a, void *const *img_n,
-                             float *x5, void *masks, const PnrSplitAux *aux, hipStream_t stream);
+// the relu bit masks (pnr_train_masks_bytes).  samples: the checked scene and samples (ray_samples(), pnr_entry.h).  Defined in pnr_split.hip.
+int eval_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32, const EvalParams &samples,
+                             float *rgbsigma, void *const *img_a, void *const *img_n, float *x5, void *masks, const PnrSplitAux *aux,
+                             hipStream_t stream);
 
 // fused data-gradient chain of the fp32-class training path (bwd_split_kernel, pnr_split.hip): transposed (head, tail) weight
 // streams packed from the raw parameters, relu masks of the TRAIN forward, g_out (P,4) unscaled + device [s, 1/s]; every layer's

@@ -19,6 +19,7 @@
 
 #include "pnr_common.h"
 #include "pnr_device.h"
+#include "pnr_entry.h"
 #include "pnr_internal.h"
 #include "pnr_layout.h"
 
@@ -502,24 +503,15 @@ static int launch(EvalParams &q, bool mv, hipStream_t st) {
     return pnr_check_launch("eval_kernel");
 }
 
+// q: from ray_samples() / points() (pnr_entry.h: scene, sizes and limits checked)
 static int eval_common(const PnrScene *s, const void *packed, int precision, EvalParams &q, bool rays, hipStream_t st,
                        const void *tables = nullptr) {
-    if (!s || !packed || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval: null argument");
-    q.tables = (const char *)tables;  // non-null: `packed` is a folded stream (pnr_pack_mlp_folded)
+    if (!packed || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval: null argument");
     if (tables && q.d_z) return pnr_fail(PNR_E_INVALID, "pnr_eval: the training instantiation is not folded");
-    q.table_stride = (long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT;
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval: bad scene shape");
-    if (!(s->n_focal == 1 || s->n_focal == s->SB) || !(s->n_c == 1 || s->n_c == s->SB))
-        return pnr_fail(PNR_E_INVALID, "pnr_eval: focal / c must have 1 or SB rows");
     if (q.P == 0) return PNR_OK;
-    scene_params(q, *s);
-    q.wstream = (const char *)packed;
-    q.bias = (const float *)((const char *)packed + BIAS_OFFSET_BYTES);
-    q.bout = (const float *)((const char *)packed + BOUT_OFFSET_BYTES);
-    if (q.P > 0x7fffff80LL) return pnr_fail(PNR_E_INVALID, "pnr_eval: too many points (P must stay below 2^31)");
-    // texel offsets are 32-bit element indices into the grid / the tables (project_point)
-    if ((long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT > 0xffffffffLL)
-        return pnr_fail(PNR_E_INVALID, "pnr_eval: feature grid too large (SB*NS*Hl*Wl*512 must stay below 2^32 elements)");
+    set_packed(q, packed);
+    q.tables = (const char *)tables;  // non-null: `packed` is a folded stream (pnr_pack_mlp_folded)
+    q.table_stride = grid_elems(*s);
     const bool mv = s->NS > 1;
     if (mv && !q.mv_ws) return pnr_fail(PNR_E_INVALID, "pnr_eval: a multi-view scene needs PnrScene.mv_workspace (pnr_mv_workspace_bytes())");
     if (precision == PNR_PREC_F16) return rays ? launch<PNR_PREC_F16, true>(q, mv, st) : launch<PNR_PREC_F16, false>(q, mv, st);
@@ -536,18 +528,15 @@ extern "C" int pnr_debug_phase_timing(const PnrScene *s, const void *packed, con
                                       const float *z, int R, int rays_per_obj, int K, float *rgbsigma, unsigned long long *tim,
                                       void *stream) {
     using namespace pnr;
-    if (!s || !packed || !rays || !z || !rgbsigma || !tim || s->NS != 1)
-        return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing: bad argument");
     EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma; q.tim = tim;
-    scene_params(q, *s);
-    q.wstream = (const char *)packed;
-    q.bias = (const float *)((const char *)packed + BIAS_OFFSET_BYTES);
-    q.bout = (const float *)((const char *)packed + BOUT_OFFSET_BYTES);
+    if (int rc = ray_samples(q, "pnr_debug_phase_timing", s, rays, z, R, rays_per_obj, K, false, EVAL_LIMITS)) return rc;
+    if (!packed || !rgbsigma || !tim || s->NS != 1) return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing: bad argument");
+    q.out = rgbsigma; q.tim = tim;
+    set_packed(q, packed);
     const int mt = tables ? 96 : 64;
     q.ntiles = (int)((q.P + mt - 1) / mt);
     q.tables = (const char *)tables;  // non-null: folded stream
-    q.table_stride = (long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT;
+    q.table_stride = grid_elems(*s);
     auto k = tables ? eval_kernel<PNR_PREC_F16, true, false, true, false, true, 96> : eval_kernel<PNR_PREC_F16, true, false, true>;
     const int lds = tables ? Tile<96>::LDS_TOTAL : Tile<64>::LDS_TOTAL;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -559,47 +548,38 @@ extern "C" int pnr_debug_phase_timing(const PnrScene *s, const void *packed, con
 }
 #endif
 
-int pnr::eval_samples_src(const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
+int pnr::eval_samples_src(const char *entry, const PnrScene *scene, const void *packed, const void *tables, int precision, const RaySrc &src,
                           const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux, hipStream_t stream) {
-    if (precision == PNR_PREC_F16X3) return eval_samples_split_src(scene, packed, tables, src, z, R, rays_per_obj, K, rgbsigma, aux, stream);
-    if (R < 0 || K <= 0 || rays_per_obj <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: bad sizes");
-    if (R > 0 && ((!src.rays && !src.poses) || !z)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: null rays/z");
-    if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples: R != SB * rays_per_obj");
+    if (precision == PNR_PREC_F16X3)
+        return eval_samples_split_src(entry, scene, packed, tables, src, z, R, rays_per_obj, K, rgbsigma, aux, stream);
     pnr::EvalParams q = {};
-    q.rays = src.rays; q.cam = src; q.cam.rays = nullptr;
-    q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
+    if (int rc = pnr::ray_samples(q, entry, scene, src, z, R, rays_per_obj, K, true, pnr::EVAL_LIMITS)) return rc;
+    q.out = rgbsigma;
     return pnr::eval_common(scene, packed, precision, q, true, stream, tables);
-}
-
-static int eval_ray_samples_impl(const PnrScene *scene, const void *packed, const void *tables, int precision,
-                                 const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
-                                 void *stream) {
-    pnr::RaySrc src = {};
-    src.rays = rays;
-    return pnr::eval_samples_src(scene, packed, tables, precision, src, z, R, rays_per_obj, K, rgbsigma, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pnr_eval_ray_samples(const PnrScene *scene, const void *packed, int precision, const float *rays,
                                     const float *z, int R, int rays_per_obj, int K, float *rgbsigma, void *stream) {
-    return eval_ray_samples_impl(scene, packed, nullptr, precision, rays, z, R, rays_per_obj, K, rgbsigma, stream);
+    return pnr::eval_samples_src("pnr_eval_ray_samples", scene, packed, nullptr, precision, pnr::explicit_rays(rays), z, R, rays_per_obj, K,
+                                 rgbsigma, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pnr_eval_ray_samples_folded(const PnrScene *scene, const void *packed_folded, const void *tables,
                                            int precision, const float *rays, const float *z, int R, int rays_per_obj,
                                            int K, float *rgbsigma, void *stream) {
     if (!tables) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_folded: null tables");
-    return eval_ray_samples_impl(scene, packed_folded, tables, precision, rays, z, R, rays_per_obj, K, rgbsigma, stream);
+    return pnr::eval_samples_src("pnr_eval_ray_samples_folded", scene, packed_folded, tables, precision, pnr::explicit_rays(rays), z, R,
+                                 rays_per_obj, K, rgbsigma, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pnr_eval_ray_samples_train(const PnrScene *scene, const void *packed, int precision, const float *rays,
                                           const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
                                           const PnrTrainDumps *dumps, void *stream) {
-    if (R <= 0 || K <= 0 || rays_per_obj <= 0 || !rays || !z || !dumps)
-        return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_train: bad argument");
-    if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_train: R != SB * rays_per_obj");
-    if (!dumps->d_in || !dumps->d_z || !dumps->d_x5) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_train: null dump buffer");
     pnr::EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
+    if (int rc = pnr::ray_samples(q, "pnr_eval_ray_samples_train", scene, rays, z, R, rays_per_obj, K, false, pnr::EVAL_LIMITS)) return rc;
+    if (!dumps) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_train: bad argument");
+    if (!dumps->d_in || !dumps->d_z || !dumps->d_x5) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_train: null dump buffer");
+    q.out = rgbsigma;
     q.d_in = (char *)dumps->d_in; q.d_z = (char *)dumps->d_z; q.d_x5 = (char *)dumps->d_x5;
     q.d_mask = (unsigned long long *)dumps->d_mask;
     if (!q.d_mask) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_train: null relu-mask buffer (PnrTrainDumps.d_mask)");
@@ -610,25 +590,23 @@ extern "C" int pnr_eval_ray_samples_train(const PnrScene *scene, const void *pac
     return pnr::eval_common(scene, packed, precision, q, true, (hipStream_t)stream);
 }
 
-static int eval_points_impl(const PnrScene *scene, const void *packed, const void *tables, int precision, const float *xyz,
-                            const float *viewdirs, int B, float *rgbsigma, void *stream) {
-    if (B < 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_points: bad sizes");
-    if (B > 0 && (!xyz || !viewdirs)) return pnr_fail(PNR_E_INVALID, "pnr_eval_points: null xyz/viewdirs");
+static int eval_points_impl(const char *entry, const PnrScene *scene, const void *packed, const void *tables, int precision,
+                            const float *xyz, const float *viewdirs, int B, float *rgbsigma, void *stream) {
     pnr::EvalParams q = {};
-    q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B > 0 ? B : 1;
-    q.P = scene ? (long long)scene->SB * B : 0; q.out = rgbsigma;
+    if (int rc = pnr::points(q, entry, scene, xyz, viewdirs, B, pnr::EVAL_LIMITS)) return rc;
+    q.out = rgbsigma;
     return pnr::eval_common(scene, packed, precision, q, false, (hipStream_t)stream, tables);
 }
 
 extern "C" int pnr_eval_points(const PnrScene *scene, const void *packed, int precision, const float *xyz,
                                const float *viewdirs, int B, float *rgbsigma, void *stream) {
-    return eval_points_impl(scene, packed, nullptr, precision, xyz, viewdirs, B, rgbsigma, stream);
+    return eval_points_impl("pnr_eval_points", scene, packed, nullptr, precision, xyz, viewdirs, B, rgbsigma, stream);
 }
 
 extern "C" int pnr_eval_points_folded(const PnrScene *scene, const void *packed_folded, const void *tables, int precision,
                                       const float *xyz, const float *viewdirs, int B, float *rgbsigma, void *stream) {
     if (!tables) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_folded: null tables");
-    return eval_points_impl(scene, packed_folded, tables, precision, xyz, viewdirs, B, rgbsigma, stream);
+    return eval_points_impl("pnr_eval_points_folded", scene, packed_folded, tables, precision, xyz, viewdirs, B, rgbsigma, stream);
 }
 
 extern "C" int pnr_profile_enable(int on) {

@@ -5,6 +5,7 @@
 
 #include "pnr_common.h"
 #include "pnr_device.h"  // EvalParams, project_point: the sparse fold marks rows with the forward kernels' own projection
+#include "pnr_entry.h"
 #include "pnr_internal.h"
 #include "pnr_layout.h"
 
@@ -724,14 +725,14 @@ extern "C" int pnr_params_checksum(const PnrMlpWeights *w, void *ws, unsigned lo
 }
 
 extern "C" size_t pnr_folded_tables_bytes(const PnrScene *s) {
-    if (!s || s->SB <= 0 || s->NS <= 0 || s->Hl <= 0 || s->Wl <= 0) return 0;
+    if (pnr::scene_defect(s)) return 0;
     return (size_t)pnr::COMBINE_LAYER * s->SB * s->NS * s->Hl * s->Wl * pnr::D_HID * 2;
 }
 
 extern "C" int pnr_fold_latent(const PnrScene *s, const PnrMlpWeights *w, int precision, void *tables, void *stream) {
     using namespace pnr;
-    if (!s || !w || !tables || !s->latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent: null argument");
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent: bad scene shape");
+    if (int rc = check_scene(s, "pnr_fold_latent")) return rc;
+    if (!w || !tables || !s->latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent: null argument");
     const long long M = (long long)s->SB * s->NS * s->Hl * s->Wl;
     if ((M + 63) / 64 > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent: grid too large");
     dim3 grid((unsigned)((M + 63) / 64), D_HID / 64, COMBINE_LAYER);
@@ -754,8 +755,8 @@ extern "C" size_t pnr_folded_tables_f32_bytes(const PnrScene *s) { return 2 * pn
 
 extern "C" int pnr_fold_latent_f32(const PnrScene *s, const PnrMlpWeights *w, float *tables, unsigned int *sat_flag, void *stream) {
     using namespace pnr;
-    if (!s || !w || !tables || !s->latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32: null argument");
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32: bad scene shape");
+    if (int rc = check_scene(s, "pnr_fold_latent_f32")) return rc;
+    if (!w || !tables || !s->latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32: null argument");
     const long long M = (long long)s->SB * s->NS * s->Hl * s->Wl;
     if ((M + 63) / 64 > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32: grid too large");
     FoldJobs jobs;
@@ -784,7 +785,7 @@ extern "C" int pnr_fold_latent_f32(const PnrScene *s, const PnrMlpWeights *w, fl
 // what it held.  workspace: marks (one byte per texel, padded to 4096) | per-workgroup counts | row count | row list
 static size_t fold_rows_blocks(long long M) { return (size_t)((M + pnr::FR_PER_WG - 1) / pnr::FR_PER_WG); }
 extern "C" size_t pnr_fold_latent_f32_rows_workspace_bytes(const PnrScene *s) {
-    if (!s || s->SB <= 0 || s->NS <= 0 || s->Hl <= 0 || s->Wl <= 0) return 0;
+    if (pnr::scene_defect(s)) return 0;
     const long long M = (long long)s->SB * s->NS * s->Hl * s->Wl;
     const size_t nb = fold_rows_blocks(M);
     return nb * pnr::FR_PER_WG + (nb + 4 + (size_t)M) * sizeof(int);
@@ -793,12 +794,10 @@ extern "C" size_t pnr_fold_latent_f32_rows_workspace_bytes(const PnrScene *s) {
 extern "C" int pnr_fold_latent_f32_rows(const PnrScene *s, const PnrMlpWeights *w, const float *rays, const float *z, int R, int rays_per_obj,
                                         int K, float *tables, void *workspace, size_t workspace_bytes, unsigned int *sat_flag, void *stream) {
     using namespace pnr;
-    if (!s || !w || !tables || !s->latent_nhwc || !rays || !z) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: null argument");
-    if (s->SB <= 0 || s->NS <= 0 || s->Hl < 2 || s->Wl < 2 || R <= 0 || K <= 0 || rays_per_obj <= 0)
-        return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: bad shape");
-    if ((long long)rays_per_obj * s->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: R != SB * rays_per_obj");
-    const long long M = (long long)s->SB * s->NS * s->Hl * s->Wl, P = (long long)R * K;
-    if (M * C_LAT > 0xffffffffLL || P * s->NS > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: grid or pass too large");
+    EvalParams q = {};  // (fold_mark_kernel: project_point's 32-bit texel offsets, an int row index view * P + point)
+    if (int rc = ray_samples(q, "pnr_fold_latent_f32_rows", s, rays, z, R, rays_per_obj, K, false, {GRID_U32, 0, INDEX_I32})) return rc;
+    if (!w || !tables || !s->latent_nhwc) return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: null argument");
+    const long long M = (long long)s->SB * s->NS * s->Hl * s->Wl, P = q.P;
     if (!workspace || workspace_bytes < pnr_fold_latent_f32_rows_workspace_bytes(s) || ((uintptr_t)workspace & 15) != 0)
         return pnr_fail(PNR_E_INVALID, "pnr_fold_latent_f32_rows: workspace missing, misaligned (16 bytes) or smaller than "
                                        "pnr_fold_latent_f32_rows_workspace_bytes()");
@@ -815,9 +814,6 @@ extern "C" int pnr_fold_latent_f32_rows(const PnrScene *s, const PnrMlpWeights *
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(flags, 0, nb * FR_PER_WG, st);
     if (e != hipSuccess) return pnr_check_hip(e, "hipMemsetAsync(fold marks)");
-    EvalParams q = {};
-    scene_params(q, *s);
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = P;
     const long long n = P * s->NS;
     hipLaunchKernelGGL(fold_mark_kernel, dim3((unsigned)((n + FM_NT - 1) / FM_NT)), dim3(FM_NT), 0, st, q, flags);
     hipLaunchKernelGGL(fold_rows_count_kernel, dim3((unsigned)nb), dim3(FR_NT), 0, st, reinterpret_cast<const uint32_t *>(flags), block_counts);

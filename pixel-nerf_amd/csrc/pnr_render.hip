@@ -7,6 +7,7 @@
 #include <climits>
 
 #include "pnr_common.h"
+#include "pnr_entry.h"
 #include "pnr_internal.h"
 #include "pnr_raysrc.h"
 #include "pnr_wave.h"
@@ -245,11 +246,6 @@ __global__ void philox_fill_ids_kernel(uint32_t seed_lo, uint32_t seed_hi, const
 
 using namespace pnr;
 
-static RaySrc explicit_rays(const float *rays) {
-    RaySrc s = {};
-    s.rays = rays;
-    return s;
-}
 static NoiseSrc explicit_noise(const float *u1, const float *u2, const float *u3, const float *n4) {
     NoiseSrc n = {};
     n.u1 = u1; n.u2 = u2; n.u3 = u3; n.n4 = n4;
@@ -382,24 +378,26 @@ extern "C" size_t pnr_render_workspace_bytes(int R, int Kc, int Kf) {
     return fl * sizeof(float);
 }
 
-// NeRFRenderer.forward (nerf.py:251-303) for any ray source / noise source
-static int render_impl(const PnrScene *scene, const void *packed_coarse, const void *tables_coarse, const void *packed_fine,
-                       const void *tables_fine, int precision, const RaySrc &rs, const NoiseSrc &ns, int R, int rays_per_obj,
+// NeRFRenderer.forward (nerf.py:251-303) for any ray source / noise source; entry: exported name of the caller
+static int render_impl(const char *entry, const PnrScene *scene, const void *packed_coarse, const void *tables_coarse,
+                       const void *packed_fine, const void *tables_fine, int precision, const RaySrc &rs, const NoiseSrc &ns, int R, int rays_per_obj,
                        int Kc, int Kf, int Kfd, float depth_std, int white_bkgd, int lindisp, float *rgb_c, float *depth_c,
                        float *weights_c, float *rgb_f, float *depth_f, float *weights_f, void *workspace,
                        const PnrSplitAux *aux_coarse, const PnrSplitAux *aux_fine, void *stream) {
     int rc;
-    if ((rc = check_split_aux(aux_coarse, precision, "pnr_render_forward")) || (rc = check_split_aux(aux_fine, precision, "pnr_render_forward")))
-        return rc;
-    if (R < 0 || Kc <= 0 || Kf < 0 || Kfd < 0 || Kfd > Kf)
-        return pnr_fail(PNR_E_INVALID, "pnr_render_forward: bad sample counts");
-    if (R == 0) return PNR_OK;
-    if (!workspace || !rgb_c || !depth_c || (Kf > 0 && (!rgb_f || !depth_f)))
-        return pnr_fail(PNR_E_INVALID, "pnr_render_forward: null output / workspace");
-    if (!rs.rays && !rs.poses) return pnr_fail(PNR_E_INVALID, "pnr_render_forward: null rays");
+    if ((rc = check_split_aux(aux_coarse, precision, entry)) || (rc = check_split_aux(aux_fine, precision, entry))) return rc;
+    if (R < 0 || Kc <= 0 || Kf < 0 || Kfd < 0 || Kfd > Kf) return entry_fail(entry, "bad sample counts");
+    if ((rc = check_scene(scene, entry))) return rc;
+    if (R == 0) return PNR_OK;  // (whatever rays_per_obj says: an empty batch renders to empty outputs)
+    if (!workspace || !rgb_c || !depth_c || (Kf > 0 && (!rgb_f || !depth_f))) return entry_fail(entry, "null output / workspace");
+    // sizes and the network kernels' limits, for the largest sample set they are handed, before the first launch (the sample
+    // sets live in the workspace)
+    const int Kmax = (packed_fine || Kf == 0) ? Kc + Kf : (Kc > Kf ? Kc : Kf);
+    EvalParams checked = {};
+    if ((rc = ray_samples(checked, entry, scene, rs, (const float *)workspace, R, rays_per_obj, Kmax, false, EVAL_LIMITS))) return rc;
     const bool gen = !ns.u1 && !ns.u2 && !ns.u3 && !ns.n4;
     if (!gen && (!ns.u1 || (Kf - Kfd > 0 && (!ns.u2 || !ns.u3)) || (Kfd > 0 && !ns.n4)))
-        return pnr_fail(PNR_E_INVALID, "pnr_render_forward: explicit noise needs u1 [, u2, u3] [, n4] (pass none of them for seeded draws)");
+        return entry_fail(entry, "explicit noise needs u1 [, u2, u3] [, n4] (pass none of them for seeded draws)");
     hipStream_t st = (hipStream_t)stream;
     const size_t r = (size_t)R, kc = (size_t)Kc, kt = (size_t)(Kc + Kf);
     float *ws = (float *)workspace;
@@ -413,19 +411,19 @@ static int render_impl(const PnrScene *scene, const void *packed_coarse, const v
     int32_t *ranks = (int32_t *)ws;
     if (weights_c) w_c = weights_c;  // write straight into the caller's buffer
     if ((rc = sample_coarse_src(rs, ns, R, Kc, lindisp, z_c, stream))) return rc;
-    if ((rc = eval_samples_src(scene, packed_coarse, tables_coarse, precision, rs, z_c, R, rays_per_obj, Kc, rgbs_c, aux_coarse, st))) return rc;
+    if ((rc = eval_samples_src(entry, scene, packed_coarse, tables_coarse, precision, rs, z_c, R, rays_per_obj, Kc, rgbs_c, aux_coarse, st))) return rc;
     if ((rc = composite_src(rs, z_c, rgbs_c, R, Kc, white_bkgd, w_c, rgb_c, depth_c, stream))) return rc;
     if (Kf > 0) {
         if (packed_fine) {
             if ((rc = sample_fine_src(rs, w_c, depth_c, z_c, ns, R, Kc, Kf - Kfd, Kfd, depth_std, lindisp, z_f, nullptr, nullptr,
                                       nullptr, stream))) return rc;
-            if ((rc = eval_samples_src(scene, packed_fine, tables_fine, precision, rs, z_f, R, rays_per_obj, Kc + Kf, rgbs_f, aux_fine, st))) return rc;
+            if ((rc = eval_samples_src(entry, scene, packed_fine, tables_fine, precision, rs, z_f, R, rays_per_obj, Kc + Kf, rgbs_f, aux_fine, st))) return rc;
         } else {
             // mlp_fine is None (models.py:242, eval/eval.py:140): the fine pass runs the coarse network on the merged
             // samples, Kc of which it has just evaluated -- evaluate the Kf new ones only and merge in sorted order
             if ((rc = sample_fine_src(rs, w_c, depth_c, z_c, ns, R, Kc, Kf - Kfd, Kfd, depth_std, lindisp, z_f, nullptr, z_new,
                                       ranks, stream))) return rc;
-            if ((rc = eval_samples_src(scene, packed_coarse, tables_coarse, precision, rs, z_new, R, rays_per_obj, Kf, rgbs_new, aux_coarse, st))) return rc;
+            if ((rc = eval_samples_src(entry, scene, packed_coarse, tables_coarse, precision, rs, z_new, R, rays_per_obj, Kf, rgbs_new, aux_coarse, st))) return rc;
             const long long n = (long long)R * (Kc + Kf);
             hipLaunchKernelGGL(merge_rgbsigma_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                (const float4 *)rgbs_c, (const float4 *)rgbs_new, ranks, R, Kc, Kf, (float4 *)rgbs_f);
@@ -442,7 +440,7 @@ extern "C" int pnr_render_forward(const PnrScene *scene, const void *packed_coar
                                   const float *u3, const float *n4, float *rgb_c, float *depth_c, float *weights_c,
                                   float *rgb_f, float *depth_f, float *weights_f, void *workspace, void *stream) {
     if (R > 0 && !u1) return pnr_fail(PNR_E_INVALID, "pnr_render_forward: null u1 (pnr_render_forward_seeded draws in-kernel)");
-    return render_impl(scene, packed_coarse, nullptr, packed_fine, nullptr, precision, explicit_rays(rays),
+    return render_impl("pnr_render_forward", scene, packed_coarse, nullptr, packed_fine, nullptr, precision, explicit_rays(rays),
                        explicit_noise(u1, u2, u3, n4), R, rays_per_obj, Kc, Kf, Kfd, depth_std, white_bkgd, lindisp, rgb_c, depth_c,
                        weights_c, rgb_f, depth_f, weights_f, workspace, nullptr, nullptr, stream);
 }
@@ -457,7 +455,7 @@ extern "C" int pnr_render_forward_folded(const PnrScene *scene, const void *pack
     if (!tables_coarse || (packed_fine && !tables_fine))
         return pnr_fail(PNR_E_INVALID, "pnr_render_forward_folded: every folded network needs its tables");
     if (R > 0 && !u1) return pnr_fail(PNR_E_INVALID, "pnr_render_forward_folded: null u1 (pnr_render_forward_seeded draws in-kernel)");
-    return render_impl(scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, explicit_rays(rays),
+    return render_impl("pnr_render_forward_folded", scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, explicit_rays(rays),
                        explicit_noise(u1, u2, u3, n4), R, rays_per_obj, Kc, Kf, Kfd, depth_std, white_bkgd, lindisp, rgb_c, depth_c,
                        weights_c, rgb_f, depth_f, weights_f, workspace, aux_coarse, aux_fine, stream);
 }
@@ -471,7 +469,7 @@ extern "C" int pnr_render_forward_seeded(const PnrScene *scene, const void *pack
                                          void *stream) {
     if ((tables_coarse == nullptr) != (tables_fine == nullptr) && packed_fine)
         return pnr_fail(PNR_E_INVALID, "pnr_render_forward_seeded: both networks folded or neither");
-    return render_impl(scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, explicit_rays(rays),
+    return render_impl("pnr_render_forward_seeded", scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, explicit_rays(rays),
                        seeded_noise(seed, ray_id_offset, ray_id_stride, rays_per_obj), R, rays_per_obj, Kc, Kf, Kfd, depth_std,
                        white_bkgd, lindisp, rgb_c, depth_c, weights_c, rgb_f, depth_f, weights_f, workspace, aux_coarse, aux_fine, stream);
 }
@@ -491,10 +489,11 @@ extern "C" int pnr_render_views(const PnrScene *scene, const void *packed_coarse
                                 const float *u3, const float *n4, unsigned long long seed, float *rgb_c, float *depth_c,
                                 float *weights_c, float *rgb_f, float *depth_f, float *weights_f, void *workspace,
                                 const PnrSplitAux *aux_coarse, const PnrSplitAux *aux_fine, void *stream) {
-    if (!scene || NV < 0 || W <= 0 || H <= 0) return pnr_fail(PNR_E_INVALID, "pnr_render_views: bad sizes");
+    if (int rc = check_scene(scene, "pnr_render_views")) return rc;
+    if (NV < 0 || W <= 0 || H <= 0) return pnr_fail(PNR_E_INVALID, "pnr_render_views: bad sizes");
     if (NV == 0) return PNR_OK;
     if (!poses_c2w) return pnr_fail(PNR_E_INVALID, "pnr_render_views: null poses");
-    if (scene->SB <= 0 || NV % scene->SB != 0) return pnr_fail(PNR_E_INVALID, "pnr_render_views: NV must be a multiple of SB (views grouped per object)");
+    if (NV % scene->SB != 0) return pnr_fail(PNR_E_INVALID, "pnr_render_views: NV must be a multiple of SB (views grouped per object)");
     const long long R = (long long)NV * W * H;
     if (R > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_render_views: too many rays for one call");
     if (packed_fine && ((tables_coarse == nullptr) != (tables_fine == nullptr)))
@@ -503,7 +502,7 @@ extern "C" int pnr_render_views(const PnrScene *scene, const void *packed_coarse
     rs.poses = poses_c2w; rs.W = W; rs.H = H; rs.fx = fx; rs.fy = fy; rs.cx = cx; rs.cy = cy; rs.z_near = z_near; rs.z_far = z_far;
     const int per_obj = (int)(R / scene->SB);
     const NoiseSrc ns = (u1 || u2 || u3 || n4) ? explicit_noise(u1, u2, u3, n4) : seeded_noise(seed, 0, per_obj, per_obj);
-    return render_impl(scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, rs, ns, (int)R, per_obj, Kc, Kf, Kfd,
+    return render_impl("pnr_render_views", scene, packed_coarse, tables_coarse, packed_fine, tables_fine, precision, rs, ns, (int)R, per_obj, Kc, Kf, Kfd,
                        depth_std, white_bkgd, lindisp, rgb_c, depth_c, weights_c, rgb_f, depth_f, weights_f, workspace, aux_coarse, aux_fine,
                        stream);
 }

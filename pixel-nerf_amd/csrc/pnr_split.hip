@@ -37,6 +37,7 @@
 
 #include "pnr_common.h"
 #include "pnr_device.h"
+#include "pnr_entry.h"
 #include "pnr_internal.h"
 #include "pnr_layout.h"
 
@@ -1165,24 +1166,14 @@ int check_split_aux(const PnrSplitAux *aux, int precision, const char *entry) {
     return PNR_OK;
 }
 
-// aux: checked by the entry (check_split_aux)
+// q: from ray_samples() / points() (pnr_entry.h: scene, sizes and limits checked); aux: checked by the entry (check_split_aux)
 static int split_launch(const PnrScene *s, const void *packed, const void *tables, EvalParams &q, bool rays, const PnrSplitAux *aux,
                         hipStream_t st) {
-    if (!s || !packed || !tables || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: null argument");
-    if (s->SB <= 0 || s->Hl < 2 || s->Wl < 2) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: bad scene shape");
-    if (s->NS <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: NS must be positive");
-    if (!(s->n_focal == 1 || s->n_focal == s->SB) || !(s->n_c == 1 || s->n_c == s->SB))
-        return pnr_fail(PNR_E_INVALID, "pnr_eval_split: focal / c must have 1 or SB rows");
+    if (!packed || !tables || !q.out) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: null argument");
     if (q.P == 0) return PNR_OK;
-    if (q.P > 0x7fffff80LL) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: too many points (P must stay below 2^31)");
-    if ((long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT > 0xffffffffLL)
-        return pnr_fail(PNR_E_INVALID, "pnr_eval_split: feature grid too large (SB*NS*Hl*Wl*512 must stay below 2^32 elements)");
-    scene_params(q, *s);
-    q.wstream = (const char *)packed;
-    q.bias = (const float *)((const char *)packed + BIAS_OFFSET_BYTES);
-    q.bout = (const float *)((const char *)packed + BOUT_OFFSET_BYTES);
+    set_packed(q, packed);
     q.tables = (const char *)tables;
-    q.table_stride = (long long)s->SB * s->NS * s->Hl * s->Wl * C_LAT;
+    q.table_stride = grid_elems(*s);
     const bool mv = s->NS > 1;
     if (mv && !q.mv_ws) return pnr_fail(PNR_E_INVALID, "pnr_eval_split: a multi-view scene needs PnrScene.mv_workspace (pnr_mv_workspace_bytes())");
     const int ncu = device_cus();
@@ -1261,25 +1252,22 @@ int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long l
 
 extern "C" size_t pnr_packed_mlp_split_bytes(void) { return 2 * pnr::PACKED_BYTES; }
 
-int pnr::eval_samples_split_src(const PnrScene *scene, const void *packed_split, const void *tables_f32, const RaySrc &src,
-                                const float *z, int R, int rays_per_obj, int K, float *rgbsigma, const PnrSplitAux *aux,
-                                hipStream_t stream) {
-    if (R < 0 || K <= 0 || rays_per_obj <= 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split: bad sizes");
-    if (R > 0 && ((!src.rays && !src.poses) || !z)) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split: null rays/z");
-    if (scene && (long long)rays_per_obj * scene->SB != R) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split: R != SB * rays_per_obj");
+int pnr::eval_samples_split_src(const char *entry, const PnrScene *scene, const void *packed_split, const void *tables_f32,
+                                const RaySrc &src, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
+                                const PnrSplitAux *aux, hipStream_t stream) {
     pnr::EvalParams q = {};
-    q.rays = src.rays; q.cam = src; q.cam.rays = nullptr;
-    q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
+    if (int rc = pnr::ray_samples(q, entry, scene, src, z, R, rays_per_obj, K, true, pnr::EVAL_LIMITS)) return rc;
+    q.out = rgbsigma;
     return pnr::split_launch(scene, packed_split, tables_f32, q, true, aux, stream);
 }
 
 // training forward of the fp32-class path (pnr_f32.hip, pnr_eval_ray_samples_split_train): outputs + what the backward keeps
-int pnr::eval_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *rays,
-                                  const float *z, int R, int rays_per_obj, int K, float *rgbsigma, void *const *img_a, void *const *img_n,
-                                  float *x5, void *masks, const PnrSplitAux *aux, hipStream_t stream) {
-    if (!rays || !z || !img_a || !img_n || !x5 || !masks) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null argument");
-    pnr::EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma;
+int pnr::eval_samples_split_train(const PnrScene *scene, const void *packed_split, const void *tables_f32, const EvalParams &samples,
+                                  float *rgbsigma, void *const *img_a, void *const *img_n, float *x5, void *masks,
+                                  const PnrSplitAux *aux, hipStream_t stream) {
+    if (!img_a || !img_n || !x5 || !masks) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null argument");
+    pnr::EvalParams q = samples;
+    q.out = rgbsigma;
     for (int b = 0; b < 5; ++b) {
         if (!img_a[b] || !img_n[b]) return pnr_fail(PNR_E_INVALID, "pnr_eval_ray_samples_split_train: null operand buffer");
         q.s_a[b] = (char *)img_a[b]; q.s_n[b] = (char *)img_n[b];
@@ -1293,9 +1281,8 @@ extern "C" int pnr_eval_ray_samples_split(const PnrScene *scene, const void *pac
                                           const float *rays, const float *z, int R, int rays_per_obj, int K, float *rgbsigma,
                                           const PnrSplitAux *aux, void *stream) {
     if (int rc = pnr::check_split_aux(aux, PNR_PREC_F16X3, "pnr_eval_ray_samples_split")) return rc;
-    pnr::RaySrc src = {};
-    src.rays = rays;
-    return pnr::eval_samples_split_src(scene, packed_split, tables_f32, src, z, R, rays_per_obj, K, rgbsigma, aux, (hipStream_t)stream);
+    return pnr::eval_samples_split_src("pnr_eval_ray_samples_split", scene, packed_split, tables_f32, pnr::explicit_rays(rays), z, R,
+                                       rays_per_obj, K, rgbsigma, aux, (hipStream_t)stream);
 }
 
 #ifdef PNR_VARIANT
@@ -1304,9 +1291,10 @@ extern "C" int pnr_eval_ray_samples_split(const PnrScene *scene, const void *pac
 extern "C" int pnr_debug_phase_timing_split(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *rays,
                                             const float *z, int R, int rays_per_obj, int K, float *rgbsigma, unsigned long long *tim,
                                             void *stream) {
-    if (!tim || !rays || !z) return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing_split: null argument");
+    if (!tim) return pnr_fail(PNR_E_INVALID, "pnr_debug_phase_timing_split: null argument");
     pnr::EvalParams q = {};
-    q.rays = rays; q.z = z; q.K = K; q.per_obj = rays_per_obj; q.P = (long long)R * K; q.out = rgbsigma; q.tim = tim;
+    if (int rc = pnr::ray_samples(q, "pnr_debug_phase_timing_split", scene, rays, z, R, rays_per_obj, K, false, pnr::EVAL_LIMITS)) return rc;
+    q.out = rgbsigma; q.tim = tim;
     return pnr::split_launch(scene, packed_split, tables_f32, q, true, nullptr, (hipStream_t)stream);
 }
 #endif
@@ -1314,10 +1302,8 @@ extern "C" int pnr_debug_phase_timing_split(const PnrScene *scene, const void *p
 extern "C" int pnr_eval_points_split(const PnrScene *scene, const void *packed_split, const void *tables_f32, const float *xyz,
                                      const float *viewdirs, int B, float *rgbsigma, const PnrSplitAux *aux, void *stream) {
     if (int rc = pnr::check_split_aux(aux, PNR_PREC_F16X3, "pnr_eval_points_split")) return rc;
-    if (B < 0) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_split: bad sizes");
-    if (B > 0 && (!xyz || !viewdirs)) return pnr_fail(PNR_E_INVALID, "pnr_eval_points_split: null xyz/viewdirs");
     pnr::EvalParams q = {};
-    q.xyz = xyz; q.viewdirs = viewdirs; q.K = 1; q.per_obj = B > 0 ? B : 1;
-    q.P = scene ? (long long)scene->SB * B : 0; q.out = rgbsigma;
+    if (int rc = pnr::points(q, "pnr_eval_points_split", scene, xyz, viewdirs, B, pnr::EVAL_LIMITS)) return rc;
+    q.out = rgbsigma;
     return pnr::split_launch(scene, packed_split, tables_f32, q, false, aux, (hipStream_t)stream);
 }

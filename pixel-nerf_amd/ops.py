@@ -65,6 +65,16 @@ class PackedMLP:
 F32_CHUNK_POINTS = 1 << 17  # points per chunk of the fp32 path (workspace ~1.4 GB x NS)
 
 
+def _ray_samples(rays, z, scene=None):
+    """rays (R,8) and their samples z (R,K), checked: (rays, z, R, K), with a scene also the rays per object"""
+    rays = _f32(rays, "rays", (None, 8))
+    R = rays.shape[0]
+    z = _f32(z, "z", (R, None))
+    if scene is None:
+        return rays, z, R, z.shape[1]
+    return rays, z, R, z.shape[1], max(R // scene.SB, 1)
+
+
 def _f32_workspace(lib, scene, P):
     chunk = max(64, min(int(P), F32_CHUNK_POINTS // scene.NS))
     nbytes = lib.pnr_eval_f32_workspace_bytes(scene.NS, chunk)
@@ -210,13 +220,11 @@ def fold_latent_rows(scene, state, rays, z, tables):
     NV, Hl, Wl, _ = scene.latent_nhwc.shape
     if tables.dtype != torch.float32 or tuple(tables.shape) != (3, NV, Hl, Wl, 512) or not tables.is_contiguous():
         raise _lib.PixelNerfHipError("fold_latent_rows: tables must be a contiguous (3, SB*NS, Hl, Wl, 512) fp32 tensor")
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     nbytes = int(lib.pnr_fold_latent_f32_rows_workspace_bytes(scene.ref))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=scene.device)
     with torch.cuda.device(scene.device):
-        _lib.check(lib.pnr_fold_latent_f32_rows(scene.ref, ctypes.byref(w), _p(rays), _p(z), R, max(R // scene.SB, 1), z.shape[1], _p(tables),
+        _lib.check(lib.pnr_fold_latent_f32_rows(scene.ref, ctypes.byref(w), _p(rays), _p(z), R, per_obj, K, _p(tables),
                                                 _p(ws), nbytes, _sat_word(scene.device), _stream()), "pnr_fold_latent_f32_rows")
     return tables
 
@@ -331,17 +339,14 @@ def eval_ray_samples(scene, packed, rays, z, tables=None):
     """rays (R,8), z (R,K) -> rgbsigma (R,K,4); R = SB * rays_per_obj.  tables: fold_latent() output when
     `packed` is a folded stream."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     if R % scene.SB != 0:
         raise ValueError("number of rays must be a multiple of the number of objects")
     out = torch.empty((R, K, 4), dtype=torch.float32, device=rays.device)
     if packed.precision == _lib.PREC_F32:
         ws, nbytes = _f32_workspace(lib, scene, R * K)
         with torch.cuda.device(rays.device):
-            _lib.check(lib.pnr_eval_ray_samples_f32(scene.ref, packed.wref, _p(rays), _p(z), R, max(R // scene.SB, 1), K,
+            _lib.check(lib.pnr_eval_ray_samples_f32(scene.ref, packed.wref, _p(rays), _p(z), R, per_obj, K,
                                                     _p(out), _p(ws), nbytes, _stream()), "pnr_eval_ray_samples_f32")
         return out
     _check_fold(packed, tables, "eval_ray_samples")
@@ -349,17 +354,17 @@ def eval_ray_samples(scene, packed, rays, z, tables=None):
         _check_split_tables(tables)
         with torch.cuda.device(rays.device):
             _lib.check(lib.pnr_eval_ray_samples_split(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), R,
-                                                      max(R // scene.SB, 1), K, _p(out), _split_aux(packed, rays.device), _stream()),
+                                                      per_obj, K, _p(out), _split_aux(packed, rays.device), _stream()),
                        "pnr_eval_ray_samples_split")
         return out
     with torch.cuda.device(rays.device):
         if tables is not None:
             _lib.check(lib.pnr_eval_ray_samples_folded(scene.ref, packed.ptr, _p(tables), packed.precision, _p(rays), _p(z), R,
-                                                       max(R // scene.SB, 1), K, _p(out), _stream()),
+                                                       per_obj, K, _p(out), _stream()),
                        "pnr_eval_ray_samples_folded")
         else:
             _lib.check(lib.pnr_eval_ray_samples(scene.ref, packed.ptr, packed.precision, _p(rays), _p(z), R,
-                                                max(R // scene.SB, 1), K, _p(out), _stream()),
+                                                per_obj, K, _p(out), _stream()),
                        "pnr_eval_ray_samples")
     return out
 
@@ -447,10 +452,7 @@ def point_features(scene, xyz, viewdirs):
 
 def composite(rays, z, rgbsigma, white_bkgd=False, want_weights=True):
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K = _ray_samples(rays, z)
     rgbsigma = _f32(rgbsigma, "rgbsigma", (R, K, 4))
     dev = rays.device
     weights = torch.empty((R, K), dtype=torch.float32, device=dev) if want_weights else None
@@ -1205,10 +1207,8 @@ def occupancy_mark_samples(rays, z, bits, reso, c1, c2):
     and in an occupied cell; a point outside the box is empty; a sample with a non-finite z, origin or direction component is
     kept.  No host synchronisation."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K = _ray_samples(rays, z)
+    dev = rays.device
     nx, ny, nz = _check_grid_args("occupancy_mark_samples", bits, reso, c1, c2, dev)
     if K < 1 or R * K >= 2 ** 31:
         raise ValueError(f"occupancy_mark_samples: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
@@ -1226,10 +1226,8 @@ def compact_samples(keep, rays, z):
     z.flatten()[index], M as a Python int).  The tensors are sized to M: the count is read on the host, the ONE synchronisation
     of a pass (they are the leading rows of R K-row allocations, which the kernels leave untouched beyond M)."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K = _ray_samples(rays, z)
+    dev = rays.device
     if not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or tuple(keep.shape) != (R, K) or keep.device != dev:
         raise ValueError(f"compact_samples: keep must be the ({R},{K}) uint8 tensor of occupancy_mark_samples on {dev}")
     if K < 1 or R * K >= 2 ** 31:
@@ -1465,15 +1463,12 @@ class BackwardDumps:
 def eval_ray_samples_train(scene, packed, rays, z):
     """eval_ray_samples + TrainDumps."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     dumps = TrainDumps.acquire(R * K, scene.NS, packed.precision, rays.device)
     out = torch.empty((R, K, 4), dtype=torch.float32, device=rays.device)
     with torch.cuda.device(rays.device):
         _lib.check(lib.pnr_eval_ray_samples_train(scene.ref, packed.ptr, packed.precision, _p(rays), _p(z), R,
-                                                  max(R // scene.SB, 1), K, _p(out), ctypes.byref(dumps.struct),
+                                                  per_obj, K, _p(out), ctypes.byref(dumps.struct),
                                                   _stream()), "pnr_eval_ray_samples_train")
     return out, dumps
 
@@ -1506,14 +1501,11 @@ def eval_ray_samples_f32_train(scene, weights, rays, z, split=False):
     split=False: exact fp32 MFMA products (validation grade); True: (head, tail) fp16 operand pairs, 3 f16 MFMAs per product
     (fp32-class, ~6x faster -- precision 'f16x3' under autograd)."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     saved = F32Saved(R * K, scene.NS, rays.device)
     out = torch.empty((R, K, 4), dtype=torch.float32, device=rays.device)
     with torch.cuda.device(rays.device):
-        _lib.check(lib.pnr_eval_ray_samples_f32_train(scene.ref, weights.wref, _p(rays), _p(z), R, max(R // scene.SB, 1), K, _p(out),
+        _lib.check(lib.pnr_eval_ray_samples_f32_train(scene.ref, weights.wref, _p(rays), _p(z), R, per_obj, K, _p(out),
                                                       ctypes.byref(saved.struct), int(bool(split)), _stream()), "pnr_eval_ray_samples_f32_train")
     saved.split = bool(split)
     return out, saved
@@ -1550,22 +1542,18 @@ def eval_ray_samples_split_train(scene, packed, tables, rays, z):
         raise ValueError("eval_ray_samples_split_train takes the folded 'f16x3' stream")
     if tables is None:
         raise ValueError("eval_ray_samples_split_train needs the folded lin_z tables (ops.fold_latent)")
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     saved = SplitSaved(R * K, scene.NS, rays.device)
     out = torch.empty((R, K, 4), dtype=torch.float32, device=rays.device)
     with torch.cuda.device(rays.device):
-        _lib.check(lib.pnr_eval_ray_samples_split_train(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), R, max(R // scene.SB, 1), K,
+        _lib.check(lib.pnr_eval_ray_samples_split_train(scene.ref, packed.ptr, _p(tables), _p(rays), _p(z), R, per_obj, K,
                                                         _p(out), ctypes.byref(saved.struct), _split_aux(packed, rays.device), _stream()),
                        "pnr_eval_ray_samples_split_train")
     return out, saved
 
 
-def mlp_backward_split(weights, saved, g_out, want_d_in=False, want_grads=True):
-    """Backward of eval_ray_samples_split_train (pnr_mlp_backward_split): weights = PackedMLP of precision 'f32' (the raw
-    nn.Linear tensors; the transposed streams are packed inside the call).  -> (grads, d_zlat, d_in | None) like mlp_backward_f32."""
+def _mlp_backward(entry, weights, saved, g_out, want_d_in, want_grads, split_flag=None):
+    """the shared body of mlp_backward_split (split_flag None: the entry has no such argument, always scaled) and mlp_backward_f32"""
     lib = _lib.load()
     P, NS = saved.P, saved.NS
     g_out = _f32(g_out, "g_out", (P, 4))
@@ -1578,38 +1566,26 @@ def mlp_backward_split(weights, saved, g_out, want_d_in=False, want_grads=True):
         gref = ctypes.byref(gstruct)
     d_zlat = torch.empty((NS * P, 512), dtype=torch.float32, device=dev)
     d_in = torch.empty((NS * P, 42), dtype=torch.float32, device=dev) if want_d_in else None
-    sc = grad_scale(g_out)  # device [s, 1/s]: no host synchronisation
-    nbytes = lib.pnr_mlp_backward_split_workspace_bytes(P, NS)
+    sc = grad_scale(g_out) if split_flag in (None, True) else None  # device [s, 1/s]: no host synchronisation
+    nbytes = getattr(lib, entry + "_workspace_bytes")(P, NS)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    flag = () if split_flag is None else (int(split_flag),)
     with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mlp_backward_split(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, gref,
-                                              _p(d_zlat), _p(d_in), _p(sc), _p(ws), nbytes, _stream()), "pnr_mlp_backward_split")
+        _lib.check(getattr(lib, entry)(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, gref, _p(d_zlat), _p(d_in), *flag,
+                                       _p(sc), _p(ws), nbytes, _stream()), entry)
     return grads, d_zlat, d_in
+
+
+def mlp_backward_split(weights, saved, g_out, want_d_in=False, want_grads=True):
+    """Backward of eval_ray_samples_split_train (pnr_mlp_backward_split): weights = PackedMLP of precision 'f32' (the raw
+    nn.Linear tensors; the transposed streams are packed inside the call).  -> (grads, d_zlat, d_in | None) like mlp_backward_f32."""
+    return _mlp_backward("pnr_mlp_backward_split", weights, saved, g_out, want_d_in, want_grads)
 
 
 def mlp_backward_f32(weights, saved, g_out, want_d_in=False, want_grads=True):
     """-> ({reference state_dict key: fp32 gradient}, d_zlat (rows_v,512), d_in (rows_v,42) | None) of one ResnetFC: exact fp32
     MFMA products, or the split-operand (fp32-class) form when the forward ran with split=True."""
-    lib = _lib.load()
-    P, NS = saved.P, saved.NS
-    g_out = _f32(g_out, "g_out", (P, 4))
-    dev = g_out.device
-    grads, gref, _keep = None, None, None
-    if want_grads:  # (want_grads=False: grads == NULL, the data-gradient chain alone, grads returned as None)
-        grads = {k: torch.empty(_MLP_SHAPES.get(k, (512, 512) if k.endswith("weight") else (512,)), dtype=torch.float32, device=dev)
-                 for k in _MLP_KEYS}
-        gstruct, _keep = _weights_struct(grads)
-        gref = ctypes.byref(gstruct)
-    d_zlat = torch.empty((NS * P, 512), dtype=torch.float32, device=dev)
-    d_in = torch.empty((NS * P, 42), dtype=torch.float32, device=dev) if want_d_in else None
-    split = bool(getattr(saved, "split", False))
-    sc = grad_scale(g_out) if split else None  # device [s, 1/s]: no host synchronisation
-    nbytes = lib.pnr_mlp_backward_f32_workspace_bytes(P, NS)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_mlp_backward_f32(weights.wref, ctypes.byref(saved.struct), _p(g_out), P, NS, gref,
-                                            _p(d_zlat), _p(d_in), int(split), _p(sc), _p(ws), nbytes, _stream()), "pnr_mlp_backward_f32")
-    return grads, d_zlat, d_in
+    return _mlp_backward("pnr_mlp_backward_f32", weights, saved, g_out, want_d_in, want_grads, bool(getattr(saved, "split", False)))
 
 
 def composite_backward(rays, z, rgbsigma, white_bkgd, d_rgb, d_depth=None, d_weights=None, want_dz=False,
@@ -1617,10 +1593,7 @@ def composite_backward(rays, z, rgbsigma, white_bkgd, d_rgb, d_depth=None, d_wei
     """-> dL/d(rgb sigma) per point (R,K,4) [after the output activations, or in front of them with
     pre_activation=True], optionally dL/dz (R,K) and (want_dfar) dL/d(far) (R,) through the last delta far - z_{K-1}."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K = _ray_samples(rays, z)
     rgbsigma = _f32(rgbsigma, "rgbsigma", (R, K, 4))
     d_rgb = _f32(d_rgb, "d_rgb", (R, 3))
     d_depth = None if d_depth is None else _f32(d_depth, "d_depth", (R,))
@@ -1700,16 +1673,13 @@ def camera_backward(scene, rays, z, d_in42, d_zlat, dz_comp=None, d_far=None, ra
 def position_backward(scene, rays, z, d_in42, d_zlat, d_z):
     """accumulate dL/dz through the network inputs into d_z (R,K)."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     rows = scene.NS * R * K
     d_in42 = _f32(d_in42, "d_in42", (rows, 42))
     d_zlat = _f32(d_zlat, "d_zlat", (rows, 512))
     d_z = _f32(d_z, "d_z", (R, K))
     with torch.cuda.device(rays.device):
-        _lib.check(lib.pnr_position_backward(scene.ref, _p(rays), _p(z), R, max(R // scene.SB, 1), K, _p(d_in42),
+        _lib.check(lib.pnr_position_backward(scene.ref, _p(rays), _p(z), R, per_obj, K, _p(d_in42),
                                              _p(d_zlat), _p(d_z), _stream()), "pnr_position_backward")
     return d_z
 
@@ -1719,10 +1689,7 @@ def depth_sample_backward(scene, rays, z, ranks, n4, depth_c, depth_std, d_in42,
     (positional code, projection + lookup) + compositing term dz_comp at the samples' sorted positions `ranks`, through
     the clamp; the per-(view, ray, sample) terms are summed in a fixed order (bit-reproducible)."""
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     Kfd = ranks.shape[1]
     if ranks.dtype != torch.int32 or not ranks.is_contiguous() or ranks.shape[0] != R:
         raise ValueError("ranks must be a contiguous (R, Kfd) int32 tensor (ops.sample_fine(..., want_ranks=True))")
@@ -1734,7 +1701,7 @@ def depth_sample_backward(scene, rays, z, ranks, n4, depth_c, depth_std, d_in42,
     dz_comp = None if dz_comp is None else _f32(dz_comp, "dz_comp", (R, K))
     contrib = torch.empty((scene.NS, R, Kfd), dtype=torch.float32, device=rays.device)
     with torch.cuda.device(rays.device):
-        _lib.check(lib.pnr_depth_sample_backward(scene.ref, _p(rays), _p(z), R, max(R // scene.SB, 1), K, _p(ranks), _p(n4), Kfd,
+        _lib.check(lib.pnr_depth_sample_backward(scene.ref, _p(rays), _p(z), R, per_obj, K, _p(ranks), _p(n4), Kfd,
                                                  _p(depth_c), float(depth_std), _p(d_in42), _p(d_zlat), _p(dz_comp), _p(contrib),
                                                  _stream()), "pnr_depth_sample_backward")
     return contrib.sum(dim=(0, 2))
@@ -1825,12 +1792,8 @@ def latent_scatter_single_owner(scene, R, K):
 
 def latent_scatter(scene, rays, z, d_zlat, d_latent_nhwc):
     lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    R = rays.shape[0]
-    z = _f32(z, "z", (R, None))
-    K = z.shape[1]
+    rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     d_zlat = _f32(d_zlat, "d_zlat", (scene.NS * R * K, 512))
-    per_obj = max(R // scene.SB, 1)
     # workspace from torch's allocator (projected positions + segment lists of the LDS-slab form): capture-safe, stream-ordered
     nbytes = int(lib.pnr_latent_scatter_workspace_bytes(scene.ref, R, per_obj, K))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=rays.device) if nbytes else None

@@ -77,7 +77,7 @@ def test_training_step_updates_and_is_deterministic(dev):
     """One optimiser step through the reference-style loop: render_par(rays, want_weights=True)
     -> MSE coarse + fine -> backward -> Adam (train/train.py:199-215, trainlib/trainer.py:232-237).
     Parameter gradients are bit-reproducible (fixed-order reductions, no atomics); so is the latent gradient on grids that take
-    the LDS-slab scatter (one zeroed buffer per pass, at most two commuting adds per element: pnr_bwd.hip, autograd.py)."""
+    the LDS-slab scatter (one zeroed buffer per pass, at most two commuting adds per element: pnr_scatter.hip, autograd.py)."""
     from pixelnerf_amd.model import make_model
     from pixelnerf_amd.render import NeRFRenderer
     from pixelnerf_amd.util import DotMap

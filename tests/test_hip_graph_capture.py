@@ -6,7 +6,7 @@ latent scatter with its segment pre-pass -- must be capturable: no allocation, n
 inside the library (the scatter's workspace comes from the caller since C ABI rev 7, the multi-view kernels' view-sum scratch since
 rev 10: a scratch keyed by stream was not found on the capture stream and failed the capture).  The replayed graph must produce the
 bits of the eager step: parameter gradients are fixed-order reductions, the grid gradient comes out of the LDS-slab scatter
-(pnr_bwd.hip).
+(pnr_scatter.hip).
 """
 import os
 import subprocess

@@ -91,7 +91,7 @@ def trained(dev, request):
 def test_training_through_the_hip_path_is_bit_reproducible(dev, name):
     """Two runs of the same 12 Adam steps (both ResnetFCs + the feature grid, default precision, the renderer's own torch draws
     under one seed) end in the SAME bits: weight gradients are fixed-order split-K reductions, the grid gradient comes out of the
-    LDS-slab scatter with at most two commuting adds per element (pnr_bwd.hip latent_scatter_owner_kernel; autograd.py keeps one
+    LDS-slab scatter with at most two commuting adds per element (pnr_scatter.hip latent_scatter_owner_kernel; autograd.py keeps one
     zeroed buffer per pass).  This is what makes the trained-weights fixture above the same network on every run."""
     from pixelnerf_amd.model import make_model
     from pixelnerf_amd.render import NeRFRenderer

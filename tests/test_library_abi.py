@@ -153,7 +153,7 @@ def test_argument_validation_without_gpu(lib):
     assert lib.pnr_position_backward(None, None, None, 1, 1, 1, None, None, None, None) == -1
     # round-6 entries (ABI rev 8): the row-wise fold of training passes on large grids, the scatter's ownership query
     sc = _lib.PnrScene()
-    sc.SB, sc.NS, sc.Hl, sc.Wl = 2, 3, 150, 200
+    sc.SB, sc.NS, sc.Hl, sc.Wl, sc.n_focal, sc.n_c = 2, 3, 150, 200, 1, 1  # (the size entries answer 0 for a scene the launch would refuse)
     M = 2 * 3 * 150 * 200
     nb = (M + 4095) // 4096
     assert lib.pnr_fold_latent_f32_rows_workspace_bytes(ctypes.byref(sc)) == nb * 4096 + (nb + 4 + M) * 4
