@@ -906,6 +906,38 @@ int pnr_compact_samples(const uint8_t *keep, const float *rays, const float *z, 
 int pnr_expand_rgbsigma(const int32_t *index, const float *rgbsigma_c /*(M,4)*/, int M, long long N,
                         float *rgbsigma /*(N,4)*/, void *stream);
 
+/* ---- early ray termination (inference): the network is not run behind the point where a ray has gone opaque.
+ * A pass with K sorted samples per ray is cut into stages at sample indices 0 = b_0 < b_1 < ... < b_S = K.  A ray STOPS at
+ * the first boundary b_s, s >= 1, at which the transmittance in front of sample b_s,
+ *   T = prod_{j < b_s} (1 - alpha_j + 1e-10),  alpha_j = 1 - exp(-delta_j relu(sigma_j)),  delta_j = z_{j+1} - z_j
+ *   (delta_{K-1} = far - z_{K-1}; src/render/nerf.py:178-182,228-235, every operation in fp32 as pnr_composite performs it),
+ * is <= eps; the samples k >= b_s of a stopped ray get rgb sigma = 0.  Stage by stage a caller runs
+ *   pnr_termination_mark(stage) -> pnr_compact_samples -> pnr_eval_ray_samples*(rays_c, z_c, R = M, K = 1) -> placement of the
+ *   kept samples into the (R,K,4) buffer, which starts as zeros,
+ * and after the last stage one pnr_composite.  The result is pnr_composite of the dense pass's outputs with rgb sigma = 0 at
+ * every sample behind its ray's stop, bit for bit (with the pair rule of the split-operand kernel stated above): the weights in
+ * front of the stop are the dense weights, behind it they are 0, and the transmittance that is left goes to the background.
+ * On a ray with every delta >= 0 the weights behind the stop and the final transmittance of the dense pass sum to T at the
+ * stop (up to the K 1e-10 terms), so with rgb in [0,1] every channel moves by at most eps -- towards the background -- and
+ * the depth by at most eps far.  A ray whose last sample lies beyond `far` has a negative last delta, hence a negative alpha
+ * and a factor above 1: the identity holds for it, the bound does not.
+ *
+ * pnr_termination_mark: rays (R,8) (only `far`, column 7, is read), z (R,K), rgbsigma (R,K,4): the outputs so far.
+ *   t_front[r] (nullable) = T in front of sample k_begin: exactly the value pnr_composite forms for that sample from the same
+ *                buffer (chunks of 64 samples, a product scan per chunk, the chunk totals carried), 1 for k_begin = 0.  Only
+ *                the sigmas of the samples < k_begin are read; z[r, k_begin] gives the last delta, `far` when k_begin = K.
+ *   keep[r,k]  = 1 iff k_begin <= k < k_end, and not (t_front[r] <= eps), and keep_in is null or keep_in[r,k] != 0
+ *                (keep_in (R,K) bytes: e.g. pnr_occupancy_mark_samples' answer).  A NaN transmittance does not stop the ray:
+ *                the rule errs towards rendering.  EVERY byte of keep is written, 0 outside the stage.
+ * One wavefront per ray, no atomics (two calls give the same bytes), no scratch, no LDS.  Later stages of a ray that has
+ * stopped see zeros behind the stop, whose factors are exactly 1; a caller that must not depend on the last place of that
+ * product also ANDs its own record of the stopped rays into keep, as the renderer does.
+ * PNR_E_INVALID, before any HIP call: R < 0, K < 1, R K >= 2^31, not 0 <= k_begin <= k_end <= K, eps NaN or outside (0, 1),
+ * a null rays / z / rgbsigma / keep (with R > 0).  R = 0: no-op. */
+int pnr_termination_mark(const float *rays, const float *z, const float *rgbsigma /*(R,K,4)*/, int R, int K, int k_begin,
+                         int k_end, float eps, const uint8_t *keep_in /*(R,K), nullable*/, uint8_t *keep /*(R,K)*/,
+                         float *t_front /*(R), nullable*/, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

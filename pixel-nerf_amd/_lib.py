@@ -195,6 +195,7 @@ PROTOTYPES = {
     "pnr_compact_samples_workspace_bytes": (_SZ, [ctypes.c_longlong]),
     "pnr_compact_samples": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "pnr_expand_rgbsigma": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _P]),
+    "pnr_termination_mark": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }

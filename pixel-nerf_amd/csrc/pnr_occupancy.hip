@@ -5,6 +5,7 @@
 // caller renders the survivors only; a culled ray gets what src/render/nerf.py:178-182,223-249 composites from sigma == 0.
 // The rays that remain can also skip the network on their samples in empty cells: occupancy_mark_kernel classifies every sample,
 // compact_* gathers the kept ones into a list of one-sample rays, expand_* puts the network's answers back between zeros.
+// termination_mark_kernel feeds the same compaction with the samples of one stage of the fine pass whose ray has not gone opaque.
 // Geometry and semantics: include/pixelnerf_hip.h.  One owner thread per output word / ray / sample, no atomics: the same bytes every run.
 #include <hip/hip_runtime.h>
 
@@ -272,6 +273,43 @@ expand_scatter_kernel(const int32_t *__restrict__ index, const float4 *__restric
     if (s >= 0 && s < N) rgbsigma[s] = rgbsigma_c[m];  // (a row outside the output is the caller's error: skipped)
 }
 
+// ---- early ray termination: which samples of a stage still need the network ----
+constexpr int TERM_WAVES = 4;  // rays per workgroup, one wavefront each (composite_kernel's shape)
+
+// One wavefront per ray.  The transmittance in front of sample k_begin is composite_kernel's own value for that sample, formed
+// the same way: chunks of 64 samples, the factor 1 - alpha + 1e-10 per lane, an inclusive product scan, the chunk totals carried
+// (lane l of a scan reads lanes <= l only, so the lanes at and behind k_begin, which hold 1, do not enter).  Then the wave writes
+// the ray's K keep bytes.  No atomics, no LDS, nothing behind k_begin is read from rgbsigma.
+__global__ void __launch_bounds__(TERM_WAVES * 64)
+termination_mark_kernel(const float *__restrict__ rays, const float *__restrict__ z, const float *__restrict__ rgbsigma, int R, int K,
+                        int k_begin, int k_end, float eps, const uint8_t *__restrict__ keep_in, uint8_t *__restrict__ keep,
+                        float *__restrict__ t_front) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * TERM_WAVES + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const float *zr = z + (size_t)r * K;
+    float T = 1.f;  // prod_{j < c0} (1 - a_j + 1e-10), then of every j < k_begin
+    for (int c0 = 0; c0 < k_begin; c0 += 64) {
+        const int i = c0 + lane;
+        float tfac = 1.f;
+        if (i < k_begin) {
+            const float znext = (i + 1 < K) ? zr[i + 1] : rays[(size_t)r * 8 + 7];  // nerf.py:181: the last delta is far - z_last
+            const float delta = znext - zr[i];
+            const float alpha = 1.f - expf(-delta * fmaxf(rgbsigma[((size_t)r * K + i) * 4 + 3], 0.f));  // :228
+            tfac = 1.f - alpha + 1e-10f;                                                                  // :230-232
+        }
+        const float incl = wave_scan_mul(tfac, lane);
+        const int last = k_begin - c0 < 64 ? k_begin - c0 - 1 : 63;  // the last lane in front of k_begin
+        T = T * __shfl(incl, last, 64);
+    }
+    const bool alive = !(T <= eps);  // a NaN transmittance does not stop the ray
+    if (t_front && lane == 0) t_front[r] = T;
+    for (int k = lane; k < K; k += 64) {
+        const size_t s = (size_t)r * K + k;
+        keep[s] = (uint8_t)(alive && k >= k_begin && k < k_end && (!keep_in || keep_in[s] != 0));
+    }
+}
+
 static const char *occ_bad_dims(int nx, int ny, int nz) {
     if (nx < 2 || ny < 2 || nz < 2) return "every axis needs at least 2 grid points";
     if ((long long)(nx - 1) * (ny - 1) * (nz - 1) >= (1LL << 31)) return "the grid must have fewer than 2^31 cells";
@@ -354,6 +392,20 @@ extern "C" int pnr_occupancy_mark_samples(const float *rays, const float *z, int
     hipLaunchKernelGGL(pnr::occupancy_mark_kernel, dim3((unsigned)(((long long)N + pnr::OCC_THREADS - 1) / pnr::OCC_THREADS)),
                        dim3(pnr::OCC_THREADS), 0, (hipStream_t)stream, rays, z, K, N, bits, g, keep);
     return pnr_check_launch("pnr_occupancy_mark_samples");
+}
+
+extern "C" int pnr_termination_mark(const float *rays, const float *z, const float *rgbsigma, int R, int K, int k_begin, int k_end,
+                                    float eps, const uint8_t *keep_in, uint8_t *keep, float *t_front, void *stream) {
+    if (R < 0 || K < 1) return pnr_fail(PNR_E_INVALID, "pnr_termination_mark: bad sizes");
+    if ((long long)R * K >= (1LL << 31)) return pnr_fail(PNR_E_INVALID, "pnr_termination_mark: R * K must be below 2^31");
+    if (k_begin < 0 || k_begin > k_end || k_end > K)
+        return pnr_fail(PNR_E_INVALID, "pnr_termination_mark: the stage must satisfy 0 <= k_begin <= k_end <= K");
+    if (!(eps > 0.f && eps < 1.f)) return pnr_fail(PNR_E_INVALID, "pnr_termination_mark: eps must lie in (0, 1)");  // (refuses a NaN)
+    if (R == 0) return PNR_OK;
+    if (!rays || !z || !rgbsigma || !keep) return pnr_fail(PNR_E_INVALID, "pnr_termination_mark: null argument");
+    hipLaunchKernelGGL(pnr::termination_mark_kernel, dim3((unsigned)((R + pnr::TERM_WAVES - 1) / pnr::TERM_WAVES)),
+                       dim3(pnr::TERM_WAVES * 64), 0, (hipStream_t)stream, rays, z, rgbsigma, R, K, k_begin, k_end, eps, keep_in, keep, t_front);
+    return pnr_check_launch("pnr_termination_mark");
 }
 
 extern "C" size_t pnr_compact_samples_workspace_bytes(long long N) {

@@ -1220,6 +1220,35 @@ def occupancy_mark_samples(rays, z, bits, reso, c1, c2):
     return keep
 
 
+def termination_mark(rays, z, rgbsigma, k_begin, k_end, eps, keep_in=None):
+    """The samples of one stage of a pass that still need the network (pnr_termination_mark; the contract is in
+    include/pixelnerf_hip.h): rays (R,8), z (R,K), rgbsigma (R,K,4) fp32 HIP tensors -- the outputs so far, read in front of k_begin
+    only --, 0 <= k_begin <= k_end <= K, 0 < eps < 1, keep_in None or (R,K) uint8 -> (keep (R,K) uint8, t_front (R,) fp32):
+    t_front = the transmittance in front of sample k_begin as ops.composite forms it, keep = 1 iff k_begin <= k < k_end and not
+    t_front <= eps and keep_in is None or non-zero there.  No host synchronisation."""
+    lib = _lib.load()
+    rays, z, R, K = _ray_samples(rays, z)
+    dev = rays.device
+    rgbsigma = _f32(rgbsigma, "rgbsigma", (R, K, 4))
+    k_begin, k_end, eps = int(k_begin), int(k_end), float(eps)
+    if K < 1 or R * K >= 2 ** 31:
+        raise ValueError(f"termination_mark: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+    if not 0 <= k_begin <= k_end <= K:
+        raise ValueError(f"termination_mark: the stage must satisfy 0 <= k_begin <= k_end <= K = {K}, got [{k_begin}, {k_end})")
+    if not 0.0 < eps < 1.0:
+        raise ValueError(f"termination_mark: eps must lie in (0, 1), got {eps}")
+    if keep_in is not None and (not isinstance(keep_in, torch.Tensor) or keep_in.dtype != torch.uint8 or tuple(keep_in.shape) != (R, K)
+                                or keep_in.device != dev):
+        raise ValueError(f"termination_mark: keep_in must be a ({R},{K}) uint8 tensor on {dev}")
+    keep = torch.empty((R, K), dtype=torch.uint8, device=dev)
+    t_front = torch.empty((R,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_termination_mark(_p(rays), _p(z), _p(rgbsigma), R, K, k_begin, k_end, eps,
+                                            None if keep_in is None else _p(keep_in.contiguous()), _p(keep), _p(t_front), _stream()),
+                   "pnr_termination_mark")
+    return keep, t_front
+
+
 def compact_samples(keep, rays, z):
     """Stable compaction of the marked samples (pnr_compact_samples): keep (R,K) uint8, rays (R,8), z (R,K) ->
     (index (M,) int32 -- the ascending ids r K + k of the samples with keep != 0 --, rays_c (M,8) = rays[index // K], z_c (M,) =
