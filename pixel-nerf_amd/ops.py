@@ -1077,7 +1077,7 @@ def marching_cubes(field, iso, c1=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0), check_
     nbytes = lib.pnr_marching_cubes_workspace_bytes(nx, ny, nz)
     ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=dev)
     counts = torch.empty((3,), dtype=torch.int32, device=dev)
-    lo, sc = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in scale])
+    lo, sc = _float3_pair(c1, scale)
     with torch.cuda.device(dev):
         _lib.check(lib.pnr_marching_cubes_count(_p(field), nx, ny, nz, float(iso), _p(ws), _p(counts), _stream()),
                    "pnr_marching_cubes_count")
@@ -1129,7 +1129,7 @@ def grid_normals(field, vertices, c1, scale):
         raise ValueError("grid_normals: c1, scale must have 3 entries each")
     nx, ny, nz = field.shape
     normals = torch.empty_like(vertices)
-    lo, sc = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in scale])
+    lo, sc = _float3_pair(c1, scale)
     with torch.cuda.device(field.device):
         _lib.check(lib.pnr_grid_normals(_p(field), nx, ny, nz, lo, sc, _p(vertices), vertices.shape[0], _p(normals), _stream()),
                    "pnr_grid_normals")
@@ -1158,33 +1158,6 @@ def occupancy_build(field, threshold, dilate=1):
     return bits, count
 
 
-def occupancy_clip_rays(rays, bits, reso, c1, c2, pad=0.0):
-    """Rays against an occupancy bitfield (pnr_occupancy_clip_rays): rays (R,8) fp32 HIP tensor, bits from occupancy_build of a
-    field with `reso` = (nx,ny,nz) points spanning [c1, c2].  -> (t_bounds (R,2) fp32, hit (R,) int32): hit = 1 iff the segment
-    t in [near, far] passes through an occupied cell, t_bounds = (max(near, t_enter - pad), min(far, t_exit + pad)) over those
-    cells; a miss keeps (near, far).  A ray that cannot be classified (non-finite, zero direction, near >= far) counts as hit."""
-    lib = _lib.load()
-    rays = _f32(rays, "rays", (None, 8))
-    if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
-        raise ValueError("occupancy_clip_rays: c1, c2, reso must have 3 entries each")
-    nx, ny, nz = (int(r) for r in reso)
-    nbytes = lib.pnr_occupancy_bytes(nx, ny, nz)
-    if nbytes == 0:
-        raise ValueError(f"occupancy_clip_rays: a grid needs at least 2 points per axis and fewer than 2^31 cells, got {(nx, ny, nz)}")
-    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or bits.dim() != 1 or bits.numel() != nbytes // 4:
-        raise ValueError(f"occupancy_clip_rays: bits must be the ({nbytes // 4},) int32 tensor of occupancy_build for reso {(nx, ny, nz)}")
-    if bits.device != rays.device:
-        raise ValueError(f"occupancy_clip_rays: bits live on {bits.device}, the rays on {rays.device}")
-    R, dev = rays.shape[0], rays.device
-    t_bounds = torch.empty((R, 2), dtype=torch.float32, device=dev)
-    hit = torch.empty((R,), dtype=torch.int32, device=dev)
-    lo, hi = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in c2])
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_occupancy_clip_rays(_p(rays), R, _p(bits.contiguous()), nx, ny, nz, lo, hi, float(pad), _p(t_bounds), _p(hit),
-                                               _stream()), "pnr_occupancy_clip_rays")
-    return t_bounds, hit
-
-
 def _check_grid_args(what, bits, reso, c1, c2, device):
     """-> (nx, ny, nz) of an occupancy bitfield checked against its geometry (occupancy_clip_rays / occupancy_mark_samples)"""
     lib = _lib.load()
@@ -1201,6 +1174,34 @@ def _check_grid_args(what, bits, reso, c1, c2, device):
     return nx, ny, nz
 
 
+def _check_sample_count(what, R, K):
+    if K < 1 or R * K >= 2 ** 31:
+        raise ValueError(f"{what}: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+
+
+def _float3_pair(a, b):
+    """two 3-vectors (box corners; origin and scale) as the C arrays the library takes"""
+    return (ctypes.c_float * 3)(*[float(v) for v in a]), (ctypes.c_float * 3)(*[float(v) for v in b])
+
+
+def occupancy_clip_rays(rays, bits, reso, c1, c2, pad=0.0):
+    """Rays against an occupancy bitfield (pnr_occupancy_clip_rays): rays (R,8) fp32 HIP tensor, bits from occupancy_build of a
+    field with `reso` = (nx,ny,nz) points spanning [c1, c2].  -> (t_bounds (R,2) fp32, hit (R,) int32): hit = 1 iff the segment
+    t in [near, far] passes through an occupied cell, t_bounds = (max(near, t_enter - pad), min(far, t_exit + pad)) over those
+    cells; a miss keeps (near, far).  A ray that cannot be classified (non-finite, zero direction, near >= far) counts as hit."""
+    lib = _lib.load()
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    nx, ny, nz = _check_grid_args("occupancy_clip_rays", bits, reso, c1, c2, dev)
+    t_bounds = torch.empty((R, 2), dtype=torch.float32, device=dev)
+    hit = torch.empty((R,), dtype=torch.int32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_occupancy_clip_rays(_p(rays), R, _p(bits.contiguous()), nx, ny, nz, lo, hi, float(pad), _p(t_bounds), _p(hit),
+                                               _stream()), "pnr_occupancy_clip_rays")
+    return t_bounds, hit
+
+
 def occupancy_mark_samples(rays, z, bits, reso, c1, c2):
     """Samples against an occupancy bitfield (pnr_occupancy_mark_samples): rays (R,8), z (R,K) fp32 HIP tensors -> keep (R,K) uint8,
     1 iff the point o + z d (separately rounded product and sum, the network kernels' own sample point) lies in the box [c1, c2]
@@ -1210,10 +1211,9 @@ def occupancy_mark_samples(rays, z, bits, reso, c1, c2):
     rays, z, R, K = _ray_samples(rays, z)
     dev = rays.device
     nx, ny, nz = _check_grid_args("occupancy_mark_samples", bits, reso, c1, c2, dev)
-    if K < 1 or R * K >= 2 ** 31:
-        raise ValueError(f"occupancy_mark_samples: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+    _check_sample_count("occupancy_mark_samples", R, K)
     keep = torch.empty((R, K), dtype=torch.uint8, device=dev)
-    lo, hi = (ctypes.c_float * 3)(*[float(v) for v in c1]), (ctypes.c_float * 3)(*[float(v) for v in c2])
+    lo, hi = _float3_pair(c1, c2)
     with torch.cuda.device(dev):
         _lib.check(lib.pnr_occupancy_mark_samples(_p(rays), _p(z), R, K, _p(bits.contiguous()), nx, ny, nz, lo, hi, _p(keep), _stream()),
                    "pnr_occupancy_mark_samples")
@@ -1231,8 +1231,7 @@ def termination_mark(rays, z, rgbsigma, k_begin, k_end, eps, keep_in=None):
     dev = rays.device
     rgbsigma = _f32(rgbsigma, "rgbsigma", (R, K, 4))
     k_begin, k_end, eps = int(k_begin), int(k_end), float(eps)
-    if K < 1 or R * K >= 2 ** 31:
-        raise ValueError(f"termination_mark: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+    _check_sample_count("termination_mark", R, K)
     if not 0 <= k_begin <= k_end <= K:
         raise ValueError(f"termination_mark: the stage must satisfy 0 <= k_begin <= k_end <= K = {K}, got [{k_begin}, {k_end})")
     if not 0.0 < eps < 1.0:
@@ -1259,8 +1258,7 @@ def compact_samples(keep, rays, z):
     dev = rays.device
     if not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or tuple(keep.shape) != (R, K) or keep.device != dev:
         raise ValueError(f"compact_samples: keep must be the ({R},{K}) uint8 tensor of occupancy_mark_samples on {dev}")
-    if K < 1 or R * K >= 2 ** 31:
-        raise ValueError(f"compact_samples: needs K >= 1 and R * K < 2^31, got R = {R}, K = {K}")
+    _check_sample_count("compact_samples", R, K)
     N = R * K
     index = torch.empty((N,), dtype=torch.int32, device=dev)
     rays_c = torch.empty((N, 8), dtype=torch.float32, device=dev)

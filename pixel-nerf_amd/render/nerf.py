@@ -9,6 +9,9 @@ sampling and compositing run as HIP kernels around the caller's model, chunked b
 eval_batch_size exactly like the reference -- and differentiably (autograd.composite_autograd /
 sample_fine_autograd), so a renderer around an arbitrary nn.Module trains as it does in the reference.
 
+What the reference does not have -- occupancy-grid culling, skip_empty, early ray termination of inference renders -- is in
+render/accel.py; forward and render_views document its keywords and hand the call over as one accel.Accel record.
+
 Random numbers.  `rng="philox"` (default in eval mode with a pixelnerf_amd net): the sampling kernels draw from a
 counter-based generator (Philox4x32-10) keyed by a 64-bit seed -- `torch.initial_seed()` of the ray device's generator
 mixed with that generator's Philox offset (advanced per call, host side), so `torch.manual_seed(s)` makes a run
@@ -21,6 +24,7 @@ import torch
 
 from .. import ops
 from ..util.dotmap import DotMap
+from . import accel as _accel
 
 
 TERMINATE_STAGES = 8  # default number of stages of a terminated fine pass: the fastest of 2 / 4 / 8 without a grid (profiles/termination_notes.md)
@@ -204,25 +208,21 @@ class NeRFRenderer(torch.nn.Module):
         :param terminate_stages the number S of stages -- boundaries at 2 ((K s) // (2 S)) --, or the increasing sequence of the
         boundaries inside (0, K) themselves; 1: no boundary, the dense render
         :return DotMap {coarse:{rgb (SB,B,3), depth (SB,B)[, weights (SB,B,K)]}, fine:{...}}"""
-        self._check_skip_args(skip_empty, occupancy)
+        accel = _accel.Accel.parse(self, occupancy, tighten, skip_empty, terminate, terminate_stages)
         with torch.profiler.record_function("renderer_forward"):  # the reference's scope name (nerf.py:264)
-            if occupancy is not None or terminate is not None:
-                assert len(rays.shape) == 3
-                self._apply_sched()
-                flat = rays.reshape(-1, 8).float().contiguous()
-                bounds = self._check_culled_call(model, flat, rays.shape[0], skip_empty, occupancy, terminate, terminate_stages)
-                res = self._render_culled(model, flat, self.ray_id_offset, occupancy, tighten, want_weights, _noise,
-                                          self._culled_seed(model, flat.device, _noise), skip_empty, terminate, bounds)[0]
-                outputs = DotMap(coarse=self._format(res["coarse"], 1, want_weights))
-                if "fine" in res:
-                    outputs.fine = self._format(res["fine"], 1, want_weights)
-                return outputs
+            if accel is not None:  # (render/accel.py: what the reference does not have)
+                return _accel.forward(self, model, rays, want_weights, _noise, accel)
             return self._forward(model, rays, want_weights, _noise)
 
     def _apply_sched(self):
         if self.sched is not None and self.last_sched.item() > 0:
             self.n_coarse = self.sched[1][self.last_sched.item() - 1]
             self.n_fine = self.sched[2][self.last_sched.item() - 1]
+
+    def _fine_counts(self):
+        """(Kf, Kfd): the samples of the fine pass (0 without one) and how many of them are depth samples"""
+        Kf = self.n_fine if self.using_fine else 0
+        return Kf, min(self.n_fine_depth, Kf)
 
     @staticmethod
     def _is_fused(model):
@@ -241,8 +241,7 @@ class NeRFRenderer(torch.nn.Module):
         seeded = (_noise is None and fused and self.rng == "philox" and not (self.training and torch.is_grad_enabled())
                   and not (rays.is_cuda and torch.cuda.is_current_stream_capturing()))
         noise = _noise if (_noise is not None or seeded) else self._draw_noise(R, rays.device)
-        Kf = self.n_fine if self.using_fine else 0
-        Kfd = min(self.n_fine_depth, Kf)
+        Kf, Kfd = self._fine_counts()
 
         if fused:  # pixelnerf_amd.PixelNeRFNet: one C call
             model._check_supported()
@@ -264,7 +263,7 @@ class NeRFRenderer(torch.nn.Module):
             else:
                 seed = self._next_seed(rays.device) if seeded else 0
                 res = self._fused_inference(model, Kf, seed, seeded, _noise, noise,
-                                            self._rays_launch(model, rays, Kf, Kfd, noise, want_weights),
+                                            self._rays_launch(model, rays, noise, want_weights),
                                             lambda: rays.reshape(SB, -1, 8))
             outputs = DotMap(coarse=self._format(res["coarse"], SB, want_weights))
             if Kf > 0:
@@ -299,290 +298,14 @@ class NeRFRenderer(torch.nn.Module):
             or rays.requires_grad  # rays and cameras: pose estimation / refinement (autograd._RenderFunction)
             or any(torch.is_tensor(t) and t.requires_grad for t in (model.poses, model.focal, model.c)))
 
-    # ---- occupancy-grid culling (inference): render the rays that can hit something, fill in the rest ----
-    @staticmethod
-    def _check_skip_args(skip_empty, occupancy):
-        if skip_empty and occupancy is None:
-            raise ValueError("skip_empty=True needs `occupancy`: the OccupancyGrid that says which cells are empty")
-
-    def _terminate_bounds(self, terminate, stages):
-        """the stage boundaries [0, b_1, ..., K] of a terminated fine pass (None without `terminate`); ValueError for a bad eps or
-        bad stages.  An int S: b_s = 2 ((K s) // (2 S)), zeros and duplicates dropped -- for even K no pair (2j, 2j+1) of the dense
-        launch straddles a stage; a sequence: the boundaries inside (0, K), as given."""
-        if terminate is None:
-            return None
-        try:
-            eps = float(terminate)
-        except (TypeError, ValueError):
-            eps = float("nan")
-        if not 0.0 < eps < 1.0:
-            raise ValueError(f"terminate: eps must lie in (0, 1) -- the transmittance below which a ray stops, e.g. 1e-2 --, got "
-                             f"{terminate!r}; pass terminate=None for the dense render")
-        K = self.n_coarse + (self.n_fine if self.using_fine else 0)
-        if isinstance(stages, (bool, float)) or (torch.is_tensor(stages) and stages.dim() == 0):
-            raise ValueError(f"terminate_stages: pass the number of stages as an int >= 1, or the boundaries as a sequence, got {stages!r}")
-        if not isinstance(stages, int) and hasattr(stages, "__index__") and not hasattr(stages, "__len__"):
-            stages = int(stages)  # (a numpy integer)
-        if isinstance(stages, int):
-            if stages < 1:
-                raise ValueError(f"terminate_stages: needs at least 1 stage (1: no boundary, the dense render), got {stages}")
-            inner = []
-            for s in range(1, stages):
-                b = 2 * ((K * s) // (2 * stages))
-                if 0 < b < K and (not inner or b > inner[-1]):
-                    inner.append(b)
-        else:
-            try:
-                inner = [int(b) for b in stages]
-            except TypeError:
-                raise ValueError(f"terminate_stages: pass the number of stages as an int >= 1, or the boundaries as a sequence, got {stages!r}")
-            if any(not 0 < b < K for b in inner) or any(b1 <= b0 for b0, b1 in zip(inner, inner[1:])):
-                raise ValueError(f"terminate_stages: the boundaries must increase strictly inside (0, K = n_coarse + n_fine = {K}), got "
-                                 f"{inner}; or pass the number of stages as an int")
-        return [0] + inner + [K]
-
-    def _check_culled_call(self, model, rays, SB, skip_empty=False, occupancy=True, terminate=None, terminate_stages=TERMINATE_STAGES):
-        """the refusals of a call with `occupancy` and / or `terminate`; rays: the call's differentiable input (the rays, or the
-        cameras of render_views).  -> the stage boundaries of a terminated call (None without `terminate`)"""
-        bounds = self._terminate_bounds(terminate, terminate_stages)
-        if occupancy is None:
-            return self._check_terminated_call(model, rays, SB, bounds)
-        if SB != 1 or int(getattr(model, "num_objs", 1) or 1) != 1:
-            raise ValueError(f"occupancy: an OccupancyGrid describes ONE object, the call has {max(SB, int(getattr(model, 'num_objs', 1) or 1))}; "
-                             "encode one object and pass its rays as (1,B,8)")
-        if bounds is not None and not self.using_fine:
-            raise NotImplementedError(self._NO_FINE)
-        if self._is_fused(model):
-            needs_grad = self._fused_needs_grad(model, rays)
-        else:
-            params = list(model.parameters()) if hasattr(model, "parameters") else []
-            needs_grad = torch.is_grad_enabled() and (rays.requires_grad or any(p.requires_grad for p in params))
-        if needs_grad:
-            raise NotImplementedError("occupancy: culling is an inference feature -- this call would take the differentiable path "
-                                      "(parameters, feature grid, rays or cameras require grad); call it under torch.no_grad()")
-        if rays.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("occupancy: the number of rays that survive is read on the host to size the launch, which a "
-                                      "HIP-graph capture cannot contain; capture the call without `occupancy`")
-        if skip_empty:
-            if not self._is_fused(model):
-                raise NotImplementedError("skip_empty: the samples in empty cells are skipped by the staged HIP pass of a fused PixelNeRFNet; "
-                                          "a generic model callable and a PixelNeRFNet on the composed (non-fused) path are not "
-                                          "implemented -- call without skip_empty")
-            if self.training and self.noise_std > 0.0:
-                raise NotImplementedError("skip_empty: noise_std > 0 in train mode is implemented on the differentiable path only")
-        if bounds is not None:
-            self._check_terminated_model(model)
-        if skip_empty:
-            self.last_skip_stats = {"coarse": (0, 0), "fine": (0, 0)}
-        if bounds is not None:
-            self.last_terminate_stats = {"evaluated": 0, "total": 0, "stopped_rays": 0, "rays": 0, "stages": []}
-        return bounds
-
-    _NO_FINE = ("terminate: early termination applies to the FINE pass (the coarse pass places the fine samples and stays dense); this "
-                "renderer has none (n_fine = 0) -- call without `terminate`, or render with n_fine > 0")
-
-    def _check_terminated_model(self, model):
-        if not self._is_fused(model):
-            raise NotImplementedError("terminate: the stages run the staged HIP pass of a fused PixelNeRFNet; a generic model callable and "
-                                      "a PixelNeRFNet on the composed (non-fused) path are not implemented -- call without `terminate`")
-        if self.training and self.noise_std > 0.0:
-            raise NotImplementedError("terminate: noise_std > 0 in train mode is implemented on the differentiable path only; put the "
-                                      "renderer in eval mode (renderer.eval()) or call without `terminate`")
-
-    def _check_terminated_call(self, model, rays, SB, bounds):
-        """the refusals of a call with `terminate` and no grid, each before any device work"""
-        n_obj = max(SB, int(getattr(model, "num_objs", 1) or 1))
-        if n_obj != 1:
-            raise ValueError(f"terminate: implemented for ONE object per call, this one has {n_obj}; encode one object and pass its rays "
-                             "as (1,B,8), object by object")
-        if not self.using_fine:
-            raise NotImplementedError(self._NO_FINE)
-        if self._is_fused(model):
-            needs_grad = self._fused_needs_grad(model, rays)
-        else:
-            params = list(model.parameters()) if hasattr(model, "parameters") else []
-            needs_grad = torch.is_grad_enabled() and (rays.requires_grad or any(p.requires_grad for p in params))
-        if needs_grad:
-            raise NotImplementedError("terminate: early termination is an inference feature -- this call would take the differentiable "
-                                      "path (parameters, feature grid, rays or cameras require grad); call it under torch.no_grad()")
-        if rays.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("terminate: every stage reads the number of samples it keeps on the host, which a HIP-graph "
-                                      "capture cannot contain; capture the call without `terminate`")
-        self._check_terminated_model(model)
-        self.last_terminate_stats = {"evaluated": 0, "total": 0, "stopped_rays": 0, "rays": 0, "stages": []}
-        return bounds
-
-    def _culled_seed(self, model, dev, given_noise):
-        """the ONE Philox key of a culled call, taken exactly where the dense call takes its own (the generator advances the same
-        way); None: the draws are torch's (rng="torch", a generic model callable, explicit noise)"""
-        seeded = (given_noise is None and self._is_fused(model) and self.rng == "philox"
-                  and not (self.training and torch.is_grad_enabled()))
-        return self._next_seed(dev) if seeded else None
-
-    def _background(self, R, K, want_weights, dev):
-        """what nerf.py:223-249 composites from sigma == 0 on every sample: T = 1 throughout, all weights 0"""
-        out = {"rgb": torch.full((R, 3), 1.0 if self.white_bkgd else 0.0, dtype=torch.float32, device=dev),
-               "depth": torch.zeros((R,), dtype=torch.float32, device=dev)}
-        if want_weights:
-            out["weights"] = torch.zeros((R, K), dtype=torch.float32, device=dev)
-        return out
-
-    def _render_culled(self, model, rays, first_id, occupancy, tighten, want_weights, given_noise, seed, skip_empty=False, terminate=None,
-                       bounds=None):
-        """The shared body of forward(occupancy=) and render_views(occupancy=): rays (R,8) of ONE object whose row r has the global
-        ray id first_id + r.  Clip against the grid, gather the rays that hit, render them through the ordinary forward with the
-        draws of their global ids (seed; given_noise is cut to the hit rows), scatter into outputs pre-filled with the empty-ray
-        value.  One host synchronisation: the number of hit rays.  skip_empty and / or terminate (with `bounds`, the stages of the
-        fine pass): the hit rays go through the staged pass of _staged_launch instead (one more synchronisation per pass or stage);
-        its counts are ADDED to last_skip_stats / last_terminate_stats.  occupancy None (terminate alone): every ray is rendered.
-        -> ({"coarse": {...}[, "fine": {...}]} flat tensors, hit (R,) bool (None without a grid), the number of rendered rays)"""
-        R, dev = rays.shape[0], rays.device
-        Kc = self.n_coarse
-        Kf = self.n_fine if self.using_fine else 0
-        Kfd = min(self.n_fine_depth, Kf)
-        if occupancy is None:
-            res, hit, idx, sub = None, None, None, rays
-            noise = given_noise
-            if noise is None and seed is not None:  # the draws of the dense call, as tensors
-                noise = ops.philox_noise_ids(torch.arange(R, dtype=torch.int64, device=dev) + int(first_id), Kc, Kf, Kfd, seed)
-        else:
-            res = {"coarse": self._background(R, Kc, want_weights, dev)}
-            if Kf > 0:
-                res["fine"] = self._background(R, Kc + Kf, want_weights, dev)
-            t_bounds, hit = occupancy.clip_rays(rays)
-            hit = hit != 0
-            idx = torch.nonzero(hit).flatten()  # ascending; its length reaches the host here
-            if idx.numel() == 0:
-                return res, hit, 0  # nothing can be hit: no network launch
-            sub = rays.index_select(0, idx)
-            if tighten:
-                sub[:, 6:8] = t_bounds.index_select(0, idx)
-            if given_noise is not None:
-                noise = {k: v.index_select(0, idx) for k, v in given_noise.items()}
-            elif seed is not None:
-                noise = ops.philox_noise_ids(idx + int(first_id), Kc, Kf, Kfd, seed)
-            else:
-                noise = None  # torch draws, for the rendered rays only
-        if skip_empty or terminate is not None:
-            model._check_supported()
-            if noise is None:
-                noise = self._draw_noise(sub.shape[0], dev)
-            launch = self._staged_launch(model, sub, Kf, Kfd, noise, want_weights, occupancy if skip_empty else None, terminate, bounds)
-            out = self._fused_inference(model, Kf, 0, False, noise, noise, launch, lambda: sub.unsqueeze(0))
-            if skip_empty:
-                self.last_skip_stats = {name: (kept + launch.stats[name][0], total + launch.stats[name][1])
-                                        for name, (kept, total) in self.last_skip_stats.items()}
-            if terminate is not None:
-                acc, new = self.last_terminate_stats, launch.term
-                stages = [(a[0] + b[0], a[1] + b[1]) for a, b in zip(acc["stages"] or [(0, 0)] * len(new["stages"]), new["stages"])]
-                self.last_terminate_stats = {k: acc[k] + new[k] for k in ("evaluated", "total", "stopped_rays", "rays")}
-                self.last_terminate_stats["stages"] = stages
-        else:
-            out = self._forward(model, sub.unsqueeze(0), want_weights, noise)
-        if occupancy is None:
-            return out, None, R
-        for name, full in res.items():
-            part = out[name]
-            for key, t in full.items():
-                t.index_copy_(0, idx, part[key].reshape(idx.numel(), *t.shape[1:]))
-        return res, hit, idx.numel()
-
-    def _rays_launch(self, model, rays, Kf, Kfd, noise, want_weights):
+    def _rays_launch(self, model, rays, noise, want_weights):
         """the launch of _fused_inference for rays (R,8): the seeded / folded one-call renderer"""
+        Kf, Kfd = self._fine_counts()
+
         def launch(pk_c, pk_f, tables, seed):
             return ops.render_forward(model.scene(), pk_c, pk_f, rays, self.n_coarse, Kf, Kfd, noise, depth_std=self.depth_std,
                                       white_bkgd=self.white_bkgd, lindisp=self.lindisp, want_weights=want_weights, tables=tables,
                                       seed=seed, ray_id_offset=self.ray_id_offset, ray_id_stride=self.ray_id_stride)
-        return launch
-
-    def _staged_launch(self, model, rays, Kf, Kfd, noise, want_weights, occupancy=None, terminate=None, bounds=None):
-        """the launch of _fused_inference for skip_empty (occupancy) and / or early termination (terminate = eps, bounds = the stage
-        boundaries of the fine pass): the stages of the one-call renderer as separate C calls, the network on the compacted list of
-        the samples it is needed on (one-sample rays: their world point is o + z d rounded as in a dense
-        launch, and eval_kernel / the fp32 path give a point the same bits wherever it stands in the launch), zeros elsewhere.
-        "f16x3": eval_split_kernel blends the fp32 table rows of an even and of an odd point of the launch with differently
-        ordered roundings (its lookup handles two points per step; the compiler contracted w0 v0 + w1 v1 into an FMA onto the
-        first product for one of them and onto the second for the other), so there a point's last places depend on the PARITY of
-        its place -- and on nothing else.  The compacted list therefore carries whole pairs (2j, 2j+1) of the dense launch, a
-        kept sample's empty partner included: every kept sample stands at a place of its own parity, and the partner's output
-        is dropped again.  At most one more point per end of a run of kept samples.
-        A pass without a grid and without stages is the dense network call.  A terminated pass goes stage by stage: the samples of
-        the stage whose ray has not stopped (pnr_termination_mark on the outputs so far, AND the grid's answer, AND the rays that
-        stopped at an earlier boundary -- a stop is final), the pair closure, compaction (the stage's host synchronisation), the
-        network, placement of the KEPT samples into the (R,K,4) buffer; a stage that keeps nothing launches no network."""
-        R, dev = rays.shape[0], rays.device
-        pairs = model._effective_precision() == "f16x3"
-
-        def evaluate(packed, tables, z, slot, keep):
-            """the network on the samples of `keep` (R,K) uint8 -> (rgbsigma (R,K,4), zeros elsewhere; the number of kept samples)"""
-            N = z.numel()
-            run = keep  # the samples the network runs on
-            if pairs:
-                flat = keep.reshape(-1)
-                p = flat[:N - N % 2].view(-1, 2)
-                run = torch.cat([(p | p.flip(1)).reshape(-1), flat[N - N % 2:]]).view_as(keep)
-                n_kept = (keep != 0).sum()
-            index, rays_c, z_c, M = ops.compact_samples(run, rays, z)  # (the host synchronisation)
-            part = None
-            if M > 0:
-                ops.saturation_guard_slot(dev, slot)  # (when the fp16-range guard is armed for this call: word 0 coarse, 1 fine)
-                part = ops.eval_ray_samples(model.scene(), packed, rays_c, z_c.unsqueeze(1), tables).reshape(M, 4)
-            rgbsigma = ops.expand_rgbsigma(index, part, N).reshape(R, z.shape[1], 4)
-            if pairs:
-                rgbsigma = torch.where(keep.unsqueeze(-1) != 0, rgbsigma, torch.zeros((), device=dev))
-                M = int(n_kept) if M > 0 else 0  # (already on its way: the stream was drained for the count above)
-            return rgbsigma, M
-
-        def network(packed, tables, z, slot, name, stages=None):
-            N, K = z.numel(), z.shape[1]
-            grid_keep = occupancy.mark_samples(rays, z) if occupancy is not None else None
-            if stages is None or len(stages) == 2:  # one stage: nothing can stop
-                if grid_keep is None:
-                    ops.saturation_guard_slot(dev, slot)
-                    rgbsigma, M = ops.eval_ray_samples(model.scene(), packed, rays, z, tables), N
-                else:
-                    rgbsigma, M = evaluate(packed, tables, z, slot, grid_keep)
-                if stages is not None:
-                    launch.term = {"evaluated": M, "total": N, "stopped_rays": 0, "rays": R, "stages": [(M, N)]}
-            else:
-                rgbsigma = torch.zeros((R, K, 4), dtype=torch.float32, device=dev)  # the outputs so far
-                live = torch.ones((R, 1), dtype=torch.uint8, device=dev)             # rays that have not stopped
-                counts = []
-                for k0, k1 in zip(stages[:-1], stages[1:]):
-                    keep, t_front = ops.termination_mark(rays, z, rgbsigma, k0, k1, terminate, keep_in=grid_keep)
-                    live = live & ~(t_front <= terminate).unsqueeze(1)
-                    keep = keep * live
-                    part, m = evaluate(packed, tables, z, slot, keep)
-                    if m > 0:
-                        rgbsigma = torch.where(keep.unsqueeze(-1) != 0, part, rgbsigma)
-                    counts.append((m, R * (k1 - k0)))
-                M = sum(m for m, _ in counts)
-                launch.term = {"evaluated": M, "total": N, "stopped_rays": R - int(live.sum()), "rays": R, "stages": counts}
-            launch.stats[name] = (M, N)
-            return rgbsigma
-
-        def launch(pk_c, pk_f, tables, seed):
-            tc, tf = tables if tables is not None else (None, None)
-            # the counts of THIS round (stream_scale="auto" may render twice)
-            launch.stats = {"coarse": (0, 0), "fine": (0, 0)}  # (kept, total) samples
-            launch.term = None
-            z_c = ops.sample_coarse(rays, noise["u1"], self.lindisp)
-            w_c, rgb_c, depth_c = ops.composite(rays, z_c, network(pk_c, tc, z_c, 0, "coarse"), self.white_bkgd, True)
-            ret = {"coarse": {"rgb": rgb_c, "depth": depth_c}}
-            if want_weights:
-                ret["coarse"]["weights"] = w_c
-            if Kf > 0:
-                z_f = ops.sample_fine(rays, w_c, depth_c, z_c, noise.get("u2") if Kf > Kfd else None, noise.get("u3") if Kf > Kfd else None,
-                                      noise.get("n4") if Kfd > 0 else None, self.depth_std, self.lindisp)
-                # mlp_fine is None: the coarse network on every kept sample of the fine pass (the one-call renderer merges the
-                # coarse pass's outputs instead -- the same bits)
-                fine = (pk_f, tf, 1) if pk_f is not None else (pk_c, tc, 0)
-                w_f, rgb_f, depth_f = ops.composite(rays, z_f, network(fine[0], fine[1], z_f, fine[2], "fine", bounds if terminate is not None else None),
-                                                    self.white_bkgd, want_weights)
-                ret["fine"] = {"rgb": rgb_f, "depth": depth_f}
-                if want_weights:
-                    ret["fine"]["weights"] = w_f
-            return ret
         return launch
 
     def _fused_inference(self, model, Kf, seed, seeded, given_noise, noise, launch, calib_rays):
@@ -648,13 +371,11 @@ class NeRFRenderer(torch.nn.Module):
         grid the rays are materialised per group of views as well, every pixel is rendered and there is no `hit`.
         `last_terminate_stats` sums over the groups of views.  One host synchronisation per stage and group of views.
         :param terminate_stages the number of stages, or the boundaries (see forward)"""
-        self._check_skip_args(skip_empty, occupancy)
+        accel = _accel.Accel.parse(self, occupancy, tighten, skip_empty, terminate, terminate_stages)
         with torch.no_grad(), torch.profiler.record_function("renderer_render_views"):
-            return self._render_views(model, poses_c2w, int(W), int(H), focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise,
-                                      occupancy, tighten, skip_empty, terminate, terminate_stages)
+            return self._render_views(model, poses_c2w, int(W), int(H), focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise, accel)
 
-    def _render_views(self, model, poses, W, H, focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise, occupancy=None,
-                      tighten=False, skip_empty=False, terminate=None, terminate_stages=TERMINATE_STAGES):
+    def _render_views(self, model, poses, W, H, focal, z_near, z_far, c, gt_rgb, want_u8, views_per_call, _noise, accel):
         from .. import util
         self._apply_sched()
         if poses.dim() == 3:
@@ -674,14 +395,12 @@ class NeRFRenderer(torch.nn.Module):
         flat = poses.reshape(-1, 4, 4).float().contiguous()
         HW = H * W
         R, dev = SB * NVt * HW, flat.device
-        Kf = self.n_fine if self.using_fine else 0
-        Kfd = min(self.n_fine_depth, Kf)
+        Kf, Kfd = self._fine_counts()
         fast = (self._is_fused(model) and flat.is_cuda and model._effective_precision() != "f32"
                 and not torch.cuda.is_current_stream_capturing() and not (self.training and self.noise_std > 0.0))
         hit = None
-        if occupancy is not None or terminate is not None:
-            rgb, depth, hit = self._render_views_culled(model, poses, W, H, focal, z_near, z_far, c, views_per_call, _noise, occupancy, tighten,
-                                                        skip_empty, terminate, terminate_stages)
+        if accel is not None:
+            rgb, depth, hit = _accel.render_views(self, model, poses, W, H, focal, z_near, z_far, c, views_per_call, _noise, accel)
         elif not fast:
             # a generic model callable, a composed-path PixelNeRFNet, the exact fp32 path, a capture in progress: the rays, then forward
             rays = util.gen_rays(flat, W, H, focal, z_near, z_far, c).reshape(SB, -1, 8)
@@ -704,7 +423,7 @@ class NeRFRenderer(torch.nn.Module):
                 last = res["fine"] if Kf > 0 else res["coarse"]
                 rgb, depth = last["rgb"], last["depth"]
             else:
-                rgb, depth = self._render_view_groups(model, poses, k, W, H, focal, z_near, z_far, c, Kf, Kfd, seed, seeded, _noise, noise)
+                rgb, depth = self._render_view_groups(model, poses, k, W, H, focal, z_near, z_far, c, seed, seeded, _noise, noise)
         ret = DotMap(rgb=rgb.reshape(SB, NVt, H, W, 3), depth=depth.reshape(SB, NVt, H, W))
         if hit is not None:
             ret.hit, ret.n_hit = hit[0].reshape(SB, NVt, H, W), hit[1]
@@ -722,39 +441,13 @@ class NeRFRenderer(torch.nn.Module):
             ret.psnr, ret.ssim = ep["psnr"].reshape(SB, NVt), ep["ssim"].reshape(SB, NVt)
         return ret
 
-    def _render_views_culled(self, model, poses, W, H, focal, z_near, z_far, c, views_per_call, given_noise, occupancy, tighten,
-                             skip_empty=False, terminate=None, terminate_stages=TERMINATE_STAGES):
-        """render_views(occupancy=) / render_views(terminate=): the rays of every group of views (all views without views_per_call)
-        through _render_culled, under ONE key; ray id = pixel index in the (NVt,H,W) order.
-        -> (rgb (R,3), depth (R,), (hit (R,) bool, n_hit) -- None without a grid)"""
-        SB, NVt = poses.shape[:2]
-        HW = H * W
-        flat = poses.reshape(-1, 4, 4).float().contiguous()
-        bounds = self._check_culled_call(model, flat, SB, skip_empty, occupancy, terminate, terminate_stages)
-        seed = self._culled_seed(model, flat.device, given_noise)
-        k = NVt if views_per_call is None else min(int(views_per_call), NVt)
-        parts, n_hit = [], 0
-        for v0 in range(0, NVt, k):
-            v1 = min(v0 + k, NVt)
-            rays = ops.gen_rays(flat[v0:v1].contiguous(), W, H, focal, z_near, z_far, c).reshape(-1, 8)
-            part = given_noise if given_noise is None else {n: t[v0 * HW:v1 * HW] for n, t in given_noise.items()}
-            res, hit, n = self._render_culled(model, rays, v0 * HW, occupancy, tighten, False, part, seed, skip_empty, terminate, bounds)
-            last = res["fine"] if "fine" in res else res["coarse"]
-            parts.append((last["rgb"], last["depth"], hit))
-            n_hit += n
-        rgb, depth = (torch.cat([p[i] for p in parts]) if len(parts) > 1 else parts[0][i] for i in range(2))
-        if occupancy is None:
-            return rgb, depth, None
-        hit = torch.cat([p[2] for p in parts]) if len(parts) > 1 else parts[0][2]
-        return rgb, depth, (hit, n_hit)
-
-    def _render_view_groups(self, model, poses, k, W, H, focal, z_near, z_far, c, Kf, Kfd, seed, seeded, given_noise, noise):
+    def _render_view_groups(self, model, poses, k, W, H, focal, z_near, z_far, c, seed, seeded, given_noise, noise):
         """render_views, k views per object at a time.  pnr_render_views numbers its rays from 0, so a group goes through its
         rays and the ray-batch entry, placed inside the whole (NVt,H,W) ray set of its object by ray_id_offset / ray_id_stride
         (include/pixelnerf_hip.h, "counter-based random draws"); explicit noise is cut to the group's rows.  Same bits as one call."""
         SB, NVt = poses.shape[:2]
         HW = H * W
-        dev = poses.device
+        dev, Kf = poses.device, self._fine_counts()[0]
         rgb = torch.empty((SB, NVt * HW, 3), dtype=torch.float32, device=dev)
         depth = torch.empty((SB, NVt * HW), dtype=torch.float32, device=dev)
         keep = (self.ray_id_offset, self.ray_id_stride)
@@ -767,7 +460,7 @@ class NeRFRenderer(torch.nn.Module):
                 # (the renderer's own placement fields: a calibration pass of stream_scale="auto" renders through forward)
                 self.ray_id_offset, self.ray_id_stride = keep[0] + v0 * HW, NVt * HW
                 res = self._fused_inference(model, Kf, seed, seeded, None if given_noise is None else part, part,
-                                            self._rays_launch(model, rays, Kf, Kfd, part, False),
+                                            self._rays_launch(model, rays, part, False),
                                             lambda: rays.reshape(SB, -1, 8))
                 last = res["fine"] if Kf > 0 else res["coarse"]
                 rgb[:, v0 * HW:v1 * HW] = last["rgb"].reshape(SB, -1, 3)

@@ -185,3 +185,42 @@ def test_refusals_fire_before_any_device_work():
         coarse_only.render_views(model, pose, 4, 4, 10.0, 1.0, 2.0, terminate=EPS)
     assert rend.last_terminate_stats is None and coarse_only.last_terminate_stats is None
     assert rend.last_skip_stats is None
+
+    # the ORDER of the refusals across feature sets: of two broken conditions the earlier one of the documented list (objects, fine
+    # pass, grad, capture, non-fused model) is raised, whatever else is asked for; and a refused call leaves the stats alone
+    class Reached(Exception):
+        pass
+
+    class Grid:
+        def clip_rays(self, rays):
+            raise Reached
+
+    grid = Grid()
+    sets = [dict(occupancy=grid), dict(occupancy=grid, skip_empty=True), dict(terminate=EPS), dict(occupancy=grid, terminate=EPS),
+            dict(occupancy=grid, skip_empty=True, terminate=EPS)]
+    skip_before, term_before = {"coarse": (1, 2), "fine": (3, 4)}, {"evaluated": 5, "total": 6, "stopped_rays": 1, "rays": 2, "stages": [(5, 6)]}
+    two_rays, two_poses, grad_rays = torch.zeros((2, 3, 8)), torch.eye(4).expand(2, 1, 4, 4), rays.clone().requires_grad_(True)
+
+    def entries(r, rays, poses):
+        p = r.bind_parallel(model, None, simple_output=True)
+        return [lambda **kw: r(model, rays, **kw), lambda **kw: p(rays, **kw),
+                lambda **kw: r.render_views(model, poses, 4, 4, 10.0, 1.0, 2.0, **kw),
+                lambda **kw: p.render_views(poses, 4, 4, 10.0, 1.0, 2.0, **kw)]
+
+    def refused(r, call, exc, match, kw):
+        r.last_skip_stats, r.last_terminate_stats = dict(skip_before), dict(term_before)
+        with pytest.raises(exc, match=match):
+            call(**kw)
+        assert r.last_skip_stats == skip_before and r.last_terminate_stats == term_before, kw
+
+    for kw in sets:
+        for call in entries(coarse_only, two_rays, two_poses):                # two objects and no fine pass
+            refused(coarse_only, call, ValueError, "ONE object", kw)
+        for call in entries(coarse_only, grad_rays, pose)[:2]:                # no fine pass and rays that require grad
+            refused(coarse_only, call, NotImplementedError, "FINE pass" if "terminate" in kw else "no_grad", kw)
+        for call in entries(rend, grad_rays, pose)[:2]:                       # rays that require grad and the generic model
+            refused(rend, call, NotImplementedError, "no_grad", kw)
+    for call in entries(rend, rays, pose)[:2]:                                # a well-formed culled call passes every refusal, and
+        refused(rend, call, Reached, None, dict(occupancy=grid))              # touches the grid only then
+    for call in entries(rend, rays, pose)[2:]:                                # (render_views makes its rays on the device before it
+        refused(rend, call, _lib.PixelNerfHipError, "no CPU path", dict(occupancy=grid))  # asks the grid: host poses end there)

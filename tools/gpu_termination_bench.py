@@ -25,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gpu_occupancy_bench import C1, C2, H, KC, KF, KFD, NVT, RESO, W, psnr, stats, timed, trained_object  # noqa: E402
 from pixelnerf_amd import ops  # noqa: E402
 from pixelnerf_amd.render import NeRFRenderer  # noqa: E402
+from pixelnerf_amd.render.accel import Accel, StagedPass  # noqa: E402
 from pixelnerf_amd.util.occupancy import OccupancyGrid  # noqa: E402
 from testdata import synthetic  # noqa: E402
 
@@ -32,21 +33,12 @@ REPS, WARMUP = 10, 2
 EPS, STAGES = (1e-2, 1e-3), (2, 4, 8)
 
 
-def machinery(rays, z, rgbsigma, bounds, eps, grid):
-    """the stages of a terminated fine pass without the network: mark (+ the grid's mark), compaction with its host read, expansion
-    and placement, on the outputs the real call ended with (in front of a boundary they are the outputs it had then)"""
-    dev = rays.device
-    grid_keep = grid.mark_samples(rays, z) if grid is not None else None
-    buf = torch.zeros_like(rgbsigma)
-    live = torch.ones((rays.shape[0], 1), dtype=torch.uint8, device=dev)
-    for k0, k1 in zip(bounds[:-1], bounds[1:]):
-        keep, t = ops.termination_mark(rays, z, rgbsigma, k0, k1, eps, keep_in=grid_keep)
-        live = live & ~(t <= eps).unsqueeze(1)
-        keep = keep * live
-        index, _, _, m = ops.compact_samples(keep, rays, z)
-        part = ops.expand_rgbsigma(index, torch.zeros((m, 4), device=dev) if m else None, z.numel()).view_as(buf)
-        buf = torch.where(keep.unsqueeze(-1) != 0, part, buf)
-    return buf
+class Machinery(StagedPass):
+    """the product's staged pass with the network left out: marking, the pair closure, compaction with its host read, expansion and
+    placement remain"""
+
+    def network(self, packed, tables, slot, rays, z):
+        return torch.zeros(z.shape + (4,), device=z.device)
 
 
 def main():
@@ -98,7 +90,7 @@ def main():
         ref = base[gname]
         info[key] = {"evaluated_share": round(st["evaluated"] / max(st["total"], 1), 5), "stopped_share": round(st["stopped_rays"] / max(st["rays"], 1), 5),
                      "rays": st["rays"], "stages": st["stages"], "psnr": psnr(img.rgb, ref.rgb), "max_abs_rgb": float((img.rgb - ref.rgb).abs().max()),
-                     "replay": seen["last"], "bounds": rend._terminate_bounds(eps, S)}
+                     "replay": seen["last"], "accel": Accel.parse(rend, kw.get("occupancy"), False, "occupancy" in kw, eps, S)}
     times = {key: [] for key in rows}
     mach = {key: [] for key in rows if key[1] is not None}
     for i in range(args.reps + WARMUP):  # every variant in every round
@@ -107,8 +99,9 @@ def main():
             if i >= WARMUP:
                 times[key].append(t)
         for key in mach:
-            rays, z, rs = info[key]["replay"]
-            t = timed(lambda: machinery(rays, z, rs, info[key]["bounds"], key[1], grid if key[0] != "no_grid" else None))[0]
+            rays, z, rs = info[key]["replay"]  # the marks are the call's own: made on the outputs it ended with
+            stages = Machinery(rend, net, rays, None, False, info[key]["accel"])
+            t = timed(lambda: stages.terminated(None, None, z, 1, grid.mark_samples(rays, z) if key[0] != "no_grid" else None, marks_from=rs))[0]
             if i >= WARMUP:
                 mach[key].append(t)
 
