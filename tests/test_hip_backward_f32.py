@@ -188,31 +188,20 @@ def test_fused_split_forward_keeps_the_operands_of_the_gemm_form(dev, scene_name
             nat = torch.empty_like(pre)
             nat[:, perm] = value(img)  # storage order -> feature order
             close(nat, torch.relu(pre), what)
-    # masks: [layer][view][tile][thread] 64-bit words, bit (it*2 + jt)*16 + r <-> feature 64 wv + 32 it + (r&3) + 8 (r>>2) + 4 h of
-    # point 32 jt + (lane & 31), thread = 64 wv + lane, h = lane >> 5  (pnr_device.h)
-    ntiles = (P + 63) // 64
-    words = sv_f.masks.view(torch.int64).reshape(11, NS, ntiles, 512).cpu().numpy().astype(np.uint64)
+    # masks: the 64-bit words of pnr_device.h, decoded to [layer][view][point][feature] by the stage reference's own reader
+    from mlp_bwd_ref import decode_relu_masks
+    bits = decode_relu_masks(sv_f.masks, P, NS)
     layers = []
     for b in range(5):
         layers += [sv_g.xin[b], sv_g.net[b]]
     layers.append(sv_g.x5)
-    t = np.arange(512)
-    wv, lane = t >> 6, t & 63
-    pl, h = lane & 31, lane >> 5
     checked = 0
     for li, pre in enumerate(layers):
         per_view = li < 6
         v = pre.cpu().numpy().reshape((NS if per_view else 1), P, 512)
         for view in range(NS if per_view else 1):
-            for it in range(2):
-                for jt in range(2):
-                    for r in range(16):
-                        feat = 64 * wv + 32 * it + (r & 3) + 8 * (r >> 2) + 4 * h
-                        bit = (words[li, view] >> np.uint64((it * 2 + jt) * 16 + r)) & np.uint64(1)  # (ntiles, 512)
-                        pt = np.arange(ntiles)[:, None] * 64 + jt * 32 + pl[None, :]
-                        ok = pt < P
-                        val = v[view][np.minimum(pt, P - 1), feat[None, :]]
-                        sure = ok & (np.abs(val) > 1e-5)  # the two forwards differ by rounding: skip values at the threshold
-                        assert ((bit == 1) == (val > 0))[sure].all(), (li, view, it, jt, r)
-                        checked += int(sure.sum())
+            bit, val = bits[li, view], v[view]
+            sure = np.abs(val) > 1e-5  # the two forwards differ by rounding: skip values at the threshold
+            assert ((bit == 1) == (val > 0))[sure].all(), (li, view)
+            checked += int(sure.sum())
     assert checked > 0.9 * 11 * 0.5 * P * 512
