@@ -938,6 +938,57 @@ int pnr_termination_mark(const float *rays, const float *z, const float *rgbsigm
                          int k_end, float eps, const uint8_t *keep_in /*(R,K), nullable*/, uint8_t *keep /*(R,K)*/,
                          float *t_front /*(R), nullable*/, void *stream);
 
+/* ---- baked volumes (inference; added within ABI rev 12: no struct or argument list changed; nothing in the reference
+ * corresponds).  The network of ONE encoded object is evaluated once on the points of its grid, for colour as well as density,
+ * and any number of views is rendered from the grid alone, with no network behind a pixel.  The image is an approximation of
+ * the network's render: trilinear in space, one view direction per grid point, equidistant samples (no importance sampling).
+ *
+ * Volume.  vol (nx,ny,nz,4) fp32, C-contiguous, 16-byte aligned: (r, g, b, sigma) at the points of
+ *   pnr_gen_grid_points(c1, c2, reso) -- x the slowest axis -- i.e. the geometry of the occupancy entries above: cells of the
+ *   TRUE spacing h = (c2 - c1) / (n - 1), h rounded once from fp64.  Every axis has at least 2 points, the grid fewer than 2^31
+ *   cells; all index arithmetic is 64-bit.  The values are the network's outputs (rgb after the sigmoid, sigma after the relu):
+ *   the kernel applies no activation.  c1, c2: HOST arrays of 3 floats, c1 < c2.
+ * Samples of a ray (o, d, near, far).  step > 0, a length in the units of z:
+ *   n = ceil((far - near) / step),  t_i = near + (i + 0.5) step for i < n,  p_i = o + t_i d  (the product and the sum rounded
+ *   separately: ray_point of csrc/pnr_geom.h).  The samples are anchored at `near`, not at the box.  A sample with a coordinate
+ *   outside [c1, c2] on any axis, or not finite, has sigma = 0.  Inside the box, per axis u = (p - c1) / h, the cell is
+ *   clamp(floor(u), 0, n - 2) and the position in it f = clamp(u - cell, 0, 1): because of the clamp no input can make the kernel
+ *   read outside the volume.  The 8 corners are one 16-byte load each; all four channels are blended as a + f (b - a), along z
+ *   (the 4 corner pairs, at f_z), then along y (at f_y), then along x (at f_x); every operation is rounded on its own.
+ *   A ray that cannot be sampled -- near >= far, a non-finite origin, direction, near or far, n > 2^20 -- gets the background
+ *   (rgb 0, or 1 with white_bkgd; depth 0; alpha 0) and does no volume reads.
+ * Compositing: src/render/nerf.py:178-182,223-249 with a constant delta, in fp32:
+ *   alpha_i = 1 - exp(-step sigma_i),  T_i = prod_{j<i} (1 - alpha_j + 1e-10),  w_i = alpha_i T_i,
+ *   rgb = sum w_i c_i  (with white_bkgd (sum + 1) - sum w_i on every channel),  depth = sum w_i t_i,  alpha = sum w_i.
+ *   One wavefront per ray: lane l of chunk c takes sample 64 c + l; T is an inclusive product scan across the lanes times the
+ *   carry of the earlier chunks (pnr_composite's scan); the four sums are per-lane accumulators, reduced once at the end in a
+ *   fixed butterfly order.  A chunk none of whose samples is inside the box (and occupied, below) issues no loads; all its
+ *   factors are exactly 1, so it leaves the carry and the sums as they are.
+ * Skipping.  bits (nullable): pnr_occupancy_build's bitfield of a field with the same nx, ny, nz.  A sample whose cell's bit is
+ *   off has sigma = 0; it enters the product as the factor 1, in its own place.  Built from vol's sigma (>= 0) at threshold 0
+ *   with dilate 0 this is exact: the 8 corners of an empty cell are 0, the blend is 0, alpha is 0 and the factor is exactly 1,
+ *   so the renders with and without bits are equal bit for bit.  At a threshold > 0 the image changes where the dropped haze
+ *   was visible.
+ * Termination.  terminate = eps in [0, 1), 0: off.  Once the transmittance carried out of a chunk of 64 samples is <= eps the
+ *   ray stops; what was left goes to the background.  With rgb in [0, 1] every channel and alpha move by at most eps and the
+ *   depth by at most eps far (the argument of pnr_termination_mark above; the deltas here are all positive).  eps = 0 gives the
+ *   bits of the plain render; a NaN transmittance does not stop a ray.
+ * No atomics, no LDS, no workspace: two calls give the same bytes.  Outputs: rgb (R,3), depth (R), alpha (R) fp32.
+ * pnr_baked_render_rays: rays (R,8) [origin, direction, near, far].  pnr_baked_render_views: poses (NV,4,4) camera-to-world and
+ *   the intrinsics of pnr_gen_rays; R = NV H W rays ordered (view, row, column), each regenerated in the kernel with
+ *   pnr_gen_rays' operations -- the same kernel, the same bits as pnr_baked_render_rays on pnr_gen_rays' rows, and no ray array
+ *   is written.
+ * PNR_E_INVALID, before any HIP call: a bad grid (as pnr_occupancy_clip_rays), step not finite or <= 0, terminate NaN or outside
+ *   [0, 1), R < 0 / NV < 0 / W <= 0 / H <= 0, more than 2^33 rays, and with R > 0 a null rays / poses / vol / rgb / depth /
+ *   alpha, a vol that is not 16-byte aligned, any other pointer that is not 4-byte aligned.  R = 0: no-op. */
+int pnr_baked_render_rays(const float *rays, long long R, const float *vol, const uint32_t *bits /*nullable*/, int nx, int ny,
+                          int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd,
+                          float terminate, float *rgb /*(R,3)*/, float *depth /*(R)*/, float *alpha /*(R)*/, void *stream);
+int pnr_baked_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                           float z_near, float z_far, const float *vol, const uint32_t *bits /*nullable*/, int nx, int ny,
+                           int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd,
+                           float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

@@ -14,6 +14,7 @@
 #include <cstdio>
 
 #include "pnr_common.h"
+#include "pnr_occgrid.h"
 #include "pnr_wave.h"
 
 namespace pnr {
@@ -82,17 +83,10 @@ occupancy_count_kernel(const uint32_t *__restrict__ bits, long long n_words, int
     }
 }
 
-struct OccGrid {
-    float c1[3], c2[3], h[3];  // h = (c2 - c1) / (n - 1): util.gen_grid's spacing (util.py:93-110)
-    int n[3];                  // grid POINTS per axis; cells: n - 1
-};
-
 #pragma clang fp contract(off)  // planes, differences and quotients are separately rounded: the header states them so
 
 // plane i of axis a: c1 + i h, the last one c2 itself (as np.linspace ends on `stop`)
 __device__ __forceinline__ float occ_plane(const OccGrid &g, int a, int i) { return i >= g.n[a] - 1 ? g.c2[a] : g.c1[a] + (float)i * g.h[a]; }
-
-__device__ __forceinline__ bool occ_finite(float f) { return fabsf(f) <= 3.402823466e+38f; }
 
 __global__ void __launch_bounds__(OCC_THREADS)
 occupancy_clip_kernel(const float *__restrict__ rays, long long R, const uint32_t *__restrict__ bits, const OccGrid g, float pad,
@@ -309,35 +303,6 @@ termination_mark_kernel(const float *__restrict__ rays, const float *__restrict_
         keep[s] = (uint8_t)(alive && k >= k_begin && k < k_end && (!keep_in || keep_in[s] != 0));
     }
 }
-
-static const char *occ_bad_dims(int nx, int ny, int nz) {
-    if (nx < 2 || ny < 2 || nz < 2) return "every axis needs at least 2 grid points";
-    if ((long long)(nx - 1) * (ny - 1) * (nz - 1) >= (1LL << 31)) return "the grid must have fewer than 2^31 cells";
-    return nullptr;
-}
-
-static int occ_fail(const char *entry, const char *why) {
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: %s", entry, why);
-    return pnr_fail(PNR_E_INVALID, msg);  // (copies the text)
-}
-
-// the grid of the clip and the mark entry: c1 / c2 checked, h = (c2 - c1) / (n - 1) rounded once from fp64; nullptr when it is usable
-static const char *occ_grid(int nx, int ny, int nz, const float *c1, const float *c2, OccGrid &g) {
-    if (!c1 || !c2) return "c1 / c2 is null (host arrays of 3 floats)";
-    const int n[3] = {nx, ny, nz};
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(c1[a]) || !std::isfinite(c2[a]) || !(c1[a] < c2[a])) return "c1 / c2 must be finite with c1 < c2 on every axis";
-        g.c1[a] = c1[a];
-        g.c2[a] = c2[a];
-        g.n[a] = n[a];
-        g.h[a] = (float)(((double)c2[a] - (double)c1[a]) / (double)(n[a] - 1));
-        if (!(g.h[a] > 0.f) || !std::isfinite(g.h[a])) return "the cell size (c2 - c1) / (n - 1) is not a positive fp32 number";
-    }
-    return nullptr;
-}
-
-static bool occ_misaligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 }  // namespace pnr
 

@@ -1293,6 +1293,84 @@ def expand_rgbsigma(index, rgbsigma_c, N):
     return out
 
 
+def _baked_args(what, vol, reso, c1, c2, step, bits, terminate):
+    """the volume, its geometry and the march settings of baked_render / baked_render_views, checked before any device work
+    -> (vol, (nx, ny, nz), step, terminate)"""
+    import math
+    lib = _lib.load()
+    if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
+        raise ValueError(f"{what}: c1, c2, reso must have 3 entries each")
+    nx, ny, nz = (int(r) for r in reso)
+    if lib.pnr_occupancy_bytes(nx, ny, nz) == 0:
+        raise ValueError(f"{what}: a grid needs at least 2 points per axis and fewer than 2^31 cells, got {(nx, ny, nz)}")
+    if not all(math.isfinite(float(a)) and math.isfinite(float(b)) and float(a) < float(b) for a, b in zip(c1, c2)):
+        raise ValueError(f"{what}: c1 must be below c2 on every axis, both finite, got {tuple(c1)} .. {tuple(c2)}")
+    step, terminate = float(step), float(terminate)
+    if not (math.isfinite(step) and step > 0.0):
+        raise ValueError(f"{what}: step must be finite and > 0, got {step}")
+    if not 0.0 <= terminate < 1.0:
+        raise ValueError(f"{what}: terminate must lie in [0, 1), got {terminate}")
+    vol = _f32(vol, "vol", (nx, ny, nz, 4))
+    if vol.data_ptr() % 16:
+        raise ValueError(f"{what}: vol must be 16-byte aligned")
+    if bits is not None:
+        _check_grid_args(what, bits, (nx, ny, nz), c1, c2, vol.device)
+    return vol, (nx, ny, nz), step, terminate
+
+
+def baked_render(rays, vol, reso, c1, c2, step, bits=None, white_bkgd=False, terminate=0.0):
+    """Rays through a baked RGBA volume (pnr_baked_render_rays; the contract is in include/pixelnerf_hip.h, "baked volumes"): rays
+    (R,8), vol (nx,ny,nz,4) fp32 HIP tensors -- (r, g, b, sigma) at the points of gen_grid_points(c1, c2, reso) --, step > 0 the sample
+    distance in the units of z, bits None or occupancy_build's bitfield of the same grid (a sample in a cell whose bit is off has
+    sigma = 0), terminate eps in [0, 1) (0: off).  -> (rgb (R,3), depth (R,), alpha (R,)) fp32.  No network, no host synchronisation,
+    the same bytes on every call."""
+    lib = _lib.load()
+    vol, (nx, ny, nz), step, terminate = _baked_args("baked_render", vol, reso, c1, c2, step, bits, terminate)
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    if vol.device != dev:
+        raise ValueError(f"baked_render: vol lives on {vol.device}, the rays on {dev}")
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_render_rays(_p(rays), R, _p(vol), None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi,
+                                             step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_render_rays")
+    return rgb, depth, alpha
+
+
+def baked_render_views(poses, width, height, focal, c, z_near, z_far, vol, reso, c1, c2, step, bits=None, white_bkgd=False,
+                       terminate=0.0):
+    """baked_render over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c) (pnr_baked_render_views):
+    poses (NV,4,4) camera-to-world, focal a scalar or (fx, fy), c (cx, cy) or None = the image centre.  The rays are regenerated
+    in the kernel -- the same bits as baked_render(gen_rays(...)), and no ray array is written.
+    -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32, rays ordered (view, row, column)."""
+    lib = _lib.load()
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"baked_render_views: the image must have at least one pixel, got {W} x {H}")
+    vol, (nx, ny, nz), step, terminate = _baked_args("baked_render_views", vol, reso, c1, c2, step, bits, terminate)
+    poses = _f32(poses, "poses", (None, 4, 4))
+    NV, dev = poses.shape[0], poses.device
+    if vol.device != dev:
+        raise ValueError(f"baked_render_views: vol lives on {vol.device}, the poses on {dev}")
+    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+    R = NV * H * W
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), _p(vol),
+                                              None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
+                                              int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_render_views")
+    return rgb, depth, alpha
+
+
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):
     """philox_noise for a list of GLOBAL ray ids (pnr_philox_noise_ids): ray_ids (R,) int64 HIP tensor -- any order, repeats
     allowed, beyond 2^31 too -- -> the dict philox_noise returns, row r holding what the seeded renderer entries draw for ray
