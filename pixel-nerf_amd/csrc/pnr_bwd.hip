@@ -896,14 +896,15 @@ position_bwd_kernel(const EvalParams q, const float *__restrict__ d_in42, const 
         const float wz = pose[2] * g0 + pose[6] * g1 + pose[10] * g2;
         float val = sp.dx * wx + sp.dy * wy + sp.dz * wz;
         if (!ds.ranks) {
-            if (val == val) atomicAdd(d_z + g, val);
+            // a point on a source camera's plane or a non-finite upstream gradient: dropped, the rule of camera_record_kernel
+            if (__builtin_isfinite(val)) atomicAdd(d_z + g, val);
         } else {
             if (view == 0 && ds.dz_comp) val += ds.dz_comp[g];
             const int r = sp.r;
             const float *ray = q.rays + (size_t)r * 8;
             const float zraw = ds.depth_c[r] + ds.n4[(size_t)r * ds.Kfd + jd] * ds.depth_std;
             const bool live = zraw < ray[7] && zraw > ray[6];  // inside the clamp: gradient passes (nerf.py:157-160)
-            ds.contrib[widx] = (live && val == val) ? val : 0.f;
+            ds.contrib[widx] = (live && __builtin_isfinite(val)) ? val : 0.f;
         }
     }
 }

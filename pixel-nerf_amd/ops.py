@@ -1789,10 +1789,11 @@ def position_backward(scene, rays, z, d_in42, d_zlat, d_z):
     return d_z
 
 
-def depth_sample_backward(scene, rays, z, ranks, n4, depth_c, depth_std, d_in42, d_zlat, dz_comp):
+def depth_sample_backward(scene, rays, z, ranks, n4, depth_c, depth_std, d_in42, d_zlat, dz_comp, want_contrib=False):
     """dL/d(coarse depth) (R,) through the depth samples of the fine pass (nerf.py:157-160,292): network-input term
     (positional code, projection + lookup) + compositing term dz_comp at the samples' sorted positions `ranks`, through
-    the clamp; the per-(view, ray, sample) terms are summed in a fixed order (bit-reproducible)."""
+    the clamp; the per-(view, ray, sample) terms are summed in a fixed order (bit-reproducible).  want_contrib: those terms
+    themselves, (NS, R, Kfd), unsummed."""
     lib = _lib.load()
     rays, z, R, K, per_obj = _ray_samples(rays, z, scene)
     Kfd = ranks.shape[1]
@@ -1809,7 +1810,7 @@ def depth_sample_backward(scene, rays, z, ranks, n4, depth_c, depth_std, d_in42,
         _lib.check(lib.pnr_depth_sample_backward(scene.ref, _p(rays), _p(z), R, per_obj, K, _p(ranks), _p(n4), Kfd,
                                                  _p(depth_c), float(depth_std), _p(d_in42), _p(d_zlat), _p(dz_comp), _p(contrib),
                                                  _stream()), "pnr_depth_sample_backward")
-    return contrib.sum(dim=(0, 2))
+    return contrib if want_contrib else contrib.sum(dim=(0, 2))
 
 
 def grad_scale(g):

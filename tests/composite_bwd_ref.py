@@ -172,3 +172,27 @@ def errors(got, ref64):
 def bar_from(err32):
     """10 x the error of torch's fp32 autograd on the same inputs, floor 2e-6, cap 2e-5 (the stage's bar in test_hip_backward.py)"""
     return min(max(BAR_FACTOR * err32, BAR_FLOOR), BAR_CAP)
+
+
+# ------------------------------------------------------------------------------------------------ sampling maps
+# (shared by tests/test_hip_stage_sweep_backward.py and tests/position_ref.py)
+def coarse_map_ref(rays, u1, dz, K, lindisp, dtype):
+    r = rays.detach().clone().to(dtype).requires_grad_(True)
+    z = O.sample_coarse(r, u1.to(dtype), K, lindisp)
+    (d_rays,) = torch.autograd.grad((z * dz.to(dtype)).sum(), r)
+    return z.detach(), d_rays
+
+
+def fine_map_ref(rays, u1, weights, u2, u3, n4, depth_c, dz, Kc, Kfd, lindisp, dtype, perm=None):
+    """the merged fine set (nerf.py:285-295) at `dtype` and d(sum dz z_all)/d rays; depth_c is a constant here: the depth samples
+    reach near / far only where clamped, the semantics of _SampleFineFunction"""
+    r = rays.detach().clone().to(dtype).requires_grad_(True)
+    parts = [O.sample_coarse(r, u1.to(dtype), Kc, lindisp), O.sample_fine(r, weights.to(dtype), u2.to(dtype), u3.to(dtype), Kc, lindisp)]
+    if Kfd:
+        parts.append(O.sample_fine_depth(r, depth_c.to(dtype), n4.to(dtype), 0.01))
+    z_cat = torch.cat(parts, -1)
+    if perm is None:
+        perm = torch.argsort(z_cat.detach(), dim=-1, stable=True)
+    z_all = torch.gather(z_cat, 1, perm)
+    (d_rays,) = torch.autograd.grad((z_all * dz.to(dtype)).sum(), r)
+    return z_all.detach(), perm, d_rays

@@ -29,7 +29,6 @@ import pytest
 import torch
 
 import composite_bwd_ref as CR
-from oracle import pnr_oracle as O
 
 pytestmark = pytest.mark.gpu
 
@@ -115,13 +114,6 @@ def _ray_errors(got, ref64):
     return float((got[:, 6:8].double() - ref64[:, 6:8]).abs().max()) / den
 
 
-def _coarse_ref(rays, u1, dz, K, lindisp, dtype):
-    r = rays.detach().clone().to(dtype).requires_grad_(True)
-    z = O.sample_coarse(r, u1.to(dtype), K, lindisp)
-    (d_rays,) = torch.autograd.grad((z * dz.to(dtype)).sum(), r)
-    return z.detach(), d_rays
-
-
 def _check_near_eq_far(got, dz):
     """s cannot be recovered from z: each sample's dz goes half to near, half to far; dn + df = 1 holds for both maps"""
     assert bool(torch.isfinite(got).all())
@@ -140,7 +132,7 @@ def test_sample_bounds_backward_coarse(ops, dev, case, lindisp):
     u1 = torch.from_numpy(rs.uniform(0, 1, (R, K)).astype(np.float32))
     dz = torch.from_numpy(rs.randn(R, K).astype(np.float32))
     d_far = torch.from_numpy(rs.randn(R).astype(np.float32))
-    z64, ref64 = _coarse_ref(rays, u1, dz, K, lindisp, torch.float64)
+    z64, ref64 = CR.coarse_map_ref(rays, u1, dz, K, lindisp, torch.float64)
     assert bool(torch.isfinite(ref64).all())
     z = z64.float()
     got = ops.sample_bounds_backward(rays.to(dev), z.to(dev), dz.to(dev), lindisp).cpu()
@@ -153,7 +145,7 @@ def test_sample_bounds_backward_coarse(ops, dev, case, lindisp):
         _check_near_eq_far(got, dz)
         _check_near_eq_far(got_far - torch.nn.functional.pad(d_far[:, None], (7, 0)), dz)
         return
-    _, ref32 = _coarse_ref(rays, u1, dz, K, lindisp, torch.float32)
+    _, ref32 = CR.coarse_map_ref(rays, u1, dz, K, lindisp, torch.float32)
     ref_far = ref64.clone()
     ref_far[:, 7] += d_far.double()
     err32, err, err_far = _ray_errors(ref32, ref64), _ray_errors(got, ref64), _ray_errors(got_far, ref_far)
@@ -163,21 +155,6 @@ def test_sample_bounds_backward_coarse(ops, dev, case, lindisp):
 
 
 KIMP, KFD = 5, 6
-
-
-def _fine_ref(rays, u1, weights, u2, u3, n4, depth_c, dz, Kc, Kfd, lindisp, dtype, perm=None):
-    """the merged fine set (nerf.py:285-295) at `dtype` and d(sum dz z_all)/d rays; depth_c is a constant here: the depth samples
-    reach near / far only where clamped, the semantics of _SampleFineFunction"""
-    r = rays.detach().clone().to(dtype).requires_grad_(True)
-    parts = [O.sample_coarse(r, u1.to(dtype), Kc, lindisp), O.sample_fine(r, weights.to(dtype), u2.to(dtype), u3.to(dtype), Kc, lindisp)]
-    if Kfd:
-        parts.append(O.sample_fine_depth(r, depth_c.to(dtype), n4.to(dtype), 0.01))
-    z_cat = torch.cat(parts, -1)
-    if perm is None:
-        perm = torch.argsort(z_cat.detach(), dim=-1, stable=True)
-    z_all = torch.gather(z_cat, 1, perm)
-    (d_rays,) = torch.autograd.grad((z_all * dz.to(dtype)).sum(), r)
-    return z_all.detach(), perm, d_rays
 
 
 @pytest.mark.parametrize("lindisp", [False, True], ids=["lin", "lindisp"])
@@ -208,7 +185,7 @@ def test_sample_bounds_backward_fine(ops, dev, case, lindisp):
     dz = torch.from_numpy(rs.randn(R, K).astype(np.float32))
     d_far = torch.from_numpy(rs.randn(R).astype(np.float32))
 
-    z64, perm, ref64 = _fine_ref(rays, u1, weights, u2, u3, n4, depth_c, dz, Kc, Kfd, lindisp, torch.float64)
+    z64, perm, ref64 = CR.fine_map_ref(rays, u1, weights, u2, u3, n4, depth_c, dz, Kc, Kfd, lindisp, torch.float64)
     assert bool(torch.isfinite(ref64).all())
     kw = {}
     if Kfd:
@@ -226,7 +203,7 @@ def test_sample_bounds_backward_fine(ops, dev, case, lindisp):
     if near == far:
         _check_near_eq_far(got - torch.nn.functional.pad(d_far[:, None], (7, 0)), dz)
         return
-    _, _, ref32 = _fine_ref(rays, u1, weights, u2, u3, n4, depth_c, dz, Kc, Kfd, lindisp, torch.float32, perm=perm)
+    _, _, ref32 = CR.fine_map_ref(rays, u1, weights, u2, u3, n4, depth_c, dz, Kc, Kfd, lindisp, torch.float32, perm=perm)
     ref_far = ref64.clone()
     ref_far[:, 7] += d_far.double()
     err32, err = _ray_errors(ref32, ref64), _ray_errors(got, ref_far)
