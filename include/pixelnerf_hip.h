@@ -989,6 +989,44 @@ int pnr_baked_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H
                            int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd,
                            float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
 
+/* View-dependent baked volumes (added within ABI rev 12 as well).  Every grid point keeps a low-order function of the VIEW
+ * DIRECTION instead of one value: real spherical harmonics up to degree L in {0, 1, 2} on all four channels, evaluated in the
+ * march for each ray's own direction.  An SH render of a ray equals the RGBA render, by the rules above, of the volume "this
+ * object seen from direction d": that sentence is the specification; what follows says how that volume's corners are computed.
+ * Still trilinear in space, still equidistant samples, still nothing outside the box; degree <= 2, fp32 only.
+ * Layout.  B = (L+1)^2 basis functions.  coef (nx,ny,nz,B,4) fp32, C-contiguous, 16-byte aligned: float4 k of a grid point holds
+ *   (r_k, g_k, b_k, sigma_k); 16 B bytes per point (64 at degree 1, 144 at degree 2).  The grid, c1, c2, the cells and the point
+ *   order are those of the RGBA volume.
+ * Basis, normalised so that Y_0 = 1 (the integral of Y_j Y_k over the sphere is 4 pi delta_jk).  From the ray's direction
+ *   (x, y, z) = d / sqrt(dx dx + dy dy + dz dz), the sum taken left to right; the constants rounded to fp32 once:
+ *     Y_1 = sqrt(3) y,  Y_2 = sqrt(3) z,  Y_3 = sqrt(3) x,
+ *     Y_4 = sqrt(15) (x y),  Y_5 = sqrt(15) (y z),  Y_6 = (sqrt(5)/2) (3 (z z) - 1),  Y_7 = sqrt(15) (x z),
+ *     Y_8 = (sqrt(15)/2) (x x - y y).
+ *   A direction whose squared norm is 0 or not finite gets Y_k = 0 for k >= 1.  Y is a per-ray constant.
+ * Corner value.  At corner p, v = coef[p][0] Y_0 + coef[p][1] Y_1 + ... in this order, every product and every sum rounded on its
+ *   own.  Then, PER CORNER AND BEFORE THE BLEND, a channel of rgb below 0 becomes 0 and one above 1 becomes 1, a sigma below 0
+ *   becomes 0; a value inside its range keeps its bits.  A corner is B contiguous 16-byte loads, a pair of corners along z 2 B.
+ * Everything else -- the sample count and positions, the inside test, the blend along z, y, x, alpha_i, the product scan, depth
+ *   and alpha, white_bkgd, the termination check every 64 samples, the ray that cannot be sampled -- is the RGBA march, unchanged.
+ * Consequences.  A volume whose coefficients k >= 1 are all zero, with rgb in [0, 1] and sigma >= 0, renders the same BYTES as
+ *   pnr_baked_render_rays on coef[..., 0, :]: v_0 1 + 0 Y_k is exact and the clamps change nothing.  Degree 0 is that case by
+ *   construction.
+ * Skipping.  bits as above, of a field that bounds sigma over all directions: |Y_k| <= m_k = (sqrt 3, sqrt 3, sqrt 3, sqrt(15)/2,
+ *   sqrt(15)/2, sqrt 5, sqrt(15)/2, sqrt(15)/2), so sigma at a corner never exceeds s_0 + sum_k m_k |s_k| (plus the rounding of Y
+ *   and of the sum: util.bake.BakedSHVolume takes a factor 1 + 2^-16 on the sum).  A cell whose 8 corners have a bound <= 0 has
+ *   sigma exactly 0 at all of them for every direction: built at threshold 0 with dilate 0 the skipped render equals the
+ *   unskipped one bit for bit.
+ * PNR_E_INVALID: what the two entries above refuse (coef in the place of vol), and a degree outside {0, 1, 2}. */
+int pnr_baked_sh_render_rays(const float *rays, long long R, const float *coef /*(nx,ny,nz,B,4)*/, int degree,
+                             const uint32_t *bits /*nullable*/, int nx, int ny, int nz, const float *c1 /*host*/,
+                             const float *c2 /*host*/, float step, int white_bkgd, float terminate, float *rgb /*(R,3)*/,
+                             float *depth /*(R)*/, float *alpha /*(R)*/, void *stream);
+int pnr_baked_sh_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                              float z_near, float z_far, const float *coef /*(nx,ny,nz,B,4)*/, int degree,
+                              const uint32_t *bits /*nullable*/, int nx, int ny, int nz, const float *c1 /*host*/,
+                              const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                              float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

@@ -199,6 +199,10 @@ PROTOTYPES = {
     "pnr_baked_render_rays": (_I, [_P, ctypes.c_longlong, _P, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P, _P]),
     "pnr_baked_render_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _I, _F,
                                     _P, _P, _P, _P]),
+    "pnr_baked_sh_render_rays": (_I, [_P, ctypes.c_longlong, _P, _I, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P,
+                                      _P]),
+    "pnr_baked_sh_render_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _I, _P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F,
+                                       _I, _F, _P, _P, _P, _P]),
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }

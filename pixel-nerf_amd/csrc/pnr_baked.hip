@@ -5,6 +5,8 @@
 // approximation of the network's render (trilinear in space, one view direction per grid point, no importance sampling).
 // Semantics: include/pixelnerf_hip.h ("baked volumes").  One wavefront per ray, composite_kernel's scan; no atomics, no LDS, no
 // workspace: the same bytes on every call.
+// The view-dependent form (pnr_baked_sh_render_*) keeps B = (L+1)^2 float4s of real spherical-harmonic coefficients per grid point
+// and evaluates them for each ray's own direction; the march is the same function (baked_march), instantiated on what a corner is.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,7 +26,6 @@ constexpr int BAKED_WAVES = 4;             // rays per workgroup
 constexpr float BAKED_MAX_SAMPLES = 1048576.f;  // 2^20 samples per ray; (float)i + 0.5f is exact far beyond it
 
 struct BakedParams {
-    const float4 *vol;     // (nx,ny,nz) x (r,g,b,sigma)
     const uint32_t *bits;  // pnr_occupancy_build's bitfield of the same grid, or NULL
     OccGrid g;
     float step, eps;       // eps == 0: no termination
@@ -38,13 +39,59 @@ __device__ __forceinline__ float4 baked_lerp(const float4 a, const float4 b, flo
     return make_float4(a.x + f * (b.x - a.x), a.y + f * (b.y - a.y), a.z + f * (b.z - a.z), a.w + f * (b.w - a.w));
 }
 
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, float *__restrict__ rgb, float *__restrict__ depth,
-                   float *__restrict__ alpha_out) {
+// What the march reads at a corner of a cell.  RGBA volume: the float4 of the grid point.
+struct RgbaCorner {
+    const float4 *vol;  // (nx,ny,nz) x (r,g,b,sigma)
+    __device__ __forceinline__ void set_ray(const Ray8 &) {}
+    static constexpr int PAIRS_IN_FLIGHT = 4;  // 8 loads: all in flight at once
+    __device__ __forceinline__ float4 at(long long point) const { return vol[point]; }
+};
+
+// fp32(sqrt 3), fp32(sqrt 15), fp32(sqrt 5 / 2), fp32(sqrt 15 / 2): rounded once from the fp64 values
+constexpr float SH_C1 = 1.7320508075688772f, SH_C2 = 3.872983346207417f, SH_C20 = 1.118033988749895f, SH_C22 = 1.9364916731037085f;
+
+// SH volume: the B contiguous float4s of the grid point, reduced with the ray's basis values to one float4 and clamped.  y[k - 1]
+// holds Y_k of the header for k >= 1 (Y_0 = 1 is not stored: c * 1 is c); a per-ray constant.
+template <int B>
+struct ShCorner {
+    const float4 *coef;  // (nx,ny,nz,B) x (r,g,b,sigma)
+    float y[B > 1 ? B - 1 : 1];
+    __device__ __forceinline__ void set_ray(const Ray8 &ray) {
+        const float n2 = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
+        const bool ok = occ_finite(n2) && n2 != 0.f;
+        const float s = sqrtf(n2);
+        const float x = ray.dx / s, yy = ray.dy / s, z = ray.dz / s;
+        float v[8] = {SH_C1 * yy, SH_C1 * z, SH_C1 * x, SH_C2 * (x * yy), SH_C2 * (yy * z), SH_C20 * (3.f * (z * z) - 1.f),
+                      SH_C2 * (x * z), SH_C22 * (x * x - yy * yy)};
+#pragma unroll
+        for (int k = 0; k + 1 < B; ++k) y[k] = ok ? v[k] : 0.f;
+    }
+    // A pair of corners along z is 2 B contiguous float4s.  All 8 B in flight would be 72 float4s at B = 9, a wave per SIMD; the
+    // march keeps this many pairs in flight instead and leaves the wait to the other waves of the SIMD.
+    static constexpr int PAIRS_IN_FLIGHT = B == 1 ? 4 : B == 4 ? 2 : 1;
+    __device__ __forceinline__ float4 at(long long point) const {
+        const float4 *c = coef + point * B;
+        float4 v = c[0];
+#pragma unroll
+        for (int k = 1; k < B; ++k) {
+            const float4 a = c[k];
+            v.x = v.x + a.x * y[k - 1]; v.y = v.y + a.y * y[k - 1]; v.z = v.z + a.z * y[k - 1]; v.w = v.w + a.w * y[k - 1];
+        }
+        // per corner, before the blend; written so that a value inside the range keeps its bits (-0 included)
+        v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w;
+        v.x = v.x > 1.f ? 1.f : v.x; v.y = v.y > 1.f ? 1.f : v.y; v.z = v.z > 1.f ? 1.f : v.z;
+        return v;
+    }
+};
+
+template <class Corner>
+__device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const BakedParams &q, Corner corner, float *__restrict__ rgb,
+                                            float *__restrict__ depth, float *__restrict__ alpha_out) {
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * BAKED_WAVES + (threadIdx.x >> 6);
     if (r >= R) return;  // the idle waves of the last workgroup (nothing below synchronises across waves)
     const Ray8 ray = load_ray(rs, r);
+    corner.set_ray(ray);
     const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
     // the number of samples; a ray that cannot be sampled (near >= far, a non-finite component, more than 2^20 samples) keeps
     // n = 0, reads nothing and gets the background
@@ -80,13 +127,42 @@ baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, float *__r
         if (__ballot(active) == 0ull) continue;  // every factor of the chunk is exactly 1: the carry and the sums stay as they are
         float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
         if (active) {
-            const float4 *c000 = q.vol + (idx[0] * sx + idx[1] * sy + idx[2]);
-            const float4 v000 = c000[0], v001 = c000[1], v010 = c000[sy], v011 = c000[sy + 1];
-            const float4 v100 = c000[sx], v101 = c000[sx + 1], v110 = c000[sx + sy], v111 = c000[sx + sy + 1];
-            // along z, then y, then x
-            const float4 v00 = baked_lerp(v000, v001, f[2]), v01 = baked_lerp(v010, v011, f[2]);
-            const float4 v10 = baked_lerp(v100, v101, f[2]), v11 = baked_lerp(v110, v111, f[2]);
-            cs = baked_lerp(baked_lerp(v00, v01, f[1]), baked_lerp(v10, v11, f[1]), f[0]);
+            const long long p000 = idx[0] * sx + idx[1] * sy + idx[2];
+            // along z (a pair of corners is contiguous in memory: each pair is reduced before the next is needed), then y, then x
+            if constexpr (Corner::PAIRS_IN_FLIGHT == 4) {
+                const float4 v00 = baked_lerp(corner.at(p000), corner.at(p000 + 1), f[2]);
+                const float4 v01 = baked_lerp(corner.at(p000 + sy), corner.at(p000 + sy + 1), f[2]);
+                const float4 v10 = baked_lerp(corner.at(p000 + sx), corner.at(p000 + sx + 1), f[2]);
+                const float4 v11 = baked_lerp(corner.at(p000 + sx + sy), corner.at(p000 + sx + sy + 1), f[2]);
+                cs = baked_lerp(baked_lerp(v00, v01, f[1]), baked_lerp(v10, v11, f[1]), f[0]);
+            } else if constexpr (Corner::PAIRS_IN_FLIGHT == 2) {
+                // the same operations on the same values; a real loop over x, so that the pairs of x + 1 are asked for after
+                // those of x have been reduced (the gathers are independent: straight-line code issues them all first)
+                float4 vy[2];
+#pragma unroll 1
+                for (int ix = 0; ix < 2; ++ix) {
+                    const long long p = p000 + ix * sx;
+                    const float4 v0 = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
+                    const float4 v1 = baked_lerp(corner.at(p + sy), corner.at(p + sy + 1), f[2]);
+                    vy[1] = baked_lerp(v0, v1, f[1]);
+                    if (ix == 0) vy[0] = vy[1];
+                }
+                cs = baked_lerp(vy[0], vy[1], f[0]);
+            } else {
+                // one pair at a time: j = 2 ix + iy
+                float4 vz = cs, vy[2] = {cs, cs};
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {
+                    const long long p = p000 + (j >> 1) * sx + (j & 1) * sy;
+                    const float4 v = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
+                    if (j & 1) {
+                        vy[1] = baked_lerp(vz, v, f[1]);
+                        if (j == 1) vy[0] = vy[1];
+                    }
+                    vz = v;
+                }
+                cs = baked_lerp(vy[0], vy[1], f[0]);
+            }
         }
         const float a_i = 1.f - expf(-(q.step * cs.w));  // nerf.py:228 with delta = step; exactly 0 for sigma == 0
         const float tfac = 1.f - a_i + 1e-10f;           // :230-232; exactly 1 for a_i == 0
@@ -111,14 +187,31 @@ baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, float *__r
         alpha_out[r] = acc_w;
     }
 }
+
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, const float4 *__restrict__ vol, float *__restrict__ rgb,
+                   float *__restrict__ depth, float *__restrict__ alpha_out) {
+    baked_march(rs, R, q, RgbaCorner{vol}, rgb, depth, alpha_out);
+}
+
+template <int B>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const float4 *__restrict__ coef, float *__restrict__ rgb,
+                      float *__restrict__ depth, float *__restrict__ alpha_out) {
+    ShCorner<B> corner;
+    corner.coef = coef;
+    baked_march(rs, R, q, corner, rgb, depth, alpha_out);
+}
 #pragma clang fp contract(fast)
 
 static bool baked_misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
-// the checks both entries share, then the launch; src holds the rays or the camera, already checked
-static int baked_launch(const char *entry, const RaySrc &src, long long R, const float *vol, const uint32_t *bits, int nx, int ny, int nz,
-                        const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
-                        float *alpha, void *stream) {
+// the checks all entries share, then the launch; src holds the rays or the camera, already checked.  degree < 0: vol is an RGBA
+// volume; 0..2: the coefficient volume of that degree
+static int baked_launch(const char *entry, const RaySrc &src, long long R, const float *vol, int degree, const uint32_t *bits, int nx,
+                        int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
+                        float *depth, float *alpha, void *stream) {
+    if (degree > 2) return occ_fail(entry, "degree must be 0, 1 or 2");
     if (const char *why = occ_bad_dims(nx, ny, nz)) return occ_fail(entry, why);
     BakedParams q;
     if (const char *why = occ_grid(nx, ny, nz, c1, c2, q.g)) return occ_fail(entry, why);
@@ -126,18 +219,22 @@ static int baked_launch(const char *entry, const RaySrc &src, long long R, const
     if (!(terminate >= 0.f && terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
     if (R == 0) return PNR_OK;
     if (!vol || !rgb || !depth || !alpha) return occ_fail(entry, "null argument");
-    if (occ_misaligned16(vol)) return occ_fail(entry, "vol must be 16-byte aligned");
+    if (occ_misaligned16(vol)) return occ_fail(entry, degree < 0 ? "vol must be 16-byte aligned" : "coef must be 16-byte aligned");
     if (baked_misaligned4(bits) || baked_misaligned4(rgb) || baked_misaligned4(depth) || baked_misaligned4(alpha))
         return occ_fail(entry, "bits, rgb, depth and alpha must be 4-byte aligned");
     const long long blocks = (R + BAKED_WAVES - 1) / BAKED_WAVES;
     if (blocks > 0x7fffffffLL) return occ_fail(entry, "the number of rays exceeds the launch limit");
-    q.vol = reinterpret_cast<const float4 *>(vol);
     q.bits = bits;
     q.step = step;
     q.eps = terminate;
     q.white_bkgd = white_bkgd;
-    hipLaunchKernelGGL(baked_march_kernel, dim3((unsigned)blocks), dim3(BAKED_WAVES * 64), 0, (hipStream_t)stream, src, R, q, rgb, depth,
-                       alpha);
+    const float4 *v4 = reinterpret_cast<const float4 *>(vol);
+    const dim3 grid((unsigned)blocks), block(BAKED_WAVES * 64);
+    hipStream_t st = (hipStream_t)stream;
+    if (degree < 0) hipLaunchKernelGGL(baked_march_kernel, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
+    else if (degree == 0) hipLaunchKernelGGL(baked_sh_march_kernel<1>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
+    else if (degree == 1) hipLaunchKernelGGL(baked_sh_march_kernel<4>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
+    else hipLaunchKernelGGL(baked_sh_march_kernel<9>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
     return pnr_check_launch(entry);
 }
 
@@ -152,7 +249,7 @@ extern "C" int pnr_baked_render_rays(const float *rays, long long R, const float
     if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
     pnr::RaySrc src = {};
     src.rays = rays;
-    return pnr::baked_launch(entry, src, R, vol, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream);
+    return pnr::baked_launch(entry, src, R, vol, -1, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream);
 }
 
 extern "C" int pnr_baked_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
@@ -168,6 +265,38 @@ extern "C" int pnr_baked_render_views(const float *poses, int NV, int W, int H, 
     src.W = W; src.H = H;
     src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
     src.z_near = z_near; src.z_far = z_far;
-    return pnr::baked_launch(entry, src, (long long)NV * W * H, vol, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth,
-                             alpha, stream);
+    return pnr::baked_launch(entry, src, (long long)NV * W * H, vol, -1, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
+                             depth, alpha, stream);
+}
+
+extern "C" int pnr_baked_sh_render_rays(const float *rays, long long R, const float *coef, int degree, const uint32_t *bits, int nx,
+                                        int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate,
+                                        float *rgb, float *depth, float *alpha, void *stream) {
+    const char *entry = "pnr_baked_sh_render_rays";
+    if (degree < 0 || degree > 2) return pnr::occ_fail(entry, "degree must be 0, 1 or 2");
+    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
+    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
+    pnr::RaySrc src = {};
+    src.rays = rays;
+    return pnr::baked_launch(entry, src, R, coef, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha,
+                             stream);
+}
+
+extern "C" int pnr_baked_sh_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
+                                         float z_far, const float *coef, int degree, const uint32_t *bits, int nx, int ny, int nz,
+                                         const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
+                                         float *depth, float *alpha, void *stream) {
+    const char *entry = "pnr_baked_sh_render_views";
+    if (degree < 0 || degree > 2) return pnr::occ_fail(entry, "degree must be 0, 1 or 2");
+    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
+    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
+    pnr::RaySrc src = {};
+    src.poses = poses;
+    src.W = W; src.H = H;
+    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
+    src.z_near = z_near; src.z_far = z_far;
+    return pnr::baked_launch(entry, src, (long long)NV * W * H, coef, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
+                             depth, alpha, stream);
 }

@@ -1293,9 +1293,8 @@ def expand_rgbsigma(index, rgbsigma_c, N):
     return out
 
 
-def _baked_args(what, vol, reso, c1, c2, step, bits, terminate):
-    """the volume, its geometry and the march settings of baked_render / baked_render_views, checked before any device work
-    -> (vol, (nx, ny, nz), step, terminate)"""
+def _baked_march_args(what, reso, c1, c2, step, terminate):
+    """the geometry and the march settings every baked render shares, checked before any device work -> ((nx, ny, nz), step, terminate)"""
     import math
     lib = _lib.load()
     if len(reso) != 3 or len(c1) != 3 or len(c2) != 3:
@@ -1310,6 +1309,13 @@ def _baked_args(what, vol, reso, c1, c2, step, bits, terminate):
         raise ValueError(f"{what}: step must be finite and > 0, got {step}")
     if not 0.0 <= terminate < 1.0:
         raise ValueError(f"{what}: terminate must lie in [0, 1), got {terminate}")
+    return (nx, ny, nz), step, terminate
+
+
+def _baked_args(what, vol, reso, c1, c2, step, bits, terminate):
+    """the volume, its geometry and the march settings of baked_render / baked_render_views, checked before any device work
+    -> (vol, (nx, ny, nz), step, terminate)"""
+    (nx, ny, nz), step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
     vol = _f32(vol, "vol", (nx, ny, nz, 4))
     if vol.data_ptr() % 16:
         raise ValueError(f"{what}: vol must be 16-byte aligned")
@@ -1368,6 +1374,76 @@ def baked_render_views(poses, width, height, focal, c, z_near, z_far, vol, reso,
                                               None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
                                               int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
                    "pnr_baked_render_views")
+    return rgb, depth, alpha
+
+
+def _baked_sh_args(what, coef, degree, reso, c1, c2, step, bits, terminate):
+    """_baked_args for a coefficient volume: coef (nx,ny,nz,(degree+1)^2,4) -> (coef, degree, (nx, ny, nz), step, terminate)"""
+    degree = int(degree)
+    if degree not in (0, 1, 2):
+        raise ValueError(f"{what}: degree must be 0, 1 or 2, got {degree}")
+    if not isinstance(coef, torch.Tensor) or coef.dim() != 5 or coef.shape[3] != (degree + 1) ** 2 or coef.shape[4] != 4:
+        raise ValueError(f"{what}: coef must be (nx,ny,nz,{(degree + 1) ** 2},4) at degree {degree}, got "
+                         f"{tuple(coef.shape) if isinstance(coef, torch.Tensor) else type(coef).__name__}")
+    if len(reso) != 3 or tuple(int(r) for r in reso) != tuple(coef.shape[:3]):
+        raise ValueError(f"{what}: coef spans {tuple(coef.shape[:3])} points, reso says {tuple(reso)}")
+    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
+    coef = _f32(coef, "coef", (*dims, (degree + 1) ** 2, 4))
+    if coef.data_ptr() % 16:
+        raise ValueError(f"{what}: coef must be 16-byte aligned")
+    if bits is not None:
+        _check_grid_args(what, bits, dims, c1, c2, coef.device)
+    return coef, degree, dims, step, terminate
+
+
+def baked_sh_render(rays, coef, degree, reso, c1, c2, step, bits=None, white_bkgd=False, terminate=0.0):
+    """baked_render through a view-dependent volume (pnr_baked_sh_render_rays; include/pixelnerf_hip.h, "baked volumes"): coef
+    (nx,ny,nz,B,4) fp32 HIP tensor, B = (degree+1)^2 real spherical-harmonic coefficients of (r, g, b, sigma) per grid point, degree
+    0, 1 or 2; every corner is evaluated for the ray's own direction and clamped before the blend.  Everything else as baked_render.
+    -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
+    lib = _lib.load()
+    coef, degree, (nx, ny, nz), step, terminate = _baked_sh_args("baked_sh_render", coef, degree, reso, c1, c2, step, bits, terminate)
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    if coef.device != dev:
+        raise ValueError(f"baked_sh_render: coef lives on {coef.device}, the rays on {dev}")
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_sh_render_rays(_p(rays), R, _p(coef), degree, None if bits is None else _p(bits.contiguous()), nx, ny, nz,
+                                                lo, hi, step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_sh_render_rays")
+    return rgb, depth, alpha
+
+
+def baked_sh_render_views(poses, width, height, focal, c, z_near, z_far, coef, degree, reso, c1, c2, step, bits=None, white_bkgd=False,
+                          terminate=0.0):
+    """baked_render_views through a view-dependent volume (pnr_baked_sh_render_views): the same bits as
+    baked_sh_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
+    lib = _lib.load()
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"baked_sh_render_views: the image must have at least one pixel, got {W} x {H}")
+    coef, degree, (nx, ny, nz), step, terminate = _baked_sh_args("baked_sh_render_views", coef, degree, reso, c1, c2, step, bits,
+                                                                 terminate)
+    poses = _f32(poses, "poses", (None, 4, 4))
+    NV, dev = poses.shape[0], poses.device
+    if coef.device != dev:
+        raise ValueError(f"baked_sh_render_views: coef lives on {coef.device}, the poses on {dev}")
+    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+    R = NV * H * W
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_sh_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), _p(coef), degree,
+                                                 None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
+                                                 int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_sh_render_views")
     return rgb, depth, alpha
 
 

@@ -6,6 +6,9 @@ The reference has no counterpart: every pixel it renders pays for 64 + 128 evalu
 
 The image is an APPROXIMATION of the network's render: trilinear in space, one view direction per grid point, equidistant samples
 (no importance sampling).  It is separate from NeRFRenderer: nothing there changes.  After a weight update, bake again (from_model).
+BakedSHVolume lifts the one-direction limit: it keeps real spherical harmonics up to degree 2 of all four channels at every grid
+point (n_dirs network passes to bake, 4 or 9 times the memory) and the march evaluates them for each ray's own direction
+(pnr_baked_sh_render_rays / pnr_baked_sh_render_views); the other limits stay.
 
 The grid is the one util.recon.marching_cubes and util.occupancy.OccupancyGrid use (points of ops.gen_grid_points, cells of the TRUE
 spacing (c2 - c1) / (reso - 1)); the skip grid of a volume is an OccupancyGrid of its sigma channel with dilate 0.
@@ -18,7 +21,68 @@ from .dotmap import DotMap
 from .occupancy import OccupancyGrid, _check_geometry
 
 
-class BakedVolume:
+class _Baked:
+    """what BakedVolume and BakedSHVolume share: the march through `self.occupancy` on the grid (reso, c1, c2).  A subclass says
+    which entries march its volume (_march_rays, _march_views)."""
+
+    @property
+    def cell_size(self):
+        return tuple((hi - lo) / (n - 1) for lo, hi, n in zip(self.c1, self.c2, self.reso))
+
+    def _march_args(self, step, terminate, skip):
+        step = min(self.cell_size) if step is None else float(step)
+        return step, (0.0 if terminate is None else float(terminate)), (self.occupancy.bits if skip else None)
+
+    def render(self, rays, step=None, white_bkgd=False, terminate=None, skip=True):
+        """rays (...,8) on the volume's device -> DotMap(rgb (...,3), depth (...), alpha (...)); ops.baked_render /
+        ops.baked_sh_render.
+        :param step the sample distance in the units of z; None: the smallest cell edge
+        :param terminate eps in [0, 1): a ray stops once its transmittance, checked every 64 samples, is <= eps (every channel and
+        alpha move by at most eps, depth by at most eps far); None / 0: off
+        :param skip march against the skip grid (exact at skip_threshold 0)"""
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError(f"{type(self).__name__}.render: rays must be (...,8)")
+        lead = tuple(rays.shape[:-1])
+        step, terminate, bits = self._march_args(step, terminate, skip)
+        with torch.no_grad():
+            rgb, depth, alpha = self._march_rays(rays.reshape(-1, 8).float(), step, bits, white_bkgd, terminate)
+        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+    def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, step=None, white_bkgd=False,
+                     terminate=None, skip=True):
+        """Every pixel of the target views from their cameras, with NeRFRenderer.render_views' epilogue on the device: poses_c2w
+        (NVt,4,4) camera-to-world, focal a scalar or (fx, fy), c (cx, cy) or None = the image centre; step, terminate, skip as
+        render.  The rays are regenerated in the kernel: the same bits as render(util.gen_rays(...)), no ray array.
+        :return DotMap: rgb (NVt,H,W,3), depth and alpha (NVt,H,W), unclamped; depth_norm = (depth - z_near) / (z_far - z_near);
+        rgb_u8 with want_u8; with gt_rgb (NVt,H,W,3) in [0,1] psnr and ssim (NVt,) float64 of clamp(rgb, 0, 1)"""
+        from .. import ops
+        name = type(self).__name__
+        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
+            raise ValueError(f"{name}.render_views: poses_c2w must be (NVt,4,4)")
+        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
+        if torch.is_tensor(focal):
+            focal = focal.flatten().tolist()
+            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
+        if torch.is_tensor(c):
+            c = c.flatten().tolist()
+        if gt_rgb is not None and tuple(gt_rgb.shape) != (NVt, H, W, 3):
+            raise ValueError(f"{name}.render_views: gt_rgb must be (NVt,H,W,3) = {(NVt, H, W, 3)}, got {tuple(gt_rgb.shape)}")
+        step, terminate, bits = self._march_args(step, terminate, skip)
+        with torch.no_grad():
+            rgb, depth, alpha = self._march_views(poses_c2w.float(), W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate)
+            gt = None if gt_rgb is None else gt_rgb.reshape(NVt, H * W, 3).float()
+            ep = ops.eval_epilogue(rgb.reshape(NVt, H * W, 3), depth.reshape(NVt, H * W), z_near, z_far, gt_rgb=gt, want_u8=want_u8,
+                                   image_shape=(H, W) if gt is not None else None)
+        ret = DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W),
+                     depth_norm=ep["depth_norm"].reshape(NVt, H, W))
+        if want_u8:
+            ret.rgb_u8 = ep["rgb_u8"].reshape(NVt, H, W, 3)
+        if gt is not None:
+            ret.psnr, ret.ssim = ep["psnr"], ep["ssim"]
+        return ret
+
+
+class BakedVolume(_Baked):
     """vol: (nx,ny,nz,4) fp32 on the device, (r, g, b, sigma) at the points of ops.gen_grid_points(c1, c2, reso) -- the network's
     outputs (rgb after the sigmoid, sigma after the relu); reso, c1, c2: the grid; skip_threshold and occupancy: the
     OccupancyGrid (dilate 0) of vol[..., 3] that `render(skip=True)` marches against -- at threshold 0 the skipped render equals the
@@ -101,62 +165,14 @@ class BakedVolume:
                 net.train()
         return cls(vol.view(*reso, 4), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
 
-    @property
-    def cell_size(self):
-        return tuple((hi - lo) / (n - 1) for lo, hi, n in zip(self.c1, self.c2, self.reso))
-
-    def _march_args(self, step, terminate, skip):
-        step = min(self.cell_size) if step is None else float(step)
-        return step, (0.0 if terminate is None else float(terminate)), (self.occupancy.bits if skip else None)
-
-    def render(self, rays, step=None, white_bkgd=False, terminate=None, skip=True):
-        """rays (...,8) on the volume's device -> DotMap(rgb (...,3), depth (...), alpha (...)); ops.baked_render.
-        :param step the sample distance in the units of z; None: the smallest cell edge
-        :param terminate eps in [0, 1): a ray stops once its transmittance, checked every 64 samples, is <= eps (every channel and
-        alpha move by at most eps, depth by at most eps far); None / 0: off
-        :param skip march against the skip grid (exact at skip_threshold 0)"""
+    def _march_rays(self, rays, step, bits, white_bkgd, terminate):
         from .. import ops
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError("BakedVolume.render: rays must be (...,8)")
-        lead = tuple(rays.shape[:-1])
-        step, terminate, bits = self._march_args(step, terminate, skip)
-        with torch.no_grad():
-            rgb, depth, alpha = ops.baked_render(rays.reshape(-1, 8).float(), self.vol, self.reso, self.c1, self.c2, step, bits=bits,
-                                                 white_bkgd=white_bkgd, terminate=terminate)
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+        return ops.baked_render(rays, self.vol, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
 
-    def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, step=None, white_bkgd=False,
-                     terminate=None, skip=True):
-        """Every pixel of the target views from their cameras, with NeRFRenderer.render_views' epilogue on the device: poses_c2w
-        (NVt,4,4) camera-to-world, focal a scalar or (fx, fy), c (cx, cy) or None = the image centre; step, terminate, skip as
-        render.  The rays are regenerated in the kernel: the same bits as render(util.gen_rays(...)), no ray array.
-        :return DotMap: rgb (NVt,H,W,3), depth and alpha (NVt,H,W), unclamped; depth_norm = (depth - z_near) / (z_far - z_near);
-        rgb_u8 with want_u8; with gt_rgb (NVt,H,W,3) in [0,1] psnr and ssim (NVt,) float64 of clamp(rgb, 0, 1)"""
+    def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
         from .. import ops
-        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
-            raise ValueError("BakedVolume.render_views: poses_c2w must be (NVt,4,4)")
-        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
-        if torch.is_tensor(focal):
-            focal = focal.flatten().tolist()
-            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
-        if torch.is_tensor(c):
-            c = c.flatten().tolist()
-        if gt_rgb is not None and tuple(gt_rgb.shape) != (NVt, H, W, 3):
-            raise ValueError(f"BakedVolume.render_views: gt_rgb must be (NVt,H,W,3) = {(NVt, H, W, 3)}, got {tuple(gt_rgb.shape)}")
-        step, terminate, bits = self._march_args(step, terminate, skip)
-        with torch.no_grad():
-            rgb, depth, alpha = ops.baked_render_views(poses_c2w.float(), W, H, focal, c, z_near, z_far, self.vol, self.reso, self.c1,
-                                                       self.c2, step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
-            gt = None if gt_rgb is None else gt_rgb.reshape(NVt, H * W, 3).float()
-            ep = ops.eval_epilogue(rgb.reshape(NVt, H * W, 3), depth.reshape(NVt, H * W), z_near, z_far, gt_rgb=gt, want_u8=want_u8,
-                                   image_shape=(H, W) if gt is not None else None)
-        ret = DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W),
-                     depth_norm=ep["depth_norm"].reshape(NVt, H, W))
-        if want_u8:
-            ret.rgb_u8 = ep["rgb_u8"].reshape(NVt, H, W, 3)
-        if gt is not None:
-            ret.psnr, ret.ssim = ep["psnr"], ep["ssim"]
-        return ret
+        return ops.baked_render_views(poses, W, H, focal, c, z_near, z_far, self.vol, self.reso, self.c1, self.c2, step, bits=bits,
+                                      white_bkgd=white_bkgd, terminate=terminate)
 
     def state_dict(self):
         """the volume, the geometry and the skip threshold; the skip grid is rebuilt on load"""
@@ -168,3 +184,199 @@ class BakedVolume:
         """:param device where to put the volume; None: where state["vol"] lives"""
         vol = state["vol"] if device is None else state["vol"].to(device)
         return cls(vol, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
+
+
+# ---------------------------------------------------------------- view-dependent volumes: real spherical harmonics up to degree 2
+
+# max |Y_k| on the sphere, k = 1..8 (the basis of sh_basis)
+_SH_MAX = (3.0 ** 0.5, 3.0 ** 0.5, 3.0 ** 0.5, 15.0 ** 0.5 / 2, 15.0 ** 0.5 / 2, 5.0 ** 0.5, 15.0 ** 0.5 / 2, 15.0 ** 0.5 / 2)
+
+
+def _degree_of(n_basis, what):
+    if n_basis not in (1, 4, 9):
+        raise ValueError(f"{what}: a coefficient volume holds 1, 4 or 9 basis functions (degree 0, 1, 2), got {n_basis}")
+    return {1: 0, 4: 1, 9: 2}[n_basis]
+
+
+def sh_basis(dirs, degree, dtype=torch.float32):
+    """The basis of include/pixelnerf_hip.h ("baked volumes"), with the kernel's operations in `dtype` on the host: dirs (...,3)
+    (any length; normalised here as the kernel does) -> Y (...,(degree+1)^2), Y_0 = 1.  The four constants are rounded to fp32
+    once, whatever `dtype`; a direction whose squared norm is 0 or not finite gets Y_k = 0 for k >= 1."""
+    degree = int(degree)
+    if degree not in (0, 1, 2):
+        raise ValueError(f"sh_basis: degree must be 0, 1 or 2, got {degree}")
+    d = torch.as_tensor(dirs, dtype=torch.float32).cpu().to(dtype)
+    if d.dim() < 1 or d.shape[-1] != 3:
+        raise ValueError("sh_basis: dirs must be (...,3)")
+    c1, c2, c20, c22 = (float(torch.tensor(v, dtype=torch.float64).float()) for v in (3.0 ** 0.5, 15.0 ** 0.5, 5.0 ** 0.5 / 2, 15.0 ** 0.5 / 2))
+    n2 = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+    s = n2.sqrt()
+    x, y, z = d[..., 0] / s, d[..., 1] / s, d[..., 2] / s
+    cols = [torch.ones_like(x), c1 * y, c1 * z, c1 * x, c2 * (x * y), c2 * (y * z), c20 * (3.0 * (z * z) - 1.0), c2 * (x * z),
+            c22 * (x * x - y * y)]
+    Y = torch.stack(cols[:(degree + 1) ** 2], dim=-1)
+    bad = ~(torch.isfinite(n2) & (n2 != 0))
+    Y[..., 1:] = torch.where(bad[..., None], torch.zeros_like(Y[..., 1:]), Y[..., 1:])
+    return Y
+
+
+class BakedSHVolume(_Baked):
+    """A baked volume that keeps the dependence on the view direction: coef (nx,ny,nz,B,4) fp32 on the device, B = (degree+1)^2 real
+    spherical-harmonic coefficients (degree 0, 1 or 2) of (r, g, b, sigma) at the points of ops.gen_grid_points(c1, c2, reso).  The
+    march evaluates every corner for the RAY's direction, clamps it (rgb to [0,1], sigma to >= 0) and then blends: a ray renders as
+    BakedVolume would render the volume "this object seen from direction d" (`at_direction`).  Still trilinear in space, still
+    equidistant samples, still nothing outside the box; degree <= 2, fp32 only.
+    Memory: 16 B bytes per grid point -- 64 / 144 bytes at degree 1 / 2, 302 MB at 128^3 and degree 2 (BakedVolume: 16 bytes, 34 MB).
+    The skip grid is an OccupancyGrid (dilate 0) of an upper bound of sigma over all directions, s_0 + (1 + 2^-16) sum_k m_k |s_k|
+    with m_k = max |Y_k|: at skip_threshold 0 a skipped cell has sigma exactly 0 at its eight corners for every direction, so
+    `render(skip=True)` equals `render(skip=False)` bit for bit."""
+
+    def __init__(self, coef, c1, c2, skip_threshold=0.0, keep_largest=None, min_voxels=None):
+        from .. import _lib
+        if not isinstance(coef, torch.Tensor) or coef.dim() != 5 or coef.shape[4] != 4 or coef.dtype != torch.float32:
+            raise ValueError("BakedSHVolume: coef must be a (nx,ny,nz,B,4) float32 tensor")
+        degree = _degree_of(coef.shape[3], "BakedSHVolume")
+        reso, c1, c2, _ = _check_geometry(coef.shape[:3], c1, c2, 0)  # (before any device work)
+        skip_threshold = float(skip_threshold)
+        if skip_threshold != skip_threshold:
+            raise ValueError("BakedSHVolume: skip_threshold is NaN")
+        if not coef.is_cuda:
+            raise _lib.PixelNerfHipError(f"BakedSHVolume: coef must live on a HIP device (got {coef.device}); pixelnerf_amd has no CPU path")
+        coef = coef.detach().contiguous()
+        if not bool(torch.isfinite(coef).all()):
+            raise ValueError("BakedSHVolume: the volume holds a non-finite value")
+        self.coef, self.degree, self.reso, self.c1, self.c2, self.skip_threshold = coef, degree, reso, c1, c2, skip_threshold
+        self.occupancy = OccupancyGrid.from_density(self.sigma_bound(), c1, c2, skip_threshold, dilate=0, keep_largest=keep_largest,
+                                                    min_voxels=min_voxels)
+
+    def sigma_bound(self):
+        """(nx,ny,nz) fp32: s_0 + (1 + 2^-16) sum_{k>=1} m_k |s_k|, in fp64 from the fp32 coefficients and rounded UP to fp32 -- no
+        direction gives the kernel a larger sigma at the point (the slack covers the fp32 rounding of Y and of the sum)"""
+        s = self.coef[..., 3].double()
+        bound = s[..., 0]
+        if s.shape[-1] > 1:
+            m = torch.tensor(_SH_MAX[:s.shape[-1] - 1], dtype=torch.float64, device=s.device)
+            bound = bound + (1.0 + 2.0 ** -16) * (s[..., 1:].abs() * m).sum(dim=-1)
+        b32 = bound.float()
+        up = torch.nextafter(b32, torch.full_like(b32, float("inf")))
+        return torch.where(b32.double() < bound, up, b32).contiguous()
+
+    @staticmethod
+    def directions(n_dirs):
+        """(n_dirs,3) fp32 on the host: the spherical Fibonacci set z_m = 1 - (2m+1)/M, phi_m = m pi (3 - sqrt 5), built in fp64 and
+        rounded to fp32 -- the directions from_model shows the network, as they are"""
+        import math
+        n_dirs = int(n_dirs)
+        if n_dirs < 1:
+            raise ValueError(f"BakedSHVolume.directions: n_dirs must be positive, got {n_dirs}")
+        m = torch.arange(n_dirs, dtype=torch.float64)
+        z = 1.0 - (2.0 * m + 1.0) / n_dirs
+        phi = m * (math.pi * (3.0 - math.sqrt(5.0)))
+        rho = (1.0 - z * z).clamp_min(0.0).sqrt()
+        return torch.stack((rho * phi.cos(), rho * phi.sin(), z), dim=1).float()
+
+    @staticmethod
+    def projection(n_dirs, degree):
+        """(B, n_dirs) fp64: pinv of the basis matrix of directions(n_dirs), built in fp64 from the fp32 directions; from_model
+        applies it rounded to fp32.  n_dirs < 2 B raises ValueError (the set must over-determine the fit: the condition number of
+        the basis matrix is 1.05 at 32 and 1.16 at 18 directions for degree 2)."""
+        degree = int(degree)
+        if degree not in (0, 1, 2):
+            raise ValueError(f"BakedSHVolume: degree must be 0, 1 or 2, got {degree}")
+        if int(n_dirs) < 2 * (degree + 1) ** 2:
+            raise ValueError(f"BakedSHVolume: degree {degree} needs n_dirs >= {2 * (degree + 1) ** 2}, got {n_dirs}")
+        return torch.linalg.pinv(sh_basis(BakedSHVolume.directions(n_dirs), degree, torch.float64))
+
+    @classmethod
+    def from_tensor(cls, coef, c1, c2, skip_threshold=0.0):
+        """wrap a caller-made volume: coef (nx,ny,nz,B,4) fp32 HIP tensor spanning [c1, c2], B in {1, 4, 9}"""
+        return cls(coef, c1, c2, skip_threshold)
+
+    @classmethod
+    def from_model(cls, net, c1, c2, reso, degree=2, n_dirs=32, coarse=None, eval_batch_size=100000, skip_threshold=0.0,
+                   keep_largest=None, min_voxels=None):
+        """Bake ONE encoded object with its dependence on the view direction: the network is evaluated on every grid point once per
+        direction u_m of `directions(n_dirs)` and all four output columns are projected, in linear space (the clamps happen at render
+        time), onto the basis: coef[:, k, :] = sum_m P[k, m] net(points, viewdirs = u_m)[:, :4] with P = fp32(projection(n_dirs,
+        degree)), accumulated in fp32 in the fixed order m = 0..M-1 -- the volume does not depend on eval_batch_size (rounded DOWN to
+        an even number, as BakedVolume.from_model) and is the same from run to run.  n_dirs network passes: n_dirs times
+        BakedVolume.from_model's time.  The checks, the eval / train flag and `coarse` are BakedVolume.from_model's.
+        A network that takes no view directions is baked at degree 0, whatever was asked, with a warning.
+        Memory: 64 / 144 bytes per point at degree 1 / 2 (302 MB at 128^3, degree 2)."""
+        from .. import ops
+        what = "BakedSHVolume.from_model"
+        if int(getattr(net, "num_objs", 1) or 1) > 1:
+            raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
+        reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
+        degree = int(degree)
+        P = cls.projection(n_dirs, degree)  # (the degree and n_dirs checks)
+        use_viewdirs = bool(getattr(net, "use_viewdirs", False))
+        if not use_viewdirs and degree > 0:
+            warnings.warn(f"{what}: the network takes no view directions; baking at degree 0")
+            degree = 0
+        device = next(net.parameters()).device
+        if use_viewdirs:
+            dirs, P = cls.directions(n_dirs).to(device), P.float().to(device)
+        else:
+            dirs, P = None, torch.ones((1, 1), device=device)  # one pass: its output is the DC part
+        nb = (degree + 1) ** 2
+        if coarse is None:
+            coarse = getattr(net, "mlp_fine", None) is None
+        chunk = max(2, int(eval_batch_size) // 2 * 2)
+        total = reso[0] * reso[1] * reso[2]
+        is_train = bool(getattr(net, "training", False))
+        if hasattr(net, "eval"):
+            net.eval()
+        try:
+            with torch.no_grad():
+                coef = torch.zeros((total, nb, 4), dtype=torch.float32, device=device)
+                for first in range(0, total, chunk):
+                    count = min(chunk, total - first)
+                    pnts, _ = ops.gen_grid_points(c1, c2, reso, first, count, device=device, viewdirs=False)
+                    part = coef[first:first + count]
+                    for m in range(P.shape[1]):
+                        vd = dirs[m].expand(count, 3).contiguous()[None] if use_viewdirs else None
+                        out = net(pnts[None], coarse=bool(coarse), viewdirs=vd).reshape(count, -1)[:, :4]
+                        part += out[:, None, :] * P[:nb, m][None, :, None]  # the product, then the sum: two roundings, in the order of m
+        finally:
+            if is_train:
+                net.train()
+        return cls(coef.view(*reso, nb, 4), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
+
+    def at_direction(self, d):
+        """The RGBA volume "this object seen from direction d" (a 3-vector of any length): per grid point coef_0 Y_0 + coef_1 Y_1
+        + ... in this order in fp32, then rgb clamped to [0,1] and sigma to >= 0 -- the kernel's corner value.  What one bakes for a
+        fixed camera side; a ray of direction d renders through it as it does through this volume."""
+        d = torch.as_tensor(d, dtype=torch.float32).flatten()
+        if d.numel() != 3:
+            raise ValueError("BakedSHVolume.at_direction: d must be a 3-vector")
+        Y = sh_basis(d, self.degree, torch.float32).tolist()
+        with torch.no_grad():
+            v = self.coef[..., 0, :] * Y[0]
+            for k in range(1, len(Y)):
+                v = v + self.coef[..., k, :] * Y[k]
+            zero, one = torch.zeros_like(v), torch.ones_like(v)
+            v = torch.where(v < 0, zero, v)
+            v[..., :3] = torch.where(v[..., :3] > 1, one[..., :3], v[..., :3])
+        return BakedVolume(v, self.c1, self.c2, self.skip_threshold)
+
+    def _march_rays(self, rays, step, bits, white_bkgd, terminate):
+        from .. import ops
+        return ops.baked_sh_render(rays, self.coef, self.degree, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
+                                   terminate=terminate)
+
+    def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
+        from .. import ops
+        return ops.baked_sh_render_views(poses, W, H, focal, c, z_near, z_far, self.coef, self.degree, self.reso, self.c1, self.c2, step,
+                                         bits=bits, white_bkgd=white_bkgd, terminate=terminate)
+
+    def state_dict(self):
+        """the coefficients (the degree follows from their shape), the geometry and the skip threshold; the skip grid is rebuilt on load"""
+        return {"coef": self.coef, "c1": torch.tensor(self.c1, dtype=torch.float64), "c2": torch.tensor(self.c2, dtype=torch.float64),
+                "skip_threshold": torch.tensor(self.skip_threshold, dtype=torch.float64)}
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        """:param device where to put the volume; None: where state["coef"] lives"""
+        coef = state["coef"] if device is None else state["coef"].to(device)
+        return cls(coef, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
