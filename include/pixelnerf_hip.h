@@ -1027,6 +1027,60 @@ int pnr_baked_sh_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, in
                               const float *c2 /*host*/, float step, int white_bkgd, float terminate,
                               float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
 
+/* Sparse baked volumes (added within ABI rev 12 as well).  The dense forms above keep 16 B bytes for every grid point, although the
+ * skipped march reads only the corners of occupied cells.  The sparse form keeps the rows of exactly those points, renders the same
+ * BYTES as the dense march with the same bits, and can be baked without evaluating the network anywhere else.
+ * The kept set -- one definition, used by every entry below.  Grid (nx,ny,nz), P = nx ny nz points, linear id p = (i ny + j) nz + k
+ *   (the order of pnr_gen_grid_points); bits: pnr_occupancy_build's bitfield of the cells of the same grid.
+ *     corner[p] = 1 iff at least one of the up to 8 cells that have p as a corner has its bit on;
+ *     keep[p]   = corner[p] | corner[p ^ 1], where p ^ 1 exists (an odd P: the last point has no partner).
+ *   The second line is the closure over the pairs (2j, 2j+1) of the dense launch -- the pair rule of the per-sample skipping above:
+ *   a compacted network launch over the kept points, in ascending order, has every point at a place of its own parity, the one
+ *   thing a point's last bits depend on with the split-operand kernel.  So baking the kept points alone gives the dense bake's
+ *   rows bit for bit at every precision.  ids (M) int32: the kept ids, ascending; index (nx,ny,nz) int32: index[p] = the rank of p
+ *   in ids if kept, else -1.  What is stored IS the pair-closed set.  What the march relies on: in a cell whose bit is on, the two
+ *   corners of a pair along z (p, p + 1) are both kept and adjacent in id, so index[p + 1] == index[p] + 1.
+ * pnr_sparse_points_mark: bits -> keep (P) bytes as defined above.  One thread per PAIR (2j, 2j+1): the closure needs no second
+ *   pass; no atomics, EVERY byte is written, two calls give the same bytes.  The prefix sum that turns keep into index and ids is
+ *   the caller's (ops.sparse_points: one cumsum and one host read of M).  PNR_E_INVALID: what pnr_occupancy_bytes calls an invalid
+ *   grid (n < 2 on an axis, 2^31 cells or more), 2^31 points or more (ranks are int32), a null pointer.
+ * pnr_gen_grid_points_at: row m of xyz (count,3) and of viewdirs (count,3, nullable) holds the bits of row ids[m] of
+ *   pnr_gen_grid_points(c1, c2, reso, 0, P, ...), coordinates and fake view directions alike (one device function computes a row
+ *   in both entries).  An id outside [0, P) gives a row of NaN.  PNR_E_INVALID: a null c1 / c2 / reso, reso < 1 on an axis, a
+ *   non-finite c1 / c2, count < 0, and with count > 0 a null ids / xyz or a pointer that is not 4-byte aligned.  count = 0: no-op.
+ * pnr_baked_sparse_render_rays / pnr_baked_sparse_render_views: the argument lists of the pnr_baked_sh_render_* pair with
+ *   (rows, M, degree, index, bits) in the place of (coef, degree, bits).  degree = -1: rows (M,4) fp32, the (r, g, b, sigma) of the
+ *   kept points (the RGBA march); degree 0, 1, 2: rows (M,B,4), their coefficients (the view-dependent march).  rows is 16-byte
+ *   aligned; bits and index are mandatory: a sparse volume has nothing to march unskipped.
+ *   Semantics: the dense march above, with ONE change in where a corner comes from.  For an active sample (inside the box, its
+ *   cell's bit on) the four index values of the pair bases p000, p000 + sy, p000 + sx, p000 + sx + sy (p000 the cell's lowest
+ *   corner, sy = nz, sx = ny nz) are loaded -- four independent 4-byte loads, issued together -- and the corners of a pair are
+ *   rows r and r + 1 of `rows`.  Everything else is the dense march unchanged, operation for operation (it is the same function,
+ *   instantiated on where a row lies): the B float4 loads of a corner, the SH evaluation and the clamps, the blend order, the
+ *   number of corner pairs in flight, the compositing, terminate and white_bkgd.  With index and rows made from a dense volume and
+ *   the same bits, the outputs are the bytes of pnr_baked_render_* / pnr_baked_sh_render_* with those bits.
+ *   Safety -- the counterpart of "no input can make the kernel read outside the volume": an index value is always read inside
+ *   index (the cell is clamped to the grid); a sample any of whose four pair rows is not in [0, M - 2] has sigma = 0 and reads NO
+ *   row; it enters the product as the factor 1, like a skipped sample.  An index built by pnr_sparse_points_mark and a prefix sum
+ *   never triggers it.  M = 0 (and M = 1): every ray gets the background; neither index nor rows is read, and with M = 0 index,
+ *   bits and rows may be null.
+ *   One wavefront per ray, no atomics, no LDS, no workspace: two calls give the same bytes.
+ *   PNR_E_INVALID: what the dense entries refuse (rows in the place of vol / coef), and M < 0, a null index, bits or rows with
+ *   R > 0 and M > 0, rows not 16-byte aligned, index not 4-byte aligned, a degree outside {-1, 0, 1, 2}.  R = 0: no-op. */
+int pnr_sparse_points_mark(const uint32_t *bits, int nx, int ny, int nz, uint8_t *keep /*(P)*/, void *stream);
+int pnr_gen_grid_points_at(const double *c1 /*host*/, const double *c2 /*host*/, const int *reso /*host*/,
+                           const int32_t *ids /*(count)*/, long long count, float *xyz, float *viewdirs /*nullable*/,
+                           void *stream);
+int pnr_baked_sparse_render_rays(const float *rays, long long R, const float *rows /*(M,4) or (M,B,4)*/, long long M, int degree,
+                                 const int32_t *index /*(nx,ny,nz)*/, const uint32_t *bits, int nx, int ny, int nz,
+                                 const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                                 float *rgb /*(R,3)*/, float *depth /*(R)*/, float *alpha /*(R)*/, void *stream);
+int pnr_baked_sparse_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                  float z_near, float z_far, const float *rows /*(M,4) or (M,B,4)*/, long long M, int degree,
+                                  const int32_t *index /*(nx,ny,nz)*/, const uint32_t *bits, int nx, int ny, int nz,
+                                  const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd,
+                                  float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

@@ -7,6 +7,9 @@
 // workspace: the same bytes on every call.
 // The view-dependent form (pnr_baked_sh_render_*) keeps B = (L+1)^2 float4s of real spherical-harmonic coefficients per grid point
 // and evaluates them for each ray's own direction; the march is the same function (baked_march), instantiated on what a corner is.
+// The sparse form (pnr_baked_sparse_render_*) keeps only the rows of the grid points that occupied cells read (the kept set of
+// pnr_sparse_points_mark) and an int32 index over the grid; baked_march is instantiated a second time on WHERE a pair of corners
+// lies: at rows p, p + 1 of the dense array, or at rows index[p], index[p] + 1 of the kept ones.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -84,9 +87,42 @@ struct ShCorner {
     }
 };
 
-template <class Corner>
-__device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const BakedParams &q, Corner corner, float *__restrict__ rgb,
-                                            float *__restrict__ depth, float *__restrict__ alpha_out) {
+// Where the rows of a pair of corners along z (grid points p, p + 1) lie in the array a Corner reads.  Dense: rows p and p + 1.
+struct DenseRows {
+    struct Pairs {};
+    __device__ __forceinline__ bool find(long long, long long, long long, Pairs &) const { return true; }
+    // pair j = 2 ix + iy of the cell, whose base is grid point p
+    __device__ __forceinline__ long long row(const Pairs &, int, long long p) const { return p; }
+};
+
+// Sparse: rows r = index[p] and r + 1 of the kept rows (the pair closure of the kept set puts the two corners of a pair of an
+// occupied cell next to each other).  The four index values are independent 4-byte loads, issued together; a sample any of whose
+// four rows is not in [0, last] reads no row and keeps sigma = 0 (last = M - 2; below 0 the index is not read either).
+struct SparseRows {
+    const int32_t *index;  // (nx,ny,nz): the rank of a kept point, -1 elsewhere
+    int last;
+    struct Pairs {
+        int r[4];
+    };
+    __device__ __forceinline__ bool find(long long p000, long long sx, long long sy, Pairs &pr) const {
+        if (last < 0) return false;
+        pr.r[0] = index[p000];
+        pr.r[1] = index[p000 + sy];
+        pr.r[2] = index[p000 + sx];
+        pr.r[3] = index[p000 + sx + sy];
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ok = ok && pr.r[j] >= 0 && pr.r[j] <= last;
+        return ok;
+    }
+    __device__ __forceinline__ long long row(const Pairs &pr, int j, long long) const {
+        return j == 0 ? pr.r[0] : j == 1 ? pr.r[1] : j == 2 ? pr.r[2] : pr.r[3];
+    }
+};
+
+template <class Corner, class Rows>
+__device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const BakedParams &q, Corner corner, const Rows rows,
+                                            float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * BAKED_WAVES + (threadIdx.x >> 6);
     if (r >= R) return;  // the idle waves of the last workgroup (nothing below synchronises across waves)
@@ -128,40 +164,47 @@ __device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const
         float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
         if (active) {
             const long long p000 = idx[0] * sx + idx[1] * sy + idx[2];
-            // along z (a pair of corners is contiguous in memory: each pair is reduced before the next is needed), then y, then x
-            if constexpr (Corner::PAIRS_IN_FLIGHT == 4) {
-                const float4 v00 = baked_lerp(corner.at(p000), corner.at(p000 + 1), f[2]);
-                const float4 v01 = baked_lerp(corner.at(p000 + sy), corner.at(p000 + sy + 1), f[2]);
-                const float4 v10 = baked_lerp(corner.at(p000 + sx), corner.at(p000 + sx + 1), f[2]);
-                const float4 v11 = baked_lerp(corner.at(p000 + sx + sy), corner.at(p000 + sx + sy + 1), f[2]);
-                cs = baked_lerp(baked_lerp(v00, v01, f[1]), baked_lerp(v10, v11, f[1]), f[0]);
-            } else if constexpr (Corner::PAIRS_IN_FLIGHT == 2) {
-                // the same operations on the same values; a real loop over x, so that the pairs of x + 1 are asked for after
-                // those of x have been reduced (the gathers are independent: straight-line code issues them all first)
-                float4 vy[2];
+            typename Rows::Pairs pr;
+            if (rows.find(p000, sx, sy, pr)) {
+                // along z (a pair of corners is contiguous in memory: each pair is reduced before the next is needed), then y, then x
+                if constexpr (Corner::PAIRS_IN_FLIGHT == 4) {
+                    const long long r00 = rows.row(pr, 0, p000), r01 = rows.row(pr, 1, p000 + sy), r10 = rows.row(pr, 2, p000 + sx),
+                                    r11 = rows.row(pr, 3, p000 + sx + sy);
+                    const float4 v00 = baked_lerp(corner.at(r00), corner.at(r00 + 1), f[2]);
+                    const float4 v01 = baked_lerp(corner.at(r01), corner.at(r01 + 1), f[2]);
+                    const float4 v10 = baked_lerp(corner.at(r10), corner.at(r10 + 1), f[2]);
+                    const float4 v11 = baked_lerp(corner.at(r11), corner.at(r11 + 1), f[2]);
+                    cs = baked_lerp(baked_lerp(v00, v01, f[1]), baked_lerp(v10, v11, f[1]), f[0]);
+                } else if constexpr (Corner::PAIRS_IN_FLIGHT == 2) {
+                    // the same operations on the same values; a real loop over x, so that the pairs of x + 1 are asked for after
+                    // those of x have been reduced (the gathers are independent: straight-line code issues them all first)
+                    float4 vy[2];
 #pragma unroll 1
-                for (int ix = 0; ix < 2; ++ix) {
-                    const long long p = p000 + ix * sx;
-                    const float4 v0 = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
-                    const float4 v1 = baked_lerp(corner.at(p + sy), corner.at(p + sy + 1), f[2]);
-                    vy[1] = baked_lerp(v0, v1, f[1]);
-                    if (ix == 0) vy[0] = vy[1];
-                }
-                cs = baked_lerp(vy[0], vy[1], f[0]);
-            } else {
-                // one pair at a time: j = 2 ix + iy
-                float4 vz = cs, vy[2] = {cs, cs};
-#pragma unroll 1
-                for (int j = 0; j < 4; ++j) {
-                    const long long p = p000 + (j >> 1) * sx + (j & 1) * sy;
-                    const float4 v = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
-                    if (j & 1) {
-                        vy[1] = baked_lerp(vz, v, f[1]);
-                        if (j == 1) vy[0] = vy[1];
+                    for (int ix = 0; ix < 2; ++ix) {
+                        const long long p = p000 + ix * sx;
+                        const long long r0 = rows.row(pr, 2 * ix, p);
+                        const float4 v0 = baked_lerp(corner.at(r0), corner.at(r0 + 1), f[2]);
+                        const long long r1 = rows.row(pr, 2 * ix + 1, p + sy);
+                        const float4 v1 = baked_lerp(corner.at(r1), corner.at(r1 + 1), f[2]);
+                        vy[1] = baked_lerp(v0, v1, f[1]);
+                        if (ix == 0) vy[0] = vy[1];
                     }
-                    vz = v;
+                    cs = baked_lerp(vy[0], vy[1], f[0]);
+                } else {
+                    // one pair at a time: j = 2 ix + iy
+                    float4 vz = cs, vy[2] = {cs, cs};
+#pragma unroll 1
+                    for (int j = 0; j < 4; ++j) {
+                        const long long p = rows.row(pr, j, p000 + (j >> 1) * sx + (j & 1) * sy);
+                        const float4 v = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
+                        if (j & 1) {
+                            vy[1] = baked_lerp(vz, v, f[1]);
+                            if (j == 1) vy[0] = vy[1];
+                        }
+                        vz = v;
+                    }
+                    cs = baked_lerp(vy[0], vy[1], f[0]);
                 }
-                cs = baked_lerp(vy[0], vy[1], f[0]);
             }
         }
         const float a_i = 1.f - expf(-(q.step * cs.w));  // nerf.py:228 with delta = step; exactly 0 for sigma == 0
@@ -191,7 +234,7 @@ __device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const
 __global__ void __launch_bounds__(BAKED_WAVES * 64)
 baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, const float4 *__restrict__ vol, float *__restrict__ rgb,
                    float *__restrict__ depth, float *__restrict__ alpha_out) {
-    baked_march(rs, R, q, RgbaCorner{vol}, rgb, depth, alpha_out);
+    baked_march(rs, R, q, RgbaCorner{vol}, DenseRows{}, rgb, depth, alpha_out);
 }
 
 template <int B>
@@ -200,26 +243,53 @@ baked_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const f
                       float *__restrict__ depth, float *__restrict__ alpha_out) {
     ShCorner<B> corner;
     corner.coef = coef;
-    baked_march(rs, R, q, corner, rgb, depth, alpha_out);
+    baked_march(rs, R, q, corner, DenseRows{}, rgb, depth, alpha_out);
+}
+
+// the sparse forms: `vol` / `coef` are the kept rows, (M,4) / (M,B,4)
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_sparse_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows, const float4 *__restrict__ vol,
+                          float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
+    baked_march(rs, R, q, RgbaCorner{vol}, rows, rgb, depth, alpha_out);
+}
+
+template <int B>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_sparse_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows, const float4 *__restrict__ coef,
+                             float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
+    ShCorner<B> corner;
+    corner.coef = coef;
+    baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
 }
 #pragma clang fp contract(fast)
 
 static bool baked_misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
+// the kept rows of a sparse volume: what the sparse entries pass to baked_launch in addition
+struct SparseArgs {
+    const int32_t *index;
+    long long M;
+};
+
 // the checks all entries share, then the launch; src holds the rays or the camera, already checked.  degree < 0: vol is an RGBA
-// volume; 0..2: the coefficient volume of that degree
+// volume; 0..2: the coefficient volume of that degree.  sp != NULL: vol holds the M kept rows, found through sp->index
 static int baked_launch(const char *entry, const RaySrc &src, long long R, const float *vol, int degree, const uint32_t *bits, int nx,
                         int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
-                        float *depth, float *alpha, void *stream) {
+                        float *depth, float *alpha, void *stream, const SparseArgs *sp = nullptr) {
     if (degree > 2) return occ_fail(entry, "degree must be 0, 1 or 2");
+    if (sp && degree < -1) return occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
+    if (sp && sp->M < 0) return occ_fail(entry, "bad sizes (M)");
     if (const char *why = occ_bad_dims(nx, ny, nz)) return occ_fail(entry, why);
     BakedParams q;
     if (const char *why = occ_grid(nx, ny, nz, c1, c2, q.g)) return occ_fail(entry, why);
     if (!(step > 0.f) || !std::isfinite(step)) return occ_fail(entry, "step must be finite and > 0");
     if (!(terminate >= 0.f && terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
     if (R == 0) return PNR_OK;
-    if (!vol || !rgb || !depth || !alpha) return occ_fail(entry, "null argument");
-    if (occ_misaligned16(vol)) return occ_fail(entry, degree < 0 ? "vol must be 16-byte aligned" : "coef must be 16-byte aligned");
+    if (!rgb || !depth || !alpha) return occ_fail(entry, "null argument");
+    if (sp ? sp->M > 0 && (!vol || !sp->index || !bits) : !vol) return occ_fail(entry, "null argument");
+    if (occ_misaligned16(vol))
+        return occ_fail(entry, sp ? "rows must be 16-byte aligned" : degree < 0 ? "vol must be 16-byte aligned" : "coef must be 16-byte aligned");
+    if (sp && baked_misaligned4(sp->index)) return occ_fail(entry, "index must be 4-byte aligned");
     if (baked_misaligned4(bits) || baked_misaligned4(rgb) || baked_misaligned4(depth) || baked_misaligned4(alpha))
         return occ_fail(entry, "bits, rgb, depth and alpha must be 4-byte aligned");
     const long long blocks = (R + BAKED_WAVES - 1) / BAKED_WAVES;
@@ -231,11 +301,48 @@ static int baked_launch(const char *entry, const RaySrc &src, long long R, const
     const float4 *v4 = reinterpret_cast<const float4 *>(vol);
     const dim3 grid((unsigned)blocks), block(BAKED_WAVES * 64);
     hipStream_t st = (hipStream_t)stream;
+    if (sp) {
+        // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
+        const SparseRows rows = {sp->index, (int)(sp->M - 2 < 0x7ffffffeLL ? sp->M - 2 : 0x7ffffffeLL)};
+        if (degree < 0) hipLaunchKernelGGL(baked_sparse_march_kernel, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
+        else if (degree == 0) hipLaunchKernelGGL(baked_sparse_sh_march_kernel<1>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
+        else if (degree == 1) hipLaunchKernelGGL(baked_sparse_sh_march_kernel<4>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
+        else hipLaunchKernelGGL(baked_sparse_sh_march_kernel<9>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
+        return pnr_check_launch(entry);
+    }
     if (degree < 0) hipLaunchKernelGGL(baked_march_kernel, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
     else if (degree == 0) hipLaunchKernelGGL(baked_sh_march_kernel<1>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
     else if (degree == 1) hipLaunchKernelGGL(baked_sh_march_kernel<4>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
     else hipLaunchKernelGGL(baked_sh_march_kernel<9>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
     return pnr_check_launch(entry);
+}
+
+// keep[p] for the pair (2 j, 2 j + 1) of grid points: a point is a corner of the cells (i - a, j - b, k - c), a, b, c in {0, 1},
+// that exist; the pair is kept whole when either point is a corner of an occupied one
+constexpr int SPARSE_MARK_THREADS = 256;
+
+__device__ __forceinline__ bool sparse_is_corner(const uint32_t *__restrict__ bits, long long p, int nx, int ny, int nz) {
+    const int k = (int)(p % nz), j = (int)((p / nz) % ny), i = (int)(p / ((long long)ny * nz));
+    bool on = false;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int ci = i - (c >> 2), cj = j - ((c >> 1) & 1), ck = k - (c & 1);
+        if (ci < 0 || cj < 0 || ck < 0 || ci > nx - 2 || cj > ny - 2 || ck > nz - 2) continue;  // no such cell: the point is on a face
+        const long long cell = ((long long)ci * (ny - 1) + cj) * (nz - 1) + ck;
+        on = on || (bits[cell >> 5] >> (cell & 31) & 1u);
+    }
+    return on;
+}
+
+__global__ void __launch_bounds__(SPARSE_MARK_THREADS)
+sparse_points_mark_kernel(const uint32_t *__restrict__ bits, int nx, int ny, int nz, long long P, uint8_t *__restrict__ keep) {
+    const long long pair = (long long)blockIdx.x * SPARSE_MARK_THREADS + threadIdx.x;
+    const long long p = 2 * pair;
+    if (p >= P) return;
+    bool on = sparse_is_corner(bits, p, nx, ny, nz);
+    if (p + 1 < P) on = sparse_is_corner(bits, p + 1, nx, ny, nz) || on;  // (an odd P: the last point has no partner)
+    keep[p] = on ? 1 : 0;
+    if (p + 1 < P) keep[p + 1] = on ? 1 : 0;
 }
 
 }  // namespace pnr
@@ -299,4 +406,53 @@ extern "C" int pnr_baked_sh_render_views(const float *poses, int NV, int W, int 
     src.z_near = z_near; src.z_far = z_far;
     return pnr::baked_launch(entry, src, (long long)NV * W * H, coef, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
                              depth, alpha, stream);
+}
+
+extern "C" int pnr_sparse_points_mark(const uint32_t *bits, int nx, int ny, int nz, uint8_t *keep, void *stream) {
+    const char *entry = "pnr_sparse_points_mark";
+    if (const char *why = pnr::occ_bad_dims(nx, ny, nz)) return pnr::occ_fail(entry, why);
+    const long long P = (long long)nx * ny * nz;
+    if (P >= (1LL << 31)) return pnr::occ_fail(entry, "the grid must have fewer than 2^31 points (ranks are int32)");
+    if (!bits || !keep) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(bits)) return pnr::occ_fail(entry, "bits must be 4-byte aligned");
+    const long long pairs = (P + 1) / 2, blocks = (pairs + pnr::SPARSE_MARK_THREADS - 1) / pnr::SPARSE_MARK_THREADS;
+    hipLaunchKernelGGL(pnr::sparse_points_mark_kernel, dim3((unsigned)blocks), dim3(pnr::SPARSE_MARK_THREADS), 0, (hipStream_t)stream, bits,
+                       nx, ny, nz, P, keep);
+    return pnr_check_launch(entry);
+}
+
+extern "C" int pnr_baked_sparse_render_rays(const float *rays, long long R, const float *rows, long long M, int degree,
+                                            const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
+                                            const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
+                                            float *alpha, void *stream) {
+    const char *entry = "pnr_baked_sparse_render_rays";
+    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
+    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
+    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
+    pnr::RaySrc src = {};
+    src.rays = rays;
+    const pnr::SparseArgs sp = {index, M};
+    return pnr::baked_launch(entry, src, R, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha,
+                             stream, &sp);
+}
+
+extern "C" int pnr_baked_sparse_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                             float z_near, float z_far, const float *rows, long long M, int degree,
+                                             const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
+                                             const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
+                                             float *alpha, void *stream) {
+    const char *entry = "pnr_baked_sparse_render_views";
+    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
+    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
+    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
+    pnr::RaySrc src = {};
+    src.poses = poses;
+    src.W = W; src.H = H;
+    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
+    src.z_near = z_near; src.z_far = z_far;
+    const pnr::SparseArgs sp = {index, M};
+    return pnr::baked_launch(entry, src, (long long)NV * W * H, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
+                             depth, alpha, stream, &sp);
 }

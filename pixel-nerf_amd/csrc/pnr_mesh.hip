@@ -231,12 +231,9 @@ __device__ __forceinline__ float grid_coord(const GridAxis &a, int i) {
     return (float)(y + a.lo);
 }
 
-__global__ void __launch_bounds__(MC_THREADS)
-gen_grid_points_kernel(GridAxis ax, GridAxis ay, GridAxis az, long long first, long long count, float *__restrict__ xyz,
-                       float *__restrict__ viewdirs) {
-    const long long r = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
-    if (r >= count) return;
-    const long long p = first + r;
+// row r of the outputs = grid point p (both kernels below: one function, the same bits)
+__device__ __forceinline__ void grid_point_row(const GridAxis &ax, const GridAxis &ay, const GridAxis &az, long long p, long long r,
+                                               float *__restrict__ xyz, float *__restrict__ viewdirs) {
     const int k = (int)(p % az.n), j = (int)((p / az.n) % ay.n), i = (int)(p / ((long long)ay.n * az.n));
     const float x = grid_coord(ax, i), y = grid_coord(ay, j), z = grid_coord(az, k);
     xyz[3 * r] = x;
@@ -250,6 +247,30 @@ gen_grid_points_kernel(GridAxis ax, GridAxis ay, GridAxis az, long long first, l
         viewdirs[3 * r + 1] = ok ? (float)(-(double)y / nrm) : 0.f;
         viewdirs[3 * r + 2] = ok ? (float)(-(double)z / nrm) : 0.f;
     }
+}
+
+__global__ void __launch_bounds__(MC_THREADS)
+gen_grid_points_kernel(GridAxis ax, GridAxis ay, GridAxis az, long long first, long long count, float *__restrict__ xyz,
+                       float *__restrict__ viewdirs) {
+    const long long r = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (r >= count) return;
+    grid_point_row(ax, ay, az, first + r, r, xyz, viewdirs);
+}
+
+// the rows of a LIST of grid points (the kept points of a sparse baked volume); an id outside the grid gives a row of NaN
+__global__ void __launch_bounds__(MC_THREADS)
+gen_grid_points_at_kernel(GridAxis ax, GridAxis ay, GridAxis az, const int32_t *__restrict__ ids, long long count,
+                          float *__restrict__ xyz, float *__restrict__ viewdirs) {
+    const long long r = (long long)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (r >= count) return;
+    const long long p = ids[r];
+    if (p < 0 || p >= (long long)ax.n * ay.n * az.n) {
+        const float nan = __int_as_float(0x7fc00000);
+        xyz[3 * r] = xyz[3 * r + 1] = xyz[3 * r + 2] = nan;
+        if (viewdirs) viewdirs[3 * r] = viewdirs[3 * r + 1] = viewdirs[3 * r + 2] = nan;
+        return;
+    }
+    grid_point_row(ax, ay, az, p, r, xyz, viewdirs);
 }
 #pragma clang fp contract(fast)
 
@@ -321,6 +342,21 @@ extern "C" int pnr_marching_cubes_emit(const float *field, int nx, int ny, int n
     return pnr_check_launch("pnr_marching_cubes_emit");
 }
 
+// c1, c2, reso of the two point entries -> the three axes; nullptr when they are usable
+static const char *grid_axes(const double *c1, const double *c2, const int *reso, pnr::GridAxis *ax) {
+    if (!c1 || !c2 || !reso) return "c1 / c2 / reso is null (host arrays of 3)";
+    if (reso[0] < 1 || reso[1] < 1 || reso[2] < 1) return "reso must be positive";
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(c1[a]) || !std::isfinite(c2[a])) return "c1 / c2 must be finite";
+        ax[a].lo = c1[a];
+        ax[a].hi = c2[a];
+        ax[a].n = reso[a];
+        ax[a].delta = c2[a] - c1[a];
+        ax[a].step = reso[a] > 1 ? ax[a].delta / (double)(reso[a] - 1) : 0.0;
+    }
+    return nullptr;
+}
+
 extern "C" int pnr_gen_grid_points(const double *c1, const double *c2, const int *reso, long long first, long long count, float *xyz,
                                    float *viewdirs, void *stream) {
     if (!c1 || !c2 || !reso) return pnr_fail(PNR_E_INVALID, "pnr_gen_grid_points: c1 / c2 / reso is null (host arrays of 3)");
@@ -331,17 +367,26 @@ extern "C" int pnr_gen_grid_points(const double *c1, const double *c2, const int
     if (count == 0) return PNR_OK;
     if (!xyz) return pnr_fail(PNR_E_INVALID, "pnr_gen_grid_points: xyz is null");
     pnr::GridAxis ax[3];
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(c1[a]) || !std::isfinite(c2[a])) return pnr_fail(PNR_E_INVALID, "pnr_gen_grid_points: c1 / c2 must be finite");
-        ax[a].lo = c1[a];
-        ax[a].hi = c2[a];
-        ax[a].n = reso[a];
-        ax[a].delta = c2[a] - c1[a];
-        ax[a].step = reso[a] > 1 ? ax[a].delta / (double)(reso[a] - 1) : 0.0;
-    }
+    if (const char *why = grid_axes(c1, c2, reso, ax)) return pnr::mc_fail("pnr_gen_grid_points", why);
     const long long blocks = (count + pnr::MC_THREADS - 1) / pnr::MC_THREADS;
     if (blocks > 0x7fffffffLL) return pnr_fail(PNR_E_INVALID, "pnr_gen_grid_points: count exceeds the grid limit");
     hipLaunchKernelGGL(pnr::gen_grid_points_kernel, dim3((unsigned)blocks), dim3(pnr::MC_THREADS), 0, (hipStream_t)stream, ax[0], ax[1],
                        ax[2], first, count, xyz, viewdirs);
     return pnr_check_launch("pnr_gen_grid_points");
+}
+
+extern "C" int pnr_gen_grid_points_at(const double *c1, const double *c2, const int *reso, const int32_t *ids, long long count,
+                                      float *xyz, float *viewdirs, void *stream) {
+    const char *entry = "pnr_gen_grid_points_at";
+    pnr::GridAxis ax[3];
+    if (const char *why = grid_axes(c1, c2, reso, ax)) return pnr::mc_fail(entry, why);
+    if (count < 0) return pnr::mc_fail(entry, "bad sizes (count)");
+    if (count == 0) return PNR_OK;
+    if (!ids || !xyz) return pnr::mc_fail(entry, "ids / xyz is null");
+    if (((uintptr_t)ids | (uintptr_t)xyz | (uintptr_t)viewdirs) & 3) return pnr::mc_fail(entry, "ids, xyz and viewdirs must be 4-byte aligned");
+    const long long blocks = (count + pnr::MC_THREADS - 1) / pnr::MC_THREADS;
+    if (blocks > 0x7fffffffLL) return pnr::mc_fail(entry, "count exceeds the launch limit");
+    hipLaunchKernelGGL(pnr::gen_grid_points_at_kernel, dim3((unsigned)blocks), dim3(pnr::MC_THREADS), 0, (hipStream_t)stream, ax[0], ax[1],
+                       ax[2], ids, count, xyz, viewdirs);
+    return pnr_check_launch(entry);
 }

@@ -1447,6 +1447,134 @@ def baked_sh_render_views(poses, width, height, focal, c, z_near, z_far, coef, d
     return rgb, depth, alpha
 
 
+def sparse_points(bits, reso):
+    """The kept set of a sparse baked volume (pnr_sparse_points_mark; the definition is in include/pixelnerf_hip.h, "baked volumes"):
+    bits from occupancy_build of a field with `reso` = (nx,ny,nz) points -> (index (nx,ny,nz) int32 -- the rank of a kept point
+    among the kept ones, -1 elsewhere --, ids (M,) int32 -- the kept linear ids (i ny + j) nz + k, ascending).  Kept: the corners of
+    the occupied cells, closed over the pairs (2j, 2j+1) of the linear ids.  The mark is the kernel's; the prefix sum behind index
+    and ids is torch's, and sizing ids costs one host read of M (as compact_samples)."""
+    lib = _lib.load()
+    if not isinstance(bits, torch.Tensor):
+        raise TypeError("bits: expected a torch.Tensor")
+    if not bits.is_cuda:
+        raise _lib.PixelNerfHipError(f"bits: tensor must live on a HIP device (got {bits.device}); pixelnerf_amd has no CPU path")
+    if len(reso) != 3:
+        raise ValueError("sparse_points: reso must have 3 entries")
+    dev = bits.device
+    nx, ny, nz = _check_grid_args("sparse_points", bits, reso, (0.0,) * 3, (1.0,) * 3, dev)
+    total = nx * ny * nz
+    if total >= 2 ** 31:
+        raise ValueError(f"sparse_points: a grid needs fewer than 2^31 points, got {(nx, ny, nz)}")
+    keep = torch.empty((total,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_sparse_points_mark(_p(bits.contiguous()), nx, ny, nz, _p(keep), _stream()), "pnr_sparse_points_mark")
+    rank = torch.cumsum(keep, dim=0, dtype=torch.int32)  # inclusive: the rank of a kept point is rank - 1
+    index = torch.where(keep != 0, rank - 1, torch.full_like(rank, -1))
+    M = int(rank[-1])  # the host synchronisation
+    ids = torch.nonzero(keep, as_tuple=False).flatten().to(torch.int32) if M else torch.empty((0,), dtype=torch.int32, device=dev)
+    return index.view(nx, ny, nz), ids
+
+
+def gen_grid_points_at(c1, c2, reso, ids, viewdirs=True):
+    """gen_grid_points for a LIST of grid points (pnr_gen_grid_points_at): ids (M,) int32 HIP tensor of linear ids (i ny + j) nz + k
+    -> (xyz (M,3), viewdirs (M,3) | None) on the ids' device; row m holds the bits of row ids[m] of gen_grid_points(c1, c2, reso),
+    an id outside the grid a row of NaN."""
+    lib = _lib.load()
+    if not isinstance(ids, torch.Tensor):
+        raise TypeError("ids: expected a torch.Tensor")
+    if not ids.is_cuda:
+        raise _lib.PixelNerfHipError(f"ids: tensor must live on a HIP device (got {ids.device}); pixelnerf_amd has no CPU path")
+    if ids.dtype != torch.int32 or ids.dim() != 1:
+        raise TypeError(f"ids: expected a 1-d int32 tensor, got {ids.dtype} {tuple(ids.shape)}")
+    if len(c1) != 3 or len(c2) != 3 or len(reso) != 3:
+        raise ValueError("gen_grid_points_at: c1, c2, reso must have 3 entries each")
+    ids, dev = ids.contiguous(), ids.device
+    xyz = torch.empty((ids.shape[0], 3), dtype=torch.float32, device=dev)
+    vd = torch.empty_like(xyz) if viewdirs else None
+    lo, hi = (ctypes.c_double * 3)(*[float(v) for v in c1]), (ctypes.c_double * 3)(*[float(v) for v in c2])
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_gen_grid_points_at(lo, hi, (ctypes.c_int * 3)(*[int(r) for r in reso]), _p(ids), ids.shape[0], _p(xyz), _p(vd),
+                                              _stream()), "pnr_gen_grid_points_at")
+    return xyz, vd
+
+
+def _baked_sparse_args(what, rows, degree, index, bits, reso, c1, c2, step, terminate):
+    """_baked_args for the kept rows of a sparse volume: rows (M,4) with degree None / -1, (M,(degree+1)^2,4) with degree 0..2; index
+    (nx,ny,nz) int32 and bits, both mandatory -> (rows, degree (-1 for RGBA), (nx, ny, nz), step, terminate)"""
+    degree = -1 if degree is None else int(degree)
+    if degree not in (-1, 0, 1, 2):
+        raise ValueError(f"{what}: degree must be None / -1 (RGBA rows), 0, 1 or 2, got {degree}")
+    shape = (None, 4) if degree < 0 else (None, (degree + 1) ** 2, 4)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != len(shape) or tuple(rows.shape[1:]) != shape[1:]:
+        raise ValueError(f"{what}: rows must be (M,{','.join(str(s) for s in shape[1:])}) at degree {degree}, got "
+                         f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
+    if bits is None or index is None:
+        raise ValueError(f"{what}: index and bits are mandatory (a sparse volume has nothing to march unskipped)")
+    rows = _f32(rows, "rows", shape)
+    if rows.numel() and rows.data_ptr() % 16:
+        raise ValueError(f"{what}: rows must be 16-byte aligned")
+    _check_grid_args(what, bits, dims, c1, c2, rows.device)
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims or index.device != rows.device:
+        raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {rows.device}")
+    return rows, degree, dims, step, terminate
+
+
+def baked_sparse_render(rays, rows, degree, index, bits, reso, c1, c2, step, white_bkgd=False, terminate=0.0):
+    """Rays through a sparse baked volume (pnr_baked_sparse_render_rays; include/pixelnerf_hip.h, "baked volumes"): rows (M,4)
+    (degree None: RGBA) or (M,B,4) (degree 0, 1, 2) fp32 HIP tensor -- the rows of the dense volume at the kept points --, index and
+    bits as sparse_points took and returned them.  The bytes of baked_render / baked_sh_render on the dense volume with the same
+    bits; an index value that names no pair of rows drops its sample (sigma = 0) instead of reading.
+    -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
+    lib = _lib.load()
+    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_args("baked_sparse_render", rows, degree, index, bits, reso, c1, c2, step,
+                                                                     terminate)
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    if rows.device != dev:
+        raise ValueError(f"baked_sparse_render: rows live on {rows.device}, the rays on {dev}")
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    M = rows.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_sparse_render_rays(_p(rays), R, _p(rows) if M else None, M, degree, _p(index.contiguous()),
+                                                    _p(bits.contiguous()), nx, ny, nz, lo, hi, step, int(bool(white_bkgd)), terminate,
+                                                    _p(rgb), _p(depth), _p(alpha), _stream()), "pnr_baked_sparse_render_rays")
+    return rgb, depth, alpha
+
+
+def baked_sparse_render_views(poses, width, height, focal, c, z_near, z_far, rows, degree, index, bits, reso, c1, c2, step,
+                              white_bkgd=False, terminate=0.0):
+    """baked_render_views through a sparse baked volume (pnr_baked_sparse_render_views): the same bits as
+    baked_sparse_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
+    lib = _lib.load()
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"baked_sparse_render_views: the image must have at least one pixel, got {W} x {H}")
+    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_args("baked_sparse_render_views", rows, degree, index, bits, reso, c1, c2,
+                                                                     step, terminate)
+    poses = _f32(poses, "poses", (None, 4, 4))
+    NV, dev = poses.shape[0], poses.device
+    if rows.device != dev:
+        raise ValueError(f"baked_sparse_render_views: rows live on {rows.device}, the poses on {dev}")
+    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+    R = NV * H * W
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    M = rows.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_sparse_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far),
+                                                     _p(rows) if M else None, M, degree, _p(index.contiguous()), _p(bits.contiguous()),
+                                                     nx, ny, nz, lo, hi, step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth),
+                                                     _p(alpha), _stream()), "pnr_baked_sparse_render_views")
+    return rgb, depth, alpha
+
+
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):
     """philox_noise for a list of GLOBAL ray ids (pnr_philox_noise_ids): ray_ids (R,) int64 HIP tensor -- any order, repeats
     allowed, beyond 2^31 too -- -> the dict philox_noise returns, row r holding what the seeded renderer entries draw for ray

@@ -9,6 +9,9 @@ The image is an APPROXIMATION of the network's render: trilinear in space, one v
 BakedSHVolume lifts the one-direction limit: it keeps real spherical harmonics up to degree 2 of all four channels at every grid
 point (n_dirs network passes to bake, 4 or 9 times the memory) and the march evaluates them for each ray's own direction
 (pnr_baked_sh_render_rays / pnr_baked_sh_render_views); the other limits stay.
+SparseBakedVolume keeps only the rows of the grid points that the occupied cells of an OccupancyGrid read, renders the bytes of the
+dense march with the same bits (pnr_baked_sparse_render_rays / pnr_baked_sparse_render_views) and is baked without touching the
+other points: less to bake and to store, not a faster march (profiles/baked_notes.md).
 
 The grid is the one util.recon.marching_cubes and util.occupancy.OccupancyGrid use (points of ops.gen_grid_points, cells of the TRUE
 spacing (c2 - c1) / (reso - 1)); the skip grid of a volume is an OccupancyGrid of its sigma channel with dilate 0.
@@ -22,8 +25,8 @@ from .occupancy import OccupancyGrid, _check_geometry
 
 
 class _Baked:
-    """what BakedVolume and BakedSHVolume share: the march through `self.occupancy` on the grid (reso, c1, c2).  A subclass says
-    which entries march its volume (_march_rays, _march_views)."""
+    """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2).  A
+    subclass says which entries march its volume (_march_rays, _march_views)."""
 
     @property
     def cell_size(self):
@@ -173,6 +176,12 @@ class BakedVolume(_Baked):
         from .. import ops
         return ops.baked_render_views(poses, W, H, focal, c, z_near, z_far, self.vol, self.reso, self.c1, self.c2, step, bits=bits,
                                       white_bkgd=white_bkgd, terminate=terminate)
+
+    def sparse(self, occupancy=None):
+        """The SparseBakedVolume of this volume: the rows of the grid points that the occupied cells of `occupancy` read (None: the
+        volume's own skip grid; or an OccupancyGrid of the same reso, c1, c2) and nothing else.  It renders the bytes of this volume's
+        march with those bits: with None, `sparse().render(...)` equals `render(..., skip=True)` bit for bit at any skip_threshold."""
+        return _sparse_of(self, self.vol.view(-1, 4), occupancy, "BakedVolume.sparse")
 
     def state_dict(self):
         """the volume, the geometry and the skip threshold; the skip grid is rebuilt on load"""
@@ -370,6 +379,11 @@ class BakedSHVolume(_Baked):
         return ops.baked_sh_render_views(poses, W, H, focal, c, z_near, z_far, self.coef, self.degree, self.reso, self.c1, self.c2, step,
                                          bits=bits, white_bkgd=white_bkgd, terminate=terminate)
 
+    def sparse(self, occupancy=None):
+        """BakedVolume.sparse for the coefficient volume: the kept points' (B,4) coefficients; `sparse().render(...)` equals
+        `render(..., skip=True)` bit for bit"""
+        return _sparse_of(self, self.coef.view(-1, *self.coef.shape[3:]), occupancy, "BakedSHVolume.sparse")
+
     def state_dict(self):
         """the coefficients (the degree follows from their shape), the geometry and the skip threshold; the skip grid is rebuilt on load"""
         return {"coef": self.coef, "c1": torch.tensor(self.c1, dtype=torch.float64), "c2": torch.tensor(self.c2, dtype=torch.float64),
@@ -380,3 +394,180 @@ class BakedSHVolume(_Baked):
         """:param device where to put the volume; None: where state["coef"] lives"""
         coef = state["coef"] if device is None else state["coef"].to(device)
         return cls(coef, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
+
+
+# ---------------------------------------------------------------- sparse volumes: only the rows that occupied cells read
+
+def _same_grid(what, occupancy, reso, c1, c2):
+    if not isinstance(occupancy, OccupancyGrid):
+        raise ValueError(f"{what}: occupancy must be an OccupancyGrid, got {type(occupancy).__name__}")
+    if (tuple(occupancy.reso), tuple(occupancy.c1), tuple(occupancy.c2)) != (tuple(reso), tuple(c1), tuple(c2)):
+        raise ValueError(f"{what}: the occupancy grid spans {occupancy.reso} points over {occupancy.c1} .. {occupancy.c2}, the volume "
+                         f"{tuple(reso)} over {tuple(c1)} .. {tuple(c2)}")
+
+
+def _sparse_of(dense, per_point, occupancy, what):
+    """BakedVolume.sparse / BakedSHVolume.sparse: the kept rows of the dense tensor `per_point` (P, ...)"""
+    occupancy = dense.occupancy if occupancy is None else occupancy
+    _same_grid(what, occupancy, dense.reso, dense.c1, dense.c2)
+    if occupancy.bits.device != per_point.device:
+        raise ValueError(f"{what}: the occupancy grid lives on {occupancy.bits.device}, the volume on {per_point.device}")
+    from .. import ops
+    index, ids = ops.sparse_points(occupancy.bits, dense.reso)
+    return SparseBakedVolume(per_point.index_select(0, ids.long()), occupancy, index=index, ids=ids)
+
+
+class SparseBakedVolume(_Baked):
+    """A baked volume that keeps only what its occupancy grid lets the march read.  rows: (M,4) fp32 (degree None: the RGBA march) or
+    (M,B,4) (degree 0, 1, 2: the view-dependent march) on the device, the rows of the dense volume at the kept points; ids (M,)
+    int32: their linear ids (i ny + j) nz + k, ascending; index (nx,ny,nz) int32: the rank of a kept point, -1 elsewhere; occupancy:
+    the OccupancyGrid whose cells decide (reso, c1, c2 are its geometry).  Kept: the corners of the occupied cells, closed over the
+    pairs (2j, 2j+1) of the linear ids (include/pixelnerf_hip.h, "baked volumes", the sparse paragraph).
+    `render` / `render_views` give the bytes of the dense volume's march with `occupancy.bits`; `from_model` bakes the kept points
+    alone and gives the dense bake's rows bit for bit.  Memory: `nbytes` = rows + 4 bytes per grid point (index) + the bitfield."""
+
+    def __init__(self, rows, occupancy, index=None, ids=None):
+        from .. import _lib, ops
+        if not isinstance(rows, torch.Tensor) or rows.dim() not in (2, 3) or rows.shape[-1] != 4 or rows.dtype != torch.float32:
+            raise ValueError("SparseBakedVolume: rows must be a (M,4) or (M,B,4) float32 tensor")
+        degree = _degree_of(rows.shape[1], "SparseBakedVolume") if rows.dim() == 3 else None
+        if not isinstance(occupancy, OccupancyGrid):
+            raise ValueError(f"SparseBakedVolume: occupancy must be an OccupancyGrid, got {type(occupancy).__name__}")
+        if not rows.is_cuda:
+            raise _lib.PixelNerfHipError(f"SparseBakedVolume: rows must live on a HIP device (got {rows.device}); pixelnerf_amd has no CPU path")
+        if occupancy.bits.device != rows.device:
+            raise ValueError(f"SparseBakedVolume: the occupancy grid lives on {occupancy.bits.device}, the rows on {rows.device}")
+        if index is None or ids is None:
+            index, ids = ops.sparse_points(occupancy.bits, occupancy.reso)
+        if ids.shape[0] != rows.shape[0]:
+            raise ValueError(f"SparseBakedVolume: the occupancy grid keeps {ids.shape[0]} points, rows holds {rows.shape[0]}")
+        rows = rows.detach().contiguous()
+        if not bool(torch.isfinite(rows).all()):
+            raise ValueError("SparseBakedVolume: the volume holds a non-finite value")
+        self.rows, self.degree, self.index, self.ids, self.occupancy = rows, degree, index, ids, occupancy
+        self.reso, self.c1, self.c2 = occupancy.reso, occupancy.c1, occupancy.c2
+
+    @property
+    def n_rows(self):
+        return self.rows.shape[0]
+
+    @property
+    def nbytes(self):
+        return 4 * (self.rows.numel() + self.index.numel() + self.occupancy.bits.numel())
+
+    @classmethod
+    def from_model(cls, net, c1, c2, reso, occupancy, degree=None, n_dirs=32, viewdirs="origin", coarse=None, eval_batch_size=100000):
+        """The sparse bake: BakedVolume.from_model's loop (degree None; `viewdirs` as there) or BakedSHVolume.from_model's (degree
+        0, 1, 2 with `n_dirs` directions; `viewdirs` is not used) -- the same checks, the same fixed projection order, even chunks, the
+        train / eval flag restored -- over the kept points of `occupancy` in ascending order (ops.gen_grid_points_at supplies them): the
+        network sees M points per pass, not nx ny nz.
+        `rows` equals the dense from_model tensor at `ids` bit for bit, at every precision and whatever eval_batch_size: the kept set is
+        closed over the pairs (2j, 2j+1) of the dense launch and a chunk has an even length, so every kept point stands at a place of
+        its own parity (profiles/occupancy_notes.md).  With occupancy = OccupancyGrid.from_model(net, c1, c2, reso, threshold,
+        dilate=1) the result is the dense bake with nothing in the cells the grid calls empty.  A non-finite output raises ValueError."""
+        from .. import ops
+        what = "SparseBakedVolume.from_model"
+        if int(getattr(net, "num_objs", 1) or 1) > 1:
+            raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
+        reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
+        _same_grid(what, occupancy, reso, c1, c2)
+        use_viewdirs = bool(getattr(net, "use_viewdirs", False))
+        device = next(net.parameters()).device
+        if occupancy.bits.device != device:
+            raise ValueError(f"{what}: the occupancy grid lives on {occupancy.bits.device}, the network on {device}")
+        origin, const_dir, dirs, P = True, None, None, None
+        if degree is None:
+            origin = isinstance(viewdirs, str)
+            if origin and viewdirs != "origin":
+                raise ValueError(f"{what}: viewdirs must be 'origin' or a 3-vector, got {viewdirs!r}")
+            if not origin:
+                const_dir = torch.as_tensor(viewdirs, dtype=torch.float32).flatten()
+                if const_dir.numel() != 3 or not bool(torch.isfinite(const_dir).all()) or float(const_dir.norm()) == 0.0:
+                    raise ValueError(f"{what}: a constant view direction must be a finite non-zero 3-vector")
+                const_dir = (const_dir / const_dir.norm()).to(device)
+            if use_viewdirs and origin:
+                warnings.warn("Running marching cubes with fake view dirs (pointing to origin), output may be invalid")
+        else:
+            degree = int(degree)
+            P = BakedSHVolume.projection(n_dirs, degree)  # (the degree and n_dirs checks)
+            if not use_viewdirs and degree > 0:
+                warnings.warn(f"{what}: the network takes no view directions; baking at degree 0")
+                degree = 0
+            if use_viewdirs:
+                dirs, P = BakedSHVolume.directions(n_dirs).to(device), P.float().to(device)
+            else:
+                P = torch.ones((1, 1), device=device)  # one pass: its output is the DC part
+        nb = None if degree is None else (degree + 1) ** 2
+        if coarse is None:
+            coarse = getattr(net, "mlp_fine", None) is None
+        chunk = max(2, int(eval_batch_size) // 2 * 2)
+        index, ids = ops.sparse_points(occupancy.bits, reso)
+        total = ids.shape[0]
+        is_train = bool(getattr(net, "training", False))
+        if hasattr(net, "eval"):
+            net.eval()
+        try:
+            with torch.no_grad():
+                if degree is None:
+                    rows = torch.empty((total, 4), dtype=torch.float32, device=device)
+                else:
+                    rows = torch.zeros((total, nb, 4), dtype=torch.float32, device=device)
+                for first in range(0, total, chunk):
+                    count = min(chunk, total - first)
+                    pnts, vd = ops.gen_grid_points_at(c1, c2, reso, ids[first:first + count],
+                                                      viewdirs=degree is None and use_viewdirs and origin)
+                    if degree is None:
+                        if use_viewdirs and not origin:
+                            vd = const_dir.expand(count, 3).contiguous()
+                        out = net(pnts[None], coarse=bool(coarse), viewdirs=vd[None] if use_viewdirs else None)
+                        rows[first:first + count] = out.reshape(count, -1)[:, :4]
+                        continue
+                    part = rows[first:first + count]
+                    for m in range(P.shape[1]):
+                        vd = dirs[m].expand(count, 3).contiguous()[None] if use_viewdirs else None
+                        out = net(pnts[None], coarse=bool(coarse), viewdirs=vd).reshape(count, -1)[:, :4]
+                        part += out[:, None, :] * P[:nb, m][None, :, None]  # the product, then the sum: two roundings, in the order of m
+        finally:
+            if is_train:
+                net.train()
+        return cls(rows, occupancy, index=index, ids=ids)
+
+    def _march_args(self, step, terminate, skip):
+        if not skip:
+            raise ValueError("SparseBakedVolume: skip=False is not available (a sparse volume holds nothing to march unskipped)")
+        return super()._march_args(step, terminate, True)
+
+    def _march_rays(self, rays, step, bits, white_bkgd, terminate):
+        from .. import ops
+        return ops.baked_sparse_render(rays, self.rows, self.degree, self.index, bits, self.reso, self.c1, self.c2, step,
+                                       white_bkgd=white_bkgd, terminate=terminate)
+
+    def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
+        from .. import ops
+        return ops.baked_sparse_render_views(poses, W, H, focal, c, z_near, z_far, self.rows, self.degree, self.index, bits, self.reso,
+                                             self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
+
+    def to_dense(self):
+        """(nx,ny,nz,4) or (nx,ny,nz,B,4): the rows at their grid points, zeros at the dropped ones -- marched with `occupancy.bits` it
+        renders the bytes of this volume"""
+        total = self.reso[0] * self.reso[1] * self.reso[2]
+        dense = torch.zeros((total, *self.rows.shape[1:]), dtype=torch.float32, device=self.rows.device)
+        dense.index_copy_(0, self.ids.long(), self.rows)
+        return dense.view(*self.reso, *self.rows.shape[1:])
+
+    def state_dict(self):
+        """the rows (the degree follows from their shape), the bitfield and the geometry; index and ids are rebuilt on load and are the
+        same bytes.  The threshold and the dilation the grid was built with are not part of the state."""
+        return {"rows": self.rows, "bits": self.occupancy.bits, "reso": torch.tensor(self.reso, dtype=torch.int64),
+                "c1": torch.tensor(self.c1, dtype=torch.float64), "c2": torch.tensor(self.c2, dtype=torch.float64)}
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        """:param device where to put the volume; None: where state["rows"] lives.  The loaded grid reports threshold NaN and dilate 0
+        (neither is recorded); its n_occupied is counted from the bits."""
+        rows = state["rows"] if device is None else state["rows"].to(device)
+        bits = state["bits"].to(rows.device).contiguous()
+        table = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int32, device=rows.device)
+        n_occupied = table[bits.view(torch.uint8).long()].sum().to(torch.int32)
+        occupancy = OccupancyGrid(bits, state["reso"].tolist(), state["c1"].tolist(), state["c2"].tolist(), float("nan"), 0, n_occupied)
+        return cls(rows, occupancy)
