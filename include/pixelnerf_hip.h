@@ -993,7 +993,8 @@ int pnr_baked_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H
  * DIRECTION instead of one value: real spherical harmonics up to degree L in {0, 1, 2} on all four channels, evaluated in the
  * march for each ray's own direction.  An SH render of a ray equals the RGBA render, by the rules above, of the volume "this
  * object seen from direction d": that sentence is the specification; what follows says how that volume's corners are computed.
- * Still trilinear in space, still equidistant samples, still nothing outside the box; degree <= 2, fp32 only.
+ * Still trilinear in space, still equidistant samples, still nothing outside the box; degree <= 2; fp32 storage here, fp16
+ * storage through the half entries below (the same march on the widened values).
  * Layout.  B = (L+1)^2 basis functions.  coef (nx,ny,nz,B,4) fp32, C-contiguous, 16-byte aligned: float4 k of a grid point holds
  *   (r_k, g_k, b_k, sigma_k); 16 B bytes per point (64 at degree 1, 144 at degree 2).  The grid, c1, c2, the cells and the point
  *   order are those of the RGBA volume.
@@ -1080,6 +1081,53 @@ int pnr_baked_sparse_render_views(const float *poses /*(NV,4,4)*/, int NV, int W
                                   const int32_t *index /*(nx,ny,nz)*/, const uint32_t *bits, int nx, int ny, int nz,
                                   const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd,
                                   float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
+
+/* Half-precision baked volumes (added within ABI rev 12 as well): fp16 STORAGE, the fp32 march.  What a volume stores -- rgb in
+ * [0, 1], a relu'd sigma, low-order SH coefficients of those -- is kept as IEEE binary16: a stored (r, g, b, sigma) is four fp16
+ * numbers in 8 bytes, a grid point 8 B bytes (8 for RGBA, 32 at degree 1, 72 at degree 2), half of the forms above.
+ * The contract, which needs no tolerance because fp16 -> fp32 is exact:
+ *     marching a half volume gives the BYTES of the fp32 march of the same values widened to fp32
+ *   -- pnr_baked_half_render_* gives the bytes of pnr_baked_render_* (degree -1) / pnr_baked_sh_render_* (degree 0, 1, 2), and
+ *   pnr_baked_sparse_half_render_* those of pnr_baked_sparse_render_*, on the widened array with every other argument the same.
+ *   Every stored number is loaded (one 8-byte load per (r, g, b, sigma)) and widened exactly, component by component; subnormals,
+ *   -0 and 65504 keep their value.  EVERYTHING ELSE IS THOSE ENTRIES' TEXT, operation for operation (it is the same function,
+ *   instantiated on what a stored number is): the left-to-right SH sum in fp32, the per-corner clamps, the blend order z, y, x, the
+ *   compositing scan, terminate, white_bkgd, skipping, the ray that cannot be sampled, the sparse safety rule (a sample whose pair
+ *   rows are not in [0, M - 2] reads no row), the number of corner pairs in flight.
+ * degree = -1: vol (nx,ny,nz,4) / rows (M,4) fp16, the RGBA march.  degree 0, 1, 2: vol (nx,ny,nz,B,4) / rows (M,B,4) fp16, the
+ *   view-dependent march.  vol / rows are C-contiguous and 16-byte aligned.  The sparse pair has the argument lists of
+ *   pnr_baked_sparse_render_rays / _views with `const uint16_t *rows`.
+ * What rounding to fp16 costs, per stored value (util.bake.to_half: round to nearest even, a finite value beyond +-65504 saturates
+ *   at +-65504, so an infinity is never stored -- it would put inf - inf into the blend):
+ *     a value v with |v| <= 65504 is off by at most max(2^-11 |v|, 2^-25);
+ *     an SH corner value before the clamp by at most 2^-11 (|c_0| + sum_k |c_k| |Y_k|) (+ k 2^-25 for subnormal coefficients) plus
+ *     the fp32 rounding of the sum that the fp32 form has as well;
+ *     a sigma above 65504 is stored as 65504: at any usable step (step sigma > 88) that corner alone still gives alpha = 1, but
+ *     the trilinear blend with its neighbours weighs 65504 where it weighed more, so samples next to it can come out less opaque.
+ *   The skip grid of a half volume is built from the widened values, so skipping stays exact at threshold 0; a sigma below 2^-25
+ *   rounds to 0 and may switch its cells off.  The effect on an image has no bound here; profiles/baked_notes.md has measurements.
+ * PNR_E_INVALID, before any HIP call: what the fp32 counterparts refuse, a degree outside {-1, 0, 1, 2}, vol / rows not 16-byte
+ *   aligned.  R = 0: no-op. */
+int pnr_baked_half_render_rays(const float *rays, long long R, const uint16_t *vol /*(nx,ny,nz,4) or (nx,ny,nz,B,4) fp16*/,
+                               int degree, const uint32_t *bits /*nullable*/, int nx, int ny, int nz, const float *c1 /*host*/,
+                               const float *c2 /*host*/, float step, int white_bkgd, float terminate, float *rgb /*(R,3)*/,
+                               float *depth /*(R)*/, float *alpha /*(R)*/, void *stream);
+int pnr_baked_half_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                float z_near, float z_far, const uint16_t *vol /*(nx,ny,nz,4) or (nx,ny,nz,B,4) fp16*/,
+                                int degree, const uint32_t *bits /*nullable*/, int nx, int ny, int nz, const float *c1 /*host*/,
+                                const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                                float *rgb /*(NV H W,3)*/, float *depth, float *alpha, void *stream);
+int pnr_baked_sparse_half_render_rays(const float *rays, long long R, const uint16_t *rows /*(M,4) or (M,B,4) fp16*/, long long M,
+                                      int degree, const int32_t *index /*(nx,ny,nz)*/, const uint32_t *bits, int nx, int ny,
+                                      int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd,
+                                      float terminate, float *rgb /*(R,3)*/, float *depth /*(R)*/, float *alpha /*(R)*/,
+                                      void *stream);
+int pnr_baked_sparse_half_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx,
+                                       float cy, float z_near, float z_far, const uint16_t *rows /*(M,4) or (M,B,4) fp16*/,
+                                       long long M, int degree, const int32_t *index /*(nx,ny,nz)*/, const uint32_t *bits,
+                                       int nx, int ny, int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step,
+                                       int white_bkgd, float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha,
+                                       void *stream);
 
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on

@@ -10,6 +10,8 @@
 // The sparse form (pnr_baked_sparse_render_*) keeps only the rows of the grid points that occupied cells read (the kept set of
 // pnr_sparse_points_mark) and an int32 index over the grid; baked_march is instantiated a second time on WHERE a pair of corners
 // lies: at rows p, p + 1 of the dense array, or at rows index[p], index[p] + 1 of the kept ones.
+// The half forms (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*) instantiate it a third time, on WHAT A STORED NUMBER IS:
+// a float4, or four fp16 numbers widened exactly to fp32 on load; everything after the load is the same code.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -42,22 +44,34 @@ __device__ __forceinline__ float4 baked_lerp(const float4 a, const float4 b, flo
     return make_float4(a.x + f * (b.x - a.x), a.y + f * (b.y - a.y), a.z + f * (b.z - a.z), a.w + f * (b.w - a.w));
 }
 
+// What a stored (r,g,b,sigma) is: a float4, or four fp16 numbers in 8 bytes (the half entries).  baked_widen is the ONLY place the
+// two differ: fp16 -> fp32 is exact (one v_cvt_f32_f16 per component; subnormals, -0 and 65504 keep their value), so the march of
+// a half volume performs the fp32 march's operations on the widened values and gives its bytes.  One 8-byte load per coefficient:
+// legal at every point (a pair of corners is 16-byte aligned only where the point's parity allows).
+struct alignas(8) Half4 {
+    _Float16 x, y, z, w;
+};
+__device__ __forceinline__ float4 baked_widen(const float4 v) { return v; }
+__device__ __forceinline__ float4 baked_widen(const Half4 v) { return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w); }
+
 // What the march reads at a corner of a cell.  RGBA volume: the float4 of the grid point.
-struct RgbaCorner {
-    const float4 *vol;  // (nx,ny,nz) x (r,g,b,sigma)
+template <class Stored>
+struct RgbaCornerOf {
+    const Stored *vol;  // (nx,ny,nz) x (r,g,b,sigma)
     __device__ __forceinline__ void set_ray(const Ray8 &) {}
     static constexpr int PAIRS_IN_FLIGHT = 4;  // 8 loads: all in flight at once
-    __device__ __forceinline__ float4 at(long long point) const { return vol[point]; }
+    __device__ __forceinline__ float4 at(long long point) const { return baked_widen(vol[point]); }
 };
+using RgbaCorner = RgbaCornerOf<float4>;
 
 // fp32(sqrt 3), fp32(sqrt 15), fp32(sqrt 5 / 2), fp32(sqrt 15 / 2): rounded once from the fp64 values
 constexpr float SH_C1 = 1.7320508075688772f, SH_C2 = 3.872983346207417f, SH_C20 = 1.118033988749895f, SH_C22 = 1.9364916731037085f;
 
 // SH volume: the B contiguous float4s of the grid point, reduced with the ray's basis values to one float4 and clamped.  y[k - 1]
 // holds Y_k of the header for k >= 1 (Y_0 = 1 is not stored: c * 1 is c); a per-ray constant.
-template <int B>
+template <int B, class Stored = float4>
 struct ShCorner {
-    const float4 *coef;  // (nx,ny,nz,B) x (r,g,b,sigma)
+    const Stored *coef;  // (nx,ny,nz,B) x (r,g,b,sigma)
     float y[B > 1 ? B - 1 : 1];
     __device__ __forceinline__ void set_ray(const Ray8 &ray) {
         const float n2 = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
@@ -71,13 +85,15 @@ struct ShCorner {
     }
     // A pair of corners along z is 2 B contiguous float4s.  All 8 B in flight would be 72 float4s at B = 9, a wave per SIMD; the
     // march keeps this many pairs in flight instead and leaves the wait to the other waves of the SIMD.
+    // The half instantiations keep the same numbers: their in-flight loads hold half the registers, but the fp32 form measured
+    // no gain from more pairs in flight (profiles/baked_notes.md); the outputs do not depend on the choice.
     static constexpr int PAIRS_IN_FLIGHT = B == 1 ? 4 : B == 4 ? 2 : 1;
     __device__ __forceinline__ float4 at(long long point) const {
-        const float4 *c = coef + point * B;
-        float4 v = c[0];
+        const Stored *c = coef + point * B;
+        float4 v = baked_widen(c[0]);
 #pragma unroll
         for (int k = 1; k < B; ++k) {
-            const float4 a = c[k];
+            const float4 a = baked_widen(c[k]);
             v.x = v.x + a.x * y[k - 1]; v.y = v.y + a.y * y[k - 1]; v.z = v.z + a.z * y[k - 1]; v.w = v.w + a.w * y[k - 1];
         }
         // per corner, before the blend; written so that a value inside the range keeps its bits (-0 included)
@@ -261,6 +277,38 @@ baked_sparse_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, 
     corner.coef = coef;
     baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
 }
+
+// the half forms (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*): the four marches above on fp16 storage
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_half_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Half4 *__restrict__ vol, float *__restrict__ rgb,
+                        float *__restrict__ depth, float *__restrict__ alpha_out) {
+    baked_march(rs, R, q, RgbaCornerOf<Half4>{vol}, DenseRows{}, rgb, depth, alpha_out);
+}
+
+template <int B>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_half_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Half4 *__restrict__ coef, float *__restrict__ rgb,
+                           float *__restrict__ depth, float *__restrict__ alpha_out) {
+    ShCorner<B, Half4> corner;
+    corner.coef = coef;
+    baked_march(rs, R, q, corner, DenseRows{}, rgb, depth, alpha_out);
+}
+
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_sparse_half_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows, const Half4 *__restrict__ vol,
+                               float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
+    baked_march(rs, R, q, RgbaCornerOf<Half4>{vol}, rows, rgb, depth, alpha_out);
+}
+
+template <int B>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_sparse_half_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows,
+                                  const Half4 *__restrict__ coef, float *__restrict__ rgb, float *__restrict__ depth,
+                                  float *__restrict__ alpha_out) {
+    ShCorner<B, Half4> corner;
+    corner.coef = coef;
+    baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
+}
 #pragma clang fp contract(fast)
 
 static bool baked_misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
@@ -272,10 +320,11 @@ struct SparseArgs {
 };
 
 // the checks all entries share, then the launch; src holds the rays or the camera, already checked.  degree < 0: vol is an RGBA
-// volume; 0..2: the coefficient volume of that degree.  sp != NULL: vol holds the M kept rows, found through sp->index
-static int baked_launch(const char *entry, const RaySrc &src, long long R, const float *vol, int degree, const uint32_t *bits, int nx,
+// volume; 0..2: the coefficient volume of that degree.  sp != NULL: vol holds the M kept rows, found through sp->index.  half: vol
+// holds fp16 numbers (the half entries), else fp32
+static int baked_launch(const char *entry, const RaySrc &src, long long R, const void *vol, int degree, const uint32_t *bits, int nx,
                         int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
-                        float *depth, float *alpha, void *stream, const SparseArgs *sp = nullptr) {
+                        float *depth, float *alpha, void *stream, const SparseArgs *sp = nullptr, bool half = false) {
     if (degree > 2) return occ_fail(entry, "degree must be 0, 1 or 2");
     if (sp && degree < -1) return occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
     if (sp && sp->M < 0) return occ_fail(entry, "bad sizes (M)");
@@ -288,7 +337,7 @@ static int baked_launch(const char *entry, const RaySrc &src, long long R, const
     if (!rgb || !depth || !alpha) return occ_fail(entry, "null argument");
     if (sp ? sp->M > 0 && (!vol || !sp->index || !bits) : !vol) return occ_fail(entry, "null argument");
     if (occ_misaligned16(vol))
-        return occ_fail(entry, sp ? "rows must be 16-byte aligned" : degree < 0 ? "vol must be 16-byte aligned" : "coef must be 16-byte aligned");
+        return occ_fail(entry, sp ? "rows must be 16-byte aligned" : degree < 0 || half ? "vol must be 16-byte aligned" : "coef must be 16-byte aligned");
     if (sp && baked_misaligned4(sp->index)) return occ_fail(entry, "index must be 4-byte aligned");
     if (baked_misaligned4(bits) || baked_misaligned4(rgb) || baked_misaligned4(depth) || baked_misaligned4(alpha))
         return occ_fail(entry, "bits, rgb, depth and alpha must be 4-byte aligned");
@@ -299,15 +348,30 @@ static int baked_launch(const char *entry, const RaySrc &src, long long R, const
     q.eps = terminate;
     q.white_bkgd = white_bkgd;
     const float4 *v4 = reinterpret_cast<const float4 *>(vol);
+    const Half4 *h4 = reinterpret_cast<const Half4 *>(vol);
     const dim3 grid((unsigned)blocks), block(BAKED_WAVES * 64);
     hipStream_t st = (hipStream_t)stream;
     if (sp) {
         // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
         const SparseRows rows = {sp->index, (int)(sp->M - 2 < 0x7ffffffeLL ? sp->M - 2 : 0x7ffffffeLL)};
+        if (half) {
+            if (degree < 0) hipLaunchKernelGGL(baked_sparse_half_march_kernel, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
+            else if (degree == 0) hipLaunchKernelGGL(baked_sparse_half_sh_march_kernel<1>, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
+            else if (degree == 1) hipLaunchKernelGGL(baked_sparse_half_sh_march_kernel<4>, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
+            else hipLaunchKernelGGL(baked_sparse_half_sh_march_kernel<9>, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
+            return pnr_check_launch(entry);
+        }
         if (degree < 0) hipLaunchKernelGGL(baked_sparse_march_kernel, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
         else if (degree == 0) hipLaunchKernelGGL(baked_sparse_sh_march_kernel<1>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
         else if (degree == 1) hipLaunchKernelGGL(baked_sparse_sh_march_kernel<4>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
         else hipLaunchKernelGGL(baked_sparse_sh_march_kernel<9>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
+        return pnr_check_launch(entry);
+    }
+    if (half) {
+        if (degree < 0) hipLaunchKernelGGL(baked_half_march_kernel, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
+        else if (degree == 0) hipLaunchKernelGGL(baked_half_sh_march_kernel<1>, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
+        else if (degree == 1) hipLaunchKernelGGL(baked_half_sh_march_kernel<4>, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
+        else hipLaunchKernelGGL(baked_half_sh_march_kernel<9>, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
         return pnr_check_launch(entry);
     }
     if (degree < 0) hipLaunchKernelGGL(baked_march_kernel, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
@@ -455,4 +519,70 @@ extern "C" int pnr_baked_sparse_render_views(const float *poses, int NV, int W, 
     const pnr::SparseArgs sp = {index, M};
     return pnr::baked_launch(entry, src, (long long)NV * W * H, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
                              depth, alpha, stream, &sp);
+}
+
+// ---- half-precision storage: the entries above on (r,g,b,sigma) kept as four fp16 numbers.  degree -1: the RGBA march
+
+static int baked_half_rays(const char *entry, const float *rays, long long R, const uint16_t *vol, int degree, const uint32_t *bits,
+                           int nx, int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate,
+                           float *rgb, float *depth, float *alpha, void *stream, const pnr::SparseArgs *sp) {
+    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA), 0, 1 or 2");
+    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
+    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
+    pnr::RaySrc src = {};
+    src.rays = rays;
+    return pnr::baked_launch(entry, src, R, vol, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream,
+                             sp, true);
+}
+
+static int baked_half_views(const char *entry, const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                            float z_near, float z_far, const uint16_t *vol, int degree, const uint32_t *bits, int nx, int ny, int nz,
+                            const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
+                            float *alpha, void *stream, const pnr::SparseArgs *sp) {
+    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA), 0, 1 or 2");
+    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
+    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
+    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
+    pnr::RaySrc src = {};
+    src.poses = poses;
+    src.W = W; src.H = H;
+    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
+    src.z_near = z_near; src.z_far = z_far;
+    return pnr::baked_launch(entry, src, (long long)NV * W * H, vol, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
+                             depth, alpha, stream, sp, true);
+}
+
+extern "C" int pnr_baked_half_render_rays(const float *rays, long long R, const uint16_t *vol, int degree, const uint32_t *bits, int nx,
+                                          int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd,
+                                          float terminate, float *rgb, float *depth, float *alpha, void *stream) {
+    return baked_half_rays("pnr_baked_half_render_rays", rays, R, vol, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
+                           depth, alpha, stream, nullptr);
+}
+
+extern "C" int pnr_baked_half_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                           float z_near, float z_far, const uint16_t *vol, int degree, const uint32_t *bits, int nx,
+                                           int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd,
+                                           float terminate, float *rgb, float *depth, float *alpha, void *stream) {
+    return baked_half_views("pnr_baked_half_render_views", poses, NV, W, H, fx, fy, cx, cy, z_near, z_far, vol, degree, bits, nx, ny, nz,
+                            c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream, nullptr);
+}
+
+extern "C" int pnr_baked_sparse_half_render_rays(const float *rays, long long R, const uint16_t *rows, long long M, int degree,
+                                                 const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
+                                                 const float *c2, float step, int white_bkgd, float terminate, float *rgb,
+                                                 float *depth, float *alpha, void *stream) {
+    const pnr::SparseArgs sp = {index, M};
+    return baked_half_rays("pnr_baked_sparse_half_render_rays", rays, R, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd,
+                           terminate, rgb, depth, alpha, stream, &sp);
+}
+
+extern "C" int pnr_baked_sparse_half_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                                  float z_near, float z_far, const uint16_t *rows, long long M, int degree,
+                                                  const int32_t *index, const uint32_t *bits, int nx, int ny, int nz,
+                                                  const float *c1, const float *c2, float step, int white_bkgd, float terminate,
+                                                  float *rgb, float *depth, float *alpha, void *stream) {
+    const pnr::SparseArgs sp = {index, M};
+    return baked_half_views("pnr_baked_sparse_half_render_views", poses, NV, W, H, fx, fy, cx, cy, z_near, z_far, rows, degree, bits, nx,
+                            ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream, &sp);
 }

@@ -1575,6 +1575,165 @@ def baked_sparse_render_views(poses, width, height, focal, c, z_near, z_far, row
     return rgb, depth, alpha
 
 
+# ---- half-precision baked volumes: fp16 storage, the fp32 march on the widened values (include/pixelnerf_hip.h, "Half-precision
+# baked volumes").  degree None / -1: the RGBA march; 0, 1, 2: the view-dependent one
+
+def _f16(t, name, shape):
+    """_f32 for a stored fp16 tensor"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
+    if not t.is_cuda:
+        raise _lib.PixelNerfHipError(f"{name}: tensor must live on a HIP device (got {t.device}); pixelnerf_amd has no CPU path")
+    if t.dtype != torch.float16:
+        raise TypeError(f"{name}: expected float16, got {t.dtype}")
+    if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _half_degree(what, degree):
+    degree = -1 if degree is None else int(degree)
+    if degree not in (-1, 0, 1, 2):
+        raise ValueError(f"{what}: degree must be None / -1 (RGBA), 0, 1 or 2, got {degree}")
+    return degree, ((4,) if degree < 0 else ((degree + 1) ** 2, 4))
+
+
+def _baked_half_args(what, vol, degree, reso, c1, c2, step, bits, terminate):
+    """_baked_args / _baked_sh_args for an fp16 volume: vol (nx,ny,nz,4) with degree None / -1, (nx,ny,nz,(degree+1)^2,4) with degree
+    0..2 -> (vol, degree (-1 for RGBA), (nx, ny, nz), step, terminate)"""
+    degree, tail = _half_degree(what, degree)
+    if not isinstance(vol, torch.Tensor) or vol.dim() != 3 + len(tail) or tuple(vol.shape[3:]) != tail:
+        raise ValueError(f"{what}: vol must be (nx,ny,nz,{','.join(str(s) for s in tail)}) at degree {degree}, got "
+                         f"{tuple(vol.shape) if isinstance(vol, torch.Tensor) else type(vol).__name__}")
+    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
+    vol = _f16(vol, "vol", (*dims, *tail))
+    if vol.data_ptr() % 16:
+        raise ValueError(f"{what}: vol must be 16-byte aligned")
+    if bits is not None:
+        _check_grid_args(what, bits, dims, c1, c2, vol.device)
+    return vol, degree, dims, step, terminate
+
+
+def _baked_sparse_half_args(what, rows, degree, index, bits, reso, c1, c2, step, terminate):
+    """_baked_sparse_args for fp16 rows -> (rows, degree (-1 for RGBA), (nx, ny, nz), step, terminate)"""
+    degree, tail = _half_degree(what, degree)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 + len(tail) or tuple(rows.shape[1:]) != tail:
+        raise ValueError(f"{what}: rows must be (M,{','.join(str(s) for s in tail)}) at degree {degree}, got "
+                         f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
+    if bits is None or index is None:
+        raise ValueError(f"{what}: index and bits are mandatory (a sparse volume has nothing to march unskipped)")
+    rows = _f16(rows, "rows", (None, *tail))
+    if rows.numel() and rows.data_ptr() % 16:
+        raise ValueError(f"{what}: rows must be 16-byte aligned")
+    _check_grid_args(what, bits, dims, c1, c2, rows.device)
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims or index.device != rows.device:
+        raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {rows.device}")
+    return rows, degree, dims, step, terminate
+
+
+def _march_outputs(R, dev):
+    return (torch.empty((R, 3), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.float32, device=dev),
+            torch.empty((R,), dtype=torch.float32, device=dev))
+
+
+def _camera_args(what, poses, width, height, focal, c, stored):
+    """the camera of a *_views entry -> (poses, NV, W, H, fx, fy, cx, cy); `stored` is the volume tensor the poses must live with"""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"{what}: the image must have at least one pixel, got {W} x {H}")
+    poses = _f32(poses, "poses", (None, 4, 4))
+    if stored.device != poses.device:
+        raise ValueError(f"{what}: the volume lives on {stored.device}, the poses on {poses.device}")
+    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+    return poses, poses.shape[0], W, H, fx, fy, cx, cy
+
+
+def baked_half_render(rays, vol, degree, reso, c1, c2, step, bits=None, white_bkgd=False, terminate=0.0):
+    """baked_render (degree None / -1: vol (nx,ny,nz,4)) or baked_sh_render (degree 0, 1, 2: vol (nx,ny,nz,B,4)) through an fp16 HIP
+    tensor (pnr_baked_half_render_rays): the bytes of that function on vol.float(), every other argument the same.
+    -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
+    lib = _lib.load()
+    vol, degree, (nx, ny, nz), step, terminate = _baked_half_args("baked_half_render", vol, degree, reso, c1, c2, step, bits, terminate)
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    if vol.device != dev:
+        raise ValueError(f"baked_half_render: vol lives on {vol.device}, the rays on {dev}")
+    rgb, depth, alpha = _march_outputs(R, dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_half_render_rays(_p(rays), R, _p(vol), degree, None if bits is None else _p(bits.contiguous()), nx, ny,
+                                                  nz, lo, hi, step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha),
+                                                  _stream()), "pnr_baked_half_render_rays")
+    return rgb, depth, alpha
+
+
+def baked_half_render_views(poses, width, height, focal, c, z_near, z_far, vol, degree, reso, c1, c2, step, bits=None, white_bkgd=False,
+                            terminate=0.0):
+    """baked_render_views / baked_sh_render_views through an fp16 volume (pnr_baked_half_render_views): the same bits as
+    baked_half_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
+    lib = _lib.load()
+    what = "baked_half_render_views"
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError(f"{what}: the image must have at least one pixel, got {int(width)} x {int(height)}")
+    vol, degree, (nx, ny, nz), step, terminate = _baked_half_args(what, vol, degree, reso, c1, c2, step, bits, terminate)
+    poses, NV, W, H, fx, fy, cx, cy = _camera_args(what, poses, width, height, focal, c, vol)
+    dev = poses.device
+    rgb, depth, alpha = _march_outputs(NV * H * W, dev)
+    lo, hi = _float3_pair(c1, c2)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_half_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), _p(vol), degree,
+                                                   None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
+                                                   int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_half_render_views")
+    return rgb, depth, alpha
+
+
+def baked_sparse_half_render(rays, rows, degree, index, bits, reso, c1, c2, step, white_bkgd=False, terminate=0.0):
+    """baked_sparse_render through fp16 rows (pnr_baked_sparse_half_render_rays): rows (M,4) (degree None / -1) or (M,B,4) fp16 HIP
+    tensor; the bytes of baked_sparse_render on rows.float().  -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
+    lib = _lib.load()
+    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_half_args("baked_sparse_half_render", rows, degree, index, bits, reso, c1,
+                                                                          c2, step, terminate)
+    rays = _f32(rays, "rays", (None, 8))
+    R, dev = rays.shape[0], rays.device
+    if rows.device != dev:
+        raise ValueError(f"baked_sparse_half_render: rows live on {rows.device}, the rays on {dev}")
+    rgb, depth, alpha = _march_outputs(R, dev)
+    lo, hi = _float3_pair(c1, c2)
+    M = rows.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_sparse_half_render_rays(_p(rays), R, _p(rows) if M else None, M, degree, _p(index.contiguous()),
+                                                         _p(bits.contiguous()), nx, ny, nz, lo, hi, step, int(bool(white_bkgd)),
+                                                         terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_sparse_half_render_rays")
+    return rgb, depth, alpha
+
+
+def baked_sparse_half_render_views(poses, width, height, focal, c, z_near, z_far, rows, degree, index, bits, reso, c1, c2, step,
+                                   white_bkgd=False, terminate=0.0):
+    """baked_sparse_render_views through fp16 rows (pnr_baked_sparse_half_render_views): the same bits as
+    baked_sparse_half_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
+    lib = _lib.load()
+    what = "baked_sparse_half_render_views"
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError(f"{what}: the image must have at least one pixel, got {int(width)} x {int(height)}")
+    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_half_args(what, rows, degree, index, bits, reso, c1, c2, step, terminate)
+    poses, NV, W, H, fx, fy, cx, cy = _camera_args(what, poses, width, height, focal, c, rows)
+    dev = poses.device
+    rgb, depth, alpha = _march_outputs(NV * H * W, dev)
+    lo, hi = _float3_pair(c1, c2)
+    M = rows.shape[0]
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_baked_sparse_half_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far),
+                                                          _p(rows) if M else None, M, degree, _p(index.contiguous()),
+                                                          _p(bits.contiguous()), nx, ny, nz, lo, hi, step, int(bool(white_bkgd)),
+                                                          terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
+                   "pnr_baked_sparse_half_render_views")
+    return rgb, depth, alpha
+
+
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):
     """philox_noise for a list of GLOBAL ray ids (pnr_philox_noise_ids): ray_ids (R,) int64 HIP tensor -- any order, repeats
     allowed, beyond 2^31 too -- -> the dict philox_noise returns, row r holding what the seeded renderer entries draw for ray

@@ -12,6 +12,8 @@ point (n_dirs network passes to bake, 4 or 9 times the memory) and the march eva
 SparseBakedVolume keeps only the rows of the grid points that the occupied cells of an OccupancyGrid read, renders the bytes of the
 dense march with the same bits (pnr_baked_sparse_render_rays / pnr_baked_sparse_render_views) and is baked without touching the
 other points: less to bake and to store, not a faster march (profiles/baked_notes.md).
+All three store fp32 or fp16 (`half()`, `from_model(dtype=torch.float16)`, `to_half`): fp16 is storage only, the march is fp32 on the
+widened values, and a half volume renders the BYTES of its `float()` (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*).
 
 The grid is the one util.recon.marching_cubes and util.occupancy.OccupancyGrid use (points of ops.gen_grid_points, cells of the TRUE
 spacing (c2 - c1) / (reso - 1)); the skip grid of a volume is an OccupancyGrid of its sigma channel with dilate 0.
@@ -24,9 +26,48 @@ from .dotmap import DotMap
 from .occupancy import OccupancyGrid, _check_geometry
 
 
+HALF_MAX = 65504.0  # the largest finite fp16 number
+
+
+def to_half(t):
+    """How a baked volume is rounded to fp16 storage: t, a floating-point tensor on any device (CPU too), -> torch.float16, every
+    value rounded to nearest even; a finite value beyond +-65504 SATURATES at +-65504, so nothing is ever stored as infinity (a
+    stored infinity would put inf - inf into the trilinear blend), and a `warnings.warn` names how many did.  A NaN or an infinity
+    in `t` raises ValueError.  A value v with |v| <= 65504 moves by at most max(2^-11 |v|, 2^-25).  An fp16 tensor is returned
+    as it is."""
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+        raise TypeError("to_half: expected a floating-point torch.Tensor")
+    t = t.detach()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("to_half: the tensor holds a non-finite value")
+    if t.dtype == torch.float16:
+        return t
+    saturated = int((t.abs() > HALF_MAX).sum())
+    if saturated:
+        warnings.warn(f"to_half: {saturated} value{'s' if saturated != 1 else ''} beyond +-65504 saturated at +-65504")
+    return t.clamp(-HALF_MAX, HALF_MAX).to(torch.float16)
+
+
+def _storage_dtype(what, dtype):
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: dtype must be torch.float32 or torch.float16, got {dtype}")
+    return dtype
+
+
 class _Baked:
     """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2).  A
-    subclass says which entries march its volume (_march_rays, _march_views)."""
+    subclass says which entries march its volume (_march_rays, _march_views) and which tensor it stores (_stored).
+    Storage is fp32 or fp16 (`dtype`); the march is fp32 either way: a half volume renders the BYTES its `float()` renders
+    (include/pixelnerf_hip.h, "Half-precision baked volumes")."""
+
+    @property
+    def dtype(self):
+        return self._stored().dtype
+
+    @property
+    def nbytes(self):
+        """the bytes of the stored values"""
+        return self._stored().numel() * self._stored().element_size()
 
     @property
     def cell_size(self):
@@ -86,15 +127,17 @@ class _Baked:
 
 
 class BakedVolume(_Baked):
-    """vol: (nx,ny,nz,4) fp32 on the device, (r, g, b, sigma) at the points of ops.gen_grid_points(c1, c2, reso) -- the network's
+    """vol: (nx,ny,nz,4) fp32 or fp16 on the device, (r, g, b, sigma) at the points of ops.gen_grid_points(c1, c2, reso) -- the network's
     outputs (rgb after the sigmoid, sigma after the relu); reso, c1, c2: the grid; skip_threshold and occupancy: the
     OccupancyGrid (dilate 0) of vol[..., 3] that `render(skip=True)` marches against -- at threshold 0 the skipped render equals the
-    unskipped one bit for bit, above 0 the image changes where the dropped haze was visible (OccupancyGrid's contract)."""
+    unskipped one bit for bit, above 0 the image changes where the dropped haze was visible (OccupancyGrid's contract).
+    An fp16 volume (`half()`, `from_model(dtype=torch.float16)`, or a caller's fp16 tensor) renders the bytes of its `float()`; its
+    skip grid is built from the widened sigma, so skipping stays exact (a sigma below 2^-25 has rounded to 0)."""
 
     def __init__(self, vol, c1, c2, skip_threshold=0.0, keep_largest=None, min_voxels=None):
         from .. import _lib
-        if not isinstance(vol, torch.Tensor) or vol.dim() != 4 or vol.shape[3] != 4 or vol.dtype != torch.float32:
-            raise ValueError("BakedVolume: vol must be a (nx,ny,nz,4) float32 tensor")
+        if not isinstance(vol, torch.Tensor) or vol.dim() != 4 or vol.shape[3] != 4 or vol.dtype not in (torch.float32, torch.float16):
+            raise ValueError("BakedVolume: vol must be a (nx,ny,nz,4) float32 or float16 tensor")
         reso, c1, c2, _ = _check_geometry(vol.shape[:3], c1, c2, 0)  # (before any device work)
         skip_threshold = float(skip_threshold)
         if skip_threshold != skip_threshold:
@@ -105,17 +148,28 @@ class BakedVolume(_Baked):
         if not bool(torch.isfinite(vol).all()):
             raise ValueError("BakedVolume: the volume holds a non-finite value")
         self.vol, self.reso, self.c1, self.c2, self.skip_threshold = vol, reso, c1, c2, skip_threshold
-        self.occupancy = OccupancyGrid.from_density(vol[..., 3].contiguous(), c1, c2, skip_threshold, dilate=0, keep_largest=keep_largest,
-                                                    min_voxels=min_voxels)
+        self.occupancy = OccupancyGrid.from_density(vol[..., 3].float().contiguous(), c1, c2, skip_threshold, dilate=0,
+                                                    keep_largest=keep_largest, min_voxels=min_voxels)
+
+    def _stored(self):
+        return self.vol
+
+    def half(self):
+        """this volume with `to_half(vol)`; a half volume is returned as it is"""
+        return self if self.vol.dtype == torch.float16 else BakedVolume(to_half(self.vol), self.c1, self.c2, self.skip_threshold)
+
+    def float(self):
+        """this volume widened to fp32 (exact); an fp32 volume is returned as it is"""
+        return self if self.vol.dtype == torch.float32 else BakedVolume(self.vol.float(), self.c1, self.c2, self.skip_threshold)
 
     @classmethod
     def from_tensor(cls, vol, c1, c2, skip_threshold=0.0):
-        """wrap a caller-made volume: vol (nx,ny,nz,4) fp32 HIP tensor spanning [c1, c2]"""
+        """wrap a caller-made volume: vol (nx,ny,nz,4) fp32 or fp16 HIP tensor spanning [c1, c2]"""
         return cls(vol, c1, c2, skip_threshold)
 
     @classmethod
     def from_model(cls, net, c1, c2, reso, coarse=None, viewdirs="origin", eval_batch_size=100000, skip_threshold=0.0,
-                   keep_largest=None, min_voxels=None):
+                   keep_largest=None, min_voxels=None, dtype=torch.float32):
         """Bake ONE encoded object (checked as util.recon.density_grid checks it): every chunk of grid points goes through
         `net(xyz (1,N,3), coarse=, viewdirs=)` under torch.no_grad() in eval mode (the train / eval flag is restored) and all four
         output columns are written into the volume.
@@ -127,9 +181,11 @@ class BakedVolume(_Baked):
         (util.recon.vertex_colors has the reason)
         :param skip_threshold, keep_largest, min_voxels the skip grid: OccupancyGrid.from_density(vol[..., 3], c1, c2,
         skip_threshold, dilate=0, keep_largest=, min_voxels=)
+        :param dtype torch.float32, or torch.float16: the bake is the fp32 one and `to_half` is applied to its result
         A non-finite value in the volume raises ValueError."""
         from .. import ops
         what = "BakedVolume.from_model"
+        _storage_dtype(what, dtype)
         if int(getattr(net, "num_objs", 1) or 1) > 1:
             raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
         reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
@@ -166,14 +222,22 @@ class BakedVolume(_Baked):
         finally:
             if is_train:
                 net.train()
+        if dtype == torch.float16:
+            vol = to_half(vol)
         return cls(vol.view(*reso, 4), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
 
     def _march_rays(self, rays, step, bits, white_bkgd, terminate):
         from .. import ops
+        if self.vol.dtype == torch.float16:
+            return ops.baked_half_render(rays, self.vol, -1, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
+                                         terminate=terminate)
         return ops.baked_render(rays, self.vol, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
 
     def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
         from .. import ops
+        if self.vol.dtype == torch.float16:
+            return ops.baked_half_render_views(poses, W, H, focal, c, z_near, z_far, self.vol, -1, self.reso, self.c1, self.c2, step,
+                                               bits=bits, white_bkgd=white_bkgd, terminate=terminate)
         return ops.baked_render_views(poses, W, H, focal, c, z_near, z_far, self.vol, self.reso, self.c1, self.c2, step, bits=bits,
                                       white_bkgd=white_bkgd, terminate=terminate)
 
@@ -230,20 +294,23 @@ def sh_basis(dirs, degree, dtype=torch.float32):
 
 
 class BakedSHVolume(_Baked):
-    """A baked volume that keeps the dependence on the view direction: coef (nx,ny,nz,B,4) fp32 on the device, B = (degree+1)^2 real
+    """A baked volume that keeps the dependence on the view direction: coef (nx,ny,nz,B,4) fp32 or fp16 on the device, B = (degree+1)^2 real
     spherical-harmonic coefficients (degree 0, 1 or 2) of (r, g, b, sigma) at the points of ops.gen_grid_points(c1, c2, reso).  The
     march evaluates every corner for the RAY's direction, clamps it (rgb to [0,1], sigma to >= 0) and then blends: a ray renders as
     BakedVolume would render the volume "this object seen from direction d" (`at_direction`).  Still trilinear in space, still
-    equidistant samples, still nothing outside the box; degree <= 2, fp32 only.
-    Memory: 16 B bytes per grid point -- 64 / 144 bytes at degree 1 / 2, 302 MB at 128^3 and degree 2 (BakedVolume: 16 bytes, 34 MB).
+    equidistant samples, still nothing outside the box; degree <= 2.  Storage is fp32 or fp16: a half volume renders the bytes of
+    its `float()`, a stored coefficient c being off by at most max(2^-11 |c|, 2^-25).
+    Memory: 16 B bytes per grid point in fp32 -- 64 / 144 bytes at degree 1 / 2, 302 MB at 128^3 and degree 2 (BakedVolume: 16 bytes,
+    34 MB) --, half of that in fp16.
     The skip grid is an OccupancyGrid (dilate 0) of an upper bound of sigma over all directions, s_0 + (1 + 2^-16) sum_k m_k |s_k|
     with m_k = max |Y_k|: at skip_threshold 0 a skipped cell has sigma exactly 0 at its eight corners for every direction, so
     `render(skip=True)` equals `render(skip=False)` bit for bit."""
 
     def __init__(self, coef, c1, c2, skip_threshold=0.0, keep_largest=None, min_voxels=None):
         from .. import _lib
-        if not isinstance(coef, torch.Tensor) or coef.dim() != 5 or coef.shape[4] != 4 or coef.dtype != torch.float32:
-            raise ValueError("BakedSHVolume: coef must be a (nx,ny,nz,B,4) float32 tensor")
+        if not isinstance(coef, torch.Tensor) or coef.dim() != 5 or coef.shape[4] != 4 \
+                or coef.dtype not in (torch.float32, torch.float16):
+            raise ValueError("BakedSHVolume: coef must be a (nx,ny,nz,B,4) float32 or float16 tensor")
         degree = _degree_of(coef.shape[3], "BakedSHVolume")
         reso, c1, c2, _ = _check_geometry(coef.shape[:3], c1, c2, 0)  # (before any device work)
         skip_threshold = float(skip_threshold)
@@ -258,10 +325,22 @@ class BakedSHVolume(_Baked):
         self.occupancy = OccupancyGrid.from_density(self.sigma_bound(), c1, c2, skip_threshold, dilate=0, keep_largest=keep_largest,
                                                     min_voxels=min_voxels)
 
+    def _stored(self):
+        return self.coef
+
+    def half(self):
+        """this volume with `to_half(coef)`; a half volume is returned as it is"""
+        return self if self.coef.dtype == torch.float16 else BakedSHVolume(to_half(self.coef), self.c1, self.c2, self.skip_threshold)
+
+    def float(self):
+        """this volume widened to fp32 (exact); an fp32 volume is returned as it is"""
+        return self if self.coef.dtype == torch.float32 else BakedSHVolume(self.coef.float(), self.c1, self.c2, self.skip_threshold)
+
     def sigma_bound(self):
-        """(nx,ny,nz) fp32: s_0 + (1 + 2^-16) sum_{k>=1} m_k |s_k|, in fp64 from the fp32 coefficients and rounded UP to fp32 -- no
-        direction gives the kernel a larger sigma at the point (the slack covers the fp32 rounding of Y and of the sum)"""
-        s = self.coef[..., 3].double()
+        """(nx,ny,nz) fp32: s_0 + (1 + 2^-16) sum_{k>=1} m_k |s_k|, in fp64 from the stored coefficients (fp16 ones widened: the
+        values the kernel sees) and rounded UP to fp32 -- no direction gives the kernel a larger sigma at the point (the slack covers
+        the fp32 rounding of Y and of the sum)"""
+        s = self.coef[..., 3].float().double()
         bound = s[..., 0]
         if s.shape[-1] > 1:
             m = torch.tensor(_SH_MAX[:s.shape[-1] - 1], dtype=torch.float64, device=s.device)
@@ -298,12 +377,12 @@ class BakedSHVolume(_Baked):
 
     @classmethod
     def from_tensor(cls, coef, c1, c2, skip_threshold=0.0):
-        """wrap a caller-made volume: coef (nx,ny,nz,B,4) fp32 HIP tensor spanning [c1, c2], B in {1, 4, 9}"""
+        """wrap a caller-made volume: coef (nx,ny,nz,B,4) fp32 or fp16 HIP tensor spanning [c1, c2], B in {1, 4, 9}"""
         return cls(coef, c1, c2, skip_threshold)
 
     @classmethod
     def from_model(cls, net, c1, c2, reso, degree=2, n_dirs=32, coarse=None, eval_batch_size=100000, skip_threshold=0.0,
-                   keep_largest=None, min_voxels=None):
+                   keep_largest=None, min_voxels=None, dtype=torch.float32):
         """Bake ONE encoded object with its dependence on the view direction: the network is evaluated on every grid point once per
         direction u_m of `directions(n_dirs)` and all four output columns are projected, in linear space (the clamps happen at render
         time), onto the basis: coef[:, k, :] = sum_m P[k, m] net(points, viewdirs = u_m)[:, :4] with P = fp32(projection(n_dirs,
@@ -311,9 +390,11 @@ class BakedSHVolume(_Baked):
         an even number, as BakedVolume.from_model) and is the same from run to run.  n_dirs network passes: n_dirs times
         BakedVolume.from_model's time.  The checks, the eval / train flag and `coarse` are BakedVolume.from_model's.
         A network that takes no view directions is baked at degree 0, whatever was asked, with a warning.
-        Memory: 64 / 144 bytes per point at degree 1 / 2 (302 MB at 128^3, degree 2)."""
+        Memory: 64 / 144 bytes per point at degree 1 / 2 (302 MB at 128^3, degree 2); half of it with dtype=torch.float16, which
+        bakes and accumulates in fp32 exactly as above and then applies `to_half` (the fp32 tensor exists during the bake)."""
         from .. import ops
         what = "BakedSHVolume.from_model"
+        _storage_dtype(what, dtype)
         if int(getattr(net, "num_objs", 1) or 1) > 1:
             raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
         reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
@@ -350,12 +431,17 @@ class BakedSHVolume(_Baked):
         finally:
             if is_train:
                 net.train()
+        if dtype == torch.float16:
+            coef = to_half(coef)
         return cls(coef.view(*reso, nb, 4), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
 
     def at_direction(self, d):
         """The RGBA volume "this object seen from direction d" (a 3-vector of any length): per grid point coef_0 Y_0 + coef_1 Y_1
         + ... in this order in fp32, then rgb clamped to [0,1] and sigma to >= 0 -- the kernel's corner value.  What one bakes for a
-        fixed camera side; a ray of direction d renders through it as it does through this volume."""
+        fixed camera side; a ray of direction d renders through it as it does through this volume.  A half volume gives the fp32
+        BakedVolume of `float().at_direction(d)`."""
+        if self.coef.dtype == torch.float16:
+            return self.float().at_direction(d)
         d = torch.as_tensor(d, dtype=torch.float32).flatten()
         if d.numel() != 3:
             raise ValueError("BakedSHVolume.at_direction: d must be a 3-vector")
@@ -371,11 +457,17 @@ class BakedSHVolume(_Baked):
 
     def _march_rays(self, rays, step, bits, white_bkgd, terminate):
         from .. import ops
+        if self.coef.dtype == torch.float16:
+            return ops.baked_half_render(rays, self.coef, self.degree, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
+                                         terminate=terminate)
         return ops.baked_sh_render(rays, self.coef, self.degree, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
                                    terminate=terminate)
 
     def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
         from .. import ops
+        if self.coef.dtype == torch.float16:
+            return ops.baked_half_render_views(poses, W, H, focal, c, z_near, z_far, self.coef, self.degree, self.reso, self.c1, self.c2,
+                                               step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
         return ops.baked_sh_render_views(poses, W, H, focal, c, z_near, z_far, self.coef, self.degree, self.reso, self.c1, self.c2, step,
                                          bits=bits, white_bkgd=white_bkgd, terminate=terminate)
 
@@ -418,8 +510,8 @@ def _sparse_of(dense, per_point, occupancy, what):
 
 
 class SparseBakedVolume(_Baked):
-    """A baked volume that keeps only what its occupancy grid lets the march read.  rows: (M,4) fp32 (degree None: the RGBA march) or
-    (M,B,4) (degree 0, 1, 2: the view-dependent march) on the device, the rows of the dense volume at the kept points; ids (M,)
+    """A baked volume that keeps only what its occupancy grid lets the march read.  rows: (M,4) (degree None: the RGBA march) or
+    (M,B,4) (degree 0, 1, 2: the view-dependent march), fp32 or fp16, on the device, the rows of the dense volume at the kept points; ids (M,)
     int32: their linear ids (i ny + j) nz + k, ascending; index (nx,ny,nz) int32: the rank of a kept point, -1 elsewhere; occupancy:
     the OccupancyGrid whose cells decide (reso, c1, c2 are its geometry).  Kept: the corners of the occupied cells, closed over the
     pairs (2j, 2j+1) of the linear ids (include/pixelnerf_hip.h, "baked volumes", the sparse paragraph).
@@ -428,8 +520,9 @@ class SparseBakedVolume(_Baked):
 
     def __init__(self, rows, occupancy, index=None, ids=None):
         from .. import _lib, ops
-        if not isinstance(rows, torch.Tensor) or rows.dim() not in (2, 3) or rows.shape[-1] != 4 or rows.dtype != torch.float32:
-            raise ValueError("SparseBakedVolume: rows must be a (M,4) or (M,B,4) float32 tensor")
+        if not isinstance(rows, torch.Tensor) or rows.dim() not in (2, 3) or rows.shape[-1] != 4 \
+                or rows.dtype not in (torch.float32, torch.float16):
+            raise ValueError("SparseBakedVolume: rows must be a (M,4) or (M,B,4) float32 or float16 tensor")
         degree = _degree_of(rows.shape[1], "SparseBakedVolume") if rows.dim() == 3 else None
         if not isinstance(occupancy, OccupancyGrid):
             raise ValueError(f"SparseBakedVolume: occupancy must be an OccupancyGrid, got {type(occupancy).__name__}")
@@ -451,12 +544,28 @@ class SparseBakedVolume(_Baked):
     def n_rows(self):
         return self.rows.shape[0]
 
+    def _stored(self):
+        return self.rows
+
     @property
     def nbytes(self):
-        return 4 * (self.rows.numel() + self.index.numel() + self.occupancy.bits.numel())
+        return self.rows.numel() * self.rows.element_size() + 4 * (self.index.numel() + self.occupancy.bits.numel())
+
+    def half(self):
+        """this volume with `to_half(rows)`; index, ids and occupancy are shared.  A half volume is returned as it is"""
+        if self.rows.dtype == torch.float16:
+            return self
+        return SparseBakedVolume(to_half(self.rows), self.occupancy, index=self.index, ids=self.ids)
+
+    def float(self):
+        """this volume with the rows widened to fp32 (exact); index, ids and occupancy are shared.  An fp32 volume is returned as it is"""
+        if self.rows.dtype == torch.float32:
+            return self
+        return SparseBakedVolume(self.rows.float(), self.occupancy, index=self.index, ids=self.ids)
 
     @classmethod
-    def from_model(cls, net, c1, c2, reso, occupancy, degree=None, n_dirs=32, viewdirs="origin", coarse=None, eval_batch_size=100000):
+    def from_model(cls, net, c1, c2, reso, occupancy, degree=None, n_dirs=32, viewdirs="origin", coarse=None, eval_batch_size=100000,
+                   dtype=torch.float32):
         """The sparse bake: BakedVolume.from_model's loop (degree None; `viewdirs` as there) or BakedSHVolume.from_model's (degree
         0, 1, 2 with `n_dirs` directions; `viewdirs` is not used) -- the same checks, the same fixed projection order, even chunks, the
         train / eval flag restored -- over the kept points of `occupancy` in ascending order (ops.gen_grid_points_at supplies them): the
@@ -464,9 +573,11 @@ class SparseBakedVolume(_Baked):
         `rows` equals the dense from_model tensor at `ids` bit for bit, at every precision and whatever eval_batch_size: the kept set is
         closed over the pairs (2j, 2j+1) of the dense launch and a chunk has an even length, so every kept point stands at a place of
         its own parity (profiles/occupancy_notes.md).  With occupancy = OccupancyGrid.from_model(net, c1, c2, reso, threshold,
-        dilate=1) the result is the dense bake with nothing in the cells the grid calls empty.  A non-finite output raises ValueError."""
+        dilate=1) the result is the dense bake with nothing in the cells the grid calls empty.  A non-finite output raises ValueError.
+        dtype=torch.float16: the fp32 bake, then `to_half` on the rows."""
         from .. import ops
         what = "SparseBakedVolume.from_model"
+        _storage_dtype(what, dtype)
         if int(getattr(net, "num_objs", 1) or 1) > 1:
             raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
         reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
@@ -530,6 +641,8 @@ class SparseBakedVolume(_Baked):
         finally:
             if is_train:
                 net.train()
+        if dtype == torch.float16:
+            rows = to_half(rows)
         return cls(rows, occupancy, index=index, ids=ids)
 
     def _march_args(self, step, terminate, skip):
@@ -539,19 +652,25 @@ class SparseBakedVolume(_Baked):
 
     def _march_rays(self, rays, step, bits, white_bkgd, terminate):
         from .. import ops
+        if self.rows.dtype == torch.float16:
+            return ops.baked_sparse_half_render(rays, self.rows, self.degree, self.index, bits, self.reso, self.c1, self.c2, step,
+                                                white_bkgd=white_bkgd, terminate=terminate)
         return ops.baked_sparse_render(rays, self.rows, self.degree, self.index, bits, self.reso, self.c1, self.c2, step,
                                        white_bkgd=white_bkgd, terminate=terminate)
 
     def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
         from .. import ops
+        if self.rows.dtype == torch.float16:
+            return ops.baked_sparse_half_render_views(poses, W, H, focal, c, z_near, z_far, self.rows, self.degree, self.index, bits,
+                                                      self.reso, self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
         return ops.baked_sparse_render_views(poses, W, H, focal, c, z_near, z_far, self.rows, self.degree, self.index, bits, self.reso,
                                              self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
 
     def to_dense(self):
         """(nx,ny,nz,4) or (nx,ny,nz,B,4): the rows at their grid points, zeros at the dropped ones -- marched with `occupancy.bits` it
-        renders the bytes of this volume"""
+        renders the bytes of this volume; the dtype is the rows'"""
         total = self.reso[0] * self.reso[1] * self.reso[2]
-        dense = torch.zeros((total, *self.rows.shape[1:]), dtype=torch.float32, device=self.rows.device)
+        dense = torch.zeros((total, *self.rows.shape[1:]), dtype=self.rows.dtype, device=self.rows.device)
         dense.index_copy_(0, self.ids.long(), self.rows)
         return dense.view(*self.reso, *self.rows.shape[1:])
 
