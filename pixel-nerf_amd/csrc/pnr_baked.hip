@@ -6,16 +6,21 @@
 // Semantics: include/pixelnerf_hip.h ("baked volumes").  One wavefront per ray, composite_kernel's scan; no atomics, no LDS, no
 // workspace: the same bytes on every call.
 // The view-dependent form (pnr_baked_sh_render_*) keeps B = (L+1)^2 float4s of real spherical-harmonic coefficients per grid point
-// and evaluates them for each ray's own direction; the march is the same function (baked_march), instantiated on what a corner is.
-// The sparse form (pnr_baked_sparse_render_*) keeps only the rows of the grid points that occupied cells read (the kept set of
-// pnr_sparse_points_mark) and an int32 index over the grid; baked_march is instantiated a second time on WHERE a pair of corners
-// lies: at rows p, p + 1 of the dense array, or at rows index[p], index[p] + 1 of the kept ones.
-// The half forms (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*) instantiate it a third time, on WHAT A STORED NUMBER IS:
-// a float4, or four fp16 numbers widened exactly to fp32 on load; everything after the load is the same code.
+// and evaluates them for each ray's own direction; the sparse form (pnr_baked_sparse_render_*) keeps only the rows of the grid
+// points that occupied cells read (the kept set of pnr_sparse_points_mark) and an int32 index over the grid; the half forms
+// (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*) store four fp16 numbers where the others store a float4.
+// Structure.  Device: ONE march (baked_march) and ONE kernel template (baked_march_kernel<Corner, Rows>) around it.  Corner says
+// what the march reads at a corner of a cell (RgbaCornerOf / ShCorner<B>) and what a stored number is (float4 or Half4, widened
+// exactly on load: everything after the load is the same code); Rows says where a pair of corners lies (DenseRows: rows p, p + 1
+// of the dense array; SparseRows: rows index[p], index[p] + 1 of the kept ones).  4 kinds x 2 storages x 2 layouts = 16 kernels.
+// Host: an entry builds its ray source (baked_explicit_rays / baked_camera_rays: the checks of the rays travel with them), says
+// what it was handed (BakedVolumeDesc: pointer, degree, storage, index + M, and the words of its refusals) and calls
+// baked_render, which holds every check, in one order for all ten entries, and dispatches layout, storage and kind once each.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 
 #include "pnr_common.h"
 #include "pnr_occgrid.h"
@@ -54,24 +59,26 @@ struct alignas(8) Half4 {
 __device__ __forceinline__ float4 baked_widen(const float4 v) { return v; }
 __device__ __forceinline__ float4 baked_widen(const Half4 v) { return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w); }
 
-// What the march reads at a corner of a cell.  RGBA volume: the float4 of the grid point.
+// What the march reads at a corner of a cell; `data` is the stored array the entry was handed (the kernel sets it).  RGBA volume:
+// the (r,g,b,sigma) of the grid point.
 template <class Stored>
 struct RgbaCornerOf {
-    const Stored *vol;  // (nx,ny,nz) x (r,g,b,sigma)
+    using stored_t = Stored;
+    const Stored *data;  // (nx,ny,nz) x (r,g,b,sigma)
     __device__ __forceinline__ void set_ray(const Ray8 &) {}
     static constexpr int PAIRS_IN_FLIGHT = 4;  // 8 loads: all in flight at once
-    __device__ __forceinline__ float4 at(long long point) const { return baked_widen(vol[point]); }
+    __device__ __forceinline__ float4 at(long long point) const { return baked_widen(data[point]); }
 };
-using RgbaCorner = RgbaCornerOf<float4>;
 
 // fp32(sqrt 3), fp32(sqrt 15), fp32(sqrt 5 / 2), fp32(sqrt 15 / 2): rounded once from the fp64 values
 constexpr float SH_C1 = 1.7320508075688772f, SH_C2 = 3.872983346207417f, SH_C20 = 1.118033988749895f, SH_C22 = 1.9364916731037085f;
 
 // SH volume: the B contiguous float4s of the grid point, reduced with the ray's basis values to one float4 and clamped.  y[k - 1]
 // holds Y_k of the header for k >= 1 (Y_0 = 1 is not stored: c * 1 is c); a per-ray constant.
-template <int B, class Stored = float4>
+template <int B, class Stored>
 struct ShCorner {
-    const Stored *coef;  // (nx,ny,nz,B) x (r,g,b,sigma)
+    using stored_t = Stored;
+    const Stored *data;  // (nx,ny,nz,B) x (r,g,b,sigma)
     float y[B > 1 ? B - 1 : 1];
     __device__ __forceinline__ void set_ray(const Ray8 &ray) {
         const float n2 = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
@@ -89,7 +96,7 @@ struct ShCorner {
     // no gain from more pairs in flight (profiles/baked_notes.md); the outputs do not depend on the choice.
     static constexpr int PAIRS_IN_FLIGHT = B == 1 ? 4 : B == 4 ? 2 : 1;
     __device__ __forceinline__ float4 at(long long point) const {
-        const Stored *c = coef + point * B;
+        const Stored *c = data + point * B;
         float4 v = baked_widen(c[0]);
 #pragma unroll
         for (int k = 1; k < B; ++k) {
@@ -247,140 +254,141 @@ __device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const
     }
 }
 
+// THE kernel of every entry.  `stored` is the dense volume or the kept rows, (M,4) / (M,B,4); the Corner is built here, and
+// ShCorner::y stays what it is: per-ray state that set_ray fills, not an argument.
+template <class Corner, class Rows>
 __global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, const float4 *__restrict__ vol, float *__restrict__ rgb,
-                   float *__restrict__ depth, float *__restrict__ alpha_out) {
-    baked_march(rs, R, q, RgbaCorner{vol}, DenseRows{}, rgb, depth, alpha_out);
-}
-
-template <int B>
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const float4 *__restrict__ coef, float *__restrict__ rgb,
-                      float *__restrict__ depth, float *__restrict__ alpha_out) {
-    ShCorner<B> corner;
-    corner.coef = coef;
-    baked_march(rs, R, q, corner, DenseRows{}, rgb, depth, alpha_out);
-}
-
-// the sparse forms: `vol` / `coef` are the kept rows, (M,4) / (M,B,4)
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_sparse_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows, const float4 *__restrict__ vol,
-                          float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
-    baked_march(rs, R, q, RgbaCorner{vol}, rows, rgb, depth, alpha_out);
-}
-
-template <int B>
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_sparse_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows, const float4 *__restrict__ coef,
-                             float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
-    ShCorner<B> corner;
-    corner.coef = coef;
-    baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
-}
-
-// the half forms (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*): the four marches above on fp16 storage
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_half_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Half4 *__restrict__ vol, float *__restrict__ rgb,
-                        float *__restrict__ depth, float *__restrict__ alpha_out) {
-    baked_march(rs, R, q, RgbaCornerOf<Half4>{vol}, DenseRows{}, rgb, depth, alpha_out);
-}
-
-template <int B>
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_half_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Half4 *__restrict__ coef, float *__restrict__ rgb,
-                           float *__restrict__ depth, float *__restrict__ alpha_out) {
-    ShCorner<B, Half4> corner;
-    corner.coef = coef;
-    baked_march(rs, R, q, corner, DenseRows{}, rgb, depth, alpha_out);
-}
-
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_sparse_half_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows, const Half4 *__restrict__ vol,
-                               float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
-    baked_march(rs, R, q, RgbaCornerOf<Half4>{vol}, rows, rgb, depth, alpha_out);
-}
-
-template <int B>
-__global__ void __launch_bounds__(BAKED_WAVES * 64)
-baked_sparse_half_sh_march_kernel(const RaySrc rs, long long R, const BakedParams q, const SparseRows rows,
-                                  const Half4 *__restrict__ coef, float *__restrict__ rgb, float *__restrict__ depth,
-                                  float *__restrict__ alpha_out) {
-    ShCorner<B, Half4> corner;
-    corner.coef = coef;
+baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Rows rows, const typename Corner::stored_t *__restrict__ stored,
+                   float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
+    Corner corner;
+    corner.data = stored;
     baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
 }
 #pragma clang fp contract(fast)
 
 static bool baked_misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
 
-// the kept rows of a sparse volume: what the sparse entries pass to baked_launch in addition
-struct SparseArgs {
-    const int32_t *index;
-    long long M;
+// ---- host only from here.  The rays of a march with their own checks, made where the entry's arguments are (pnr_entry.h's
+// explicit_rays for the baked entries).  defect: what is wrong with them (NULL: nothing); baked_render reports it after the
+// entry's degree check, which every entry makes first.
+struct BakedRays {
+    RaySrc src;
+    long long R;
+    const char *defect;
 };
 
-// the checks all entries share, then the launch; src holds the rays or the camera, already checked.  degree < 0: vol is an RGBA
-// volume; 0..2: the coefficient volume of that degree.  sp != NULL: vol holds the M kept rows, found through sp->index.  half: vol
-// holds fp16 numbers (the half entries), else fp32
-static int baked_launch(const char *entry, const RaySrc &src, long long R, const void *vol, int degree, const uint32_t *bits, int nx,
-                        int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
-                        float *depth, float *alpha, void *stream, const SparseArgs *sp = nullptr, bool half = false) {
-    if (degree > 2) return occ_fail(entry, "degree must be 0, 1 or 2");
-    if (sp && degree < -1) return occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
-    if (sp && sp->M < 0) return occ_fail(entry, "bad sizes (M)");
-    if (const char *why = occ_bad_dims(nx, ny, nz)) return occ_fail(entry, why);
+static BakedRays baked_explicit_rays(const float *rays, long long R) {
+    BakedRays s = {};
+    s.src.rays = rays;
+    s.R = R;
+    s.defect = R < 0 ? "bad sizes (R)" : R > 0 && !rays ? "null argument"
+               : baked_misaligned4(rays) ? "rays must be 4-byte aligned" : nullptr;
+    return s;
+}
+
+static BakedRays baked_camera_rays(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
+                                   float z_far) {
+    BakedRays s = {};
+    s.src.poses = poses;
+    s.src.W = W; s.src.H = H;
+    s.src.fx = fx; s.src.fy = fy; s.src.cx = cx; s.src.cy = cy;
+    s.src.z_near = z_near; s.src.z_far = z_far;
+    s.R = (long long)NV * W * H;
+    s.defect = NV < 0 || W <= 0 || H <= 0 ? "bad sizes (NV, W, H)" : NV > 0 && !poses ? "null argument"
+               : baked_misaligned4(poses) ? "poses must be 4-byte aligned" : nullptr;
+    return s;
+}
+
+// What an entry was handed to march through, and the words of its refusals.
+struct BakedVolumeDesc {
+    const void *stored;       // dense: (nx,ny,nz) x B x (r,g,b,sigma); sparse: the M kept rows of that array
+    int degree;               // -1: an RGBA volume (B = 1, no basis); 0..2: the coefficient volume of that degree, B = (degree+1)^2
+    bool half;                // an (r,g,b,sigma) is four fp16 numbers (Half4), else a float4
+    bool sparse;              // `stored` holds kept rows, found through index; bits are then mandatory
+    const int32_t *index;     // sparse: (nx,ny,nz), the rank of a kept point, -1 elsewhere
+    long long M;              // sparse: the number of kept rows
+    const char *name;         // what the header calls `stored`: "vol", "coef" or "rows"
+    int min_degree;           // the entry's degree argument lies in [min_degree, 2] ...
+    const char *degree_rule;  // ... or the entry refuses with these words (the RGBA entries take no degree: never said)
+};
+constexpr const char *DEGREE_SH = "degree must be 0, 1 or 2", *DEGREE_SPARSE = "degree must be -1 (RGBA rows), 0, 1 or 2",
+                     *DEGREE_HALF = "degree must be -1 (RGBA), 0, 1 or 2";
+
+static BakedVolumeDesc baked_dense(const void *stored, int degree, bool half, const char *name, int min_degree, const char *degree_rule) {
+    return {stored, degree, half, false, nullptr, 0, name, min_degree, degree_rule};
+}
+static BakedVolumeDesc baked_sparse(const void *rows, long long M, const int32_t *index, int degree, bool half, const char *degree_rule) {
+    return {rows, degree, half, true, index, M, "rows", -1, degree_rule};
+}
+
+// the grid, the march settings, the outputs and the stream: the tail of every entry's argument list, in its order
+struct BakedMarchArgs {
+    const uint32_t *bits;
+    int nx, ny, nz;
+    const float *c1, *c2;
+    float step;
+    int white_bkgd;
+    float terminate;
+    float *rgb, *depth, *alpha;
+    void *stream;
+};
+
+template <class T>
+struct BakedType {
+    using type = T;
+};
+
+// every check of every entry, in one order, then the launch
+static int baked_render(const char *entry, const BakedRays &rays, const BakedVolumeDesc &v, const BakedMarchArgs &a) {
+    if (v.degree < v.min_degree || v.degree > 2) return occ_fail(entry, v.degree_rule);
+    if (rays.defect) return occ_fail(entry, rays.defect);
+    if (v.sparse && v.M < 0) return occ_fail(entry, "bad sizes (M)");
+    if (const char *why = occ_bad_dims(a.nx, a.ny, a.nz)) return occ_fail(entry, why);
     BakedParams q;
-    if (const char *why = occ_grid(nx, ny, nz, c1, c2, q.g)) return occ_fail(entry, why);
-    if (!(step > 0.f) || !std::isfinite(step)) return occ_fail(entry, "step must be finite and > 0");
-    if (!(terminate >= 0.f && terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
+    if (const char *why = occ_grid(a.nx, a.ny, a.nz, a.c1, a.c2, q.g)) return occ_fail(entry, why);
+    if (!(a.step > 0.f) || !std::isfinite(a.step)) return occ_fail(entry, "step must be finite and > 0");
+    if (!(a.terminate >= 0.f && a.terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
+    const long long R = rays.R;
     if (R == 0) return PNR_OK;
-    if (!rgb || !depth || !alpha) return occ_fail(entry, "null argument");
-    if (sp ? sp->M > 0 && (!vol || !sp->index || !bits) : !vol) return occ_fail(entry, "null argument");
-    if (occ_misaligned16(vol))
-        return occ_fail(entry, sp ? "rows must be 16-byte aligned" : degree < 0 || half ? "vol must be 16-byte aligned" : "coef must be 16-byte aligned");
-    if (sp && baked_misaligned4(sp->index)) return occ_fail(entry, "index must be 4-byte aligned");
-    if (baked_misaligned4(bits) || baked_misaligned4(rgb) || baked_misaligned4(depth) || baked_misaligned4(alpha))
+    if (!a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
+    if (v.sparse ? v.M > 0 && (!v.stored || !v.index || !a.bits) : !v.stored) return occ_fail(entry, "null argument");
+    if (occ_misaligned16(v.stored)) {
+        char why[40];
+        std::snprintf(why, sizeof(why), "%s must be 16-byte aligned", v.name);
+        return occ_fail(entry, why);
+    }
+    if (v.sparse && baked_misaligned4(v.index)) return occ_fail(entry, "index must be 4-byte aligned");
+    if (baked_misaligned4(a.bits) || baked_misaligned4(a.rgb) || baked_misaligned4(a.depth) || baked_misaligned4(a.alpha))
         return occ_fail(entry, "bits, rgb, depth and alpha must be 4-byte aligned");
     const long long blocks = (R + BAKED_WAVES - 1) / BAKED_WAVES;
     if (blocks > 0x7fffffffLL) return occ_fail(entry, "the number of rays exceeds the launch limit");
-    q.bits = bits;
-    q.step = step;
-    q.eps = terminate;
-    q.white_bkgd = white_bkgd;
-    const float4 *v4 = reinterpret_cast<const float4 *>(vol);
-    const Half4 *h4 = reinterpret_cast<const Half4 *>(vol);
-    const dim3 grid((unsigned)blocks), block(BAKED_WAVES * 64);
-    hipStream_t st = (hipStream_t)stream;
-    if (sp) {
-        // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
-        const SparseRows rows = {sp->index, (int)(sp->M - 2 < 0x7ffffffeLL ? sp->M - 2 : 0x7ffffffeLL)};
-        if (half) {
-            if (degree < 0) hipLaunchKernelGGL(baked_sparse_half_march_kernel, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
-            else if (degree == 0) hipLaunchKernelGGL(baked_sparse_half_sh_march_kernel<1>, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
-            else if (degree == 1) hipLaunchKernelGGL(baked_sparse_half_sh_march_kernel<4>, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
-            else hipLaunchKernelGGL(baked_sparse_half_sh_march_kernel<9>, grid, block, 0, st, src, R, q, rows, h4, rgb, depth, alpha);
-            return pnr_check_launch(entry);
-        }
-        if (degree < 0) hipLaunchKernelGGL(baked_sparse_march_kernel, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
-        else if (degree == 0) hipLaunchKernelGGL(baked_sparse_sh_march_kernel<1>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
-        else if (degree == 1) hipLaunchKernelGGL(baked_sparse_sh_march_kernel<4>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
-        else hipLaunchKernelGGL(baked_sparse_sh_march_kernel<9>, grid, block, 0, st, src, R, q, rows, v4, rgb, depth, alpha);
-        return pnr_check_launch(entry);
-    }
-    if (half) {
-        if (degree < 0) hipLaunchKernelGGL(baked_half_march_kernel, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
-        else if (degree == 0) hipLaunchKernelGGL(baked_half_sh_march_kernel<1>, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
-        else if (degree == 1) hipLaunchKernelGGL(baked_half_sh_march_kernel<4>, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
-        else hipLaunchKernelGGL(baked_half_sh_march_kernel<9>, grid, block, 0, st, src, R, q, h4, rgb, depth, alpha);
-        return pnr_check_launch(entry);
-    }
-    if (degree < 0) hipLaunchKernelGGL(baked_march_kernel, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
-    else if (degree == 0) hipLaunchKernelGGL(baked_sh_march_kernel<1>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
-    else if (degree == 1) hipLaunchKernelGGL(baked_sh_march_kernel<4>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
-    else hipLaunchKernelGGL(baked_sh_march_kernel<9>, grid, block, 0, st, src, R, q, v4, rgb, depth, alpha);
+    q.bits = a.bits;
+    q.step = a.step;
+    q.eps = a.terminate;
+    q.white_bkgd = a.white_bkgd;
+    // layout, storage and kind, each decided once: 2 x 2 x 4 instantiations of the one kernel
+    const auto launch = [&](auto corner, auto rows) {
+        using Corner = typename decltype(corner)::type;
+        hipLaunchKernelGGL((baked_march_kernel<Corner, decltype(rows)>), dim3((unsigned)blocks), dim3(BAKED_WAVES * 64), 0,
+                           (hipStream_t)a.stream, rays.src, R, q, rows, static_cast<const typename Corner::stored_t *>(v.stored), a.rgb,
+                           a.depth, a.alpha);
+    };
+    const auto by_kind = [&](auto stored, auto rows) {
+        using Stored = typename decltype(stored)::type;
+        if (v.degree < 0) launch(BakedType<RgbaCornerOf<Stored>>{}, rows);
+        else if (v.degree == 0) launch(BakedType<ShCorner<1, Stored>>{}, rows);
+        else if (v.degree == 1) launch(BakedType<ShCorner<4, Stored>>{}, rows);
+        else launch(BakedType<ShCorner<9, Stored>>{}, rows);
+    };
+    const auto by_storage = [&](auto rows) {
+        if (v.half) by_kind(BakedType<Half4>{}, rows);
+        else by_kind(BakedType<float4>{}, rows);
+    };
+    // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
+    if (v.sparse) by_storage(SparseRows{v.index, (int)(v.M - 2 < 0x7ffffffeLL ? v.M - 2 : 0x7ffffffeLL)});
+    else by_storage(DenseRows{});
     return pnr_check_launch(entry);
 }
-
 // keep[p] for the pair (2 j, 2 j + 1) of grid points: a point is a corner of the cells (i - a, j - b, k - c), a, b, c in {0, 1},
 // that exist; the pair is kept whole when either point is a corner of an occupied one
 constexpr int SPARSE_MARK_THREADS = 256;
@@ -411,65 +419,40 @@ sparse_points_mark_kernel(const uint32_t *__restrict__ bits, int nx, int ny, int
 
 }  // namespace pnr
 
+// Every entry: its ray source, what it was handed, the tail of its argument list.
+
 extern "C" int pnr_baked_render_rays(const float *rays, long long R, const float *vol, const uint32_t *bits, int nx, int ny, int nz,
                                      const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
                                      float *depth, float *alpha, void *stream) {
-    const char *entry = "pnr_baked_render_rays";
-    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
-    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.rays = rays;
-    return pnr::baked_launch(entry, src, R, vol, -1, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream);
+    return pnr::baked_render("pnr_baked_render_rays", pnr::baked_explicit_rays(rays, R),
+                             pnr::baked_dense(vol, -1, false, "vol", -1, nullptr),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
                                       float z_far, const float *vol, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
                                       const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
                                       float *alpha, void *stream) {
-    const char *entry = "pnr_baked_render_views";
-    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
-    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.poses = poses;
-    src.W = W; src.H = H;
-    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
-    src.z_near = z_near; src.z_far = z_far;
-    return pnr::baked_launch(entry, src, (long long)NV * W * H, vol, -1, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
-                             depth, alpha, stream);
+    return pnr::baked_render("pnr_baked_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                             pnr::baked_dense(vol, -1, false, "vol", -1, nullptr),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_sh_render_rays(const float *rays, long long R, const float *coef, int degree, const uint32_t *bits, int nx,
                                         int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate,
                                         float *rgb, float *depth, float *alpha, void *stream) {
-    const char *entry = "pnr_baked_sh_render_rays";
-    if (degree < 0 || degree > 2) return pnr::occ_fail(entry, "degree must be 0, 1 or 2");
-    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
-    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.rays = rays;
-    return pnr::baked_launch(entry, src, R, coef, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha,
-                             stream);
+    return pnr::baked_render("pnr_baked_sh_render_rays", pnr::baked_explicit_rays(rays, R),
+                             pnr::baked_dense(coef, degree, false, "coef", 0, pnr::DEGREE_SH),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_sh_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
                                          float z_far, const float *coef, int degree, const uint32_t *bits, int nx, int ny, int nz,
                                          const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb,
                                          float *depth, float *alpha, void *stream) {
-    const char *entry = "pnr_baked_sh_render_views";
-    if (degree < 0 || degree > 2) return pnr::occ_fail(entry, "degree must be 0, 1 or 2");
-    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
-    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.poses = poses;
-    src.W = W; src.H = H;
-    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
-    src.z_near = z_near; src.z_far = z_far;
-    return pnr::baked_launch(entry, src, (long long)NV * W * H, coef, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
-                             depth, alpha, stream);
+    return pnr::baked_render("pnr_baked_sh_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                             pnr::baked_dense(coef, degree, false, "coef", 0, pnr::DEGREE_SH),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_sparse_points_mark(const uint32_t *bits, int nx, int ny, int nz, uint8_t *keep, void *stream) {
@@ -489,16 +472,9 @@ extern "C" int pnr_baked_sparse_render_rays(const float *rays, long long R, cons
                                             const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
                                             const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
                                             float *alpha, void *stream) {
-    const char *entry = "pnr_baked_sparse_render_rays";
-    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
-    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
-    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.rays = rays;
-    const pnr::SparseArgs sp = {index, M};
-    return pnr::baked_launch(entry, src, R, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha,
-                             stream, &sp);
+    return pnr::baked_render("pnr_baked_sparse_render_rays", pnr::baked_explicit_rays(rays, R),
+                             pnr::baked_sparse(rows, M, index, degree, false, pnr::DEGREE_SPARSE),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_sparse_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
@@ -506,75 +482,37 @@ extern "C" int pnr_baked_sparse_render_views(const float *poses, int NV, int W, 
                                              const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
                                              const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
                                              float *alpha, void *stream) {
-    const char *entry = "pnr_baked_sparse_render_views";
-    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA rows), 0, 1 or 2");
-    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
-    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.poses = poses;
-    src.W = W; src.H = H;
-    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
-    src.z_near = z_near; src.z_far = z_far;
-    const pnr::SparseArgs sp = {index, M};
-    return pnr::baked_launch(entry, src, (long long)NV * W * H, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
-                             depth, alpha, stream, &sp);
+    return pnr::baked_render("pnr_baked_sparse_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                             pnr::baked_sparse(rows, M, index, degree, false, pnr::DEGREE_SPARSE),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 // ---- half-precision storage: the entries above on (r,g,b,sigma) kept as four fp16 numbers.  degree -1: the RGBA march
 
-static int baked_half_rays(const char *entry, const float *rays, long long R, const uint16_t *vol, int degree, const uint32_t *bits,
-                           int nx, int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd, float terminate,
-                           float *rgb, float *depth, float *alpha, void *stream, const pnr::SparseArgs *sp) {
-    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA), 0, 1 or 2");
-    if (R < 0) return pnr::occ_fail(entry, "bad sizes (R)");
-    if (R > 0 && !rays) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(rays)) return pnr::occ_fail(entry, "rays must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.rays = rays;
-    return pnr::baked_launch(entry, src, R, vol, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream,
-                             sp, true);
-}
-
-static int baked_half_views(const char *entry, const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
-                            float z_near, float z_far, const uint16_t *vol, int degree, const uint32_t *bits, int nx, int ny, int nz,
-                            const float *c1, const float *c2, float step, int white_bkgd, float terminate, float *rgb, float *depth,
-                            float *alpha, void *stream, const pnr::SparseArgs *sp) {
-    if (degree < -1 || degree > 2) return pnr::occ_fail(entry, "degree must be -1 (RGBA), 0, 1 or 2");
-    if (NV < 0 || W <= 0 || H <= 0) return pnr::occ_fail(entry, "bad sizes (NV, W, H)");
-    if (NV > 0 && !poses) return pnr::occ_fail(entry, "null argument");
-    if (pnr::baked_misaligned4(poses)) return pnr::occ_fail(entry, "poses must be 4-byte aligned");
-    pnr::RaySrc src = {};
-    src.poses = poses;
-    src.W = W; src.H = H;
-    src.fx = fx; src.fy = fy; src.cx = cx; src.cy = cy;
-    src.z_near = z_near; src.z_far = z_far;
-    return pnr::baked_launch(entry, src, (long long)NV * W * H, vol, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
-                             depth, alpha, stream, sp, true);
-}
-
 extern "C" int pnr_baked_half_render_rays(const float *rays, long long R, const uint16_t *vol, int degree, const uint32_t *bits, int nx,
                                           int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd,
                                           float terminate, float *rgb, float *depth, float *alpha, void *stream) {
-    return baked_half_rays("pnr_baked_half_render_rays", rays, R, vol, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb,
-                           depth, alpha, stream, nullptr);
+    return pnr::baked_render("pnr_baked_half_render_rays", pnr::baked_explicit_rays(rays, R),
+                             pnr::baked_dense(vol, degree, true, "vol", -1, pnr::DEGREE_HALF),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_half_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
                                            float z_near, float z_far, const uint16_t *vol, int degree, const uint32_t *bits, int nx,
                                            int ny, int nz, const float *c1, const float *c2, float step, int white_bkgd,
                                            float terminate, float *rgb, float *depth, float *alpha, void *stream) {
-    return baked_half_views("pnr_baked_half_render_views", poses, NV, W, H, fx, fy, cx, cy, z_near, z_far, vol, degree, bits, nx, ny, nz,
-                            c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream, nullptr);
+    return pnr::baked_render("pnr_baked_half_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                             pnr::baked_dense(vol, degree, true, "vol", -1, pnr::DEGREE_HALF),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_sparse_half_render_rays(const float *rays, long long R, const uint16_t *rows, long long M, int degree,
                                                  const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
                                                  const float *c2, float step, int white_bkgd, float terminate, float *rgb,
                                                  float *depth, float *alpha, void *stream) {
-    const pnr::SparseArgs sp = {index, M};
-    return baked_half_rays("pnr_baked_sparse_half_render_rays", rays, R, rows, degree, bits, nx, ny, nz, c1, c2, step, white_bkgd,
-                           terminate, rgb, depth, alpha, stream, &sp);
+    return pnr::baked_render("pnr_baked_sparse_half_render_rays", pnr::baked_explicit_rays(rays, R),
+                             pnr::baked_sparse(rows, M, index, degree, true, pnr::DEGREE_HALF),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }
 
 extern "C" int pnr_baked_sparse_half_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
@@ -582,7 +520,7 @@ extern "C" int pnr_baked_sparse_half_render_views(const float *poses, int NV, in
                                                   const int32_t *index, const uint32_t *bits, int nx, int ny, int nz,
                                                   const float *c1, const float *c2, float step, int white_bkgd, float terminate,
                                                   float *rgb, float *depth, float *alpha, void *stream) {
-    const pnr::SparseArgs sp = {index, M};
-    return baked_half_views("pnr_baked_sparse_half_render_views", poses, NV, W, H, fx, fy, cx, cy, z_near, z_far, rows, degree, bits, nx,
-                            ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream, &sp);
+    return pnr::baked_render("pnr_baked_sparse_half_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                             pnr::baked_sparse(rows, M, index, degree, true, pnr::DEGREE_HALF),
+                             {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
 }

@@ -25,14 +25,15 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _f32(t, name, shape=None):
+def _f32(t, name, shape=None, dtype=torch.float32):
+    """a contiguous HIP tensor of `dtype` (fp32 unless said: a baked volume may be stored in fp16) and of `shape` (None: any size)"""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor")
     if not t.is_cuda:
         raise _lib.PixelNerfHipError(f"{name}: tensor must live on a HIP device (got {t.device}); "
                                      "pixelnerf_amd has no CPU path")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {t.dtype}")
     if shape is not None:
         if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
             raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
@@ -1312,16 +1313,89 @@ def _baked_march_args(what, reso, c1, c2, step, terminate):
     return (nx, ny, nz), step, terminate
 
 
-def _baked_args(what, vol, reso, c1, c2, step, bits, terminate):
-    """the volume, its geometry and the march settings of baked_render / baked_render_views, checked before any device work
-    -> (vol, (nx, ny, nz), step, terminate)"""
-    (nx, ny, nz), step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
-    vol = _f32(vol, "vol", (nx, ny, nz, 4))
-    if vol.data_ptr() % 16:
-        raise ValueError(f"{what}: vol must be 16-byte aligned")
+def _baked_volume(what, stored, degree, reso, c1, c2, step, bits, terminate, *, dtype, name, index=None, sparse=False):
+    """The stored tensor of any baked march, its geometry and the march settings, checked before any device work.  `name` is what
+    the caller's signature calls the tensor, and with `dtype` it says what the tensor may be: "vol" in fp32 is baked_render's RGBA
+    volume (nx,ny,nz,4), which takes no degree; "coef" (nx,ny,nz,B,4) at degree 0, 1, 2; an fp16 "vol" or "rows" at degree None /
+    -1 (RGBA: no B axis) or 0, 1, 2; `sparse`: (M,...) kept rows, with `index` (nx,ny,nz) int32 and bits both mandatory.
+    -> the tuple _baked_launch takes: what, name, stored (contiguous), degree (-1 for RGBA; None: the entry takes none), dims, c1, c2,
+    step, terminate, bits, index (None: not sparse)"""
+    takes_degree = not (name == "vol" and dtype == torch.float32)
+    tail = (4,)
+    if takes_degree:
+        degree = int(degree) if name == "coef" or degree is not None else -1
+        if degree not in (0, 1, 2) and (degree != -1 or name == "coef"):
+            allowed = "0, 1 or 2" if name == "coef" else f"None / -1 (RGBA{' rows' if dtype == torch.float32 else ''}), 0, 1 or 2"
+            raise ValueError(f"{what}: degree must be {allowed}, got {degree}")
+        tail = (4,) if degree < 0 else ((degree + 1) ** 2, 4)
+        lead = 1 if sparse else 3
+        if not isinstance(stored, torch.Tensor) or stored.dim() != lead + len(tail) or tuple(stored.shape[lead:]) != tail:
+            raise ValueError(f"{what}: {name} must be ({'M' if sparse else 'nx,ny,nz'},{','.join(str(s) for s in tail)}) at degree {degree}"
+                             f", got {tuple(stored.shape) if isinstance(stored, torch.Tensor) else type(stored).__name__}")
+        if name == "coef" and (len(reso) != 3 or tuple(int(r) for r in reso) != tuple(stored.shape[:3])):
+            raise ValueError(f"{what}: coef spans {tuple(stored.shape[:3])} points, reso says {tuple(reso)}")
+    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
+    if sparse and (bits is None or index is None):
+        raise ValueError(f"{what}: index and bits are mandatory (a sparse volume has nothing to march unskipped)")
+    stored = _f32(stored, name, ((None,) if sparse else dims) + tail, dtype)
+    if stored.numel() and stored.data_ptr() % 16:
+        raise ValueError(f"{what}: {name} must be 16-byte aligned")
     if bits is not None:
-        _check_grid_args(what, bits, (nx, ny, nz), c1, c2, vol.device)
-    return vol, (nx, ny, nz), step, terminate
+        _check_grid_args(what, bits, dims, c1, c2, stored.device)
+    if sparse and (not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims
+                   or index.device != stored.device):
+        raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {stored.device}")
+    return what, name, stored, (degree if takes_degree else None), dims, c1, c2, step, terminate, bits, (index if sparse else None)
+
+
+def _image_size(what, width, height):
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"{what}: the image must have at least one pixel, got {W} x {H}")
+    return W, H
+
+
+def _baked_launch(entry, v, white_bkgd, rays=None, camera=None):
+    """March the checked volume `v` (_baked_volume) through the library entry `entry`, along `rays` (R,8) or over the pixels of
+    `camera` = (poses (NV,4,4), W, H, focal, c, z_near, z_far) -> (rgb (R,3), depth (R,), alpha (R,)) fp32, R = NV H W for a camera"""
+    lib = _lib.load()
+    what, name, stored, degree, dims, c1, c2, step, terminate, bits, index = v
+    if camera is None:
+        source = _f32(rays, "rays", (None, 8))
+        R = source.shape[0]
+    else:
+        poses, W, H, focal, c, z_near, z_far = camera
+        source = _f32(poses, "poses", (None, 4, 4))
+        R = source.shape[0] * H * W
+    dev = source.device
+    if stored.device != dev:
+        subject = f"{name} {'live' if name == 'rows' else 'lives'}"
+        if camera is not None and stored.dtype == torch.float16:
+            subject = "the volume lives"
+        raise ValueError(f"{what}: {subject} on {stored.device}, the {'rays' if camera is None else 'poses'} on {dev}")
+    args = [_p(source), R]
+    if camera is not None:
+        fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+        cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+        args = [_p(source), source.shape[0], W, H, fx, fy, cx, cy, float(z_near), float(z_far)]
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    if index is None:
+        args.append(_p(stored))
+    else:
+        M = stored.shape[0]
+        args += (_p(stored) if M else None, M)
+    if degree is not None:
+        args.append(degree)
+    if index is not None:
+        args.append(_p(index.contiguous()))
+    args += (None if bits is None else _p(bits.contiguous()), dims[0], dims[1], dims[2], lo, hi, step, int(bool(white_bkgd)), terminate,
+             _p(rgb), _p(depth), _p(alpha))
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    return rgb, depth, alpha
 
 
 def baked_render(rays, vol, reso, c1, c2, step, bits=None, white_bkgd=False, terminate=0.0):
@@ -1330,21 +1404,8 @@ def baked_render(rays, vol, reso, c1, c2, step, bits=None, white_bkgd=False, ter
     distance in the units of z, bits None or occupancy_build's bitfield of the same grid (a sample in a cell whose bit is off has
     sigma = 0), terminate eps in [0, 1) (0: off).  -> (rgb (R,3), depth (R,), alpha (R,)) fp32.  No network, no host synchronisation,
     the same bytes on every call."""
-    lib = _lib.load()
-    vol, (nx, ny, nz), step, terminate = _baked_args("baked_render", vol, reso, c1, c2, step, bits, terminate)
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    if vol.device != dev:
-        raise ValueError(f"baked_render: vol lives on {vol.device}, the rays on {dev}")
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((R,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
-    lo, hi = _float3_pair(c1, c2)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_render_rays(_p(rays), R, _p(vol), None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi,
-                                             step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_render_rays")
-    return rgb, depth, alpha
+    v = _baked_volume("baked_render", vol, None, reso, c1, c2, step, bits, terminate, dtype=torch.float32, name="vol")
+    return _baked_launch("pnr_baked_render_rays", v, white_bkgd, rays=rays)
 
 
 def baked_render_views(poses, width, height, focal, c, z_near, z_far, vol, reso, c1, c2, step, bits=None, white_bkgd=False,
@@ -1353,47 +1414,9 @@ def baked_render_views(poses, width, height, focal, c, z_near, z_far, vol, reso,
     poses (NV,4,4) camera-to-world, focal a scalar or (fx, fy), c (cx, cy) or None = the image centre.  The rays are regenerated
     in the kernel -- the same bits as baked_render(gen_rays(...)), and no ray array is written.
     -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32, rays ordered (view, row, column)."""
-    lib = _lib.load()
-    W, H = int(width), int(height)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"baked_render_views: the image must have at least one pixel, got {W} x {H}")
-    vol, (nx, ny, nz), step, terminate = _baked_args("baked_render_views", vol, reso, c1, c2, step, bits, terminate)
-    poses = _f32(poses, "poses", (None, 4, 4))
-    NV, dev = poses.shape[0], poses.device
-    if vol.device != dev:
-        raise ValueError(f"baked_render_views: vol lives on {vol.device}, the poses on {dev}")
-    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
-    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
-    R = NV * H * W
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((R,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
-    lo, hi = _float3_pair(c1, c2)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), _p(vol),
-                                              None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
-                                              int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_render_views")
-    return rgb, depth, alpha
-
-
-def _baked_sh_args(what, coef, degree, reso, c1, c2, step, bits, terminate):
-    """_baked_args for a coefficient volume: coef (nx,ny,nz,(degree+1)^2,4) -> (coef, degree, (nx, ny, nz), step, terminate)"""
-    degree = int(degree)
-    if degree not in (0, 1, 2):
-        raise ValueError(f"{what}: degree must be 0, 1 or 2, got {degree}")
-    if not isinstance(coef, torch.Tensor) or coef.dim() != 5 or coef.shape[3] != (degree + 1) ** 2 or coef.shape[4] != 4:
-        raise ValueError(f"{what}: coef must be (nx,ny,nz,{(degree + 1) ** 2},4) at degree {degree}, got "
-                         f"{tuple(coef.shape) if isinstance(coef, torch.Tensor) else type(coef).__name__}")
-    if len(reso) != 3 or tuple(int(r) for r in reso) != tuple(coef.shape[:3]):
-        raise ValueError(f"{what}: coef spans {tuple(coef.shape[:3])} points, reso says {tuple(reso)}")
-    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
-    coef = _f32(coef, "coef", (*dims, (degree + 1) ** 2, 4))
-    if coef.data_ptr() % 16:
-        raise ValueError(f"{what}: coef must be 16-byte aligned")
-    if bits is not None:
-        _check_grid_args(what, bits, dims, c1, c2, coef.device)
-    return coef, degree, dims, step, terminate
+    W, H = _image_size("baked_render_views", width, height)
+    v = _baked_volume("baked_render_views", vol, None, reso, c1, c2, step, bits, terminate, dtype=torch.float32, name="vol")
+    return _baked_launch("pnr_baked_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
 def baked_sh_render(rays, coef, degree, reso, c1, c2, step, bits=None, white_bkgd=False, terminate=0.0):
@@ -1401,50 +1424,17 @@ def baked_sh_render(rays, coef, degree, reso, c1, c2, step, bits=None, white_bkg
     (nx,ny,nz,B,4) fp32 HIP tensor, B = (degree+1)^2 real spherical-harmonic coefficients of (r, g, b, sigma) per grid point, degree
     0, 1 or 2; every corner is evaluated for the ray's own direction and clamped before the blend.  Everything else as baked_render.
     -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
-    lib = _lib.load()
-    coef, degree, (nx, ny, nz), step, terminate = _baked_sh_args("baked_sh_render", coef, degree, reso, c1, c2, step, bits, terminate)
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    if coef.device != dev:
-        raise ValueError(f"baked_sh_render: coef lives on {coef.device}, the rays on {dev}")
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((R,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
-    lo, hi = _float3_pair(c1, c2)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_sh_render_rays(_p(rays), R, _p(coef), degree, None if bits is None else _p(bits.contiguous()), nx, ny, nz,
-                                                lo, hi, step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_sh_render_rays")
-    return rgb, depth, alpha
+    v = _baked_volume("baked_sh_render", coef, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float32, name="coef")
+    return _baked_launch("pnr_baked_sh_render_rays", v, white_bkgd, rays=rays)
 
 
 def baked_sh_render_views(poses, width, height, focal, c, z_near, z_far, coef, degree, reso, c1, c2, step, bits=None, white_bkgd=False,
                           terminate=0.0):
     """baked_render_views through a view-dependent volume (pnr_baked_sh_render_views): the same bits as
     baked_sh_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
-    lib = _lib.load()
-    W, H = int(width), int(height)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"baked_sh_render_views: the image must have at least one pixel, got {W} x {H}")
-    coef, degree, (nx, ny, nz), step, terminate = _baked_sh_args("baked_sh_render_views", coef, degree, reso, c1, c2, step, bits,
-                                                                 terminate)
-    poses = _f32(poses, "poses", (None, 4, 4))
-    NV, dev = poses.shape[0], poses.device
-    if coef.device != dev:
-        raise ValueError(f"baked_sh_render_views: coef lives on {coef.device}, the poses on {dev}")
-    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
-    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
-    R = NV * H * W
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((R,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
-    lo, hi = _float3_pair(c1, c2)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_sh_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), _p(coef), degree,
-                                                 None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
-                                                 int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_sh_render_views")
-    return rgb, depth, alpha
+    W, H = _image_size("baked_sh_render_views", width, height)
+    v = _baked_volume("baked_sh_render_views", coef, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float32, name="coef")
+    return _baked_launch("pnr_baked_sh_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
 def sparse_points(bits, reso):
@@ -1498,240 +1488,63 @@ def gen_grid_points_at(c1, c2, reso, ids, viewdirs=True):
     return xyz, vd
 
 
-def _baked_sparse_args(what, rows, degree, index, bits, reso, c1, c2, step, terminate):
-    """_baked_args for the kept rows of a sparse volume: rows (M,4) with degree None / -1, (M,(degree+1)^2,4) with degree 0..2; index
-    (nx,ny,nz) int32 and bits, both mandatory -> (rows, degree (-1 for RGBA), (nx, ny, nz), step, terminate)"""
-    degree = -1 if degree is None else int(degree)
-    if degree not in (-1, 0, 1, 2):
-        raise ValueError(f"{what}: degree must be None / -1 (RGBA rows), 0, 1 or 2, got {degree}")
-    shape = (None, 4) if degree < 0 else (None, (degree + 1) ** 2, 4)
-    if not isinstance(rows, torch.Tensor) or rows.dim() != len(shape) or tuple(rows.shape[1:]) != shape[1:]:
-        raise ValueError(f"{what}: rows must be (M,{','.join(str(s) for s in shape[1:])}) at degree {degree}, got "
-                         f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
-    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
-    if bits is None or index is None:
-        raise ValueError(f"{what}: index and bits are mandatory (a sparse volume has nothing to march unskipped)")
-    rows = _f32(rows, "rows", shape)
-    if rows.numel() and rows.data_ptr() % 16:
-        raise ValueError(f"{what}: rows must be 16-byte aligned")
-    _check_grid_args(what, bits, dims, c1, c2, rows.device)
-    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims or index.device != rows.device:
-        raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {rows.device}")
-    return rows, degree, dims, step, terminate
-
-
 def baked_sparse_render(rays, rows, degree, index, bits, reso, c1, c2, step, white_bkgd=False, terminate=0.0):
     """Rays through a sparse baked volume (pnr_baked_sparse_render_rays; include/pixelnerf_hip.h, "baked volumes"): rows (M,4)
     (degree None: RGBA) or (M,B,4) (degree 0, 1, 2) fp32 HIP tensor -- the rows of the dense volume at the kept points --, index and
     bits as sparse_points took and returned them.  The bytes of baked_render / baked_sh_render on the dense volume with the same
     bits; an index value that names no pair of rows drops its sample (sigma = 0) instead of reading.
     -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
-    lib = _lib.load()
-    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_args("baked_sparse_render", rows, degree, index, bits, reso, c1, c2, step,
-                                                                     terminate)
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    if rows.device != dev:
-        raise ValueError(f"baked_sparse_render: rows live on {rows.device}, the rays on {dev}")
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((R,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
-    lo, hi = _float3_pair(c1, c2)
-    M = rows.shape[0]
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_sparse_render_rays(_p(rays), R, _p(rows) if M else None, M, degree, _p(index.contiguous()),
-                                                    _p(bits.contiguous()), nx, ny, nz, lo, hi, step, int(bool(white_bkgd)), terminate,
-                                                    _p(rgb), _p(depth), _p(alpha), _stream()), "pnr_baked_sparse_render_rays")
-    return rgb, depth, alpha
+    v = _baked_volume("baked_sparse_render", rows, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float32,
+                      name="rows", index=index, sparse=True)
+    return _baked_launch("pnr_baked_sparse_render_rays", v, white_bkgd, rays=rays)
 
 
 def baked_sparse_render_views(poses, width, height, focal, c, z_near, z_far, rows, degree, index, bits, reso, c1, c2, step,
                               white_bkgd=False, terminate=0.0):
     """baked_render_views through a sparse baked volume (pnr_baked_sparse_render_views): the same bits as
     baked_sparse_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
-    lib = _lib.load()
-    W, H = int(width), int(height)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"baked_sparse_render_views: the image must have at least one pixel, got {W} x {H}")
-    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_args("baked_sparse_render_views", rows, degree, index, bits, reso, c1, c2,
-                                                                     step, terminate)
-    poses = _f32(poses, "poses", (None, 4, 4))
-    NV, dev = poses.shape[0], poses.device
-    if rows.device != dev:
-        raise ValueError(f"baked_sparse_render_views: rows live on {rows.device}, the poses on {dev}")
-    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
-    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
-    R = NV * H * W
-    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((R,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
-    lo, hi = _float3_pair(c1, c2)
-    M = rows.shape[0]
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_sparse_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far),
-                                                     _p(rows) if M else None, M, degree, _p(index.contiguous()), _p(bits.contiguous()),
-                                                     nx, ny, nz, lo, hi, step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth),
-                                                     _p(alpha), _stream()), "pnr_baked_sparse_render_views")
-    return rgb, depth, alpha
+    W, H = _image_size("baked_sparse_render_views", width, height)
+    v = _baked_volume("baked_sparse_render_views", rows, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float32,
+                      name="rows", index=index, sparse=True)
+    return _baked_launch("pnr_baked_sparse_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
 # ---- half-precision baked volumes: fp16 storage, the fp32 march on the widened values (include/pixelnerf_hip.h, "Half-precision
 # baked volumes").  degree None / -1: the RGBA march; 0, 1, 2: the view-dependent one
 
-def _f16(t, name, shape):
-    """_f32 for a stored fp16 tensor"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor")
-    if not t.is_cuda:
-        raise _lib.PixelNerfHipError(f"{name}: tensor must live on a HIP device (got {t.device}); pixelnerf_amd has no CPU path")
-    if t.dtype != torch.float16:
-        raise TypeError(f"{name}: expected float16, got {t.dtype}")
-    if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
-        raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
-    return t.contiguous()
-
-
-def _half_degree(what, degree):
-    degree = -1 if degree is None else int(degree)
-    if degree not in (-1, 0, 1, 2):
-        raise ValueError(f"{what}: degree must be None / -1 (RGBA), 0, 1 or 2, got {degree}")
-    return degree, ((4,) if degree < 0 else ((degree + 1) ** 2, 4))
-
-
-def _baked_half_args(what, vol, degree, reso, c1, c2, step, bits, terminate):
-    """_baked_args / _baked_sh_args for an fp16 volume: vol (nx,ny,nz,4) with degree None / -1, (nx,ny,nz,(degree+1)^2,4) with degree
-    0..2 -> (vol, degree (-1 for RGBA), (nx, ny, nz), step, terminate)"""
-    degree, tail = _half_degree(what, degree)
-    if not isinstance(vol, torch.Tensor) or vol.dim() != 3 + len(tail) or tuple(vol.shape[3:]) != tail:
-        raise ValueError(f"{what}: vol must be (nx,ny,nz,{','.join(str(s) for s in tail)}) at degree {degree}, got "
-                         f"{tuple(vol.shape) if isinstance(vol, torch.Tensor) else type(vol).__name__}")
-    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
-    vol = _f16(vol, "vol", (*dims, *tail))
-    if vol.data_ptr() % 16:
-        raise ValueError(f"{what}: vol must be 16-byte aligned")
-    if bits is not None:
-        _check_grid_args(what, bits, dims, c1, c2, vol.device)
-    return vol, degree, dims, step, terminate
-
-
-def _baked_sparse_half_args(what, rows, degree, index, bits, reso, c1, c2, step, terminate):
-    """_baked_sparse_args for fp16 rows -> (rows, degree (-1 for RGBA), (nx, ny, nz), step, terminate)"""
-    degree, tail = _half_degree(what, degree)
-    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 + len(tail) or tuple(rows.shape[1:]) != tail:
-        raise ValueError(f"{what}: rows must be (M,{','.join(str(s) for s in tail)}) at degree {degree}, got "
-                         f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
-    dims, step, terminate = _baked_march_args(what, reso, c1, c2, step, terminate)
-    if bits is None or index is None:
-        raise ValueError(f"{what}: index and bits are mandatory (a sparse volume has nothing to march unskipped)")
-    rows = _f16(rows, "rows", (None, *tail))
-    if rows.numel() and rows.data_ptr() % 16:
-        raise ValueError(f"{what}: rows must be 16-byte aligned")
-    _check_grid_args(what, bits, dims, c1, c2, rows.device)
-    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims or index.device != rows.device:
-        raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {rows.device}")
-    return rows, degree, dims, step, terminate
-
-
-def _march_outputs(R, dev):
-    return (torch.empty((R, 3), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.float32, device=dev),
-            torch.empty((R,), dtype=torch.float32, device=dev))
-
-
-def _camera_args(what, poses, width, height, focal, c, stored):
-    """the camera of a *_views entry -> (poses, NV, W, H, fx, fy, cx, cy); `stored` is the volume tensor the poses must live with"""
-    W, H = int(width), int(height)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"{what}: the image must have at least one pixel, got {W} x {H}")
-    poses = _f32(poses, "poses", (None, 4, 4))
-    if stored.device != poses.device:
-        raise ValueError(f"{what}: the volume lives on {stored.device}, the poses on {poses.device}")
-    fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
-    cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
-    return poses, poses.shape[0], W, H, fx, fy, cx, cy
-
-
 def baked_half_render(rays, vol, degree, reso, c1, c2, step, bits=None, white_bkgd=False, terminate=0.0):
     """baked_render (degree None / -1: vol (nx,ny,nz,4)) or baked_sh_render (degree 0, 1, 2: vol (nx,ny,nz,B,4)) through an fp16 HIP
     tensor (pnr_baked_half_render_rays): the bytes of that function on vol.float(), every other argument the same.
     -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
-    lib = _lib.load()
-    vol, degree, (nx, ny, nz), step, terminate = _baked_half_args("baked_half_render", vol, degree, reso, c1, c2, step, bits, terminate)
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    if vol.device != dev:
-        raise ValueError(f"baked_half_render: vol lives on {vol.device}, the rays on {dev}")
-    rgb, depth, alpha = _march_outputs(R, dev)
-    lo, hi = _float3_pair(c1, c2)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_half_render_rays(_p(rays), R, _p(vol), degree, None if bits is None else _p(bits.contiguous()), nx, ny,
-                                                  nz, lo, hi, step, int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha),
-                                                  _stream()), "pnr_baked_half_render_rays")
-    return rgb, depth, alpha
+    v = _baked_volume("baked_half_render", vol, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16, name="vol")
+    return _baked_launch("pnr_baked_half_render_rays", v, white_bkgd, rays=rays)
 
 
 def baked_half_render_views(poses, width, height, focal, c, z_near, z_far, vol, degree, reso, c1, c2, step, bits=None, white_bkgd=False,
                             terminate=0.0):
     """baked_render_views / baked_sh_render_views through an fp16 volume (pnr_baked_half_render_views): the same bits as
     baked_half_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
-    lib = _lib.load()
-    what = "baked_half_render_views"
-    if int(width) <= 0 or int(height) <= 0:
-        raise ValueError(f"{what}: the image must have at least one pixel, got {int(width)} x {int(height)}")
-    vol, degree, (nx, ny, nz), step, terminate = _baked_half_args(what, vol, degree, reso, c1, c2, step, bits, terminate)
-    poses, NV, W, H, fx, fy, cx, cy = _camera_args(what, poses, width, height, focal, c, vol)
-    dev = poses.device
-    rgb, depth, alpha = _march_outputs(NV * H * W, dev)
-    lo, hi = _float3_pair(c1, c2)
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_half_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far), _p(vol), degree,
-                                                   None if bits is None else _p(bits.contiguous()), nx, ny, nz, lo, hi, step,
-                                                   int(bool(white_bkgd)), terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_half_render_views")
-    return rgb, depth, alpha
+    W, H = _image_size("baked_half_render_views", width, height)
+    v = _baked_volume("baked_half_render_views", vol, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16, name="vol")
+    return _baked_launch("pnr_baked_half_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
 def baked_sparse_half_render(rays, rows, degree, index, bits, reso, c1, c2, step, white_bkgd=False, terminate=0.0):
     """baked_sparse_render through fp16 rows (pnr_baked_sparse_half_render_rays): rows (M,4) (degree None / -1) or (M,B,4) fp16 HIP
     tensor; the bytes of baked_sparse_render on rows.float().  -> (rgb (R,3), depth (R,), alpha (R,)) fp32."""
-    lib = _lib.load()
-    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_half_args("baked_sparse_half_render", rows, degree, index, bits, reso, c1,
-                                                                          c2, step, terminate)
-    rays = _f32(rays, "rays", (None, 8))
-    R, dev = rays.shape[0], rays.device
-    if rows.device != dev:
-        raise ValueError(f"baked_sparse_half_render: rows live on {rows.device}, the rays on {dev}")
-    rgb, depth, alpha = _march_outputs(R, dev)
-    lo, hi = _float3_pair(c1, c2)
-    M = rows.shape[0]
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_sparse_half_render_rays(_p(rays), R, _p(rows) if M else None, M, degree, _p(index.contiguous()),
-                                                         _p(bits.contiguous()), nx, ny, nz, lo, hi, step, int(bool(white_bkgd)),
-                                                         terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_sparse_half_render_rays")
-    return rgb, depth, alpha
+    v = _baked_volume("baked_sparse_half_render", rows, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16,
+                      name="rows", index=index, sparse=True)
+    return _baked_launch("pnr_baked_sparse_half_render_rays", v, white_bkgd, rays=rays)
 
 
 def baked_sparse_half_render_views(poses, width, height, focal, c, z_near, z_far, rows, degree, index, bits, reso, c1, c2, step,
                                    white_bkgd=False, terminate=0.0):
     """baked_sparse_render_views through fp16 rows (pnr_baked_sparse_half_render_views): the same bits as
     baked_sparse_half_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
-    lib = _lib.load()
-    what = "baked_sparse_half_render_views"
-    if int(width) <= 0 or int(height) <= 0:
-        raise ValueError(f"{what}: the image must have at least one pixel, got {int(width)} x {int(height)}")
-    rows, degree, (nx, ny, nz), step, terminate = _baked_sparse_half_args(what, rows, degree, index, bits, reso, c1, c2, step, terminate)
-    poses, NV, W, H, fx, fy, cx, cy = _camera_args(what, poses, width, height, focal, c, rows)
-    dev = poses.device
-    rgb, depth, alpha = _march_outputs(NV * H * W, dev)
-    lo, hi = _float3_pair(c1, c2)
-    M = rows.shape[0]
-    with torch.cuda.device(dev):
-        _lib.check(lib.pnr_baked_sparse_half_render_views(_p(poses), NV, W, H, fx, fy, cx, cy, float(z_near), float(z_far),
-                                                          _p(rows) if M else None, M, degree, _p(index.contiguous()),
-                                                          _p(bits.contiguous()), nx, ny, nz, lo, hi, step, int(bool(white_bkgd)),
-                                                          terminate, _p(rgb), _p(depth), _p(alpha), _stream()),
-                   "pnr_baked_sparse_half_render_views")
-    return rgb, depth, alpha
+    W, H = _image_size("baked_sparse_half_render_views", width, height)
+    v = _baked_volume("baked_sparse_half_render_views", rows, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16,
+                      name="rows", index=index, sparse=True)
+    return _baked_launch("pnr_baked_sparse_half_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):

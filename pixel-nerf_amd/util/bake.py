@@ -54,11 +54,138 @@ def _storage_dtype(what, dtype):
     return dtype
 
 
+def _bake(what, net, c1, c2, reso, dtype, coarse, eval_batch_size, sparse=False, occupancy=None, degree=None, n_dirs=32,
+          viewdirs="origin"):
+    """The bake loop of the three from_model methods.  Points: every grid point in ascending order (ops.gen_grid_points), or with
+    `sparse` the kept points of `occupancy` alone (ops.sparse_points, ops.gen_grid_points_at).  Mode: degree None -- all four output
+    columns of ONE pass with `viewdirs` -- or degree 0, 1, 2 -- n_dirs passes projected onto the basis in fp32, the product then the
+    sum, in the order of m.  Even chunks, eval mode with the train flag restored, `to_half` at the end for dtype=torch.float16.
+    -> (stored (P or M,4) or (P or M,B,4), (reso, c1, c2) as checked, (index, ids) or None)"""
+    from .. import ops
+    _storage_dtype(what, dtype)
+    if int(getattr(net, "num_objs", 1) or 1) > 1:
+        raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
+    reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
+    if sparse:
+        _same_grid(what, occupancy, reso, c1, c2)
+    use_viewdirs = bool(getattr(net, "use_viewdirs", False))
+    origin, const_dir, dirs, P = True, None, None, None
+    if degree is None:
+        origin = isinstance(viewdirs, str)
+        if origin and viewdirs != "origin":
+            raise ValueError(f"{what}: viewdirs must be 'origin' or a 3-vector, got {viewdirs!r}")
+    else:
+        degree = int(degree)
+        P = BakedSHVolume.projection(n_dirs, degree)  # (the degree and n_dirs checks)
+        if not use_viewdirs and degree > 0:
+            warnings.warn(f"{what}: the network takes no view directions; baking at degree 0")
+            degree = 0
+    device = next(net.parameters()).device
+    if sparse and occupancy.bits.device != device:
+        raise ValueError(f"{what}: the occupancy grid lives on {occupancy.bits.device}, the network on {device}")
+    if degree is None:
+        if not origin:
+            const_dir = torch.as_tensor(viewdirs, dtype=torch.float32).flatten()
+            if const_dir.numel() != 3 or not bool(torch.isfinite(const_dir).all()) or float(const_dir.norm()) == 0.0:
+                raise ValueError(f"{what}: a constant view direction must be a finite non-zero 3-vector")
+            const_dir = (const_dir / const_dir.norm()).to(device)
+        if use_viewdirs and origin:
+            warnings.warn("Running marching cubes with fake view dirs (pointing to origin), output may be invalid")
+    elif use_viewdirs:
+        dirs, P = BakedSHVolume.directions(n_dirs).to(device), P.float().to(device)
+    else:
+        P = torch.ones((1, 1), device=device)  # one pass: its output is the DC part
+    nb = None if degree is None else (degree + 1) ** 2
+    if coarse is None:
+        coarse = getattr(net, "mlp_fine", None) is None
+    chunk = max(2, int(eval_batch_size) // 2 * 2)
+    kept = ops.sparse_points(occupancy.bits, reso) if sparse else None
+    total = reso[0] * reso[1] * reso[2] if kept is None else kept[1].shape[0]
+    is_train = bool(getattr(net, "training", False))
+    if hasattr(net, "eval"):
+        net.eval()
+    try:
+        with torch.no_grad():
+            if degree is None:
+                stored = torch.empty((total, 4), dtype=torch.float32, device=device)
+            else:
+                stored = torch.zeros((total, nb, 4), dtype=torch.float32, device=device)
+            for first in range(0, total, chunk):
+                count = min(chunk, total - first)
+                fake_dirs = degree is None and use_viewdirs and origin
+                if kept is None:
+                    pnts, vd = ops.gen_grid_points(c1, c2, reso, first, count, device=device, viewdirs=fake_dirs)
+                else:
+                    pnts, vd = ops.gen_grid_points_at(c1, c2, reso, kept[1][first:first + count], viewdirs=fake_dirs)
+                if degree is None:
+                    if use_viewdirs and not origin:
+                        vd = const_dir.expand(count, 3).contiguous()
+                    out = net(pnts[None], coarse=bool(coarse), viewdirs=vd[None] if use_viewdirs else None)
+                    stored[first:first + count] = out.reshape(count, -1)[:, :4]
+                    continue
+                part = stored[first:first + count]
+                for m in range(P.shape[1]):
+                    vd = dirs[m].expand(count, 3).contiguous()[None] if use_viewdirs else None
+                    out = net(pnts[None], coarse=bool(coarse), viewdirs=vd).reshape(count, -1)[:, :4]
+                    part += out[:, None, :] * P[:nb, m][None, :, None]  # the product, then the sum: two roundings, in the order of m
+    finally:
+        if is_train:
+            net.train()
+    if dtype == torch.float16:
+        stored = to_half(stored)
+    return stored, (reso, c1, c2), kept
+
+
 class _Baked:
-    """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2).  A
-    subclass says which entries march its volume (_march_rays, _march_views) and which tensor it stores (_stored).
+    """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2) and
+    the storage methods.  A subclass names the tensor it stores (`_stored_name`: the attribute, and the key of its state) and has a
+    `degree` when its march is the view-dependent one.
     Storage is fp32 or fp16 (`dtype`); the march is fp32 either way: a half volume renders the BYTES its `float()` renders
     (include/pixelnerf_hip.h, "Half-precision baked volumes")."""
+
+    _stored_name = None  # "vol", "coef" or "rows"
+    degree = None        # None: the RGBA march
+
+    def _stored(self):
+        return getattr(self, self._stored_name)
+
+    def _around(self, stored):
+        """this volume around another stored tensor"""
+        return type(self)(stored, self.c1, self.c2, self.skip_threshold)
+
+    def half(self):
+        """this volume with `to_half` of its stored tensor (a sparse volume shares index, ids and occupancy); a half volume is
+        returned as it is"""
+        return self if self.dtype == torch.float16 else self._around(to_half(self._stored()))
+
+    def float(self):
+        """this volume widened to fp32 (exact; a sparse volume shares index, ids and occupancy); an fp32 volume is returned as it is"""
+        return self if self.dtype == torch.float32 else self._around(self._stored().float())
+
+    def state_dict(self):
+        """the stored tensor under its name (a degree follows from its shape), the geometry and the skip threshold; the skip grid is
+        rebuilt on load"""
+        return {self._stored_name: self._stored(), "c1": torch.tensor(self.c1, dtype=torch.float64),
+                "c2": torch.tensor(self.c2, dtype=torch.float64), "skip_threshold": torch.tensor(self.skip_threshold, dtype=torch.float64)}
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        """:param device where to put the volume; None: where the stored tensor lives"""
+        stored = state[cls._stored_name] if device is None else state[cls._stored_name].to(device)
+        return cls(stored, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
+
+    def _march(self, source, step, bits, white_bkgd, terminate):
+        """source: (rays (R,8),), or the camera (poses, W, H, focal, c, z_near, z_far); which ops function marches follows from the
+        stored dtype, the degree and whether the volume is sparse"""
+        from .. import ops
+        stored, sparse = self._stored(), self._stored_name == "rows"
+        kind = "half_" if stored.dtype == torch.float16 else "" if sparse or self.degree is None else "sh_"
+        kind = ("sparse_" if sparse else "") + kind
+        march = getattr(ops, f"baked_{kind}render" + ("" if len(source) == 1 else "_views"))
+        volume = (stored, self.degree) if kind else (stored,)  # (baked_render alone takes no degree)
+        if sparse:
+            return march(*source, *volume, self.index, bits, self.reso, self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
+        return march(*source, *volume, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
 
     @property
     def dtype(self):
@@ -89,7 +216,7 @@ class _Baked:
         lead = tuple(rays.shape[:-1])
         step, terminate, bits = self._march_args(step, terminate, skip)
         with torch.no_grad():
-            rgb, depth, alpha = self._march_rays(rays.reshape(-1, 8).float(), step, bits, white_bkgd, terminate)
+            rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), step, bits, white_bkgd, terminate)
         return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
 
     def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, step=None, white_bkgd=False,
@@ -113,7 +240,7 @@ class _Baked:
             raise ValueError(f"{name}.render_views: gt_rgb must be (NVt,H,W,3) = {(NVt, H, W, 3)}, got {tuple(gt_rgb.shape)}")
         step, terminate, bits = self._march_args(step, terminate, skip)
         with torch.no_grad():
-            rgb, depth, alpha = self._march_views(poses_c2w.float(), W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate)
+            rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, bits, white_bkgd, terminate)
             gt = None if gt_rgb is None else gt_rgb.reshape(NVt, H * W, 3).float()
             ep = ops.eval_epilogue(rgb.reshape(NVt, H * W, 3), depth.reshape(NVt, H * W), z_near, z_far, gt_rgb=gt, want_u8=want_u8,
                                    image_shape=(H, W) if gt is not None else None)
@@ -134,6 +261,8 @@ class BakedVolume(_Baked):
     An fp16 volume (`half()`, `from_model(dtype=torch.float16)`, or a caller's fp16 tensor) renders the bytes of its `float()`; its
     skip grid is built from the widened sigma, so skipping stays exact (a sigma below 2^-25 has rounded to 0)."""
 
+    _stored_name = "vol"
+
     def __init__(self, vol, c1, c2, skip_threshold=0.0, keep_largest=None, min_voxels=None):
         from .. import _lib
         if not isinstance(vol, torch.Tensor) or vol.dim() != 4 or vol.shape[3] != 4 or vol.dtype not in (torch.float32, torch.float16):
@@ -150,17 +279,6 @@ class BakedVolume(_Baked):
         self.vol, self.reso, self.c1, self.c2, self.skip_threshold = vol, reso, c1, c2, skip_threshold
         self.occupancy = OccupancyGrid.from_density(vol[..., 3].float().contiguous(), c1, c2, skip_threshold, dilate=0,
                                                     keep_largest=keep_largest, min_voxels=min_voxels)
-
-    def _stored(self):
-        return self.vol
-
-    def half(self):
-        """this volume with `to_half(vol)`; a half volume is returned as it is"""
-        return self if self.vol.dtype == torch.float16 else BakedVolume(to_half(self.vol), self.c1, self.c2, self.skip_threshold)
-
-    def float(self):
-        """this volume widened to fp32 (exact); an fp32 volume is returned as it is"""
-        return self if self.vol.dtype == torch.float32 else BakedVolume(self.vol.float(), self.c1, self.c2, self.skip_threshold)
 
     @classmethod
     def from_tensor(cls, vol, c1, c2, skip_threshold=0.0):
@@ -183,80 +301,14 @@ class BakedVolume(_Baked):
         skip_threshold, dilate=0, keep_largest=, min_voxels=)
         :param dtype torch.float32, or torch.float16: the bake is the fp32 one and `to_half` is applied to its result
         A non-finite value in the volume raises ValueError."""
-        from .. import ops
-        what = "BakedVolume.from_model"
-        _storage_dtype(what, dtype)
-        if int(getattr(net, "num_objs", 1) or 1) > 1:
-            raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
-        reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
-        use_viewdirs = bool(getattr(net, "use_viewdirs", False))
-        origin = isinstance(viewdirs, str)
-        if origin and viewdirs != "origin":
-            raise ValueError(f"{what}: viewdirs must be 'origin' or a 3-vector, got {viewdirs!r}")
-        device = next(net.parameters()).device
-        const_dir = None
-        if not origin:
-            const_dir = torch.as_tensor(viewdirs, dtype=torch.float32).flatten()
-            if const_dir.numel() != 3 or not bool(torch.isfinite(const_dir).all()) or float(const_dir.norm()) == 0.0:
-                raise ValueError(f"{what}: a constant view direction must be a finite non-zero 3-vector")
-            const_dir = (const_dir / const_dir.norm()).to(device)
-        if use_viewdirs and origin:
-            warnings.warn("Running marching cubes with fake view dirs (pointing to origin), output may be invalid")
-        if coarse is None:
-            coarse = getattr(net, "mlp_fine", None) is None
-        chunk = max(2, int(eval_batch_size) // 2 * 2)
-        total = reso[0] * reso[1] * reso[2]
-        is_train = bool(getattr(net, "training", False))
-        if hasattr(net, "eval"):
-            net.eval()
-        try:
-            with torch.no_grad():
-                vol = torch.empty((total, 4), dtype=torch.float32, device=device)
-                for first in range(0, total, chunk):
-                    count = min(chunk, total - first)
-                    pnts, vd = ops.gen_grid_points(c1, c2, reso, first, count, device=device, viewdirs=use_viewdirs and origin)
-                    if use_viewdirs and not origin:
-                        vd = const_dir.expand(count, 3).contiguous()
-                    out = net(pnts[None], coarse=bool(coarse), viewdirs=vd[None] if use_viewdirs else None)
-                    vol[first:first + count] = out.reshape(count, -1)[:, :4]
-        finally:
-            if is_train:
-                net.train()
-        if dtype == torch.float16:
-            vol = to_half(vol)
+        vol, (reso, c1, c2), _ = _bake("BakedVolume.from_model", net, c1, c2, reso, dtype, coarse, eval_batch_size, viewdirs=viewdirs)
         return cls(vol.view(*reso, 4), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
-
-    def _march_rays(self, rays, step, bits, white_bkgd, terminate):
-        from .. import ops
-        if self.vol.dtype == torch.float16:
-            return ops.baked_half_render(rays, self.vol, -1, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
-                                         terminate=terminate)
-        return ops.baked_render(rays, self.vol, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
-
-    def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
-        from .. import ops
-        if self.vol.dtype == torch.float16:
-            return ops.baked_half_render_views(poses, W, H, focal, c, z_near, z_far, self.vol, -1, self.reso, self.c1, self.c2, step,
-                                               bits=bits, white_bkgd=white_bkgd, terminate=terminate)
-        return ops.baked_render_views(poses, W, H, focal, c, z_near, z_far, self.vol, self.reso, self.c1, self.c2, step, bits=bits,
-                                      white_bkgd=white_bkgd, terminate=terminate)
 
     def sparse(self, occupancy=None):
         """The SparseBakedVolume of this volume: the rows of the grid points that the occupied cells of `occupancy` read (None: the
         volume's own skip grid; or an OccupancyGrid of the same reso, c1, c2) and nothing else.  It renders the bytes of this volume's
         march with those bits: with None, `sparse().render(...)` equals `render(..., skip=True)` bit for bit at any skip_threshold."""
         return _sparse_of(self, self.vol.view(-1, 4), occupancy, "BakedVolume.sparse")
-
-    def state_dict(self):
-        """the volume, the geometry and the skip threshold; the skip grid is rebuilt on load"""
-        return {"vol": self.vol, "c1": torch.tensor(self.c1, dtype=torch.float64), "c2": torch.tensor(self.c2, dtype=torch.float64),
-                "skip_threshold": torch.tensor(self.skip_threshold, dtype=torch.float64)}
-
-    @classmethod
-    def from_state_dict(cls, state, device=None):
-        """:param device where to put the volume; None: where state["vol"] lives"""
-        vol = state["vol"] if device is None else state["vol"].to(device)
-        return cls(vol, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
 
 
 # ---------------------------------------------------------------- view-dependent volumes: real spherical harmonics up to degree 2
@@ -306,6 +358,8 @@ class BakedSHVolume(_Baked):
     with m_k = max |Y_k|: at skip_threshold 0 a skipped cell has sigma exactly 0 at its eight corners for every direction, so
     `render(skip=True)` equals `render(skip=False)` bit for bit."""
 
+    _stored_name = "coef"
+
     def __init__(self, coef, c1, c2, skip_threshold=0.0, keep_largest=None, min_voxels=None):
         from .. import _lib
         if not isinstance(coef, torch.Tensor) or coef.dim() != 5 or coef.shape[4] != 4 \
@@ -324,17 +378,6 @@ class BakedSHVolume(_Baked):
         self.coef, self.degree, self.reso, self.c1, self.c2, self.skip_threshold = coef, degree, reso, c1, c2, skip_threshold
         self.occupancy = OccupancyGrid.from_density(self.sigma_bound(), c1, c2, skip_threshold, dilate=0, keep_largest=keep_largest,
                                                     min_voxels=min_voxels)
-
-    def _stored(self):
-        return self.coef
-
-    def half(self):
-        """this volume with `to_half(coef)`; a half volume is returned as it is"""
-        return self if self.coef.dtype == torch.float16 else BakedSHVolume(to_half(self.coef), self.c1, self.c2, self.skip_threshold)
-
-    def float(self):
-        """this volume widened to fp32 (exact); an fp32 volume is returned as it is"""
-        return self if self.coef.dtype == torch.float32 else BakedSHVolume(self.coef.float(), self.c1, self.c2, self.skip_threshold)
 
     def sigma_bound(self):
         """(nx,ny,nz) fp32: s_0 + (1 + 2^-16) sum_{k>=1} m_k |s_k|, in fp64 from the stored coefficients (fp16 ones widened: the
@@ -392,48 +435,9 @@ class BakedSHVolume(_Baked):
         A network that takes no view directions is baked at degree 0, whatever was asked, with a warning.
         Memory: 64 / 144 bytes per point at degree 1 / 2 (302 MB at 128^3, degree 2); half of it with dtype=torch.float16, which
         bakes and accumulates in fp32 exactly as above and then applies `to_half` (the fp32 tensor exists during the bake)."""
-        from .. import ops
-        what = "BakedSHVolume.from_model"
-        _storage_dtype(what, dtype)
-        if int(getattr(net, "num_objs", 1) or 1) > 1:
-            raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
-        reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
-        degree = int(degree)
-        P = cls.projection(n_dirs, degree)  # (the degree and n_dirs checks)
-        use_viewdirs = bool(getattr(net, "use_viewdirs", False))
-        if not use_viewdirs and degree > 0:
-            warnings.warn(f"{what}: the network takes no view directions; baking at degree 0")
-            degree = 0
-        device = next(net.parameters()).device
-        if use_viewdirs:
-            dirs, P = cls.directions(n_dirs).to(device), P.float().to(device)
-        else:
-            dirs, P = None, torch.ones((1, 1), device=device)  # one pass: its output is the DC part
-        nb = (degree + 1) ** 2
-        if coarse is None:
-            coarse = getattr(net, "mlp_fine", None) is None
-        chunk = max(2, int(eval_batch_size) // 2 * 2)
-        total = reso[0] * reso[1] * reso[2]
-        is_train = bool(getattr(net, "training", False))
-        if hasattr(net, "eval"):
-            net.eval()
-        try:
-            with torch.no_grad():
-                coef = torch.zeros((total, nb, 4), dtype=torch.float32, device=device)
-                for first in range(0, total, chunk):
-                    count = min(chunk, total - first)
-                    pnts, _ = ops.gen_grid_points(c1, c2, reso, first, count, device=device, viewdirs=False)
-                    part = coef[first:first + count]
-                    for m in range(P.shape[1]):
-                        vd = dirs[m].expand(count, 3).contiguous()[None] if use_viewdirs else None
-                        out = net(pnts[None], coarse=bool(coarse), viewdirs=vd).reshape(count, -1)[:, :4]
-                        part += out[:, None, :] * P[:nb, m][None, :, None]  # the product, then the sum: two roundings, in the order of m
-        finally:
-            if is_train:
-                net.train()
-        if dtype == torch.float16:
-            coef = to_half(coef)
-        return cls(coef.view(*reso, nb, 4), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
+        coef, (reso, c1, c2), _ = _bake("BakedSHVolume.from_model", net, c1, c2, reso, dtype, coarse, eval_batch_size, degree=int(degree),
+                                        n_dirs=n_dirs)
+        return cls(coef.view(*reso, *coef.shape[1:]), c1, c2, skip_threshold, keep_largest=keep_largest, min_voxels=min_voxels)
 
     def at_direction(self, d):
         """The RGBA volume "this object seen from direction d" (a 3-vector of any length): per grid point coef_0 Y_0 + coef_1 Y_1
@@ -455,37 +459,10 @@ class BakedSHVolume(_Baked):
             v[..., :3] = torch.where(v[..., :3] > 1, one[..., :3], v[..., :3])
         return BakedVolume(v, self.c1, self.c2, self.skip_threshold)
 
-    def _march_rays(self, rays, step, bits, white_bkgd, terminate):
-        from .. import ops
-        if self.coef.dtype == torch.float16:
-            return ops.baked_half_render(rays, self.coef, self.degree, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
-                                         terminate=terminate)
-        return ops.baked_sh_render(rays, self.coef, self.degree, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd,
-                                   terminate=terminate)
-
-    def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
-        from .. import ops
-        if self.coef.dtype == torch.float16:
-            return ops.baked_half_render_views(poses, W, H, focal, c, z_near, z_far, self.coef, self.degree, self.reso, self.c1, self.c2,
-                                               step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
-        return ops.baked_sh_render_views(poses, W, H, focal, c, z_near, z_far, self.coef, self.degree, self.reso, self.c1, self.c2, step,
-                                         bits=bits, white_bkgd=white_bkgd, terminate=terminate)
-
     def sparse(self, occupancy=None):
         """BakedVolume.sparse for the coefficient volume: the kept points' (B,4) coefficients; `sparse().render(...)` equals
         `render(..., skip=True)` bit for bit"""
         return _sparse_of(self, self.coef.view(-1, *self.coef.shape[3:]), occupancy, "BakedSHVolume.sparse")
-
-    def state_dict(self):
-        """the coefficients (the degree follows from their shape), the geometry and the skip threshold; the skip grid is rebuilt on load"""
-        return {"coef": self.coef, "c1": torch.tensor(self.c1, dtype=torch.float64), "c2": torch.tensor(self.c2, dtype=torch.float64),
-                "skip_threshold": torch.tensor(self.skip_threshold, dtype=torch.float64)}
-
-    @classmethod
-    def from_state_dict(cls, state, device=None):
-        """:param device where to put the volume; None: where state["coef"] lives"""
-        coef = state["coef"] if device is None else state["coef"].to(device)
-        return cls(coef, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
 
 
 # ---------------------------------------------------------------- sparse volumes: only the rows that occupied cells read
@@ -518,6 +495,8 @@ class SparseBakedVolume(_Baked):
     `render` / `render_views` give the bytes of the dense volume's march with `occupancy.bits`; `from_model` bakes the kept points
     alone and gives the dense bake's rows bit for bit.  Memory: `nbytes` = rows + 4 bytes per grid point (index) + the bitfield."""
 
+    _stored_name = "rows"
+
     def __init__(self, rows, occupancy, index=None, ids=None):
         from .. import _lib, ops
         if not isinstance(rows, torch.Tensor) or rows.dim() not in (2, 3) or rows.shape[-1] != 4 \
@@ -544,24 +523,12 @@ class SparseBakedVolume(_Baked):
     def n_rows(self):
         return self.rows.shape[0]
 
-    def _stored(self):
-        return self.rows
-
     @property
     def nbytes(self):
         return self.rows.numel() * self.rows.element_size() + 4 * (self.index.numel() + self.occupancy.bits.numel())
 
-    def half(self):
-        """this volume with `to_half(rows)`; index, ids and occupancy are shared.  A half volume is returned as it is"""
-        if self.rows.dtype == torch.float16:
-            return self
-        return SparseBakedVolume(to_half(self.rows), self.occupancy, index=self.index, ids=self.ids)
-
-    def float(self):
-        """this volume with the rows widened to fp32 (exact); index, ids and occupancy are shared.  An fp32 volume is returned as it is"""
-        if self.rows.dtype == torch.float32:
-            return self
-        return SparseBakedVolume(self.rows.float(), self.occupancy, index=self.index, ids=self.ids)
+    def _around(self, rows):
+        return type(self)(rows, self.occupancy, index=self.index, ids=self.ids)
 
     @classmethod
     def from_model(cls, net, c1, c2, reso, occupancy, degree=None, n_dirs=32, viewdirs="origin", coarse=None, eval_batch_size=100000,
@@ -575,96 +542,14 @@ class SparseBakedVolume(_Baked):
         its own parity (profiles/occupancy_notes.md).  With occupancy = OccupancyGrid.from_model(net, c1, c2, reso, threshold,
         dilate=1) the result is the dense bake with nothing in the cells the grid calls empty.  A non-finite output raises ValueError.
         dtype=torch.float16: the fp32 bake, then `to_half` on the rows."""
-        from .. import ops
-        what = "SparseBakedVolume.from_model"
-        _storage_dtype(what, dtype)
-        if int(getattr(net, "num_objs", 1) or 1) > 1:
-            raise ValueError(f"{what}: the network encoded {int(net.num_objs)} objects; encode one object")
-        reso, c1, c2, _ = _check_geometry(reso, c1, c2, 0)
-        _same_grid(what, occupancy, reso, c1, c2)
-        use_viewdirs = bool(getattr(net, "use_viewdirs", False))
-        device = next(net.parameters()).device
-        if occupancy.bits.device != device:
-            raise ValueError(f"{what}: the occupancy grid lives on {occupancy.bits.device}, the network on {device}")
-        origin, const_dir, dirs, P = True, None, None, None
-        if degree is None:
-            origin = isinstance(viewdirs, str)
-            if origin and viewdirs != "origin":
-                raise ValueError(f"{what}: viewdirs must be 'origin' or a 3-vector, got {viewdirs!r}")
-            if not origin:
-                const_dir = torch.as_tensor(viewdirs, dtype=torch.float32).flatten()
-                if const_dir.numel() != 3 or not bool(torch.isfinite(const_dir).all()) or float(const_dir.norm()) == 0.0:
-                    raise ValueError(f"{what}: a constant view direction must be a finite non-zero 3-vector")
-                const_dir = (const_dir / const_dir.norm()).to(device)
-            if use_viewdirs and origin:
-                warnings.warn("Running marching cubes with fake view dirs (pointing to origin), output may be invalid")
-        else:
-            degree = int(degree)
-            P = BakedSHVolume.projection(n_dirs, degree)  # (the degree and n_dirs checks)
-            if not use_viewdirs and degree > 0:
-                warnings.warn(f"{what}: the network takes no view directions; baking at degree 0")
-                degree = 0
-            if use_viewdirs:
-                dirs, P = BakedSHVolume.directions(n_dirs).to(device), P.float().to(device)
-            else:
-                P = torch.ones((1, 1), device=device)  # one pass: its output is the DC part
-        nb = None if degree is None else (degree + 1) ** 2
-        if coarse is None:
-            coarse = getattr(net, "mlp_fine", None) is None
-        chunk = max(2, int(eval_batch_size) // 2 * 2)
-        index, ids = ops.sparse_points(occupancy.bits, reso)
-        total = ids.shape[0]
-        is_train = bool(getattr(net, "training", False))
-        if hasattr(net, "eval"):
-            net.eval()
-        try:
-            with torch.no_grad():
-                if degree is None:
-                    rows = torch.empty((total, 4), dtype=torch.float32, device=device)
-                else:
-                    rows = torch.zeros((total, nb, 4), dtype=torch.float32, device=device)
-                for first in range(0, total, chunk):
-                    count = min(chunk, total - first)
-                    pnts, vd = ops.gen_grid_points_at(c1, c2, reso, ids[first:first + count],
-                                                      viewdirs=degree is None and use_viewdirs and origin)
-                    if degree is None:
-                        if use_viewdirs and not origin:
-                            vd = const_dir.expand(count, 3).contiguous()
-                        out = net(pnts[None], coarse=bool(coarse), viewdirs=vd[None] if use_viewdirs else None)
-                        rows[first:first + count] = out.reshape(count, -1)[:, :4]
-                        continue
-                    part = rows[first:first + count]
-                    for m in range(P.shape[1]):
-                        vd = dirs[m].expand(count, 3).contiguous()[None] if use_viewdirs else None
-                        out = net(pnts[None], coarse=bool(coarse), viewdirs=vd).reshape(count, -1)[:, :4]
-                        part += out[:, None, :] * P[:nb, m][None, :, None]  # the product, then the sum: two roundings, in the order of m
-        finally:
-            if is_train:
-                net.train()
-        if dtype == torch.float16:
-            rows = to_half(rows)
+        rows, _, (index, ids) = _bake("SparseBakedVolume.from_model", net, c1, c2, reso, dtype, coarse, eval_batch_size, sparse=True,
+                                      occupancy=occupancy, degree=degree, n_dirs=n_dirs, viewdirs=viewdirs)
         return cls(rows, occupancy, index=index, ids=ids)
 
     def _march_args(self, step, terminate, skip):
         if not skip:
             raise ValueError("SparseBakedVolume: skip=False is not available (a sparse volume holds nothing to march unskipped)")
         return super()._march_args(step, terminate, True)
-
-    def _march_rays(self, rays, step, bits, white_bkgd, terminate):
-        from .. import ops
-        if self.rows.dtype == torch.float16:
-            return ops.baked_sparse_half_render(rays, self.rows, self.degree, self.index, bits, self.reso, self.c1, self.c2, step,
-                                                white_bkgd=white_bkgd, terminate=terminate)
-        return ops.baked_sparse_render(rays, self.rows, self.degree, self.index, bits, self.reso, self.c1, self.c2, step,
-                                       white_bkgd=white_bkgd, terminate=terminate)
-
-    def _march_views(self, poses, W, H, focal, c, z_near, z_far, step, bits, white_bkgd, terminate):
-        from .. import ops
-        if self.rows.dtype == torch.float16:
-            return ops.baked_sparse_half_render_views(poses, W, H, focal, c, z_near, z_far, self.rows, self.degree, self.index, bits,
-                                                      self.reso, self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
-        return ops.baked_sparse_render_views(poses, W, H, focal, c, z_near, z_far, self.rows, self.degree, self.index, bits, self.reso,
-                                             self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
 
     def to_dense(self):
         """(nx,ny,nz,4) or (nx,ny,nz,B,4): the rows at their grid points, zeros at the dropped ones -- marched with `occupancy.bits` it
