@@ -1129,6 +1129,53 @@ int pnr_baked_sparse_half_render_views(const float *poses /*(NV,4,4)*/, int NV, 
                                        int white_bkgd, float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha,
                                        void *stream);
 
+/* Gradients of the baked march with respect to the STORED VALUES (added within ABI rev 12 as well): what lets a caller fit a
+ * volume to images -- distil the network's renders past the point-sample bake, or refine per scene -- instead of only baking it.
+ * pnr_baked_backward_rays / pnr_baked_backward_views are the backward of every fp32 march above: `stored` is
+ *     degree -1: the RGBA volume (nx,ny,nz,4);   degree 0, 1, 2: the coefficient volume (nx,ny,nz,B,4), B = (degree+1)^2;
+ *     index == NULL: that dense array, and M is not looked at;
+ *     index != NULL: the M kept rows (M,4) / (M,B,4) of pnr_baked_sparse_render_*, and bits are then mandatory.
+ * d_rgb (R,3), d_depth (R), d_alpha (R): the upstream gradients dL/d rgb, dL/d depth, dL/d alpha of the march's three outputs;
+ *   each may be NULL and is then read as zeros.  A ray whose upstream gradients are all exactly zero is not walked.
+ * d_stored: fp32, the shape of `stored`.  The entry ADDS dL/d stored into it (fp32 atomicAdd on global memory, exact zeros are
+ *   skipped): the caller zeroes it before the first call, and calls on several batches of rays accumulate.  Only elements that a
+ *   sample of the march read are touched.
+ * The samples are EXACTLY the forward's: the kernels call the same device functions for the inside-the-box test, the cell, the
+ *   skip-bit test, the sparse row lookup and the blend (and count the samples with the same five lines), and with terminate > 0 the backward first walks the
+ *   chunks in the forward's direction with the forward's operations and stops after the chunk the forward stopped after.
+ *   With w_i = a_i T_i, T_i = prod_{j<i} (1 - a_j + 1e-10), a_i = 1 - exp(-step sigma_i):
+ *     g_i = d_rgb . c_i + d_depth t_i + d_alpha - [white_bkgd] (d_rgb.r + d_rgb.g + d_rgb.b)
+ *     dL/da_i = T_i (g_i - S_i),  S_i = g_{i+1} a_{i+1} + (1 - a_{i+1} + 1e-10) S_{i+1}  (S of the last sample: 0)
+ *     dL/dsigma_i = dL/da_i step exp(-step sigma_i),   dL/dc_i = w_i d_rgb
+ *   S is carried from the last chunk of 64 samples to the first by a reverse scan of these affine maps: it is never formed as a
+ *   difference of sums and nothing is divided by 1 - a_j, so a sample with a_i = 1 in fp32 keeps the gradients on both sides of it
+ *   finite and accurate.  Through the blend: corner (ix,iy,iz) of the sample's cell gets the product over the axes of f or 1 - f
+ *   (the derivative of the nested a + f (b - a)).  Through a view-dependent corner: coefficient k gets that times Y_k (Y_0 = 1)
+ *   times the derivative of the clamp, per channel, under torch.clamp's convention: 1 where the unclamped value lies in the closed
+ *   range ([0,1] for rgb, >= 0 for sigma), 0 outside and for a NaN.  The RGBA form has no clamp and no relu, as its forward.
+ * With bits, a sample in a cell whose bit is off contributes nothing and receives nothing: fitting against a skip grid freezes the
+ *   empty cells, and cannot grow density in them.  Without bits such a sample reaches sigma like any other.
+ * This is the one path of the baked family that is NOT bit-reproducible from run to run: the order in which the atomics of
+ *   different samples arrive varies, so a sum can differ in its last bits.
+ * No gradient is given with respect to rays, poses, step or the geometry.  fp32 storage only: there is no fp16 entry (fit the fp32
+ *   volume, round it afterwards).  No workspace.
+ * PNR_E_INVALID, before any HIP call, in the order and with the words of the march entries: a degree outside {-1, 0, 1, 2}; bad
+ *   sizes, a null or misaligned ray / pose array; M < 0 with an index; the grid and march settings; a null d_stored or stored, an
+ *   index with M > 0 and no bits ("null argument"); stored not 16-byte aligned; index, bits, d_rgb, d_depth, d_alpha or d_stored not
+ *   4-byte aligned.  R = 0 (NV = 0): no-op, PNR_OK. */
+int pnr_baked_backward_rays(const float *rays, long long R, const float *stored, long long M, int degree,
+                            const int32_t *index /*nullable: dense*/, const uint32_t *bits /*nullable when dense*/, int nx, int ny,
+                            int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                            const float *d_rgb /*(R,3), nullable*/, const float *d_depth /*(R), nullable*/,
+                            const float *d_alpha /*(R), nullable*/, float *d_stored /*fp32, the shape of stored; added into*/,
+                            void *stream);
+int pnr_baked_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                             float z_near, float z_far, const float *stored, long long M, int degree,
+                             const int32_t *index /*nullable: dense*/, const uint32_t *bits /*nullable when dense*/, int nx, int ny,
+                             int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                             const float *d_rgb /*(NV H W,3), nullable*/, const float *d_depth /*nullable*/,
+                             const float *d_alpha /*nullable*/, float *d_stored, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

@@ -545,3 +545,51 @@ def render_autograd(renderer, net, rays, noise, want_weights):
         for v in res.values():
             v.pop("weights")
     return res
+
+
+class _BakedMarchFunction(torch.autograd.Function):
+    """The baked-volume ray march, differentiable with respect to the STORED values (include/pixelnerf_hip.h, "Gradients of the
+    baked march").  forward IS the inference entry -- ops.baked_render / baked_sh_render / baked_sparse_render or their _views
+    forms, so its outputs are the bytes of util.bake's `render` -- and backward one pnr_baked_backward_* launch into a zeroed
+    buffer.  Nothing is saved but the stored tensor: the backward recomputes the samples.  No gradient reaches rays, poses, step
+    or the geometry."""
+
+    @staticmethod
+    def forward(ctx, stored, source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate):
+        ctx.set_materialize_grads(False)
+        views = "" if len(source) == 1 else "_views"
+        tail = dict(white_bkgd=white_bkgd, terminate=terminate)
+        if index is not None:
+            out = getattr(ops, "baked_sparse_render" + views)(*source, stored, degree, index, bits, reso, c1, c2, step, **tail)
+        elif degree is None or degree < 0:
+            out = getattr(ops, "baked_render" + views)(*source, stored, reso, c1, c2, step, bits=bits, **tail)
+        else:
+            out = getattr(ops, "baked_sh_render" + views)(*source, stored, degree, reso, c1, c2, step, bits=bits, **tail)
+        ctx.save_for_backward(stored)
+        ctx.march = (source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_alpha):
+        (stored,) = ctx.saved_tensors
+        source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate = ctx.march
+        if not ctx.needs_input_grad[0] or (d_rgb is None and d_depth is None and d_alpha is None):
+            return (None,) * 11
+        fp32 = lambda g: None if g is None else g.contiguous().float()
+        entry = ops.baked_render_backward if len(source) == 1 else ops.baked_render_views_backward
+        d_stored = entry(*source, stored.detach(), degree, reso, c1, c2, step, d_rgb=fp32(d_rgb), d_depth=fp32(d_depth),
+                         d_alpha=fp32(d_alpha), bits=bits, index=index, white_bkgd=white_bkgd, terminate=terminate)
+        return (d_stored,) + (None,) * 10
+
+
+def baked_march_autograd(stored, source, degree, reso, c1, c2, step, bits=None, index=None, white_bkgd=False, terminate=0.0):
+    """-> (rgb (R,3), depth (R,), alpha (R,)) of the baked march, differentiable with respect to `stored` (fp32: (nx,ny,nz,4) at
+    degree None, (nx,ny,nz,B,4) at degree 0, 1, 2, or with `index` the kept rows of a sparse volume).  source: (rays (R,8),) or the
+    camera (poses (NV,4,4), W, H, focal, c, z_near, z_far); neither may require grad."""
+    if not isinstance(stored, torch.Tensor) or stored.dtype != torch.float32:
+        raise TypeError("baked_march_autograd: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
+    if isinstance(source[0], torch.Tensor) and source[0].requires_grad:
+        raise ValueError(f"baked_march_autograd: no gradient is given with respect to {'rays' if len(source) == 1 else 'poses'}; "
+                         "detach them")
+    return _BakedMarchFunction.apply(stored, tuple(source), degree, index, bits, tuple(reso), tuple(c1), tuple(c2), float(step),
+                                     bool(white_bkgd), float(terminate))

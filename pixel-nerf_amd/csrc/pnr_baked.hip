@@ -16,6 +16,12 @@
 // Host: an entry builds its ray source (baked_explicit_rays / baked_camera_rays: the checks of the rays travel with them), says
 // what it was handed (BakedVolumeDesc: pointer, degree, storage, index + M, and the words of its refusals) and calls
 // baked_render, which holds every check, in one order for all ten entries, and dispatches layout, storage and kind once each.
+// Backward (pnr_baked_backward_rays / _views: dL/d stored, what fitting a volume needs).  The per-sample part of the march --
+// the point, its cell and fractions, whether it contributes, the rows of its corners, the blend, alpha -- lives in device functions
+// that baked_march and baked_march_bwd_kernel both call, so the backward's samples are the forward's (the sample count: the same
+// five lines, in place in the forward and as baked_sample_count in the backward).  The
+// backward is the ONE path here with atomics (fp32 atomicAdd into the caller's zeroed buffer): not bit-reproducible from run to run.
+// fp32 storage only; baked_check holds the checks of both directions.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -59,6 +65,14 @@ struct alignas(8) Half4 {
 __device__ __forceinline__ float4 baked_widen(const float4 v) { return v; }
 __device__ __forceinline__ float4 baked_widen(const Half4 v) { return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w); }
 
+// the backward's scatter: one fp32 atomic per channel of a stored (r,g,b,sigma), exact zeros skipped (most of a clamped corner)
+__device__ __forceinline__ void baked_add4(float *__restrict__ dst, const float4 g) {
+    if (g.x != 0.f) atomicAdd(dst + 0, g.x);
+    if (g.y != 0.f) atomicAdd(dst + 1, g.y);
+    if (g.z != 0.f) atomicAdd(dst + 2, g.z);
+    if (g.w != 0.f) atomicAdd(dst + 3, g.w);
+}
+
 // What the march reads at a corner of a cell; `data` is the stored array the entry was handed (the kernel sets it).  RGBA volume:
 // the (r,g,b,sigma) of the grid point.
 template <class Stored>
@@ -68,6 +82,10 @@ struct RgbaCornerOf {
     __device__ __forceinline__ void set_ray(const Ray8 &) {}
     static constexpr int PAIRS_IN_FLIGHT = 4;  // 8 loads: all in flight at once
     __device__ __forceinline__ float4 at(long long point) const { return baked_widen(data[point]); }
+    // backward: g = weight x dL/d(blended value) of this corner goes to the stored numbers as it is (no clamp, no relu)
+    __device__ __forceinline__ void scatter(float *__restrict__ d_stored, long long point, const float4 g) const {
+        baked_add4(d_stored + point * 4, g);
+    }
 };
 
 // fp32(sqrt 3), fp32(sqrt 15), fp32(sqrt 5 / 2), fp32(sqrt 15 / 2): rounded once from the fp64 values
@@ -95,7 +113,8 @@ struct ShCorner {
     // The half instantiations keep the same numbers: their in-flight loads hold half the registers, but the fp32 form measured
     // no gain from more pairs in flight (profiles/baked_notes.md); the outputs do not depend on the choice.
     static constexpr int PAIRS_IN_FLIGHT = B == 1 ? 4 : B == 4 ? 2 : 1;
-    __device__ __forceinline__ float4 at(long long point) const {
+    // the sum over the basis, before the clamps
+    __device__ __forceinline__ float4 unclamped(long long point) const {
         const Stored *c = data + point * B;
         float4 v = baked_widen(c[0]);
 #pragma unroll
@@ -103,10 +122,30 @@ struct ShCorner {
             const float4 a = baked_widen(c[k]);
             v.x = v.x + a.x * y[k - 1]; v.y = v.y + a.y * y[k - 1]; v.z = v.z + a.z * y[k - 1]; v.w = v.w + a.w * y[k - 1];
         }
+        return v;
+    }
+    __device__ __forceinline__ float4 at(long long point) const {
+        float4 v = unclamped(point);
         // per corner, before the blend; written so that a value inside the range keeps its bits (-0 included)
         v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w;
         v.x = v.x > 1.f ? 1.f : v.x; v.y = v.y > 1.f ? 1.f : v.y; v.z = v.z > 1.f ? 1.f : v.z;
         return v;
+    }
+    // backward: g = weight x dL/d(blended value) of this corner, through the clamps (torch.clamp's derivative: 1 where the
+    // unclamped value lies in the closed range, 0 outside and for a NaN) to coefficient k as g Y_k, Y_0 = 1.  The unclamped value
+    // is summed again from the coefficients the forward just read.
+    __device__ __forceinline__ void scatter(float *__restrict__ d_stored, long long point, float4 g) const {
+        const float4 v = unclamped(point);
+        g.x = v.x >= 0.f && v.x <= 1.f ? g.x : 0.f;
+        g.y = v.y >= 0.f && v.y <= 1.f ? g.y : 0.f;
+        g.z = v.z >= 0.f && v.z <= 1.f ? g.z : 0.f;
+        g.w = v.w >= 0.f ? g.w : 0.f;
+        if (g.x == 0.f && g.y == 0.f && g.z == 0.f && g.w == 0.f) return;
+        float *dst = d_stored + point * (B * 4);
+        baked_add4(dst, g);
+#pragma unroll
+        for (int k = 1; k < B; ++k)
+            baked_add4(dst + k * 4, make_float4(g.x * y[k - 1], g.y * y[k - 1], g.z * y[k - 1], g.w * y[k - 1]));
     }
 };
 
@@ -143,6 +182,145 @@ struct SparseRows {
     }
 };
 
+// ---- what the forward march and its backward share: the samples of a ray and the value at each.  Both kernels call these, so
+// the set of samples a gradient is given for is the set the forward composited, decided by the same operations in the same order.
+
+// the number of samples; a ray that cannot be sampled (near >= far, a non-finite component, more than 2^20 samples) keeps
+// n = 0, reads nothing and gets the background.  (The backward calls this; baked_march holds the same five lines in place.)
+__device__ __forceinline__ int baked_sample_count(const Ray8 &ray, float step) {
+    const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
+    bool ok = occ_finite(ray.near) && occ_finite(ray.far) && ray.near < ray.far;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok = ok && occ_finite(o[a]) && occ_finite(d[a]);
+    const float count = ceilf((ray.far - ray.near) / step);
+    return ok && count <= BAKED_MAX_SAMPLES ? (int)count : 0;  // (a NaN count compares false)
+}
+
+// sample i of a ray of n: its depth, whether it contributes (i < n, inside the box, its cell's bit on), its cell and its place in it
+struct BakedSample {
+    float t;
+    bool active;
+    int idx[3];
+    float f[3];
+};
+
+__device__ __forceinline__ BakedSample baked_sample(const Ray8 &ray, const BakedParams &q, int i, int n) {
+    const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
+    BakedSample s;
+    s.t = ray.near + ((float)i + 0.5f) * q.step;
+    s.active = i < n;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p = o[a] + s.t * d[a];                    // ray_point's operations (pnr_geom.h)
+        s.active = s.active && p >= q.g.c1[a] && p <= q.g.c2[a];  // (a NaN or infinite coordinate is outside)
+        const float u = (p - q.g.c1[a]) / q.g.h[a];
+        const float c = fminf(fmaxf(floorf(u), 0.f), (float)(q.g.n[a] - 2));  // (fmaxf drops a NaN: always a cell of the grid)
+        s.idx[a] = (int)c;
+        s.f[a] = fminf(fmaxf(u - c, 0.f), 1.f);
+    }
+    if (q.bits) {
+        const long long cy = q.g.n[2] - 1, cx = (long long)(q.g.n[1] - 1) * (q.g.n[2] - 1);  // cell strides of the bitfield
+        const long long cell = s.idx[0] * cx + s.idx[1] * cy + s.idx[2];
+        s.active = s.active && (q.bits[cell >> 5] >> (cell & 31) & 1u);
+    }
+    return s;
+}
+
+// where the eight corners of an active sample's cell lie: base point p000, the rows of its four pairs along z
+template <class Rows>
+struct BakedCell {
+    long long p000, sx, sy;  // point strides in float4s; z is the fastest axis
+    typename Rows::Pairs pr;
+    // the row of corner iz = 0 of pair j = 2 ix + iy (corner iz = 1 is the next row)
+    __device__ __forceinline__ long long row(const Rows &rows, int j) const {
+        return rows.row(pr, j, p000 + (j >> 1) * sx + (j & 1) * sy);
+    }
+};
+
+// false: the sample reads no row (a sparse volume that does not hold its corners) and keeps sigma = 0
+template <class Rows>
+__device__ __forceinline__ bool baked_find_cell(const BakedParams &q, const Rows &rows, const BakedSample &s, BakedCell<Rows> &cell) {
+    cell.sy = q.g.n[2];
+    cell.sx = (long long)q.g.n[1] * q.g.n[2];
+    cell.p000 = s.idx[0] * cell.sx + s.idx[1] * cell.sy + s.idx[2];
+    return rows.find(cell.p000, cell.sx, cell.sy, cell.pr);
+}
+
+// the trilinear blend of the cell's eight corner values
+template <class Corner, class Rows>
+__device__ __forceinline__ float4 baked_blend(const Corner &corner, const Rows &rows, const BakedCell<Rows> &cell, const float (&f)[3],
+                                              float4 cs /*zeros*/) {
+    const long long p000 = cell.p000, sx = cell.sx, sy = cell.sy;
+    const typename Rows::Pairs &pr = cell.pr;
+    // along z (a pair of corners is contiguous in memory: each pair is reduced before the next is needed), then y, then x
+    if constexpr (Corner::PAIRS_IN_FLIGHT == 4) {
+        const long long r00 = rows.row(pr, 0, p000), r01 = rows.row(pr, 1, p000 + sy), r10 = rows.row(pr, 2, p000 + sx),
+                        r11 = rows.row(pr, 3, p000 + sx + sy);
+        const float4 v00 = baked_lerp(corner.at(r00), corner.at(r00 + 1), f[2]);
+        const float4 v01 = baked_lerp(corner.at(r01), corner.at(r01 + 1), f[2]);
+        const float4 v10 = baked_lerp(corner.at(r10), corner.at(r10 + 1), f[2]);
+        const float4 v11 = baked_lerp(corner.at(r11), corner.at(r11 + 1), f[2]);
+        cs = baked_lerp(baked_lerp(v00, v01, f[1]), baked_lerp(v10, v11, f[1]), f[0]);
+    } else if constexpr (Corner::PAIRS_IN_FLIGHT == 2) {
+        // the same operations on the same values; a real loop over x, so that the pairs of x + 1 are asked for after
+        // those of x have been reduced (the gathers are independent: straight-line code issues them all first)
+        float4 vy[2];
+#pragma unroll 1
+        for (int ix = 0; ix < 2; ++ix) {
+            const long long p = p000 + ix * sx;
+            const long long r0 = rows.row(pr, 2 * ix, p);
+            const float4 v0 = baked_lerp(corner.at(r0), corner.at(r0 + 1), f[2]);
+            const long long r1 = rows.row(pr, 2 * ix + 1, p + sy);
+            const float4 v1 = baked_lerp(corner.at(r1), corner.at(r1 + 1), f[2]);
+            vy[1] = baked_lerp(v0, v1, f[1]);
+            if (ix == 0) vy[0] = vy[1];
+        }
+        cs = baked_lerp(vy[0], vy[1], f[0]);
+    } else {
+        // one pair at a time: j = 2 ix + iy
+        float4 vz = cs, vy[2] = {cs, cs};
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+            const long long p = rows.row(pr, j, p000 + (j >> 1) * sx + (j & 1) * sy);
+            const float4 v = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
+            if (j & 1) {
+                vy[1] = baked_lerp(vz, v, f[1]);
+                if (j == 1) vy[0] = vy[1];
+            }
+            vz = v;
+        }
+        cs = baked_lerp(vy[0], vy[1], f[0]);
+    }
+    return cs;
+}
+
+// the (r,g,b,sigma) of a sample: the blend where the sample is active and finds its rows, zeros elsewhere
+template <class Corner, class Rows>
+__device__ __forceinline__ float4 baked_value(const BakedParams &q, const Corner &corner, const Rows &rows, const BakedSample &s,
+                                              BakedCell<Rows> &cell, bool &found) {
+    float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
+    found = false;
+    if (s.active) {
+        if (baked_find_cell(q, rows, s, cell)) {
+            found = true;
+            cs = baked_blend(corner, rows, cell, s.f, cs);
+        }
+    }
+    return cs;
+}
+
+// alpha of a sample and what it leaves of the transmittance; ex = exp(-step sigma) is d alpha / d sigma / step
+struct BakedAlpha {
+    float ex, a, tfac;
+};
+__device__ __forceinline__ BakedAlpha baked_alpha(float step, float sigma) {
+    BakedAlpha r;
+    r.ex = expf(-(step * sigma));
+    r.a = 1.f - r.ex;            // nerf.py:228 with delta = step; exactly 0 for sigma == 0
+    r.tfac = 1.f - r.a + 1e-10f;  // :230-232; exactly 1 for a == 0
+    return r;
+}
+
 template <class Corner, class Rows>
 __device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const BakedParams &q, Corner corner, const Rows rows,
                                             float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
@@ -151,93 +329,29 @@ __device__ __forceinline__ void baked_march(const RaySrc &rs, long long R, const
     if (r >= R) return;  // the idle waves of the last workgroup (nothing below synchronises across waves)
     const Ray8 ray = load_ray(rs, r);
     corner.set_ray(ray);
+    // baked_sample_count's five lines, in place: as a call the degree-2 march took 19 % longer (2.61 against 2.21 ms at 128^3, the
+    // same instructions scheduled otherwise; profiles/baked_notes.md, "Backward and fitting").  Keep the two texts the same.
     const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
-    // the number of samples; a ray that cannot be sampled (near >= far, a non-finite component, more than 2^20 samples) keeps
-    // n = 0, reads nothing and gets the background
     bool ok = occ_finite(ray.near) && occ_finite(ray.far) && ray.near < ray.far;
 #pragma unroll
     for (int a = 0; a < 3; ++a) ok = ok && occ_finite(o[a]) && occ_finite(d[a]);
     const float count = ceilf((ray.far - ray.near) / q.step);
     const int n = ok && count <= BAKED_MAX_SAMPLES ? (int)count : 0;  // (a NaN count compares false)
-
-    const long long sy = q.g.n[2], sx = (long long)q.g.n[1] * q.g.n[2];  // point strides in float4s; z is the fastest axis
-    const long long cy = q.g.n[2] - 1, cx = (long long)(q.g.n[1] - 1) * (q.g.n[2] - 1);  // cell strides of the bitfield
     float carry = 1.f;  // transmittance in front of this chunk: prod_{j < c0} (1 - a_j + 1e-10)
     float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f, acc_w = 0.f;
     for (int c0 = 0; c0 < n; c0 += 64) {
-        const int i = c0 + lane;
-        const float t = ray.near + ((float)i + 0.5f) * q.step;
-        bool active = i < n;
-        int idx[3];
-        float f[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float p = o[a] + t * d[a];                    // ray_point's operations (pnr_geom.h)
-            active = active && p >= q.g.c1[a] && p <= q.g.c2[a];  // (a NaN or infinite coordinate is outside)
-            const float u = (p - q.g.c1[a]) / q.g.h[a];
-            const float c = fminf(fmaxf(floorf(u), 0.f), (float)(q.g.n[a] - 2));  // (fmaxf drops a NaN: always a cell of the grid)
-            idx[a] = (int)c;
-            f[a] = fminf(fmaxf(u - c, 0.f), 1.f);
-        }
-        if (q.bits) {
-            const long long cell = idx[0] * cx + idx[1] * cy + idx[2];
-            active = active && (q.bits[cell >> 5] >> (cell & 31) & 1u);
-        }
-        if (__ballot(active) == 0ull) continue;  // every factor of the chunk is exactly 1: the carry and the sums stay as they are
-        float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (active) {
-            const long long p000 = idx[0] * sx + idx[1] * sy + idx[2];
-            typename Rows::Pairs pr;
-            if (rows.find(p000, sx, sy, pr)) {
-                // along z (a pair of corners is contiguous in memory: each pair is reduced before the next is needed), then y, then x
-                if constexpr (Corner::PAIRS_IN_FLIGHT == 4) {
-                    const long long r00 = rows.row(pr, 0, p000), r01 = rows.row(pr, 1, p000 + sy), r10 = rows.row(pr, 2, p000 + sx),
-                                    r11 = rows.row(pr, 3, p000 + sx + sy);
-                    const float4 v00 = baked_lerp(corner.at(r00), corner.at(r00 + 1), f[2]);
-                    const float4 v01 = baked_lerp(corner.at(r01), corner.at(r01 + 1), f[2]);
-                    const float4 v10 = baked_lerp(corner.at(r10), corner.at(r10 + 1), f[2]);
-                    const float4 v11 = baked_lerp(corner.at(r11), corner.at(r11 + 1), f[2]);
-                    cs = baked_lerp(baked_lerp(v00, v01, f[1]), baked_lerp(v10, v11, f[1]), f[0]);
-                } else if constexpr (Corner::PAIRS_IN_FLIGHT == 2) {
-                    // the same operations on the same values; a real loop over x, so that the pairs of x + 1 are asked for after
-                    // those of x have been reduced (the gathers are independent: straight-line code issues them all first)
-                    float4 vy[2];
-#pragma unroll 1
-                    for (int ix = 0; ix < 2; ++ix) {
-                        const long long p = p000 + ix * sx;
-                        const long long r0 = rows.row(pr, 2 * ix, p);
-                        const float4 v0 = baked_lerp(corner.at(r0), corner.at(r0 + 1), f[2]);
-                        const long long r1 = rows.row(pr, 2 * ix + 1, p + sy);
-                        const float4 v1 = baked_lerp(corner.at(r1), corner.at(r1 + 1), f[2]);
-                        vy[1] = baked_lerp(v0, v1, f[1]);
-                        if (ix == 0) vy[0] = vy[1];
-                    }
-                    cs = baked_lerp(vy[0], vy[1], f[0]);
-                } else {
-                    // one pair at a time: j = 2 ix + iy
-                    float4 vz = cs, vy[2] = {cs, cs};
-#pragma unroll 1
-                    for (int j = 0; j < 4; ++j) {
-                        const long long p = rows.row(pr, j, p000 + (j >> 1) * sx + (j & 1) * sy);
-                        const float4 v = baked_lerp(corner.at(p), corner.at(p + 1), f[2]);
-                        if (j & 1) {
-                            vy[1] = baked_lerp(vz, v, f[1]);
-                            if (j == 1) vy[0] = vy[1];
-                        }
-                        vz = v;
-                    }
-                    cs = baked_lerp(vy[0], vy[1], f[0]);
-                }
-            }
-        }
-        const float a_i = 1.f - expf(-(q.step * cs.w));  // nerf.py:228 with delta = step; exactly 0 for sigma == 0
-        const float tfac = 1.f - a_i + 1e-10f;           // :230-232; exactly 1 for a_i == 0
-        const float incl = wave_scan_mul(tfac, lane);
+        const BakedSample s = baked_sample(ray, q, c0 + lane, n);
+        if (__ballot(s.active) == 0ull) continue;  // every factor of the chunk is exactly 1: the carry and the sums stay as they are
+        BakedCell<Rows> cell;
+        bool found;
+        const float4 cs = baked_value(q, corner, rows, s, cell, found);
+        const BakedAlpha al = baked_alpha(q.step, cs.w);
+        const float incl = wave_scan_mul(al.tfac, lane);
         float excl = __shfl_up(incl, 1, 64);
         if (lane == 0) excl = 1.f;
-        const float w = a_i * (carry * excl);  // :234-236
+        const float w = al.a * (carry * excl);  // :234-236
         acc_r += w * cs.x; acc_g += w * cs.y; acc_b += w * cs.z;
-        acc_d += w * t;
+        acc_d += w * s.t;
         acc_w += w;
         carry = carry * __shfl(incl, 63, 64);
         if (q.eps > 0.f && carry <= q.eps) break;  // wave-uniform; a NaN transmittance does not stop the ray
@@ -263,6 +377,103 @@ baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Rows
     Corner corner;
     corner.data = stored;
     baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
+}
+
+// ---- backward of the march with respect to the stored values (pnr_baked_backward_*; fp32 storage only).
+// w_i = a_i T_i, T_i = prod_{j<i} tf_j, tf_j = 1 - a_j + 1e-10, a_i = 1 - exp(-step sigma_i); with the upstream gradients of a ray
+//   g_i = dL/dw_i = d_rgb . c_i + d_depth t_i + d_alpha - [white] sum(d_rgb)
+//   dL/da_i = T_i (g_i - S_i),  S_i = sum_{j>i} g_j a_j prod_{i<k<j} tf_k = g_{i+1} a_{i+1} + tf_{i+1} S_{i+1}
+//   dL/dsigma_i = dL/da_i step exp(-step sigma_i),  dL/dc_i = w_i d_rgb
+// composite_bwd_kernel's walk (pnr_bwd.hip): the 64-sample chunks from the last to the first, per chunk a reverse wave scan of the
+// maps S -> g_j a_j + tf_j S carried across chunks -- the suffix is never a difference of sums and nothing is divided by tf -- and
+// T_i from the forward product scan, formed as the forward forms it.  A first walk in the forward's direction finds the chunk the
+// forward stopped after (terminate) and leaves the transmittance at the head of chunk c < 64 in lane c; the chunks beyond 4096
+// samples rebuild theirs from chunk 63's.  No workspace.
+// Then through the blend: corner (ix,iy,iz) of the cell gets the product of f or 1 - f per axis (the derivative of the nested
+// baked_lerps) times (dL/dc_i, dL/dsigma_i), and Corner::scatter adds it to the stored numbers with fp32 atomics.
+
+// prod of tf over chunk c (every lane), with the forward's operations
+template <class Corner, class Rows>
+__device__ __forceinline__ float baked_chunk_product(const Ray8 &ray, const BakedParams &q, const Corner &corner, const Rows &rows, int c,
+                                                     int n, int lane) {
+    const BakedSample s = baked_sample(ray, q, c * 64 + lane, n);
+    if (__ballot(s.active) == 0ull) return 1.f;
+    BakedCell<Rows> cell;
+    bool found;
+    const float4 cs = baked_value(q, corner, rows, s, cell, found);
+    return __shfl(wave_scan_mul(baked_alpha(q.step, cs.w).tfac, lane), 63, 64);
+}
+
+template <class Corner, class Rows>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_march_bwd_kernel(const RaySrc rs, long long R, const BakedParams q, const Rows rows, const typename Corner::stored_t *__restrict__ stored,
+                       const float *__restrict__ d_rgb, const float *__restrict__ d_depth, const float *__restrict__ d_alpha,
+                       float *__restrict__ d_stored) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * BAKED_WAVES + (threadIdx.x >> 6);
+    if (r >= R) return;
+    float3 drgb = make_float3(0.f, 0.f, 0.f);
+    if (d_rgb) drgb = make_float3(d_rgb[r * 3], d_rgb[r * 3 + 1], d_rgb[r * 3 + 2]);
+    const float ddepth = d_depth ? d_depth[r] : 0.f, dalpha = d_alpha ? d_alpha[r] : 0.f;
+    if (drgb.x == 0.f && drgb.y == 0.f && drgb.z == 0.f && ddepth == 0.f && dalpha == 0.f) return;  // nothing to send back
+    const float gwhite = q.white_bkgd ? (drgb.x + drgb.y + drgb.z) : 0.f;  // rgb += 1 - sum w
+    Corner corner;
+    corner.data = stored;
+    const Ray8 ray = load_ray(rs, r);
+    corner.set_ray(ray);
+    const int n = baked_sample_count(ray, q.step);
+    int nc = (n + 63) >> 6;
+
+    // the forward's walk: T at the head of chunk c < 64 into lane c, and the chunk it stopped after
+    float heads = 1.f, carry = 1.f;
+    for (int c = 0; c < nc; ++c) {
+        if (lane == c) heads = carry;
+        const BakedSample s = baked_sample(ray, q, c * 64 + lane, n);
+        if (__ballot(s.active) == 0ull) continue;
+        BakedCell<Rows> cell;
+        bool found;
+        const float4 cs = baked_value(q, corner, rows, s, cell, found);
+        carry = carry * __shfl(wave_scan_mul(baked_alpha(q.step, cs.w).tfac, lane), 63, 64);
+        if (q.eps > 0.f && carry <= q.eps) nc = c + 1;  // the forward's break, in its words
+    }
+
+    float S_in = 0.f;  // S of the chunk's last sample
+    for (int c = nc - 1; c >= 0; --c) {
+        const BakedSample s = baked_sample(ray, q, c * 64 + lane, n);
+        if (__ballot(s.active) == 0ull) continue;  // 64 identity maps: S stays, nothing to scatter
+        carry = __shfl(heads, c < 64 ? c : 63, 64);
+        for (int cc = 63; cc < c; ++cc) carry = carry * baked_chunk_product(ray, q, corner, rows, cc, n, lane);
+        BakedCell<Rows> cell;
+        bool found;
+        const float4 cs = baked_value(q, corner, rows, s, cell, found);
+        const BakedAlpha al = baked_alpha(q.step, cs.w);
+        const float incl = wave_scan_mul(al.tfac, lane);
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.f;
+        const float T = carry * excl;
+        const float w = al.a * T;
+        // a sample that is not active, or found no rows, has a = 0 and tf = 1: the identity map
+        const float g = found ? drgb.x * cs.x + drgb.y * cs.y + drgb.z * cs.z + ddepth * s.t + dalpha - gwhite : 0.f;
+        float m = found ? al.tfac : 1.f, b = found ? g * al.a : 0.f;
+        wave_rscan_affine(m, b, lane);
+        const float mn = __shfl_down(m, 1, 64), bn = __shfl_down(b, 1, 64);
+        const float S = lane == 63 ? S_in : bn + mn * S_in;
+        S_in = __shfl(b + m * S_in, 0, 64);  // S of sample 64 c - 1
+        if (found) {  // (no wave operation below: the lanes part here and meet again at the head of the loop)
+            const float da = T * (g - S);
+            const float4 dcs = make_float4(w * drgb.x, w * drgb.y, w * drgb.z, da * q.step * al.ex);
+#pragma unroll 1
+            for (int j = 0; j < 4; ++j) {  // pair j = 2 ix + iy
+                const long long row = cell.row(rows, j);
+                const float wxy = (j >> 1 ? s.f[0] : 1.f - s.f[0]) * (j & 1 ? s.f[1] : 1.f - s.f[1]);
+#pragma unroll
+                for (int iz = 0; iz < 2; ++iz) {
+                    const float wt = wxy * (iz ? s.f[2] : 1.f - s.f[2]);
+                    if (wt != 0.f) corner.scatter(d_stored, row + iz, make_float4(wt * dcs.x, wt * dcs.y, wt * dcs.z, wt * dcs.w));
+                }
+            }
+        }
+    }
 }
 #pragma clang fp contract(fast)
 
@@ -338,19 +549,32 @@ struct BakedType {
     using type = T;
 };
 
-// every check of every entry, in one order, then the launch
-static int baked_render(const char *entry, const BakedRays &rays, const BakedVolumeDesc &v, const BakedMarchArgs &a) {
+// what a backward entry takes next to the march arguments: the upstream gradients (each NULL: zeros) and the buffer it adds into
+struct BakedGrads {
+    const float *d_rgb, *d_depth, *d_alpha;
+    float *d_stored;
+};
+
+// ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
+static SparseRows baked_sparse_rows(const BakedVolumeDesc &v) {
+    return SparseRows{v.index, (int)(v.M - 2 < 0x7ffffffeLL ? v.M - 2 : 0x7ffffffeLL)};
+}
+
+// every check of every entry, forward (grads == NULL: a's rgb, depth and alpha are written) and backward, in one order.
+// -> PNR_OK with `blocks` workgroups to launch (0: no rays, nothing to do) and the march settings in q
+static int baked_check(const char *entry, const BakedRays &rays, const BakedVolumeDesc &v, const BakedMarchArgs &a, const BakedGrads *grads,
+                       BakedParams &q, long long &blocks) {
+    blocks = 0;
     if (v.degree < v.min_degree || v.degree > 2) return occ_fail(entry, v.degree_rule);
     if (rays.defect) return occ_fail(entry, rays.defect);
     if (v.sparse && v.M < 0) return occ_fail(entry, "bad sizes (M)");
     if (const char *why = occ_bad_dims(a.nx, a.ny, a.nz)) return occ_fail(entry, why);
-    BakedParams q;
     if (const char *why = occ_grid(a.nx, a.ny, a.nz, a.c1, a.c2, q.g)) return occ_fail(entry, why);
     if (!(a.step > 0.f) || !std::isfinite(a.step)) return occ_fail(entry, "step must be finite and > 0");
     if (!(a.terminate >= 0.f && a.terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
     const long long R = rays.R;
     if (R == 0) return PNR_OK;
-    if (!a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
+    if (grads ? !grads->d_stored : !a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
     if (v.sparse ? v.M > 0 && (!v.stored || !v.index || !a.bits) : !v.stored) return occ_fail(entry, "null argument");
     if (occ_misaligned16(v.stored)) {
         char why[40];
@@ -358,14 +582,54 @@ static int baked_render(const char *entry, const BakedRays &rays, const BakedVol
         return occ_fail(entry, why);
     }
     if (v.sparse && baked_misaligned4(v.index)) return occ_fail(entry, "index must be 4-byte aligned");
-    if (baked_misaligned4(a.bits) || baked_misaligned4(a.rgb) || baked_misaligned4(a.depth) || baked_misaligned4(a.alpha))
+    if (grads) {
+        if (baked_misaligned4(a.bits) || baked_misaligned4(grads->d_rgb) || baked_misaligned4(grads->d_depth) ||
+            baked_misaligned4(grads->d_alpha) || baked_misaligned4(grads->d_stored))
+            return occ_fail(entry, "bits, d_rgb, d_depth, d_alpha and d_stored must be 4-byte aligned");
+    } else if (baked_misaligned4(a.bits) || baked_misaligned4(a.rgb) || baked_misaligned4(a.depth) || baked_misaligned4(a.alpha)) {
         return occ_fail(entry, "bits, rgb, depth and alpha must be 4-byte aligned");
-    const long long blocks = (R + BAKED_WAVES - 1) / BAKED_WAVES;
+    }
+    blocks = (R + BAKED_WAVES - 1) / BAKED_WAVES;
     if (blocks > 0x7fffffffLL) return occ_fail(entry, "the number of rays exceeds the launch limit");
     q.bits = a.bits;
     q.step = a.step;
     q.eps = a.terminate;
     q.white_bkgd = a.white_bkgd;
+    return PNR_OK;
+}
+
+// The backward entries: fp32 storage, dense (index == NULL) or sparse rows, degree -1..2: 2 x 4 instantiations.
+static int baked_backward(const char *entry, const BakedRays &rays, const void *stored, long long M, int degree, const int32_t *index,
+                          const BakedMarchArgs &a, const BakedGrads &grads) {
+    const BakedVolumeDesc v = {stored, degree, false, index != nullptr, index, index ? M : 0, "stored", -1, DEGREE_HALF};
+    BakedParams q;
+    long long blocks;
+    if (const int rc = baked_check(entry, rays, v, a, &grads, q, blocks)) return rc;
+    if (blocks == 0) return PNR_OK;
+    const auto launch = [&](auto corner, auto rows) {
+        using Corner = typename decltype(corner)::type;
+        hipLaunchKernelGGL((baked_march_bwd_kernel<Corner, decltype(rows)>), dim3((unsigned)blocks), dim3(BAKED_WAVES * 64), 0,
+                           (hipStream_t)a.stream, rays.src, rays.R, q, rows, static_cast<const float4 *>(v.stored), grads.d_rgb,
+                           grads.d_depth, grads.d_alpha, grads.d_stored);
+    };
+    const auto by_kind = [&](auto rows) {
+        if (v.degree < 0) launch(BakedType<RgbaCornerOf<float4>>{}, rows);
+        else if (v.degree == 0) launch(BakedType<ShCorner<1, float4>>{}, rows);
+        else if (v.degree == 1) launch(BakedType<ShCorner<4, float4>>{}, rows);
+        else launch(BakedType<ShCorner<9, float4>>{}, rows);
+    };
+    if (v.sparse) by_kind(baked_sparse_rows(v));
+    else by_kind(DenseRows{});
+    return pnr_check_launch(entry);
+}
+
+// the forward entries: the checks, then the launch
+static int baked_render(const char *entry, const BakedRays &rays, const BakedVolumeDesc &v, const BakedMarchArgs &a) {
+    BakedParams q;
+    long long blocks;
+    if (const int rc = baked_check(entry, rays, v, a, nullptr, q, blocks)) return rc;
+    if (blocks == 0) return PNR_OK;
+    const long long R = rays.R;
     // layout, storage and kind, each decided once: 2 x 2 x 4 instantiations of the one kernel
     const auto launch = [&](auto corner, auto rows) {
         using Corner = typename decltype(corner)::type;
@@ -384,8 +648,7 @@ static int baked_render(const char *entry, const BakedRays &rays, const BakedVol
         if (v.half) by_kind(BakedType<Half4>{}, rows);
         else by_kind(BakedType<float4>{}, rows);
     };
-    // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
-    if (v.sparse) by_storage(SparseRows{v.index, (int)(v.M - 2 < 0x7ffffffeLL ? v.M - 2 : 0x7ffffffeLL)});
+    if (v.sparse) by_storage(baked_sparse_rows(v));
     else by_storage(DenseRows{});
     return pnr_check_launch(entry);
 }
@@ -523,4 +786,25 @@ extern "C" int pnr_baked_sparse_half_render_views(const float *poses, int NV, in
     return pnr::baked_render("pnr_baked_sparse_half_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
                              pnr::baked_sparse(rows, M, index, degree, true, pnr::DEGREE_HALF),
                              {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
+}
+
+// ---- gradients with respect to the stored values (fp32 storage; index == NULL: a dense volume, M is then not looked at)
+
+extern "C" int pnr_baked_backward_rays(const float *rays, long long R, const float *stored, long long M, int degree, const int32_t *index,
+                                       const uint32_t *bits, int nx, int ny, int nz, const float *c1, const float *c2, float step,
+                                       int white_bkgd, float terminate, const float *d_rgb, const float *d_depth, const float *d_alpha,
+                                       float *d_stored, void *stream) {
+    return pnr::baked_backward("pnr_baked_backward_rays", pnr::baked_explicit_rays(rays, R), stored, M, degree, index,
+                               {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, nullptr, nullptr, nullptr, stream},
+                               {d_rgb, d_depth, d_alpha, d_stored});
+}
+
+extern "C" int pnr_baked_backward_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
+                                        float z_far, const float *stored, long long M, int degree, const int32_t *index,
+                                        const uint32_t *bits, int nx, int ny, int nz, const float *c1, const float *c2, float step,
+                                        int white_bkgd, float terminate, const float *d_rgb, const float *d_depth, const float *d_alpha,
+                                        float *d_stored, void *stream) {
+    return pnr::baked_backward("pnr_baked_backward_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far), stored,
+                               M, degree, index, {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, nullptr, nullptr, nullptr, stream},
+                               {d_rgb, d_depth, d_alpha, d_stored});
 }

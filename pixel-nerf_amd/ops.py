@@ -1325,7 +1325,7 @@ def _baked_volume(what, stored, degree, reso, c1, c2, step, bits, terminate, *, 
     if takes_degree:
         degree = int(degree) if name == "coef" or degree is not None else -1
         if degree not in (0, 1, 2) and (degree != -1 or name == "coef"):
-            allowed = "0, 1 or 2" if name == "coef" else f"None / -1 (RGBA{' rows' if dtype == torch.float32 else ''}), 0, 1 or 2"
+            allowed = "0, 1 or 2" if name == "coef" else f"None / -1 (RGBA{' rows' if dtype == torch.float32 and name == 'rows' else ''}), 0, 1 or 2"
             raise ValueError(f"{what}: degree must be {allowed}, got {degree}")
         tail = (4,) if degree < 0 else ((degree + 1) ** 2, 4)
         lead = 1 if sparse else 3
@@ -1355,11 +1355,10 @@ def _image_size(what, width, height):
     return W, H
 
 
-def _baked_launch(entry, v, white_bkgd, rays=None, camera=None):
-    """March the checked volume `v` (_baked_volume) through the library entry `entry`, along `rays` (R,8) or over the pixels of
-    `camera` = (poses (NV,4,4), W, H, focal, c, z_near, z_far) -> (rgb (R,3), depth (R,), alpha (R,)) fp32, R = NV H W for a camera"""
-    lib = _lib.load()
-    what, name, stored, degree, dims, c1, c2, step, terminate, bits, index = v
+def _baked_source(v, rays=None, camera=None):
+    """the head of a baked entry's argument list: `rays` (R,8), or `camera` = (poses (NV,4,4), W, H, focal, c, z_near, z_far), checked
+    against the volume `v` (_baked_volume) -> (args, R, device, the contiguous rays / poses: keep it alive over the call)"""
+    what, name, stored = v[:3]
     if camera is None:
         source = _f32(rays, "rays", (None, 8))
         R = source.shape[0]
@@ -1378,6 +1377,15 @@ def _baked_launch(entry, v, white_bkgd, rays=None, camera=None):
         fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
         cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
         args = [_p(source), source.shape[0], W, H, fx, fy, cx, cy, float(z_near), float(z_far)]
+    return args, R, dev, source
+
+
+def _baked_launch(entry, v, white_bkgd, rays=None, camera=None):
+    """March the checked volume `v` (_baked_volume) through the library entry `entry`, along `rays` (R,8) or over the pixels of
+    `camera` = (poses (NV,4,4), W, H, focal, c, z_near, z_far) -> (rgb (R,3), depth (R,), alpha (R,)) fp32, R = NV H W for a camera"""
+    lib = _lib.load()
+    what, name, stored, degree, dims, c1, c2, step, terminate, bits, index = v
+    args, R, dev, source = _baked_source(v, rays, camera)  # (source: kept alive over the call)
     rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
     depth = torch.empty((R,), dtype=torch.float32, device=dev)
     alpha = torch.empty((R,), dtype=torch.float32, device=dev)
@@ -1545,6 +1553,68 @@ def baked_sparse_half_render_views(poses, width, height, focal, c, z_near, z_far
     v = _baked_volume("baked_sparse_half_render_views", rows, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16,
                       name="rows", index=index, sparse=True)
     return _baked_launch("pnr_baked_sparse_half_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
+
+
+# ---- gradients of the baked march with respect to the stored values (include/pixelnerf_hip.h, "Gradients of the baked march")
+
+def _baked_backward(what, entry, stored, degree, reso, c1, c2, step, bits, index, white_bkgd, terminate, d_rgb, d_depth, d_alpha, out,
+                    rays=None, camera=None):
+    """checks before any device work, then pnr_baked_backward_rays / _views INTO `out` (None: a fresh zeroed buffer) -> out"""
+    lib = _lib.load()
+    if isinstance(stored, torch.Tensor) and stored.dtype == torch.float16:
+        raise TypeError(f"{what}: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
+    source = rays if camera is None else camera[0]
+    if isinstance(source, torch.Tensor) and source.requires_grad:
+        raise ValueError(f"{what}: no gradient is given with respect to {'rays' if camera is None else 'poses'}; detach them")
+    sparse = index is not None
+    v = _baked_volume(what, stored, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float32,
+                      name="rows" if sparse else "stored", index=index, sparse=sparse)
+    _, _, stored, degree, dims, c1, c2, step, terminate, bits, index = v
+    args, R, dev, source = _baked_source(v, rays, camera)  # (source: kept alive over the call)
+    grads = []
+    for g, name, shape in ((d_rgb, "d_rgb", (R, 3)), (d_depth, "d_depth", (R,)), (d_alpha, "d_alpha", (R,))):
+        g = None if g is None else _f32(g.detach() if isinstance(g, torch.Tensor) else g, name, shape)
+        if g is not None and g.device != dev:
+            raise ValueError(f"{what}: {name} lives on {g.device}, the {'rays' if camera is None else 'poses'} on {dev}")
+        grads.append(g)
+    if out is None:
+        out = torch.zeros(stored.shape, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != stored.shape or out.device != dev \
+            or not out.is_contiguous() or out.requires_grad:
+        raise ValueError(f"{what}: out must be a contiguous float32 tensor of shape {tuple(stored.shape)} on {dev} that does not require "
+                         "grad (it is added into)")
+    lo, hi = _float3_pair(c1, c2)
+    M = stored.shape[0] if sparse else 0
+    args += (_p(stored) if stored.numel() else None, M, degree, None if index is None else _p(index.contiguous()),
+             None if bits is None else _p(bits.contiguous()), dims[0], dims[1], dims[2], lo, hi, step, int(bool(white_bkgd)), terminate,
+             _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(out) if out.numel() else None)
+    if R and out.numel():
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    return out
+
+
+def baked_render_backward(rays, stored, degree, reso, c1, c2, step, d_rgb=None, d_depth=None, d_alpha=None, bits=None, index=None,
+                          white_bkgd=False, terminate=0.0, out=None):
+    """The gradient of baked_render / baked_sh_render / baked_sparse_render with respect to the stored values
+    (pnr_baked_backward_rays): stored fp32 (nx,ny,nz,4) (degree None / -1) or (nx,ny,nz,B,4) (degree 0, 1, 2), or with `index` the
+    kept rows (M,4) / (M,B,4) (bits are then mandatory); d_rgb (R,3), d_depth (R,), d_alpha (R,) the upstream gradients of the
+    march's outputs, None = zeros.  -> dL/d stored, fp32, the shape of stored.  `out`: a buffer the gradient is ADDED into (the
+    caller zeroes it before the first batch); None: a fresh one.  The samples are exactly the forward's with the same rays, bits,
+    step and terminate; with bits the cells whose bit is off receive nothing.  Not bit-reproducible from run to run (fp32 atomics).
+    No gradient with respect to rays, step or the geometry: rays that require grad are refused.  An fp16 volume is refused."""
+    return _baked_backward("baked_render_backward", "pnr_baked_backward_rays", stored, degree, reso, c1, c2, step, bits, index, white_bkgd,
+                           terminate, d_rgb, d_depth, d_alpha, out, rays=rays)
+
+
+def baked_render_views_backward(poses, width, height, focal, c, z_near, z_far, stored, degree, reso, c1, c2, step, d_rgb=None,
+                                d_depth=None, d_alpha=None, bits=None, index=None, white_bkgd=False, terminate=0.0, out=None):
+    """baked_render_backward over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c)
+    (pnr_baked_backward_views): the rays are regenerated in the kernel, d_rgb (NV*H*W,3), d_depth and d_alpha (NV*H*W,) ordered
+    (view, row, column) as baked_render_views returns its outputs.  -> dL/d stored."""
+    W, H = _image_size("baked_render_views_backward", width, height)
+    return _baked_backward("baked_render_views_backward", "pnr_baked_backward_views", stored, degree, reso, c1, c2, step, bits, index,
+                           white_bkgd, terminate, d_rgb, d_depth, d_alpha, out, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):

@@ -162,6 +162,12 @@ class _Baked:
         """this volume widened to fp32 (exact; a sparse volume shares index, ids and occupancy); an fp32 volume is returned as it is"""
         return self if self.dtype == torch.float32 else self._around(self._stored().float())
 
+    def trainable(self):
+        """-> TrainableBaked: an nn.Module whose one nn.Parameter is a copy of this volume's fp32 stored tensor; `forward(rays, ...)`
+        and `forward_views(...)` render with gradients attached, `.volume()` gives the fitted volume back (`fit` is the loop around
+        it).  An fp16 volume is refused: fit in fp32 and call `half()` afterwards."""
+        return TrainableBaked(self)
+
     def state_dict(self):
         """the stored tensor under its name (a degree follows from its shape), the geometry and the skip threshold; the skip grid is
         rebuilt on load"""
@@ -575,3 +581,101 @@ class SparseBakedVolume(_Baked):
         n_occupied = table[bits.view(torch.uint8).long()].sum().to(torch.int32)
         occupancy = OccupancyGrid(bits, state["reso"].tolist(), state["c1"].tolist(), state["c2"].tolist(), float("nan"), 0, n_occupied)
         return cls(rows, occupancy)
+
+
+# ---------------------------------------------------------------- fitting: gradients with respect to the stored values
+
+_FP32_ONLY = "gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards"
+
+
+class TrainableBaked(torch.nn.Module):
+    """`volume.trainable()`: the fp32 stored tensor of a BakedVolume, BakedSHVolume or SparseBakedVolume as this module's one
+    nn.Parameter (`stored`, a copy: the volume itself never changes), marched by the inference entries with gradients attached
+    (autograd.baked_march_autograd: forward = the bytes of `volume.render`, backward = pnr_baked_backward_*).  Gradients reach the
+    stored values only -- rays and poses that require grad are refused -- and are not bit-reproducible from run to run (fp32
+    atomics).  An fp16 volume is refused: fit in fp32 and call `half()` afterwards.
+    `skip=True` marches against the skip grid of the volume `trainable()` was called on, as it was then: the cells it calls empty
+    receive no gradient and stay as they are -- fitting with skip=True FREEZES the empty cells; with skip=False (the default) every
+    cell a ray crosses can change.  A sparse volume holds nothing else, so it always marches against its grid."""
+
+    def __init__(self, volume):
+        super().__init__()
+        if not isinstance(volume, _Baked):
+            raise TypeError(f"TrainableBaked: expected a baked volume, got {type(volume).__name__}")
+        if volume.dtype != torch.float32:
+            raise TypeError(f"{type(volume).__name__}.trainable: {_FP32_ONLY}")
+        self._source = volume
+        self.stored = torch.nn.Parameter(volume._stored().clone())
+
+    def _march(self, source, step, white_bkgd, terminate, skip):
+        from .. import autograd
+        v = self._source
+        sparse = v._stored_name == "rows"
+        step, terminate, bits = _Baked._march_args(v, step, terminate, skip or sparse)
+        return autograd.baked_march_autograd(self.stored, source, v.degree, v.reso, v.c1, v.c2, step, bits=bits,
+                                             index=v.index if sparse else None, white_bkgd=white_bkgd, terminate=terminate)
+
+    def forward(self, rays, step=None, white_bkgd=False, terminate=None, skip=False):
+        """rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)) as `render`, differentiable with respect to `stored`"""
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError("TrainableBaked.forward: rays must be (...,8)")
+        lead = tuple(rays.shape[:-1])
+        rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), step, white_bkgd, terminate, skip)
+        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+    def forward_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, white_bkgd=False, terminate=None, skip=False):
+        """every pixel of the views, the rays regenerated in the kernel (as `render_views`, without its epilogue)
+        -> DotMap(rgb (NVt,H,W,3), depth (NVt,H,W), alpha (NVt,H,W)), differentiable with respect to `stored`"""
+        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
+            raise ValueError("TrainableBaked.forward_views: poses_c2w must be (NVt,4,4)")
+        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
+        if torch.is_tensor(focal):
+            focal = focal.flatten().tolist()
+            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
+        if torch.is_tensor(c):
+            c = c.flatten().tolist()
+        rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, white_bkgd, terminate, skip)
+        return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
+
+    def volume(self):
+        """a fresh volume of the current values: checked as its constructor checks (a non-finite value raises ValueError) and with
+        its skip grid rebuilt from them (a sparse volume keeps its occupancy grid, index and ids: its kept set does not grow)"""
+        return self._source._around(self.stored.detach().clone())
+
+
+def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=None, white_bkgd=False, terminate=None, skip=False):
+    """Fit a baked volume to colours: Adam on `volume.trainable()` over `steps` batches of `batch` rays drawn with replacement from
+    rays (...,8) by a CPU torch.Generator seeded with `seed`, loss = mean((rgb - target_rgb)^2) over the batch.  After every step
+    an RGBA volume (BakedVolume, RGBA rows) is projected back onto what it stores: rgb into [0,1], sigma >= 0; a coefficient volume
+    is left alone (its clamps are part of the march).  step, white_bkgd, terminate, skip: as TrainableBaked.forward (skip=True
+    freezes the cells the volume's skip grid calls empty).
+    -> (the fitted volume -- a new one, `volume` is unchanged --, losses: the `steps` batch losses as floats, read once at the end)"""
+    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+        raise ValueError("fit: rays must be (...,8)")
+    if not isinstance(target_rgb, torch.Tensor) or tuple(target_rgb.shape) != tuple(rays.shape[:-1]) + (3,):
+        raise ValueError(f"fit: target_rgb must be {tuple(rays.shape[:-1]) + (3,)}, got "
+                         f"{tuple(target_rgb.shape) if isinstance(target_rgb, torch.Tensor) else type(target_rgb).__name__}")
+    steps, batch = int(steps), int(batch)
+    if steps < 0 or batch < 1:
+        raise ValueError(f"fit: steps must be >= 0 and batch >= 1, got {steps}, {batch}")
+    module = volume.trainable()
+    rays, target = rays.detach().reshape(-1, 8).float(), target_rgb.detach().reshape(-1, 3).float()
+    R = rays.shape[0]
+    if R == 0:
+        raise ValueError("fit: no rays")
+    optimiser = torch.optim.Adam(module.parameters(), lr=float(lr))
+    gen = torch.Generator().manual_seed(int(seed))
+    losses = []
+    for _ in range(steps):
+        ids = torch.randint(0, R, (min(batch, R),), generator=gen).to(rays.device)
+        out = module(rays[ids], step=step, white_bkgd=white_bkgd, terminate=terminate, skip=skip)
+        loss = ((out.rgb - target[ids]) ** 2).mean()
+        optimiser.zero_grad(set_to_none=True)
+        loss.backward()
+        optimiser.step()
+        if volume.degree is None:
+            with torch.no_grad():
+                module.stored[..., :3].clamp_(0.0, 1.0)
+                module.stored[..., 3].clamp_(min=0.0)
+        losses.append(loss.detach())
+    return module.volume(), (torch.stack(losses).tolist() if losses else [])
