@@ -109,6 +109,92 @@ __host__ __device__ constexpr int slot_of(int f) {
     return (f & ~31) + 16 * ((f >> 2) & 1) + (f & 3) + 4 * ((f & 31) >> 3);
 }
 
+// ---- the 16x16x32 core of the split-operand INFERENCE kernel (pnr_split.hip, eval_split_kernel<.., TRAIN = false, ..>) ----
+// v_mfma_f32_16x16x32_f16, lane (c = l & 15, g = l >> 4):  A: row c, the 8 K values of group g   B: col c, the same K group
+//                                                          D: col c, rows 4 g + r (r = 0..3)
+// A wave's 64 features are 4 row tiles t of 16, the 64 points of a tile 4 column tiles jt of 16.  The operand images, the tables
+// and the bias table keep their storage order; what changes is which storage slot an accumulator register holds:
+//   register r of tile (t, jt), lane (c, g)  =  wave-local storage slot slot16(t, g, r) of point 16 jt + c
+// so that the 8 slots a lane owns in tiles 2m and 2m + 1 are the 8 consecutive slots 32 m + 8 g .. + 7: the lane's B fragment
+// of K-step m (32 slots) of the wave's own block, as the MFMA wants it -- and 16 contiguous bytes of the image row.
+constexpr int NT16 = SL / 16;            // feature tiles per wave (4)
+constexpr int NJ16 = MT / 16;            // point tiles (4)
+__host__ __device__ constexpr int slot16(int t, int g, int r) { return 32 * (t >> 1) + 8 * g + 4 * (t & 1) + r; }
+// MFMA row i = 4 g + r of tile t
+__host__ __device__ constexpr int slot16_row(int t, int i) { return slot16(t, i >> 2, i & 3); }
+// hidden feature in global storage slot s (the inverse of slot_of)
+__host__ __device__ constexpr int feat_of_slot(int s) { return 32 * (s >> 5) + (s & 3) + 8 * ((s & 15) >> 2) + 4 * ((s >> 4) & 1); }
+__host__ __device__ constexpr bool slot16_is_bijection() {
+    bool seen[64] = {};
+    for (int t = 0; t < 4; ++t)
+        for (int g = 0; g < 4; ++g)
+            for (int r = 0; r < 4; ++r) {
+                const int s = slot16(t, g, r);
+                if (s < 0 || s >= 64 || seen[s]) return false;
+                seen[s] = true;
+            }
+    return true;
+}
+__host__ __device__ constexpr bool slot16_own_k() {  // K-step m, lane group g: registers 0..3 of tiles 2m, 2m+1 = slots 32m + 8g .. +7
+    for (int m = 0; m < 2; ++m)
+        for (int g = 0; g < 4; ++g)
+            for (int e = 0; e < 8; ++e)
+                if (slot16(2 * m + (e >> 2), g, e & 3) != 32 * m + 8 * g + e) return false;
+    return true;
+}
+__host__ __device__ constexpr bool feat_of_slot_inverts() {
+    for (int f = 0; f < 512; ++f)
+        if (feat_of_slot((f & ~31) + 16 * ((f >> 2) & 1) + (f & 3) + 4 * ((f & 31) >> 3)) != f) return false;
+    return true;
+}
+static_assert(NW != 8 || (NT16 == 4 && NJ16 == 4), "16x16x32 core: 4 x 4 tiles per wave");
+static_assert(slot16_is_bijection(), "slot16 must map (t, g, r) onto the wave's 64 storage slots one to one");
+static_assert(slot16_own_k(), "K-step m of lane group g must be the slots 32 m + 8 g .. + 7");
+static_assert(feat_of_slot_inverts(), "feat_of_slot is the inverse of slot_of");
+// Its A fragments come out of the SAME packed (head, tail) streams the 32x32x16 core reads (pnr_pack.hip, OWNK; no second
+// stream, no pack cost): a 16-byte piece of that stream is 8 K values of one weight row, which is what a lane of either shape
+// holds, so the core only addresses the pieces differently.  One ring step of this core = one K = 32 step = two ring steps of
+// the packed stream (IT fragments of 1 KiB each); lane (i, g) of row tile t takes
+//   row         a16_row(t, i) of fragment `it` = t >> 1   (the packed rows are features in natural order, feat_of_slot(slot16_row))
+//   K group g   from packed step 2 K + (g >> 1), lane half g & 1         (lin_in, and the blocks of the other waves: image order)
+//               from packed step 2 K + (g & 1),  lane half g >> 1        (the wave's own block: the 32x32x16 core's register order)
+// -- runs of four consecutive pieces (64 B), pairs of which share a 128-byte line.  lin_out's 4 rows sit in packed steps 0, 1.
+constexpr int KS16_IN = D_IN_PAD / 32;   // 2
+constexpr int KS16_BIG = D_HID / 32;     // 16: the wave's own block (2 steps) first, then the blocks of waves wv+1 .. wv+7
+constexpr int KS16_OUT = KS_OUT / 2;     // 2
+constexpr int RS16_VIEW_END = RS_VIEW_END_F / 2;  // 98
+constexpr int RS16_TOTAL = RS_TOTAL_F / 2;        // 164
+static_assert(RS16_VIEW_END == KS16_IN + 2 * COMBINE_LAYER * KS16_BIG && RS16_TOTAL == KS16_IN + 2 * N_BLOCKS * KS16_BIG + KS16_OUT,
+              "one K = 32 step = two packed ring steps");
+static_assert(RS16_VIEW_END % 2 == 0 && RS16_TOTAL % 2 == 0, "ring depth 2 needs aligned segments");
+static_assert(NW != 8 || IT == 2, "the address maps below are for two packed fragments per ring step");
+constexpr int RS16_BYTES = 2 * IT * 1024;  // one K = 32 step of one wave in one blob
+// packed row (within its 32-row fragment t >> 1) of MFMA row i of row tile t
+__host__ __device__ constexpr int a16_row(int t, int i) { return (i & 3) + 4 * (i >> 3) + 16 * ((i >> 2) & 1) + 8 * (t & 1); }
+__host__ __device__ constexpr bool a16_row_is_the_feature() {
+    for (int t = 0; t < 4; ++t)
+        for (int i = 0; i < 16; ++i)
+            if (feat_of_slot(slot16_row(t, i)) != 32 * (t >> 1) + a16_row(t, i)) return false;
+    return true;
+}
+static_assert(a16_row_is_the_feature(), "a16_row must name the packed row that holds the feature of slot16_row");
+// byte offset of lane (i, g)'s piece for row tile 0 inside a K = 32 step (row tile t: + (t >> 1) * 1024 + (t & 1) * 128)
+__host__ __device__ constexpr int a16_lane_off(int i, int g, bool own) {
+    return own ? (g & 1) * (IT * 1024) + (a16_row(0, i) + 32 * (g >> 1)) * 16 : (g >> 1) * (IT * 1024) + (a16_row(0, i) + 32 * (g & 1)) * 16;
+}
+// K-order check of the two maps against the packed stream's own definition (pnr_pack.hip, kind == 2): first storage slot of the 8
+// K values of K-step j, lane half h -- own block: register order 32 (j >> 1) + 16 h + 8 (j & 1); other blocks: 16 j + 8 h
+__host__ __device__ constexpr bool a16_k_order() {
+    for (int m = 0; m < 2; ++m)
+        for (int g = 0; g < 4; ++g) {
+            const int jo = 2 * m + (g & 1), ho = g >> 1, jg = 2 * m + (g >> 1), hg = g & 1;
+            if (32 * (jo >> 1) + 16 * ho + 8 * (jo & 1) != 32 * m + 8 * g) return false;
+            if (16 * jg + 8 * hg != 32 * m + 8 * g) return false;
+        }
+    return true;
+}
+static_assert(a16_k_order(), "K group g of K-step m must be the storage slots 32 m + 8 g .. + 7 in both maps");
+
 // ---- backward chain: transposed weight stream, consumption order per tile ----
 //   head (pooled, once): lin_out^T (4 ring steps, k-step 0 real) | fc_1[4]^T fc_0[4]^T fc_1[3]^T fc_0[3]^T
 //   per source view    : fc_1[2]^T fc_0[2]^T fc_1[1]^T fc_0[1]^T fc_1[0]^T fc_0[0]^T

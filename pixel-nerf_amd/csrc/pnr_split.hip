@@ -20,6 +20,12 @@
 // Round 4: every 512-wide linear starts with the products against the wave's OWN 64 features, taken from its accumulators (they
 // are B fragments as they are), while the same fragments go to the operand images for the other waves: stage_own / gemm_split_rot.
 //
+// Round 7: two MFMA cores behind one kernel body.  The INFERENCE instantiations (TRAIN = false) run every product on
+// v_mfma_f32_16x16x32_f16 (4 x 4 tiles of 16 features x 16 points per wave; "the 16x16x32 core" below), the training forward keeps
+// v_mfma_f32_32x32x16_f16 with its masks and dumps, bit for bit.  Same arithmetic, same packed streams, same bias / table layout;
+// the chip holds 1.99 GHz under the new core against 1.88 GHz under the old one and needs 3 % fewer cycles: sn64 +9.9 %, srn_car
+// +6.8 %, DTU +7.4 % same-box (profiles/r07_split_kernel_ab.txt).
+//
 // Kernels of this file:
 //   eval_split_kernel<RAYS, MV, TIMING, TRAIN, GUARD, SC>   the fused network (SC: the stream-scale / range-probe forms, below).  GUARD = the fp16-range guard (PnrSplitAux.sat_flag): the
 //                                                same bits, plus one flag bit per layer whose operand image received a value >= 65504.
@@ -489,6 +495,198 @@ __device__ __forceinline__ void add_from_table(f32x16 (&x)[IT][JT], const char *
         }
 }
 
+// ---- the 16x16x32 core of the INFERENCE instantiations (round 7) -------------------------------------------------------------
+// The kernel is power-limited and the chip holds a higher clock on v_mfma_f32_16x16x32_f16 than on 32x32x16 at equal cycles per
+// FLOP (tools/ubench/split_gemm.hip, profiles/r07_split_gemm_16x16x32.txt: the GEMM loop of this kernel x1.16 by wall).  Same
+// footprint: 8 waves x 64 features x 64 points, x + net = 128 accumulators, 16 KiB of weight ring per wave; the images, tables and
+// biases keep their storage order (pnr_layout.h, slot16).  Lane (c = l & 15, g = l >> 4); accumulator (t, jt) = 16 features x 16
+// points; one ring step = one K = 32 step = 4 A fragments per blob, ring of 2; the B fragment pair of ONE point tile is fetched
+// just in time (two pairs in rotation: 16 registers, each pair feeds 12 MFMAs) -- a whole K-step of B, double-buffered, spills.
+// The A fragments are 16-byte pieces of the SAME packed streams the 32x32x16 core reads, addressed per lane (pnr_layout.h,
+// a16_lane_off): one blob, one pack, nothing new on the host side.
+// The TRAIN instantiations keep the 32x32x16 core above, its masks and dumps.
+struct SplitRing16 {
+    h8 h[2][NT16], l[2][NT16];
+    const char *base_h, *base_l;  // this wave's head / tail stream
+    uint32_t off_gen, off_own;    // this lane's piece inside a K = 32 step: image K order / the own block's register K order
+    int pf_rs, pf_view;           // prefetch cursor in K = 32 steps
+};
+// byte offset of the cursor's step for this lane: the first two steps of every 512-wide linear are the wave's own block
+__device__ __forceinline__ size_t ring_pf16(const SplitRing16 &R) {
+    const int r = R.pf_rs - KS16_IN;
+    const bool own = r >= 0 && R.pf_rs < RS16_TOTAL - KS16_OUT && (r & (KS16_BIG - 1)) == 0;
+    return (size_t)R.pf_rs * RS16_BYTES + (own ? R.off_own : R.off_gen);
+}
+__device__ __forceinline__ void ring_advance16(SplitRing16 &R, int NS) {
+    int rs = R.pf_rs + 2, v = R.pf_view;
+    if (rs == RS16_VIEW_END && v + 1 < NS) { v += 1; rs = 0; }
+    else if (rs == RS16_TOTAL) { rs = 0; v = 0; }
+    R.pf_rs = rs; R.pf_view = v;
+}
+__device__ __forceinline__ f32x4 mf16(h8 a, h8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+
+// the 12 MFMAs of one (K-step j, point tile jt): head x head, head x tail, tail x head, the four row tiles side by side
+__device__ __forceinline__ void mfma12(f32x4 (&acc)[NT16][NJ16], int jt, const h8 (&ah)[NT16], const h8 (&al)[NT16], h8 bh, h8 bl) {
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) acc[t][jt] = mf16(ah[t], bh, acc[t][jt]);
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) acc[t][jt] = mf16(ah[t], bl, acc[t][jt]);
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) acc[t][jt] = mf16(al[t], bh, acc[t][jt]);
+}
+__device__ __forceinline__ void refill16(SplitRing16 &R, int j, size_t pf) {
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+        R.h[j][t] = gload8<PH>(R.base_h + pf + j * RS16_BYTES + (t >> 1) * 1024 + (t & 1) * 128);
+        R.l[j][t] = gload8<PH>(R.base_l + pf + j * RS16_BYTES + (t >> 1) * 1024 + (t & 1) * 128);
+    }
+}
+
+// One ring body from an image: 2 K-steps x 4 point tiles, B fragments at base + 64 j + jt jstride (+ lo_delta for the tails);
+// bh[0] / bl[0] hold the first pair on entry and the pair at `nxt` on exit.  Pinned issue order per point tile: (M L) x 2, then
+// the other 10 MFMAs; a step's 8 refills ride on the last pass (tail x head, the last reader of a tile's fragments) of its last
+// point tile, 2 per MFMA.
+__device__ __forceinline__ void body16(f32x4 (&acc)[NT16][NJ16], const char *smem, h8 (&bh)[2], h8 (&bl)[2], uint32_t base,
+                                       uint32_t jstride, uint32_t lo_delta, uint32_t nxt, SplitRing16 &R) {
+    const size_t pf = ring_pf16(R);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int jt = 0; jt < NJ16; ++jt) {
+            const int cur = (j * NJ16 + jt) & 1;
+            const bool lastj = jt == NJ16 - 1;
+            const uint32_t rd = lastj ? (j == 1 ? nxt : base + 64) : base + 64 * j + (jt + 1) * jstride;
+            bh[cur ^ 1] = lds8<PH>(smem, rd);
+            bl[cur ^ 1] = lds8<PH>(smem, rd + lo_delta);
+            mfma12(acc, jt, R.h[j], R.l[j], bh[cur], bl[cur]);
+            if (lastj) refill16(R, j, pf);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // 1 LDS read
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            if (lastj) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 2 * NT16 - 2, 0);
+#pragma unroll
+                for (int t = 0; t < NT16; ++t) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);  // 2 VMEM reads
+                }
+            } else {
+                __builtin_amdgcn_sched_group_barrier(0x008, 3 * NT16 - 2, 0);
+            }
+        }
+}
+
+// lin_in: K = 64 = one ring body, B rows in the lin_in operand images
+__device__ __forceinline__ void gemm_split16_in(f32x4 (&acc)[NT16][NJ16], const char *smem, uint32_t rd0, uint32_t jstride,
+                                                uint32_t lo_delta, SplitRing16 &R, int NS) {
+    h8 bh[2], bl[2];
+    bh[0] = lds8<PH>(smem, rd0);
+    bl[0] = lds8<PH>(smem, rd0 + lo_delta);
+    body16(acc, smem, bh, bl, rd0, jstride, lo_delta, rd0, R);  // (after the last pair: the first again, read and dropped)
+    ring_advance16(R, NS);
+}
+
+// stage_own on this core: K-step m of the wave's own block is, per point tile, registers 0..3 of accumulator tiles 2m and 2m + 1
+// (pnr_layout.h, slot16_own_k): relu + (head, tail) split of those 8 values = the B fragment pair, multiplied at once (12 MFMAs)
+// and stored -- the same 16 bytes the 32x32x16 core stores there -- to both images for the other seven waves.
+template <typename ST, bool GUARD, typename MARK = NoMark>
+__device__ __forceinline__ void stage_own16(f32x4 (&acc)[NT16][NJ16], const f32x4 (&src)[NT16][NJ16], char *smem, uint32_t waddr,
+                                            SplitRing16 &R, int NS, [[maybe_unused]] uint32_t *amax, MARK mark = MARK()) {
+    h8 bh[2], bl[2];
+    auto make = [&](int q, int buf) {
+        const int m = q / NJ16, jt = q % NJ16;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[e] = src[2 * m][jt][e]; v[4 + e] = src[2 * m + 1][jt][e]; }
+        split8<true, GUARD>(v, bh[buf], bl[buf], amax);
+    };
+    make(0, 0);
+    mark(PH_OWN_PROLOGUE);
+    const size_t pf = ring_pf16(R);
+#pragma unroll
+    for (int q = 0; q < 2 * NJ16; ++q) {
+        const int m = q / NJ16, jt = q % NJ16, cur = q & 1;
+        const bool lastj = jt == NJ16 - 1;
+        if (q + 1 < 2 * NJ16) make(q + 1, cur ^ 1);
+        mfma12(acc, jt, R.h[m], R.l[m], bh[cur], bl[cur]);
+        const uint32_t ad = waddr + jt * 16 * ROW_ACT + m * 64;
+        *reinterpret_cast<h8 *>(smem + ST::A_HI + ad) = bh[cur];
+        *reinterpret_cast<h8 *>(smem + ST::A_LO + ad) = bl[cur];
+        if (lastj) refill16(R, m, pf);
+        // pinned: the split of the NEXT pair (~24 VALU) spread under this pair's MFMAs, the two image stores behind the 5th and
+        // the 7th, a step's refills behind the last four MFMAs of its last point tile
+#pragma unroll
+        for (int i = 0; i < 3 * NT16; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   // 1 MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                   // up to 3 VALU
+            if (i == 4 || i == 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);             // 1 LDS write
+            if (lastj && i >= 2 * NT16) __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);       // 2 VMEM reads
+        }
+    }
+    ring_advance16(R, NS);
+    mark(PH_OWN_KSTEPS);
+}
+
+// the other seven K blocks, from the operand images: blocks (wv + 1) .. (wv + 7) mod 8, one ring body each
+__device__ __forceinline__ void gemm_split_rot16(f32x4 (&acc)[NT16][NJ16], const char *smem, uint32_t a_rd0, uint32_t jstride,
+                                                 uint32_t lo_delta, int wv, SplitRing16 &R, int NS) {
+    static_assert(SL == 64, "one ring body per wave block");
+    h8 bh[2], bl[2];
+    uint32_t base = a_rd0 + (uint32_t)((wv + 1) & (NW - 1)) * 128;
+    bh[0] = lds8<PH>(smem, base);
+    bl[0] = lds8<PH>(smem, base + lo_delta);
+#pragma unroll 1
+    for (int m = 2; m <= NW; ++m) {  // (after the last block: this wave's own, read and dropped)
+        const uint32_t nxt = a_rd0 + (uint32_t)((wv + m) & (NW - 1)) * 128;
+        body16(acc, smem, bh, bl, base, jstride, lo_delta, nxt, R);
+        base = nxt;
+        ring_advance16(R, NS);
+    }
+}
+
+template <bool INIT>
+__device__ __forceinline__ void add_bias16(f32x4 (&acc)[NT16][NJ16], const float *bias_wave, int g, int slot) {
+    // bias_wave = bias + wave * BIAS_FLOATS_PER_WAVE: the wave's 64 values of a slot in storage order
+    const float *b = bias_wave + (size_t)slot * (NW * BIAS_FLOATS_PER_WAVE);
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(b + slot16(t, g, 0));
+#pragma unroll
+        for (int jt = 0; jt < NJ16; ++jt) {
+            if (INIT) acc[t][jt] = v;
+            else acc[t][jt] += v;
+        }
+    }
+}
+
+template <typename ST, bool SCALED = false>
+__device__ __forceinline__ void add_from_table16(f32x4 (&x)[NT16][NJ16], const char *smem, int c, int g, int wv, [[maybe_unused]] float sc = 1.f) {
+#pragma unroll
+    for (int t = 0; t < NT16; ++t)
+#pragma unroll
+        for (int jt = 0; jt < NJ16; ++jt) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(smem + (jt * 16 + c) * ST::ROW_TAB + (wv * SL + slot16(t, g, 0)) * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (SCALED) x[t][jt][e] = __builtin_fmaf(sc, v[e], x[t][jt][e]);
+                else x[t][jt][e] += v[e];
+            }
+        }
+}
+
+// accumulator set, ring and tile counts of a core
+template <bool M16> struct SplitCore {
+    typedef f32x16 acc_t;
+    typedef SplitRing ring_t;
+    static constexpr int AI = IT, AJ = JT, AR = 16;
+};
+template <> struct SplitCore<true> {
+    typedef f32x4 acc_t;
+    typedef SplitRing16 ring_t;
+    static constexpr int AI = NT16, AJ = NJ16, AR = 4;
+};
+
 // MV: views go through blocks 0-2 one after the other on the same 64 points; the running view sum (util.combine_interleaved,
 // util.py:461-466) does not fit the registers next to x + net + the 64-register head/tail ring, so it is PARKED in a
 // per-workgroup scratch (q.mv_ws, [slot][thread] layout: every lane re-reads only what it wrote itself, no synchronisation;
@@ -513,6 +711,11 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef SplitTileT<64> ST;
     constexpr bool PROBE = SC == 2;
+    constexpr bool M16 = !TRAIN;  // the inference instantiations run the 16x16x32 core, the training forward the 32x32x16 core
+    typedef SplitCore<M16> CORE;
+    typedef typename CORE::acc_t acc_t;
+    typedef typename CORE::ring_t ring_t;
+    constexpr int AI = CORE::AI, AJ = CORE::AJ, AR = CORE::AR;  // accumulator tiles per wave and registers per tile
     static_assert(!(SC && (TRAIN || TIMING || !GUARD)), "the stream scale is an inference form, instantiated with the guard on");
     [[maybe_unused]] float sc_c = 1.f, sc_inv = 1.f, sc_out = 1.f;
     if constexpr (SC != 0) {
@@ -530,30 +733,50 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pl = lane & 31, h = lane >> 5;
+    // lane = (point pl, K half h) on the 32x32x16 core, (point pl, K group h) on the 16x16x32 core
+    const int pl = M16 ? lane & 15 : lane & 31, h = M16 ? lane >> 4 : lane >> 5;
     const int NS = MV ? q.NS : 1;
 
-    const uint32_t a_rd0 = ST::A_HI + pl * ROW_ACT + h * 16;
+    // 16x16x32 core: a ds_read_b128 is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same
+    // + 32 -- i.e. points {0-3, 12-15} of one K group next to points {4-11} of its neighbour; with 65 slots per row those two
+    // runs of 8 slots overlap in one slot whatever the odd pad (2-way).  So rows 4..11 (mod 16) of the INFERENCE kernel's
+    // activation images hold each pair of 16-byte chunks swapped: both runs then start at the same slot and tile the 16 slots.
+    // SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE over the kernel: 0.415 plain, 0.186 swapped (what is left: the table and lin_in
+    // reads and the image stores), 0.004 on the 32x32x16 core (profiles/r07_split_kernel_ab.txt, counter passes of their own).
+    // Writer (stage_own16) and readers share `a_sw`; the images never leave this kernel (the training forward, which dumps them,
+    // keeps the plain order, and so does every buffer another kernel or the host sees).
+    const uint32_t a_sw = M16 ? ((uint32_t)(h ^ (((pl + 4) >> 3) & 1))) * 16 : h * 16;
+    const uint32_t a_rd0 = ST::A_HI + pl * ROW_ACT + a_sw;
     const uint32_t in_rd0 = ST::LDS_IN + pl * ROW_IN + h * 16;
-    const uint32_t a_wr = pl * ROW_ACT + (wv * IT) * 64 + h * 32;
-    const float *bias_lane = q.bias + wv * BIAS_FLOATS_PER_WAVE + h * 16;
+    const uint32_t a_wr = pl * ROW_ACT + wv * (SL * 2) + (M16 ? a_sw : h * 32);
+    const float *bias_lane = q.bias + wv * BIAS_FLOATS_PER_WAVE + (M16 ? 0 : h * 16);
 
     f16_ovfl_mode<PH>();
     // static priority for the second-dispatched half of the workgroup (the arbitration loser of every segment when both waves of
     // a SIMD run at priority 0; MI355X_MICROARCH.md, "two waves per SIMD", item 4): one s_setprio before the main loop, no flips.
     // Same-box A/B: +0.9 % on sn64 / srn_car / DTU (profiles/r03_split_kernel_ab.txt).  Does not touch results.
     if (NW > 4 && wv >= NW / 2) __builtin_amdgcn_s_setprio(1);
-    SplitRing R;
-    R.base_h = q.wstream + (size_t)wv * (RS_TOTAL_F * IT * 1024) + lane * 16;
-    R.base_l = R.base_h + PACKED_BYTES;  // the tail blob follows the head blob (pnr_pack_mlp_split)
+    ring_t R;
+    if constexpr (M16) {  // the same two blobs, pieces addressed for the 16x16x32 shape
+        R.base_h = q.wstream + (size_t)wv * (RS_TOTAL_F * IT * 1024);
+        R.base_l = R.base_h + PACKED_BYTES;
+        R.off_gen = a16_lane_off(pl, h, false);
+        R.off_own = a16_lane_off(pl, h, true);
+        refill16(R, 0, R.off_gen);
+        refill16(R, 1, R.off_gen);
+        R.pf_rs = 2;
+    } else {
+        R.base_h = q.wstream + (size_t)wv * (RS_TOTAL_F * IT * 1024) + lane * 16;
+        R.base_l = R.base_h + PACKED_BYTES;  // the tail blob follows the head blob (pnr_pack_mlp_split)
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            R.h[j][it] = gload8<PH>(R.base_h + j * (IT * 1024) + it * 1024);
-            R.l[j][it] = gload8<PH>(R.base_l + j * (IT * 1024) + it * 1024);
-        }
-    R.pf_rs = 4;
+            for (int it = 0; it < IT; ++it) {
+                R.h[j][it] = gload8<PH>(R.base_h + j * (IT * 1024) + it * 1024);
+                R.l[j][it] = gload8<PH>(R.base_l + j * (IT * 1024) + it * 1024);
+            }
+        R.pf_rs = 4;
+    }
     R.pf_view = 0;
     [[maybe_unused]] unsigned long long *tim = q.tim;
     [[maybe_unused]] unsigned long long tlast = TIMING ? __builtin_readcyclecounter() : 0ull;
@@ -615,60 +838,81 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
     // PROBE: the largest relu'd value of the accumulator tiles a stage is about to split -> LDS word `layer`.  One LDS max per
     // lane, straight-line (an atomicMax() becomes a branch + a wave-reduction loop); the file has no static LDS, so the dynamic
     // block starts at LDS address 0.  NaNs are skipped (fmaxf); an inf arrives as inf.
-    [[maybe_unused]] auto probe_note = [&](const f32x16 (&a)[IT][JT], int layer) {
+    [[maybe_unused]] auto probe_note = [&](const acc_t (&a)[AI][AJ], int layer) {
         if constexpr (PROBE) {
             float m = 0.f;
 #pragma unroll
-            for (int it = 0; it < IT; ++it)
+            for (int it = 0; it < AI; ++it)
 #pragma unroll
-                for (int jt = 0; jt < JT; ++jt)
+                for (int jt = 0; jt < AJ; ++jt)
 #pragma unroll
-                    for (int r = 0; r < 16; r += 2) m = fmaxf(fmaxf(m, a[it][jt][r]), a[it][jt][r + 1]);
+                    for (int r = 0; r < AR; r += 2) m = fmaxf(fmaxf(m, a[it][jt][r]), a[it][jt][r + 1]);
             const uint32_t ad = ST::LDS_TOTAL + 4u * (uint32_t)layer;
             asm volatile("ds_max_u32 %0, %1" : : "v"(ad), "v"(m) : "memory");
         }
     };
     [[maybe_unused]] auto own_mark = [&](int ph) { PNR_T(ph); };
+    // the stages of a 512-wide linear on this instantiation's core
+    auto bias_set = [&](acc_t (&a)[AI][AJ], int slot) {
+        if constexpr (M16) add_bias16<true>(a, bias_lane, h, slot);
+        else add_bias<true>(a, bias_lane, slot);
+    };
+    auto bias_add = [&](acc_t (&a)[AI][AJ], int slot) {
+        if constexpr (M16) add_bias16<false>(a, bias_lane, h, slot);
+        else add_bias<false>(a, bias_lane, slot);
+    };
+    auto own = [&](acc_t (&a)[AI][AJ], const acc_t (&src)[AI][AJ]) {
+        if constexpr (M16) stage_own16<ST, GUARD>(a, src, smem, a_wr, R, NS, &amax, own_mark);
+        else stage_own<ST, JT, GUARD>(a, src, smem, a_wr, R, NS, &amax, own_mark);
+    };
+    auto rot = [&](acc_t (&a)[AI][AJ]) {
+        if constexpr (M16) gemm_split_rot16(a, smem, a_rd0, 16 * ROW_ACT, ST::A_LO - ST::A_HI, wv, R, NS);
+        else gemm_split_rot<JT>(a, smem, a_rd0, 32 * ROW_ACT, ST::A_LO - ST::A_HI, wv, R, NS);
+    };
+    auto table_add = [&](acc_t (&a)[AI][AJ], auto scaled, float sc) {
+        if constexpr (M16) add_from_table16<ST, decltype(scaled)::value>(a, smem, pl, h, wv, sc);
+        else add_from_table<ST, decltype(scaled)::value>(a, smem, pl, h, wv, sc);
+    };
     // one residual block on x (resnetfc.py:66-88); lookup: lin_z[b+1] via table b+1 behind it.
     // Every 512-wide linear = stage_own (split epilogue + this wave's own K block, from registers) | barrier | gemm_split_rot
-    auto block = [&](f32x16 (&x)[IT][JT], int b, bool lookup) {
+    auto block = [&](acc_t (&x)[AI][AJ], int b, bool lookup) {
         if constexpr (TRAIN) put_mask(x, 2 * b, b < COMBINE_LAYER ? tr_mask_view : tr_mask_pooled);
         __syncthreads();  // table rows / previous operand images are no longer read
         PNR_T(PH_BAR1);
         {
-            f32x16 net[IT][JT];
-            add_bias<true>(net, bias_lane, 1 + 2 * b);
+            acc_t net[AI][AJ];
+            bias_set(net, 1 + 2 * b);
             if constexpr (TIMING) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the bias has ARRIVED when the stage's clock starts (diagnostic: also drains the ring)
             own_mark(PH_OWN_BIAS);
             probe_note(x, 2 * b);
-            stage_own<ST, JT, GUARD>(net, x, smem, a_wr, R, NS, &amax, own_mark);                  // fc_0, own block
+            own(net, x);                                                                           // fc_0, own block
             sat_note(2 * b);
             PNR_T(PH_WRITE_X);
             __syncthreads();
             PNR_T(PH_BAR2);
             if constexpr (TRAIN) dump_pair(q.s_a[b], b);
-            gemm_split_rot<JT>(net, smem, a_rd0, 32 * ROW_ACT, ST::A_LO - ST::A_HI, wv, R, NS);   // fc_0, blocks of the other waves
+            rot(net);                                                                              // fc_0, blocks of the other waves
             PNR_T(PH_GEMM_FC0);
             if constexpr (TRAIN) put_mask(net, 2 * b + 1, b < COMBINE_LAYER ? tr_mask_view : tr_mask_pooled);
             __syncthreads();
             PNR_T(PH_BAR3);
-            add_bias<false>(x, bias_lane, 2 + 2 * b);
+            bias_add(x, 2 + 2 * b);
             own_mark(PH_OWN_BIAS);
             probe_note(net, 2 * b + 1);
-            stage_own<ST, JT, GUARD>(x, net, smem, a_wr, R, NS, &amax, own_mark);                  // fc_1, own block
+            own(x, net);                                                                           // fc_1, own block
             sat_note(2 * b + 1);
             PNR_T(PH_WRITE_NET);
         }
         __syncthreads();
         PNR_T(PH_BAR4);
         if constexpr (TRAIN) dump_pair(q.s_n[b], b);
-        gemm_split_rot<JT>(x, smem, a_rd0, 32 * ROW_ACT, ST::A_LO - ST::A_HI, wv, R, NS);         // fc_1
+        rot(x);                                                                                    // fc_1
         PNR_T(PH_GEMM_FC1_Z);
         if (lookup) {
             __syncthreads();
             gather_table_f32<2, ST>(q, smem, wv, lane, b + 1);
             __syncthreads();
-            add_from_table<ST, SC != 0>(x, smem, pl, h, wv, sc_c);
+            table_add(x, std::integral_constant<bool, SC != 0>(), sc_c);
             PNR_T(PH_TABLE);
         }
     };
@@ -676,7 +920,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
     // XCD-aware tile order (pnr_device.h tile_range; which tile a workgroup runs does not touch any result)
     const TileRange order = tile_range(q.ntiles, q.n_xcd);
     for (int tile = order.begin; tile < order.end; tile += order.step) {
-        f32x16 x[IT][JT];
+        acc_t x[AI][AJ];
 #pragma unroll 1
         for (int view = 0; view < NS; ++view) {
             __syncthreads();  // previous tile / view: every reader of the images / IN / META is done
@@ -692,15 +936,16 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             PNR_T(PH_GEOMETRY);
             gather_table_f32<2, ST>(q, smem, wv, lane, 0);
             PNR_T(PH_GATHER);
-            add_bias<true>(x, bias_lane, B_IN_Z0);
-            gemm_split(x, smem, in_rd0, 32 * ROW_IN, ST::IN_LO_DELTA, KS_IN / 4, R, NS);  // lin_in   resnetfc.py:147
+            bias_set(x, B_IN_Z0);
+            if constexpr (M16) gemm_split16_in(x, smem, in_rd0, 16 * ROW_IN, ST::IN_LO_DELTA, R, NS);
+            else gemm_split(x, smem, in_rd0, 32 * ROW_IN, ST::IN_LO_DELTA, KS_IN / 4, R, NS);  // lin_in   resnetfc.py:147
             __syncthreads();  // table rows of every wave are in place
-            add_from_table<ST>(x, smem, pl, h, wv);                                           // lin_z[0] via table 0
+            table_add(x, std::false_type(), 1.f);                                             // lin_z[0] via table 0
             if constexpr (SC != 0) {  // from here on the stream is c x
 #pragma unroll
-                for (int it = 0; it < IT; ++it)
+                for (int it = 0; it < AI; ++it)
 #pragma unroll
-                    for (int jt = 0; jt < JT; ++jt) x[it][jt] *= sc_c;
+                    for (int jt = 0; jt < AJ; ++jt) x[it][jt] *= sc_c;
             }
             PNR_T(PH_GEMM_IN_Z0);
             if constexpr (TRAIN) {
@@ -713,19 +958,20 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
 #pragma unroll 1
             for (int b = 0; b < COMBINE_LAYER; ++b) block(x, b, b + 1 < COMBINE_LAYER);
             if constexpr (MV) {
+                static_assert(AI * AJ * AR == IT * JT * 16, "both cores park 16 slots of 16 bytes per thread");
                 f32x4 *ws = reinterpret_cast<f32x4 *>(q.mv_ws) + (size_t)blockIdx.x * (IT * JT * 4 * NTHREADS) + tid;
                 const float inv = 1.f / (float)NS;
                 const bool first = view == 0, last = view + 1 == NS;
                 // util.combine_interleaved (util.py:461-471): mean, or -- network flag -- the maximum over the source views
                 const bool cmax = (reinterpret_cast<const int *>(q.bout)[BOUT_FLAGS_INDEX] & 1) != 0;
 #pragma unroll
-                for (int it = 0; it < IT; ++it)
+                for (int it = 0; it < AI; ++it)
 #pragma unroll
-                    for (int jt = 0; jt < JT; ++jt) {
-                        __builtin_amdgcn_sched_barrier(0);  // one accumulator tile (4 loads) in flight at a time: no register spike
+                    for (int jt = 0; jt < AJ; ++jt) {
+                        if (AR == 16 || jt == 0) __builtin_amdgcn_sched_barrier(0);  // 4 loads in flight at a time: no register spike
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int i = (it * JT + jt) * 4 + k;
+                        for (int k = 0; k < AR / 4; ++k) {
+                            const int i = (it * AJ + jt) * (AR / 4) + k;
                             f32x4 v = {x[it][jt][4 * k], x[it][jt][4 * k + 1], x[it][jt][4 * k + 2], x[it][jt][4 * k + 3]};
                             if (!first) {  // 1 KiB per wave-instruction
                                 const f32x4 prev = ws[i * NTHREADS];  // (ordinary, L2-resident accesses: non-temporal ones measured -1 ... -2.5 %)
@@ -748,7 +994,51 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
 
         // lin_out(relu(x)): each wave contracts its own 64 features (the wave's accumulators are the B operand)
         probe_note(x, 10);
-        {
+        if constexpr (M16) {
+            // A = lin_out's 4 rows padded to 16 (row tile 0 of the two ring steps), B = the own block's two K-steps from the
+            // accumulators as in stage_own16: the 4 outputs of point 16 jt + pl land in registers 0..3 of the lanes of group 0
+            f32x4 o[NJ16];
+#pragma unroll
+            for (int jt = 0; jt < NJ16; ++jt) o[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // Its fragments are the one place where the packed stream is not "two packed steps per K = 32 step": K-step m, group g
+            // is row pl of packed fragment (step m, it = g & 1), lane half g >> 1 (rows 4..31 of those fragments are zero).  They are
+            // fetched here rather than through the ring: a ring step is 4 KiB further on for every lane, lin_out's second K-step
+            // is 2 KiB behind its first, and a per-lane offset cannot turn one stride into the other.  The ring's two steps at this
+            // cursor (packed steps 324-327: lin_out's pieces in another order, and zero padding) are read and dropped, as the
+            // 32x32x16 core drops its zero steps 2-3 there: 16 KiB per wave against the 1.3 MB a wave streams per tile.  The four
+            // loads wait ~1 us per 176 us tile; the next tile's lin_in steps are requested first, so the ring fills meanwhile.
+            const size_t pf = ring_pf16(R);
+            refill16(R, 0, pf);
+            refill16(R, 1, pf);
+            ring_advance16(R, NS);
+            const size_t out_off = (size_t)(RS_TOTAL_F - KS_OUT) * (IT * 1024) + (h & 1) * 1024 + (pl + 32 * (h >> 1)) * 16;
+            h8 oh[2], ol[2];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                oh[m] = gload8<PH>(R.base_h + out_off + m * (IT * 1024));
+                ol[m] = gload8<PH>(R.base_l + out_off + m * (IT * 1024));
+            }
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const h8 ah = oh[m], al = ol[m];
+#pragma unroll
+                for (int jt = 0; jt < NJ16; ++jt) {
+                    float v[8];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { v[e] = x[2 * m][jt][e]; v[4 + e] = x[2 * m + 1][jt][e]; }
+                    h8 bh, bl;
+                    split8<true, GUARD>(v, bh, bl, &amax);
+                    o[jt] = mf16(ah, bh, o[jt]);
+                    o[jt] = mf16(ah, bl, o[jt]);
+                    o[jt] = mf16(al, bh, o[jt]);
+                }
+            }
+            sat_note(10);
+            if (h == 0) {
+#pragma unroll
+                for (int jt = 0; jt < NJ16; ++jt) *reinterpret_cast<f32x4 *>(smem + ST::LDS_OUT + (wv * MT + jt * 16 + pl) * 16) = o[jt];
+            }
+        } else {
             f32x16 o[JT];
 #pragma unroll
             for (int jt = 0; jt < JT; ++jt)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""List, per gfx950 kernel of a .hip translation unit, the inner-loop headers that open with `s_waitcnt vmcnt(0)`.
+"""List, per gfx950 kernel of a .hip translation unit, the inner-loop headers that open with `s_waitcnt vmcnt(0)`, and the
+scratch loads / stores that sit inside inner loops (all of them, and those in loops that issue MFMAs: the GEMM loop bodies).
 
     python tools/loop_header_waits.py pixel-nerf_amd/csrc/pnr_split.hip [--filter eval_split] [-DMACRO ...]
 
@@ -28,25 +29,36 @@ def main():
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-S",
                         src, "-o", f.name] + extra, check=True, stderr=subprocess.DEVNULL)
         lines = open(f.name).read().split("\n")
-    name, loops, bad = None, 0, 0
+    name, loops, bad, scr, mfma_scr = None, 0, 0, 0, 0
     out = []
     for i, ln in enumerate(lines):
         m = re.match(r"^(_Z\w+):", ln)
         if m:
-            name, loops, bad = m.group(1), 0, 0
+            name, loops, bad, scr, mfma_scr = m.group(1), 0, 0, 0, 0
         if "Inner Loop Header" in ln and name:
             loops += 1
             if any("vmcnt(0)" in x for x in lines[i + 1:i + 4]):
                 bad += 1
+            # the loop's body: from its header label to the backward branch to that label
+            label = ln.split(":")[0].strip()
+            body = []
+            for x in lines[i + 1:]:
+                body.append(x)
+                if re.search(r"s_cbranch_\w+\s+" + re.escape(label) + r"\b", x) or "s_endpgm" in x:
+                    break
+            n_scr = sum(1 for x in body if re.match(r"\s*scratch_(load|store)", x))
+            scr += n_scr
+            if any("v_mfma" in x for x in body):
+                mfma_scr += n_scr
         if "s_endpgm" in ln and name:
-            out.append((name, loops, bad))
+            out.append((name, loops, bad, scr, mfma_scr))
             name = None
-    dem = subprocess.run(["c++filt"] + [n for n, _, _ in out], capture_output=True, text=True).stdout.split("\n")
-    print("loops  vmcnt(0)-headers  kernel")
-    for (n, l, b), d in zip(out, dem):
+    dem = subprocess.run(["c++filt"] + [o[0] for o in out], capture_output=True, text=True).stdout.split("\n")
+    print("loops  vmcnt(0)-headers  scratch-in-inner-loops  (of which in loops with MFMAs)  kernel")
+    for (n, l, b, s, ms), d in zip(out, dem):
         if flt and flt not in d:
             continue
-        print(f"{l:5d}  {b:16d}  {d}")
+        print(f"{l:5d}  {b:16d}  {s:22d}  {ms:30d}  {d}")
 
 
 if __name__ == "__main__":
