@@ -1176,6 +1176,43 @@ int pnr_baked_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W, int
                              const float *d_rgb /*(NV H W,3), nullable*/, const float *d_depth /*nullable*/,
                              const float *d_alpha /*nullable*/, float *d_stored, void *stream);
 
+/* Total-variation prior of a fitted volume (added within ABI rev 12 as well): the smoothness term a fit to few views needs, its
+ * value and its gradient in one pass, with no atomics.  `stored` is what pnr_baked_backward_* calls `stored`: fp32 (nx,ny,nz,4)
+ * (degree -1) or (nx,ny,nz,B,4) (degree 0, 1, 2; B = 1, 4, 9); with index != NULL the M kept rows (M,4) / (M,B,4), `index`
+ * (nx,ny,nz) and `ids` (M) being those of pnr_sparse_points_mark's kept set (ops.sparse_points).  index == NULL: M is not looked at.
+ * A point p holds E = 4 or 4 B elements; w: a HOST array of E floats, finite and >= 0, one weight per element of a row.
+ *   d_a(p,c) = S[p + e_a, c] - S[p, c] for the axes a = x, y, z: raw differences, not divided by the spacing; 0 where p + e_a lies
+ *     beyond the grid, and in the sparse form 0 where p + e_a is not kept (index < 0, or a rank that is not in [0, M)).
+ *   n(p,c) = sqrt(d_x^2 + d_y^2 + d_z^2 + eps), eps finite and > 0
+ *   value = (1/N) sum_p sum_c w_c n(p,c),   N = nx ny nz (dense) or M (sparse: the sum runs over the kept points)
+ *   grad[p,c] += scale * d value / d S[p,c]
+ *             = scale * (fp32(w_c / N) * (-(d_x + d_y + d_z)/n(p,c) + sum_a d_a(p - e_a, c)/n(p - e_a, c)))
+ *     over the back neighbours p - e_a that exist (and are kept), in the order x, y, z.  The entry ADDS into the caller's buffer, as
+ *     the march backward does.  scale: a DEVICE pointer to one float, NULL = 1 (an autograd backward hands its upstream gradient over
+ *     without a host read).  A scale that is a power of two scales the added term exactly.
+ * Arithmetic: the differences, squares, the sum ((d_x^2 + d_y^2) + d_z^2) + eps, sqrtf and the quotients are fp32, each rounded on
+ *   its own.  The value is accumulated in fp64 (w_c n(p,c) as a product of doubles) and reduced in a fixed order: a thread over the
+ *   float4s it owns, the lanes of a wave by a butterfly, the four waves of a block in order, and one last block over the block
+ *   partials; sum / N is written as one fp64 (value64) and the same number rounded to fp32 (value32).
+ * Guarantees: no atomics; two calls on equal inputs give equal bytes, value and gradient; the dense entry and the sparse entry with
+ *   every point kept give equal bytes; the library allocates nothing.  workspace: pnr_baked_tv_workspace_bytes() bytes of device
+ *   memory (16 KiB, whatever the volume), 8-byte aligned, needed only when a value is asked for; two calls in flight on different
+ *   streams need one each.  Either half may be asked for alone (grad == NULL; value32 == value64 == NULL); with neither the call is
+ *   a no-op.  M = 0: nothing is read, the value written is 0.  stored and grad must not overlap.
+ * The kernel takes one float4 (point, basis k) per thread -- consecutive lanes read consecutive 16-byte words -- and the thread that
+ *   owns S[p] recomputes the norms of its three back neighbours: a 13-point stencil, nothing stored in between.  Index arithmetic
+ *   is 64-bit; an id outside the grid or a rank outside [0, M) is treated as "not kept": no input makes the kernel read outside
+ *   stored, index or ids.
+ * PNR_E_INVALID before any HIP call, in this order: a degree outside {-1, 0, 1, 2}; index without ids or ids without index; M < 0
+ *   with an index; the grid (every axis >= 2 points, fewer than 2^31 cells; sparse: fewer than 2^31 points); eps not finite or <= 0;
+ *   a null w; a weight that is negative or not finite; a value asked for without a workspace; a null stored with N > 0; stored or
+ *   grad not 16-byte aligned; index, ids, scale or value32 not 4-byte aligned, value64 or workspace not 8-byte aligned. */
+size_t pnr_baked_tv_workspace_bytes(void);
+int pnr_baked_tv(const float *stored, long long M, int degree, const int32_t *index /*nullable: dense*/,
+                 const int32_t *ids /*(M) int32, with index*/, int nx, int ny, int nz, const float *w /*host, E floats*/, float eps,
+                 const float *scale /*device, nullable*/, float *value32 /*device, nullable*/, double *value64 /*device, nullable*/,
+                 float *grad /*device, nullable, the shape of stored; added into*/, void *workspace, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

@@ -593,3 +593,35 @@ def baked_march_autograd(stored, source, degree, reso, c1, c2, step, bits=None, 
                          "detach them")
     return _BakedMarchFunction.apply(stored, tuple(source), degree, index, bits, tuple(reso), tuple(c1), tuple(c2), float(step),
                                      bool(white_bkgd), float(terminate))
+
+
+class _BakedTvFunction(torch.autograd.Function):
+    """The total-variation prior of a baked volume's stored values (include/pixelnerf_hip.h, "Total-variation prior").  forward asks
+    pnr_baked_tv for the value alone, backward for the gradient alone with scale = grad_output left on the device: no host read on
+    either side.  Nothing is consumed, so a second backward is allowed."""
+
+    @staticmethod
+    def forward(ctx, stored, degree, reso, weights, eps, index, ids):
+        value32, _ = ops.baked_tv(stored, degree, reso, weights, eps=eps, index=index, ids=ids, want_value=True)
+        ctx.save_for_backward(stored)
+        ctx.tv = (degree, reso, weights, eps, index, ids)
+        return value32
+
+    @staticmethod
+    def backward(ctx, g):
+        (stored,) = ctx.saved_tensors
+        degree, reso, weights, eps, index, ids = ctx.tv
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        d_stored = torch.zeros_like(stored, memory_format=torch.contiguous_format)
+        ops.baked_tv(stored.detach(), degree, reso, weights, eps=eps, index=index, ids=ids, want_value=False, grad_out=d_stored,
+                     scale=g.detach().reshape(1).float())
+        return (d_stored,) + (None,) * 6
+
+
+def baked_tv_autograd(stored, degree, reso, weights, eps=1e-8, index=None, ids=None):
+    """-> the total variation of `stored` (ops.baked_tv's value32, a 0-dim fp32 tensor), differentiable with respect to `stored`
+    (fp32: (nx,ny,nz,4) at degree None, (nx,ny,nz,B,4) at degree 0, 1, 2, or with `index` and `ids` the kept rows of a sparse volume)"""
+    if not isinstance(stored, torch.Tensor) or stored.dtype != torch.float32:
+        raise TypeError("baked_tv_autograd: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
+    return _BakedTvFunction.apply(stored, degree, tuple(reso), tuple(float(w) for w in weights), float(eps), index, ids)

@@ -1617,6 +1617,83 @@ def baked_render_views_backward(poses, width, height, focal, c, z_near, z_far, s
                            white_bkgd, terminate, d_rgb, d_depth, d_alpha, out, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
+# ---- the total-variation prior of a fitted volume (include/pixelnerf_hip.h, "Total-variation prior")
+
+def baked_tv(stored, degree, reso, weights, eps=1e-8, index=None, ids=None, want_value=True, grad_out=None, scale=None):
+    """Total variation of the stored values of a baked volume and its gradient (pnr_baked_tv): stored fp32 (nx,ny,nz,4) (degree None
+    / -1) or (nx,ny,nz,B,4) (degree 0, 1, 2), or with `index` (nx,ny,nz) int32 and `ids` (M,) int32 (sparse_points) the kept rows
+    (M,4) / (M,B,4); weights: E = 4 or 4 B floats, finite and >= 0, one per element of a row.
+    value = (1/N) sum_p sum_c w_c sqrt(d_x^2 + d_y^2 + d_z^2 + eps) over the raw forward differences (0 beyond the grid and, sparse,
+    where either end is not kept), N = nx ny nz or M.
+    -> (value32, value64): 0-dim fp32 and fp64 tensors on the device, or (None, None) with want_value=False.
+    grad_out: a contiguous fp32 tensor of stored's shape that scale * d value / d stored is ADDED into (None: no gradient is
+    computed); scale: None (1), a number, or a one-element fp32 tensor on the device, which is read by the kernel -- no host read.
+    No atomics: the same bytes on every call.  An fp16 volume and a non-contiguous `stored` are refused."""
+    import math
+    what = "baked_tv"
+    lib = _lib.load()
+    if isinstance(stored, torch.Tensor) and stored.dtype == torch.float16:
+        raise TypeError(f"{what}: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
+    degree = -1 if degree is None else int(degree)
+    if degree not in (-1, 0, 1, 2):
+        raise ValueError(f"{what}: degree must be None / -1 (RGBA), 0, 1 or 2, got {degree}")
+    if len(reso) != 3:
+        raise ValueError(f"{what}: reso must have 3 entries")
+    dims = tuple(int(r) for r in reso)
+    if lib.pnr_occupancy_bytes(*dims) == 0:
+        raise ValueError(f"{what}: a grid needs at least 2 points per axis and fewer than 2^31 cells, got {dims}")
+    if (index is None) != (ids is None):
+        raise ValueError(f"{what}: index and ids go together (both for the kept rows of a sparse volume, neither for a dense one)")
+    sparse = index is not None
+    tail = (4,) if degree < 0 else ((degree + 1) ** 2, 4)
+    lead = (None,) if sparse else dims
+    if not isinstance(stored, torch.Tensor) or stored.dim() != len(lead) + len(tail) or tuple(stored.shape[len(lead):]) != tail \
+            or (not sparse and tuple(stored.shape[:3]) != dims):
+        raise ValueError(f"{what}: stored must be ({'M' if sparse else ','.join(str(d) for d in dims)},{','.join(str(s) for s in tail)}) at "
+                         f"degree {degree}, got {tuple(stored.shape) if isinstance(stored, torch.Tensor) else type(stored).__name__}")
+    if not stored.is_contiguous():
+        raise ValueError(f"{what}: stored must be contiguous (the kernel walks it as rows of float4; call .contiguous() on a copy you keep)")
+    E = 4 * (1 if degree < 0 else (degree + 1) ** 2)
+    w = [float(x) for x in (weights.flatten().tolist() if isinstance(weights, torch.Tensor) else weights)]
+    if len(w) != E or not all(math.isfinite(x) and x >= 0.0 for x in w):
+        raise ValueError(f"{what}: weights must be {E} finite numbers >= 0 (one per element of a row), got {w}")
+    eps = float(eps)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"{what}: eps must be finite and > 0, got {eps}")
+    stored = _f32(stored.detach(), "stored", lead + tail)
+    dev = stored.device
+    if stored.numel() and stored.data_ptr() % 16:
+        raise ValueError(f"{what}: stored must be 16-byte aligned")
+    M = stored.shape[0] if sparse else 0
+    if sparse:
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims or index.device != dev:
+            raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {dev}")
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or tuple(ids.shape) != (M,) or ids.device != dev:
+            raise ValueError(f"{what}: ids must be the ({M},) int32 tensor of sparse_points on {dev}")
+        index = index.contiguous()
+        ids = ids.contiguous() if M else torch.zeros((1,), dtype=torch.int32, device=dev)  # (no rows: a pointer that is not null)
+    if grad_out is not None and (not isinstance(grad_out, torch.Tensor) or grad_out.dtype != torch.float32 or grad_out.shape != stored.shape
+                                 or grad_out.device != dev or not grad_out.is_contiguous() or grad_out.requires_grad):
+        raise ValueError(f"{what}: grad_out must be a contiguous float32 tensor of shape {tuple(stored.shape)} on {dev} that does not "
+                         "require grad (it is added into)")
+    if scale is not None and not isinstance(scale, torch.Tensor):
+        scale = torch.full((1,), float(scale), dtype=torch.float32, device=dev)
+    if scale is not None:
+        if scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != dev:
+            raise ValueError(f"{what}: scale must be one float32 number on {dev}")
+        scale = scale.detach().contiguous()
+    value32 = torch.empty((), dtype=torch.float32, device=dev) if want_value else None
+    value64 = torch.empty((), dtype=torch.float64, device=dev) if want_value else None
+    workspace = torch.empty((lib.pnr_baked_tv_workspace_bytes() // 8,), dtype=torch.float64, device=dev) if want_value else None
+    if want_value or grad_out is not None:
+        some = stored.numel() > 0
+        with torch.cuda.device(dev):
+            _lib.check(lib.pnr_baked_tv(_p(stored) if some else None, M, degree, _p(index) if sparse else None, _p(ids) if sparse else None,
+                                        dims[0], dims[1], dims[2], (ctypes.c_float * E)(*w), eps, _p(scale), _p(value32), _p(value64),
+                                        _p(grad_out) if grad_out is not None and some else None, _p(workspace), _stream()), "pnr_baked_tv")
+    return value32, value64
+
+
 def philox_noise_ids(ray_ids, n_coarse, n_fine, n_fine_depth, seed):
     """philox_noise for a list of GLOBAL ray ids (pnr_philox_noise_ids): ray_ids (R,) int64 HIP tensor -- any order, repeats
     allowed, beyond 2^31 too -- -> the dict philox_noise returns, row r holding what the seeded renderer entries draw for ray

@@ -136,6 +136,19 @@ def _bake(what, net, c1, c2, reso, dtype, coarse, eval_batch_size, sparse=False,
     return stored, (reso, c1, c2), kept
 
 
+def _tv_weights(what, degree, rgb, sigma, sh):
+    """the per-element weights of ops.baked_tv: (rgb, rgb, rgb, sigma) for the RGBA row or the DC basis row, and `sh` -- one number
+    for every channel, None = the DC weights -- for the basis rows k >= 1"""
+    import math
+    rgb, sigma = float(rgb), float(sigma)
+    dc = [rgb, rgb, rgb, sigma]
+    higher = dc if sh is None else [float(sh)] * 4
+    weights = dc + higher * (0 if degree is None else (int(degree) + 1) ** 2 - 1)
+    if not all(math.isfinite(w) and w >= 0.0 for w in weights):
+        raise ValueError(f"{what}: the weights rgb, sigma and sh must be finite and >= 0, got {rgb}, {sigma}, {sh}")
+    return weights
+
+
 class _Baked:
     """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2) and
     the storage methods.  A subclass names the tensor it stores (`_stored_name`: the attribute, and the key of its state) and has a
@@ -167,6 +180,19 @@ class _Baked:
         and `forward_views(...)` render with gradients attached, `.volume()` gives the fitted volume back (`fit` is the loop around
         it).  An fp16 volume is refused: fit in fp32 and call `half()` afterwards."""
         return TrainableBaked(self)
+
+    def tv(self, rgb=1.0, sigma=1.0, sh=None, eps=1e-8):
+        """the total variation of the stored values as a float (ops.baked_tv's fp32 value, under no_grad): what
+        `trainable().tv(...)` returns with gradients attached; the weights are explained there.  An fp16 volume is refused."""
+        from .. import ops
+        name = type(self).__name__
+        if self.dtype != torch.float32:
+            raise TypeError(f"{name}.tv: {_FP32_ONLY}")
+        sparse = self._stored_name == "rows"
+        with torch.no_grad():
+            value32, _ = ops.baked_tv(self._stored(), self.degree, self.reso, _tv_weights(f"{name}.tv", self.degree, rgb, sigma, sh),
+                                      eps=eps, index=self.index if sparse else None, ids=self.ids if sparse else None)
+        return float(value32)
 
     def state_dict(self):
         """the stored tensor under its name (a degree follows from its shape), the geometry and the skip threshold; the skip grid is
@@ -596,7 +622,8 @@ class TrainableBaked(torch.nn.Module):
     atomics).  An fp16 volume is refused: fit in fp32 and call `half()` afterwards.
     `skip=True` marches against the skip grid of the volume `trainable()` was called on, as it was then: the cells it calls empty
     receive no gradient and stay as they are -- fitting with skip=True FREEZES the empty cells; with skip=False (the default) every
-    cell a ray crosses can change.  A sparse volume holds nothing else, so it always marches against its grid."""
+    cell a ray crosses can change.  A sparse volume holds nothing else, so it always marches against its grid.
+    `tv(...)` is the smoothness prior a fit to few views needs: the total variation of `stored`, differentiable, with no atomics."""
 
     def __init__(self, volume):
         super().__init__()
@@ -637,18 +664,36 @@ class TrainableBaked(torch.nn.Module):
         rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, white_bkgd, terminate, skip)
         return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
 
+    def tv(self, rgb=1.0, sigma=1.0, sh=None, eps=1e-8):
+        """The total-variation prior of the stored values (include/pixelnerf_hip.h, "Total-variation prior"): a 0-dim fp32 tensor,
+        differentiable with respect to `stored` (autograd.baked_tv_autograd; no atomics: value and gradient are bit-reproducible).
+        (1/N) sum over points and elements of weight x sqrt(d_x^2 + d_y^2 + d_z^2 + eps), the d raw differences to the next grid
+        point; N the number of grid points (a sparse volume: of kept points, and a difference to a dropped point is 0).
+        :param rgb weighs channels 0..2 of the RGBA row or of the DC basis row
+        :param sigma weighs channel 3 of the same row
+        :param sh weighs every channel of the basis rows k >= 1; None: the DC weights"""
+        from .. import autograd
+        v = self._source
+        sparse = v._stored_name == "rows"
+        return autograd.baked_tv_autograd(self.stored, v.degree, v.reso, _tv_weights("TrainableBaked.tv", v.degree, rgb, sigma, sh), eps=eps,
+                                          index=v.index if sparse else None, ids=v.ids if sparse else None)
+
     def volume(self):
         """a fresh volume of the current values: checked as its constructor checks (a non-finite value raises ValueError) and with
         its skip grid rebuilt from them (a sparse volume keeps its occupancy grid, index and ids: its kept set does not grow)"""
         return self._source._around(self.stored.detach().clone())
 
 
-def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=None, white_bkgd=False, terminate=None, skip=False):
+def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=None, white_bkgd=False, terminate=None, skip=False,
+        tv_rgb=0.0, tv_sigma=0.0, tv_sh=None, tv_eps=1e-8):
     """Fit a baked volume to colours: Adam on `volume.trainable()` over `steps` batches of `batch` rays drawn with replacement from
     rays (...,8) by a CPU torch.Generator seeded with `seed`, loss = mean((rgb - target_rgb)^2) over the batch.  After every step
     an RGBA volume (BakedVolume, RGBA rows) is projected back onto what it stores: rgb into [0,1], sigma >= 0; a coefficient volume
     is left alone (its clamps are part of the march).  step, white_bkgd, terminate, skip: as TrainableBaked.forward (skip=True
     freezes the cells the volume's skip grid calls empty).
+    tv_rgb, tv_sigma, tv_sh, tv_eps: the total-variation prior, `TrainableBaked.tv`'s rgb, sigma, sh and eps: when any weight is > 0
+    the step's loss is mse + module.tv(...) (`losses` keeps reporting the mse alone); with all of them 0 -- the default -- no TV call
+    is made.
     -> (the fitted volume -- a new one, `volume` is unchanged --, losses: the `steps` batch losses as floats, read once at the end)"""
     if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
         raise ValueError("fit: rays must be (...,8)")
@@ -659,6 +704,8 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
     if steps < 0 or batch < 1:
         raise ValueError(f"fit: steps must be >= 0 and batch >= 1, got {steps}, {batch}")
     module = volume.trainable()
+    prior = dict(rgb=tv_rgb, sigma=tv_sigma, sh=tv_sh, eps=tv_eps)
+    use_prior = any(w > 0 for w in _tv_weights("fit", volume.degree, tv_rgb, tv_sigma, tv_sh))
     rays, target = rays.detach().reshape(-1, 8).float(), target_rgb.detach().reshape(-1, 3).float()
     R = rays.shape[0]
     if R == 0:
@@ -671,7 +718,7 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
         out = module(rays[ids], step=step, white_bkgd=white_bkgd, terminate=terminate, skip=skip)
         loss = ((out.rgb - target[ids]) ** 2).mean()
         optimiser.zero_grad(set_to_none=True)
-        loss.backward()
+        (loss + module.tv(**prior) if use_prior else loss).backward()
         optimiser.step()
         if volume.degree is None:
             with torch.no_grad():
