@@ -1157,7 +1157,8 @@ int pnr_baked_sparse_half_render_views(const float *poses /*(NV,4,4)*/, int NV, 
  *   empty cells, and cannot grow density in them.  Without bits such a sample reaches sigma like any other.
  * This is the one path of the baked family that is NOT bit-reproducible from run to run: the order in which the atomics of
  *   different samples arrive varies, so a sum can differ in its last bits.
- * No gradient is given with respect to rays, poses, step or the geometry.  fp32 storage only: there is no fp16 entry (fit the fp32
+ * These two entries give no gradient with respect to rays or poses (pnr_baked_ray_backward_* below do); none exists with respect
+ *   to step or the geometry.  fp32 storage only: there is no fp16 entry (fit the fp32
  *   volume, round it afterwards).  No workspace.
  * PNR_E_INVALID, before any HIP call, in the order and with the words of the march entries: a degree outside {-1, 0, 1, 2}; bad
  *   sizes, a null or misaligned ray / pose array; M < 0 with an index; the grid and march settings; a null d_stored or stored, an
@@ -1175,6 +1176,64 @@ int pnr_baked_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W, int
                              int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd, float terminate,
                              const float *d_rgb /*(NV H W,3), nullable*/, const float *d_depth /*nullable*/,
                              const float *d_alpha /*nullable*/, float *d_stored, void *stream);
+
+/* Gradients of the baked march with respect to the RAYS (added within ABI rev 12 as well): what lets a caller register a camera
+ * against a baked volume -- move a pose by gradient descent until the march matches an image.  (The sentence above, "no gradient
+ * with respect to rays", stays true of pnr_baked_backward_*; these two entries are that gradient.)
+ * pnr_baked_ray_backward_rays / pnr_baked_ray_backward_views are the backward of EVERY march above: `stored` is what
+ *   pnr_baked_backward_* calls `stored` (degree -1: (nx,ny,nz,4); 0, 1, 2: (nx,ny,nz,B,4); index != NULL: the M kept rows, bits then
+ *   mandatory), as fp32 (storage_half 0) or as fp16 (storage_half 1: four fp16 numbers per (r,g,b,sigma), widened exactly on load).
+ *   The volume is not differentiated here, so a half volume is a legitimate target, and gives the BYTES of the call on the widened
+ *   values.  d_rgb, d_depth, d_alpha: as pnr_baked_backward_*.
+ * d_rays: (R,8) fp32, dL/d [ox,oy,oz,dx,dy,dz,near,far].  EVERY row is WRITTEN (not added into): a ray with no samples, a ray that
+ *   misses the box and a ray whose upstream gradients are all exactly zero get a row of exact zeros; the caller zeroes nothing.
+ *   The views form regenerates each ray from the camera as the march does and writes the gradient with respect to that regenerated
+ *   ray, rows ordered (view, row, column): pnr_gen_rays_backward applied to it is the gradient with respect to the poses.
+ * The samples are EXACTLY the forward's, found by the device functions of the forward and of pnr_baked_backward_*; g_i, S_i, T_i,
+ *   w_i, dL/da_i, dL/dsigma_i and dL/dc_i are those of pnr_baked_backward_*, by the same walk and the same reverse scan.  Then,
+ *   with the corner values v[ix][iy][iz] of the sample's cell (clamped, for a view-dependent volume) and (fx, fy, fz) its fractions:
+ *     d val / d fz = the x,y-blend of (v[..][..][1] - v[..][..][0])
+ *     d val / d fy = the x-blend of the z-blended (y1 - y0)
+ *     d val / d fx = vy[1] - vy[0]
+ *     d val / d p_a = (d val / d f_a) / h_a, times the derivative of f's clamp (torch.clamp's convention: 1 on the closed [0,1])
+ *     dL/dp_i = sum_c dL/dval_{i,c} d val_c / d p,   dL/dval_i = (w_i d_rgb.r, w_i d_rgb.g, w_i d_rgb.b, dL/dsigma_i)
+ *     dL/dt_i = dL/dp_i . d + d_depth w_i            (depth = sum w_i t_i, and t_i = near + (i + 1/2) step moves with near alone)
+ *     d_o = sum_i dL/dp_i,   d_d = sum_i t_i dL/dp_i,   d_near = sum_i dL/dt_i,   d_far = 0
+ *   A view-dependent volume (degree >= 1) adds the way through the basis: dL/dY_k = sum over samples and corners of (trilinear
+ *   weight) x (the clamps' derivative, as pnr_baked_backward_* forms it) x coef[point][k] . dL/dval for k = 1..B-1, and
+ *     d_d += (I - n n^T) / |d| . sum_k dL/dY_k grad Y_k(n),   n = d / |d|, with
+ *     grad Y_1 = (0, s3, 0)   grad Y_2 = (0, 0, s3)   grad Y_3 = (s3, 0, 0)   grad Y_4 = s15 (y, x, 0)   grad Y_5 = s15 (0, z, y)
+ *     grad Y_6 = (0, 0, 3 s5 z)   grad Y_7 = s15 (z, 0, x)   grad Y_8 = s15 (x, -y, 0)      (s3 = sqrt 3, s5 = sqrt 5, s15 = sqrt 15)
+ *   A direction whose squared norm is 0 or not finite has Y_k = 0 for k >= 1 and gets no such term.
+ * Treated as CONSTANTS: the number of samples n = ceil((far - near) / step) -- far enters through it alone, so d_far is exactly 0 --,
+ *   the inside-the-box test, the skip bits, the sparse row lookup, the chunk the march stops after (terminate), the cell floor()
+ *   names, and which side of each clamp a value lies on.  The march is piecewise smooth in the ray: the gradient is the exact
+ *   derivative almost everywhere, and for a sample ON a cell plane the one-sided derivative of the cell the floor convention puts
+ *   it in (a caller comparing against another precision must keep samples off the planes: the two may name different cells).
+ * Arithmetic: the per-sample part (the point, the blend and its partials, dL/dval, dL/dp) is fp32, each operation rounded on its
+ *   own.  What runs ALONG the ray is carried in fp64: alpha is a_i = -expm1f(-step sigma_i) in fp32 and the factor 1 - a_i + 1e-10
+ *   a double, and the products T_i, the affine maps of S_i and the seven sums of the row are doubles, rounded to fp32 once at the
+ *   end.  The forward's fp32 chain is not used for them: over thousands of samples expf's rounding of a number next to 1 and the
+ *   rounding of every factor make T drift by 1e-6 .. 3e-5, which a sum whose terms cancel (d_o across a blob) does not average
+ *   away (profiles/baked_notes.md, "Ray gradients and registration").  The alphas differ from the forward's by less than an ulp of
+ *   1; where the forward STOPPED (terminate) is decided by its own fp32 factors, formed with its operations.
+ * Everything a ray's samples contribute is summed inside the ray's own wavefront -- per lane over the chunks, then across the 64
+ *   lanes in a fixed butterfly order -- and one lane writes the row: no atomics, no LDS, no workspace; two calls on equal inputs
+ *   give equal bytes, and the sparse entry gives the bytes of the dense entry with the same bits.
+ * PNR_E_INVALID, before any HIP call, in the order and with the words of pnr_baked_backward_*, d_rays in the place of d_stored
+ *   ("null argument"; "bits, d_rgb, d_depth, d_alpha and d_rays must be 4-byte aligned"), and after the degree rule one more:
+ *   "storage_half must be 0 or 1".  R = 0 (NV = 0): no-op, PNR_OK. */
+int pnr_baked_ray_backward_rays(const float *rays, long long R, const void *stored, int storage_half, long long M, int degree,
+                                const int32_t *index /*nullable: dense*/, const uint32_t *bits /*nullable when dense*/, int nx, int ny,
+                                int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                                const float *d_rgb /*(R,3), nullable*/, const float *d_depth /*(R), nullable*/,
+                                const float *d_alpha /*(R), nullable*/, float *d_rays /*(R,8), every row written*/, void *stream);
+int pnr_baked_ray_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                 float z_near, float z_far, const void *stored, int storage_half, long long M, int degree,
+                                 const int32_t *index /*nullable: dense*/, const uint32_t *bits /*nullable when dense*/, int nx, int ny,
+                                 int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, int white_bkgd, float terminate,
+                                 const float *d_rgb /*(NV H W,3), nullable*/, const float *d_depth /*nullable*/,
+                                 const float *d_alpha /*nullable*/, float *d_rays /*(NV H W,8), every row written*/, void *stream);
 
 /* Total-variation prior of a fitted volume (added within ABI rev 12 as well): the smoothness term a fit to few views needs, its
  * value and its gradient in one pass, with no atomics.  `stored` is what pnr_baked_backward_* calls `stored`: fp32 (nx,ny,nz,4)

@@ -222,6 +222,10 @@ PROTOTYPES = {
                                      ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P, _P, _P]),
     "pnr_baked_backward_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, ctypes.c_longlong, _I, _P, _P, _I, _I, _I,
                                       ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P, _P, _P]),
+    "pnr_baked_ray_backward_rays": (_I, [_P, ctypes.c_longlong, _P, _I, ctypes.c_longlong, _I, _P, _P, _I, _I, _I, ctypes.POINTER(_F),
+                                         ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P, _P, _P]),
+    "pnr_baked_ray_backward_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _I, ctypes.c_longlong, _I, _P, _P, _I, _I, _I,
+                                          ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P, _P, _P]),
     "pnr_baked_tv_workspace_bytes": (_SZ, []),
     "pnr_baked_tv": (_I, [_P, ctypes.c_longlong, _I, _P, _P, _I, _I, _I, ctypes.POINTER(_F), _F, _P, _P, _P, _P, _P, _P]),
     "pnr_profile_enable": (_I, [_I]),

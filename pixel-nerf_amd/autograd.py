@@ -595,6 +595,74 @@ def baked_march_autograd(stored, source, degree, reso, c1, c2, step, bits=None, 
                                      bool(white_bkgd), float(terminate))
 
 
+def _baked_forward(stored, source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate):
+    """the inference entry of a stored tensor: which ops function marches follows from the dtype, the degree and the index"""
+    views = "" if len(source) == 1 else "_views"
+    tail = dict(white_bkgd=white_bkgd, terminate=terminate)
+    half = "half_" if stored.dtype == torch.float16 else ""
+    if index is not None:
+        return getattr(ops, f"baked_sparse_{half}render{views}")(*source, stored, degree, index, bits, reso, c1, c2, step, **tail)
+    if half:
+        return getattr(ops, "baked_half_render" + views)(*source, stored, degree, reso, c1, c2, step, bits=bits, **tail)
+    if degree is None or degree < 0:
+        return getattr(ops, "baked_render" + views)(*source, stored, reso, c1, c2, step, bits=bits, **tail)
+    return getattr(ops, "baked_sh_render" + views)(*source, stored, degree, reso, c1, c2, step, bits=bits, **tail)
+
+
+class _BakedMarchRaysFunction(torch.autograd.Function):
+    """The baked-volume ray march, differentiable with respect to its RAYS or POSES (include/pixelnerf_hip.h, "Gradients of the baked
+    march with respect to the RAYS") and, for an fp32 volume that requires grad, with respect to the stored values too.  forward IS
+    the inference entry; backward one pnr_baked_ray_backward_* launch (no atomics: the same bytes on every call), for a camera
+    followed by ops.gen_rays_backward, and one pnr_baked_backward_* launch when `stored` asks for its gradient."""
+
+    @staticmethod
+    def forward(ctx, stored, lead, rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate):
+        ctx.set_materialize_grads(False)
+        out = _baked_forward(stored, (lead,) + rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate)
+        ctx.save_for_backward(stored, lead)
+        ctx.march = (rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_alpha):
+        stored, lead = ctx.saved_tensors
+        rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate = ctx.march
+        if d_rgb is None and d_depth is None and d_alpha is None:
+            return (None,) * 12
+        fp32 = lambda g: None if g is None else g.contiguous().float()
+        source = (lead.detach(),) + rest
+        kw = dict(d_rgb=fp32(d_rgb), d_depth=fp32(d_depth), d_alpha=fp32(d_alpha), bits=bits, index=index, white_bkgd=white_bkgd,
+                  terminate=terminate)
+        d_stored = d_lead = None
+        if ctx.needs_input_grad[0]:
+            entry = ops.baked_render_backward if not rest else ops.baked_render_views_backward
+            d_stored = entry(*source, stored.detach(), degree, reso, c1, c2, step, **kw)
+        if ctx.needs_input_grad[1]:
+            if not rest:
+                d_lead = ops.baked_ray_backward(*source, stored.detach(), degree, reso, c1, c2, step, **kw)
+            else:
+                W, H, focal, c = rest[:4]
+                d_rays = ops.baked_ray_backward_views(*source, stored.detach(), degree, reso, c1, c2, step, **kw)
+                d_lead = ops.gen_rays_backward(d_rays, W, H, focal, c)
+        return (d_stored, d_lead) + (None,) * 10
+
+
+def baked_march_rays_autograd(stored, source, degree, reso, c1, c2, step, bits=None, index=None, white_bkgd=False, terminate=0.0):
+    """-> (rgb (R,3), depth (R,), alpha (R,)) of the baked march -- the bytes of the inference entry --, differentiable with respect
+    to source[0]: the rays (R,8) of source = (rays,), or the poses (NV,4,4) of the camera source = (poses, W, H, focal, c, z_near,
+    z_far) (through ops.gen_rays_backward).  `stored` is fp32 or fp16; an fp32 `stored` that requires grad gets its gradient as well
+    (pnr_baked_backward_*: fp32 atomics), an fp16 one that requires grad is refused."""
+    if not isinstance(stored, torch.Tensor) or stored.dtype not in (torch.float32, torch.float16):
+        raise TypeError("baked_march_rays_autograd: stored must be a float32 or float16 tensor")
+    if stored.dtype == torch.float16 and stored.requires_grad:
+        raise TypeError("baked_march_rays_autograd: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
+    source = tuple(source)
+    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
+        raise ValueError("baked_march_rays_autograd: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
+    return _BakedMarchRaysFunction.apply(stored, source[0], source[1:], degree, index, bits, tuple(reso), tuple(c1), tuple(c2), float(step),
+                                         bool(white_bkgd), float(terminate))
+
+
 class _BakedTvFunction(torch.autograd.Function):
     """The total-variation prior of a baked volume's stored values (include/pixelnerf_hip.h, "Total-variation prior").  forward asks
     pnr_baked_tv for the value alone, backward for the gradient alone with scale = grad_output left on the device: no host read on

@@ -22,6 +22,9 @@
 // five lines, in place in the forward and as baked_sample_count in the backward).  The
 // backward is the ONE path here with atomics (fp32 atomicAdd into the caller's zeroed buffer): not bit-reproducible from run to run.
 // fp32 storage only; baked_check holds the checks of both directions.
+// Ray backward (pnr_baked_ray_backward_rays / _views: dL/d rays, what registering a camera needs): baked_march_ray_bwd_kernel, the
+// same walk over the same samples, through the spatial derivative of the blend (baked_blend_grad) instead of its corner weights;
+// every storage and layout (the forward's 16 instantiations), no atomics, every row written.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -476,6 +479,324 @@ baked_march_bwd_kernel(const RaySrc rs, long long R, const BakedParams q, const 
         }
     }
 }
+
+// ---- backward of the march with respect to the RAYS (pnr_baked_ray_backward_*; every storage): what registering a camera against
+// a volume needs.  The walk, the samples and g_i, S_i, T_i, w_i, dL/da_i, dL/dsigma_i, dL/dc_i are baked_march_bwd_kernel's; what
+// a sample sends back goes through the SPATIAL derivative of the blend instead of its corner weights:
+//   dL/dp_i = sum_c dL/dval_{i,c} (d val_c / d f_a) / h_a,   dL/dval_i = (w_i d_rgb, dL/dsigma_i)
+//   dL/dt_i = dL/dp_i . d + d_depth w_i                       (depth = sum w_i t_i; t_i moves with near alone)
+//   d_o += dL/dp_i,  d_d += t_i dL/dp_i,  d_near += dL/dt_i,  d_far = 0
+// and, for a view-dependent volume, dL/dY_k through Y(d / |d|) to d_d.  n, the inside test, the skip bits, the stop chunk, the cell
+// and the regions of the clamps are constants: the exact derivative wherever the march is smooth in the ray, and on a cell plane
+// the one-sided derivative of the cell that floor() names.  Everything of a ray is summed in its own wave (per-lane sums over the
+// chunks, then wave_sum's butterfly, in fp64) and one lane writes the row: no atomics, no LDS, no workspace, the same bytes on every call,
+// and EVERY row is written (exact zeros for a ray with no samples or no upstream gradient): the caller zeroes nothing.
+
+__device__ __forceinline__ float4 baked_sub(const float4 b, const float4 a) { return make_float4(b.x - a.x, b.y - a.y, b.z - a.z, b.w - a.w); }
+__device__ __forceinline__ float baked_dot(const float4 a, const float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// the blend and its partials along the fractions f: x = (vy[1] - vy[0]), y = the x-blend of the z-blended (y1 - y0), z = the
+// x,y-blend of (v[..][..][1] - v[..][..][0]).  val is baked_blend's: the same operations on the same values
+struct BakedBlendGrad {
+    float4 val, x, y, z;
+};
+
+// a pair of corners along z, reduced: its value at f[2] and its slope
+struct BakedPairGrad {
+    float4 v, z;
+};
+template <class Corner>
+__device__ __forceinline__ BakedPairGrad baked_pair_grad(const Corner &corner, long long row, float fz) {
+    const float4 c0 = corner.at(row), c1 = corner.at(row + 1);
+    return {baked_lerp(c0, c1, fz), baked_sub(c1, c0)};
+}
+
+// two reduced pairs (iy = 0, 1) of one ix, reduced along y: value, slope along y, slope along z
+struct BakedFaceGrad {
+    float4 v, y, z;
+};
+__device__ __forceinline__ BakedFaceGrad baked_face_grad(const BakedPairGrad &p0, const BakedPairGrad &p1, float fy) {
+    return {baked_lerp(p0.v, p1.v, fy), baked_sub(p1.v, p0.v), baked_lerp(p0.z, p1.z, fy)};
+}
+
+template <class Corner, class Rows>
+__device__ __forceinline__ BakedBlendGrad baked_blend_grad(const Corner &corner, const Rows &rows, const BakedCell<Rows> &cell,
+                                                           const float (&f)[3]) {
+    BakedFaceGrad face[2];
+    // baked_blend's three forms: as many pairs in flight as the forward keeps (the slopes are differences of what it reads)
+    if constexpr (Corner::PAIRS_IN_FLIGHT == 4) {
+        const BakedPairGrad p00 = baked_pair_grad(corner, cell.row(rows, 0), f[2]), p01 = baked_pair_grad(corner, cell.row(rows, 1), f[2]),
+                            p10 = baked_pair_grad(corner, cell.row(rows, 2), f[2]), p11 = baked_pair_grad(corner, cell.row(rows, 3), f[2]);
+        face[0] = baked_face_grad(p00, p01, f[1]);
+        face[1] = baked_face_grad(p10, p11, f[1]);
+    } else if constexpr (Corner::PAIRS_IN_FLIGHT == 2) {
+#pragma unroll 1
+        for (int ix = 0; ix < 2; ++ix) {
+            const BakedPairGrad p0 = baked_pair_grad(corner, cell.row(rows, 2 * ix), f[2]);
+            const BakedPairGrad p1 = baked_pair_grad(corner, cell.row(rows, 2 * ix + 1), f[2]);
+            face[1] = baked_face_grad(p0, p1, f[1]);
+            if (ix == 0) face[0] = face[1];
+        }
+    } else {
+        BakedPairGrad last = {};
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {  // pair j = 2 ix + iy
+            const BakedPairGrad p = baked_pair_grad(corner, cell.row(rows, j), f[2]);
+            if (j & 1) {
+                face[1] = baked_face_grad(last, p, f[1]);
+                if (j == 1) face[0] = face[1];
+            }
+            last = p;
+        }
+    }
+    return {baked_lerp(face[0].v, face[1].v, f[0]), baked_sub(face[1].v, face[0].v), baked_lerp(face[0].y, face[1].y, f[0]),
+            baked_lerp(face[0].z, face[1].z, f[0])};
+}
+
+// d f_a / d u_a of a sample, f = clamp(u - cell, 0, 1) under torch.clamp's convention: 1 on the closed range, 0 outside and for a
+// NaN.  u - cell is formed again with baked_sample's operations (the clamped f cannot tell 0 from "below 0")
+__device__ __forceinline__ void baked_frac_slope(const Ray8 &ray, const BakedParams &q, const BakedSample &s, float (&slope)[3]) {
+    const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p = o[a] + s.t * d[a];
+        const float raw = (p - q.g.c1[a]) / q.g.h[a] - (float)s.idx[a];
+        slope[a] = raw >= 0.f && raw <= 1.f ? 1.f : 0.f;
+    }
+}
+
+// alpha and the transmittance factor for the ray gradient: a = -expm1f(-step sigma) in fp32, tf = 1 - a + 1e-10 in fp64, and the
+// products of tf (T) and the affine maps of S carried in fp64.  Two things the forward's fp32 chain does to a LONG ray (measured on
+// the 4500-sample case, tests/test_hip_baked_ray_grad.py): baked_alpha's 1 - expf(-x) carries expf's rounding of a number next to 1
+// into a, and where that rounding leans one way (gfx950: a tenth of an ulp low below x = 3e-3) thousands of factors of T lean with
+// it -- 2.6e-5 of T after 4500 thin samples --; and each factor rounded to fp32 moves T by up to 3e-8, a random walk of 1e-6 .. 3e-6
+// by the end of the ray.  Neither averages away in a sum over samples whose terms cancel (d_o across a blob: 880 to 1 on one ray of
+// that case), because the drift weighs the front of the ray and its back differently.  The derivative is taken of the march as the
+// header defines it, not of those roundings: the alphas differ from the forward's by less than an ulp of 1, with the same exact 0
+// for sigma == 0 and the same 1 for an opaque sample.  Where the forward STOPPED is still decided by its own fp32 factors.
+struct BakedAlphaExact {
+    float a, ex;  // ex = 1 - a = d alpha / d sigma / step
+    double tf;
+};
+__device__ __forceinline__ BakedAlphaExact baked_alpha_exact(float step, float sigma) {
+    BakedAlphaExact r;
+    r.a = -expm1f(-(step * sigma));
+    r.ex = 1.f - r.a;
+    r.tf = 1.0 - (double)r.a + 1e-10;
+    return r;
+}
+
+// pnr_wave.h's wave_scan_mul and wave_rscan_affine on doubles: the same lanes in the same order
+__device__ __forceinline__ double wave_scan_mul64(double v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double t = __shfl_up(v, o, 64);
+        if (lane >= o) v *= t;
+    }
+    return v;
+}
+__device__ __forceinline__ void wave_rscan_affine64(double &m, double &b, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double mt = __shfl_down(m, o, 64), bt = __shfl_down(b, o, 64);
+        if (lane + o < 64) {
+            b += m * bt;
+            m *= mt;
+        }
+    }
+}
+
+// the factor of sample s for the fp64 product: 1 where the forward's is exactly 1 (not active, or no rows)
+template <class Corner, class Rows>
+__device__ __forceinline__ double baked_tf_exact(const BakedParams &q, const Corner &corner, const Rows &rows, const BakedSample &s,
+                                                 float &sigma) {
+    BakedCell<Rows> cell;
+    bool found;
+    sigma = baked_value(q, corner, rows, s, cell, found).w;
+    return found ? baked_alpha_exact(q.step, sigma).tf : 1.0;
+}
+
+// baked_chunk_product with those factors
+template <class Corner, class Rows>
+__device__ __forceinline__ double baked_chunk_product_exact(const Ray8 &ray, const BakedParams &q, const Corner &corner, const Rows &rows, int c,
+                                                            int n, int lane) {
+    const BakedSample s = baked_sample(ray, q, c * 64 + lane, n);
+    if (__ballot(s.active) == 0ull) return 1.0;
+    float sigma;
+    return __shfl(wave_scan_mul64(baked_tf_exact(q, corner, rows, s, sigma), lane), 63, 64);
+}
+
+// how many basis values of a Corner depend on the direction of the ray: Y_1 .. Y_{B-1}
+template <class Corner>
+struct BakedBasis {
+    static constexpr int N = 0;
+};
+template <int B, class Stored>
+struct BakedBasis<ShCorner<B, Stored>> {
+    static constexpr int N = B - 1;
+};
+
+// dL/dY_k += sum_c mask_c coef[point][k][c] g_c for k >= 1; g = weight x dL/d(blended value) of this corner, mask the derivative
+// of the clamps as ShCorner::scatter forms it
+template <class Stored, int N>
+__device__ __forceinline__ void baked_basis_grad(const RgbaCornerOf<Stored> &, long long, float4, float (&)[N]) {}
+template <int B, class Stored, int N>
+__device__ __forceinline__ void baked_basis_grad(const ShCorner<B, Stored> &corner, long long point, float4 g, float (&dY)[N]) {
+    const float4 v = corner.unclamped(point);
+    g.x = v.x >= 0.f && v.x <= 1.f ? g.x : 0.f;
+    g.y = v.y >= 0.f && v.y <= 1.f ? g.y : 0.f;
+    g.z = v.z >= 0.f && v.z <= 1.f ? g.z : 0.f;
+    g.w = v.w >= 0.f ? g.w : 0.f;
+    if (g.x == 0.f && g.y == 0.f && g.z == 0.f && g.w == 0.f) return;
+    const Stored *c = corner.data + point * B;
+#pragma unroll
+    for (int k = 1; k < B; ++k) dY[k - 1] += baked_dot(baked_widen(c[k]), g);
+}
+
+// dL/dY_k, k = 1..N, through Y(n), n = d / |d|, and through the normalisation: (I - n n^T) / |d| . sum_k dL/dY_k grad Y_k(n) is
+// added to (gx, gy, gz).  ShCorner::set_ray's n and its test: a direction it gives no basis gets no term
+template <int N>
+__device__ __forceinline__ void baked_basis_to_dir(const Ray8 &ray, const float (&dY)[N], float &gx, float &gy, float &gz) {
+    const float n2 = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
+    if (!(occ_finite(n2) && n2 != 0.f)) return;
+    const float s = sqrtf(n2);
+    const float x = ray.dx / s, y = ray.dy / s, z = ray.dz / s;
+    float ax = SH_C1 * dY[2], ay = SH_C1 * dY[0], az = SH_C1 * dY[1];  // Y_1 = c y, Y_2 = c z, Y_3 = c x
+    if constexpr (N == 8) {
+        // Y_4 = c2 x y, Y_5 = c2 y z, Y_6 = c20 (3 z^2 - 1), Y_7 = c2 x z, Y_8 = c22 (x^2 - y^2)
+        ax = ax + SH_C2 * (y * dY[3]) + SH_C2 * (z * dY[6]) + (2.f * SH_C22) * (x * dY[7]);
+        ay = ay + SH_C2 * (x * dY[3]) + SH_C2 * (z * dY[4]) - (2.f * SH_C22) * (y * dY[7]);
+        az = az + SH_C2 * (y * dY[4]) + (6.f * SH_C20) * (z * dY[5]) + SH_C2 * (x * dY[6]);
+    }
+    const float along = ax * x + ay * y + az * z;
+    gx += (ax - x * along) / s;
+    gy += (ay - y * along) / s;
+    gz += (az - z * along) / s;
+}
+
+template <class Corner, class Rows>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_march_ray_bwd_kernel(const RaySrc rs, long long R, const BakedParams q, const Rows rows, const typename Corner::stored_t *__restrict__ stored,
+                           const float *__restrict__ d_rgb, const float *__restrict__ d_depth, const float *__restrict__ d_alpha,
+                           float *__restrict__ d_rays) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * BAKED_WAVES + (threadIdx.x >> 6);
+    if (r >= R) return;
+    float *__restrict__ out = d_rays + r * 8;
+    float3 drgb = make_float3(0.f, 0.f, 0.f);
+    if (d_rgb) drgb = make_float3(d_rgb[r * 3], d_rgb[r * 3 + 1], d_rgb[r * 3 + 2]);
+    const float ddepth = d_depth ? d_depth[r] : 0.f, dalpha = d_alpha ? d_alpha[r] : 0.f;
+    if (drgb.x == 0.f && drgb.y == 0.f && drgb.z == 0.f && ddepth == 0.f && dalpha == 0.f) {  // nothing to send back: the row of zeros
+        if (lane < 8) out[lane] = 0.f;
+        return;
+    }
+    const float gwhite = q.white_bkgd ? (drgb.x + drgb.y + drgb.z) : 0.f;  // rgb += 1 - sum w
+    Corner corner;
+    corner.data = stored;
+    const Ray8 ray = load_ray(rs, r);
+    corner.set_ray(ray);
+    const int n = baked_sample_count(ray, q.step);
+    int nc = (n + 63) >> 6;
+
+    // the forward's walk: T at the head of chunk c < 64 into lane c, and -- by the forward's own factors -- the chunk it stopped after
+    double heads = 1.0, carry = 1.0;
+    float stop = 1.f;
+    for (int c = 0; c < nc; ++c) {
+        if (lane == c) heads = carry;
+        const BakedSample s = baked_sample(ray, q, c * 64 + lane, n);
+        if (__ballot(s.active) == 0ull) continue;
+        float sigma;
+        carry = carry * __shfl(wave_scan_mul64(baked_tf_exact(q, corner, rows, s, sigma), lane), 63, 64);
+        if (q.eps > 0.f) {  // (wave-uniform)
+            stop = stop * __shfl(wave_scan_mul(baked_alpha(q.step, sigma).tfac, lane), 63, 64);
+            if (stop <= q.eps) nc = c + 1;  // the forward's break, in its words
+        }
+    }
+
+    constexpr int NY = BakedBasis<Corner>::N;
+    double d_o[3] = {0.0, 0.0, 0.0}, d_d[3] = {0.0, 0.0, 0.0}, d_near = 0.0;  // this lane's part of the row
+    float dY[NY > 0 ? NY : 1] = {};
+    const float dir[3] = {ray.dx, ray.dy, ray.dz};
+    double S_in = 0.0;  // S of the chunk's last sample
+    for (int c = nc - 1; c >= 0; --c) {
+        const BakedSample s = baked_sample(ray, q, c * 64 + lane, n);
+        if (__ballot(s.active) == 0ull) continue;  // 64 identity maps: S stays, nothing to send back
+        carry = __shfl(heads, c < 64 ? c : 63, 64);
+        for (int cc = 63; cc < c; ++cc) carry = carry * baked_chunk_product_exact(ray, q, corner, rows, cc, n, lane);
+        BakedCell<Rows> cell;
+        bool found = false;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        BakedBlendGrad bg = {zero, zero, zero, zero};
+        if (s.active) {
+            if (baked_find_cell(q, rows, s, cell)) {
+                found = true;
+                bg = baked_blend_grad(corner, rows, cell, s.f);
+            }
+        }
+        const float4 cs = bg.val;
+        const BakedAlphaExact al = baked_alpha_exact(q.step, cs.w);
+        // a sample that is not active, or found no rows, has a = 0 and tf = 1: the identity map
+        double m = found ? al.tf : 1.0;
+        const double incl = wave_scan_mul64(m, lane);
+        double excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.0;
+        const double T = carry * excl;
+        const double g = found ? (double)(drgb.x * cs.x + drgb.y * cs.y + drgb.z * cs.z + ddepth * s.t + dalpha - gwhite) : 0.0;
+        double b = found ? g * (double)al.a : 0.0;
+        wave_rscan_affine64(m, b, lane);
+        const double mn = __shfl_down(m, 1, 64), bn = __shfl_down(b, 1, 64);
+        const double S = lane == 63 ? S_in : bn + mn * S_in;
+        S_in = __shfl(b + m * S_in, 0, 64);  // S of sample 64 c - 1
+        if (found) {  // (no wave operation below: the lanes part here and meet again at the head of the loop)
+            const float w = (float)((double)al.a * T);
+            const float da = (float)(T * (g - S));
+            const float4 dcs = make_float4(w * drgb.x, w * drgb.y, w * drgb.z, da * q.step * al.ex);
+            float slope[3];
+            baked_frac_slope(ray, q, s, slope);
+            const float dp[3] = {slope[0] * baked_dot(dcs, bg.x) / q.g.h[0], slope[1] * baked_dot(dcs, bg.y) / q.g.h[1],
+                                 slope[2] * baked_dot(dcs, bg.z) / q.g.h[2]};
+            float dt = ddepth * w;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                d_o[a] += (double)dp[a];
+                d_d[a] += (double)s.t * (double)dp[a];
+                dt += dp[a] * dir[a];
+            }
+            d_near += (double)dt;
+            if constexpr (NY > 0) {
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {  // pair j = 2 ix + iy
+                    const long long row = cell.row(rows, j);
+                    const float wxy = (j >> 1 ? s.f[0] : 1.f - s.f[0]) * (j & 1 ? s.f[1] : 1.f - s.f[1]);
+#pragma unroll
+                    for (int iz = 0; iz < 2; ++iz) {
+                        const float wt = wxy * (iz ? s.f[2] : 1.f - s.f[2]);
+                        if (wt != 0.f) baked_basis_grad(corner, row + iz, make_float4(wt * dcs.x, wt * dcs.y, wt * dcs.z, wt * dcs.w), dY);
+                    }
+                }
+            }
+        }
+    }
+    // the 64 lanes of the ray, in wave_sum's fixed order; then the basis values' share of d_d
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        d_o[a] = wave_sum(d_o[a]);
+        d_d[a] = wave_sum(d_d[a]);
+    }
+    d_near = wave_sum(d_near);
+    float basis[3] = {0.f, 0.f, 0.f};
+    if constexpr (NY > 0) {
+#pragma unroll
+        for (int k = 0; k < NY; ++k) dY[k] = wave_sum(dY[k]);
+        baked_basis_to_dir(ray, dY, basis[0], basis[1], basis[2]);
+    }
+    if (lane == 0) {
+        out[0] = (float)d_o[0]; out[1] = (float)d_o[1]; out[2] = (float)d_o[2];
+        out[3] = (float)(d_d[0] + (double)basis[0]); out[4] = (float)(d_d[1] + (double)basis[1]); out[5] = (float)(d_d[2] + (double)basis[2]);
+        out[6] = (float)d_near;
+        out[7] = 0.f;  // far enters through the sample count alone
+    }
+}
 #pragma clang fp contract(fast)
 
 static bool baked_misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
@@ -522,6 +843,7 @@ struct BakedVolumeDesc {
     const char *name;         // what the header calls `stored`: "vol", "coef" or "rows"
     int min_degree;           // the entry's degree argument lies in [min_degree, 2] ...
     const char *degree_rule;  // ... or the entry refuses with these words (the RGBA entries take no degree: never said)
+    bool bad_storage = false; // the entry takes a storage_half argument and it was neither 0 nor 1
 };
 constexpr const char *DEGREE_SH = "degree must be 0, 1 or 2", *DEGREE_SPARSE = "degree must be -1 (RGBA rows), 0, 1 or 2",
                      *DEGREE_HALF = "degree must be -1 (RGBA), 0, 1 or 2";
@@ -551,9 +873,11 @@ struct BakedType {
 };
 
 // what a backward entry takes next to the march arguments: the upstream gradients (each NULL: zeros) and the buffer it adds into
+// (d_stored) or writes every row of (d_rays), with the name the header gives it
 struct BakedGrads {
     const float *d_rgb, *d_depth, *d_alpha;
-    float *d_stored;
+    float *out;
+    const char *out_name = "d_stored";
 };
 
 // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
@@ -567,6 +891,7 @@ static int baked_check(const char *entry, const BakedRays &rays, const BakedVolu
                        BakedParams &q, long long &blocks) {
     blocks = 0;
     if (v.degree < v.min_degree || v.degree > 2) return occ_fail(entry, v.degree_rule);
+    if (v.bad_storage) return occ_fail(entry, "storage_half must be 0 or 1");
     if (rays.defect) return occ_fail(entry, rays.defect);
     if (v.sparse && v.M < 0) return occ_fail(entry, "bad sizes (M)");
     if (const char *why = occ_bad_dims(a.nx, a.ny, a.nz)) return occ_fail(entry, why);
@@ -575,7 +900,7 @@ static int baked_check(const char *entry, const BakedRays &rays, const BakedVolu
     if (!(a.terminate >= 0.f && a.terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
     const long long R = rays.R;
     if (R == 0) return PNR_OK;
-    if (grads ? !grads->d_stored : !a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
+    if (grads ? !grads->out : !a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
     if (v.sparse ? v.M > 0 && (!v.stored || !v.index || !a.bits) : !v.stored) return occ_fail(entry, "null argument");
     if (occ_misaligned16(v.stored)) {
         char why[40];
@@ -585,8 +910,11 @@ static int baked_check(const char *entry, const BakedRays &rays, const BakedVolu
     if (v.sparse && baked_misaligned4(v.index)) return occ_fail(entry, "index must be 4-byte aligned");
     if (grads) {
         if (baked_misaligned4(a.bits) || baked_misaligned4(grads->d_rgb) || baked_misaligned4(grads->d_depth) ||
-            baked_misaligned4(grads->d_alpha) || baked_misaligned4(grads->d_stored))
-            return occ_fail(entry, "bits, d_rgb, d_depth, d_alpha and d_stored must be 4-byte aligned");
+            baked_misaligned4(grads->d_alpha) || baked_misaligned4(grads->out)) {
+            char why[80];
+            std::snprintf(why, sizeof(why), "bits, d_rgb, d_depth, d_alpha and %s must be 4-byte aligned", grads->out_name);
+            return occ_fail(entry, why);
+        }
     } else if (baked_misaligned4(a.bits) || baked_misaligned4(a.rgb) || baked_misaligned4(a.depth) || baked_misaligned4(a.alpha)) {
         return occ_fail(entry, "bits, rgb, depth and alpha must be 4-byte aligned");
     }
@@ -611,7 +939,7 @@ static int baked_backward(const char *entry, const BakedRays &rays, const void *
         using Corner = typename decltype(corner)::type;
         hipLaunchKernelGGL((baked_march_bwd_kernel<Corner, decltype(rows)>), dim3((unsigned)blocks), dim3(BAKED_WAVES * 64), 0,
                            (hipStream_t)a.stream, rays.src, rays.R, q, rows, static_cast<const float4 *>(v.stored), grads.d_rgb,
-                           grads.d_depth, grads.d_alpha, grads.d_stored);
+                           grads.d_depth, grads.d_alpha, grads.out);
     };
     const auto by_kind = [&](auto rows) {
         if (v.degree < 0) launch(BakedType<RgbaCornerOf<float4>>{}, rows);
@@ -621,6 +949,37 @@ static int baked_backward(const char *entry, const BakedRays &rays, const void *
     };
     if (v.sparse) by_kind(baked_sparse_rows(v));
     else by_kind(DenseRows{});
+    return pnr_check_launch(entry);
+}
+
+// The ray-gradient entries: fp32 or fp16 storage, dense (index == NULL) or sparse rows, degree -1..2: the forward's 16 instantiations.
+static int baked_ray_backward(const char *entry, const BakedRays &rays, const void *stored, int storage_half, long long M, int degree,
+                              const int32_t *index, const BakedMarchArgs &a, const BakedGrads &grads) {
+    BakedVolumeDesc v = {stored, degree, storage_half == 1, index != nullptr, index, index ? M : 0, "stored", -1, DEGREE_HALF};
+    v.bad_storage = storage_half != 0 && storage_half != 1;
+    BakedParams q;
+    long long blocks;
+    if (const int rc = baked_check(entry, rays, v, a, &grads, q, blocks)) return rc;
+    if (blocks == 0) return PNR_OK;
+    const auto launch = [&](auto corner, auto rows) {
+        using Corner = typename decltype(corner)::type;
+        hipLaunchKernelGGL((baked_march_ray_bwd_kernel<Corner, decltype(rows)>), dim3((unsigned)blocks), dim3(BAKED_WAVES * 64), 0,
+                           (hipStream_t)a.stream, rays.src, rays.R, q, rows, static_cast<const typename Corner::stored_t *>(v.stored),
+                           grads.d_rgb, grads.d_depth, grads.d_alpha, grads.out);
+    };
+    const auto by_kind = [&](auto stored_type, auto rows) {
+        using Stored = typename decltype(stored_type)::type;
+        if (v.degree < 0) launch(BakedType<RgbaCornerOf<Stored>>{}, rows);
+        else if (v.degree == 0) launch(BakedType<ShCorner<1, Stored>>{}, rows);
+        else if (v.degree == 1) launch(BakedType<ShCorner<4, Stored>>{}, rows);
+        else launch(BakedType<ShCorner<9, Stored>>{}, rows);
+    };
+    const auto by_storage = [&](auto rows) {
+        if (v.half) by_kind(BakedType<Half4>{}, rows);
+        else by_kind(BakedType<float4>{}, rows);
+    };
+    if (v.sparse) by_storage(baked_sparse_rows(v));
+    else by_storage(DenseRows{});
     return pnr_check_launch(entry);
 }
 
@@ -968,6 +1327,28 @@ extern "C" int pnr_baked_backward_views(const float *poses, int NV, int W, int H
     return pnr::baked_backward("pnr_baked_backward_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far), stored,
                                M, degree, index, {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, nullptr, nullptr, nullptr, stream},
                                {d_rgb, d_depth, d_alpha, d_stored});
+}
+
+// ---- gradients with respect to the rays (fp32 or fp16 storage; index == NULL: a dense volume, M is then not looked at)
+
+extern "C" int pnr_baked_ray_backward_rays(const float *rays, long long R, const void *stored, int storage_half, long long M, int degree,
+                                           const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
+                                           const float *c2, float step, int white_bkgd, float terminate, const float *d_rgb,
+                                           const float *d_depth, const float *d_alpha, float *d_rays, void *stream) {
+    return pnr::baked_ray_backward("pnr_baked_ray_backward_rays", pnr::baked_explicit_rays(rays, R), stored, storage_half, M, degree, index,
+                                   {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, nullptr, nullptr, nullptr, stream},
+                                   {d_rgb, d_depth, d_alpha, d_rays, "d_rays"});
+}
+
+extern "C" int pnr_baked_ray_backward_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
+                                            float z_far, const void *stored, int storage_half, long long M, int degree,
+                                            const int32_t *index, const uint32_t *bits, int nx, int ny, int nz, const float *c1,
+                                            const float *c2, float step, int white_bkgd, float terminate, const float *d_rgb,
+                                            const float *d_depth, const float *d_alpha, float *d_rays, void *stream) {
+    return pnr::baked_ray_backward("pnr_baked_ray_backward_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                                   stored, storage_half, M, degree, index,
+                                   {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, nullptr, nullptr, nullptr, stream},
+                                   {d_rgb, d_depth, d_alpha, d_rays, "d_rays"});
 }
 
 // ---- total variation of the stored values: the value, and its gradient ADDED into `grad` (fp32 storage; index == NULL: dense)

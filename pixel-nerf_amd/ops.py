@@ -1617,6 +1617,68 @@ def baked_render_views_backward(poses, width, height, focal, c, z_near, z_far, s
                            white_bkgd, terminate, d_rgb, d_depth, d_alpha, out, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
+# ---- gradients of the baked march with respect to the rays (include/pixelnerf_hip.h, "Gradients of the baked march with respect to
+# the RAYS")
+
+def _baked_ray_backward(what, entry, stored, degree, reso, c1, c2, step, bits, index, white_bkgd, terminate, d_rgb, d_depth, d_alpha,
+                        rays=None, camera=None):
+    """checks before any device work, then pnr_baked_ray_backward_rays / _views -> d_rays (R,8), every row written by the kernel"""
+    lib = _lib.load()
+    sparse = index is not None
+    half = isinstance(stored, torch.Tensor) and stored.dtype == torch.float16
+    v = _baked_volume(what, stored, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16 if half else torch.float32,
+                      name="rows" if sparse else "stored", index=index, sparse=sparse)
+    _, _, stored, degree, dims, c1, c2, step, terminate, bits, index = v
+    detached = lambda t: t.detach() if isinstance(t, torch.Tensor) else t  # (the gradient goes to what the caller holds)
+    if camera is None:
+        rays = detached(rays)
+    else:
+        camera = (detached(camera[0]),) + tuple(camera[1:])
+    args, R, dev, source = _baked_source(v, rays, camera)  # (source: kept alive over the call)
+    grads = []
+    for g, name, shape in ((d_rgb, "d_rgb", (R, 3)), (d_depth, "d_depth", (R,)), (d_alpha, "d_alpha", (R,))):
+        g = None if g is None else _f32(g.detach() if isinstance(g, torch.Tensor) else g, name, shape)
+        if g is not None and g.device != dev:
+            raise ValueError(f"{what}: {name} lives on {g.device}, the {'rays' if camera is None else 'poses'} on {dev}")
+        grads.append(g)
+    out = torch.empty((R, 8), dtype=torch.float32, device=dev)
+    lo, hi = _float3_pair(c1, c2)
+    M = stored.shape[0] if sparse else 0
+    args += (_p(stored) if stored.numel() else None, int(half), M, degree, None if index is None else _p(index.contiguous()),
+             None if bits is None else _p(bits.contiguous()), dims[0], dims[1], dims[2], lo, hi, step, int(bool(white_bkgd)), terminate,
+             _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(out) if R else None)
+    if R:
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    return out
+
+
+def baked_ray_backward(rays, stored, degree, reso, c1, c2, step, d_rgb=None, d_depth=None, d_alpha=None, bits=None, index=None,
+                       white_bkgd=False, terminate=0.0):
+    """The gradient of any baked march with respect to its RAYS (pnr_baked_ray_backward_rays): rays (R,8); stored fp32 or fp16,
+    (nx,ny,nz,4) (degree None / -1) or (nx,ny,nz,B,4) (degree 0, 1, 2), or with `index` the kept rows (M,4) / (M,B,4) (bits are then
+    mandatory); d_rgb (R,3), d_depth (R,), d_alpha (R,) the upstream gradients of the march's outputs, None = zeros.
+    -> d_rays (R,8) fp32 = dL/d [origin, direction, near, far]; column 7 is exactly 0 (far only sets the sample count).  Every row is
+    written by the kernel: rays without samples or without upstream gradient get exact zeros.  The samples are exactly the
+    forward's; the sample count, the inside test, the skip bits, the stop chunk, the cells and the clamps' regions are constants, so
+    the gradient is the exact derivative almost everywhere and one-sided on a cell plane.  No atomics: the same bytes on every call;
+    an fp16 volume gives the bytes of its float()."""
+    return _baked_ray_backward("baked_ray_backward", "pnr_baked_ray_backward_rays", stored, degree, reso, c1, c2, step, bits, index,
+                               white_bkgd, terminate, d_rgb, d_depth, d_alpha, rays=rays)
+
+
+def baked_ray_backward_views(poses, width, height, focal, c, z_near, z_far, stored, degree, reso, c1, c2, step, d_rgb=None, d_depth=None,
+                             d_alpha=None, bits=None, index=None, white_bkgd=False, terminate=0.0):
+    """baked_ray_backward over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c)
+    (pnr_baked_ray_backward_views): the rays are regenerated in the kernel, d_rgb (NV*H*W,3), d_depth and d_alpha (NV*H*W,) ordered
+    (view, row, column).  -> (NV,H,W,8): the gradient with respect to the regenerated rays, the bytes of
+    baked_ray_backward(gen_rays(...)); gen_rays_backward of it is the gradient with respect to the poses."""
+    W, H = _image_size("baked_ray_backward_views", width, height)
+    out = _baked_ray_backward("baked_ray_backward_views", "pnr_baked_ray_backward_views", stored, degree, reso, c1, c2, step, bits, index,
+                              white_bkgd, terminate, d_rgb, d_depth, d_alpha, camera=(poses, W, H, focal, c, z_near, z_far))
+    return out.reshape(-1, H, W, 8)
+
+
 # ---- the total-variation prior of a fitted volume (include/pixelnerf_hip.h, "Total-variation prior")
 
 def baked_tv(stored, degree, reso, weights, eps=1e-8, index=None, ids=None, want_value=True, grad_out=None, scale=None):

@@ -284,6 +284,41 @@ class _Baked:
             ret.psnr, ret.ssim = ep["psnr"], ep["ssim"]
         return ret
 
+    def _march_diff(self, source, step, bits, white_bkgd, terminate):
+        from .. import autograd
+        sparse = self._stored_name == "rows"
+        return autograd.baked_march_rays_autograd(self._stored(), source, self.degree, self.reso, self.c1, self.c2, step, bits=bits,
+                                                  index=self.index if sparse else None, white_bkgd=white_bkgd, terminate=terminate)
+
+    def render_diff(self, rays, step=None, white_bkgd=False, terminate=None, skip=True):
+        """`render` with autograd to the RAYS: rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)), the bytes `render` gives,
+        and a backward that hands dL/d rays to whatever made them (pnr_baked_ray_backward_rays: no atomics, the same bytes on every
+        call; include/pixelnerf_hip.h, "Gradients of the baked march with respect to the RAYS").  The volume itself gets no gradient
+        (`trainable()` is for that) and may be fp16.  step, terminate, skip: as render."""
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError(f"{type(self).__name__}.render_diff: rays must be (...,8)")
+        lead = tuple(rays.shape[:-1])
+        step, terminate, bits = self._march_args(step, terminate, skip)
+        rgb, depth, alpha = self._march_diff((rays.reshape(-1, 8).float(),), step, bits, white_bkgd, terminate)
+        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+    def render_views_diff(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, white_bkgd=False, terminate=None, skip=True):
+        """`render_views` without its epilogue and with autograd to the POSES: poses_c2w (NVt,4,4) -> DotMap(rgb (NVt,H,W,3), depth
+        and alpha (NVt,H,W)), the bytes `render_views` gives; the backward is pnr_baked_ray_backward_views followed by
+        ops.gen_rays_backward (the intrinsics are constants).  What `register` descends on."""
+        name = type(self).__name__
+        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
+            raise ValueError(f"{name}.render_views_diff: poses_c2w must be (NVt,4,4)")
+        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
+        if torch.is_tensor(focal):
+            focal = focal.flatten().tolist()
+            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
+        if torch.is_tensor(c):
+            c = c.flatten().tolist()
+        step, terminate, bits = self._march_args(step, terminate, skip)
+        rgb, depth, alpha = self._march_diff((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, bits, white_bkgd, terminate)
+        return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
+
 
 class BakedVolume(_Baked):
     """vol: (nx,ny,nz,4) fp32 or fp16 on the device, (r, g, b, sigma) at the points of ops.gen_grid_points(c1, c2, reso) -- the network's
@@ -618,8 +653,9 @@ class TrainableBaked(torch.nn.Module):
     """`volume.trainable()`: the fp32 stored tensor of a BakedVolume, BakedSHVolume or SparseBakedVolume as this module's one
     nn.Parameter (`stored`, a copy: the volume itself never changes), marched by the inference entries with gradients attached
     (autograd.baked_march_autograd: forward = the bytes of `volume.render`, backward = pnr_baked_backward_*).  Gradients reach the
-    stored values only -- rays and poses that require grad are refused -- and are not bit-reproducible from run to run (fp32
-    atomics).  An fp16 volume is refused: fit in fp32 and call `half()` afterwards.
+    stored values only -- rays and poses that require grad are refused unless `forward(ray_grad=True)` / `forward_views(
+    pose_grad=True)` asks for theirs too (pnr_baked_ray_backward_*) -- and those of the stored values are not bit-reproducible from
+    run to run (fp32 atomics).  An fp16 volume is refused: fit in fp32 and call `half()` afterwards.
     `skip=True` marches against the skip grid of the volume `trainable()` was called on, as it was then: the cells it calls empty
     receive no gradient and stay as they are -- fitting with skip=True FREEZES the empty cells; with skip=False (the default) every
     cell a ray crosses can change.  A sparse volume holds nothing else, so it always marches against its grid.
@@ -634,25 +670,31 @@ class TrainableBaked(torch.nn.Module):
         self._source = volume
         self.stored = torch.nn.Parameter(volume._stored().clone())
 
-    def _march(self, source, step, white_bkgd, terminate, skip):
+    def _march(self, source, step, white_bkgd, terminate, skip, source_grad=False):
         from .. import autograd
         v = self._source
         sparse = v._stored_name == "rows"
         step, terminate, bits = _Baked._march_args(v, step, terminate, skip or sparse)
-        return autograd.baked_march_autograd(self.stored, source, v.degree, v.reso, v.c1, v.c2, step, bits=bits,
-                                             index=v.index if sparse else None, white_bkgd=white_bkgd, terminate=terminate)
+        march = autograd.baked_march_rays_autograd if source_grad else autograd.baked_march_autograd
+        return march(self.stored, source, v.degree, v.reso, v.c1, v.c2, step, bits=bits, index=v.index if sparse else None,
+                     white_bkgd=white_bkgd, terminate=terminate)
 
-    def forward(self, rays, step=None, white_bkgd=False, terminate=None, skip=False):
-        """rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)) as `render`, differentiable with respect to `stored`"""
+    def forward(self, rays, step=None, white_bkgd=False, terminate=None, skip=False, ray_grad=False):
+        """rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)) as `render`, differentiable with respect to `stored`.
+        ray_grad=True: differentiable with respect to the rays as well (pnr_baked_ray_backward_rays); the default refuses rays that
+        require grad."""
         if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
             raise ValueError("TrainableBaked.forward: rays must be (...,8)")
         lead = tuple(rays.shape[:-1])
-        rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), step, white_bkgd, terminate, skip)
+        rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), step, white_bkgd, terminate, skip, source_grad=bool(ray_grad))
         return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
 
-    def forward_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, white_bkgd=False, terminate=None, skip=False):
+    def forward_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, white_bkgd=False, terminate=None, skip=False,
+                      pose_grad=False):
         """every pixel of the views, the rays regenerated in the kernel (as `render_views`, without its epilogue)
-        -> DotMap(rgb (NVt,H,W,3), depth (NVt,H,W), alpha (NVt,H,W)), differentiable with respect to `stored`"""
+        -> DotMap(rgb (NVt,H,W,3), depth (NVt,H,W), alpha (NVt,H,W)), differentiable with respect to `stored`.  pose_grad=True:
+        differentiable with respect to the poses as well (pnr_baked_ray_backward_views, then ops.gen_rays_backward); the default
+        refuses poses that require grad."""
         if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
             raise ValueError("TrainableBaked.forward_views: poses_c2w must be (NVt,4,4)")
         W, H, NVt = int(W), int(H), poses_c2w.shape[0]
@@ -661,7 +703,8 @@ class TrainableBaked(torch.nn.Module):
             focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
         if torch.is_tensor(c):
             c = c.flatten().tolist()
-        rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, white_bkgd, terminate, skip)
+        rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, white_bkgd, terminate, skip,
+                                        source_grad=bool(pose_grad))
         return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
 
     def tv(self, rgb=1.0, sigma=1.0, sh=None, eps=1e-8):
@@ -726,3 +769,69 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
                 module.stored[..., 3].clamp_(min=0.0)
         losses.append(loss.detach())
     return module.volume(), (torch.stack(losses).tolist() if losses else [])
+
+
+# ---------------------------------------------------------------- registration: gradients with respect to the poses
+
+def rodrigues(w):
+    """Axis-angle vectors w (...,3) -> rotation matrices (...,3,3): R = I + A K + B K^2 with K the cross-product matrix of w,
+    A = sin(t) / t, B = (1 - cos(t)) / t^2, t = |w|.  Below t^2 = 1e-6 the two are their series (1 - t^2/6 + t^4/120 and
+    1/2 - t^2/24 + t^4/720; the terms left out are below 1e-21), so value and derivative are finite at w = 0 -- where R = I and
+    dR/dw_a is the generator of axis a -- and nothing is divided by t."""
+    if not isinstance(w, torch.Tensor) or w.dim() < 1 or w.shape[-1] != 3:
+        raise ValueError("rodrigues: w must be (...,3)")
+    t2 = (w * w).sum(dim=-1)
+    small = t2 < 1e-6
+    safe = torch.where(small, torch.ones_like(t2), t2)  # (the branch not taken still gets finite derivatives)
+    t = safe.sqrt()
+    A = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, t.sin() / t)
+    B = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, (1.0 - t.cos()) / safe)
+    x, y, z = w[..., 0], w[..., 1], w[..., 2]
+    o = torch.zeros_like(x)
+    K = torch.stack((torch.stack((o, -z, y), dim=-1), torch.stack((z, o, -x), dim=-1), torch.stack((-y, x, o), dim=-1)), dim=-2)
+    eye = torch.eye(3, dtype=w.dtype, device=w.device).expand(K.shape)
+    return eye + A[..., None, None] * K + B[..., None, None] * (K @ K)
+
+
+def moved_poses(poses0, w, v):
+    """the poses `register` descends on: P = [R(w) R0 | t0 + v] over the bottom row of poses0; poses0 (NV,4,4), w and v (NV,3)"""
+    top = torch.cat((rodrigues(w) @ poses0[:, :3, :3], (poses0[:, :3, 3] + v)[:, :, None]), dim=2)
+    return torch.cat((top, poses0[:, 3:, :]), dim=1)
+
+
+def register(volume, target_rgb, poses0, W, H, focal, z_near, z_far, c=None, steps=200, lr=1e-2, step=None, white_bkgd=False,
+             terminate=None, skip=True):
+    """Register cameras against a baked volume (iNeRF-style): Adam on a 6-DoF update per view, P = [R(w) R0 | t0 + v] with w an
+    axis-angle vector through `rodrigues` and v a translation, both starting at 0, loss = mean((rgb - target_rgb)^2) over all pixels
+    of all views, rgb = volume.render_views_diff(P, ...).rgb.  volume: any baked volume, fp32 or fp16 (it is not changed);
+    target_rgb (NV,H,W,3); poses0 (NV,4,4) camera-to-world, the starting poses; W, H, focal, z_near, z_far, c: the camera, as
+    render_views takes it; step, white_bkgd, terminate, skip: as render.
+    A step costs one march and one ray-gradient launch, no network.  The loss is only piecewise smooth in the pose and the descent is
+    local: it converges from a start inside the basin of the true pose (profiles/baked_notes.md, "Ray gradients and registration").
+    -> (poses (NV,4,4), losses: the `steps` losses as floats, read once at the end)"""
+    if not isinstance(volume, _Baked):
+        raise TypeError(f"register: expected a baked volume, got {type(volume).__name__}")
+    if not isinstance(poses0, torch.Tensor) or poses0.dim() != 3 or tuple(poses0.shape[1:]) != (4, 4):
+        raise ValueError("register: poses0 must be (NV,4,4)")
+    W, H, NV, steps = int(W), int(H), poses0.shape[0], int(steps)
+    if not isinstance(target_rgb, torch.Tensor) or tuple(target_rgb.shape) != (NV, H, W, 3):
+        raise ValueError(f"register: target_rgb must be (NV,H,W,3) = {(NV, H, W, 3)}, got "
+                         f"{tuple(target_rgb.shape) if isinstance(target_rgb, torch.Tensor) else type(target_rgb).__name__}")
+    if steps < 0:
+        raise ValueError(f"register: steps must be >= 0, got {steps}")
+    poses0, target = poses0.detach().float(), target_rgb.detach().float()
+    w = torch.zeros((NV, 3), dtype=torch.float32, device=poses0.device, requires_grad=True)
+    v = torch.zeros((NV, 3), dtype=torch.float32, device=poses0.device, requires_grad=True)
+    optimiser = torch.optim.Adam([w, v], lr=float(lr))
+    losses = []
+    for _ in range(steps):
+        out = volume.render_views_diff(moved_poses(poses0, w, v), W, H, focal, z_near, z_far, c=c, step=step, white_bkgd=white_bkgd,
+                                       terminate=terminate, skip=skip)
+        loss = ((out.rgb - target) ** 2).mean()
+        optimiser.zero_grad(set_to_none=True)
+        loss.backward()
+        optimiser.step()
+        losses.append(loss.detach())
+    with torch.no_grad():
+        poses = moved_poses(poses0, w, v)
+    return poses, (torch.stack(losses).tolist() if losses else [])
