@@ -1272,6 +1272,74 @@ int pnr_baked_tv(const float *stored, long long M, int degree, const int32_t *in
                  const float *scale /*device, nullable*/, float *value32 /*device, nullable*/, double *value64 /*device, nullable*/,
                  float *grad /*device, nullable, the shape of stored; added into*/, void *workspace, void *stream);
 
+/* Scenes of several baked volumes (inference; added within ABI rev 12 as well: one struct and two entries, nothing existing
+ * changes).  Every entry above renders ONE volume in ONE axis-aligned box.  A baked object lives in its own frame; these two
+ * entries march up to PNR_BAKED_SCENE_MAX_OBJECTS posed volumes in one image.  Separate marches cannot be merged afterwards:
+ * where boxes overlap, or one object stands in front of another, the transmittance of one attenuates the other sample by sample.
+ * Objects.  `objects`: a HOST array of n_objects PnrBakedObject, 1 <= n_objects <= 8; every pointer inside is a device pointer.
+ *   Per object: `stored` as pnr_baked_ray_backward_* take it (degree -1: (nx,ny,nz,4); 0, 1, 2: (nx,ny,nz,B,4); with index != NULL
+ *   the M kept rows, bits then mandatory; storage_half 0: fp32, 1: fp16), its skip grid `bits`, its own grid (nx,ny,nz) and box
+ *   (c1, c2) IN THE OBJECT'S FRAME, and pose = [R | t], row-major (3,4): object-to-world, x_world = R x_object + t, rigid.
+ *   One kind per scene: all objects share degree, storage_half and whether index is set; grids, boxes and poses may differ.
+ * The world ray.  n = ceil((far - near) / step) and t_i = near + (i + 0.5) step are those of the single-volume march, taken from
+ *   the WORLD ray (o, d, near, far); a ray that cannot be sampled -- by that march's rule, applied to the world ray -- gets the
+ *   background and reads nothing.
+ * The ray in the frame of object j.  q = o - t_j, then for the axes a = x, y, z
+ *     o'_a = (q_x R_xa + q_y R_ya) + q_z R_za,   d'_a = (d_x R_xa + d_y R_ya) + d_z R_za      (R_ra = pose[4 r + a])
+ *   every product, difference and sum rounded on its own.  The pose is rigid, so t is shared: p'_i = o' + t_i d'.
+ * The value of object j at sample i is exactly what the single-volume march computes for the ray (o', d', near, far): the inside
+ *   test against the object's own box, its skip bit, its cell, its blend; for a coefficient volume the basis is evaluated on d'
+ *   and the clamps are per corner.  A sample that is outside, skipped, or (sparse) finds no rows contributes nothing.
+ * Mixing.  Over the objects that contribute to sample i, in list order:
+ *     sigma = sum_j sigma_j  (summed left to right),   c = sum_j (sigma_j / sigma) c_j  when sigma > 0 (left to right), else 0
+ *   -- the colour of a mixture of media weighted by density.  alpha_i = 1 - exp(-step sigma), the product scan, rgb, depth, alpha,
+ *   white_bkgd and the termination check every 64 samples are the single-volume march's, applied to (c, sigma).  A chunk in which
+ *   no object has a sample inside its box and occupied issues no loads and leaves the carry as it is.  Stored sigmas are taken to
+ *   be >= 0, as a bake's are (a negative sum gives c = 0).
+ * What the rules imply (tests/test_hip_baked_scene.py holds the kernel to each):
+ *   (a) one object whose pose is exactly [I | 0] renders the BYTES of the matching single-volume entry: products with 0 and 1 and
+ *       sums with 0 are exact for finite rays, x / x = 1; no special case in the code;
+ *   (b) one object whose rotation has entries in {0, +1, -1} renders the bytes of the single-volume entry on the rays (o', d')
+ *       formed by the same fp32 operations;
+ *   (c) an object whose sigma is 0 at every sample of a ray leaves that ray's bytes as they are without it (x + 0, x / x, 0 c);
+ *   (d) two objects commute;
+ *   (e) the same volume listed twice at one pose renders the bytes of that volume with sigma doubled (sigma / (2 sigma) = 0.5,
+ *       0.5 c + 0.5 c = c, and doubling commutes with the blend's roundings);
+ *   (f) with every object's bits built at threshold 0 and dilate 0, skipping is exact;
+ *   (g) no atomics, no LDS, no workspace: two calls give the same bytes;
+ *   (h) pnr_baked_scene_render_views gives the bytes of pnr_baked_scene_render_rays on pnr_gen_rays' rows.
+ * Kernel.  One wavefront per ray, lane l of chunk c takes sample 64 c + l; the objects are an inner loop.  The scene travels by
+ *   value as a kernel argument (128 bytes per object) and the loop's index is wave-uniform, so an object's fields are scalar
+ *   loads.  A lane to whose sample ONE object contributes keeps that value; a lane with several walks the objects a second time,
+ *   because the weights need the finished sum -- the second walk repeats the first one's loads, in overlaps only.
+ * Cost: per sample and object one transform and one inside test; the loads are those of the single marches.
+ * PNR_E_INVALID, before any HIP call, in this order: n_objects outside [1, 8]; objects == NULL; per object "object j: reserved
+ *   must be 0", then "object j: mixed kinds ..." (degree, storage_half or index-set differs from object 0); the rays / poses
+ *   checks, step, terminate, and with R > 0 a null or misaligned rgb / depth / alpha, in the words of pnr_baked_render_*; then per
+ *   object, under "entry: object j: ", everything pnr_baked_ray_backward_* refuse about a volume in their words (degree,
+ *   storage_half, M < 0, the grid, c1 / c2, nulls, 16-byte alignment of stored, 4-byte alignment of index and bits, bits missing
+ *   for sparse rows) and "pose must be finite and rigid": all 12 numbers finite, max |R^T R - I| <= 1e-4 and det R > 0, computed
+ *   in fp64 -- far above what an fp32 rotation leaves, far below a visible shear.  R = 0 (NV = 0): no-op, PNR_OK.
+ * Not here: gradients of any kind, mixed kinds, scale or shear, more than 8 objects, a step per object, a background layer. */
+#define PNR_BAKED_SCENE_MAX_OBJECTS 8
+typedef struct PnrBakedObject {      /* one posed volume; all pointers are device pointers */
+    const void *stored;              /* dense (nx,ny,nz[,B],4) or the M kept rows; fp32 or fp16 */
+    const uint32_t *bits;            /* skip grid of this object; nullable for dense, mandatory for sparse */
+    const int32_t *index;            /* sparse only, else NULL */
+    long long M;                     /* sparse only, else 0 */
+    int nx, ny, nz, degree;          /* degree -1: RGBA, 0..2: coefficient volume */
+    int storage_half, reserved;      /* 0 | 1; reserved must be 0 */
+    float c1[3], c2[3];              /* the object's box, in the OBJECT's frame */
+    float pose[12];                  /* object-to-world [R | t], row-major (3,4), rigid */
+} PnrBakedObject;
+int pnr_baked_scene_render_rays(const float *rays, long long R, const PnrBakedObject *objects /*host*/, int n_objects,
+                                float step, int white_bkgd, float terminate, float *rgb /*(R,3)*/, float *depth /*(R)*/,
+                                float *alpha /*(R)*/, void *stream);
+int pnr_baked_scene_render_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                 float z_near, float z_far, const PnrBakedObject *objects /*host*/, int n_objects, float step,
+                                 int white_bkgd, float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha,
+                                 void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

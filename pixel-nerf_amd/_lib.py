@@ -76,6 +76,16 @@ class PnrSplitSaved(ctypes.Structure):
                 ("x5", ctypes.c_void_p), ("masks", ctypes.c_void_p)]
 
 
+BAKED_SCENE_MAX_OBJECTS = 8  # PNR_BAKED_SCENE_MAX_OBJECTS
+
+
+class PnrBakedObject(ctypes.Structure):
+    _fields_ = [("stored", ctypes.c_void_p), ("bits", ctypes.c_void_p), ("index", ctypes.c_void_p), ("M", ctypes.c_longlong),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int), ("degree", ctypes.c_int),
+                ("storage_half", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("c1", ctypes.c_float * 3), ("c2", ctypes.c_float * 3), ("pose", ctypes.c_float * 12)]
+
+
 # every symbol include/pixelnerf_hip.h declares: name -> (restype, argtypes)
 _I, _F, _P, _SZ = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 _AUX = ctypes.POINTER(PnrSplitAux)
@@ -228,6 +238,9 @@ PROTOTYPES = {
                                           ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _I, _F, _P, _P, _P, _P, _P]),
     "pnr_baked_tv_workspace_bytes": (_SZ, []),
     "pnr_baked_tv": (_I, [_P, ctypes.c_longlong, _I, _P, _P, _I, _I, _I, ctypes.POINTER(_F), _F, _P, _P, _P, _P, _P, _P]),
+    "pnr_baked_scene_render_rays": (_I, [_P, ctypes.c_longlong, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F, _P, _P, _P, _P]),
+    "pnr_baked_scene_render_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F,
+                                          _P, _P, _P, _P]),
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }

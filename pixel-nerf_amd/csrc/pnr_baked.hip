@@ -25,6 +25,8 @@
 // Ray backward (pnr_baked_ray_backward_rays / _views: dL/d rays, what registering a camera needs): baked_march_ray_bwd_kernel, the
 // same walk over the same samples, through the spatial derivative of the blend (baked_blend_grad) instead of its corner weights;
 // every storage and layout (the forward's 16 instantiations), no atomics, every row written.
+// Scenes (pnr_baked_scene_render_rays / _views: up to 8 posed volumes of one kind in one image): baked_scene_march_kernel, the
+// forward's walk with an inner loop over the objects, each seeing the world ray in its own frame; the same 16 instantiations.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -381,6 +383,169 @@ baked_march_kernel(const RaySrc rs, long long R, const BakedParams q, const Rows
     Corner corner;
     corner.data = stored;
     baked_march(rs, R, q, corner, rows, rgb, depth, alpha_out);
+}
+
+// ---- scenes of several posed volumes (pnr_baked_scene_render_*; include/pixelnerf_hip.h, "Scenes of several baked volumes").
+// The march above with an inner loop over objects: the samples are the WORLD ray's, every object sees the ray in its own frame,
+// and the values of the objects that contribute to a sample are mixed before alpha and the scan.  The per-sample work is the
+// device functions of the single march, so one object at the identity renders that march's bytes.
+
+// One posed volume as the kernel sees it: what baked_check made of a PnrBakedObject.  The scene travels BY VALUE as a kernel
+// argument (8 x 128 bytes) and the object loop's index is wave-uniform: the fields are scalar loads from the kernarg segment.
+struct BakedSceneObject {
+    const void *stored;
+    const uint32_t *bits;
+    const int32_t *index;  // sparse only
+    int last;              // sparse only: SparseRows::last
+    OccGrid g;             // the object's own box and grid
+    float rot[9], t[3];    // object-to-world [R | t]; the kernel applies the inverse, R^T (x - t)
+};
+struct BakedSceneDesc {
+    BakedSceneObject obj[PNR_BAKED_SCENE_MAX_OBJECTS];
+    int n;
+};
+static_assert(sizeof(BakedSceneObject) == 128, "eight objects are 1 KiB of kernel arguments");
+
+template <class Rows>
+__device__ __forceinline__ Rows baked_scene_rows(const BakedSceneObject &ob) {
+    if constexpr (std::is_same<Rows, SparseRows>::value) return SparseRows{ob.index, ob.last};
+    else return DenseRows{};
+}
+
+// the world ray in the object's frame: q = o - t, then R^T q and R^T d, each as (x R_xa + y R_ya) + z R_za; near and far are shared
+__device__ __forceinline__ Ray8 baked_scene_ray(const Ray8 &w, const BakedSceneObject &ob) {
+    const float qx = w.ox - ob.t[0], qy = w.oy - ob.t[1], qz = w.oz - ob.t[2];
+    Ray8 r;
+    r.ox = (qx * ob.rot[0] + qy * ob.rot[3]) + qz * ob.rot[6];
+    r.oy = (qx * ob.rot[1] + qy * ob.rot[4]) + qz * ob.rot[7];
+    r.oz = (qx * ob.rot[2] + qy * ob.rot[5]) + qz * ob.rot[8];
+    r.dx = (w.dx * ob.rot[0] + w.dy * ob.rot[3]) + w.dz * ob.rot[6];
+    r.dy = (w.dx * ob.rot[1] + w.dy * ob.rot[4]) + w.dz * ob.rot[7];
+    r.dz = (w.dx * ob.rot[2] + w.dy * ob.rot[5]) + w.dz * ob.rot[8];
+    r.near = w.near;
+    r.far = w.far;
+    return r;
+}
+
+// The value of one object at sample i of the world ray: what baked_march computes for the ray in the object's frame.  -> whether
+// the sample contributes (active, and its rows found); `active`: baked_sample's.  The ray is transformed anew for every chunk
+// (21 operations, nothing kept per object), and the basis of a coefficient volume is evaluated only for a chunk that reads.
+template <class Corner, class Rows>
+__device__ __forceinline__ bool baked_scene_value(const BakedSceneObject &ob, const Ray8 &world, float step, int i, int n, bool &active,
+                                                  float4 &cs) {
+    const Ray8 ray = baked_scene_ray(world, ob);
+    active = false;
+    cs = make_float4(0.f, 0.f, 0.f, 0.f);
+    // baked_sample's inside test alone, first -- the same operations on the same numbers, so exactly its answer -- and nothing
+    // more for a chunk that does not touch the object's box: most (chunk, object) pairs of a scene end here, before the divisions
+    const float t = ray.near + ((float)i + 0.5f) * step;
+    const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
+    bool inside = i < n;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p = o[a] + t * d[a];
+        inside = inside && p >= ob.g.c1[a] && p <= ob.g.c2[a];
+    }
+    if (__ballot(inside) == 0ull) return false;
+    BakedParams q;
+    q.bits = ob.bits;
+    q.g = ob.g;
+    q.step = step;
+    q.eps = 0.f;
+    q.white_bkgd = 0;
+    const BakedSample s = baked_sample(ray, q, i, n);
+    active = s.active;
+    if (__ballot(s.active) == 0ull) return false;  // nothing of this object in the chunk: no loads
+    Corner corner;
+    corner.data = static_cast<const typename Corner::stored_t *>(ob.stored);
+    corner.set_ray(ray);
+    const Rows rows = baked_scene_rows<Rows>(ob);
+    BakedCell<Rows> cell;
+    bool found;
+    cs = baked_value(q, corner, rows, s, cell, found);
+    return found;
+}
+
+template <class Corner, class Rows>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_scene_march_kernel(const RaySrc rs, long long R, const BakedSceneDesc sc, float step, float eps, int white_bkgd,
+                         float *__restrict__ rgb, float *__restrict__ depth, float *__restrict__ alpha_out) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * BAKED_WAVES + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const Ray8 ray = load_ray(rs, r);
+    // baked_sample_count's five lines on the WORLD ray, in place as in baked_march
+    const float o[3] = {ray.ox, ray.oy, ray.oz}, d[3] = {ray.dx, ray.dy, ray.dz};
+    bool ok = occ_finite(ray.near) && occ_finite(ray.far) && ray.near < ray.far;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok = ok && occ_finite(o[a]) && occ_finite(d[a]);
+    const float count = ceilf((ray.far - ray.near) / step);
+    const int n = ok && count <= BAKED_MAX_SAMPLES ? (int)count : 0;
+    float carry = 1.f;
+    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f, acc_w = 0.f;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int i = c0 + lane;
+        const float t = ray.near + ((float)i + 0.5f) * step;  // baked_sample's depth
+        // first pass: sigma = sum sigma_j over the objects that contribute, in list order; the first such value is kept
+        float4 first = make_float4(0.f, 0.f, 0.f, 0.f);
+        float sigma = 0.f;
+        int cnt = 0;
+        bool any = false;
+#pragma unroll 1
+        for (int j = 0; j < sc.n; ++j) {
+            bool active;
+            float4 cs;
+            const bool found = baked_scene_value<Corner, Rows>(sc.obj[j], ray, step, i, n, active, cs);
+            any = any || active;
+            if (found) {
+                if (cnt == 0) first = cs;
+                sigma = sigma + cs.w;
+                ++cnt;
+            }
+        }
+        if (__ballot(any) == 0ull) continue;  // every factor of the chunk is exactly 1: the carry and the sums stay as they are
+        // c = sum (sigma_j / sigma) c_j.  One contributor (all but the samples where boxes overlap): the kept value.  More: the
+        // weights need the finished sum, so those lanes walk the objects again -- the same loads, the same values -- instead of
+        // keeping eight float4s per lane.
+        float cr = 0.f, cg = 0.f, cb = 0.f;
+        if (cnt == 1 && sigma > 0.f) {
+            const float wj = first.w / sigma;
+            cr = wj * first.x; cg = wj * first.y; cb = wj * first.z;
+        }
+        if (__ballot(cnt >= 2) != 0ull) {
+            if (cnt >= 2 && sigma > 0.f) {
+#pragma unroll 1
+                for (int j = 0; j < sc.n; ++j) {
+                    bool active;
+                    float4 cs;
+                    if (baked_scene_value<Corner, Rows>(sc.obj[j], ray, step, i, n, active, cs)) {
+                        const float wj = cs.w / sigma;
+                        cr = cr + wj * cs.x; cg = cg + wj * cs.y; cb = cb + wj * cs.z;
+                    }
+                }
+            }
+        }
+        const BakedAlpha al = baked_alpha(step, sigma);
+        const float incl = wave_scan_mul(al.tfac, lane);
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.f;
+        const float w = al.a * (carry * excl);
+        acc_r += w * cr; acc_g += w * cg; acc_b += w * cb;
+        acc_d += w * t;
+        acc_w += w;
+        carry = carry * __shfl(incl, 63, 64);
+        if (eps > 0.f && carry <= eps) break;  // wave-uniform; a NaN transmittance does not stop the ray
+    }
+    acc_r = wave_sum(acc_r); acc_g = wave_sum(acc_g); acc_b = wave_sum(acc_b);
+    acc_d = wave_sum(acc_d); acc_w = wave_sum(acc_w);
+    if (lane == 0) {
+        if (white_bkgd) {
+            acc_r = acc_r + 1.f - acc_w; acc_g = acc_g + 1.f - acc_w; acc_b = acc_b + 1.f - acc_w;
+        }
+        rgb[r * 3 + 0] = acc_r; rgb[r * 3 + 1] = acc_g; rgb[r * 3 + 2] = acc_b;
+        depth[r] = acc_d;
+        alpha_out[r] = acc_w;
+    }
 }
 
 // ---- backward of the march with respect to the stored values (pnr_baked_backward_*; fp32 storage only).
@@ -1012,6 +1177,97 @@ static int baked_render(const char *entry, const BakedRays &rays, const BakedVol
     else by_storage(DenseRows{});
     return pnr_check_launch(entry);
 }
+
+// [R | t] of a PnrBakedObject: finite, max |R^T R - I| <= 1e-4 and det R > 0, in fp64
+static bool baked_pose_rigid(const float *pose) {
+    double m[3][3];
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return false;
+    for (int r = 0; r < 3; ++r)
+        for (int a = 0; a < 3; ++a) m[r][a] = pose[4 * r + a];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const double dot = m[0][a] * m[0][b] + m[1][a] * m[1][b] + m[2][a] * m[2][b];
+            if (!(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4)) return false;
+        }
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    return det > 0.0;
+}
+
+// the scene entries: what concerns the call as a whole, then every object through baked_check under "entry: object j", then the launch
+static int baked_scene_render(const char *entry, const BakedRays &rays, const PnrBakedObject *objects, int n_objects, float step,
+                              int white_bkgd, float terminate, float *rgb, float *depth, float *alpha, void *stream) {
+    if (n_objects < 1 || n_objects > PNR_BAKED_SCENE_MAX_OBJECTS) return occ_fail(entry, "n_objects must lie in [1, 8]");
+    if (!objects) return occ_fail(entry, "null argument (objects)");
+    char where[96], why[96];
+    for (int j = 0; j < n_objects; ++j) {
+        const PnrBakedObject &ob = objects[j], &ob0 = objects[0];
+        if (ob.reserved != 0) {
+            std::snprintf(why, sizeof(why), "object %d: reserved must be 0", j);
+            return occ_fail(entry, why);
+        }
+        if (ob.degree != ob0.degree || ob.storage_half != ob0.storage_half || (ob.index != nullptr) != (ob0.index != nullptr)) {
+            std::snprintf(why, sizeof(why), "object %d: mixed kinds (degree, storage_half and index must be those of object 0)", j);
+            return occ_fail(entry, why);
+        }
+    }
+    if (rays.defect) return occ_fail(entry, rays.defect);
+    if (!(step > 0.f) || !std::isfinite(step)) return occ_fail(entry, "step must be finite and > 0");
+    if (!(terminate >= 0.f && terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");
+    if (rays.R > 0) {
+        if (!rgb || !depth || !alpha) return occ_fail(entry, "null argument");
+        if (baked_misaligned4(rgb) || baked_misaligned4(depth) || baked_misaligned4(alpha))
+            return occ_fail(entry, "rgb, depth and alpha must be 4-byte aligned");
+    }
+    BakedSceneDesc sc = {};
+    sc.n = n_objects;
+    BakedVolumeDesc v0 = {};
+    long long blocks = 0;
+    for (int j = 0; j < n_objects; ++j) {
+        const PnrBakedObject &ob = objects[j];
+        std::snprintf(where, sizeof(where), "%s: object %d", entry, j);
+        BakedVolumeDesc v = {ob.stored, ob.degree, ob.storage_half == 1, ob.index != nullptr, ob.index, ob.index ? ob.M : 0, "stored", -1,
+                             DEGREE_HALF};
+        v.bad_storage = ob.storage_half != 0 && ob.storage_half != 1;
+        BakedParams q;
+        if (const int rc = baked_check(where, rays, v, {ob.bits, ob.nx, ob.ny, ob.nz, ob.c1, ob.c2, step, white_bkgd, terminate, rgb, depth,
+                                                        alpha, stream}, nullptr, q, blocks))
+            return rc;
+        if (!baked_pose_rigid(ob.pose)) return occ_fail(where, "pose must be finite and rigid (max |R^T R - I| <= 1e-4, det R > 0)");
+        BakedSceneObject &o = sc.obj[j];
+        o.stored = ob.stored;
+        o.bits = ob.bits;
+        o.index = ob.index;
+        o.last = v.sparse ? baked_sparse_rows(v).last : -1;
+        o.g = q.g;
+        for (int r = 0; r < 3; ++r) {
+            for (int a = 0; a < 3; ++a) o.rot[3 * r + a] = ob.pose[4 * r + a];
+            o.t[r] = ob.pose[4 * r + 3];
+        }
+        if (j == 0) v0 = v;
+    }
+    if (blocks == 0) return PNR_OK;
+    const auto launch = [&](auto corner, auto rows) {
+        using Corner = typename decltype(corner)::type;
+        hipLaunchKernelGGL((baked_scene_march_kernel<Corner, typename decltype(rows)::type>), dim3((unsigned)blocks), dim3(BAKED_WAVES * 64),
+                           0, (hipStream_t)stream, rays.src, rays.R, sc, step, terminate, white_bkgd, rgb, depth, alpha);
+    };
+    const auto by_kind = [&](auto stored, auto rows) {
+        using Stored = typename decltype(stored)::type;
+        if (v0.degree < 0) launch(BakedType<RgbaCornerOf<Stored>>{}, rows);
+        else if (v0.degree == 0) launch(BakedType<ShCorner<1, Stored>>{}, rows);
+        else if (v0.degree == 1) launch(BakedType<ShCorner<4, Stored>>{}, rows);
+        else launch(BakedType<ShCorner<9, Stored>>{}, rows);
+    };
+    const auto by_storage = [&](auto rows) {
+        if (v0.half) by_kind(BakedType<Half4>{}, rows);
+        else by_kind(BakedType<float4>{}, rows);
+    };
+    if (v0.sparse) by_storage(BakedType<SparseRows>{});
+    else by_storage(BakedType<DenseRows>{});
+    return pnr_check_launch(entry);
+}
 // keep[p] for the pair (2 j, 2 j + 1) of grid points: a point is a corner of the cells (i - a, j - b, k - c), a, b, c in {0, 1},
 // that exist; the pair is kept whole when either point is a corner of an occupied one
 constexpr int SPARSE_MARK_THREADS = 256;
@@ -1306,6 +1562,21 @@ extern "C" int pnr_baked_sparse_half_render_views(const float *poses, int NV, in
     return pnr::baked_render("pnr_baked_sparse_half_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
                              pnr::baked_sparse(rows, M, index, degree, true, pnr::DEGREE_HALF),
                              {bits, nx, ny, nz, c1, c2, step, white_bkgd, terminate, rgb, depth, alpha, stream});
+}
+
+// ---- scenes of several posed volumes of one kind (objects: a HOST array)
+
+extern "C" int pnr_baked_scene_render_rays(const float *rays, long long R, const PnrBakedObject *objects, int n_objects, float step,
+                                           int white_bkgd, float terminate, float *rgb, float *depth, float *alpha, void *stream) {
+    return pnr::baked_scene_render("pnr_baked_scene_render_rays", pnr::baked_explicit_rays(rays, R), objects, n_objects, step, white_bkgd,
+                                   terminate, rgb, depth, alpha, stream);
+}
+
+extern "C" int pnr_baked_scene_render_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy, float z_near,
+                                            float z_far, const PnrBakedObject *objects, int n_objects, float step, int white_bkgd,
+                                            float terminate, float *rgb, float *depth, float *alpha, void *stream) {
+    return pnr::baked_scene_render("pnr_baked_scene_render_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
+                                   objects, n_objects, step, white_bkgd, terminate, rgb, depth, alpha, stream);
 }
 
 // ---- gradients with respect to the stored values (fp32 storage; index == NULL: a dense volume, M is then not looked at)

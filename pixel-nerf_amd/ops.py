@@ -1555,6 +1555,117 @@ def baked_sparse_half_render_views(poses, width, height, focal, c, z_near, z_far
     return _baked_launch("pnr_baked_sparse_half_render_views", v, white_bkgd, camera=(poses, W, H, focal, c, z_near, z_far))
 
 
+# ---- scenes of several posed baked volumes (include/pixelnerf_hip.h, "Scenes of several baked volumes")
+
+def _baked_pose(what, pose):
+    """an object-to-world pose, (3,4) or (4,4), as 12 host floats [R | t] row-major; finite and rigid by the library's rule (fp64 on
+    the fp32 numbers: max |R^T R - I| <= 1e-4, det R > 0)"""
+    import math
+    p = torch.as_tensor(pose).detach().to("cpu", torch.float32)
+    if tuple(p.shape) not in ((3, 4), (4, 4)):
+        raise ValueError(f"{what}: pose must be (3,4) or (4,4) object-to-world, got {tuple(p.shape)}")
+    m = p[:3].double()
+    if not all(math.isfinite(v) for v in m.flatten().tolist()):
+        raise ValueError(f"{what}: pose is not finite")
+    rot = m[:, :3]
+    if float((rot.T @ rot - torch.eye(3, dtype=torch.float64)).abs().max()) > 1e-4 or not float(torch.linalg.det(rot)) > 0.0:
+        raise ValueError(f"{what}: pose is not rigid (max |R^T R - I| <= 1e-4 and det R > 0; no scale, shear or reflection)")
+    return p[:3].flatten().tolist()
+
+
+def _baked_scene(what, objects, step, terminate):
+    """the objects of a scene march, checked before any device work -> (the PnrBakedObject array, device, what to keep alive)"""
+    if not isinstance(objects, (list, tuple)) or not 1 <= len(objects) <= _lib.BAKED_SCENE_MAX_OBJECTS:
+        raise ValueError(f"{what}: objects must be a list of 1 to {_lib.BAKED_SCENE_MAX_OBJECTS} posed volumes, got "
+                         f"{len(objects) if isinstance(objects, (list, tuple)) else type(objects).__name__}")
+    arr = (_lib.PnrBakedObject * len(objects))()
+    keep, kind0, dev, parsed = [], None, None, []
+    for j, ob in enumerate(objects):  # what needs no device, for every object first
+        if not isinstance(ob, (list, tuple)) or not 6 <= len(ob) <= 8:
+            raise ValueError(f"{what}: object {j} must be (stored, degree, reso, c1, c2, pose[, bits[, index]])")
+        stored, degree, reso, c1, c2, pose = ob[:6]
+        bits = ob[6] if len(ob) > 6 else None
+        index = ob[7] if len(ob) > 7 else None
+        sparse = index is not None
+        if not isinstance(stored, torch.Tensor) or stored.dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"{what}: object {j}: stored must be a float32 or float16 torch.Tensor")
+        pose12 = _baked_pose(f"{what}: object {j}", pose)
+        kind = (-1 if degree is None else int(degree), stored.dtype, sparse)
+        if kind0 is None:
+            kind0, dev = kind, stored.device
+        elif kind != kind0:
+            raise ValueError(f"{what}: objects 0 and {j} differ in kind -- (degree, dtype, sparse) {kind0} against {kind} -- and one "
+                             "scene holds one kind")
+        if stored.device != dev:
+            raise ValueError(f"{what}: object {j} lives on {stored.device}, object 0 on {dev}")
+        parsed.append((stored, degree, reso, c1, c2, pose12, bits, index, sparse))
+    for j, (stored, degree, reso, c1, c2, pose12, bits, index, sparse) in enumerate(parsed):
+        v = _baked_volume(f"{what}: object {j}", stored, degree, reso, c1, c2, step, bits, terminate, dtype=stored.dtype,
+                          name="rows" if sparse else "stored", index=index, sparse=sparse)
+        _, _, stored, degree, dims, c1, c2, _, _, bits, index = v
+        o = arr[j]
+        bits = None if bits is None else bits.contiguous()
+        index = None if index is None else index.contiguous()
+        keep += [stored, bits, index]
+        o.stored = stored.data_ptr() if stored.numel() else None
+        o.bits = None if bits is None else bits.data_ptr()
+        o.index = None if index is None else index.data_ptr()
+        o.M = stored.shape[0] if sparse else 0
+        o.nx, o.ny, o.nz = dims
+        o.degree, o.storage_half, o.reserved = degree, int(stored.dtype == torch.float16), 0
+        o.c1[:], o.c2[:] = [float(x) for x in c1], [float(x) for x in c2]
+        o.pose[:] = pose12
+    return arr, dev, keep
+
+
+def _baked_scene_launch(what, entry, objects, step, white_bkgd, terminate, rays=None, camera=None):
+    lib = _lib.load()
+    arr, dev, keep = _baked_scene(what, objects, step, terminate)
+    if camera is None:
+        source = _f32(rays, "rays", (None, 8))
+        R = source.shape[0]
+        args = [_p(source), R]
+    else:
+        poses, W, H, focal, c, z_near, z_far = camera
+        source = _f32(poses, "poses", (None, 4, 4))
+        R = source.shape[0] * H * W
+        fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+        cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+        args = [_p(source), source.shape[0], W, H, fx, fy, cx, cy, float(z_near), float(z_far)]
+    if source.device != dev:
+        raise ValueError(f"{what}: the volumes live on {dev}, the {'rays' if camera is None else 'poses'} on {source.device}")
+    rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((R,), dtype=torch.float32, device=dev)
+    alpha = torch.empty((R,), dtype=torch.float32, device=dev)
+    args += (arr, len(arr), float(step), int(bool(white_bkgd)), float(terminate), _p(rgb), _p(depth), _p(alpha))
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    del keep
+    return rgb, depth, alpha
+
+
+def baked_scene_render(rays, objects, step, white_bkgd=False, terminate=0.0):
+    """Rays through a SCENE of 1 to 8 posed baked volumes of one kind (pnr_baked_scene_render_rays; the contract is in
+    include/pixelnerf_hip.h, "Scenes of several baked volumes"): rays (R,8) in the world frame; objects a list of
+    (stored, degree, reso, c1, c2, pose, bits=None, index=None) -- stored fp32 or fp16, (nx,ny,nz,4) (degree None / -1) or
+    (nx,ny,nz,B,4) (degree 0, 1, 2), or with `index` the kept rows (M,4) / (M,B,4) (bits are then mandatory); reso, c1, c2 the object's
+    grid and box in its OWN frame; pose (3,4) or (4,4) object-to-world, rigid, read on the host.  All objects share degree, dtype and
+    layout.  The samples are the world ray's; each object is sampled as its own march samples the ray in its frame, and the values at a
+    sample are mixed (sigma = the sum, colour weighted by sigma) before alpha and the product scan: volumes that overlap or stand in
+    front of each other attenuate each other sample by sample.  One object at the identity renders baked_render's bytes.
+    -> (rgb (R,3), depth (R,), alpha (R,)) fp32.  Inference only: no gradients."""
+    return _baked_scene_launch("baked_scene_render", "pnr_baked_scene_render_rays", objects, step, white_bkgd, terminate, rays=rays)
+
+
+def baked_scene_render_views(poses, width, height, focal, c, z_near, z_far, objects, step, white_bkgd=False, terminate=0.0):
+    """baked_scene_render over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c)
+    (pnr_baked_scene_render_views): poses (NV,4,4) camera-to-world; the rays are regenerated in the kernel -- the same bits as
+    baked_scene_render(gen_rays(...)), no ray array.  -> (rgb (NV*H*W,3), depth (NV*H*W,), alpha (NV*H*W,)) fp32."""
+    W, H = _image_size("baked_scene_render_views", width, height)
+    return _baked_scene_launch("baked_scene_render_views", "pnr_baked_scene_render_views", objects, step, white_bkgd, terminate,
+                               camera=(poses, W, H, focal, c, z_near, z_far))
+
+
 # ---- gradients of the baked march with respect to the stored values (include/pixelnerf_hip.h, "Gradients of the baked march")
 
 def _baked_backward(what, entry, stored, degree, reso, c1, c2, step, bits, index, white_bkgd, terminate, d_rgb, d_depth, d_alpha, out,

@@ -14,6 +14,7 @@ dense march with the same bits (pnr_baked_sparse_render_rays / pnr_baked_sparse_
 other points: less to bake and to store, not a faster march (profiles/baked_notes.md).
 All three store fp32 or fp16 (`half()`, `from_model(dtype=torch.float16)`, `to_half`): fp16 is storage only, the march is fp32 on the
 widened values, and a half volume renders the BYTES of its `float()` (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*).
+BakedScene places up to 8 volumes of one kind in one world by rigid poses and marches them together (pnr_baked_scene_render_*).
 
 The grid is the one util.recon.marching_cubes and util.occupancy.OccupancyGrid use (points of ops.gen_grid_points, cells of the TRUE
 spacing (c2 - c1) / (reso - 1)); the skip grid of a volume is an OccupancyGrid of its sigma channel with dilate 0.
@@ -149,6 +150,37 @@ def _tv_weights(what, degree, rgb, sigma, sh):
     return weights
 
 
+def _camera_args(what, poses_c2w, W, H, focal, c, gt_rgb):
+    """the camera of a render_views call, checked -> (W, H, focal, c) as the ops functions take them"""
+    if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
+        raise ValueError(f"{what}: poses_c2w must be (NVt,4,4)")
+    W, H, NVt = int(W), int(H), poses_c2w.shape[0]
+    if torch.is_tensor(focal):
+        focal = focal.flatten().tolist()
+        focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
+    if torch.is_tensor(c):
+        c = c.flatten().tolist()
+    if gt_rgb is not None and tuple(gt_rgb.shape) != (NVt, H, W, 3):
+        raise ValueError(f"{what}: gt_rgb must be (NVt,H,W,3) = {(NVt, H, W, 3)}, got {tuple(gt_rgb.shape)}")
+    return W, H, focal, c
+
+
+def _views_result(rgb, depth, alpha, NVt, W, H, z_near, z_far, gt_rgb, want_u8):
+    """the outputs of a march over NVt views through NeRFRenderer.render_views' epilogue (ops.eval_epilogue) -> the DotMap of
+    render_views"""
+    from .. import ops
+    gt = None if gt_rgb is None else gt_rgb.reshape(NVt, H * W, 3).float()
+    ep = ops.eval_epilogue(rgb.reshape(NVt, H * W, 3), depth.reshape(NVt, H * W), z_near, z_far, gt_rgb=gt, want_u8=want_u8,
+                           image_shape=(H, W) if gt is not None else None)
+    ret = DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W),
+                 depth_norm=ep["depth_norm"].reshape(NVt, H, W))
+    if want_u8:
+        ret.rgb_u8 = ep["rgb_u8"].reshape(NVt, H, W, 3)
+    if gt is not None:
+        ret.psnr, ret.ssim = ep["psnr"], ep["ssim"]
+    return ret
+
+
 class _Baked:
     """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2) and
     the storage methods.  A subclass names the tensor it stores (`_stored_name`: the attribute, and the key of its state) and has a
@@ -258,31 +290,11 @@ class _Baked:
         render.  The rays are regenerated in the kernel: the same bits as render(util.gen_rays(...)), no ray array.
         :return DotMap: rgb (NVt,H,W,3), depth and alpha (NVt,H,W), unclamped; depth_norm = (depth - z_near) / (z_far - z_near);
         rgb_u8 with want_u8; with gt_rgb (NVt,H,W,3) in [0,1] psnr and ssim (NVt,) float64 of clamp(rgb, 0, 1)"""
-        from .. import ops
-        name = type(self).__name__
-        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
-            raise ValueError(f"{name}.render_views: poses_c2w must be (NVt,4,4)")
-        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
-        if torch.is_tensor(focal):
-            focal = focal.flatten().tolist()
-            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
-        if torch.is_tensor(c):
-            c = c.flatten().tolist()
-        if gt_rgb is not None and tuple(gt_rgb.shape) != (NVt, H, W, 3):
-            raise ValueError(f"{name}.render_views: gt_rgb must be (NVt,H,W,3) = {(NVt, H, W, 3)}, got {tuple(gt_rgb.shape)}")
+        W, H, focal, c = _camera_args(f"{type(self).__name__}.render_views", poses_c2w, W, H, focal, c, gt_rgb)
         step, terminate, bits = self._march_args(step, terminate, skip)
         with torch.no_grad():
             rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, bits, white_bkgd, terminate)
-            gt = None if gt_rgb is None else gt_rgb.reshape(NVt, H * W, 3).float()
-            ep = ops.eval_epilogue(rgb.reshape(NVt, H * W, 3), depth.reshape(NVt, H * W), z_near, z_far, gt_rgb=gt, want_u8=want_u8,
-                                   image_shape=(H, W) if gt is not None else None)
-        ret = DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W),
-                     depth_norm=ep["depth_norm"].reshape(NVt, H, W))
-        if want_u8:
-            ret.rgb_u8 = ep["rgb_u8"].reshape(NVt, H, W, 3)
-        if gt is not None:
-            ret.psnr, ret.ssim = ep["psnr"], ep["ssim"]
-        return ret
+            return _views_result(rgb, depth, alpha, poses_c2w.shape[0], W, H, z_near, z_far, gt_rgb, want_u8)
 
     def _march_diff(self, source, step, bits, white_bkgd, terminate):
         from .. import autograd
@@ -642,6 +654,101 @@ class SparseBakedVolume(_Baked):
         n_occupied = table[bits.view(torch.uint8).long()].sum().to(torch.int32)
         occupancy = OccupancyGrid(bits, state["reso"].tolist(), state["c1"].tolist(), state["c2"].tolist(), float("nan"), 0, n_occupied)
         return cls(rows, occupancy)
+
+
+# ---------------------------------------------------------------- scenes: several posed volumes in one image
+
+def _kind_of(v):
+    return type(v).__name__, v.degree, v.dtype, v._stored_name == "rows"
+
+
+class BakedScene:
+    """1 to 8 baked volumes of ONE kind, each placed in the world by a rigid pose, marched together (ops.baked_scene_render;
+    include/pixelnerf_hip.h, "Scenes of several baked volumes").  Each object keeps its own frame, grid and box; along a world ray the
+    objects are sampled at the same depths, each as its own `render` samples the ray in its frame, and mixed per sample (sigma = the
+    sum, colour weighted by sigma) before compositing -- so overlapping volumes, and one in front of another, attenuate each other as
+    separate renders cannot.  One volume at the identity pose renders the bytes of its own `render`.
+    volumes: a list of BakedVolume, BakedSHVolume or SparseBakedVolume of one class, degree, dtype and layout on one device; poses:
+    (N,4,4) or (N,3,4) object-to-world, rigid (what `register` recovers, inverted, is such a pose); kept as given, on the host, fp32.
+    Inference only: `render` and `render_views` run under torch.no_grad().  Nothing is copied: the scene refers to its volumes."""
+
+    def __init__(self, volumes, poses):
+        from .. import _lib
+        if not isinstance(volumes, (list, tuple)) or not 1 <= len(volumes) <= _lib.BAKED_SCENE_MAX_OBJECTS:
+            raise ValueError(f"BakedScene: volumes must be a list of 1 to {_lib.BAKED_SCENE_MAX_OBJECTS} baked volumes, got "
+                             f"{len(volumes) if isinstance(volumes, (list, tuple)) else type(volumes).__name__}")
+        for j, v in enumerate(volumes):
+            if not isinstance(v, _Baked):
+                raise ValueError(f"BakedScene: volume {j} is a {type(v).__name__}, not a baked volume")
+            if _kind_of(v) != _kind_of(volumes[0]):
+                raise ValueError(f"BakedScene: volumes 0 and {j} differ in kind -- (class, degree, dtype, sparse) {_kind_of(volumes[0])} against "
+                                 f"{_kind_of(v)} -- and one scene holds one kind; convert with .float() / .half() (dtype), .sparse(occ) / "
+                                 ".to_dense() (layout), sh.at_direction(d) (a coefficient volume as an RGBA one)")
+            if v._stored().device != volumes[0]._stored().device:
+                raise ValueError(f"BakedScene: volume {j} lives on {v._stored().device}, volume 0 on {volumes[0]._stored().device}")
+        poses = torch.as_tensor(poses).detach().to("cpu", torch.float32)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((4, 4), (3, 4)) or poses.shape[0] != len(volumes):
+            raise ValueError(f"BakedScene: poses must be ({len(volumes)},4,4) or ({len(volumes)},3,4) object-to-world, got {tuple(poses.shape)}")
+        from .. import ops
+        for j, pose in enumerate(poses):
+            ops._baked_pose(f"BakedScene: object {j}", pose)  # (finite and rigid: refused here, not at the first render)
+        self.volumes, self.poses = list(volumes), poses
+
+    def __len__(self):
+        return len(self.volumes)
+
+    def with_pose(self, j, pose):
+        """this scene with object j at another pose (3,4) or (4,4); the volumes are shared"""
+        j = int(j)
+        if not 0 <= j < len(self):
+            raise IndexError(f"BakedScene.with_pose: no object {j} in a scene of {len(self)}")
+        pose = torch.as_tensor(pose).detach().to("cpu", torch.float32)
+        if tuple(pose.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"BakedScene.with_pose: pose must be (3,4) or (4,4), got {tuple(pose.shape)}")
+        poses = self.poses.clone()
+        poses[j, :3] = pose[:3]
+        return BakedScene(self.volumes, poses)
+
+    def _objects(self, skip):
+        """the list ops.baked_scene_render takes"""
+        objects = []
+        for v, pose in zip(self.volumes, self.poses):
+            sparse = v._stored_name == "rows"
+            bits = v.occupancy.bits if skip or sparse else None
+            objects.append((v._stored(), v.degree, v.reso, v.c1, v.c2, pose, bits, v.index if sparse else None))
+        return objects
+
+    def _march_args(self, step, terminate):
+        step = min(min(v.cell_size) for v in self.volumes) if step is None else float(step)
+        return step, (0.0 if terminate is None else float(terminate))
+
+    def render(self, rays, step=None, white_bkgd=False, terminate=None, skip=True):
+        """world rays (...,8) on the scene's device -> DotMap(rgb (...,3), depth (...), alpha (...)); ops.baked_scene_render.
+        :param step the sample distance in the units of z; None: the smallest cell edge over all objects
+        :param terminate as BakedVolume.render: checked every 64 samples on the transmittance of the mixture
+        :param skip march every dense volume against its skip grid (exact at skip_threshold 0); sparse volumes always do"""
+        from .. import ops
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError("BakedScene.render: rays must be (...,8)")
+        lead = tuple(rays.shape[:-1])
+        step, terminate = self._march_args(step, terminate)
+        with torch.no_grad():
+            rgb, depth, alpha = ops.baked_scene_render(rays.reshape(-1, 8).float(), self._objects(skip), step, white_bkgd=white_bkgd,
+                                                       terminate=terminate)
+        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+    def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, step=None, white_bkgd=False,
+                     terminate=None, skip=True):
+        """Every pixel of the target views from their cameras, as BakedVolume.render_views: poses_c2w (NVt,4,4) camera-to-WORLD; the
+        rays are regenerated in the kernel (the same bits as render(util.gen_rays(...))), and the outputs go through the same
+        epilogue.  :return DotMap: rgb (NVt,H,W,3), depth, alpha, depth_norm (NVt,H,W); rgb_u8 with want_u8; psnr, ssim with gt_rgb"""
+        from .. import ops
+        W, H, focal, c = _camera_args("BakedScene.render_views", poses_c2w, W, H, focal, c, gt_rgb)
+        step, terminate = self._march_args(step, terminate)
+        with torch.no_grad():
+            rgb, depth, alpha = ops.baked_scene_render_views(poses_c2w.float(), W, H, focal, c, z_near, z_far, self._objects(skip), step,
+                                                             white_bkgd=white_bkgd, terminate=terminate)
+            return _views_result(rgb, depth, alpha, poses_c2w.shape[0], W, H, z_near, z_far, gt_rgb, want_u8)
 
 
 # ---------------------------------------------------------------- fitting: gradients with respect to the stored values
