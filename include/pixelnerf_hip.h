@@ -1340,6 +1340,81 @@ int pnr_baked_scene_render_views(const float *poses /*(NV,4,4)*/, int NV, int W,
                                  int white_bkgd, float terminate, float *rgb /*(NV H W,3)*/, float *depth, float *alpha,
                                  void *stream);
 
+/* Gradients of the scene march (added within ABI rev 12 as well; "Not here: gradients of any kind" above stays true of the two
+ * render entries -- these two are the gradient with respect to the world RAYS and to each object's POSE; the stored values of a
+ * scene are not differentiated).  What lets a caller find where an object stands: move its pose by gradient descent until the
+ * scene matches its images, or refine a camera against a scene with an occluder in it.
+ * pnr_baked_scene_backward_rays / _views are the backward of pnr_baked_scene_render_rays / _views for every kind those take:
+ *   RGBA and degree 0, 1, 2, dense and sparse rows, fp32 and fp16 storage (the volumes are not differentiated, so a half volume is
+ *   legitimate, as in pnr_baked_ray_backward_*).  objects, step, white_bkgd, terminate: the forward's.  d_rgb, d_depth, d_alpha:
+ *   the upstream gradients of the march's outputs, each NULL = zeros.
+ * Outputs, each WRITTEN (not added into):
+ *   d_rays  (R,8)            dL/d [ox,oy,oz,dx,dy,dz,near,far] of the WORLD ray; column 7 is exactly 0.  The views form writes the
+ *                            gradient with respect to the regenerated ray, rows ordered (view, row, column): pnr_gen_rays_backward
+ *                            applied to it is the gradient with respect to the cameras.
+ *   d_local (R,n_objects,6)  dL/d (o'_j, d'_j): the gradient with respect to the ray in the frame of object j.
+ *   d_poses (n_objects,12)   nullable.  dL/d [R_j | t_j] as 12 FREE numbers, row-major (3,4) as PnrBakedObject::pose; the caller
+ *                            projects onto the tangent of the rigid motions.
+ * Samples: exactly the forward's.  The walk is pnr_baked_ray_backward_*'s: a first walk in the forward's direction finds the chunk
+ *   the forward stopped after (by the forward's own fp32 factors) and the fp64 transmittance at the head of each chunk; then the
+ *   chunks from last to first with the fp64 reverse affine scan; beyond 4096 samples the heads are rebuilt.  It is applied to the
+ *   mixture (c_i, sigma_i) of the scene march, formed with the forward's operations in list order.
+ * Along the ray: g_i, T_i, S_i, w_i, dL/da_i, dL/dsigma_i = dL/da_i step (1 - a_i) and dL/dc_i = w_i d_rgb are those of
+ *   pnr_baked_ray_backward_*, computed on sigma_i = sum_j sigma_ij and c_i = sum_j (sigma_ij / sigma_i) c_ij.
+ * Through the mixing, for every object j that contributes to sample i, where sigma_i > 0:
+ *     dL/dc_ij = (sigma_ij / sigma_i) dL/dc_i,      dL/dsigma_ij = dL/dsigma_i + ((c_ij - c_i) . dL/dc_i) / sigma_i
+ *   CONVENTION: where sigma_i is not > 0 the forward's colour is the constant 0, so there dL/dc_ij = 0 and dL/dsigma_ij =
+ *   dL/dsigma_i.  Off the cell planes a blended sigma of exactly 0 (stored sigmas >= 0) has zero spatial slope, so nothing is lost.
+ *   With one contributor sigma_ij / sigma_i is exactly 1 and c_ij - c_i exactly 0: no special case.
+ * Through each object's blend, exactly as pnr_baked_ray_backward_* do in that object's frame on the object ray (o', d'): the
+ *   partials of the blend, the clamp of the fractions, the division by that object's h, and for a coefficient volume dL/dY_k and
+ *   its way through Y(d' / |d'|).  Per sample this gives dp'_ij (fp32), and per ray and object
+ *     d_local[r][j] = (sum_i dp'_ij,  sum_i t_i dp'_ij + the basis term of object j)
+ * World ray: dp_i = sum_j R_j dp'_ij in fp32, objects in list order, each component (R_a0 x + R_a1 y) + R_a2 z;
+ *     dL/dt_i = sum_j dp'_ij . d'_j + d_depth w_i
+ *     d_o = sum_i dp_i,   d_d = sum_i t_i dp_i + sum_j R_j basis_j,   d_near = sum_i dL/dt_i,   d_far = 0
+ * Poses: with q = o - t_j as the forward forms it,
+ *     dL/dR_j[r][a] = sum_rays (q_r d_local.o'_a + d_r d_local.d'_a),      dL/dt_j[r] = - sum_rays sum_a R_j[r][a] d_local.o'_a
+ *   reduced by a second kernel that regenerates (o, d) from the same ray source (explicit rows or cameras).
+ * Treated as CONSTANTS: everything pnr_baked_ray_backward_* list, per object -- the sample count, the inside tests, the skip bits,
+ *   the row lookup, the stop chunk, the cells floor() names, the sides of the clamps -- and which objects contribute to a sample.
+ * Arithmetic: the per-sample part is fp32, each operation rounded on its own; what runs along the ray (T_i, the maps of S_i) is
+ *   fp64 as in pnr_baked_ray_backward_*.  The seven sums of the world row are per-lane doubles over the chunks, reduced by the
+ *   butterfly of the ray's wavefront, in that entry's order.  dL/dt_i is formed per contributing object as that entry's fp32 chain
+ *   ((d_depth w_i + x) + y) + z on dp'_ij . d'_j; the chains are added in fp64 and the cnt - 1 surplus d_depth w_i taken off, so
+ *   one contributor gives that entry's number and two objects commute.  The six numbers of an object are summed per chunk across the lanes
+ *   (fp64, the same butterfly) and added, chunk after chunk from the last to the first, into one fp64 accumulator per (object,
+ *   number); the basis sums dL/dY_k are per-lane fp32 sums per object, reduced at the end as that entry reduces them.  The pose
+ *   reduction is fp64 in a fixed order -- a thread over the rays it owns, the lanes by the butterfly, one last wave per object over
+ *   the block partials -- and rounds to fp32 once; a ray whose d_local row of an object is all zeros is not added for it.
+ * Guarantees: no atomics, no LDS, no memory allocated by the library; every row of d_rays and d_local is written; exact zeros
+ *   (8 + 6 n_objects of them) for a ray with no samples or with all-zero upstream gradients; an object no ray meets gets 12 exact
+ *   zeros in d_poses; two calls give equal bytes; the sparse form gives the dense form's bytes; fp16 storage gives the bytes of the
+ *   call on the widened values; the views entry gives the rays entry's bytes on pnr_gen_rays' rows; ONE object whose pose is
+ *   exactly [I | 0] gives pnr_baked_ray_backward_*'s bytes in d_rays (products with 0 and 1 and sums with 0 are exact).
+ *   workspace: pnr_baked_scene_backward_workspace_bytes() bytes of device memory (384 KiB, whatever the scene), 8-byte aligned,
+ *   needed only with d_poses; two calls in flight on different streams need one each.  Index arithmetic is 64-bit; no input makes a
+ *   kernel read outside an object's stored, index or bits, or outside the workspace.
+ * PNR_E_INVALID, before any HIP call: the refusals of pnr_baked_scene_render_*, in their order and words, through the same
+ *   checking function, with d_rays / d_local in the place of rgb / depth / alpha ("null argument" with R > 0); the alignment
+ *   sentence is "d_rgb, d_depth, d_alpha, d_rays, d_local and d_poses must be 4-byte aligned"; then one more: d_poses without a
+ *   workspace, or with one that is not 8-byte aligned ("d_poses needs the workspace of
+ *   pnr_baked_scene_backward_workspace_bytes(), 8-byte aligned"); per object the words are those of pnr_baked_ray_backward_*.
+ *   R = 0 (NV = 0): nothing is marched, PNR_OK; d_poses, if given, is still WRITTEN, as zeros. */
+size_t pnr_baked_scene_backward_workspace_bytes(void);
+int pnr_baked_scene_backward_rays(const float *rays, long long R, const PnrBakedObject *objects /*host*/, int n_objects, float step,
+                                  int white_bkgd, float terminate, const float *d_rgb /*(R,3), nullable*/,
+                                  const float *d_depth /*(R), nullable*/, const float *d_alpha /*(R), nullable*/,
+                                  float *d_rays /*(R,8), every row written*/, float *d_local /*(R,n_objects,6), every row written*/,
+                                  float *d_poses /*(n_objects,12), nullable; written*/, void *workspace /*needed only with d_poses*/,
+                                  void *stream);
+int pnr_baked_scene_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                   float z_near, float z_far, const PnrBakedObject *objects /*host*/, int n_objects, float step,
+                                   int white_bkgd, float terminate, const float *d_rgb /*(NV H W,3), nullable*/,
+                                   const float *d_depth /*nullable*/, const float *d_alpha /*nullable*/,
+                                   float *d_rays /*(NV H W,8)*/, float *d_local /*(NV H W,n_objects,6)*/,
+                                   float *d_poses /*(n_objects,12), nullable*/, void *workspace, void *stream);
+
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on
  * that stream (call only after the stream has been synchronised). */

@@ -241,6 +241,11 @@ PROTOTYPES = {
     "pnr_baked_scene_render_rays": (_I, [_P, ctypes.c_longlong, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F, _P, _P, _P, _P]),
     "pnr_baked_scene_render_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F,
                                           _P, _P, _P, _P]),
+    "pnr_baked_scene_backward_workspace_bytes": (_SZ, []),
+    "pnr_baked_scene_backward_rays": (_I, [_P, ctypes.c_longlong, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F, _P, _P, _P, _P, _P, _P,
+                                           _P, _P]),
+    "pnr_baked_scene_backward_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F,
+                                            _P, _P, _P, _P, _P, _P, _P, _P]),
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }

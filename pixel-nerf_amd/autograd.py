@@ -663,6 +663,62 @@ def baked_march_rays_autograd(stored, source, degree, reso, c1, c2, step, bits=N
                                          bool(white_bkgd), float(terminate))
 
 
+class _BakedSceneMarchFunction(torch.autograd.Function):
+    """The scene march of several posed baked volumes, differentiable with respect to its world RAYS or camera POSES and to the
+    OBJECT poses (include/pixelnerf_hip.h, "Gradients of the scene march").  forward IS the inference entry; backward one
+    pnr_baked_scene_backward_* call (no atomics: the same bytes on every call), for a camera followed by ops.gen_rays_backward.
+    The stored values are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, lead, obj_poses, rest, volumes, step, white_bkgd, terminate):
+        ctx.set_materialize_grads(False)
+        host = obj_poses.detach().to("cpu", torch.float32)  # the poses are kernel arguments by value: one host read
+        objects = [(stored, degree, reso, c1, c2, host[j], bits, index) for j, (stored, degree, reso, c1, c2, bits, index) in enumerate(volumes)]
+        entry = ops.baked_scene_render if not rest else ops.baked_scene_render_views
+        out = entry(lead, *rest, objects, step, white_bkgd=white_bkgd, terminate=terminate)
+        ctx.save_for_backward(lead, obj_poses)
+        ctx.march = (rest, objects, step, white_bkgd, terminate)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_alpha):
+        lead, obj_poses = ctx.saved_tensors
+        rest, objects, step, white_bkgd, terminate = ctx.march
+        if (d_rgb is None and d_depth is None and d_alpha is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 7
+        fp32 = lambda g: None if g is None else g.contiguous().float()
+        entry = ops.baked_scene_backward if not rest else ops.baked_scene_backward_views
+        d_rays, _, d_poses = entry(lead.detach(), *rest, objects, step, d_rgb=fp32(d_rgb), d_depth=fp32(d_depth), d_alpha=fp32(d_alpha),
+                                   white_bkgd=white_bkgd, terminate=terminate, want_poses=ctx.needs_input_grad[1])
+        d_lead = d_obj = None
+        if ctx.needs_input_grad[0]:
+            d_lead = d_rays if not rest else ops.gen_rays_backward(d_rays, rest[0], rest[1], rest[2], rest[3])
+        if ctx.needs_input_grad[1]:
+            d_obj = d_poses.reshape(-1, 3, 4).to(device=obj_poses.device, dtype=obj_poses.dtype)
+        return (d_lead, d_obj) + (None,) * 5
+
+
+def baked_scene_march_autograd(source, objects, obj_poses, step, white_bkgd=False, terminate=0.0):
+    """-> (rgb (R,3), depth (R,), alpha (R,)) of the scene march -- the bytes of ops.baked_scene_render / _views --, differentiable
+    with respect to source[0] -- the world rays (R,8) of source = (rays,), or the camera poses (NV,4,4) of source = (poses, W, H,
+    focal, c, z_near, z_far) (through ops.gen_rays_backward) -- and with respect to obj_poses (N,3,4), the object-to-world poses, on
+    any device.  objects: a list of (stored, degree, reso, c1, c2, bits, index) -- ops.baked_scene_render's tuples without the pose.
+    The gradient of obj_poses is that of 12 free numbers per object: a caller that parametrises rigid motions (util.bake.moved_poses)
+    gets the projection from autograd.  The stored values are not differentiated.
+    The object poses are kernel arguments BY VALUE: a differentiable call reads the N x 12 numbers to the host once per forward (a
+    synchronisation when they live on the device)."""
+    source = tuple(source)
+    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
+        raise ValueError("baked_scene_march_autograd: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
+    if not isinstance(obj_poses, torch.Tensor) or obj_poses.dim() != 3 or tuple(obj_poses.shape[1:]) != (3, 4) \
+            or obj_poses.shape[0] != len(objects) or not obj_poses.is_floating_point():
+        raise ValueError(f"baked_scene_march_autograd: obj_poses must be a float tensor ({len(objects)},3,4) object-to-world")
+    volumes = tuple(tuple(ob) for ob in objects)
+    if any(len(ob) != 7 for ob in volumes):
+        raise ValueError("baked_scene_march_autograd: an object must be (stored, degree, reso, c1, c2, bits, index)")
+    return _BakedSceneMarchFunction.apply(source[0], obj_poses, source[1:], volumes, float(step), bool(white_bkgd), float(terminate))
+
+
 class _BakedTvFunction(torch.autograd.Function):
     """The total-variation prior of a baked volume's stored values (include/pixelnerf_hip.h, "Total-variation prior").  forward asks
     pnr_baked_tv for the value alone, backward for the gradient alone with scale = grad_output left on the device: no host read on

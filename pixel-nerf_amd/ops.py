@@ -1653,7 +1653,8 @@ def baked_scene_render(rays, objects, step, white_bkgd=False, terminate=0.0):
     layout.  The samples are the world ray's; each object is sampled as its own march samples the ray in its frame, and the values at a
     sample are mixed (sigma = the sum, colour weighted by sigma) before alpha and the product scan: volumes that overlap or stand in
     front of each other attenuate each other sample by sample.  One object at the identity renders baked_render's bytes.
-    -> (rgb (R,3), depth (R,), alpha (R,)) fp32.  Inference only: no gradients."""
+    -> (rgb (R,3), depth (R,), alpha (R,)) fp32.  No autograd here: baked_scene_backward is its gradient with respect to the rays
+    and the poses, autograd.baked_scene_march_autograd ties the two together."""
     return _baked_scene_launch("baked_scene_render", "pnr_baked_scene_render_rays", objects, step, white_bkgd, terminate, rays=rays)
 
 
@@ -1664,6 +1665,78 @@ def baked_scene_render_views(poses, width, height, focal, c, z_near, z_far, obje
     W, H = _image_size("baked_scene_render_views", width, height)
     return _baked_scene_launch("baked_scene_render_views", "pnr_baked_scene_render_views", objects, step, white_bkgd, terminate,
                                camera=(poses, W, H, focal, c, z_near, z_far))
+
+
+# ---- gradients of the scene march with respect to the world rays and the objects' poses (include/pixelnerf_hip.h, "Gradients of
+# the scene march")
+
+def _baked_scene_backward(what, entry, objects, step, white_bkgd, terminate, d_rgb, d_depth, d_alpha, want_poses, rays=None, camera=None):
+    """baked_scene_render's checks before any device work, then pnr_baked_scene_backward_rays / _views
+    -> (d_rays (R,8), d_local (R,N,6), d_poses (N,12) or None), every row written by the kernels"""
+    lib = _lib.load()
+    arr, dev, keep = _baked_scene(what, objects, step, terminate)
+    detached = lambda t: t.detach() if isinstance(t, torch.Tensor) else t  # (the gradient goes to what the caller holds)
+    if camera is None:
+        source = _f32(detached(rays), "rays", (None, 8))
+        R = source.shape[0]
+        args = [_p(source), R]
+    else:
+        poses, W, H, focal, c, z_near, z_far = camera
+        source = _f32(detached(poses), "poses", (None, 4, 4))
+        R = source.shape[0] * H * W
+        fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+        cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+        args = [_p(source), source.shape[0], W, H, fx, fy, cx, cy, float(z_near), float(z_far)]
+    if source.device != dev:
+        raise ValueError(f"{what}: the volumes live on {dev}, the {'rays' if camera is None else 'poses'} on {source.device}")
+    grads = []
+    for g, name, shape in ((d_rgb, "d_rgb", (R, 3)), (d_depth, "d_depth", (R,)), (d_alpha, "d_alpha", (R,))):
+        g = None if g is None else _f32(detached(g), name, shape)
+        if g is not None and g.device != dev:
+            raise ValueError(f"{what}: {name} lives on {g.device}, the volumes on {dev}")
+        grads.append(g)
+    N = len(arr)
+    d_rays = torch.empty((R, 8), dtype=torch.float32, device=dev)
+    d_local = torch.empty((R, N, 6), dtype=torch.float32, device=dev)
+    d_poses = workspace = None
+    if want_poses:
+        d_poses = torch.empty((N, 12), dtype=torch.float32, device=dev)
+        workspace = torch.empty((int(lib.pnr_baked_scene_backward_workspace_bytes()) // 8,), dtype=torch.float64, device=dev)
+    args += (arr, N, float(step), int(bool(white_bkgd)), float(terminate), _p(grads[0]), _p(grads[1]), _p(grads[2]),
+             _p(d_rays) if R else None, _p(d_local) if R else None, _p(d_poses), _p(workspace))
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    del keep
+    return d_rays, d_local, d_poses
+
+
+def baked_scene_backward(rays, objects, step, d_rgb=None, d_depth=None, d_alpha=None, white_bkgd=False, terminate=0.0, want_poses=True):
+    """The gradient of baked_scene_render with respect to the world RAYS and the objects' POSES (pnr_baked_scene_backward_rays;
+    the contract is in include/pixelnerf_hip.h, "Gradients of the scene march"): rays (R,8) and objects as baked_scene_render takes
+    them, every kind it takes (the volumes are not differentiated: fp16 is legitimate); d_rgb (R,3), d_depth (R,), d_alpha (R,) the
+    upstream gradients of its outputs, None = zeros.
+    -> (d_rays (R,8) = dL/d [origin, direction, near, far] of the world ray, column 7 exactly 0;
+        d_local (R,N,6) = dL/d (o', d') of the ray in each object's frame;
+        d_poses (N,12) = dL/d [R | t] of each object as 12 free numbers, row-major (3,4) -- None with want_poses=False).
+    Every row is written by the kernels (exact zeros for a ray without samples or without upstream gradient, 12 exact zeros for an
+    object no ray meets).  The samples are exactly the forward's; the sample count, the inside tests, the skip bits, the stop chunk,
+    the cells, the clamps' sides and which objects contribute to a sample are constants.  No atomics: the same bytes on every call.
+    One object at the identity gives baked_ray_backward's bytes in d_rays."""
+    return _baked_scene_backward("baked_scene_backward", "pnr_baked_scene_backward_rays", objects, step, white_bkgd, terminate, d_rgb,
+                                 d_depth, d_alpha, want_poses, rays=rays)
+
+
+def baked_scene_backward_views(poses, width, height, focal, c, z_near, z_far, objects, step, d_rgb=None, d_depth=None, d_alpha=None,
+                               white_bkgd=False, terminate=0.0, want_poses=True):
+    """baked_scene_backward over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c)
+    (pnr_baked_scene_backward_views): the rays are regenerated in the kernels, d_rgb (NV*H*W,3), d_depth and d_alpha (NV*H*W,)
+    ordered (view, row, column).  -> (d_rays (NV,H,W,8), d_local (NV*H*W,N,6), d_poses (N,12) or None): the bytes of
+    baked_scene_backward(gen_rays(...)); gen_rays_backward of d_rays is the gradient with respect to the cameras."""
+    W, H = _image_size("baked_scene_backward_views", width, height)
+    d_rays, d_local, d_poses = _baked_scene_backward("baked_scene_backward_views", "pnr_baked_scene_backward_views", objects, step,
+                                                     white_bkgd, terminate, d_rgb, d_depth, d_alpha, want_poses,
+                                                     camera=(poses, W, H, focal, c, z_near, z_far))
+    return d_rays.reshape(-1, H, W, 8), d_local, d_poses
 
 
 # ---- gradients of the baked march with respect to the stored values (include/pixelnerf_hip.h, "Gradients of the baked march")

@@ -670,7 +670,10 @@ class BakedScene:
     separate renders cannot.  One volume at the identity pose renders the bytes of its own `render`.
     volumes: a list of BakedVolume, BakedSHVolume or SparseBakedVolume of one class, degree, dtype and layout on one device; poses:
     (N,4,4) or (N,3,4) object-to-world, rigid (what `register` recovers, inverted, is such a pose); kept as given, on the host, fp32.
-    Inference only: `render` and `render_views` run under torch.no_grad().  Nothing is copied: the scene refers to its volumes."""
+    `render` and `render_views` are inference: they run under torch.no_grad().  `render_diff` and `render_views_diff` give the same
+    bytes with autograd to the world rays or the cameras and to the object poses (include/pixelnerf_hip.h, "Gradients of the scene
+    march"); `place` descends on the poses of chosen objects.  The stored values of a scene get no gradient.  Nothing is copied: the
+    scene refers to its volumes."""
 
     def __init__(self, volumes, poses):
         from .. import _lib
@@ -749,6 +752,49 @@ class BakedScene:
             rgb, depth, alpha = ops.baked_scene_render_views(poses_c2w.float(), W, H, focal, c, z_near, z_far, self._objects(skip), step,
                                                              white_bkgd=white_bkgd, terminate=terminate)
             return _views_result(rgb, depth, alpha, poses_c2w.shape[0], W, H, z_near, z_far, gt_rgb, want_u8)
+
+    def _obj_poses(self, what, poses):
+        """the object poses of a differentiable call: self.poses, or the tensor (N,3,4) / (N,4,4) that replaces them -> (N,3,4)"""
+        if poses is None:
+            return self.poses[:, :3]
+        if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)) \
+                or poses.shape[0] != len(self) or not poses.is_floating_point():
+            raise ValueError(f"BakedScene.{what}: the object poses must be a float tensor ({len(self)},3,4) or ({len(self)},4,4) "
+                             f"object-to-world, got {tuple(poses.shape) if isinstance(poses, torch.Tensor) else type(poses).__name__}")
+        return poses[:, :3]
+
+    def _march_diff(self, source, obj_poses, step, white_bkgd, terminate, skip):
+        from .. import autograd
+        volumes = [ob[:5] + ob[6:] for ob in self._objects(skip)]
+        return autograd.baked_scene_march_autograd(source, volumes, obj_poses, step, white_bkgd=white_bkgd, terminate=terminate)
+
+    def render_diff(self, rays, poses=None, step=None, white_bkgd=False, terminate=None, skip=True):
+        """`render` with autograd: world rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)), the bytes `render` gives, and a
+        backward (one pnr_baked_scene_backward_rays call: no atomics, the same bytes on every call) that hands dL/d rays to whatever
+        made them and, when `poses` requires grad, dL/d poses to it.
+        :param poses None: the scene's own poses (constants); else a tensor (N,3,4) or (N,4,4), object-to-world, that REPLACES them
+        for this call -- it must be rigid, as the scene's are; the gradient is that of 12 free numbers per object, and a caller that
+        builds the poses from rigid parameters (`moved_poses`) gets its projection from autograd.  The poses are kernel arguments by
+        value: they are read to the host once per call.  step, terminate, skip: as render."""
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError("BakedScene.render_diff: rays must be (...,8)")
+        obj_poses = self._obj_poses("render_diff", poses)
+        lead = tuple(rays.shape[:-1])
+        step, terminate = self._march_args(step, terminate)
+        rgb, depth, alpha = self._march_diff((rays.reshape(-1, 8).float(),), obj_poses, step, white_bkgd, terminate, skip)
+        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+    def render_views_diff(self, poses_c2w, W, H, focal, z_near, z_far, c=None, obj_poses=None, step=None, white_bkgd=False, terminate=None,
+                          skip=True):
+        """`render_views` without its epilogue and with autograd: poses_c2w (NVt,4,4) -> DotMap(rgb (NVt,H,W,3), depth and alpha
+        (NVt,H,W)), the bytes `render_views` gives; the backward is pnr_baked_scene_backward_views, followed by ops.gen_rays_backward
+        for the cameras (the intrinsics are constants).  obj_poses: as `poses` of render_diff.  What `place` descends on."""
+        W, H, focal, c = _camera_args("BakedScene.render_views_diff", poses_c2w, W, H, focal, c, None)
+        obj_poses = self._obj_poses("render_views_diff", obj_poses)
+        NVt = poses_c2w.shape[0]
+        step, terminate = self._march_args(step, terminate)
+        rgb, depth, alpha = self._march_diff((poses_c2w.float(), W, H, focal, c, z_near, z_far), obj_poses, step, white_bkgd, terminate, skip)
+        return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
 
 
 # ---------------------------------------------------------------- fitting: gradients with respect to the stored values
@@ -942,3 +988,56 @@ def register(volume, target_rgb, poses0, W, H, focal, z_near, z_far, c=None, ste
     with torch.no_grad():
         poses = moved_poses(poses0, w, v)
     return poses, (torch.stack(losses).tolist() if losses else [])
+
+
+# ---------------------------------------------------------------- placing: gradients with respect to the objects' poses
+
+def place(scene, target_rgb, cam_poses, W, H, focal, z_near, z_far, c=None, objects=None, steps=200, lr=1e-2, step=None,
+          white_bkgd=False, terminate=None, skip=True):
+    """Place objects of a scene against images: Adam on a 6-DoF update per moved object, P_j = [R(w_j) R0_j | t0_j + v_j] with w an
+    axis-angle vector through `rodrigues` and v a translation, both starting at 0 (`moved_poses`: the object turns about its own
+    origin), loss = mean((rgb - target_rgb)^2) over all pixels of all views, rgb = scene.render_views_diff(cam_poses, ...,
+    obj_poses=P).rgb.  scene: a BakedScene of any kind, fp32 or fp16 (it is not changed); target_rgb (NV,H,W,3); cam_poses (NV,4,4)
+    camera-to-world, fixed; W, H, focal, z_near, z_far, c: the camera, as render_views takes it; objects: the indices of the
+    objects that move (None: all) -- the others keep their poses bit for bit; step, white_bkgd, terminate, skip: as render.
+    A step costs one scene march, one pnr_baked_scene_backward_views call and one host read of the poses; no network.  The loss is
+    only piecewise smooth in a pose and the descent is local: it converges from a start inside the basin of the true pose
+    (profiles/baked_notes.md, "Scene gradients and placing objects").
+    -> (a BakedScene with the new poses -- the volumes are shared --, losses: the `steps` losses as floats, read once at the end)"""
+    if not isinstance(scene, BakedScene):
+        raise TypeError(f"place: expected a BakedScene, got {type(scene).__name__}")
+    if not isinstance(cam_poses, torch.Tensor) or cam_poses.dim() != 3 or tuple(cam_poses.shape[1:]) != (4, 4):
+        raise ValueError("place: cam_poses must be (NV,4,4)")
+    W, H, NV, steps, N = int(W), int(H), cam_poses.shape[0], int(steps), len(scene)
+    if not isinstance(target_rgb, torch.Tensor) or tuple(target_rgb.shape) != (NV, H, W, 3):
+        raise ValueError(f"place: target_rgb must be (NV,H,W,3) = {(NV, H, W, 3)}, got "
+                         f"{tuple(target_rgb.shape) if isinstance(target_rgb, torch.Tensor) else type(target_rgb).__name__}")
+    if steps < 0:
+        raise ValueError(f"place: steps must be >= 0, got {steps}")
+    moved = list(range(N)) if objects is None else [int(j) for j in objects]
+    if not moved or len(set(moved)) != len(moved) or not all(0 <= j < N for j in moved):
+        raise ValueError(f"place: objects must be distinct indices into a scene of {N} (None: all), got {objects}")
+    cam_poses, target = cam_poses.detach().float(), target_rgb.detach().float()
+    poses0 = scene.poses[:, :3].clone()  # (N,3,4) on the host, where the kernels take them from
+    w = torch.zeros((len(moved), 3), dtype=torch.float32, requires_grad=True)
+    v = torch.zeros((len(moved), 3), dtype=torch.float32, requires_grad=True)
+
+    def current():
+        poses = poses0.clone()
+        poses[moved] = moved_poses(poses0[moved], w, v)
+        return poses
+
+    optimiser = torch.optim.Adam([w, v], lr=float(lr))
+    losses = []
+    for _ in range(steps):
+        out = scene.render_views_diff(cam_poses, W, H, focal, z_near, z_far, c=c, obj_poses=current(), step=step, white_bkgd=white_bkgd,
+                                      terminate=terminate, skip=skip)
+        loss = ((out.rgb - target) ** 2).mean()
+        optimiser.zero_grad(set_to_none=True)
+        loss.backward()
+        optimiser.step()
+        losses.append(loss.detach())
+    with torch.no_grad():
+        poses = scene.poses.clone()
+        poses[:, :3] = current()
+    return BakedScene(scene.volumes, poses), (torch.stack(losses).tolist() if losses else [])
