@@ -15,8 +15,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # experiment switch is compiled with -DPNR_VARIANT and reports a NEGATIVE ABI revision: load() refuses it unless the
 # process says PIXELNERF_ALLOW_VARIANT=1 (the A/B tools do) -- a stray -D can no longer yield a library that passes for the product
 LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelnerf_hip.so")
-SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_scatter.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip", "pnr_mesh.hip", "pnr_occupancy.hip", "pnr_meshfinish.hip", "pnr_baked.hip"]
-HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_geom.h", "pnr_wave.h", "pnr_raysrc.h", "pnr_internal.h", "pnr_entry.h", "pnr_scatter_plan.h", "pnr_occgrid.h", "pnr_mc_tables.inc", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
+SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_scatter.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip", "pnr_mesh.hip", "pnr_occupancy.hip", "pnr_meshfinish.hip", "pnr_baked.hip", "pnr_baked_grad.hip", "pnr_baked_scene.hip", "pnr_baked_tv.hip"]
+HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_geom.h", "pnr_wave.h", "pnr_raysrc.h", "pnr_internal.h", "pnr_entry.h", "pnr_scatter_plan.h", "pnr_occgrid.h", "pnr_baked.h", "pnr_baked_grad.h", "pnr_mc_tables.inc", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
 ABI_VERSION = 12  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3
@@ -297,7 +297,12 @@ def build_library(force=False, verbose=False, jobs=None):
         os.replace(cmd[-1], obj)
         return obj, None
 
-    with ThreadPoolExecutor(max_workers=jobs or min(len(SOURCES), os.cpu_count() or 1)) as pool:
+    # at most MAX_JOBS compilers at once (16 where it is not set): a shared machine's CPU count is not this process's allowance
+    try:
+        limit = int(os.environ.get("MAX_JOBS") or 16)
+    except ValueError:
+        raise PixelNerfHipError(f"MAX_JOBS must be a number of parallel compilers, got {os.environ['MAX_JOBS']!r}") from None
+    with ThreadPoolExecutor(max_workers=jobs or max(1, min(len(SOURCES), os.cpu_count() or 1, limit))) as pool:
         results = list(pool.map(compile_unit, SOURCES))
     errors = [e for _, e in results if e]
     if errors:

@@ -43,4 +43,28 @@ __device__ __forceinline__ void wave_rscan_affine(float &m, float &b, int lane) 
     }
 }
 
+// wave_scan_mul and wave_rscan_affine on doubles: the same lanes in the same order.  Every product and sum is rounded on its own
+// (the fp32 twins above leave contraction to the compiler; the ray gradients of the baked march state their operations).  The
+// pragma stands inside each body, so including this header changes nothing for the text after the include.
+__device__ __forceinline__ double wave_scan_mul64(double v, int lane) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double t = __shfl_up(v, o, 64);
+        if (lane >= o) v *= t;
+    }
+    return v;
+}
+__device__ __forceinline__ void wave_rscan_affine64(double &m, double &b, int lane) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double mt = __shfl_down(m, o, 64), bt = __shfl_down(b, o, 64);
+        if (lane + o < 64) {
+            b += m * bt;
+            m *= mt;
+        }
+    }
+}
+
 }  // namespace pnr

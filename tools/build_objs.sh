@@ -3,7 +3,7 @@
 #   compiles every pixel-nerf_amd/csrc/pnr_*.hip to build/obj_NAME/*.o (one hipcc per TU, in parallel; a TU listed as
 #   `pnr_bwd=-DPNR_X_FOO` gets that flag) with -DPNR_VARIANT and links build/libpnr_NAME.so.  Objects of TUs without a flag are
 #   shared through build/obj_base/ (rebuilt when the source is newer).  Select with PIXELNERF_HIP_LIB=build/libpnr_NAME.so
-#   PIXELNERF_ALLOW_VARIANT=1.  (The product library is built by __graft_entry__.build() in one hipcc call.)
+#   PIXELNERF_ALLOW_VARIANT=1.  (The product library is built by __graft_entry__.build(): one hipcc per TU too, at most MAX_JOBS at once.)
 set -e
 REPO="$(cd "$(dirname "$0")/.." && pwd)"; NAME=$1; shift
 declare -A FLAGS; for kv in "$@"; do FLAGS[${kv%%=*}]="${kv#*=}"; done

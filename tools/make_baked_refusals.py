@@ -6,7 +6,7 @@
 All of it runs before any device work (no GPU needed): each call carries ONE defect, or one of a few pairs that pin the order of the
 checks, and stand-in pointers that are never touched.  tests/test_baked_refusals_host.py records the same calls with the library of
 the checkout and compares them with the fixture, which was written by this script at the commit before the entries were folded
-into one checked description (pnr_baked.hip, baked_render)."""
+into one checked description (pnr_baked.h: baked_check, which baked_render and every other family of baked entries calls)."""
 import ctypes
 import json
 import os
