@@ -1342,7 +1342,7 @@ int pnr_baked_scene_render_views(const float *poses /*(NV,4,4)*/, int NV, int W,
 
 /* Gradients of the scene march (added within ABI rev 12 as well; "Not here: gradients of any kind" above stays true of the two
  * render entries -- these two are the gradient with respect to the world RAYS and to each object's POSE; the stored values of a
- * scene are not differentiated).  What lets a caller find where an object stands: move its pose by gradient descent until the
+ * scene are differentiated by pnr_baked_scene_stored_backward_* below, not here).  What lets a caller find where an object stands: move its pose by gradient descent until the
  * scene matches its images, or refine a camera against a scene with an occluder in it.
  * pnr_baked_scene_backward_rays / _views are the backward of pnr_baked_scene_render_rays / _views for every kind those take:
  *   RGBA and degree 0, 1, 2, dense and sparse rows, fp32 and fp16 storage (the volumes are not differentiated, so a half volume is
@@ -1414,6 +1414,61 @@ int pnr_baked_scene_backward_views(const float *poses /*(NV,4,4)*/, int NV, int 
                                    const float *d_depth /*nullable*/, const float *d_alpha /*nullable*/,
                                    float *d_rays /*(NV H W,8)*/, float *d_local /*(NV H W,n_objects,6)*/,
                                    float *d_poses /*(n_objects,12), nullable*/, void *workspace, void *stream);
+
+/* Gradients of the scene march with respect to the STORED VALUES of its objects (added within ABI rev 12 as well: two entries,
+ * PnrBakedObject unchanged): what lets a caller fit the contents of a scene to images of the scene.  Where objects overlap or
+ * stand in front of one another the mixing makes every object's gradient depend on the others, so the single-volume backward of
+ * each object alone is not this gradient.
+ * pnr_baked_scene_stored_backward_rays / _views are the backward of pnr_baked_scene_render_rays / _views for fp32 storage: RGBA and
+ *   degree 0, 1, 2, dense and sparse rows.  objects, step, white_bkgd, terminate: the forward's.  d_rgb, d_depth, d_alpha: the
+ *   upstream gradients of the march's outputs, each NULL = zeros; a ray whose upstream gradients are all exactly zero is not walked.
+ * d_stored: a HOST array of n_objects DEVICE pointers.  d_stored[j] is fp32 and has the shape of object j's `stored` (dense
+ *   (nx,ny,nz,4) or (nx,ny,nz,B,4); sparse: the M kept rows).  The entry ADDS dL/d stored_j into it (fp32 atomicAdd on global
+ *   memory, exact zeros are skipped): the caller zeroes it before the first call, and successive calls accumulate.  Only elements
+ *   that a sample of the march read are touched.
+ *   d_stored[j] == NULL: object j is FROZEN.  It still attenuates and mixes -- the mixture is formed over all objects --, receives
+ *   nothing, and no atomic is issued for it: this is how one object is fitted in the presence of the others.
+ *   Two entries may hold the same pointer (a volume listed twice): the buffer receives the sum of both listings' gradients.
+ *   Every entry NULL: a no-op returning PNR_OK, after the checks.
+ * Samples: exactly the scene forward's, found by its device functions.  The walk is pnr_baked_scene_backward_*'s: a first walk in
+ *   the forward's direction finds the chunk the forward stopped after (by the forward's own fp32 factors) and the fp64
+ *   transmittance at the head of each chunk; then the chunks from last to first with the fp64 reverse affine scan; beyond 4096
+ *   samples the heads are rebuilt.  g_i, T_i, S_i, w_i, dL/da_i, dL/dsigma_i = dL/da_i step (1 - a_i) and dL/dc_i = w_i d_rgb are
+ *   that entry's, on the mixture sigma_i = sum_j sigma_ij, c_i = sum_j (sigma_ij / sigma_i) c_ij; what runs along the ray is fp64
+ *   (a_i = -expm1f(-step sigma_i) in fp32, the factor 1 - a_i + 1e-10 a double), rounded to fp32 once per sample; the rest is
+ *   fp32, each operation rounded on its own.
+ * Through the mixing, for every object j that contributes to sample i and is not frozen, where sigma_i > 0:
+ *     dL/dc_ij = (sigma_ij / sigma_i) dL/dc_i,      dL/dsigma_ij = dL/dsigma_i + ((c_ij - c_i) . dL/dc_i) / sigma_i
+ *   and where sigma_i is not > 0 (the forward's colour is the constant 0): dL/dc_ij = 0, dL/dsigma_ij = dL/dsigma_i -- the
+ *   convention of pnr_baked_scene_backward_*.  Seen from the stored values it shows: g_i of such a sample has no d_rgb . c_i, so
+ *   one object at [I | 0] gets pnr_baked_backward_*'s gradient EXCEPT from samples whose blended sigma is exactly 0 -- there that
+ *   entry keeps the blended colour and its dL/dsigma_i is larger by T_i step (d_rgb . c_i).  The forward does not tell the two
+ *   apart (w_i = 0).  With a skip grid, cells made of exactly empty points alone are not marched and the two agree.
+ * Through the object's blend in ITS frame, exactly as pnr_baked_backward_* do: corner (ix,iy,iz) of the sample's cell gets the
+ *   product over the axes of f or 1 - f; through a view-dependent corner, coefficient k gets that times Y_k (evaluated on d'_j)
+ *   times the derivative of the clamps under torch.clamp's convention.  The RGBA form has no clamp.
+ * With bits, a sample in a cell of object j whose bit is off contributes nothing and receives nothing, exactly as in
+ *   pnr_baked_backward_*.
+ * NOT bit-reproducible from run to run, like pnr_baked_backward_*: the order in which the atomics arrive varies.  No gradient
+ *   with respect to rays or poses from these entries (pnr_baked_scene_backward_* give those).  No workspace, no LDS; the library
+ *   allocates nothing.  Index arithmetic is 64-bit; only rows that the forward read are added into.
+ * PNR_E_INVALID, before any HIP call, through the checking function of the other scene entries and in its order: n_objects,
+ *   objects == NULL, "object j: reserved must be 0", "object j: mixed kinds ..."; then storage_half != 0 ("gradients exist for fp32
+ *   volumes only; fit the volume in fp32 and call half() afterwards"); the rays / poses checks, step, terminate; with R > 0 a null
+ *   d_stored array ("null argument (d_stored)"); "d_rgb, d_depth, d_alpha and every d_stored[j] must be 4-byte aligned"; then per
+ *   object, under "entry: object j: ", the words of pnr_baked_backward_* and "pose must be finite and rigid".  R = 0 (NV = 0):
+ *   no-op, PNR_OK, after these checks (d_stored may then be NULL). */
+int pnr_baked_scene_stored_backward_rays(const float *rays, long long R, const PnrBakedObject *objects /*host*/, int n_objects,
+                                         float step, int white_bkgd, float terminate, const float *d_rgb /*(R,3), nullable*/,
+                                         const float *d_depth /*(R), nullable*/, const float *d_alpha /*(R), nullable*/,
+                                         float *const *d_stored /*HOST array of n_objects device pointers; an entry may be NULL*/,
+                                         void *stream);
+int pnr_baked_scene_stored_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx,
+                                          float cy, float z_near, float z_far, const PnrBakedObject *objects /*host*/,
+                                          int n_objects, float step, int white_bkgd, float terminate,
+                                          const float *d_rgb /*(NV H W,3), nullable*/, const float *d_depth /*nullable*/,
+                                          const float *d_alpha /*nullable*/, float *const *d_stored /*HOST array, as above*/,
+                                          void *stream);
 
 /* Timing hook for bench.py: seconds spent in the fused network kernel launches issued on
  * `stream` since the last reset, measured with HIP events recorded around each launch on

@@ -246,6 +246,11 @@ PROTOTYPES = {
                                            _P, _P]),
     "pnr_baked_scene_backward_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F,
                                             _P, _P, _P, _P, _P, _P, _P, _P]),
+    # d_stored: a HOST array of n_objects device pointers (ctypes.c_void_p * n), an entry None = that object is frozen
+    "pnr_baked_scene_stored_backward_rays": (_I, [_P, ctypes.c_longlong, ctypes.POINTER(PnrBakedObject), _I, _F, _I, _F, _P, _P, _P,
+                                                  ctypes.POINTER(ctypes.c_void_p), _P]),
+    "pnr_baked_scene_stored_backward_views": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, ctypes.POINTER(PnrBakedObject), _I, _F, _I,
+                                                   _F, _P, _P, _P, ctypes.POINTER(ctypes.c_void_p), _P]),
     "pnr_profile_enable": (_I, [_I]),
     "pnr_profile_read": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
 }

@@ -719,6 +719,87 @@ def baked_scene_march_autograd(source, objects, obj_poses, step, white_bkgd=Fals
     return _BakedSceneMarchFunction.apply(source[0], obj_poses, source[1:], volumes, float(step), bool(white_bkgd), float(terminate))
 
 
+class _BakedSceneFitFunction(torch.autograd.Function):
+    """The scene march of several posed baked volumes, differentiable with respect to the STORED VALUES of its objects (include/
+    pixelnerf_hip.h, "Gradients of the scene march with respect to the STORED VALUES") and, as _BakedSceneMarchFunction, to its world
+    rays or camera poses and to the object poses.  forward IS the inference entry; backward one pnr_baked_scene_stored_backward_*
+    call when any stored tensor needs its gradient (fp32 atomics: not bit-reproducible) and one pnr_baked_scene_backward_* call when
+    the lead or the poses need theirs.  The stored tensors are tensor arguments, one per DISTINCT tensor: `meta` says which of them
+    each object marches (slot) -- a volume listed twice is one argument and gets the sum of both listings."""
+
+    @staticmethod
+    def forward(ctx, lead, obj_poses, rest, meta, step, white_bkgd, terminate, *stored):
+        ctx.set_materialize_grads(False)
+        host = obj_poses.detach().to("cpu", torch.float32)  # the poses are kernel arguments by value: one host read
+        objects = [(stored[slot], degree, reso, c1, c2, host[j], bits, index)
+                   for j, (slot, degree, reso, c1, c2, bits, index) in enumerate(meta)]
+        entry = ops.baked_scene_render if not rest else ops.baked_scene_render_views
+        out = entry(lead, *rest, objects, step, white_bkgd=white_bkgd, terminate=terminate)
+        ctx.save_for_backward(lead, obj_poses, *stored)
+        ctx.march = (rest, meta, host, step, white_bkgd, terminate)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_alpha):
+        lead, obj_poses, *stored = ctx.saved_tensors
+        rest, meta, host, step, white_bkgd, terminate = ctx.march
+        need_stored = ctx.needs_input_grad[7:]
+        none = (None,) * (7 + len(stored))
+        if (d_rgb is None and d_depth is None and d_alpha is None) or not any(ctx.needs_input_grad):
+            return none
+        fp32 = lambda g: None if g is None else g.contiguous().float()
+        kw = dict(d_rgb=fp32(d_rgb), d_depth=fp32(d_depth), d_alpha=fp32(d_alpha), white_bkgd=white_bkgd, terminate=terminate)
+        stored = [s.detach() for s in stored]  # (one tensor object per slot: ops shares a buffer between its listings)
+        objects = [(stored[slot], degree, reso, c1, c2, host[j], bits, index)
+                   for j, (slot, degree, reso, c1, c2, bits, index) in enumerate(meta)]
+        d_stored = [None] * len(stored)
+        if any(need_stored):
+            entry = ops.baked_scene_stored_backward if not rest else ops.baked_scene_stored_backward_views
+            bufs = entry(lead.detach(), *rest, objects, step, want=[need_stored[m[0]] for m in meta], **kw)
+            for m, buf in zip(meta, bufs):
+                d_stored[m[0]] = buf
+        d_lead = d_obj = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            entry = ops.baked_scene_backward if not rest else ops.baked_scene_backward_views
+            d_rays, _, d_poses = entry(lead.detach(), *rest, objects, step, want_poses=ctx.needs_input_grad[1], **kw)
+            if ctx.needs_input_grad[0]:
+                d_lead = d_rays if not rest else ops.gen_rays_backward(d_rays, rest[0], rest[1], rest[2], rest[3])
+            if ctx.needs_input_grad[1]:
+                d_obj = d_poses.reshape(-1, 3, 4).to(device=obj_poses.device, dtype=obj_poses.dtype)
+        return (d_lead, d_obj) + (None,) * 5 + tuple(d_stored)
+
+
+def baked_scene_fit_autograd(source, stored, volumes_meta, obj_poses, step, white_bkgd=False, terminate=0.0):
+    """-> (rgb (R,3), depth (R,), alpha (R,)) of the scene march -- the bytes of ops.baked_scene_render / _views --, differentiable
+    with respect to the STORED VALUES of its objects: stored, a list of one fp32 tensor per object ((nx,ny,nz,4) at degree None,
+    (nx,ny,nz,B,4) at degree 0, 1, 2, or with an index the kept rows); a tensor that requires grad gets its gradient
+    (pnr_baked_scene_stored_backward_*: fp32 atomics), one that does not is frozen -- it mixes and attenuates and receives nothing.
+    The SAME tensor at two positions is one volume listed twice: it gets the sum of both listings' gradients.
+    volumes_meta: per object (degree, reso, c1, c2, bits, index) -- baked_scene_march_autograd's tuples without the tensor.
+    source and obj_poses: as baked_scene_march_autograd takes them; source[0] and obj_poses may require grad and then get that
+    function's gradient (pnr_baked_scene_backward_*)."""
+    source = tuple(source)
+    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
+        raise ValueError("baked_scene_fit_autograd: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
+    stored, volumes_meta = list(stored), [tuple(m) for m in volumes_meta]
+    if not stored or len(stored) != len(volumes_meta) or any(len(m) != 6 for m in volumes_meta):
+        raise ValueError("baked_scene_fit_autograd: stored and volumes_meta must list the same objects, each meta (degree, reso, c1, c2, "
+                         "bits, index)")
+    if not all(isinstance(s, torch.Tensor) and s.dtype == torch.float32 for s in stored):
+        raise TypeError("baked_scene_fit_autograd: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
+    if not isinstance(obj_poses, torch.Tensor) or obj_poses.dim() != 3 or tuple(obj_poses.shape[1:]) != (3, 4) \
+            or obj_poses.shape[0] != len(stored) or not obj_poses.is_floating_point():
+        raise ValueError(f"baked_scene_fit_autograd: obj_poses must be a float tensor ({len(stored)},3,4) object-to-world")
+    unique, slots = [], []
+    for s in stored:
+        slot = next((k for k, u in enumerate(unique) if u is s), len(unique))
+        if slot == len(unique):
+            unique.append(s)
+        slots.append(slot)
+    meta = tuple((slot,) + m for slot, m in zip(slots, volumes_meta))
+    return _BakedSceneFitFunction.apply(source[0], obj_poses, source[1:], meta, float(step), bool(white_bkgd), float(terminate), *unique)
+
+
 class _BakedTvFunction(torch.autograd.Function):
     """The total-variation prior of a baked volume's stored values (include/pixelnerf_hip.h, "Total-variation prior").  forward asks
     pnr_baked_tv for the value alone, backward for the gradient alone with scale = grad_output left on the device: no host read on

@@ -413,6 +413,7 @@ struct BakedGrads {
     const float *d_rgb, *d_depth, *d_alpha;
     float *out;
     const char *out_name = "d_stored";
+    bool out_nullable = false;  // a scene's stored backward: NULL = this object is frozen
 };
 
 // ranks are int32: a row beyond 2^31 - 2 cannot be named.  M < 2 (last < 0): no sample finds its rows, nothing is read
@@ -435,7 +436,7 @@ static inline int baked_check(const char *entry, const BakedRays &rays, const Ba
     if (!(a.terminate >= 0.f && a.terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");  // (refuses a NaN)
     const long long R = rays.R;
     if (R == 0) return PNR_OK;
-    if (grads ? !grads->out : !a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
+    if (grads ? !grads->out && !grads->out_nullable : !a.rgb || !a.depth || !a.alpha) return occ_fail(entry, "null argument");
     if (v.sparse ? v.M > 0 && (!v.stored || !v.index || !a.bits) : !v.stored) return occ_fail(entry, "null argument");
     if (occ_misaligned16(v.stored)) {
         char why[40];

@@ -10,7 +10,10 @@
 // pnr_baked_grad.h, and two small kernels that reduce the poses' gradient over the rays in a fixed order; no atomics, no LDS.
 // The walk itself (upstream gradient, first walk, scan step, row write) is baked_march_ray_bwd_kernel's, written out here as
 // there: shared, it cost this kernel 3 to 10 % (profiles/baked_notes.md, "A file per concern").
-// The four entries share one checking function, baked_scene_check.
+// Stored backward (pnr_baked_scene_stored_backward_rays / _views: dL/d every object's stored values, what fitting a scene needs):
+// baked_scene_stored_bwd_kernel, the same walk on the mixture, then baked_march_bwd_kernel's corner weights and Corner::scatter
+// per contributing object; fp32 storage only, fp32 atomics into the caller's buffers, not bit-reproducible from run to run.
+// The six entries share one checking function, baked_scene_check.
 #include "pnr_baked_grad.h"
 
 namespace pnr {
@@ -527,6 +530,129 @@ baked_scene_pose_final_kernel(const double *__restrict__ partials, int blocks, i
         if (threadIdx.x == 0) d_poses[j * 12 + k] = (float)v;
     }
 }
+
+// ---- backward of the SCENE march with respect to every object's STORED VALUES (pnr_baked_scene_stored_backward_*; fp32 storage
+// only): what fitting the contents of a scene to images of the scene needs.  The walk is baked_scene_ray_bwd_kernel's on the
+// mixture -- the first walk with the fp64 heads and the forward's own fp32 factors for the stop chunk, the reverse affine scan in
+// fp64, the rebuild beyond 4096 samples -- and gives dL/dc_i = w_i d_rgb and dL/dsigma_i of the mixture.  Through the mixing to every
+// contributing object j (that kernel's convention: where sigma is not > 0 the colour is the constant 0), then through the object's
+// blend in ITS frame as baked_march_bwd_kernel does: corner (ix,iy,iz) gets the product of f or 1 - f per axis, and
+// Corner::scatter adds it into d_stored[j] with fp32 atomics.  A NULL d_stored[j] is a frozen object: it mixes and attenuates (the
+// mixture above is formed over ALL objects) and the loop below passes it over, on a scalar test.  No workspace, no LDS.
+
+// the buffers dL/d stored_j is added into, by value next to the scene; NULL: object j is frozen
+struct BakedSceneStoredGrads {
+    float *p[PNR_BAKED_SCENE_MAX_OBJECTS];
+};
+
+template <class Corner, class Rows>
+__global__ void __launch_bounds__(BAKED_WAVES * 64)
+baked_scene_stored_bwd_kernel(const RaySrc rs, long long R, const BakedSceneDesc sc, const BakedSceneStoredGrads out, float step, float eps,
+                              int white_bkgd, const float *__restrict__ d_rgb, const float *__restrict__ d_depth,
+                              const float *__restrict__ d_alpha) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * BAKED_WAVES + (threadIdx.x >> 6);
+    if (r >= R) return;
+    float3 drgb = make_float3(0.f, 0.f, 0.f);
+    if (d_rgb) drgb = make_float3(d_rgb[r * 3], d_rgb[r * 3 + 1], d_rgb[r * 3 + 2]);
+    const float ddepth = d_depth ? d_depth[r] : 0.f, dalpha = d_alpha ? d_alpha[r] : 0.f;
+    if (drgb.x == 0.f && drgb.y == 0.f && drgb.z == 0.f && ddepth == 0.f && dalpha == 0.f) return;  // nothing to send back
+    const float gwhite = white_bkgd ? (drgb.x + drgb.y + drgb.z) : 0.f;  // rgb += 1 - sum w
+    const Ray8 ray = load_ray(rs, r);
+    const int n = baked_sample_count(ray, step);  // the WORLD ray decides the samples
+    int nc = (n + 63) >> 6;
+
+    // the forward's walk: T at the head of chunk c < 64 into lane c, and -- by the forward's own factors -- the chunk it stopped after
+    double heads = 1.0, carry = 1.0;
+    float stop = 1.f;
+    for (int c = 0; c < nc; ++c) {
+        if (lane == c) heads = carry;
+        float4 first;
+        float sigma;
+        int cnt;
+        const bool any = baked_scene_sigma<Corner, Rows>(sc, ray, step, c * 64 + lane, n, first, sigma, cnt);
+        if (__ballot(any) == 0ull) continue;
+        carry = carry * __shfl(wave_scan_mul64(cnt > 0 ? baked_alpha_exact(step, sigma).tf : 1.0, lane), 63, 64);
+        if (eps > 0.f) {  // (wave-uniform)
+            stop = stop * __shfl(wave_scan_mul(baked_alpha(step, sigma).tfac, lane), 63, 64);
+            if (stop <= eps) nc = c + 1;  // the forward's break, in its words
+        }
+    }
+
+    double S_in = 0.0;  // S of the chunk's last sample
+    for (int c = nc - 1; c >= 0; --c) {
+        const int i = c * 64 + lane;
+        const float t = ray.near + ((float)i + 0.5f) * step;  // baked_sample's depth
+        float4 first;
+        float sigma;
+        int cnt;
+        const bool any = baked_scene_sigma<Corner, Rows>(sc, ray, step, i, n, first, sigma, cnt);
+        if (__ballot(any) == 0ull) continue;  // 64 identity maps: S stays, nothing to scatter
+        const float3 col = baked_scene_colour<Corner, Rows>(sc, ray, step, i, n, first, sigma, cnt);
+        carry = __shfl(heads, c < 64 ? c : 63, 64);
+        for (int cc = 63; cc < c; ++cc) carry = carry * baked_scene_chunk_product_exact<Corner, Rows>(sc, ray, step, cc, n, lane);
+        const bool mixed = cnt > 0;  // the single kernel's `found`
+        const BakedAlphaExact al = baked_alpha_exact(step, sigma);
+        double m = mixed ? al.tf : 1.0;
+        const double incl = wave_scan_mul64(m, lane);
+        double excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.0;
+        const double T = carry * excl;
+        const double g = mixed ? (double)(drgb.x * col.x + drgb.y * col.y + drgb.z * col.z + ddepth * t + dalpha - gwhite) : 0.0;
+        double b = mixed ? g * (double)al.a : 0.0;
+        wave_rscan_affine64(m, b, lane);
+        const double mn = __shfl_down(m, 1, 64), bn = __shfl_down(b, 1, 64);
+        const double S = lane == 63 ? S_in : bn + mn * S_in;
+        S_in = __shfl(b + m * S_in, 0, 64);  // S of sample 64 c - 1
+        // dL/dc_i and dL/dsigma_i of the mixture; zeros in a lane nothing contributes to
+        const float w = mixed ? (float)((double)al.a * T) : 0.f;
+        const float da = mixed ? (float)(T * (g - S)) : 0.f;
+        const float3 dc = make_float3(w * drgb.x, w * drgb.y, w * drgb.z);
+        const float dsig = da * step * al.ex;
+#pragma unroll 1
+        for (int j = 0; j < sc.n; ++j) {
+            float *__restrict__ dst = out.p[j];
+            if (!dst) continue;  // a frozen object (j is wave-uniform: a scalar test)
+            const BakedSceneObject &ob = sc.obj[j];
+            // baked_scene_value's steps, keeping the cell for the scatter
+            const Ray8 oray = baked_scene_ray(ray, ob);
+            BakedParams q;
+            q.bits = ob.bits;
+            q.g = ob.g;
+            q.step = step;
+            q.eps = 0.f;
+            q.white_bkgd = 0;
+            const BakedSample s = baked_sample(oray, q, i, n);
+            if (__ballot(s.active) == 0ull) continue;  // nothing of this object in the chunk: no loads
+            Corner corner;
+            corner.data = static_cast<const typename Corner::stored_t *>(ob.stored);
+            corner.set_ray(oray);
+            const Rows rows = baked_scene_rows<Rows>(ob);
+            BakedCell<Rows> cell;
+            bool found;
+            const float4 cs = baked_value(q, corner, rows, s, cell, found);
+            if (found) {  // (no wave operation below; found implies mixed)
+                // through the mixing; where sigma is not > 0 the forward's colour is the constant 0
+                float wj = 0.f, dsj = dsig;
+                if (sigma > 0.f) {
+                    wj = cs.w / sigma;
+                    dsj = dsig + ((cs.x - col.x) * dc.x + (cs.y - col.y) * dc.y + (cs.z - col.z) * dc.z) / sigma;
+                }
+                const float4 dcs = make_float4(wj * dc.x, wj * dc.y, wj * dc.z, dsj);
+#pragma unroll 1
+                for (int pj = 0; pj < 4; ++pj) {  // pair pj = 2 ix + iy
+                    const long long row = cell.row(rows, pj);
+                    const float wxy = (pj >> 1 ? s.f[0] : 1.f - s.f[0]) * (pj & 1 ? s.f[1] : 1.f - s.f[1]);
+#pragma unroll
+                    for (int iz = 0; iz < 2; ++iz) {
+                        const float wt = wxy * (iz ? s.f[2] : 1.f - s.f[2]);
+                        if (wt != 0.f) corner.scatter(dst, row + iz, make_float4(wt * dcs.x, wt * dcs.y, wt * dcs.z, wt * dcs.w));
+                    }
+                }
+            }
+        }
+    }
+}
 #pragma clang fp contract(fast)
 
 // ---- host only from here
@@ -555,9 +681,11 @@ struct BakedSceneOut {
     const BakedGrads *grads;
     float *d_local, *d_poses;
     void *workspace;
+    float *const *d_stored = nullptr;  // the stored backward alone (stored_grads): the HOST array of n_objects device pointers
+    bool stored_grads = false;
 };
 
-// Every check of the four scene entries, in one order: what concerns the call as a whole, then every object through baked_check
+// Every check of the six scene entries, in one order: what concerns the call as a whole, then every object through baked_check
 // under "entry: object j".  -> PNR_OK with the scene as the kernels take it, the kind in v0 and `blocks` workgroups (0: no rays)
 static int baked_scene_check(const char *entry, const BakedRays &rays, const PnrBakedObject *objects, int n_objects, float step,
                              int white_bkgd, float terminate, const BakedSceneOut &o, void *stream, BakedSceneDesc &sc, BakedVolumeDesc &v0,
@@ -577,11 +705,19 @@ static int baked_scene_check(const char *entry, const BakedRays &rays, const Pnr
             return occ_fail(entry, why);
         }
     }
+    if (o.stored_grads && objects[0].storage_half != 0)
+        return occ_fail(entry, "gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards");
     if (rays.defect) return occ_fail(entry, rays.defect);
     if (!(step > 0.f) || !std::isfinite(step)) return occ_fail(entry, "step must be finite and > 0");
     if (!(terminate >= 0.f && terminate < 1.f)) return occ_fail(entry, "terminate must lie in [0, 1)");
-    if (rays.R > 0 && (o.grads ? !o.grads->out || !o.d_local : !o.rgb || !o.depth || !o.alpha)) return occ_fail(entry, "null argument");
-    if (o.grads) {  // (a misaligned d_poses is wrong whatever R: it is written at R = 0 too)
+    if (o.stored_grads) {
+        if (rays.R > 0 && !o.d_stored) return occ_fail(entry, "null argument (d_stored)");
+        bool bad = baked_misaligned4(o.grads->d_rgb) || baked_misaligned4(o.grads->d_depth) || baked_misaligned4(o.grads->d_alpha);
+        for (int j = 0; o.d_stored && j < n_objects; ++j) bad = bad || baked_misaligned4(o.d_stored[j]);
+        if (bad) return occ_fail(entry, "d_rgb, d_depth, d_alpha and every d_stored[j] must be 4-byte aligned");
+    } else if (rays.R > 0 && (o.grads ? !o.grads->out || !o.d_local : !o.rgb || !o.depth || !o.alpha)) {
+        return occ_fail(entry, "null argument");
+    } else if (o.grads) {  // (a misaligned d_poses is wrong whatever R: it is written at R = 0 too)
         if (baked_misaligned4(o.grads->d_rgb) || baked_misaligned4(o.grads->d_depth) || baked_misaligned4(o.grads->d_alpha) ||
             baked_misaligned4(o.grads->out) || baked_misaligned4(o.d_local) || baked_misaligned4(o.d_poses))
             return occ_fail(entry, "d_rgb, d_depth, d_alpha, d_rays, d_local and d_poses must be 4-byte aligned");
@@ -598,8 +734,14 @@ static int baked_scene_check(const char *entry, const BakedRays &rays, const Pnr
         std::snprintf(where, sizeof(where), "%s: object %d", entry, j);
         const BakedVolumeDesc v = baked_stored(ob.stored, ob.storage_half, ob.M, ob.degree, ob.index);
         BakedParams q;
+        BakedGrads og;
+        if (o.grads) og = *o.grads;
+        if (o.stored_grads) {  // this object's own buffer; NULL: frozen
+            og.out = o.d_stored ? o.d_stored[j] : nullptr;
+            og.out_nullable = true;
+        }
         if (const int rc = baked_check(where, rays, v, {ob.bits, ob.nx, ob.ny, ob.nz, ob.c1, ob.c2, step, white_bkgd, terminate, o.rgb,
-                                                        o.depth, o.alpha, stream}, o.grads, q, blocks))
+                                                        o.depth, o.alpha, stream}, o.grads ? &og : nullptr, q, blocks))
             return rc;
         if (!baked_pose_rigid(ob.pose)) return occ_fail(where, "pose must be finite and rigid (max |R^T R - I| <= 1e-4, det R > 0)");
         BakedSceneObject &so = sc.obj[j];
@@ -669,6 +811,35 @@ static int baked_scene_backward(const char *entry, const BakedRays &rays, const 
     return pnr_check_launch(entry);
 }
 
+// the scene's stored-value backward entries: the same checks, then one launch that adds into every buffer that is not NULL
+static int baked_scene_stored_backward(const char *entry, const BakedRays &rays, const PnrBakedObject *objects, int n_objects, float step,
+                                       int white_bkgd, float terminate, const float *d_rgb, const float *d_depth, const float *d_alpha,
+                                       float *const *d_stored, void *stream) {
+    const BakedGrads grads = {d_rgb, d_depth, d_alpha, nullptr};
+    BakedSceneOut o = {nullptr, nullptr, nullptr, &grads, nullptr, nullptr, nullptr};
+    o.d_stored = d_stored;
+    o.stored_grads = true;
+    BakedSceneDesc sc;
+    BakedVolumeDesc v0;
+    long long blocks;
+    if (const int rc = baked_scene_check(entry, rays, objects, n_objects, step, white_bkgd, terminate, o, stream, sc, v0, blocks)) return rc;
+    if (blocks == 0) return PNR_OK;
+    BakedSceneStoredGrads out = {};
+    bool any = false;
+    for (int j = 0; j < n_objects; ++j) {
+        out.p[j] = d_stored[j];
+        any = any || d_stored[j];
+    }
+    if (!any) return PNR_OK;  // every object frozen: nothing to add
+    baked_dispatch(v0, [&](auto corner, auto rows) {
+        using Corner = typename decltype(corner)::type;
+        if constexpr (std::is_same<typename Corner::stored_t, float4>::value)  // (no fp16 instantiation: the check refused it)
+            hipLaunchKernelGGL((baked_scene_stored_bwd_kernel<Corner, decltype(rows)>), dim3((unsigned)blocks), dim3(BAKED_WAVES * 64), 0,
+                               (hipStream_t)stream, rays.src, rays.R, sc, out, step, terminate, white_bkgd, d_rgb, d_depth, d_alpha);
+    });
+    return pnr_check_launch(entry);
+}
+
 }  // namespace pnr
 
 // ---- scenes of several posed volumes of one kind (objects: a HOST array)
@@ -706,4 +877,22 @@ extern "C" int pnr_baked_scene_backward_views(const float *poses, int NV, int W,
     return pnr::baked_scene_backward("pnr_baked_scene_backward_views", pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far),
                                      objects, n_objects, step, white_bkgd, terminate, d_rgb, d_depth, d_alpha, d_rays, d_local, d_poses,
                                      workspace, stream);
+}
+
+// ---- gradients of the scene march with respect to every object's stored values (fp32 storage; d_stored: a HOST array)
+
+extern "C" int pnr_baked_scene_stored_backward_rays(const float *rays, long long R, const PnrBakedObject *objects, int n_objects, float step,
+                                                    int white_bkgd, float terminate, const float *d_rgb, const float *d_depth,
+                                                    const float *d_alpha, float *const *d_stored, void *stream) {
+    return pnr::baked_scene_stored_backward("pnr_baked_scene_stored_backward_rays", pnr::baked_explicit_rays(rays, R), objects, n_objects,
+                                            step, white_bkgd, terminate, d_rgb, d_depth, d_alpha, d_stored, stream);
+}
+
+extern "C" int pnr_baked_scene_stored_backward_views(const float *poses, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                                                     float z_near, float z_far, const PnrBakedObject *objects, int n_objects, float step,
+                                                     int white_bkgd, float terminate, const float *d_rgb, const float *d_depth,
+                                                     const float *d_alpha, float *const *d_stored, void *stream) {
+    return pnr::baked_scene_stored_backward("pnr_baked_scene_stored_backward_views",
+                                            pnr::baked_camera_rays(poses, NV, W, H, fx, fy, cx, cy, z_near, z_far), objects, n_objects, step,
+                                            white_bkgd, terminate, d_rgb, d_depth, d_alpha, d_stored, stream);
 }

@@ -1739,6 +1739,108 @@ def baked_scene_backward_views(poses, width, height, focal, c, z_near, z_far, ob
     return d_rays.reshape(-1, H, W, 8), d_local, d_poses
 
 
+# ---- gradients of the scene march with respect to every object's stored values (include/pixelnerf_hip.h, "Gradients of the scene
+# march with respect to the STORED VALUES")
+
+def _baked_scene_stored_backward(what, entry, objects, step, white_bkgd, terminate, d_rgb, d_depth, d_alpha, want, out, rays=None,
+                                 camera=None):
+    """baked_scene_render's checks and _baked_backward's before any device work, then pnr_baked_scene_stored_backward_rays / _views
+    INTO the buffers -> a list with one buffer per object, None where want is False; objects whose `stored` is the same tensor
+    share one buffer"""
+    lib = _lib.load()
+    if isinstance(objects, (list, tuple)):
+        for j, ob in enumerate(objects):
+            if isinstance(ob, (list, tuple)) and len(ob) and isinstance(ob[0], torch.Tensor) and ob[0].dtype == torch.float16:
+                raise TypeError(f"{what}: object {j}: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() "
+                                "afterwards")
+    source = rays if camera is None else camera[0]
+    if isinstance(source, torch.Tensor) and source.requires_grad:
+        raise ValueError(f"{what}: no gradient is given with respect to {'rays' if camera is None else 'poses'}; detach them "
+                         "(baked_scene_backward gives that gradient)")
+    arr, dev, keep = _baked_scene(what, objects, step, terminate)
+    N = len(arr)
+    if camera is None:
+        source = _f32(rays, "rays", (None, 8))
+        R = source.shape[0]
+        args = [_p(source), R]
+    else:
+        poses, W, H, focal, c, z_near, z_far = camera
+        source = _f32(poses, "poses", (None, 4, 4))
+        R = source.shape[0] * H * W
+        fx, fy = (float(focal), float(focal)) if not hasattr(focal, "__len__") else (float(focal[0]), float(focal[-1]))
+        cx, cy = (W * 0.5, H * 0.5) if c is None else (float(c[0]), float(c[1]))
+        args = [_p(source), source.shape[0], W, H, fx, fy, cx, cy, float(z_near), float(z_far)]
+    if source.device != dev:
+        raise ValueError(f"{what}: the volumes live on {dev}, the {'rays' if camera is None else 'poses'} on {source.device}")
+    grads = []
+    for g, name, shape in ((d_rgb, "d_rgb", (R, 3)), (d_depth, "d_depth", (R,)), (d_alpha, "d_alpha", (R,))):
+        g = None if g is None else _f32(g.detach() if isinstance(g, torch.Tensor) else g, name, shape)
+        if g is not None and g.device != dev:
+            raise ValueError(f"{what}: {name} lives on {g.device}, the volumes on {dev}")
+        grads.append(g)
+    want = [True] * N if want is None else [bool(w) for w in want]
+    if len(want) != N:
+        raise ValueError(f"{what}: want must hold one bool per object ({N}), got {len(want)}")
+    if out is not None and (not isinstance(out, (list, tuple)) or len(out) != N):
+        raise ValueError(f"{what}: out must be a list of one buffer (or None) per object ({N})")
+    stored = [keep[3 * j] for j in range(N)]  # (_baked_scene's contiguous tensors)
+    bufs, shared = [None] * N, {}
+    for j in range(N):
+        if not want[j]:
+            continue
+        key = id(objects[j][0])  # the SAME tensor listed twice: one buffer, the sum of both listings
+        given = None if out is None else out[j]
+        if key in shared:
+            if given is not None and given is not shared[key]:
+                raise ValueError(f"{what}: object {j} shares its stored tensor with an earlier object; out[{j}] must be that object's buffer")
+            bufs[j] = shared[key]
+            continue
+        if given is None:
+            given = torch.zeros(stored[j].shape, dtype=torch.float32, device=dev)
+        elif not isinstance(given, torch.Tensor) or given.dtype != torch.float32 or given.shape != stored[j].shape or given.device != dev \
+                or not given.is_contiguous() or given.requires_grad:
+            raise ValueError(f"{what}: out[{j}] must be a contiguous float32 tensor of shape {tuple(stored[j].shape)} on {dev} that does "
+                             "not require grad (it is added into)")
+        bufs[j] = shared[key] = given
+    ptrs = (ctypes.c_void_p * N)(*[None if b is None or not b.numel() else b.data_ptr() for b in bufs])
+    args += (arr, N, float(step), int(bool(white_bkgd)), float(terminate), _p(grads[0]), _p(grads[1]), _p(grads[2]), ptrs)
+    if R and any(p for p in ptrs):
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    del keep
+    return bufs
+
+
+def baked_scene_stored_backward(rays, objects, step, d_rgb=None, d_depth=None, d_alpha=None, white_bkgd=False, terminate=0.0, want=None,
+                                out=None):
+    """The gradient of baked_scene_render with respect to every object's STORED VALUES (pnr_baked_scene_stored_backward_rays; the
+    contract is in include/pixelnerf_hip.h, "Gradients of the scene march with respect to the STORED VALUES"): rays (R,8) and
+    objects as baked_scene_render takes them, fp32 only; d_rgb (R,3), d_depth (R,), d_alpha (R,) the upstream gradients of its
+    outputs, None = zeros.
+    :param want one bool per object (None: all).  False FREEZES the object: it still mixes and attenuates, gets no gradient, and its
+    position in the result is None -- one object fitted in the presence of the others
+    :param out a list of buffers the gradients are ADDED into (the caller zeroes them before the first batch), None entries or
+    None: fresh zeroed ones
+    -> a list of dL/d stored_j, fp32, each the shape of its object's stored.  Objects whose `stored` is the SAME tensor share one
+    buffer, returned at each of their positions, holding the sum of their listings' gradients.  Where objects overlap, or one
+    stands in front of another, this is not what baked_render_backward gives for each object alone.  The samples are exactly the
+    forward's; with bits the cells whose bit is off receive nothing.  Not bit-reproducible from run to run (fp32 atomics).  No
+    gradient with respect to rays or poses: baked_scene_backward gives those."""
+    return _baked_scene_stored_backward("baked_scene_stored_backward", "pnr_baked_scene_stored_backward_rays", objects, step, white_bkgd,
+                                        terminate, d_rgb, d_depth, d_alpha, want, out, rays=rays)
+
+
+def baked_scene_stored_backward_views(poses, width, height, focal, c, z_near, z_far, objects, step, d_rgb=None, d_depth=None,
+                                      d_alpha=None, white_bkgd=False, terminate=0.0, want=None, out=None):
+    """baked_scene_stored_backward over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c)
+    (pnr_baked_scene_stored_backward_views): the rays are regenerated in the kernel, d_rgb (NV*H*W,3), d_depth and d_alpha
+    (NV*H*W,) ordered (view, row, column) as baked_scene_render_views returns its outputs.  -> the list of dL/d stored_j."""
+    W, H = _image_size("baked_scene_stored_backward_views", width, height)
+    return _baked_scene_stored_backward("baked_scene_stored_backward_views", "pnr_baked_scene_stored_backward_views", objects, step,
+                                        white_bkgd, terminate, d_rgb, d_depth, d_alpha, want, out,
+                                        camera=(poses, W, H, focal, c, z_near, z_far))
+
+
 # ---- gradients of the baked march with respect to the stored values (include/pixelnerf_hip.h, "Gradients of the baked march")
 
 def _baked_backward(what, entry, stored, degree, reso, c1, c2, step, bits, index, white_bkgd, terminate, d_rgb, d_depth, d_alpha, out,

@@ -672,8 +672,9 @@ class BakedScene:
     (N,4,4) or (N,3,4) object-to-world, rigid (what `register` recovers, inverted, is such a pose); kept as given, on the host, fp32.
     `render` and `render_views` are inference: they run under torch.no_grad().  `render_diff` and `render_views_diff` give the same
     bytes with autograd to the world rays or the cameras and to the object poses (include/pixelnerf_hip.h, "Gradients of the scene
-    march"); `place` descends on the poses of chosen objects.  The stored values of a scene get no gradient.  Nothing is copied: the
-    scene refers to its volumes."""
+    march"); `place` descends on the poses of chosen objects.  `trainable()` gives the stored values of chosen objects their
+    gradient through the same march (include/pixelnerf_hip.h, "Gradients of the scene march with respect to the STORED VALUES"), and
+    `fit_scene` descends on them.  Nothing is copied: the scene refers to its volumes."""
 
     def __init__(self, volumes, poses):
         from .. import _lib
@@ -752,6 +753,12 @@ class BakedScene:
             rgb, depth, alpha = ops.baked_scene_render_views(poses_c2w.float(), W, H, focal, c, z_near, z_far, self._objects(skip), step,
                                                              white_bkgd=white_bkgd, terminate=terminate)
             return _views_result(rgb, depth, alpha, poses_c2w.shape[0], W, H, z_near, z_far, gt_rgb, want_u8)
+
+    def trainable(self, objects=None):
+        """-> TrainableScene: an nn.Module whose nn.ParameterList holds copies of the fp32 stored tensors of the chosen objects
+        (indices; None: all), the others referenced and frozen; `forward(rays, ...)` and `forward_views(...)` render with gradients
+        attached, `.scene()` gives the fitted scene back (`fit_scene` is the loop around it).  An fp16 scene is refused."""
+        return TrainableScene(self, objects)
 
     def _obj_poses(self, what, poses):
         """the object poses of a differentiable call: self.poses, or the tensor (N,3,4) / (N,4,4) that replaces them -> (N,3,4)"""
@@ -922,6 +929,156 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
                 module.stored[..., 3].clamp_(min=0.0)
         losses.append(loss.detach())
     return module.volume(), (torch.stack(losses).tolist() if losses else [])
+
+
+# ---------------------------------------------------------------- fitting a scene: stored-value gradients through the mixture
+
+class TrainableScene(torch.nn.Module):
+    """`scene.trainable(objects)`: the fp32 stored tensors of the chosen objects of a BakedScene (None: all) as this module's
+    nn.ParameterList `stored` (copies: the scene and its volumes never change), marched TOGETHER by the inference entries with
+    gradients attached (autograd.baked_scene_fit_autograd: forward = the bytes of `scene.render`, backward =
+    pnr_baked_scene_stored_backward_*).  Where objects overlap or stand in front of one another every object's gradient depends on
+    the others: fitting each volume alone against images of the scene gives another, wrong, answer.  The objects that are not
+    chosen are referenced and FROZEN: they mix and attenuate and receive nothing.  A volume listed twice in the scene is ONE
+    parameter and gets the sum of both listings' gradients (chosen when either listing is).  The gradients of the stored values are
+    not bit-reproducible from run to run (fp32 atomics).  An fp16 scene is refused: fit in fp32 and call `half()` afterwards.
+    `poses` / `obj_poses` that require grad get the gradient of `render_diff` (pnr_baked_scene_backward_*) in the same backward.
+    `skip=True` marches every dense volume against the skip grid it had when `trainable()` was called: the cells it calls empty are
+    frozen, as in TrainableBaked.  Sparse volumes always march against their grid.
+    Where the mixture's density is exactly 0 its colour is the constant 0 (the header's convention): the density gradient of such a
+    sample has no colour term, which TrainableBaked's has -- one object at the identity pose gets TrainableBaked's gradient except
+    from those samples."""
+
+    def __init__(self, scene, objects=None):
+        super().__init__()
+        if not isinstance(scene, BakedScene):
+            raise TypeError(f"TrainableScene: expected a BakedScene, got {type(scene).__name__}")
+        if scene.volumes[0].dtype != torch.float32:
+            raise TypeError(f"BakedScene.trainable: {_FP32_ONLY}")
+        N = len(scene)
+        chosen = list(range(N)) if objects is None else [int(j) for j in objects]
+        if not chosen or len(set(chosen)) != len(chosen) or not all(0 <= j < N for j in chosen):
+            raise ValueError(f"BakedScene.trainable: objects must be distinct indices into a scene of {N} (None: all), got {objects}")
+        self._source = scene
+        self.slots, params, owner = [None] * N, [], {}  # slots[j]: the parameter object j marches, None: frozen
+        for j, v in enumerate(scene.volumes):
+            twin = next((k for k in range(N) if scene.volumes[k] is v and k in chosen), None)
+            if twin is None:
+                continue
+            if id(v) not in owner:
+                owner[id(v)] = len(params)
+                params.append(torch.nn.Parameter(v._stored().clone()))
+            self.slots[j] = owner[id(v)]
+        self.stored = torch.nn.ParameterList(params)
+
+    def _tensors(self):
+        return [v._stored() if slot is None else self.stored[slot] for v, slot in zip(self._source.volumes, self.slots)]
+
+    def _march(self, source, obj_poses, step, white_bkgd, terminate, skip):
+        from .. import autograd
+        scene = self._source
+        step, terminate = scene._march_args(step, terminate)
+        meta = [ob[1:5] + ob[6:] for ob in scene._objects(skip)]
+        return autograd.baked_scene_fit_autograd(source, self._tensors(), meta, obj_poses, step, white_bkgd=white_bkgd, terminate=terminate)
+
+    def forward(self, rays, poses=None, step=None, white_bkgd=False, terminate=None, skip=False):
+        """world rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)) as `BakedScene.render`, differentiable with respect to
+        the parameters; rays, and `poses` (None: the scene's own; else (N,3,4) or (N,4,4) object-to-world, as render_diff takes
+        them), get their gradient when they require it."""
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError("TrainableScene.forward: rays must be (...,8)")
+        obj_poses = self._source._obj_poses("trainable().forward", poses)
+        lead = tuple(rays.shape[:-1])
+        rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), obj_poses, step, white_bkgd, terminate, skip)
+        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+    def forward_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, obj_poses=None, step=None, white_bkgd=False, terminate=None,
+                      skip=False):
+        """every pixel of the views, the rays regenerated in the kernel (as `BakedScene.render_views`, without its epilogue)
+        -> DotMap(rgb (NVt,H,W,3), depth (NVt,H,W), alpha (NVt,H,W)), differentiable with respect to the parameters; poses_c2w and
+        obj_poses get their gradient when they require it."""
+        W, H, focal, c = _camera_args("TrainableScene.forward_views", poses_c2w, W, H, focal, c, None)
+        obj_poses = self._source._obj_poses("trainable().forward_views", obj_poses)
+        NVt = poses_c2w.shape[0]
+        rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), obj_poses, step, white_bkgd, terminate, skip)
+        return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
+
+    def tv(self, rgb=1.0, sigma=1.0, sh=None, eps=1e-8):
+        """the sum of the total-variation priors of the trainable objects (TrainableBaked.tv of each, a volume listed twice counted
+        once): a 0-dim fp32 tensor, differentiable with respect to the parameters, no atomics"""
+        from .. import autograd
+        total, seen = None, set()
+        for v, slot in zip(self._source.volumes, self.slots):
+            if slot is None or slot in seen:
+                continue
+            seen.add(slot)
+            sparse = v._stored_name == "rows"
+            term = autograd.baked_tv_autograd(self.stored[slot], v.degree, v.reso, _tv_weights("TrainableScene.tv", v.degree, rgb, sigma, sh),
+                                              eps=eps, index=v.index if sparse else None, ids=v.ids if sparse else None)
+            total = term if total is None else total + term
+        return total
+
+    def scene(self):
+        """a fresh BakedScene of the current values: every trainable volume rebuilt as TrainableBaked.volume rebuilds it (checked,
+        its skip grid rebuilt; a volume listed twice rebuilt once), the frozen ones shared, the poses kept"""
+        rebuilt = {}
+        volumes = []
+        for v, slot in zip(self._source.volumes, self.slots):
+            if slot is None:
+                volumes.append(v)
+                continue
+            if slot not in rebuilt:
+                rebuilt[slot] = v._around(self.stored[slot].detach().clone())
+            volumes.append(rebuilt[slot])
+        return BakedScene(volumes, self._source.poses.clone())
+
+
+def fit_scene(scene, rays, target_rgb, objects=None, steps=200, lr=1e-2, batch=4096, seed=0, step=None, white_bkgd=False, terminate=None,
+              skip=False, tv_rgb=0.0, tv_sigma=0.0, tv_sh=None, tv_eps=1e-8):
+    """Fit the contents of a scene to colours of the scene: `fit`'s loop on `scene.trainable(objects)` -- Adam over `steps` batches of
+    `batch` world rays drawn with replacement from rays (...,8) by a CPU torch.Generator seeded with `seed`, loss = mean((rgb -
+    target_rgb)^2) over the batch; after every step RGBA volumes are projected back onto what they store (rgb into [0,1], sigma >=
+    0), coefficient volumes are left alone.  objects: the indices of the objects that are fitted (None: all); the others are frozen
+    and still mix and attenuate.  The poses stay where they are (`place` moves them; TrainableScene hands their gradient through for
+    whoever wants a joint descent).  step, white_bkgd, terminate, skip: as TrainableScene.forward.  tv_*: the total-variation prior
+    summed over the fitted objects, as in `fit` (`losses` reports the mse alone; all 0: no TV call).
+    A step costs one scene march and one pnr_baked_scene_stored_backward_rays call; no network.
+    -> (the fitted scene -- a new one, `scene` and its volumes are unchanged --, losses: the `steps` batch losses as floats)"""
+    if not isinstance(scene, BakedScene):
+        raise TypeError(f"fit_scene: expected a BakedScene, got {type(scene).__name__}")
+    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+        raise ValueError("fit_scene: rays must be (...,8)")
+    if not isinstance(target_rgb, torch.Tensor) or tuple(target_rgb.shape) != tuple(rays.shape[:-1]) + (3,):
+        raise ValueError(f"fit_scene: target_rgb must be {tuple(rays.shape[:-1]) + (3,)}, got "
+                         f"{tuple(target_rgb.shape) if isinstance(target_rgb, torch.Tensor) else type(target_rgb).__name__}")
+    steps, batch = int(steps), int(batch)
+    if steps < 0 or batch < 1:
+        raise ValueError(f"fit_scene: steps must be >= 0 and batch >= 1, got {steps}, {batch}")
+    module = scene.trainable(objects)
+    degree = scene.volumes[0].degree
+    prior = dict(rgb=tv_rgb, sigma=tv_sigma, sh=tv_sh, eps=tv_eps)
+    use_prior = any(w > 0 for w in _tv_weights("fit_scene", degree, tv_rgb, tv_sigma, tv_sh))
+    rays, target = rays.detach().reshape(-1, 8).float(), target_rgb.detach().reshape(-1, 3).float()
+    R = rays.shape[0]
+    if R == 0:
+        raise ValueError("fit_scene: no rays")
+    optimiser = torch.optim.Adam(module.parameters(), lr=float(lr))
+    gen = torch.Generator().manual_seed(int(seed))
+    losses = []
+    for _ in range(steps):
+        ids = torch.randint(0, R, (min(batch, R),), generator=gen).to(rays.device)
+        out = module(rays[ids], step=step, white_bkgd=white_bkgd, terminate=terminate, skip=skip)
+        loss = ((out.rgb - target[ids]) ** 2).mean()
+        optimiser.zero_grad(set_to_none=True)
+        (loss + module.tv(**prior) if use_prior else loss).backward()
+        optimiser.step()
+        if degree is None:
+            with torch.no_grad():
+                for p in module.stored:
+                    p[..., :3].clamp_(0.0, 1.0)
+                    p[..., 3].clamp_(min=0.0)
+        losses.append(loss.detach())
+    return module.scene(), (torch.stack(losses).tolist() if losses else [])
 
 
 # ---------------------------------------------------------------- registration: gradients with respect to the poses
