@@ -1235,6 +1235,65 @@ int pnr_baked_ray_backward_views(const float *poses /*(NV,4,4)*/, int NV, int W,
                                  const float *d_rgb /*(NV H W,3), nullable*/, const float *d_depth /*nullable*/,
                                  const float *d_alpha /*nullable*/, float *d_rays /*(NV H W,8), every row written*/, void *stream);
 
+/* Visibility of a baked volume (added within ABI rev 12 as well): which stored rows a set of rays SEES -- per row the largest
+ * compositing weight any sample gave it.  The pruning criterion of a fitted volume (a row no ray sees is not constrained by the
+ * fit), and the picture of what a set of views determines.
+ * pnr_baked_visibility_rays / pnr_baked_visibility_views take the argument list of pnr_baked_ray_backward_* without white_bkgd and
+ *   without upstream gradients: `stored`, storage_half, M, degree, index, bits, the grid, c1 / c2, step, terminate, then vis.
+ *   All 16 kinds are served (RGBA and degree 0, 1, 2; fp32 and fp16; dense and sparse); the pass only READS the volume.
+ * vis: fp32, (nx,ny,nz) when index == NULL, (M) -- one number per kept row -- when sparse.  The CALLER zeroes it once; the entry
+ *   max-accumulates into it, so calls on several batches or views accumulate.
+ * The samples are EXACTLY the forward's (its sample count, points, cells, skip bits, row lookup, blend and alpha, its product scan
+ *   and carry; with terminate > 0 the walk stops after the chunk the forward stops after), and w_i = a_i (carry x excl_i) is formed
+ *   with the forward's own fp32 operations: the forward's weight bit for bit.  For an active sample that found its rows, corner
+ *   c = (ix,iy,iz) of its cell proposes
+ *     v = w_i * omega_c,   omega_c = ((ix ? fx : 1 - fx) * (iy ? fy : 1 - fy)) * (iz ? fz : 1 - fz)
+ *   -- the corner weights of pnr_baked_backward_*, by its operations and in its order --, a proposal that is not > 0 is dropped
+ *   (zeros, and anything that is not a number), and vis[row(c)] = max(vis[row(c)], v).
+ * The maximum is taken by an unsigned-integer atomic max on the bit pattern of the float: every proposal is a positive finite
+ *   float, on which the two orders agree.  Maximum is commutative and associative EXACTLY: unlike pnr_baked_backward_*, two calls
+ *   on equal inputs give EQUAL BYTES, and so do any order of the rays and any split of them into accumulating calls; the sparse
+ *   entry gives the dense entry's bytes (with the same bits) at the kept points; a half volume gives the bytes of its widened one.
+ *   No scratch, no LDS, no workspace; one wavefront per ray.  vis must hold non-negative finite floats on entry (zeros, or the
+ *   result of earlier calls).
+ * Out of scope: scenes (pnr_baked_scene_* have no visibility).
+ * PNR_E_INVALID, before any HIP call, in the order and with the words of pnr_baked_ray_backward_*, vis in the place of d_rays
+ *   ("null argument"; "bits, d_rgb, d_depth, d_alpha and vis must be 4-byte aligned").  R = 0 (NV = 0): no-op, PNR_OK. */
+int pnr_baked_visibility_rays(const float *rays, long long R, const void *stored, int storage_half, long long M, int degree,
+                              const int32_t *index /*nullable: dense*/, const uint32_t *bits /*nullable when dense*/, int nx, int ny,
+                              int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, float terminate,
+                              float *vis /*(nx,ny,nz) or (M); zeroed by the caller, max-accumulated into*/, void *stream);
+int pnr_baked_visibility_views(const float *poses /*(NV,4,4)*/, int NV, int W, int H, float fx, float fy, float cx, float cy,
+                               float z_near, float z_far, const void *stored, int storage_half, long long M, int degree,
+                               const int32_t *index /*nullable: dense*/, const uint32_t *bits /*nullable when dense*/, int nx, int ny,
+                               int nz, const float *c1 /*host*/, const float *c2 /*host*/, float step, float terminate, float *vis,
+                               void *stream);
+
+/* Resampling a baked volume (added within ABI rev 12 as well): the stored values on ANOTHER point count over the SAME box -- what
+ * lets a fitted volume go from a coarse grid to a fine one without another bake.
+ * src: what pnr_baked_ray_backward_* call `stored` -- (nx,ny,nz,4) (degree -1) or (nx,ny,nz,B,4) (degree 0, 1, 2), fp32
+ *   (storage_half 0) or fp16 (1), or with index != NULL the M kept rows and `index` (nx,ny,nz).  index == NULL: M is not looked at.
+ * dst: always fp32.  ids_dst == NULL: dense, (nx',ny',nz'[,B],4), M_dst not looked at; otherwise the M_dst rows at the int32
+ *   linear ids `ids_dst` of the destination grid -- an id outside that grid writes a row of zeros and reads nothing.
+ * Per axis, for destination point i of n' over n source points, in 64-bit INTEGER arithmetic:
+ *     num = i (n - 1),  q = num / (n' - 1),  rem = num % (n' - 1),  i0 = q,  i1 = min(q + 1, n - 1),  f = (float)rem / (float)(n' - 1)
+ *   -- f is the one rounding.  The value is the nested blend of the march, along z, then y, then x, each 1-D blend
+ *     f == 0 ? a : a + f (b - a)
+ *   with the product, the difference and the sum rounded on their own and the f == 0 case a SELECT: a destination point that
+ *   coincides with a source point copies its value, -0 included.  So resampling to the same point count is the identity, and a
+ *   refinement n' - 1 = m (n - 1) keeps the old points, bit for bit, at stride m.  A view-dependent volume interpolates its
+ *   COEFFICIENTS: no basis, no clamp.  A sparse source reads a corner that is not kept (index < 0 or a rank outside [0, M)) as
+ *   zeros -- what the dense form of the volume holds there.
+ * One thread per destination float4 (point, k), k fastest, then z.  No atomics; two calls on equal inputs give equal bytes.
+ * Out of scope: autograd through the resampling, another box, fp16 destinations.
+ * PNR_E_INVALID before any HIP call, in this order: a degree outside {-1, 0, 1, 2}; storage_half neither 0 nor 1; either grid with
+ *   an axis < 2 points, or with 2^31 points or more; M < 0 with an index, M_dst < 0 with ids_dst; (no destination rows: no-op,
+ *   PNR_OK;) a null dst, a null src with source rows; src or dst not 16-byte aligned (fp16 src: 8-byte); index or ids_dst not
+ *   4-byte aligned. */
+int pnr_baked_resample(const void *src, int storage_half, long long M, int degree, const int32_t *index /*nullable: dense*/, int nx,
+                       int ny, int nz, float *dst, long long M_dst, const int32_t *ids_dst /*nullable: dense*/, int nx_dst, int ny_dst,
+                       int nz_dst, void *stream);
+
 /* Total-variation prior of a fitted volume (added within ABI rev 12 as well): the smoothness term a fit to few views needs, its
  * value and its gradient in one pass, with no atomics.  `stored` is what pnr_baked_backward_* calls `stored`: fp32 (nx,ny,nz,4)
  * (degree -1) or (nx,ny,nz,B,4) (degree 0, 1, 2; B = 1, 4, 9); with index != NULL the M kept rows (M,4) / (M,B,4), `index`

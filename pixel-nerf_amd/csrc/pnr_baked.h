@@ -1,5 +1,5 @@
 // pnr_baked.h -- what every march through a baked volume shares (pnr_baked.hip, pnr_baked_grad.hip, pnr_baked_scene.hip,
-// pnr_baked_tv.hip).  Semantics: include/pixelnerf_hip.h ("baked volumes").
+// pnr_baked_tv.hip, pnr_baked_visibility.hip, pnr_baked_resample.hip).  Semantics: include/pixelnerf_hip.h ("baked volumes").
 // Structure.  Device: ONE march (baked_march, pnr_baked.hip) and ONE kernel template (baked_march_kernel<Corner, Rows>) around it.
 // Corner says what the march reads at a corner of a cell (RgbaCornerOf / ShCorner<B>) and what a stored number is (float4 or Half4,
 // widened exactly on load: everything after the load is the same code); Rows says where a pair of corners lies (DenseRows: rows

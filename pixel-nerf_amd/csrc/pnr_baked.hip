@@ -11,7 +11,8 @@
 // (pnr_baked_half_render_* / pnr_baked_sparse_half_render_*) store four fp16 numbers where the others store a float4.
 // This file: the forward kernel, its ten entries and pnr_sparse_points_mark.  What every march shares, device and host, and the
 // structure of the family: pnr_baked.h.  The backward kernels (dL/d stored, dL/d rays): pnr_baked_grad.hip.  Scenes of several posed
-// volumes and their gradients: pnr_baked_scene.hip.  The total-variation prior: pnr_baked_tv.hip.
+// volumes and their gradients: pnr_baked_scene.hip.  The total-variation prior: pnr_baked_tv.hip.  What the rays see:
+// pnr_baked_visibility.hip.  A volume on another grid: pnr_baked_resample.hip.
 #include "pnr_baked.h"
 
 namespace pnr {

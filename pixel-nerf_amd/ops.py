@@ -1965,6 +1965,119 @@ def baked_ray_backward_views(poses, width, height, focal, c, z_near, z_far, stor
     return out.reshape(-1, H, W, 8)
 
 
+# ---- what the rays of a march see, and a volume on another grid (include/pixelnerf_hip.h, "Visibility of a baked volume",
+# "Resampling a baked volume")
+
+def _stored_tail(what, degree):
+    """degree None / -1 (RGBA), 0, 1 or 2, checked -> (degree as the library takes it, the shape of a row)"""
+    degree = -1 if degree is None else int(degree)
+    if degree not in (-1, 0, 1, 2):
+        raise ValueError(f"{what}: degree must be None / -1 (RGBA), 0, 1 or 2, got {degree}")
+    return degree, ((4,) if degree < 0 else ((degree + 1) ** 2, 4))
+
+
+def _baked_visibility(what, entry, stored, degree, reso, c1, c2, step, bits, index, terminate, out, rays=None, camera=None):
+    """checks before any device work, then pnr_baked_visibility_rays / _views INTO `out` (None: a fresh zeroed field) -> out"""
+    lib = _lib.load()
+    sparse = index is not None
+    half = isinstance(stored, torch.Tensor) and stored.dtype == torch.float16
+    # the shape of the field, from the arguments alone: a wrong `out` is refused before anything else looks at a device
+    if out is not None and isinstance(stored, torch.Tensor) and len(reso) == 3:
+        shape = (stored.shape[0],) if sparse else tuple(int(r) for r in reso)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() \
+                or out.requires_grad:
+            raise ValueError(f"{what}: out must be a contiguous float32 tensor of shape {shape} that does not require grad (it is "
+                             "max-accumulated into)")
+    v = _baked_volume(what, stored, degree, reso, c1, c2, step, bits, terminate, dtype=torch.float16 if half else torch.float32,
+                      name="rows" if sparse else "stored", index=index, sparse=sparse)
+    _, _, stored, degree, dims, c1, c2, step, terminate, bits, index = v
+    detached = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    if camera is None:
+        rays = detached(rays)
+    else:
+        camera = (detached(camera[0]),) + tuple(camera[1:])
+    args, R, dev, source = _baked_source(v, rays, camera)  # (source: kept alive over the call)
+    shape = (stored.shape[0],) if sparse else dims
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=dev)
+    elif out.device != dev:
+        raise ValueError(f"{what}: out lives on {out.device}, the {'rays' if camera is None else 'poses'} on {dev}")
+    lo, hi = _float3_pair(c1, c2)
+    M = stored.shape[0] if sparse else 0
+    args += (_p(stored) if stored.numel() else None, int(half), M, degree, None if index is None else _p(index.contiguous()),
+             None if bits is None else _p(bits.contiguous()), dims[0], dims[1], dims[2], lo, hi, step, terminate, _p(out))
+    if R and out.numel():
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    return out
+
+
+def baked_visibility(rays, stored, degree, reso, c1, c2, step, bits=None, index=None, terminate=0.0, out=None):
+    """Which stored rows the rays of a march SEE (pnr_baked_visibility_rays): per row the largest w_i x (trilinear corner weight) over
+    every sample of every ray, w_i the forward's compositing weight bit for bit.  rays (R,8); stored fp32 or fp16, (nx,ny,nz,4)
+    (degree None / -1) or (nx,ny,nz,B,4) (degree 0, 1, 2), or with `index` the kept rows (M,4) / (M,B,4) (bits are then mandatory).
+    -> vis fp32, (nx,ny,nz) for a dense volume, (M,) for a sparse one.  `out`: a field the result is MAX-accumulated into (zeroed
+    by the caller before the first batch); None: a fresh one.  The samples are exactly the forward's with the same rays, bits, step
+    and terminate.  An integer atomic max: the same bytes on every call, for any order of the rays and any split into batches."""
+    return _baked_visibility("baked_visibility", "pnr_baked_visibility_rays", stored, degree, reso, c1, c2, step, bits, index, terminate,
+                             out, rays=rays)
+
+
+def baked_visibility_views(poses, width, height, focal, c, z_near, z_far, stored, degree, reso, c1, c2, step, bits=None, index=None,
+                           terminate=0.0, out=None):
+    """baked_visibility over every pixel of the views of gen_rays(poses, width, height, focal, z_near, z_far, c)
+    (pnr_baked_visibility_views): the rays are regenerated in the kernel -- the bytes of baked_visibility(gen_rays(...))."""
+    W, H = _image_size("baked_visibility_views", width, height)
+    return _baked_visibility("baked_visibility_views", "pnr_baked_visibility_views", stored, degree, reso, c1, c2, step, bits, index,
+                             terminate, out, camera=(poses, W, H, focal, c, z_near, z_far))
+
+
+def baked_resample(stored, degree, reso, reso_dst, index=None, ids_dst=None):
+    """The stored values of a baked volume on another point count over the SAME box (pnr_baked_resample): stored fp32 or fp16,
+    (nx,ny,nz,4) (degree None / -1) or (nx,ny,nz,B,4) (degree 0, 1, 2) with reso = (nx,ny,nz), or with `index` (nx,ny,nz) int32 the
+    kept rows (M,4) / (M,B,4) (a corner that is not kept reads as zeros).  reso_dst: the new point counts.
+    -> fp32, dense (nx',ny',nz'[,B],4), or with ids_dst (M',) int32 -- linear ids of the NEW grid -- the rows (M'[,B],4) at those
+    points (an id outside the grid: a row of zeros).  Integer index arithmetic and a select at fraction 0: the same reso is the
+    identity, a refinement n' - 1 = m (n - 1) keeps the old points bit for bit.  A view-dependent volume interpolates its
+    coefficients.  No atomics: the same bytes on every call.  No autograd."""
+    what = "baked_resample"
+    lib = _lib.load()
+    degree, tail = _stored_tail(what, degree)
+    if len(reso) != 3 or len(reso_dst) != 3:
+        raise ValueError(f"{what}: reso and reso_dst must have 3 entries each")
+    dims, dims_dst = tuple(int(r) for r in reso), tuple(int(r) for r in reso_dst)
+    for d in (dims, dims_dst):
+        if any(n < 2 for n in d) or d[0] * d[1] * d[2] >= 2 ** 31:
+            raise ValueError(f"{what}: a grid needs at least 2 points per axis and fewer than 2^31 points, got {d}")
+    sparse = index is not None
+    lead = (None,) if sparse else dims
+    if not isinstance(stored, torch.Tensor) or stored.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"{what}: stored must be a float32 or float16 tensor")
+    if stored.dim() != len(lead) + len(tail) or tuple(stored.shape[len(lead):]) != tail or (not sparse and tuple(stored.shape[:3]) != dims):
+        raise ValueError(f"{what}: stored must be ({'M' if sparse else ','.join(str(d) for d in dims)},{','.join(str(s) for s in tail)}) at "
+                         f"degree {degree}, got {tuple(stored.shape)}")
+    half = stored.dtype == torch.float16
+    stored = _f32(stored.detach(), "stored", lead + tail, stored.dtype)
+    dev = stored.device
+    if stored.numel() and stored.data_ptr() % (8 if half else 16):
+        raise ValueError(f"{what}: stored must be {8 if half else 16}-byte aligned")
+    if sparse and (not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != dims or index.device != dev):
+        raise ValueError(f"{what}: index must be the {dims} int32 tensor of sparse_points on {dev}")
+    if ids_dst is not None and (not isinstance(ids_dst, torch.Tensor) or ids_dst.dtype != torch.int32 or ids_dst.dim() != 1
+                                or ids_dst.device != dev):
+        raise ValueError(f"{what}: ids_dst must be a 1-d int32 tensor on {dev}")
+    M = stored.shape[0] if sparse else 0
+    M_dst = ids_dst.shape[0] if ids_dst is not None else 0
+    out = torch.empty(((M_dst,) if ids_dst is not None else dims_dst) + tail, dtype=torch.float32, device=dev)
+    if out.numel():
+        ids_dst = None if ids_dst is None else ids_dst.contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(lib.pnr_baked_resample(_p(stored) if stored.numel() else None, int(half), M, degree,
+                                              _p(index.contiguous()) if sparse else None, *dims, _p(out), M_dst, _p(ids_dst), *dims_dst,
+                                              _stream()), "pnr_baked_resample")
+    return out
+
+
 # ---- the total-variation prior of a fitted volume (include/pixelnerf_hip.h, "Total-variation prior")
 
 def baked_tv(stored, degree, reso, weights, eps=1e-8, index=None, ids=None, want_value=True, grad_out=None, scale=None):

@@ -181,6 +181,85 @@ def _views_result(rgb, depth, alpha, NVt, W, H, z_near, z_far, gt_rgb, want_u8):
     return ret
 
 
+def _check_field(what, name, field, shape, nullable=False):
+    """a visibility field (or the `out` of one): a contiguous fp32 tensor of `shape`; checked before any device work"""
+    if field is None and nullable:
+        return
+    if not isinstance(field, torch.Tensor) or field.dtype != torch.float32 or tuple(field.shape) != tuple(shape) \
+            or not field.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of shape {tuple(shape)}, got "
+                         f"{(tuple(field.shape), field.dtype) if isinstance(field, torch.Tensor) else type(field).__name__}")
+
+
+def _resample_reso(what, reso):
+    """an int or three ints, each >= 2 -> (nx, ny, nz)"""
+    import numbers
+    reso = (reso,) * 3 if isinstance(reso, numbers.Integral) and not isinstance(reso, bool) else reso
+    try:
+        reso = tuple(reso)
+    except TypeError:
+        raise ValueError(f"{what}: reso must be an int or three ints, got {reso!r}") from None
+    if len(reso) != 3 or not all(isinstance(r, numbers.Integral) and not isinstance(r, bool) for r in reso):
+        raise ValueError(f"{what}: reso must be an int or three ints, got {reso!r}")
+    reso = tuple(int(r) for r in reso)
+    if any(r < 2 for r in reso) or reso[0] * reso[1] * reso[2] >= 2 ** 31:
+        raise ValueError(f"{what}: every axis needs at least 2 grid points and the grid fewer than 2^31, got reso {reso}")
+    return reso
+
+
+def _sparse_refinement(what, reso, new):
+    """the integer factors m_a with n'_a - 1 == m_a (n_a - 1), or ValueError: a sparse volume keeps whole cells, and only an integer
+    refinement maps every new cell into ONE old cell"""
+    if any((b - 1) % (a - 1) for a, b in zip(reso, new)):
+        raise ValueError(f"{what}: a sparse volume takes integer refinements only (n' - 1 == m (n - 1) on every axis), got {tuple(reso)} -> "
+                         f"{tuple(new)}; resample the dense volume and prune again")
+    return tuple((b - 1) // (a - 1) for a, b in zip(reso, new))
+
+
+def _cells_of(bits, reso):
+    """the bitfield of ops.occupancy_build as a (nx-1,ny-1,nz-1) bool tensor"""
+    shape = tuple(r - 1 for r in reso)
+    shifts = torch.arange(32, device=bits.device)
+    flat = ((bits.long()[:, None] >> shifts) & 1).bool().flatten()
+    return flat[:shape[0] * shape[1] * shape[2]].view(shape)
+
+
+def _bits_of(cells):
+    """a bool tensor of cells as the bitfield of ops.occupancy_build: cell index i is bit (i & 31) of int32 word (i >> 5)"""
+    flat = cells.flatten()
+    words = (flat.numel() + 31) // 32
+    padded = torch.zeros((words * 32,), dtype=torch.int64, device=flat.device)
+    padded[:flat.numel()] = flat
+    value = (padded.view(words, 32) << torch.arange(32, device=flat.device)).sum(dim=1)
+    return torch.where(value >= 2 ** 31, value - 2 ** 32, value).to(torch.int32)
+
+
+def _count_bits(bits):
+    """the number of bits set, as the 0-d int32 device tensor an OccupancyGrid carries"""
+    table = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.int32, device=bits.device)
+    return table[bits.contiguous().view(torch.uint8).long()].sum().to(torch.int32)
+
+
+def _check_stages(what, stages):
+    """stages of fit_coarse_to_fine: a non-empty sequence of (reso | None, steps) -> [(reso (nx,ny,nz) | None, steps)]"""
+    import numbers
+    try:
+        stages = list(stages)
+    except TypeError:
+        raise ValueError(f"{what}: stages must be a sequence of (reso | None, steps)") from None
+    if not stages:
+        raise ValueError(f"{what}: stages must hold at least one (reso | None, steps)")
+    out = []
+    for k, stage in enumerate(stages):
+        if not isinstance(stage, (tuple, list)) or len(stage) != 2:
+            raise ValueError(f"{what}: stage {k} must be (reso | None, steps), got {stage!r}")
+        reso, steps = stage
+        if not isinstance(steps, numbers.Integral) or isinstance(steps, bool) or steps < 0:
+            raise ValueError(f"{what}: stage {k}: steps must be an int >= 0, got {steps!r}")
+        out.append((None if reso is None else _resample_reso(f"{what}: stage {k}", reso), int(steps)))
+    return out
+
+
 class _Baked:
     """what BakedVolume, BakedSHVolume and SparseBakedVolume share: the march through `self.occupancy` on the grid (reso, c1, c2) and
     the storage methods.  A subclass names the tensor it stores (`_stored_name`: the attribute, and the key of its state) and has a
@@ -330,6 +409,90 @@ class _Baked:
         step, terminate, bits = self._march_args(step, terminate, skip)
         rgb, depth, alpha = self._march_diff((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, bits, white_bkgd, terminate)
         return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
+
+    # ---- coarse to fine: what the rays see, pruning by it, and the volume on another grid
+
+    def _vis_shape(self):
+        return (self._stored().shape[0],) if self._stored_name == "rows" else tuple(self.reso)
+
+    def _visibility(self, what, source, step, terminate, skip, out):
+        from .. import ops
+        _check_field(what, "out", out, self._vis_shape(), nullable=True)
+        step, terminate, bits = self._march_args(step, terminate, skip)
+        sparse = self._stored_name == "rows"
+        kw = dict(bits=bits, index=self.index if sparse else None, terminate=terminate, out=out)
+        with torch.no_grad():
+            if len(source) == 1:
+                return ops.baked_visibility(source[0], self._stored(), self.degree, self.reso, self.c1, self.c2, step, **kw)
+            poses, W, H, focal, c, z_near, z_far = source
+            return ops.baked_visibility_views(poses, W, H, focal, c, z_near, z_far, self._stored(), self.degree, self.reso, self.c1,
+                                              self.c2, step, **kw)
+
+    def visibility(self, rays, step=None, terminate=None, skip=True, out=None):
+        """Which stored values the rays SEE (ops.baked_visibility): rays (...,8) -> fp32 (nx,ny,nz) for a dense volume, (M,) -- one
+        number per kept row -- for a sparse one: the largest compositing weight x trilinear corner weight any sample of any ray gave
+        the point, with exactly the samples and weights of `render(rays, step, terminate=, skip=)`.  0: no ray constrains the point.
+        :param out a field of that shape from an earlier call: the result is max-accumulated into it and returned (batches, views)
+        The same bytes on every call, whatever the order of the rays and however they are split into calls."""
+        name = f"{type(self).__name__}.visibility"
+        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+            raise ValueError(f"{name}: rays must be (...,8)")
+        return self._visibility(name, (rays.detach().reshape(-1, 8).float(),), step, terminate, skip, out)
+
+    def visibility_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, terminate=None, skip=True, out=None):
+        """`visibility` over every pixel of the views (ops.baked_visibility_views): the rays are regenerated in the kernel -- the bytes
+        of visibility(util.gen_rays(...)), no ray array.  poses_c2w, W, H, focal, z_near, z_far, c: as render_views."""
+        name = f"{type(self).__name__}.visibility_views"
+        W, H, focal, c = _camera_args(name, poses_c2w, W, H, focal, c, None)
+        return self._visibility(name, (poses_c2w.detach().float(), W, H, focal, c, z_near, z_far), step, terminate, skip, out)
+
+    def resample(self, reso):
+        """This volume on another point count over the SAME box (ops.baked_resample): reso an int or (nx,ny,nz).  Trilinear in the
+        stored values (a view-dependent volume: in its coefficients), exact index arithmetic: the same reso gives the same values,
+        a refinement n' - 1 = m (n - 1) keeps every old point bit for bit.  -> a new volume of this class: a dense one with this
+        skip_threshold and its skip grid rebuilt from the new sigma; a half one is the fp32 result through `to_half` (the one
+        rounding path); a SparseBakedVolume takes integer refinements only (ValueError otherwise, before any device work): a cell
+        of the new occupancy grid is occupied iff its parent cell was, and the dense tensor is never formed.  No autograd."""
+        from .. import ops
+        name = f"{type(self).__name__}.resample"
+        reso = _resample_reso(name, reso)
+        half = self.dtype == torch.float16
+        if self._stored_name != "rows":
+            out = ops.baked_resample(self._stored(), self.degree, self.reso, reso)
+            return self._around(to_half(out) if half else out)
+        m = _sparse_refinement(name, self.reso, reso)
+        old = self.occupancy
+        cells = _cells_of(old.bits, old.reso)
+        for axis in range(3):
+            cells = cells.repeat_interleave(m[axis], dim=axis)
+        occupancy = OccupancyGrid(_bits_of(cells), reso, self.c1, self.c2, old.threshold, old.dilate,
+                                  (old.n_occupied * (m[0] * m[1] * m[2])).to(torch.int32))
+        index, ids = ops.sparse_points(occupancy.bits, reso)
+        rows = ops.baked_resample(self.rows, self.degree, self.reso, reso, index=self.index, ids_dst=ids)
+        return SparseBakedVolume(to_half(rows) if half else rows, occupancy, index=index, ids=ids)
+
+    def prune(self, visibility, threshold, dilate=1):
+        """Keep what the rays see: `visibility` the field of `visibility(...)` on this volume -- (nx,ny,nz), or (M,) of a sparse one --,
+        -> the SparseBakedVolume of the cells within `dilate` cells of a cell with a corner whose visibility is > threshold
+        (OccupancyGrid.from_density of the field), ANDed with this volume's own occupancy bits: pruning never adds a cell.  The
+        result renders the bytes of this volume's `render(skip=True)` on every ray whose samples all lie in kept cells."""
+        from .. import ops
+        name = f"{type(self).__name__}.prune"
+        _check_field(name, "visibility", visibility, self._vis_shape())
+        sparse = self._stored_name == "rows"
+        field = visibility.detach()
+        if sparse:
+            dense = torch.zeros((self.reso[0] * self.reso[1] * self.reso[2],), dtype=torch.float32, device=field.device)
+            dense.index_copy_(0, self.ids.long(), field)
+            field = dense.view(*self.reso)
+        seen = OccupancyGrid.from_density(field.contiguous(), self.c1, self.c2, threshold, dilate=dilate)
+        bits = (seen.bits & self.occupancy.bits).contiguous()
+        occupancy = OccupancyGrid(bits, self.reso, self.c1, self.c2, threshold, dilate, _count_bits(bits))
+        if not sparse:
+            return self.sparse(occupancy)
+        index, ids = ops.sparse_points(bits, self.reso)  # a subset of this volume's kept points: fewer cells, the same closure
+        ranks = self.index.view(-1).index_select(0, ids.long())
+        return SparseBakedVolume(self.rows.index_select(0, ranks.long()), occupancy, index=index, ids=ids)
 
 
 class BakedVolume(_Baked):
@@ -929,6 +1092,58 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
                 module.stored[..., 3].clamp_(min=0.0)
         losses.append(loss.detach())
     return module.volume(), (torch.stack(losses).tolist() if losses else [])
+
+
+_VISIBILITY_BATCH = 1 << 18  # rays per visibility call of fit_coarse_to_fine (the result does not depend on it)
+
+
+def fit_coarse_to_fine(volume, rays, target_rgb, stages, prune=None, **fit_kwargs):
+    """`fit` over a sequence of grids: stages = [(reso | None, steps), ...], reso an int, (nx,ny,nz) or None = stay.  Per stage k the
+    volume is resampled (`volume.resample(reso)`) when the reso differs from its own, then fitted: fit(volume, rays, target_rgb,
+    steps=steps, seed=seed + k, **fit_kwargs) -- every other argument of `fit` goes through, `seed` (default 0) is the first stage's.
+    prune = dict(threshold=, dilate=1): after every stage the visibility of ALL rays (in batches, with the stage's step, terminate
+    and skip) is taken and the volume pruned by it (`volume.prune`): the next stages fit a SparseBakedVolume, with skip=True, and
+    refine by integer factors only.  Everything is checked before any device work.
+    -> (the volume of the last stage, [the losses of each stage])"""
+    what = "fit_coarse_to_fine"
+    if not isinstance(volume, _Baked):
+        raise TypeError(f"{what}: expected a baked volume, got {type(volume).__name__}")
+    stages = _check_stages(what, stages)
+    if prune is not None:
+        if not isinstance(prune, dict) or "threshold" not in prune or set(prune) - {"threshold", "dilate"}:
+            raise ValueError(f"{what}: prune must be None or dict(threshold=, dilate=1), got {prune!r}")
+        prune = dict(threshold=float(prune["threshold"]), dilate=int(prune.get("dilate", 1)))
+        if prune["threshold"] != prune["threshold"] or not 0 <= prune["dilate"] <= 4:
+            raise ValueError(f"{what}: prune needs a threshold that is a number and a dilate in [0, 4], got {prune!r}")
+    if "steps" in fit_kwargs:
+        raise ValueError(f"{what}: the steps belong to the stages")
+    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+        raise ValueError(f"{what}: rays must be (...,8)")
+    seed = int(fit_kwargs.pop("seed", 0))
+    reso, sparse = tuple(volume.reso), volume._stored_name == "rows"
+    for k, (new, _) in enumerate(stages):  # the chain of grids, walked on the host first
+        if new is not None and new != reso:
+            if sparse:
+                _sparse_refinement(f"{what}: stage {k}", reso, new)
+            reso = new
+        sparse = sparse or prune is not None
+    flat = rays.detach().reshape(-1, 8).float()
+    all_losses = []
+    for k, (new, steps) in enumerate(stages):
+        if new is not None and new != tuple(volume.reso):
+            volume = volume.resample(new)
+        kw = dict(fit_kwargs)
+        if volume._stored_name == "rows":
+            kw["skip"] = True
+        volume, losses = fit(volume, rays, target_rgb, steps=steps, seed=seed + k, **kw)
+        all_losses.append(losses)
+        if prune is not None:
+            vis = None
+            for first in range(0, flat.shape[0], _VISIBILITY_BATCH):
+                vis = volume.visibility(flat[first:first + _VISIBILITY_BATCH], step=kw.get("step"), terminate=kw.get("terminate"),
+                                        skip=bool(kw.get("skip", False)), out=vis)
+            volume = volume.prune(vis, prune["threshold"], prune["dilate"])
+    return volume, all_losses
 
 
 # ---------------------------------------------------------------- fitting a scene: stored-value gradients through the mixture
