@@ -547,6 +547,41 @@ def render_autograd(renderer, net, rays, noise, want_weights):
     return res
 
 
+def _fp32(g):
+    """an upstream gradient as the ops backward entries take it (None stays None)"""
+    return None if g is None else g.contiguous().float()
+
+
+def _checked_source(what, source):
+    """source of a baked march: (rays,) or (poses, W, H, focal, c, z_near, z_far), the first a tensor -> the tuple"""
+    source = tuple(source)
+    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
+        raise ValueError(f"{what}: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
+    return source
+
+
+def _check_obj_poses(what, obj_poses, n):
+    if not isinstance(obj_poses, torch.Tensor) or obj_poses.dim() != 3 or tuple(obj_poses.shape[1:]) != (3, 4) \
+            or obj_poses.shape[0] != n or not obj_poses.is_floating_point():
+        raise ValueError(f"{what}: obj_poses must be a float tensor ({n},3,4) object-to-world")
+
+
+def _posed(volumes, host):
+    """ops.baked_scene_render's objects: every (stored, degree, reso, c1, c2, bits, index) with its pose, a row of `host`, put in"""
+    return [ob[:5] + (host[j],) + ob[5:] for j, ob in enumerate(volumes)]
+
+
+def _scene_source_grads(ctx, rest, obj_poses, d_rays, d_poses):
+    """what pnr_baked_scene_backward_* gave -> (d_lead, d_obj) for the inputs that need them: the rays' gradient as it is, the
+    cameras' through ops.gen_rays_backward, the object poses' on their own device and dtype"""
+    d_lead = d_obj = None
+    if ctx.needs_input_grad[0]:
+        d_lead = d_rays if not rest else ops.gen_rays_backward(d_rays, rest[0], rest[1], rest[2], rest[3])
+    if ctx.needs_input_grad[1]:
+        d_obj = d_poses.reshape(-1, 3, 4).to(device=obj_poses.device, dtype=obj_poses.dtype)
+    return d_lead, d_obj
+
+
 class _BakedMarchFunction(torch.autograd.Function):
     """The baked-volume ray march, differentiable with respect to the STORED values (include/pixelnerf_hip.h, "Gradients of the
     baked march").  forward IS the inference entry -- ops.baked_render / baked_sh_render / baked_sparse_render or their _views
@@ -557,14 +592,7 @@ class _BakedMarchFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stored, source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate):
         ctx.set_materialize_grads(False)
-        views = "" if len(source) == 1 else "_views"
-        tail = dict(white_bkgd=white_bkgd, terminate=terminate)
-        if index is not None:
-            out = getattr(ops, "baked_sparse_render" + views)(*source, stored, degree, index, bits, reso, c1, c2, step, **tail)
-        elif degree is None or degree < 0:
-            out = getattr(ops, "baked_render" + views)(*source, stored, reso, c1, c2, step, bits=bits, **tail)
-        else:
-            out = getattr(ops, "baked_sh_render" + views)(*source, stored, degree, reso, c1, c2, step, bits=bits, **tail)
+        out = ops.baked_march(source, stored, degree, reso, c1, c2, step, bits=bits, index=index, white_bkgd=white_bkgd, terminate=terminate)
         ctx.save_for_backward(stored)
         ctx.march = (source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate)
         return out
@@ -575,10 +603,9 @@ class _BakedMarchFunction(torch.autograd.Function):
         source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate = ctx.march
         if not ctx.needs_input_grad[0] or (d_rgb is None and d_depth is None and d_alpha is None):
             return (None,) * 11
-        fp32 = lambda g: None if g is None else g.contiguous().float()
         entry = ops.baked_render_backward if len(source) == 1 else ops.baked_render_views_backward
-        d_stored = entry(*source, stored.detach(), degree, reso, c1, c2, step, d_rgb=fp32(d_rgb), d_depth=fp32(d_depth),
-                         d_alpha=fp32(d_alpha), bits=bits, index=index, white_bkgd=white_bkgd, terminate=terminate)
+        d_stored = entry(*source, stored.detach(), degree, reso, c1, c2, step, d_rgb=_fp32(d_rgb), d_depth=_fp32(d_depth),
+                         d_alpha=_fp32(d_alpha), bits=bits, index=index, white_bkgd=white_bkgd, terminate=terminate)
         return (d_stored,) + (None,) * 10
 
 
@@ -595,20 +622,6 @@ def baked_march_autograd(stored, source, degree, reso, c1, c2, step, bits=None, 
                                      bool(white_bkgd), float(terminate))
 
 
-def _baked_forward(stored, source, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate):
-    """the inference entry of a stored tensor: which ops function marches follows from the dtype, the degree and the index"""
-    views = "" if len(source) == 1 else "_views"
-    tail = dict(white_bkgd=white_bkgd, terminate=terminate)
-    half = "half_" if stored.dtype == torch.float16 else ""
-    if index is not None:
-        return getattr(ops, f"baked_sparse_{half}render{views}")(*source, stored, degree, index, bits, reso, c1, c2, step, **tail)
-    if half:
-        return getattr(ops, "baked_half_render" + views)(*source, stored, degree, reso, c1, c2, step, bits=bits, **tail)
-    if degree is None or degree < 0:
-        return getattr(ops, "baked_render" + views)(*source, stored, reso, c1, c2, step, bits=bits, **tail)
-    return getattr(ops, "baked_sh_render" + views)(*source, stored, degree, reso, c1, c2, step, bits=bits, **tail)
-
-
 class _BakedMarchRaysFunction(torch.autograd.Function):
     """The baked-volume ray march, differentiable with respect to its RAYS or POSES (include/pixelnerf_hip.h, "Gradients of the baked
     march with respect to the RAYS") and, for an fp32 volume that requires grad, with respect to the stored values too.  forward IS
@@ -618,7 +631,8 @@ class _BakedMarchRaysFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stored, lead, rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate):
         ctx.set_materialize_grads(False)
-        out = _baked_forward(stored, (lead,) + rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate)
+        out = ops.baked_march((lead,) + rest, stored, degree, reso, c1, c2, step, bits=bits, index=index, white_bkgd=white_bkgd,
+                              terminate=terminate)
         ctx.save_for_backward(stored, lead)
         ctx.march = (rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate)
         return out
@@ -629,9 +643,8 @@ class _BakedMarchRaysFunction(torch.autograd.Function):
         rest, degree, index, bits, reso, c1, c2, step, white_bkgd, terminate = ctx.march
         if d_rgb is None and d_depth is None and d_alpha is None:
             return (None,) * 12
-        fp32 = lambda g: None if g is None else g.contiguous().float()
         source = (lead.detach(),) + rest
-        kw = dict(d_rgb=fp32(d_rgb), d_depth=fp32(d_depth), d_alpha=fp32(d_alpha), bits=bits, index=index, white_bkgd=white_bkgd,
+        kw = dict(d_rgb=_fp32(d_rgb), d_depth=_fp32(d_depth), d_alpha=_fp32(d_alpha), bits=bits, index=index, white_bkgd=white_bkgd,
                   terminate=terminate)
         d_stored = d_lead = None
         if ctx.needs_input_grad[0]:
@@ -656,9 +669,7 @@ def baked_march_rays_autograd(stored, source, degree, reso, c1, c2, step, bits=N
         raise TypeError("baked_march_rays_autograd: stored must be a float32 or float16 tensor")
     if stored.dtype == torch.float16 and stored.requires_grad:
         raise TypeError("baked_march_rays_autograd: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
-    source = tuple(source)
-    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
-        raise ValueError("baked_march_rays_autograd: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
+    source = _checked_source("baked_march_rays_autograd", source)
     return _BakedMarchRaysFunction.apply(stored, source[0], source[1:], degree, index, bits, tuple(reso), tuple(c1), tuple(c2), float(step),
                                          bool(white_bkgd), float(terminate))
 
@@ -673,7 +684,7 @@ class _BakedSceneMarchFunction(torch.autograd.Function):
     def forward(ctx, lead, obj_poses, rest, volumes, step, white_bkgd, terminate):
         ctx.set_materialize_grads(False)
         host = obj_poses.detach().to("cpu", torch.float32)  # the poses are kernel arguments by value: one host read
-        objects = [(stored, degree, reso, c1, c2, host[j], bits, index) for j, (stored, degree, reso, c1, c2, bits, index) in enumerate(volumes)]
+        objects = _posed(volumes, host)
         entry = ops.baked_scene_render if not rest else ops.baked_scene_render_views
         out = entry(lead, *rest, objects, step, white_bkgd=white_bkgd, terminate=terminate)
         ctx.save_for_backward(lead, obj_poses)
@@ -686,16 +697,10 @@ class _BakedSceneMarchFunction(torch.autograd.Function):
         rest, objects, step, white_bkgd, terminate = ctx.march
         if (d_rgb is None and d_depth is None and d_alpha is None) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return (None,) * 7
-        fp32 = lambda g: None if g is None else g.contiguous().float()
         entry = ops.baked_scene_backward if not rest else ops.baked_scene_backward_views
-        d_rays, _, d_poses = entry(lead.detach(), *rest, objects, step, d_rgb=fp32(d_rgb), d_depth=fp32(d_depth), d_alpha=fp32(d_alpha),
+        d_rays, _, d_poses = entry(lead.detach(), *rest, objects, step, d_rgb=_fp32(d_rgb), d_depth=_fp32(d_depth), d_alpha=_fp32(d_alpha),
                                    white_bkgd=white_bkgd, terminate=terminate, want_poses=ctx.needs_input_grad[1])
-        d_lead = d_obj = None
-        if ctx.needs_input_grad[0]:
-            d_lead = d_rays if not rest else ops.gen_rays_backward(d_rays, rest[0], rest[1], rest[2], rest[3])
-        if ctx.needs_input_grad[1]:
-            d_obj = d_poses.reshape(-1, 3, 4).to(device=obj_poses.device, dtype=obj_poses.dtype)
-        return (d_lead, d_obj) + (None,) * 5
+        return _scene_source_grads(ctx, rest, obj_poses, d_rays, d_poses) + (None,) * 5
 
 
 def baked_scene_march_autograd(source, objects, obj_poses, step, white_bkgd=False, terminate=0.0):
@@ -707,12 +712,8 @@ def baked_scene_march_autograd(source, objects, obj_poses, step, white_bkgd=Fals
     gets the projection from autograd.  The stored values are not differentiated.
     The object poses are kernel arguments BY VALUE: a differentiable call reads the N x 12 numbers to the host once per forward (a
     synchronisation when they live on the device)."""
-    source = tuple(source)
-    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
-        raise ValueError("baked_scene_march_autograd: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
-    if not isinstance(obj_poses, torch.Tensor) or obj_poses.dim() != 3 or tuple(obj_poses.shape[1:]) != (3, 4) \
-            or obj_poses.shape[0] != len(objects) or not obj_poses.is_floating_point():
-        raise ValueError(f"baked_scene_march_autograd: obj_poses must be a float tensor ({len(objects)},3,4) object-to-world")
+    source = _checked_source("baked_scene_march_autograd", source)
+    _check_obj_poses("baked_scene_march_autograd", obj_poses, len(objects))
     volumes = tuple(tuple(ob) for ob in objects)
     if any(len(ob) != 7 for ob in volumes):
         raise ValueError("baked_scene_march_autograd: an object must be (stored, degree, reso, c1, c2, bits, index)")
@@ -731,8 +732,7 @@ class _BakedSceneFitFunction(torch.autograd.Function):
     def forward(ctx, lead, obj_poses, rest, meta, step, white_bkgd, terminate, *stored):
         ctx.set_materialize_grads(False)
         host = obj_poses.detach().to("cpu", torch.float32)  # the poses are kernel arguments by value: one host read
-        objects = [(stored[slot], degree, reso, c1, c2, host[j], bits, index)
-                   for j, (slot, degree, reso, c1, c2, bits, index) in enumerate(meta)]
+        objects = _posed([(stored[m[0]],) + m[1:] for m in meta], host)
         entry = ops.baked_scene_render if not rest else ops.baked_scene_render_views
         out = entry(lead, *rest, objects, step, white_bkgd=white_bkgd, terminate=terminate)
         ctx.save_for_backward(lead, obj_poses, *stored)
@@ -747,11 +747,9 @@ class _BakedSceneFitFunction(torch.autograd.Function):
         none = (None,) * (7 + len(stored))
         if (d_rgb is None and d_depth is None and d_alpha is None) or not any(ctx.needs_input_grad):
             return none
-        fp32 = lambda g: None if g is None else g.contiguous().float()
-        kw = dict(d_rgb=fp32(d_rgb), d_depth=fp32(d_depth), d_alpha=fp32(d_alpha), white_bkgd=white_bkgd, terminate=terminate)
+        kw = dict(d_rgb=_fp32(d_rgb), d_depth=_fp32(d_depth), d_alpha=_fp32(d_alpha), white_bkgd=white_bkgd, terminate=terminate)
         stored = [s.detach() for s in stored]  # (one tensor object per slot: ops shares a buffer between its listings)
-        objects = [(stored[slot], degree, reso, c1, c2, host[j], bits, index)
-                   for j, (slot, degree, reso, c1, c2, bits, index) in enumerate(meta)]
+        objects = _posed([(stored[m[0]],) + m[1:] for m in meta], host)
         d_stored = [None] * len(stored)
         if any(need_stored):
             entry = ops.baked_scene_stored_backward if not rest else ops.baked_scene_stored_backward_views
@@ -762,10 +760,7 @@ class _BakedSceneFitFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             entry = ops.baked_scene_backward if not rest else ops.baked_scene_backward_views
             d_rays, _, d_poses = entry(lead.detach(), *rest, objects, step, want_poses=ctx.needs_input_grad[1], **kw)
-            if ctx.needs_input_grad[0]:
-                d_lead = d_rays if not rest else ops.gen_rays_backward(d_rays, rest[0], rest[1], rest[2], rest[3])
-            if ctx.needs_input_grad[1]:
-                d_obj = d_poses.reshape(-1, 3, 4).to(device=obj_poses.device, dtype=obj_poses.dtype)
+            d_lead, d_obj = _scene_source_grads(ctx, rest, obj_poses, d_rays, d_poses)
         return (d_lead, d_obj) + (None,) * 5 + tuple(d_stored)
 
 
@@ -778,18 +773,14 @@ def baked_scene_fit_autograd(source, stored, volumes_meta, obj_poses, step, whit
     volumes_meta: per object (degree, reso, c1, c2, bits, index) -- baked_scene_march_autograd's tuples without the tensor.
     source and obj_poses: as baked_scene_march_autograd takes them; source[0] and obj_poses may require grad and then get that
     function's gradient (pnr_baked_scene_backward_*)."""
-    source = tuple(source)
-    if len(source) not in (1, 7) or not isinstance(source[0], torch.Tensor):
-        raise ValueError("baked_scene_fit_autograd: source must be (rays,) or (poses, W, H, focal, c, z_near, z_far)")
+    source = _checked_source("baked_scene_fit_autograd", source)
     stored, volumes_meta = list(stored), [tuple(m) for m in volumes_meta]
     if not stored or len(stored) != len(volumes_meta) or any(len(m) != 6 for m in volumes_meta):
         raise ValueError("baked_scene_fit_autograd: stored and volumes_meta must list the same objects, each meta (degree, reso, c1, c2, "
                          "bits, index)")
     if not all(isinstance(s, torch.Tensor) and s.dtype == torch.float32 for s in stored):
         raise TypeError("baked_scene_fit_autograd: gradients exist for fp32 volumes only; fit the volume in fp32 and call half() afterwards")
-    if not isinstance(obj_poses, torch.Tensor) or obj_poses.dim() != 3 or tuple(obj_poses.shape[1:]) != (3, 4) \
-            or obj_poses.shape[0] != len(stored) or not obj_poses.is_floating_point():
-        raise ValueError(f"baked_scene_fit_autograd: obj_poses must be a float tensor ({len(stored)},3,4) object-to-world")
+    _check_obj_poses("baked_scene_fit_autograd", obj_poses, len(stored))
     unique, slots = [], []
     for s in stored:
         slot = next((k for k, u in enumerate(unique) if u is s), len(unique))

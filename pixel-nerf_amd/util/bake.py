@@ -150,6 +150,17 @@ def _tv_weights(what, degree, rgb, sigma, sh):
     return weights
 
 
+def _flat_rays(what, rays):
+    """rays (...,8), checked -> (the rays as (R,8) fp32, the leading shape the outputs take back)"""
+    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
+        raise ValueError(f"{what}: rays must be (...,8)")
+    return rays.reshape(-1, 8).float(), tuple(rays.shape[:-1])
+
+
+def _ray_result(rgb, depth, alpha, lead):
+    return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+
+
 def _camera_args(what, poses_c2w, W, H, focal, c, gt_rgb):
     """the camera of a render_views call, checked -> (W, H, focal, c) as the ops functions take them"""
     if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
@@ -299,10 +310,9 @@ class _Baked:
         name = type(self).__name__
         if self.dtype != torch.float32:
             raise TypeError(f"{name}.tv: {_FP32_ONLY}")
-        sparse = self._stored_name == "rows"
         with torch.no_grad():
             value32, _ = ops.baked_tv(self._stored(), self.degree, self.reso, _tv_weights(f"{name}.tv", self.degree, rgb, sigma, sh),
-                                      eps=eps, index=self.index if sparse else None, ids=self.ids if sparse else None)
+                                      eps=eps, index=self._index, ids=self._ids)
         return float(value32)
 
     def state_dict(self):
@@ -317,18 +327,14 @@ class _Baked:
         stored = state[cls._stored_name] if device is None else state[cls._stored_name].to(device)
         return cls(stored, state["c1"].tolist(), state["c2"].tolist(), float(state["skip_threshold"]))
 
+    _index = _ids = None  # what the ops functions take as index and ids: a SparseBakedVolume's, None for a dense volume
+
     def _march(self, source, step, bits, white_bkgd, terminate):
-        """source: (rays (R,8),), or the camera (poses, W, H, focal, c, z_near, z_far); which ops function marches follows from the
+        """source: (rays (R,8),), or the camera (poses, W, H, focal, c, z_near, z_far); ops.baked_march picks the function from the
         stored dtype, the degree and whether the volume is sparse"""
         from .. import ops
-        stored, sparse = self._stored(), self._stored_name == "rows"
-        kind = "half_" if stored.dtype == torch.float16 else "" if sparse or self.degree is None else "sh_"
-        kind = ("sparse_" if sparse else "") + kind
-        march = getattr(ops, f"baked_{kind}render" + ("" if len(source) == 1 else "_views"))
-        volume = (stored, self.degree) if kind else (stored,)  # (baked_render alone takes no degree)
-        if sparse:
-            return march(*source, *volume, self.index, bits, self.reso, self.c1, self.c2, step, white_bkgd=white_bkgd, terminate=terminate)
-        return march(*source, *volume, self.reso, self.c1, self.c2, step, bits=bits, white_bkgd=white_bkgd, terminate=terminate)
+        return ops.baked_march(source, self._stored(), self.degree, self.reso, self.c1, self.c2, step, bits=bits, index=self._index,
+                               white_bkgd=white_bkgd, terminate=terminate)
 
     @property
     def dtype(self):
@@ -354,13 +360,10 @@ class _Baked:
         :param terminate eps in [0, 1): a ray stops once its transmittance, checked every 64 samples, is <= eps (every channel and
         alpha move by at most eps, depth by at most eps far); None / 0: off
         :param skip march against the skip grid (exact at skip_threshold 0)"""
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError(f"{type(self).__name__}.render: rays must be (...,8)")
-        lead = tuple(rays.shape[:-1])
+        flat, lead = _flat_rays(f"{type(self).__name__}.render", rays)
         step, terminate, bits = self._march_args(step, terminate, skip)
         with torch.no_grad():
-            rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), step, bits, white_bkgd, terminate)
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+            return _ray_result(*self._march((flat,), step, bits, white_bkgd, terminate), lead)
 
     def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, step=None, white_bkgd=False,
                      terminate=None, skip=True):
@@ -377,35 +380,24 @@ class _Baked:
 
     def _march_diff(self, source, step, bits, white_bkgd, terminate):
         from .. import autograd
-        sparse = self._stored_name == "rows"
         return autograd.baked_march_rays_autograd(self._stored(), source, self.degree, self.reso, self.c1, self.c2, step, bits=bits,
-                                                  index=self.index if sparse else None, white_bkgd=white_bkgd, terminate=terminate)
+                                                  index=self._index, white_bkgd=white_bkgd, terminate=terminate)
 
     def render_diff(self, rays, step=None, white_bkgd=False, terminate=None, skip=True):
         """`render` with autograd to the RAYS: rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)), the bytes `render` gives,
         and a backward that hands dL/d rays to whatever made them (pnr_baked_ray_backward_rays: no atomics, the same bytes on every
         call; include/pixelnerf_hip.h, "Gradients of the baked march with respect to the RAYS").  The volume itself gets no gradient
         (`trainable()` is for that) and may be fp16.  step, terminate, skip: as render."""
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError(f"{type(self).__name__}.render_diff: rays must be (...,8)")
-        lead = tuple(rays.shape[:-1])
+        flat, lead = _flat_rays(f"{type(self).__name__}.render_diff", rays)
         step, terminate, bits = self._march_args(step, terminate, skip)
-        rgb, depth, alpha = self._march_diff((rays.reshape(-1, 8).float(),), step, bits, white_bkgd, terminate)
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+        return _ray_result(*self._march_diff((flat,), step, bits, white_bkgd, terminate), lead)
 
     def render_views_diff(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, white_bkgd=False, terminate=None, skip=True):
         """`render_views` without its epilogue and with autograd to the POSES: poses_c2w (NVt,4,4) -> DotMap(rgb (NVt,H,W,3), depth
         and alpha (NVt,H,W)), the bytes `render_views` gives; the backward is pnr_baked_ray_backward_views followed by
         ops.gen_rays_backward (the intrinsics are constants).  What `register` descends on."""
-        name = type(self).__name__
-        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
-            raise ValueError(f"{name}.render_views_diff: poses_c2w must be (NVt,4,4)")
-        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
-        if torch.is_tensor(focal):
-            focal = focal.flatten().tolist()
-            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
-        if torch.is_tensor(c):
-            c = c.flatten().tolist()
+        W, H, focal, c = _camera_args(f"{type(self).__name__}.render_views_diff", poses_c2w, W, H, focal, c, None)
+        NVt = poses_c2w.shape[0]
         step, terminate, bits = self._march_args(step, terminate, skip)
         rgb, depth, alpha = self._march_diff((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, bits, white_bkgd, terminate)
         return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
@@ -419,8 +411,7 @@ class _Baked:
         from .. import ops
         _check_field(what, "out", out, self._vis_shape(), nullable=True)
         step, terminate, bits = self._march_args(step, terminate, skip)
-        sparse = self._stored_name == "rows"
-        kw = dict(bits=bits, index=self.index if sparse else None, terminate=terminate, out=out)
+        kw = dict(bits=bits, index=self._index, terminate=terminate, out=out)
         with torch.no_grad():
             if len(source) == 1:
                 return ops.baked_visibility(source[0], self._stored(), self.degree, self.reso, self.c1, self.c2, step, **kw)
@@ -435,9 +426,7 @@ class _Baked:
         :param out a field of that shape from an earlier call: the result is max-accumulated into it and returned (batches, views)
         The same bytes on every call, whatever the order of the rays and however they are split into calls."""
         name = f"{type(self).__name__}.visibility"
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError(f"{name}: rays must be (...,8)")
-        return self._visibility(name, (rays.detach().reshape(-1, 8).float(),), step, terminate, skip, out)
+        return self._visibility(name, (_flat_rays(name, rays)[0].detach(),), step, terminate, skip, out)
 
     def visibility_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, terminate=None, skip=True, out=None):
         """`visibility` over every pixel of the views (ops.baked_visibility_views): the rays are regenerated in the kernel -- the bytes
@@ -761,6 +750,9 @@ class SparseBakedVolume(_Baked):
         self.rows, self.degree, self.index, self.ids, self.occupancy = rows, degree, index, ids, occupancy
         self.reso, self.c1, self.c2 = occupancy.reso, occupancy.c1, occupancy.c2
 
+    _index = property(lambda self: self.index)
+    _ids = property(lambda self: self.ids)
+
     @property
     def n_rows(self):
         return self.rows.shape[0]
@@ -880,9 +872,8 @@ class BakedScene:
         """the list ops.baked_scene_render takes"""
         objects = []
         for v, pose in zip(self.volumes, self.poses):
-            sparse = v._stored_name == "rows"
-            bits = v.occupancy.bits if skip or sparse else None
-            objects.append((v._stored(), v.degree, v.reso, v.c1, v.c2, pose, bits, v.index if sparse else None))
+            bits = v.occupancy.bits if skip or v._index is not None else None
+            objects.append((v._stored(), v.degree, v.reso, v.c1, v.c2, pose, bits, v._index))
         return objects
 
     def _march_args(self, step, terminate):
@@ -895,14 +886,10 @@ class BakedScene:
         :param terminate as BakedVolume.render: checked every 64 samples on the transmittance of the mixture
         :param skip march every dense volume against its skip grid (exact at skip_threshold 0); sparse volumes always do"""
         from .. import ops
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError("BakedScene.render: rays must be (...,8)")
-        lead = tuple(rays.shape[:-1])
+        flat, lead = _flat_rays("BakedScene.render", rays)
         step, terminate = self._march_args(step, terminate)
         with torch.no_grad():
-            rgb, depth, alpha = ops.baked_scene_render(rays.reshape(-1, 8).float(), self._objects(skip), step, white_bkgd=white_bkgd,
-                                                       terminate=terminate)
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+            return _ray_result(*ops.baked_scene_render(flat, self._objects(skip), step, white_bkgd=white_bkgd, terminate=terminate), lead)
 
     def render_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, gt_rgb=None, want_u8=False, step=None, white_bkgd=False,
                      terminate=None, skip=True):
@@ -946,13 +933,10 @@ class BakedScene:
         for this call -- it must be rigid, as the scene's are; the gradient is that of 12 free numbers per object, and a caller that
         builds the poses from rigid parameters (`moved_poses`) gets its projection from autograd.  The poses are kernel arguments by
         value: they are read to the host once per call.  step, terminate, skip: as render."""
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError("BakedScene.render_diff: rays must be (...,8)")
+        flat, lead = _flat_rays("BakedScene.render_diff", rays)
         obj_poses = self._obj_poses("render_diff", poses)
-        lead = tuple(rays.shape[:-1])
         step, terminate = self._march_args(step, terminate)
-        rgb, depth, alpha = self._march_diff((rays.reshape(-1, 8).float(),), obj_poses, step, white_bkgd, terminate, skip)
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+        return _ray_result(*self._march_diff((flat,), obj_poses, step, white_bkgd, terminate, skip), lead)
 
     def render_views_diff(self, poses_c2w, W, H, focal, z_near, z_far, c=None, obj_poses=None, step=None, white_bkgd=False, terminate=None,
                           skip=True):
@@ -996,21 +980,17 @@ class TrainableBaked(torch.nn.Module):
     def _march(self, source, step, white_bkgd, terminate, skip, source_grad=False):
         from .. import autograd
         v = self._source
-        sparse = v._stored_name == "rows"
-        step, terminate, bits = _Baked._march_args(v, step, terminate, skip or sparse)
+        step, terminate, bits = _Baked._march_args(v, step, terminate, skip or v._index is not None)
         march = autograd.baked_march_rays_autograd if source_grad else autograd.baked_march_autograd
-        return march(self.stored, source, v.degree, v.reso, v.c1, v.c2, step, bits=bits, index=v.index if sparse else None,
-                     white_bkgd=white_bkgd, terminate=terminate)
+        return march(self.stored, source, v.degree, v.reso, v.c1, v.c2, step, bits=bits, index=v._index, white_bkgd=white_bkgd,
+                     terminate=terminate)
 
     def forward(self, rays, step=None, white_bkgd=False, terminate=None, skip=False, ray_grad=False):
         """rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)) as `render`, differentiable with respect to `stored`.
         ray_grad=True: differentiable with respect to the rays as well (pnr_baked_ray_backward_rays); the default refuses rays that
         require grad."""
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError("TrainableBaked.forward: rays must be (...,8)")
-        lead = tuple(rays.shape[:-1])
-        rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), step, white_bkgd, terminate, skip, source_grad=bool(ray_grad))
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+        flat, lead = _flat_rays("TrainableBaked.forward", rays)
+        return _ray_result(*self._march((flat,), step, white_bkgd, terminate, skip, source_grad=bool(ray_grad)), lead)
 
     def forward_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, step=None, white_bkgd=False, terminate=None, skip=False,
                       pose_grad=False):
@@ -1018,14 +998,8 @@ class TrainableBaked(torch.nn.Module):
         -> DotMap(rgb (NVt,H,W,3), depth (NVt,H,W), alpha (NVt,H,W)), differentiable with respect to `stored`.  pose_grad=True:
         differentiable with respect to the poses as well (pnr_baked_ray_backward_views, then ops.gen_rays_backward); the default
         refuses poses that require grad."""
-        if not isinstance(poses_c2w, torch.Tensor) or poses_c2w.dim() != 3 or tuple(poses_c2w.shape[1:]) != (4, 4):
-            raise ValueError("TrainableBaked.forward_views: poses_c2w must be (NVt,4,4)")
-        W, H, NVt = int(W), int(H), poses_c2w.shape[0]
-        if torch.is_tensor(focal):
-            focal = focal.flatten().tolist()
-            focal = focal[0] if len(focal) == 1 else (focal[0], focal[1])
-        if torch.is_tensor(c):
-            c = c.flatten().tolist()
+        W, H, focal, c = _camera_args("TrainableBaked.forward_views", poses_c2w, W, H, focal, c, None)
+        NVt = poses_c2w.shape[0]
         rgb, depth, alpha = self._march((poses_c2w.float(), W, H, focal, c, z_near, z_far), step, white_bkgd, terminate, skip,
                                         source_grad=bool(pose_grad))
         return DotMap(rgb=rgb.reshape(NVt, H, W, 3), depth=depth.reshape(NVt, H, W), alpha=alpha.reshape(NVt, H, W))
@@ -1040,9 +1014,8 @@ class TrainableBaked(torch.nn.Module):
         :param sh weighs every channel of the basis rows k >= 1; None: the DC weights"""
         from .. import autograd
         v = self._source
-        sparse = v._stored_name == "rows"
         return autograd.baked_tv_autograd(self.stored, v.degree, v.reso, _tv_weights("TrainableBaked.tv", v.degree, rgb, sigma, sh), eps=eps,
-                                          index=v.index if sparse else None, ids=v.ids if sparse else None)
+                                          index=v._index, ids=v._ids)
 
     def volume(self):
         """a fresh volume of the current values: checked as its constructor checks (a non-finite value raises ValueError) and with
@@ -1061,8 +1034,7 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
     the step's loss is mse + module.tv(...) (`losses` keeps reporting the mse alone); with all of them 0 -- the default -- no TV call
     is made.
     -> (the fitted volume -- a new one, `volume` is unchanged --, losses: the `steps` batch losses as floats, read once at the end)"""
-    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-        raise ValueError("fit: rays must be (...,8)")
+    flat, _ = _flat_rays("fit", rays)
     if not isinstance(target_rgb, torch.Tensor) or tuple(target_rgb.shape) != tuple(rays.shape[:-1]) + (3,):
         raise ValueError(f"fit: target_rgb must be {tuple(rays.shape[:-1]) + (3,)}, got "
                          f"{tuple(target_rgb.shape) if isinstance(target_rgb, torch.Tensor) else type(target_rgb).__name__}")
@@ -1072,7 +1044,7 @@ def fit(volume, rays, target_rgb, steps=200, lr=1e-2, batch=4096, seed=0, step=N
     module = volume.trainable()
     prior = dict(rgb=tv_rgb, sigma=tv_sigma, sh=tv_sh, eps=tv_eps)
     use_prior = any(w > 0 for w in _tv_weights("fit", volume.degree, tv_rgb, tv_sigma, tv_sh))
-    rays, target = rays.detach().reshape(-1, 8).float(), target_rgb.detach().reshape(-1, 3).float()
+    rays, target = flat.detach(), target_rgb.detach().reshape(-1, 3).float()
     R = rays.shape[0]
     if R == 0:
         raise ValueError("fit: no rays")
@@ -1117,8 +1089,7 @@ def fit_coarse_to_fine(volume, rays, target_rgb, stages, prune=None, **fit_kwarg
             raise ValueError(f"{what}: prune needs a threshold that is a number and a dilate in [0, 4], got {prune!r}")
     if "steps" in fit_kwargs:
         raise ValueError(f"{what}: the steps belong to the stages")
-    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-        raise ValueError(f"{what}: rays must be (...,8)")
+    flat = _flat_rays(what, rays)[0].detach()
     seed = int(fit_kwargs.pop("seed", 0))
     reso, sparse = tuple(volume.reso), volume._stored_name == "rows"
     for k, (new, _) in enumerate(stages):  # the chain of grids, walked on the host first
@@ -1127,7 +1098,6 @@ def fit_coarse_to_fine(volume, rays, target_rgb, stages, prune=None, **fit_kwarg
                 _sparse_refinement(f"{what}: stage {k}", reso, new)
             reso = new
         sparse = sparse or prune is not None
-    flat = rays.detach().reshape(-1, 8).float()
     all_losses = []
     for k, (new, steps) in enumerate(stages):
         if new is not None and new != tuple(volume.reso):
@@ -1200,12 +1170,9 @@ class TrainableScene(torch.nn.Module):
         """world rays (...,8) -> DotMap(rgb (...,3), depth (...), alpha (...)) as `BakedScene.render`, differentiable with respect to
         the parameters; rays, and `poses` (None: the scene's own; else (N,3,4) or (N,4,4) object-to-world, as render_diff takes
         them), get their gradient when they require it."""
-        if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-            raise ValueError("TrainableScene.forward: rays must be (...,8)")
+        flat, lead = _flat_rays("TrainableScene.forward", rays)
         obj_poses = self._source._obj_poses("trainable().forward", poses)
-        lead = tuple(rays.shape[:-1])
-        rgb, depth, alpha = self._march((rays.reshape(-1, 8).float(),), obj_poses, step, white_bkgd, terminate, skip)
-        return DotMap(rgb=rgb.reshape(*lead, 3), depth=depth.reshape(lead), alpha=alpha.reshape(lead))
+        return _ray_result(*self._march((flat,), obj_poses, step, white_bkgd, terminate, skip), lead)
 
     def forward_views(self, poses_c2w, W, H, focal, z_near, z_far, c=None, obj_poses=None, step=None, white_bkgd=False, terminate=None,
                       skip=False):
@@ -1227,9 +1194,8 @@ class TrainableScene(torch.nn.Module):
             if slot is None or slot in seen:
                 continue
             seen.add(slot)
-            sparse = v._stored_name == "rows"
             term = autograd.baked_tv_autograd(self.stored[slot], v.degree, v.reso, _tv_weights("TrainableScene.tv", v.degree, rgb, sigma, sh),
-                                              eps=eps, index=v.index if sparse else None, ids=v.ids if sparse else None)
+                                              eps=eps, index=v._index, ids=v._ids)
             total = term if total is None else total + term
         return total
 
@@ -1261,8 +1227,7 @@ def fit_scene(scene, rays, target_rgb, objects=None, steps=200, lr=1e-2, batch=4
     -> (the fitted scene -- a new one, `scene` and its volumes are unchanged --, losses: the `steps` batch losses as floats)"""
     if not isinstance(scene, BakedScene):
         raise TypeError(f"fit_scene: expected a BakedScene, got {type(scene).__name__}")
-    if not isinstance(rays, torch.Tensor) or rays.dim() < 1 or rays.shape[-1] != 8:
-        raise ValueError("fit_scene: rays must be (...,8)")
+    flat, _ = _flat_rays("fit_scene", rays)
     if not isinstance(target_rgb, torch.Tensor) or tuple(target_rgb.shape) != tuple(rays.shape[:-1]) + (3,):
         raise ValueError(f"fit_scene: target_rgb must be {tuple(rays.shape[:-1]) + (3,)}, got "
                          f"{tuple(target_rgb.shape) if isinstance(target_rgb, torch.Tensor) else type(target_rgb).__name__}")
@@ -1273,7 +1238,7 @@ def fit_scene(scene, rays, target_rgb, objects=None, steps=200, lr=1e-2, batch=4
     degree = scene.volumes[0].degree
     prior = dict(rgb=tv_rgb, sigma=tv_sigma, sh=tv_sh, eps=tv_eps)
     use_prior = any(w > 0 for w in _tv_weights("fit_scene", degree, tv_rgb, tv_sigma, tv_sh))
-    rays, target = rays.detach().reshape(-1, 8).float(), target_rgb.detach().reshape(-1, 3).float()
+    rays, target = flat.detach(), target_rgb.detach().reshape(-1, 3).float()
     R = rays.shape[0]
     if R == 0:
         raise ValueError("fit_scene: no rays")
