@@ -155,10 +155,11 @@ __device__ __forceinline__ void zero_acc(f32x16 (&a)[IT][JT]) {
 //   dY(fc_1) = G ;  d net = (fc_1^T G) . [net > 0] = dY(fc_0) ;  G += (fc_0^T d net) . [x > 0]
 template <typename P>
 __device__ __forceinline__ void bwd_block(f32x16 (&G)[IT][JT], char *smem, int b, Ring<P> &R, int NS, const BwdParams &q,
-                                          size_t off, const bool *valid, uint32_t a_rd0, uint32_t a_rd1, uint32_t a_wr,
+                                          size_t off, uint32_t a_rd0, uint32_t a_rd1, uint32_t a_wr,
                                           uint32_t mask_off, size_t mask_layer, long long rows_left, int wv, int lane) {
     constexpr bool DUMP = true;
-    // gradient dumps (operands of the weight-gradient GEMMs): copied out of the image behind the barrier, whole rows
+    // gradient dumps (operands of the weight-gradient GEMMs): copied out of the image behind the barrier, whole rows; rows beyond
+    // the last point stay out through dump_image's rows_left (no per-lane validity is needed here)
     const size_t off_tile = off - (size_t)(((lane & 31) * D_HID + (wv * IT) * 32 + (lane >> 5) * 16) * 2);
     __syncthreads();  // every wave is done reading the gradient image (previous GEMM)
     write_act<P, false, false>(G, smem, a_wr);
@@ -232,7 +233,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) bwd_kernel(const BwdParams q
         }
 #pragma unroll 1
         for (int b = N_BLOCKS - 1; b >= COMBINE_LAYER; --b)
-            bwd_block<P>(G, smem, b, R, NS, q, off_pooled, valid, a_rd0, a_rd1, a_wr, mask_pooled, mask_layer, rows_left, wv, lane);
+            bwd_block<P>(G, smem, b, R, NS, q, off_pooled, a_rd0, a_rd1, a_wr, mask_pooled, mask_layer, rows_left, wv, lane);
         // backward of the view mean (util.py:461-466): every view starts from G / NS.  That gradient is PARKED in a
         // per-workgroup scratch ([slot][thread]: every lane re-reads what it wrote, L2-resident) instead of 64 registers held
         // across the whole per-view loop -- the in-register form spilled 106 registers.
@@ -265,7 +266,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) bwd_kernel(const BwdParams q
             }
 #pragma unroll 1
             for (int b = COMBINE_LAYER - 1; b >= 0; --b)
-                bwd_block<P>(G, smem, b, R, NS, q, off_view, valid, a_rd0, a_rd1, a_wr,
+                bwd_block<P>(G, smem, b, R, NS, q, off_view, a_rd0, a_rd1, a_wr,
                              mask_pooled + (uint32_t)view * (uint32_t)q.ntiles * NTHREADS, mask_layer, rows_left, wv, lane);
             // ---- d z_lat = sum_b dY_b W_z[b] and d(code) = dY_0 W_in (resnetfc.py:147,175-180 backward): four more
             // transposed-stream GEMMs on gradient images this tile has just produced.  dY_2, dY_1 (= g_fc1[1], g_fc1[0])

@@ -383,6 +383,11 @@ def test_fused_chain_latent_and_input_gradients(dev, name, prec):
         assert torch.isfinite(got).all()
         err = (got - ref).abs().max().item()
         assert err <= 2e-5 * max(ref.abs().max().item(), 1e-12) + 1e-12, f"{what}: max err {err:.3e} vs scale {ref.abs().max().item():.3e}"
+    # and element by element against the float64 reference of the same four GEMMs, at its derived bound (tests/mlp16_ref.py)
+    import mlp16_ref as M
+    D = {"g_fc1": [M.from_storage(t, perm) for t in bd.g_fc1], "g_x0": M.from_storage(bd.g_x0, perm),
+         "d_zlat": bd.d_zlat.cpu().double(), "d_in_grad": bd.d_in.cpu().double()}
+    M.assert_within(M.tail_items(mf, D, inv_s, M.FMTS[prec]), f"{name} {prec}")
 
 
 @pytest.mark.parametrize("name", ["train_64_32", "srn_mini_64_128", "dtu_mini_64_128"])  # NS = 1 (SB = 4), 2, 3
