@@ -15,8 +15,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # experiment switch is compiled with -DPNR_VARIANT and reports a NEGATIVE ABI revision: load() refuses it unless the
 # process says PIXELNERF_ALLOW_VARIANT=1 (the A/B tools do) -- a stray -D can no longer yield a library that passes for the product
 LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelnerf_hip.so")
-SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_scatter.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip", "pnr_mesh.hip", "pnr_occupancy.hip", "pnr_meshfinish.hip", "pnr_baked.hip", "pnr_baked_grad.hip", "pnr_baked_scene.hip", "pnr_baked_tv.hip", "pnr_baked_visibility.hip", "pnr_baked_resample.hip"]
-HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_geom.h", "pnr_wave.h", "pnr_raysrc.h", "pnr_internal.h", "pnr_entry.h", "pnr_scatter_plan.h", "pnr_occgrid.h", "pnr_baked.h", "pnr_baked_grad.h", "pnr_mc_tables.inc", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
+SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_bwd_split.hip", "pnr_scatter.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip", "pnr_mesh.hip", "pnr_occupancy.hip", "pnr_meshfinish.hip", "pnr_baked.hip", "pnr_baked_grad.hip", "pnr_baked_scene.hip", "pnr_baked_tv.hip", "pnr_baked_visibility.hip", "pnr_baked_resample.hip"]
+HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_geom.h", "pnr_wave.h", "pnr_raysrc.h", "pnr_internal.h", "pnr_entry.h", "pnr_split_ops.h", "pnr_scatter_plan.h", "pnr_occgrid.h", "pnr_baked.h", "pnr_baked_grad.h", "pnr_mc_tables.inc", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
 ABI_VERSION = 12  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3

@@ -98,73 +98,19 @@ struct BwdParams {
     float *mv_ws;   // multi-view: per-workgroup scratch for the pooled gradient every view starts from ([slot][thread])
 };
 
-// relu masks: one 64-bit word per thread and layer from the forward kernel (bit (it*JT + jt)*16 + r = register r of the
-// thread's accumulator tile (it, jt) was positive); fetched BEFORE the GEMM whose result it gates.  (Reading the masks
-// from the 1 KiB dump rows instead cost the chain a third of its time: 592 -> 405 us for 49 152 points without them.)
-static_assert(IT * JT * 16 == 64, "one 64-bit mask word per thread");
-
-// acc = bit ? acc : 0
-__device__ __forceinline__ void apply_mask(f32x16 (&acc)[IT][JT], unsigned long long mk) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt) {
-            const uint32_t m16 = (uint32_t)(mk >> ((it * JT + jt) * 16)) & 0xffffu;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[it][jt][r] = (m16 >> r) & 1u ? acc[it][jt][r] : 0.f;
-        }
-}
-
-// G += bit ? t : 0
-__device__ __forceinline__ void masked_add(f32x16 (&G)[IT][JT], const f32x16 (&t)[IT][JT], unsigned long long mk) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt) {
-            const uint32_t m16 = (uint32_t)(mk >> ((it * JT + jt) * 16)) & 0xffffu;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) G[it][jt][r] += (m16 >> r) & 1u ? t[it][jt][r] : 0.f;
-        }
-}
-
-template <typename P>
-__device__ __forceinline__ void dump_only(const f32x16 (&acc)[IT][JT], char *dump_lane, const bool *valid) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt) {
-            if (!valid[jt]) continue;
-            const f32x16 &a = acc[it][jt];
-            char *d = dump_lane + (size_t)jt * 32 * (D_HID * 2) + it * 64;
-            *reinterpret_cast<typename P::T8 *>(d) = pack8<P, false>(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
-            *reinterpret_cast<typename P::T8 *>(d + 16) =
-                pack8<P, false>(a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15]);
-        }
-}
-
-__device__ __forceinline__ void zero_acc(f32x16 (&a)[IT][JT]) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[it][jt][r] = 0.f;
-}
-
 // reverse of one residual block (resnetfc.py:55-62):  given G = dL/d(x + fc_1(relu(fc_0(relu(x))))),
 //   dY(fc_1) = G ;  d net = (fc_1^T G) . [net > 0] = dY(fc_0) ;  G += (fc_0^T d net) . [x > 0]
 template <typename P>
 __device__ __forceinline__ void bwd_block(f32x16 (&G)[IT][JT], char *smem, int b, Ring<P> &R, int NS, const BwdParams &q,
                                           size_t off, uint32_t a_rd0, uint32_t a_rd1, uint32_t a_wr,
                                           uint32_t mask_off, size_t mask_layer, long long rows_left, int wv, int lane) {
-    constexpr bool DUMP = true;
     // gradient dumps (operands of the weight-gradient GEMMs): copied out of the image behind the barrier, whole rows; rows beyond
     // the last point stay out through dump_image's rows_left (no per-lane validity is needed here)
     const size_t off_tile = off - (size_t)(((lane & 31) * D_HID + (wv * IT) * 32 + (lane >> 5) * 16) * 2);
     __syncthreads();  // every wave is done reading the gradient image (previous GEMM)
     write_act<P, false, false>(G, smem, a_wr);
     __syncthreads();
-    if (DUMP) dump_image<MT>(smem, LDS_A, q.g_fc1[b] + off_tile, rows_left, wv, lane);
+    dump_image<MT>(smem, LDS_A, q.g_fc1[b] + off_tile, rows_left, wv, lane);
     f32x16 t[IT][JT];
     // mask_off / mask_layer: this thread's word within a layer of q.d_mask / words per layer (layer 2b: x, 2b+1: net)
     const unsigned long long mk_n = (q.d_mask + (size_t)(2 * b + 1) * mask_layer)[mask_off];
@@ -174,7 +120,7 @@ __device__ __forceinline__ void bwd_block(f32x16 (&G)[IT][JT], char *smem, int b
     __syncthreads();
     write_act<P, false, false>(t, smem, a_wr);
     __syncthreads();
-    if (DUMP) dump_image<MT>(smem, LDS_A, q.g_fc0[b] + off_tile, rows_left, wv, lane);
+    dump_image<MT>(smem, LDS_A, q.g_fc0[b] + off_tile, rows_left, wv, lane);
     const unsigned long long mk_a = (q.d_mask + (size_t)(2 * b) * mask_layer)[mask_off];
     zero_acc(t);
     gemm<P, AdvanceBwd>(t, smem, a_rd0, a_rd1, KS_BIG / 4, R, NS);

@@ -1,6 +1,6 @@
-// pnr_device.h -- device-side building blocks shared by the forward (pnr_mlp.hip) and backward
-// (pnr_bwd.hip, pnr_scatter.hip) fused network kernels: MFMA traits, 16-bit packing, the weight prefetch ring,
-// the tile GEMM, activation-image writes.  gfx950 only.
+// pnr_device.h -- device-side building blocks shared by the forward (pnr_mlp.hip, pnr_split.hip) and backward
+// (pnr_bwd.hip, pnr_bwd_split.hip, pnr_scatter.hip) fused network kernels: MFMA traits, 16-bit packing, the weight prefetch
+// ring, the tile GEMM, activation-image writes, the relu-mask gates of the backward chains, the output stage.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -365,6 +365,80 @@ __device__ __forceinline__ void add_bias(f32x16 (&acc)[IT][JT_], const float *bi
     }
 }
 
+
+// ---------------------------------------------------------------- pieces of the backward chains
+// (bwd_kernel, pnr_bwd.hip; bwd_split_kernel, pnr_bwd_split.hip)
+// relu masks: one 64-bit word per thread and layer from the forward kernel (bit (it*JT + jt)*16 + r = register r of the
+// thread's accumulator tile (it, jt) was positive); fetched BEFORE the GEMM whose result it gates.  (Reading the masks
+// from the 1 KiB dump rows instead cost the chain a third of its time: 592 -> 405 us for 49 152 points without them.)
+static_assert(IT * JT * 16 == 64, "one 64-bit mask word per thread");
+
+// acc = bit ? acc : 0
+__device__ __forceinline__ void apply_mask(f32x16 (&acc)[IT][JT], unsigned long long mk) {
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            const uint32_t m16 = (uint32_t)(mk >> ((it * JT + jt) * 16)) & 0xffffu;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[it][jt][r] = (m16 >> r) & 1u ? acc[it][jt][r] : 0.f;
+        }
+}
+
+// G += bit ? t : 0
+__device__ __forceinline__ void masked_add(f32x16 (&G)[IT][JT], const f32x16 (&t)[IT][JT], unsigned long long mk) {
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            const uint32_t m16 = (uint32_t)(mk >> ((it * JT + jt) * 16)) & 0xffffu;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) G[it][jt][r] += (m16 >> r) & 1u ? t[it][jt][r] : 0.f;
+        }
+}
+
+__device__ __forceinline__ void zero_acc(f32x16 (&a)[IT][JT]) {
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) a[it][jt][r] = 0.f;
+}
+
+// ---------------------------------------------------------------- output stage of the forward kernels
+// (eval_kernel, pnr_mlp.hip; eval_split_kernel, pnr_split.hip)
+// Output stage of a tile: thread p < MT sums the NW lin_out partials of point p (out_lds: [wave][point] 16-byte pieces), adds
+// lin_out's bias, applies the output activation and writes 16 bytes if the point exists.  SCALED: the partials are at a
+// power-of-two scale, undone (times sc_out) in front of the bias.  GUARD: bit 11 of *sat_bits = a non-finite output.
+template <int MT_, bool SCALED = false, bool GUARD = false>
+__device__ __forceinline__ void output_stage(const char *out_lds, int tid, int tile, const float *bout, float *out, long long P,
+                                             [[maybe_unused]] float sc_out = 1.f, [[maybe_unused]] uint32_t *sat_bits = nullptr) {
+    if (tid < MT_) {
+        const long long g = (long long)tile * MT_ + tid;
+        f32x4 s;
+        if constexpr (SCALED) {
+            s = *reinterpret_cast<const f32x4 *>(out_lds + tid * 16);
+#pragma unroll
+            for (int w = 1; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(out_lds + (w * MT_ + tid) * 16);
+            s = s * sc_out + *reinterpret_cast<const f32x4 *>(bout);
+        } else {
+            s = *reinterpret_cast<const f32x4 *>(bout);
+#pragma unroll
+            for (int w = 0; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(out_lds + (w * MT_ + tid) * 16);
+        }
+        // models.py:260-265: rgb = sigmoid(out[:3]), sigma = relu(out[3]).  (Spelled here, not in a function of its own: behind a
+        // call boundary hipcc orders the three exponentials differently in every instantiation of both kernels.)
+        f32x4 res = {1.f / (1.f + expf(-s[0])), 1.f / (1.f + expf(-s[1])), 1.f / (1.f + expf(-s[2])), fmaxf(s[3], 0.f)};
+        if (g < P) {
+            *reinterpret_cast<f32x4 *>(out + g * 4) = res;
+            if constexpr (GUARD) {
+                const float t = res[0] + res[1] + res[2] + res[3];
+                if (!(fabsf(t) <= 3.0e38f)) *sat_bits |= 1u << 11;  // NaN / inf output
+            }
+        }
+    }
+}
 
 }  // namespace pnr
 

@@ -20,7 +20,8 @@
 //   GEMM per layer   the same entries with split_gemm = 1: every product on gemm3_kernel (128x128-tile GEMM that splits its
 //                    fp32 operands into (head, tail) f16 pairs on the way into LDS, three f16 MFMAs per product)
 //   fused (default)  pnr_eval_ray_samples_split_train / pnr_mlp_backward_split: the launch sequence around the fused
-//                    split-operand kernels of pnr_split.hip (forward, data-gradient chain) and pnr_bwd.hip (weight gradients)
+//                    split-operand kernels of pnr_split.hip (forward), pnr_bwd_split.hip (data-gradient chain) and pnr_bwd.hip
+//                    (weight gradients)
 #include <hip/hip_runtime.h>
 
 #include "pnr_common.h"

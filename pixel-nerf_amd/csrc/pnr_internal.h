@@ -26,7 +26,7 @@ int eval_samples_split_train(const PnrScene *scene, const void *packed_split, co
                              float *rgbsigma, void *const *img_a, void *const *img_n, float *x5, void *masks, const PnrSplitAux *aux,
                              hipStream_t stream);
 
-// fused data-gradient chain of the fp32-class training path (bwd_split_kernel, pnr_split.hip): transposed (head, tail) weight
+// fused data-gradient chain of the fp32-class training path (bwd_split_kernel; defined in pnr_bwd_split.hip): transposed (head, tail) weight
 // streams packed from the raw parameters, relu masks of the TRAIN forward, g_out (P,4) unscaled + device [s, 1/s]; every layer's
 // output gradient leaves at scale s as (head | tail) 16-bit rows in storage order (g_fc1[b] = dY of blocks[b].fc_1 = gradient of
 // the stream behind block b, g_fc0[b] = dY of blocks[b].fc_0, g_x0 = gradient of the stream entering block 0; b < 3 and g_x0:

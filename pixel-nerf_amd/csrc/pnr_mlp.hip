@@ -23,15 +23,11 @@
 #include "pnr_internal.h"
 #include "pnr_layout.h"
 
-// table-lookup batch sizes of the 96-point tile (points in flight per wave; 12 points per wave and table)
-#ifndef PNR_GB0
-#define PNR_GB0 6   // tile start: no accumulator is live
-#endif
-#ifndef PNR_GB12
-#define PNR_GB12 4  // inside blocks 0-1: the residual stream is live
-#endif
-
 namespace pnr {
+
+// table-lookup batch sizes of the 96-point tile (points in flight per wave; 12 points per wave and table)
+constexpr int GB0 = 6;   // tile start: no accumulator is live
+constexpr int GB12 = 4;  // inside blocks 0-1: the residual stream is live
 
 // bilinear lookup: wave handles points wave*8..+7; lane handles channels 8*lane..+7
 template <typename P, bool TRAIN, int GB, typename TL>
@@ -171,18 +167,17 @@ __device__ __forceinline__ void add_from_z(f32x16 (&x)[IT][JT_], const char *sme
 
 // one residual block (+ the lin_z of the next block when with_z):
 //   net = fc_0(relu(x)); x += fc_1(relu(net)) [+ lin_z[b+1](z)]       resnetfc.py:55-62,174-182
-template <typename P, bool TIMING, bool TRAIN, bool FOLD, typename TL, bool MV_PARK = false>
+template <typename P, bool TIMING, bool TRAIN, bool FOLD, typename TL>
 __device__ __forceinline__ void res_block(f32x16 (&x)[IT][TL::JT], char *smem, int b, bool with_z, Ring<P> &R,
                                           int NS, const float *bias_lane, uint32_t a_rd0, uint32_t a_rd1,
                                           uint32_t z_rd0, uint32_t z_rd1, uint32_t a_wr, int tid,
                                           unsigned long long *tim, unsigned long long &tlast,
                                           const EvalParams &q, size_t dump_off, const bool *valid, int wv, int lane,
-                                          uint32_t mask_off = 0, size_t mask_layer = 0, long long rows_left = 0, f32x4 *park = nullptr, bool park_first = true, bool park_last = true, float park_inv = 1.f, bool park_max = false) {
+                                          uint32_t mask_off = 0, size_t mask_layer = 0, long long rows_left = 0) {
     typedef Advance<0, FOLD ? RS_VIEW_END_F : RS_VIEW_END, FOLD ? RS_TOTAL_F : RS_TOTAL> ADV;
     constexpr int JT = TL::JT;
     // dump_off: byte offset of this lane's 32-byte slot in a (rows,512) 16-bit dump array
     // mask_off / mask_layer: this thread's word within a layer of q.d_mask / words per layer (layer 2b: x, 2b+1: net)
-    // park (multi-view, last per-view block only): this thread's slots of the parked running view sum (see eval_kernel)
     __syncthreads();  // every wave is done reading LDS_A (previous fc_1)
     PNR_T(PH_BAR1);
     // training dumps: relu bit masks from the registers, the rows themselves copied out of the image behind the barrier
@@ -206,41 +201,12 @@ __device__ __forceinline__ void res_block(f32x16 (&x)[IT][TL::JT], char *smem, i
     PNR_T(PH_BAR4);
     if constexpr (TRAIN) dump_image<TL::MT>(smem, TL::LDS_A, q.d_n[b] + dump_tile, rows_left, wv, lane);
     add_bias<false>(x, bias_lane, 2 + 2 * b);
-    // multi-view pooling: the running sum of the previous views comes back from its scratch UNDER this GEMM (`net` is dead,
-    // its registers hold the loads in flight), so the view boundary costs no exposed memory round trip
-    f32x4 parked[(MV_PARK ? IT * JT * 4 : 1)];
-    if constexpr (MV_PARK) {
-        if (park && !park_first) {
-#pragma unroll
-            for (int i = 0; i < IT * JT * 4; ++i) parked[i] = park[i * NTHREADS];  // [slot][thread]: 1 KiB per wave-instruction
-        }
-    }
     gemm<P, ADV>(x, smem, a_rd0, a_rd1, KS_BIG / 4, R, NS);
-    if constexpr (MV_PARK) {
-        if (park) {
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int i = (it * JT + jt) * 4 + k;
-                        f32x4 v = {x[it][jt][4 * k], x[it][jt][4 * k + 1], x[it][jt][4 * k + 2], x[it][jt][4 * k + 3]};
-                        if (!park_first) {
-                            if (park_max) { v[0] = fmaxf(parked[i][0], v[0]); v[1] = fmaxf(parked[i][1], v[1]); v[2] = fmaxf(parked[i][2], v[2]); v[3] = fmaxf(parked[i][3], v[3]); }
-                            else v += parked[i];
-                        }
-                        if (!park_last) park[i * NTHREADS] = v;
-                        else if (!park_max) v *= park_inv;
-                        x[it][jt][4 * k] = v[0]; x[it][jt][4 * k + 1] = v[1]; x[it][jt][4 * k + 2] = v[2]; x[it][jt][4 * k + 3] = v[3];
-                    }
-        }
-    }
     if (with_z) {
         if constexpr (FOLD) {  // lin_z[b+1](z) = bilinear lookup in table b+1 (LDS_Z is free: its last readers ran before fc_0)
             PNR_T(PH_GEMM_FC1_Z);
             if constexpr (TL::SINGLE_IMAGE) __syncthreads();  // the rows land in the image fc_1 has just been reading
-            gather_table<P, TL::SINGLE_IMAGE ? PNR_GB12 : 2, TL>(q, smem, wv, lane, b + 1);  // the residual stream is live here: smaller batches
+            gather_table<P, TL::SINGLE_IMAGE ? GB12 : 2, TL>(q, smem, wv, lane, b + 1);  // the residual stream is live here: smaller batches
             __syncthreads();
             add_from_z<P>(x, smem, a_wr - TL::LDS_A + TL::LDS_Z);
             PNR_T(PH_TABLE);
@@ -302,15 +268,14 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_kernel(const EvalParams
         bool valid[JT];
 #pragma unroll
         for (int jt = 0; jt < JT; ++jt) valid[jt] = (long long)tile * MT + jt * 32 + pl < q.P;
-        // training + multi-view: the running view sum is parked (simple read-modify-write at the view boundary, as in
-        // pnr_split.hip) -- with the dump bookkeeping live as well, the in-register form spilled 76 registers
+        // pooling over the source views: util.combine_interleaved's mean, or (network flag word, pnr_layout.h) its "max".
+        // Inference keeps the running view sum in 64 live registers (xsum).  The instantiation then sits at the 256-register
+        // limit and spills 20-40 registers to scratch OUTSIDE the GEMM loops; parking the sum in the L2-resident scratch
+        // instead, plainly or prefetched under the last fc_1, measured 2.7-4 % and 4-8 % SLOWER on the same box
+        // (profiles/r02_mv_pooling_ab.txt), so the registers stay.  Training parks it (simple read-modify-write at the view
+        // boundary, as in pnr_split.hip): with the dump bookkeeping live as well, the in-register form spilled 76 registers.
         [[maybe_unused]] constexpr bool PARK_SUM = MV && TRAIN;
-        // pooling over the source views: util.combine_interleaved's mean, or (network flag word, pnr_layout.h) its "max"
         [[maybe_unused]] const bool cmax = MV && (reinterpret_cast<const int *>(q.bout)[BOUT_FLAGS_INDEX] & 1) != 0;
-        // multi-view: running view sum in 64 live registers.  The instantiation then sits at the 256-register limit and spills
-        // 20-40 registers to scratch OUTSIDE the GEMM loops; the spill-free alternatives (-DPNR_MV_PARK: sum parked in an
-        // L2-resident scratch, simple or prefetched under the last fc_1) measured 2.7-4 % and 4-8 % SLOWER on the same box
-        // (profiles/r02_mv_pooling_ab.txt), so the registers stay.
         [[maybe_unused]] f32x16 xsum[(MV && !PARK_SUM) ? IT : 1][(MV && !PARK_SUM) ? JT : 1];
         const size_t dump_pooled = (((size_t)tile * MT + pl) * D_HID + (wv * IT) * 32 + h * 16) * 2;
         // relu bit masks (training): [layer][view][tile][thread] words; pooled layers use view slot 0
@@ -333,7 +298,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_kernel(const EvalParams
                     *reinterpret_cast<u32x4 *>(q.d_in + (((long long)view * q.P + g) * D_IN_PAD + chunk * 8) * 2) =
                         *reinterpret_cast<const u32x4 *>(smem + LDS_IN + row * ROW_IN + chunk * 16);
             }
-            if constexpr (FOLD) gather_table<P, TL::SINGLE_IMAGE ? PNR_GB0 : (MV ? 2 : 4), TL>(q, smem, wv, lane, 0);
+            if constexpr (FOLD) gather_table<P, TL::SINGLE_IMAGE ? GB0 : (MV ? 2 : 4), TL>(q, smem, wv, lane, 0);
             else gather<P, TRAIN, MV ? 2 : 4, TL>(q, smem, wv, lane, tile, view);  // multi-view also holds the view sum
             __syncthreads();
             PNR_T(PH_GATHER);
@@ -436,16 +401,7 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_kernel(const EvalParams
         PNR_T(PH_LIN_OUT);
         __syncthreads();
         PNR_T(PH_BAR_OUT);
-        if (tid < MT) {
-            const long long g = (long long)tile * MT + tid;
-            f32x4 s = *reinterpret_cast<const f32x4 *>(q.bout);
-#pragma unroll
-            for (int w = 0; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(smem + LDS_OUT + (w * MT + tid) * 16);
-            // models.py:260-265: rgb = sigmoid(out[:3]), sigma = relu(out[3])
-            f32x4 res = {1.f / (1.f + expf(-s[0])), 1.f / (1.f + expf(-s[1])), 1.f / (1.f + expf(-s[2])),
-                         fmaxf(s[3], 0.f)};
-            if (g < q.P) *reinterpret_cast<f32x4 *>(q.out + g * 4) = res;
-        }
+        output_stage<MT>(smem + LDS_OUT, tid, tile, q.bout, q.out, q.P);
         PNR_T(PH_FINAL);
     }
 }

@@ -26,7 +26,7 @@
 // the chip holds 1.99 GHz under the new core against 1.88 GHz under the old one and needs 3 % fewer cycles: sn64 +9.9 %, srn_car
 // +6.8 %, DTU +7.4 % same-box (profiles/r07_split_kernel_ab.txt).
 //
-// Kernels of this file:
+// The kernel of this file:
 //   eval_split_kernel<RAYS, MV, TIMING, TRAIN, GUARD, SC>   the fused network (SC: the stream-scale / range-probe forms, below).  GUARD = the fp16-range guard (PnrSplitAux.sat_flag): the
 //                                                same bits, plus one flag bit per layer whose operand image received a value >= 65504.
 //                                                TRAIN = the fp32-class TRAINING forward: the same launch also
@@ -34,11 +34,9 @@
 //                                                relu(net): the operands of the weight gradients), writes 1-bit relu masks and
 //                                                the stream in front of lin_out; the inference instantiations compile to the
 //                                                code they had before the flag existed.
-//   bwd_split_kernel<MV>                         the fused data-gradient chain behind it: all 15 transposed products of a network
-//                                                (transposed head / tail streams, gradient of the stream in the accumulators,
-//                                                gradient images copied out the same way, d z_lat / d code as fp32 rows).
-//   pack_weights_bwd_split_kernel                its weight streams, from the raw parameters.
-// The weight gradients over those images are dw_split_kernel (pnr_bwd.hip); host side: pnr_f32.hip (pnr_*_split_train).
+// What it shares with the data-gradient chain behind it (bwd_split_kernel, pnr_bwd_split.hip) -- the LDS map, the ring, the
+// 32x32x16 GEMM, the (head, tail) split -- is pnr_split_ops.h.  The weight gradients over the dumped images are dw_split_kernel
+// (pnr_bwd.hip); host side of the training path: pnr_f32.hip (pnr_*_split_train).
 #include <hip/hip_runtime.h>
 
 #include "pnr_common.h"
@@ -46,199 +44,9 @@
 #include "pnr_entry.h"
 #include "pnr_internal.h"
 #include "pnr_layout.h"
+#include "pnr_split_ops.h"
 
 namespace pnr {
-
-typedef Prec<PNR_PREC_F16> PH;
-typedef PH::T8 h8;
-
-// The split kernels are generic in the wave count (stage_own, gemm_split_rot, the geometry loop, the own-K packing: IT = 4, BODIES = 2
-// at NW = 4), but only the 8-wave form is parity-tested; the 4-wave build exists for timing (profiles/r05_split_gemm_ubench.txt: -13 %)
-// and has to ask for itself.
-#if !defined(PNR_VARIANT)
-static_assert(NW == 8, "pnr_split.hip: the product build is 8 waves per workgroup (other wave counts: variant builds, timing only)");
-#endif
-
-// LDS map: two activation images (head / tail), two lin_in operand images, corner metadata, lin_out partials.
-// The fp32 table rows (2 KiB + 16 B pad per point) are looked up into the space of the two activation images
-// while those are free (tile start, and after fc_1 of blocks 0-1 has finished reading).
-template <int MT_> struct SplitTileT {
-    static_assert(MT_ == 64, "64-point tiles");
-    static constexpr int MT = MT_, JT = MT_ / 32;
-    static constexpr int A_HI = 0;
-    static constexpr int A_LO = MT * ROW_ACT;             // 66,560 (64)
-    static constexpr int LDS_IN = 2 * MT * ROW_ACT;        // 133,120 (head image of the lin_in operand)
-    static constexpr int IN_LO_DELTA = MT * ROW_IN;        // tail image right behind it
-    static constexpr int LDS_META = LDS_IN + 2 * MT * ROW_IN;
-    static constexpr int LDS_OUT = LDS_META + MT * 32;
-    static constexpr int LDS_TOTAL = LDS_OUT + NW * MT * 16;  // 161,792 B
-    static constexpr int ROW_TAB = D_HID * 4 + 16;          // fp32 table row: 2064 B (129 16-B slots: conflict-free)
-    static constexpr int LDS_Z = 0;                         // (geometry_item only needs LDS_IN / LDS_META)
-    static_assert(MT * ROW_TAB <= LDS_IN, "table image must fit in the space of the two activation images");
-    static_assert(LDS_TOTAL <= 160 * 1024, "LDS budget");
-};
-
-struct SplitRing {
-    h8 h[4][IT], l[4][IT];
-    const char *base_h, *base_l;  // this wave's head / tail stream + lane*16
-    int pf_rs, pf_view;
-};
-
-// prefetch cursor: the per-view segment [0, RS_VIEW_END_F) is consumed NS times, then the pooled tail, then wrap
-__device__ __forceinline__ void ring_advance(SplitRing &R, int NS) {
-    int rs = R.pf_rs + 4, v = R.pf_view;
-    if (rs == RS_VIEW_END_F && v + 1 < NS) { v += 1; rs = 0; }
-    else if (rs == RS_TOTAL_F) { rs = 0; v = 0; }
-    R.pf_rs = rs; R.pf_view = v;
-}
-
-// the fp32-class BACKWARD chain (bwd_split_kernel below) walks a transposed stream in the layout of pnr_layout.h's backward
-// stream: pooled head [0, BRS_HEAD_END) once, then the per-view segment [BRS_HEAD_END, BSRS_TOTAL) NS times, then wrap
-// (lin_out^T, fc_1[4]^T fc_0[4]^T fc_1[3]^T fc_0[3]^T | fc_1[2]^T ... fc_0[0]^T, lin_z[2]^T lin_z[1]^T lin_z[0]^T, lin_in^T)
-constexpr int BSRS_TOTAL = BRS_TOTAL;  // 424
-static_assert(BSRS_TOTAL % 4 == 0, "ring depth 4 needs aligned segments");
-constexpr size_t BSPACKED_BYTES = (size_t)BSRS_TOTAL * IT * 1024 * NW;  // one blob (head or tail): 5,308,416 B
-struct SplitAdvFwd {
-    static __device__ __forceinline__ void step(SplitRing &R, int NS) { ring_advance(R, NS); }
-};
-struct SplitAdvBwd {
-    static __device__ __forceinline__ void step(SplitRing &R, int NS) {
-        int rs = R.pf_rs + 4, v = R.pf_view;
-        if (rs == BSRS_TOTAL) {
-            if (v + 1 < NS) { v += 1; rs = BRS_HEAD_END; }
-            else { rs = 0; v = 0; }
-        }
-        R.pf_rs = rs; R.pf_view = v;
-    }
-};
-
-__device__ __forceinline__ f32x16 mf(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-// acc[it][jt] += (Wh + Wl)(Xh + Xl) without the tail-tail term; B rows at bhi0 + jt*jstride (+ lo_delta for the tails)
-template <int JT, typename ADV = SplitAdvFwd>
-__device__ __forceinline__ void gemm_split(f32x16 (&acc)[IT][JT], const char *smem, uint32_t bhi0, uint32_t jstride,
-                                           uint32_t lo_delta, int nbody, SplitRing &R, int NS) {
-    h8 bh[2][JT], bl[2][JT];
-#pragma unroll
-    for (int jt = 0; jt < JT; ++jt) {
-        bh[0][jt] = lds8<PH>(smem, bhi0 + jt * jstride);
-        bl[0][jt] = lds8<PH>(smem, bhi0 + jt * jstride + lo_delta);
-    }
-#pragma unroll 1
-    for (int body = 0; body < nbody; ++body) {
-        const size_t pf = (size_t)R.pf_rs * (IT * 1024);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int cur = j & 1;
-#pragma unroll
-            for (int jt = 0; jt < JT; ++jt) {
-                bh[cur ^ 1][jt] = lds8<PH>(smem, bhi0 + jt * jstride + (j + 1) * 32);
-                bl[cur ^ 1][jt] = lds8<PH>(smem, bhi0 + jt * jstride + lo_delta + (j + 1) * 32);
-            }
-            h8 ah[IT], al[IT];
-#pragma unroll
-            for (int it = 0; it < IT; ++it) { ah[it] = R.h[j][it]; al[it] = R.l[j][it]; }
-            // the three products of one accumulator are spread over the step so that consecutive MFMAs are independent
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt) acc[it][jt] = mf(ah[it], bh[cur][jt], acc[it][jt]);
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt) acc[it][jt] = mf(ah[it], bl[cur][jt], acc[it][jt]);
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt) acc[it][jt] = mf(al[it], bh[cur][jt], acc[it][jt]);
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                R.h[j][it] = gload8<PH>(R.base_h + pf + j * (IT * 1024) + it * 1024);
-                R.l[j][it] = gload8<PH>(R.base_l + pf + j * (IT * 1024) + it * 1024);
-            }
-            // Issue order of one k-step, pinned (round 3): hipcc batches the 16 refills of a loop body behind its last MFMA and
-            // clusters the LDS reads; here every LDS read of the next step's B fragments follows ONE MFMA and every weight
-            // refill follows TWO -- (M L) x 2JT, (M M G) x 2IT.  Same-box A/B on sn64 / srn_car / DTU: +2.7 ... +6 % in four
-            // runs (profiles/r03_split_kernel_ab.txt, which also lists the eleven other orders tried: -6 ... +4 %; the order
-            // matters here, unlike in the f16 kernel where the same kind of pinning measured -1.9 %).  Results unchanged.
-#pragma unroll
-            for (int i = 0; i < 2 * JT; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // 1 LDS read
-            }
-#pragma unroll
-            for (int i = 0; i < 2 * IT; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // 2 MFMAs
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // 1 VMEM read
-            }
-            if constexpr (3 * IT * JT - 2 * JT - 4 * IT > 0) __builtin_amdgcn_sched_group_barrier(0x008, 3 * IT * JT - 2 * JT - 4 * IT, 0);
-        }
-        bhi0 += 128;
-        ADV::step(R, NS);
-    }
-}
-
-// head / tail of 8 fp32 values (optionally through relu); MODE.FP16_OVFL is set: heads saturate at 65504.
-// tail = f16(v - head): one v_fma_mix{lo,hi}_f16 per value (fp32 FMA of the f16 head taken straight out of its packed
-// register, times -1, plus v; result rounded once to f16) -- the same bits as convert-back + subtract + convert
-// (v - head is exact in fp32), 5 VALU operations per pair instead of 8.
-// GUARD: `amax` (a packed f16 pair) follows the largest HEAD produced, one v_pk_maximum3_f16 per FOUR values (gfx950; the
-// IEEE-2019 maximum: a NaN head sticks): the fp16-range guard (PnrSplitAux.sat_flag).  Half the VALU cost of following the
-// fp32 inputs with v_max3_f32 (round 5), which is what lets the guard run on every inference call (round 6).  Heads are >= 0
-// behind the relu, so no magnitudes are needed; a head of 65504 means v >= 65488 (round to nearest): the guard fires 16 below
-// the exact saturation point.
-template <bool RELU, bool GUARD = false>
-__device__ __forceinline__ void split8(const float (&v)[8], h8 &hi, h8 &lo, [[maybe_unused]] uint32_t *amax = nullptr) {
-    static_assert(RELU || !GUARD, "the guard follows relu'd heads");
-    u32x4 uh, ul;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f32x2 p = {v[2 * k], v[2 * k + 1]};
-        if (RELU) {
-            // one v_med3_f32 per value: median(v, 0, FLT_MAX) = max(v, 0) for every finite v (the head saturates at 65504 anyway;
-            // with +inf as the upper bound LLVM folds the median back into the two-instruction maxnum).  NOT an inline-asm
-            // v_max_f32: the accumulators come straight out of the MFMA pipe and hipcc does not place the MFMA -> VALU wait
-            // states in front of inline asm -- that form read stale registers in the multi-view instantiations.
-            p[0] = __builtin_amdgcn_fmed3f(p[0], 0.f, 3.402823466e38f); p[1] = __builtin_amdgcn_fmed3f(p[1], 0.f, 3.402823466e38f);
-        }
-        const f16x2 h = __builtin_convertvector(p, f16x2);
-        uh[k] = __builtin_bit_cast(uint32_t, h);
-        uint32_t l;
-        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l) : "v"(uh[k]), "v"(p[0]));
-        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(uh[k]), "v"(p[1]));
-        ul[k] = l;
-    }
-    if constexpr (GUARD) {  // (the operands are v_cvt_pk results, never straight MFMA outputs: inline asm is safe here)
-        uint32_t m = *amax;
-        asm("v_pk_maximum3_f16 %0, %0, %1, %2" : "+v"(m) : "v"(uh[0]), "v"(uh[1]));
-        asm("v_pk_maximum3_f16 %0, %0, %1, %2" : "+v"(m) : "v"(uh[2]), "v"(uh[3]));
-        *amax = m;
-    }
-    hi = __builtin_bit_cast(h8, uh);
-    lo = __builtin_bit_cast(h8, ul);
-}
-
-// [relu](acc) -> head / tail images (storage order, like write_act)
-template <typename ST, bool RELU = true, int JT>
-__device__ __forceinline__ void write_split(const f32x16 (&acc)[IT][JT], char *smem, uint32_t waddr) {
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt) {
-            const f32x16 &a = acc[it][jt];
-            const uint32_t ad = waddr + jt * 32 * ROW_ACT + it * 64;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = a[8 * half + e];
-                h8 hi, lo;
-                split8<RELU>(v, hi, lo);
-                *reinterpret_cast<h8 *>(smem + ST::A_HI + ad + 16 * half) = hi;
-                *reinterpret_cast<h8 *>(smem + ST::A_LO + ad + 16 * half) = lo;
-            }
-        }
-}
 
 // ---- "own K block first" form of the 512 x 512 linears (round 4) -----------------------------------------------------------
 // A wave's accumulators ARE B fragments of the next linear: lane (point pl, half h) holds, in registers 8 rr .. 8 rr + 7 of
@@ -1081,29 +889,8 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
         PNR_T(PH_LIN_OUT);
         __syncthreads();
         PNR_T(PH_BAR_OUT);
-        if (tid < MT) {
-            const long long g = (long long)tile * MT + tid;
-            f32x4 s;
-            if constexpr (SC != 0) {  // the partials are at scale c 2^t: undone in front of lin_out's bias
-                s = *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + tid * 16);
-#pragma unroll
-                for (int w = 1; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + (w * MT + tid) * 16);
-                s = s * sc_out + *reinterpret_cast<const f32x4 *>(q.bout);
-            } else {
-                s = *reinterpret_cast<const f32x4 *>(q.bout);
-#pragma unroll
-                for (int w = 0; w < NW; ++w) s += *reinterpret_cast<const f32x4 *>(smem + ST::LDS_OUT + (w * MT + tid) * 16);
-            }
-            // models.py:260-265: rgb = sigmoid(out[:3]), sigma = relu(out[3])
-            f32x4 res = {1.f / (1.f + expf(-s[0])), 1.f / (1.f + expf(-s[1])), 1.f / (1.f + expf(-s[2])), fmaxf(s[3], 0.f)};
-            if (g < q.P) {
-                *reinterpret_cast<f32x4 *>(q.out + g * 4) = res;
-                if constexpr (GUARD) {
-                    const float t = res[0] + res[1] + res[2] + res[3];
-                    if (!(fabsf(t) <= 3.0e38f)) sat_bits |= 1u << 11;  // NaN / inf output
-                }
-            }
-        }
+        // (SC: the partials are at scale c 2^t, undone in front of lin_out's bias; GUARD: bit 11 = a non-finite output)
+        output_stage<MT, SC != 0, GUARD>(smem + ST::LDS_OUT, tid, tile, q.bout, q.out, q.P, sc_out, &sat_bits);
         PNR_T(PH_FINAL);
     }
     if constexpr (GUARD) {
@@ -1116,305 +903,6 @@ __global__ void __launch_bounds__(NTHREADS, NW / 4) eval_split_kernel(const Eval
             const uint32_t m = probe_lds[tid];
             const float v = tid < 11 ? __builtin_bit_cast(float, m) * sc_inv : __builtin_bit_cast(float, m);  // true units
             if (m) atomicMax(q.probe + tid, __builtin_bit_cast(uint32_t, v));
-        }
-    }
-}
-
-// ================================================================ fp32-class backward chain (training), round 3
-// The data-gradient chain of one ResnetFC at split-operand precision, fused like pnr_bwd.hip's bwd_kernel: same tile geometry as
-// the forward (persistent 512-thread workgroup, 64-point tiles, wave w owns features 64w..64w+63), the gradient G of the residual
-// stream resident in fp32 accumulators, a TRANSPOSED (head, tail) weight stream
-//     lin_out^T | fc_1[4]^T fc_0[4]^T fc_1[3]^T fc_0[3]^T | per source view: fc_1[2]^T fc_0[2]^T ... fc_0[0]^T,
-// gradient images as (head, tail) f16 pairs in LDS, relu masks = the TRAIN forward's 1-bit words.  Every layer's output gradient
-// dY leaves as fp32 rows (natural feature order) at the chain's power-of-two scale: the operands of the weight-gradient GEMMs
-// and of the lin_z^T / lin_in^T products, which stay on the split-operand GEMM kernel of pnr_f32.hip.
-// (reference: torch autograd through src/model/resnetfc.py:132-184, resnetfc.py:55-62 per block.)
-
-// one thread = one lane's 8-element fragment slice of the head AND the tail stream (16-byte stores)
-__global__ void pack_weights_bwd_split_kernel(PnrMlpWeights p, _Float16 *__restrict__ out_h, _Float16 *__restrict__ out_l) {
-    const size_t idx8 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx8 >= (size_t)BSRS_TOTAL * IT * 64 * NW) return;
-    const int lane = idx8 & 63;
-    const int it = (idx8 >> 6) % IT;
-    const size_t rest = idx8 / (64 * IT);
-    const int rs = rest % BSRS_TOTAL;
-    const int wv = rest / BSRS_TOTAL;
-    int g = 0;
-    while (g + 1 < NBGEMM && rs >= bgemm_offset(g + 1)) ++g;
-    const int st = rs - bgemm_offset(g);
-    const int i = lane & 31, h = lane >> 5;
-    const int f_row = wv * SL + it * 32 + i;  // A-operand row = output row of the transposed GEMM = INPUT feature of the layer
-    __attribute__((aligned(16))) _Float16 oh[8], ol[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        float v = 0.f;
-        if (g == BG_Z2 || g == BG_Z1 || g == BG_Z0) {
-            // d z_lat[c] += sum_f dY_b[f] W_z[b][f][c]: rows = latent channel c (natural order, wave w owns 64w..64w+63),
-            // K = hidden feature f in the storage order of the gradient image
-            const int b = g == BG_Z2 ? 2 : (g == BG_Z1 ? 1 : 0);
-            const int f_o = feat_of(st >> 1, st & 1, 8 * h + e);
-            v = p.lin_z_w[b][f_o * C_LAT + f_row];
-        } else if (g == BG_IN) {
-            // d(code | viewdir)[k] = sum_f dY[f] W_in[f][k]: every wave holds the FULL 64 (42 real) output rows and contracts
-            // only its own 64 hidden features = storage elements 64w + 16s + 8h + e (K-split, reduced across waves in LDS)
-            const int k_row = it * 32 + i;
-            const int f_o = feat_of(wv * IT + (st >> 1), st & 1, 8 * h + e);
-            if (k_row < D_IN) v = p.lin_in_w[f_o * D_IN + k_row];
-        } else if (g == BG_OUT) {
-            const int k = st * 16 + h * 8 + e;  // natural order of the 4 network outputs, zero padded
-            if (k < D_OUT) v = p.lin_out_w[k * D_HID + f_row];
-        } else {
-            const int b = 4 - (g - 1) / 2;       // BG_FC1_4, BG_FC0_4, BG_FC1_3, ... -> block index
-            const float *w = ((g - 1) & 1) == 0 ? p.fc1_w[b] : p.fc0_w[b];
-            const int f_o = feat_of(st >> 1, st & 1, 8 * h + e);  // K index = OUTPUT feature, storage order of the gradient image
-            v = w[f_o * D_HID + f_row];
-        }
-        const _Float16 hh = (_Float16)v;
-        oh[e] = hh;
-        ol[e] = (_Float16)(v - (float)hh);
-    }
-    *reinterpret_cast<uint4 *>(out_h + idx8 * 8) = *reinterpret_cast<const uint4 *>(oh);
-    *reinterpret_cast<uint4 *>(out_l + idx8 * 8) = *reinterpret_cast<const uint4 *>(ol);
-}
-
-struct BwdSplitParams {
-    const char *wstream;                 // head blob; the tail blob follows at + BSPACKED_BYTES
-    const unsigned long long *d_mask;    // relu bit masks of the forward, [layer][view][tile][thread]
-    const float *g_out;                  // (P,4) dL/d(lin_out output), unscaled
-    const float *scale_dev;              // device [s, 1/s]: the chain runs at s (pnr_grad_scale)
-    long long P;
-    int NS, ntiles;
-    char *g_fc1[5], *g_fc0[5], *g_x0;    // dY at scale s as (head | tail) 16-bit rows in storage order (copies of the gradient images):
-                                         // b < 3 (NS*P,512) [view][point], else (P,512); g_x0 (NS*P,512); tail array behind the head array
-    float *d_zlat;                       // (NS*P, 512) fp32, natural channel order, UNSCALED: d(interpolated latent) = sum_b dY_b W_z[b]
-    float *d_in;                         // (NS*P, 42) fp32, unscaled: d(positional code | view direction)   (nullable: not written)
-    float *mv_ws;                        // several views: per-workgroup scratch for the pooled gradient every view starts from
-};
-
-template <bool MV>
-__global__ void __launch_bounds__(NTHREADS, NW / 4) bwd_split_kernel(const BwdSplitParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef SplitTileT<64> ST;
-    constexpr int JT = ST::JT, MT = ST::MT;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pl = lane & 31, h = lane >> 5;
-    const int NS = MV ? q.NS : 1;
-    const uint32_t a_rd0 = ST::A_HI + pl * ROW_ACT + h * 16;
-    const uint32_t in_rd0 = ST::LDS_IN + pl * ROW_IN + h * 16;
-    const uint32_t a_wr = pl * ROW_ACT + (wv * IT) * 64 + h * 32;
-    f16_ovfl_mode<PH>();
-    SplitRing R;
-    R.base_h = q.wstream + (size_t)wv * (BSRS_TOTAL * IT * 1024) + lane * 16;
-    R.base_l = R.base_h + BSPACKED_BYTES;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            R.h[j][it] = gload8<PH>(R.base_h + j * (IT * 1024) + it * 1024);
-            R.l[j][it] = gload8<PH>(R.base_l + j * (IT * 1024) + it * 1024);
-        }
-    R.pf_rs = 4;
-    R.pf_view = 0;
-    const float scale = q.scale_dev[0], inv_scale = q.scale_dev[1];
-    const size_t mask_layer = (size_t)NS * (size_t)q.ntiles * NTHREADS;
-
-    auto zero = [&](f32x16 (&a)[IT][JT]) {
-#pragma unroll
-        for (int it = 0; it < IT; ++it)
-#pragma unroll
-            for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[it][jt][r] = 0.f;
-    };
-    // acc = bit ? acc : 0   /   G += bit ? t : 0
-    auto apply_mask = [&](f32x16 (&a)[IT][JT], unsigned long long mk) {
-#pragma unroll
-        for (int it = 0; it < IT; ++it)
-#pragma unroll
-            for (int jt = 0; jt < JT; ++jt) {
-                const uint32_t m16 = (uint32_t)(mk >> ((it * JT + jt) * 16)) & 0xffffu;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[it][jt][r] = (m16 >> r) & 1u ? a[it][jt][r] : 0.f;
-            }
-    };
-    auto masked_add = [&](f32x16 (&G)[IT][JT], const f32x16 (&t)[IT][JT], unsigned long long mk) {
-#pragma unroll
-        for (int it = 0; it < IT; ++it)
-#pragma unroll
-            for (int jt = 0; jt < JT; ++jt) {
-                const uint32_t m16 = (uint32_t)(mk >> ((it * JT + jt) * 16)) & 0xffffu;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) G[it][jt][r] += (m16 >> r) & 1u ? t[it][jt][r] : 0.f;
-            }
-    };
-    long long rows_left = 0;
-    // the gradient image just published (head, tail) -> its 16-bit row sets (operands of the weight-gradient GEMM), whole rows
-    auto dump_pair = [&](char *head, long long rows, bool per_view) {
-        const size_t total = (size_t)(per_view ? (long long)NS * q.P : q.P) * (D_HID * 2);
-        dump_image<MT>(smem, ST::A_HI, head + (size_t)rows * (D_HID * 2), rows_left, wv, lane);
-        dump_image<MT>(smem, ST::A_LO, head + total + (size_t)rows * (D_HID * 2), rows_left, wv, lane);
-    };
-    // the GEMM on the image just published, with the image's copy-out in front of it
-    auto gemm_dump = [&](f32x16 (&a)[IT][JT], char *head, long long rows, bool per_view) {
-        dump_pair(head, rows, per_view);
-        gemm_split<JT, SplitAdvBwd>(a, smem, a_rd0, 32 * ROW_ACT, ST::A_LO - ST::A_HI, KS_BIG / 4, R, NS);
-    };
-    // reverse of one residual block (resnetfc.py:55-62):  given G = dL/d(x + fc_1(relu(fc_0(relu(x))))),
-    //   dY(fc_1) = G ;  d net = (fc_1^T G) . [net > 0] = dY(fc_0) ;  G += (fc_0^T d net) . [x > 0]
-    auto bwd_block = [&](f32x16 (&G)[IT][JT], int b, long long rows, size_t mask_off) {
-        __syncthreads();  // every wave is done reading the gradient image (previous GEMM)
-        write_split<ST, false>(G, smem, a_wr);
-        __syncthreads();
-        f32x16 t[IT][JT];
-        const unsigned long long mk_n = (q.d_mask + (size_t)(2 * b + 1) * mask_layer)[mask_off];
-        zero(t);
-        gemm_dump(t, q.g_fc1[b], rows, b < COMBINE_LAYER);
-        apply_mask(t, mk_n);
-        __syncthreads();
-        write_split<ST, false>(t, smem, a_wr);
-        __syncthreads();
-        const unsigned long long mk_a = (q.d_mask + (size_t)(2 * b) * mask_layer)[mask_off];
-        zero(t);
-        gemm_dump(t, q.g_fc0[b], rows, b < COMBINE_LAYER);
-        masked_add(G, t, mk_a);
-    };
-
-    for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
-        rows_left = q.P - (long long)tile * MT;
-        const long long rows_pooled = (long long)tile * MT;
-        const size_t mask_pooled = (size_t)tile * NTHREADS + tid;
-        __syncthreads();  // previous tile: readers of the staging rows / gradient image are done
-        {   // stage s * g_out as (head, tail) operand rows [point][64] (4 real values, zero padded)
-            const int row = tid >> 3, chunk = tid & 7;
-            const long long g = rows_pooled + row;
-            float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (chunk == 0 && g < q.P) {
-                const f32x4 gv = *reinterpret_cast<const f32x4 *>(q.g_out + g * 4) * scale;
-                v[0] = gv[0]; v[1] = gv[1]; v[2] = gv[2]; v[3] = gv[3];
-            }
-            h8 hi, lo;
-            split8<false>(v, hi, lo);
-            *reinterpret_cast<h8 *>(smem + ST::LDS_IN + row * ROW_IN + chunk * 16) = hi;
-            *reinterpret_cast<h8 *>(smem + ST::LDS_IN + ST::IN_LO_DELTA + row * ROW_IN + chunk * 16) = lo;
-        }
-        __syncthreads();
-        f32x16 G[IT][JT];
-        {
-            const unsigned long long mk = (q.d_mask + (size_t)10 * mask_layer)[mask_pooled];
-            zero(G);
-            gemm_split<JT, SplitAdvBwd>(G, smem, in_rd0, 32 * ROW_IN, ST::IN_LO_DELTA, KS_IN / 4, R, NS);  // lin_out^T g_out
-            apply_mask(G, mk);                                                                             // . [x5 > 0]
-        }
-#pragma unroll 1
-        for (int b = N_BLOCKS - 1; b >= COMBINE_LAYER; --b) bwd_block(G, b, rows_pooled, mask_pooled);
-        // backward of the view mean (util.py:461-466): every view starts from G / NS, parked in the per-workgroup scratch
-        [[maybe_unused]] f32x4 *gws = MV ? reinterpret_cast<f32x4 *>(q.mv_ws) + (size_t)blockIdx.x * (IT * JT * 4 * NTHREADS) + tid : nullptr;
-        if constexpr (MV) {
-            const float inv = 1.f / (float)NS;
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const f32x4 v = {G[it][jt][4 * k], G[it][jt][4 * k + 1], G[it][jt][4 * k + 2], G[it][jt][4 * k + 3]};
-                        gws[((it * JT + jt) * 4 + k) * NTHREADS] = v * inv;
-                    }
-        }
-#pragma unroll 1
-        for (int view = 0; view < NS; ++view) {
-            if constexpr (MV) {
-#pragma unroll
-                for (int it = 0; it < IT; ++it)
-#pragma unroll
-                    for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const f32x4 v = gws[((it * JT + jt) * 4 + k) * NTHREADS];
-                            G[it][jt][4 * k] = v[0]; G[it][jt][4 * k + 1] = v[1]; G[it][jt][4 * k + 2] = v[2]; G[it][jt][4 * k + 3] = v[3];
-                        }
-            }
-            const long long rows_view = (long long)view * q.P + rows_pooled;
-            const size_t mask_view = mask_pooled + (size_t)view * (size_t)q.ntiles * NTHREADS;
-#pragma unroll 1
-            for (int b = COMBINE_LAYER - 1; b >= 0; --b) bwd_block(G, b, rows_view, mask_view);
-            // ---- d z_lat = sum_b dY_b W_z[b] and d(code) = dY_0 W_in (resnetfc.py:147,175-180 backward): four more transposed-
-            // stream GEMMs on gradient images this tile has just produced.  dY_2, dY_1 (= g_fc1[1], g_fc1[0]) come back from the
-            // rows this workgroup copied out a moment ago (L2-resident); dY_0 = G is still in registers.
-            f32x16 Z[IT][JT];
-            zero(Z);
-#pragma unroll 1
-            for (int b = COMBINE_LAYER - 1; b >= 1; --b) {
-                __threadfence_block();
-                __syncthreads();  // the image's readers are done; the rows this tile dumped are visible
-                {
-                    const char *src = q.g_fc1[b - 1] + (size_t)rows_view * (D_HID * 2);
-                    const size_t total = (size_t)NS * (size_t)q.P * (D_HID * 2);
-#pragma unroll
-                    for (int u = 0; u < MT / NW; ++u) {
-                        const int row = wv * (MT / NW) + u;
-                        u32x4 vh = {0, 0, 0, 0}, vl = vh;
-                        if (row < rows_left) {
-                            vh = *reinterpret_cast<const u32x4 *>(src + (size_t)row * (D_HID * 2) + lane * 16);
-                            vl = *reinterpret_cast<const u32x4 *>(src + total + (size_t)row * (D_HID * 2) + lane * 16);
-                        }
-                        *reinterpret_cast<u32x4 *>(smem + ST::A_HI + row * ROW_ACT + lane * 16) = vh;
-                        *reinterpret_cast<u32x4 *>(smem + ST::A_LO + row * ROW_ACT + lane * 16) = vl;
-                    }
-                }
-                __syncthreads();
-                gemm_split<JT, SplitAdvBwd>(Z, smem, a_rd0, 32 * ROW_ACT, ST::A_LO - ST::A_HI, KS_BIG / 4, R, NS);  // lin_z[b]^T dY_b
-            }
-            __syncthreads();
-            write_split<ST, false>(G, smem, a_wr);  // dY of lin_in and lin_z[0]
-            __syncthreads();
-            gemm_dump(Z, q.g_x0, rows_view, true);                                                                   // lin_z[0]^T dY_0
-            {   // accumulator (channel 64 wv + 32 it + (r&3) + 8(r>>2) + 4h, point) -> fp32 rows, 16-byte pieces, out of the scaled domain
-                float *dst = q.d_zlat + ((size_t)rows_view + pl) * C_LAT + (wv * IT) * 32 + 4 * h;
-#pragma unroll
-                for (int jt = 0; jt < JT; ++jt) {
-                    if (jt * 32 + pl >= rows_left) continue;
-#pragma unroll
-                    for (int it = 0; it < IT; ++it)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const f32x4 v = {Z[it][jt][4 * k], Z[it][jt][4 * k + 1], Z[it][jt][4 * k + 2], Z[it][jt][4 * k + 3]};
-                            __builtin_nontemporal_store(v * inv_scale, reinterpret_cast<f32x4 *>(dst + (size_t)jt * 32 * C_LAT + it * 32 + 8 * k));
-                        }
-                }
-            }
-            // lin_in^T, K-split: this wave's 64 hidden features = bytes [128 wv, 128 wv + 128) of every image row
-            zero(Z);
-            gemm_split<JT, SplitAdvBwd>(Z, smem, a_rd0 + wv * 128, 32 * ROW_ACT, ST::A_LO - ST::A_HI, KS_IN / 4, R, NS);
-            __syncthreads();  // every wave is done with the images: their space takes the partials
-            {
-                // partial[w][point][k], 66-float rows: lanes of a half-wave write consecutive points -> distinct banks
-                float *part = reinterpret_cast<float *>(smem) + (size_t)wv * (MT * 66);
-#pragma unroll
-                for (int it = 0; it < IT; ++it)
-#pragma unroll
-                    for (int jt = 0; jt < JT; ++jt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            part[(jt * 32 + pl) * 66 + it * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = Z[it][jt][r];
-            }
-            __syncthreads();
-            if (q.d_in) {
-                const int pnt = tid >> 3, k0 = (tid & 7) * 8;
-                if (pnt < rows_left) {
-#pragma unroll
-                    for (int k = k0; k < k0 + 8; ++k) {
-                        if (k >= D_IN) break;
-                        float sum = 0.f;
-#pragma unroll
-                        for (int w = 0; w < NW; ++w) sum += reinterpret_cast<const float *>(smem)[(size_t)w * (MT * 66) + pnt * 66 + k];
-                        q.d_in[((size_t)rows_view + pnt) * D_IN + k] = sum * inv_scale;
-                    }
-                }
-            }
-            __syncthreads();  // the partials are consumed before the next view / tile reuses the space
         }
     }
 }
@@ -1498,44 +986,6 @@ static int split_launch(const PnrScene *s, const void *packed, const void *table
         hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds + lds_extra, st, q);
     }
     return pnr_check_launch("eval_split_kernel");
-}
-
-size_t bwd_split_packed_bytes() { return 2 * BSPACKED_BYTES; }
-
-int pack_bwd_split(const PnrMlpWeights *w, void *packed, hipStream_t st) {
-    if (!w || !packed) return pnr_fail(PNR_E_INVALID, "pack_bwd_split: null argument");
-    const size_t n8 = (size_t)BSRS_TOTAL * IT * 64 * NW;
-    hipLaunchKernelGGL(pack_weights_bwd_split_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, *w, (_Float16 *)packed,
-                       (_Float16 *)((char *)packed + BSPACKED_BYTES));
-    return pnr_check_launch("pack_weights_bwd_split_kernel");
-}
-
-int mlp_backward_split_chain(const void *packed_bwd_split, const unsigned long long *masks, const float *g_out, const float *scale_dev,
-                             long long P, int NS, void *const *g_fc1, void *const *g_fc0, void *g_x0, float *d_zlat, float *d_in,
-                             float *mv_ws, hipStream_t st) {
-    if (!packed_bwd_split || !masks || !g_out || !scale_dev || !g_fc1 || !g_fc0 || !g_x0 || !d_zlat || P <= 0 || NS <= 0)
-        return pnr_fail(PNR_E_INVALID, "mlp_backward_split_chain: bad argument");
-    BwdSplitParams q = {};
-    q.wstream = (const char *)packed_bwd_split; q.d_mask = masks; q.g_out = g_out; q.scale_dev = scale_dev; q.P = P; q.NS = NS;
-    const long long nt = (P + 63) / 64;
-    if (nt * NTHREADS * NS > 0xffffffffLL) return pnr_fail(PNR_E_INVALID, "mlp_backward_split_chain: too many points");
-    q.ntiles = (int)nt;
-    for (int b = 0; b < 5; ++b) {
-        if (!g_fc1[b] || !g_fc0[b]) return pnr_fail(PNR_E_INVALID, "mlp_backward_split_chain: null gradient buffer");
-        q.g_fc1[b] = (char *)g_fc1[b]; q.g_fc0[b] = (char *)g_fc0[b];
-    }
-    q.g_x0 = (char *)g_x0; q.d_zlat = d_zlat; q.d_in = d_in;
-    const int cus = device_cus();
-    const int grid = (int)(nt < cus ? nt : cus);
-    const bool mv = NS > 1;
-    if (mv && !mv_ws) return pnr_fail(PNR_E_INVALID, "mlp_backward_split_chain: NS > 1 needs the multi-view scratch");
-    q.mv_ws = mv_ws;
-    auto k = mv ? bwd_split_kernel<true> : bwd_split_kernel<false>;
-    const int lds = SplitTileT<64>::LDS_TOTAL;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return pnr_check_hip(e, "hipFuncSetAttribute(bwd_split_kernel)");
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, q);
-    return pnr_check_launch("bwd_split_kernel");
 }
 
 }  // namespace pnr

@@ -2,7 +2,7 @@
 GPU tests (-m gpu) of the MLP backward STAGE of the fp32-class training paths at its own resolution: the three forms of one
 arithmetic
 
-  fused   pnr_eval_ray_samples_split_train + pnr_mlp_backward_split (bwd_split_kernel, the batched split-operand weight-gradient
+  fused   pnr_eval_ray_samples_split_train + pnr_mlp_backward_split (bwd_split_kernel of pnr_bwd_split.hip, the batched split-operand weight-gradient
           launch, lin_out's gradient): what precision "f16x3" trains with
   gemms   pnr_eval_ray_samples_f32_train(split) + pnr_mlp_backward_f32(split_gemm = 1): one split-operand GEMM per layer
   exact   the same with split_gemm = 0: exact fp32 MFMA products, the yardstick
