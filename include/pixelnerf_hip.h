@@ -380,8 +380,13 @@ int pnr_mlp_backward(const void *packed_bwd, int precision, const PnrTrainDumps 
                      device scalar that overrides grad_scale (no host sync to pick it)*/,
                      long long P, int NS, const PnrBackwardDumps *out /*host*/, void *stream);
 
-/* Picks that scale on the device: scales[0] = 2^(6 - ceil(log2 max|g|)) (1 for g == 0), scales[1] =
- * 1/scales[0]; both NaN when g holds a non-finite value (the gradients then come out NaN).  g: n floats. */
+/* Picks that scale on the device: scales[0] = 2^e with e = 6 - ceil(log2 max|g|) (1 for g == 0), scales[1] =
+ * 2^-e; both NaN when g holds a non-finite value (the gradients then come out NaN).  g: n floats, any 4-byte alignment.
+ * e is clamped to [-100, 100]: both scales stay finite NORMAL powers of two for a vanishing (subnormal-range) or a huge
+ * gradient (unclamped, 2^e overflows to inf for max|g| < 2^-121 and the step dies of 0 * inf); with the clamp a maximum below
+ * 2^-94 is scaled to max|g| 2^100 < 2^6 and one above 2^106 to max|g| 2^-100 > 2^6, still exactly.  A subnormal max|g| counts
+ * (it is not flushed to zero).  At a maximum that IS a power of two, 2^k, ceil(log2) = k: the scaled maximum is 2^6 itself;
+ * otherwise it lies in (2^5, 2^6) (log2 is evaluated in fp32: a maximum a few last places above 2^k may still count as 2^k). */
 int pnr_grad_scale(const float *g, long long n, float *scales /*device, 2 floats*/, void *stream);
 
 /* Weight gradient of one 512x512 linear from the 16-bit dumps: dW (512,512) fp32 = out_scale *

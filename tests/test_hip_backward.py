@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_ref as G
 from helpers import golden_setup
 from oracle import pnr_oracle as O
 
@@ -288,10 +289,19 @@ def test_weight_grad_kernel_single_and_batched(dev, prec, dt):
         jobs.append((dY, X, rs, cs))
     outs = ops.weight_grad_batched(jobs, p, 0.25)
     again = ops.weight_grad_batched(jobs, p, 0.25)
+    nsplit = _lib.load().pnr_weight_grad_batched_workspace_bytes(len(jobs), 4096 + 5) // (len(jobs) * (512 * 512 + 512) * 4)
     for (dY, X, rs, cs), (dW, db), (dW2, db2) in zip(jobs, outs, again):
         rW, rb = ref(dY, X, rs, cs, 0.25)
         assert (dW - rW).norm() <= 2e-6 * rW.norm() and (db - rb).norm() <= 2e-6 * rb.norm()
         assert (dW - rW).abs().max() <= 1e-4 * rW.abs().max()
+        # and every element inside the derived bound of tests/gemm_ref.py around the fp64 product (small elements included, which
+        # a bar relative to the tensor's maximum does not see)
+        y64, x64, rows = dY.float().cpu().numpy().T, X.float().cpu().numpy().T, dY.shape[0]
+        vW, bW = G.finish(G.product(y64, x64), rows, nsplit, out_scale=0.25)
+        vb, bb = G.finish(G.product(y64, np.ones((1, rows))), rows, nsplit, out_scale=0.25)
+        vW, vb = G.scatter_perm(vW, vb[:, 0], perm.cpu().numpy(), rs, cs)
+        bW, bb = G.scatter_perm(bW, bb[:, 0], perm.cpu().numpy(), rs, cs)
+        assert G.worst_ratio(dW.cpu().numpy(), vW, bW) <= 1.0 and G.worst_ratio(db.cpu().numpy(), vb, bb) <= 1.0
         assert torch.equal(dW, dW2) and torch.equal(db, db2)
         sW, sb = ops.weight_grad(dY, X, p, 0.25, rows_st=rs, cols_st=cs)  # single-job entry: same maths
         assert (sW - rW).norm() <= 2e-6 * rW.norm() and (sb - rb).norm() <= 2e-6 * rb.norm()
@@ -317,6 +327,13 @@ def test_weight_grad_kernel_single_and_batched(dev, prec, dt):
     r = torch.empty(4, 512, device=dev)
     r[:, perm] = g.t() @ x5.float()
     assert (oW - r).norm() <= 2e-6 * r.norm() and torch.allclose(ob, g.sum(0), rtol=1e-5, atol=1e-4)
+    # per element, dW and db, against the fp64 product: 256 row slices of ceil(P / 256) rows, fp32 x 16-bit products
+    g64, x64, per = g.cpu().numpy().T, x5.float().cpu().numpy().T, -(-P // 256)
+    vW, bW = G.finish(G.product(g64, x64), per, 256, rounded=True)
+    vb, bb = G.finish(G.product(g64, np.ones((1, P))), per, 256)
+    vW, _ = G.scatter_perm(vW, None, perm.cpu().numpy(), False, True)
+    bW, _ = G.scatter_perm(bW, None, perm.cpu().numpy(), False, True)
+    assert G.worst_ratio(oW.cpu().numpy(), vW, bW) <= 1.0 and G.worst_ratio(ob.cpu().numpy(), vb[:, 0], bb[:, 0]) <= 1.0
     oW2, ob2 = ops.lin_out_grad(g, x5, p)
     assert torch.equal(oW, oW2) and torch.equal(ob, ob2)
 
@@ -350,6 +367,54 @@ def test_grad_scale_is_picked_on_device(dev):
     a = ops.mlp_backward(pkb, dumps, g_out, float(s[0].item()))
     b = ops.mlp_backward(pkb, dumps, g_out, s[0:1])
     assert torch.equal(a.g_x0, b.g_x0) and all(torch.equal(x, y) for x, y in zip(a.g_fc0, b.g_fc0))
+
+
+def test_grad_scale_edges_follow_the_header_rule(dev):
+    """pnr_grad_scale at the edges of its rule (include/pixelnerf_hip.h): scales[0] = 2^e, e = 6 - ceil(log2 max|g|) clamped to
+    [-100, 100], scales[1] = 2^-e; both exact powers of two.  max|g| AT a power of two (the ceil must not step), one element,
+    n % 4 != 0 with the maximum in the scalar tail, a pointer that is not 16-byte aligned (no vector loads at all), a subnormal
+    maximum (the clamp), and the many-workgroup form (n > 2^20) with the same misalignment and tail."""
+    from pixelnerf_amd import ops
+
+    def want(mx):
+        m, e = np.frexp(np.float64(mx))                # mx = m 2^e, 0.5 <= m < 1: ceil(log2 mx) = e, or e - 1 at a power of two
+        c = int(e) - 1 if m == 0.5 else int(e)
+        k = min(max(6 - c, -100), 100)
+        return [2.0 ** k, 2.0 ** -k]
+
+    def scales(t):
+        return ops.grad_scale(t).cpu().double().tolist()
+
+    for k in range(-30, 31):                           # exact powers of two, the maximum anywhere in a ragged vector
+        g = torch.full((11,), 2.0 ** (k - 3), device=dev)
+        g[(k + 30) % 11] = -(2.0 ** k)
+        assert scales(g) == want(2.0 ** k) == [2.0 ** (6 - k), 2.0 ** (k - 6)], k
+    for v in (3.0, 0.75, 1e-3, 2.0 ** -126, 1e30):       # one element
+        assert scales(torch.tensor([-v], device=dev)) == want(np.float32(v)), v
+    base = torch.zeros(64 + 8, device=dev)
+    for n in (1, 2, 3, 5, 6, 7, 9, 63):                # n % 4 != 0: the maximum in the LAST element, then in the first
+        for off in (0, 1, 2, 3):                       # off != 0: the pointer is 4, 8, 12 bytes past a 16-byte boundary
+            for pos in (n - 1, 0):
+                base.fill_(float("nan"))               # whatever lies around the n elements must not be read
+                g = base[4 + off:4 + off + n]
+                g.fill_(0.01)
+                g[pos] = 5.5
+                assert g.data_ptr() % 16 == 4 * off and scales(g) == want(5.5), (n, off, pos)
+    for mx in (2.0 ** -127, 2.0 ** -140, 2.0 ** -149):  # subnormal maxima: 6 - ceil(log2 mx) > 100, clamped
+        g = torch.zeros(9, device=dev)
+        g[8] = mx
+        assert scales(g) == [2.0 ** 100, 2.0 ** -100] == want(mx), mx
+    assert scales(torch.tensor([2.0 ** 100], device=dev)) == want(2.0 ** 100) == [2.0 ** -94, 2.0 ** 94]
+    assert scales(torch.tensor([3.0e38], device=dev)) == want(np.float32(3.0e38)) == [2.0 ** -100, 2.0 ** 100]  # 6 - 128 clamped
+    big = torch.full(((1 << 20) + 16,), float("nan"), device=dev)
+    for off, n in ((0, (1 << 20) + 4), (1, (1 << 20) + 3), (0, (1 << 20) + 7)):   # many-workgroup form: aligned, misaligned, ragged
+        g = big[4 + off:4 + off + n]
+        g.fill_(-0.25)
+        g[n - 1] = 17.0
+        assert scales(g) == want(17.0), (off, n)
+        g[n - 1] = 0.25
+        g[12345] = -1024.0
+        assert scales(g) == want(1024.0), (off, n)
 
 
 @pytest.mark.parametrize("name,prec", [("train_64_32", "f16"), ("srn_mini_64_128", "f16"), ("srn_mini_64_128", "bf16")])
