@@ -626,6 +626,72 @@ int pnr_pyramid_to_latent_backward(const float *d_latent, int d_latent_is_nchw, 
                                    const int *channels, const int *heights, const int *widths,
                                    int n_stages, int NV, void *stream);
 
+/* ---- the encoder's ResNet trunk for inference (added within ABI rev 12) ----------------------
+ * src/model/encoder.py:111-164 over torchvision's BasicBlock trunk (resnet18 / resnet34), batch norm in eval mode folded
+ * into a per-channel affine.  Everything is fp32 in and out, NCHW, contiguous.
+ *
+ * pnr_conv2d_affine: convolution + affine + optional residual + optional ReLU in one call,
+ *   y[n,co,oy,ox] = act( (sum_{ci,ky,kx} x[n,ci, oy s + ky - p, ox s + kx - p] w[co,ci,ky,kx]) scale[co] + shift[co]
+ *                        + res[n,co,oy,ox] )
+ *   x (N,Cin,H,W); w (Cout,Cin,k,k) in torch's order; scale, shift (Cout); res (nullable) and y (N,Cout,Ho,Wo);
+ *   Ho = (H + 2p - k) / s + 1 floored, likewise Wo; p = k / 2 (3, 1, 0 for k = 7, 3, 1); zeros lie outside the image;
+ *   act = ReLU when relu != 0, else the identity.  (k, s) is one of (7,2), (3,1), (3,2), (1,2); Cin is 3 or a multiple of 64;
+ *   Cout is a multiple of 64.  y must not overlap x, res or the workspace.
+ *   THE BATCH-NORM FOLD is the caller's: scale = gamma / sqrt(var + eps), shift = beta - mean scale, formed in fp64 and
+ *   rounded to fp32 once.
+ *   ARITHMETIC: exact fp32 -- fp32 operands, one fused multiply-add per term, fp32 accumulation; acc scale + shift is one
+ *   fused multiply-add, the residual one addition.  No 16-bit operands, no (head, tail) splits.
+ *   DETERMINISM: no atomics.  The K = Cin k k terms of an output element are taken in ascending (ci, ky, kx).  The
+ *   reduction is cut into S contiguous slices (S = 1 below K = 1152, else min(8, K / 576)) of ceil(K / S) terms rounded up
+ *   to 64, and every slice into four equal quarters; a quarter is one chain started from zero, the quarters of a slice are
+ *   added in ascending order, then the slices in ascending order in a second pass.  pnr_conv2d_affine_slices(Cin, k) = 4 S
+ *   is the number of partial sums that meet in one element.  That order is a function of (Cin, k) alone: never of N, H, W,
+ *   the tile an element falls in or the launch.  Hence two calls give equal bytes, and image n of a batch gets the bytes it
+ *   gets when it is sent alone.
+ *   workspace: pnr_conv2d_affine_workspace_bytes(...) bytes of device scratch, the caller's (0 for S = 1, then
+ *   workspace may be NULL; else S x the output's size); the size entry answers 0 for a shape the entry refuses.
+ * pnr_maxpool2d_3x3s2: nn.MaxPool2d(3, 2, 1).  x (N,C,H,W) -> y (N,C,Ho,Wo), Ho = (H - 1) / 2 + 1.  The padding never wins
+ *   the maximum; the maximum is exact, so the output equals torch's bit for bit.
+ * PNR_E_INVALID, before any HIP call: a null pointer (res excepted) or one that is not 4-byte aligned; N < 0 or another
+ *   size <= 0; a (ksize, stride) outside the four pairs; channel counts outside the rule; N Ho Wo >= 2^31; a workspace
+ *   that is too small.  N = 0 is a no-op. */
+int pnr_conv2d_affine_slices(int Cin, int ksize);
+size_t pnr_conv2d_affine_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ksize, int stride);
+int pnr_conv2d_affine(const float *x, int N, int Cin, int H, int W, const float *w, const float *scale,
+                      const float *shift, int Cout, int ksize, int stride, const float *res /*nullable*/, int relu,
+                      float *y, void *workspace, size_t workspace_bytes, void *stream);
+int pnr_maxpool2d_3x3s2(const float *x, int N, int C, int H, int W, float *y, void *stream);
+
+/* One convolution of the trunk with its folded batch norm (host struct of device pointers). */
+typedef struct PnrConvRecord {
+    const float *w;       /* (cout, cin, ksize, ksize) */
+    const float *scale;   /* (cout) gamma / sqrt(var + eps) */
+    const float *shift;   /* (cout) beta - mean scale       */
+    int32_t cin, cout, ksize, stride;
+} PnrConvRecord;
+
+/* The whole trunk as one host loop over the two entries above (SpatialEncoder._stages): the stem (7x7 / 2, ReLU) gives
+ * level 0, BEFORE the pool; then, if use_first_pool, the max pool; then residual stage i = 1 .. n_levels - 1 of blocks[i-1]
+ * BasicBlocks (64, 128, 256, 512 channels; stages 2.. halve the size in their first block) gives level i.  A block is
+ * relu(affine2(conv2(relu(affine1(conv1(x))))) + idt), idt = x or the block's 1x1 / 2 downsample convolution with its affine.
+ *   convs: HOST array of n_convs records in the order the layers run: the stem; then per block its downsample (first block
+ *     of stages 2, 3, 4 only), conv1, conv2.  n_convs = 1 + sum over the stages run of (2 blocks + [stage > 1]).
+ *   blocks: HOST array of 4 block counts, (3,4,6,3) for resnet34, (2,2,2,2) for resnet18 (each in [1, 64]; all four are
+ *     checked, the first n_levels - 1 are run);  n_levels in [1, 5] (the encoder's num_layers);
+ *   images (NV,3,H,W); levels: HOST array of n_levels device pointers, level i is (NV, C_i, h_i, w_i) with C = 64, 64, 128,
+ *     256, 512 and (h_i, w_i) = pnr_encoder_level_shape(H, W, i, use_first_pool) (host arithmetic only; level in [0, 4]):
+ *     exactly what pnr_pyramid_to_latent takes;
+ *   workspace: pnr_encoder_trunk_workspace_bytes(...) bytes of device scratch, the caller's (0 for a shape refused).
+ * The determinism rules of pnr_conv2d_affine hold for the whole: equal bytes from call to call, and per image whatever NV.
+ * PNR_E_INVALID, before any HIP call: a null or misaligned pointer (records' included); H, W <= 0 or NV < 0; n_levels or a
+ * block count out of range; n_convs or a record that does not describe the layer at its place; a workspace that is too
+ * small.  NV = 0 is a no-op. */
+int pnr_encoder_level_shape(int H, int W, int level, int use_first_pool, int *h /*host*/, int *w /*host*/);
+size_t pnr_encoder_trunk_workspace_bytes(const int *blocks /*host*/, int n_levels, int use_first_pool, int NV, int H, int W);
+int pnr_encoder_trunk_forward(const PnrConvRecord *convs /*host*/, int n_convs, const int *blocks /*host*/, int n_levels,
+                              int use_first_pool, const float *images, int NV, int H, int W, float *const *levels /*host*/,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- next-row helpers: eval epilogue on device ----------------------
  * eval/eval.py:283-290,327-329 and util.psnr (src/util/util.py:474-481): rgb (n_views,pixels,3) ->
  * clamp to [0,1] [-> uint8 = trunc(x*255)]; depth -> (d - z_near)/(z_far - z_near); per-view sum

@@ -129,7 +129,14 @@ class SpatialEncoder(nn.Module):
     # pnr_pyramid_to_latent_backward (deterministic gather, takes the renderer's channel-last grid gradient as it is).
     # False restores torch's interpolate + cat under autograd (A/B timing, comparison tests).
     hip_format_backward = True
-    _TRANSIENT = ("_graphs", "latents", "_nhwc", "_scaling_cache", "_hip_latent")  # per-process caches: rebuilt on demand, never part of a copy / checkpoint
+    # "torch": the trunk below runs as PyTorch-ROCm modules (MIOpen convolutions), for training and inference.  "hip": for
+    # inference the stem, the pool and the residual stages run as pnr_encoder_trunk_forward (csrc/pnr_conv.hip): exact fp32 with
+    # a summation order fixed by each layer's shape, so an encode gives the same bytes from call to call, from process to
+    # process, and per image whatever the batch.  The batch norms are folded into per-channel (scale, shift) in fp64 once
+    # per set of weights (`_hip_trunk`, rebuilt when a parameter or BN buffer is replaced or written in place).  Inference
+    # only: a module in training mode, a call with grad enabled or a non-fp32 / non-HIP input raises (no fallback).
+    trunk = "torch"
+    _TRANSIENT = ("_graphs", "latents", "_nhwc", "_scaling_cache", "_hip_latent", "_hip_trunk")  # per-process caches: rebuilt on demand, never part of a copy / checkpoint
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -141,11 +148,59 @@ class SpatialEncoder(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):
         self.__dict__.pop("_scaling_cache", None)
+        self.__dict__.pop("_hip_trunk", None)
         self.__dict__.pop("_graphs", None)  # the captured launches point at the storages `fn` is about to replace
         return super()._apply(fn, *args, **kwargs)
 
     def _storage_fingerprint(self):
-        return tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
+        fp = tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
+        if self.trunk == "hip":
+            # a capture of the HIP trunk points at the FOLDED (scale, shift), which follow an in-place write only through a rebuild
+            self._hip_trunk_records()
+            fp += ("hip", self._hip_trunk[0])
+        return fp
+
+    def _trunk_convs(self):
+        """(conv, bn) of the trunk in the order the layers run: stem; per block its downsample, conv1, conv2"""
+        m = self.model
+        pairs = [(m.conv1, m.bn1)]
+        for stage in (m.layer1, m.layer2, m.layer3, m.layer4)[: self.num_layers - 1]:
+            for blk in stage:
+                if blk.downsample is not None:
+                    pairs.append((blk.downsample[0], blk.downsample[1]))
+                pairs += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
+        return pairs
+
+    def _hip_trunk_records(self):
+        """the record array of pnr_encoder_trunk_forward with the batch norms folded (fp64, rounded to fp32 once); cached on
+        the address and version of every tensor that enters it"""
+        pairs = self._trunk_convs()
+        tensors = [t for conv, bn in pairs for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        ent = self.__dict__.get("_hip_trunk")
+        if ent is None or ent[0] != key:
+            convs = []
+            for conv, bn in pairs:
+                scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps)
+                shift = bn.bias.detach().double() - bn.running_mean.double() * scale
+                convs.append((conv.weight.detach(), scale.float(), shift.float(), conv.stride[0]))
+            ent = (key,) + ops.encoder_trunk_records(convs)
+            self._hip_trunk = ent
+        return ent[1]
+
+    def _stages_hip(self, x):
+        why = None
+        if self.training:
+            why = "the module is in training mode (batch norm would use batch statistics)"
+        elif torch.is_grad_enabled():
+            why = "grad is enabled (the HIP trunk has no backward)"
+        elif not x.is_cuda or x.dtype != torch.float32:
+            why = f"the input is {x.dtype} on {x.device}, not float32 on a HIP device"
+        if why is not None:
+            raise RuntimeError(f"SpatialEncoder.trunk = 'hip' is inference only and {why}: call net.eval() and encode under "
+                               "torch.no_grad() with a float32 HIP image, or set encoder.trunk = 'torch'")
+        blocks = [len(s) for s in (self.model.layer1, self.model.layer2, self.model.layer3, self.model.layer4)]
+        return ops.encoder_trunk(x, self._hip_trunk_records(), blocks, self.num_layers, self.use_first_pool)
 
     def _graphable(self, x):
         return (self.use_graph and not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
@@ -209,6 +264,10 @@ class SpatialEncoder(nn.Module):
 
     def _stages(self, x):
         """the stem and the first num_layers - 1 residual stages of the trunk; every stage's output is one pyramid level"""
+        if self.trunk == "hip":
+            return self._stages_hip(x)
+        if self.trunk != "torch":
+            raise ValueError(f"SpatialEncoder.trunk must be 'torch' or 'hip', got {self.trunk!r}")
         trunk = self.model
         levels = [trunk.relu(trunk.bn1(trunk.conv1(x)))]
         for depth, stage in enumerate((trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4)[: self.num_layers - 1]):
@@ -302,12 +361,18 @@ class SpatialEncoder(nn.Module):
 
     @classmethod
     def from_conf(cls, conf):
-        return cls(conf.get_string("backbone"), pretrained=conf.get_bool("pretrained", True),
-                   num_layers=conf.get_int("num_layers", 4), index_interp=conf.get_string("index_interp", "bilinear"),
-                   index_padding=conf.get_string("index_padding", "border"),
-                   upsample_interp=conf.get_string("upsample_interp", "bilinear"),
-                   feature_scale=conf.get_float("feature_scale", 1.0),
-                   use_first_pool=conf.get_bool("use_first_pool", True))
+        enc = cls(conf.get_string("backbone"), pretrained=conf.get_bool("pretrained", True),
+                  num_layers=conf.get_int("num_layers", 4), index_interp=conf.get_string("index_interp", "bilinear"),
+                  index_padding=conf.get_string("index_padding", "border"),
+                  upsample_interp=conf.get_string("upsample_interp", "bilinear"),
+                  feature_scale=conf.get_float("feature_scale", 1.0),
+                  use_first_pool=conf.get_bool("use_first_pool", True))
+        trunk = conf.get_string("trunk", "torch")
+        if trunk not in ("torch", "hip"):
+            raise ValueError(f"encoder.trunk must be 'torch' or 'hip', got {trunk!r}")
+        if trunk != "torch":
+            enc.trunk = trunk
+        return enc
 
 
 class ImageEncoder(nn.Module):

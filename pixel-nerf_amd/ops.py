@@ -964,6 +964,102 @@ def pyramid_to_latent_backward(d_latent, stage_shapes, nchw=False):
     return outs
 
 
+def _workspace(nbytes, dev):
+    """caller-owned device scratch of at least `nbytes` (None for 0), from torch's allocator: inside a graph capture it comes
+    from the graph's pool"""
+    return None if nbytes == 0 else torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)
+
+
+def conv2d_affine(x, weight, scale, shift, stride=1, residual=None, relu=False):
+    """pnr_conv2d_affine: y = act(conv(x, weight, stride, padding = k // 2) * scale[c] + shift[c] + residual), exact fp32 with a
+    summation order that depends on (Cin, k) alone.  x (N,Cin,H,W), weight (Cout,Cin,k,k), scale / shift (Cout), residual
+    (N,Cout,Ho,Wo) | None, all fp32 HIP tensors; (k, stride) one of (7,2), (3,1), (3,2), (1,2).  -> (N,Cout,Ho,Wo)."""
+    lib = _lib.load()
+    x = _f32(x, "x", (None, None, None, None))
+    N, Cin, H, W = x.shape
+    weight = _f32(weight, "weight", (None, Cin, None, None))
+    Cout, _, k, k2 = weight.shape
+    if k != k2:
+        raise ValueError(f"weight: expected a square kernel, got {tuple(weight.shape)}")
+    scale, shift = _f32(scale, "scale", (Cout,)), _f32(shift, "shift", (Cout,))
+    stride = int(stride)
+    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+    if residual is not None:
+        residual = _f32(residual, "residual", (N, Cout, Ho, Wo))
+    dev = x.device
+    y = torch.empty((N, Cout, max(Ho, 0), max(Wo, 0)), dtype=torch.float32, device=dev)
+    nbytes = lib.pnr_conv2d_affine_workspace_bytes(N, Cin, H, W, Cout, k, stride)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_conv2d_affine(_p(x), N, Cin, H, W, _p(weight), _p(scale), _p(shift), Cout, k, stride, _p(residual),
+                                         1 if relu else 0, _p(y), _p(ws), nbytes, _stream()), "pnr_conv2d_affine")
+    return y
+
+
+def maxpool2d_3x3s2(x):
+    """pnr_maxpool2d_3x3s2: nn.MaxPool2d(3, 2, 1) of an fp32 HIP tensor (N,C,H,W), bit for bit torch's."""
+    lib = _lib.load()
+    x = _f32(x, "x", (None, None, None, None))
+    N, C, H, W = x.shape
+    y = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pnr_maxpool2d_3x3s2(_p(x), N, C, H, W, _p(y), _stream()), "pnr_maxpool2d_3x3s2")
+    return y
+
+
+def encoder_level_shape(H, W, level, use_first_pool=True):
+    """(h, w) of pyramid level `level` for an (H, W) image: pnr_encoder_level_shape, host arithmetic only"""
+    lib = _lib.load()
+    h, w = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(lib.pnr_encoder_level_shape(int(H), int(W), int(level), 1 if use_first_pool else 0, ctypes.byref(h), ctypes.byref(w)),
+               "pnr_encoder_level_shape")
+    return h.value, w.value
+
+
+def encoder_trunk_records(convs):
+    """convs: [(weight (Cout,Cin,k,k), scale (Cout), shift (Cout), stride)] in the order the layers run -> (the host array of
+    PnrConvRecord that pnr_encoder_trunk_forward takes, the tensors it points into: keep both alive together)"""
+    keep, recs = [], (_lib.PnrConvRecord * len(convs))()
+    for i, (weight, scale, shift, stride) in enumerate(convs):
+        weight = _f32(weight, f"convs[{i}].weight", (None, None, None, None))
+        Cout, Cin, k, _ = weight.shape
+        scale, shift = _f32(scale, f"convs[{i}].scale", (Cout,)), _f32(shift, f"convs[{i}].shift", (Cout,))
+        keep += [weight, scale, shift]
+        recs[i].w, recs[i].scale, recs[i].shift = weight.data_ptr(), scale.data_ptr(), shift.data_ptr()
+        recs[i].cin, recs[i].cout, recs[i].ksize, recs[i].stride = Cin, Cout, k, int(stride)
+    return recs, keep
+
+
+def encoder_trunk(images, records, blocks, n_levels, use_first_pool=True):
+    """pnr_encoder_trunk_forward: the ResNet trunk of the encoder for inference, one host loop over conv2d_affine and
+    maxpool2d_3x3s2.  images (NV,3,H,W) fp32 HIP; records: encoder_trunk_records(...)[0]; blocks: the BasicBlock counts of the
+    four stages.  -> the list of n_levels pyramid levels (NV,C_i,h_i,w_i), what SpatialEncoder._stages returns."""
+    lib = _lib.load()
+    images = _f32(images, "images", (None, 3, None, None))
+    NV, _, H, W = images.shape
+    if len(blocks) != 4:
+        raise ValueError("blocks: the BasicBlock counts of the four residual stages, e.g. (3, 4, 6, 3)")
+    n_levels = int(n_levels)
+    if not 1 <= n_levels <= 5:
+        raise ValueError(f"n_levels must be in [1, 5], got {n_levels}")
+    blk = (ctypes.c_int * 4)(*[int(b) for b in blocks])
+    pool = 1 if use_first_pool else 0
+    dev = images.device
+    levels = []
+    for i in range(n_levels):
+        h, w = encoder_level_shape(H, W, i, use_first_pool)
+        levels.append(torch.empty((NV, (64, 64, 128, 256, 512)[i], h, w), dtype=torch.float32, device=dev))
+    if NV == 0:
+        return levels
+    ptrs = (ctypes.c_void_p * n_levels)(*[t.data_ptr() for t in levels])
+    nbytes = lib.pnr_encoder_trunk_workspace_bytes(blk, n_levels, pool, NV, H, W)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_encoder_trunk_forward(records, len(records), blk, n_levels, pool, _p(images), NV, H, W, ptrs, _p(ws),
+                                                 nbytes, _stream()), "pnr_encoder_trunk_forward")
+    return levels
+
+
 def sample_training_rays(poses, images, focal, z_near, z_far, ids, c=None, bboxes=None, ux=None, uy=None):
     """train/train.py:143-182 on device.  poses (SB,NV,4,4), images (SB,NV,3,H,W) in [-1,1], focal (SB,2),
     c (SB,2)|None; ids (SB,B) int64: view ids (with bboxes (SB,NV,4) + ux, uy (SB,B)) or flat pixel indices.
