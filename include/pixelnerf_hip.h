@@ -692,6 +692,104 @@ int pnr_encoder_trunk_forward(const PnrConvRecord *convs /*host*/, int n_convs, 
                               int use_first_pool, const float *images, int NV, int H, int W, float *const *levels /*host*/,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the encoder's ResNet trunk under training (added within ABI rev 12) ---------------------
+ * The same trunk with batch norm in BATCH mode and a backward for every layer (trainer.py:180 net.train(), Adam over
+ * net.parameters()).  fp32 in and out, NCHW, contiguous; exact fp32 arithmetic (sums of the batch norm in fp64); no atomics;
+ * every output element is written; no host synchronisation and no device -> host copy, so a forward + backward can be captured
+ * into a HIP graph.  Every reduction runs in an order fixed by the layer's shape alone: two calls give equal bytes.
+ *
+ * pnr_batchnorm2d_train_forward:  v (N,C,H,W) the raw convolution output, M = N H W values per channel, numbered
+ *   m = (n H + y) W + x.
+ *     mean = sum v / M, var = sum (v - mean)^2 / M (biased), both accumulated in fp64 (order below);
+ *     save_mean = fp32(mean), save_invstd = fp32(1 / sqrt(var + eps));
+ *     xhat = (v - save_mean) save_invstd;  y = act(fma(xhat, gamma, beta) + res);   res nullable, act = ReLU when relu != 0;
+ *     running_mean <- (1 - momentum) running_mean + momentum mean, running_var likewise with the unbiased M / (M - 1) var
+ *     (formed in fp64, rounded once), when the two pointers are not NULL -- nn.BatchNorm2d in training mode.
+ *   frozen != 0 is the module in eval() with grad enabled: mean and var ARE running_mean and running_var (required), nothing
+ *   is updated.  M < 2 in batch mode is refused, as torch refuses it.
+ *   ORDER: the M values are cut into S contiguous slices (S = 1 below M = 8192, else min(64, M / 4096)) of ceil(M / S) values
+ *   rounded up to 256.  Within a slice thread t of 256 adds m = begin + t, + 256, ... ascending into one fp64 sum from +0;
+ *   the 256 sums are folded a[t] += a[t + s], s = 128, 64, .., 1; the slices are added in ascending order.  A function of M alone.
+ * pnr_batchnorm2d_backward:  g_y the gradient of y; y (nullable) the forward's output, given when the layer had a ReLU:
+ *   g = g_y where y > 0, else 0 (g = g_y without y).  d_res (nullable) receives g: the residual branch's gradient.
+ *     d_beta = sum g, d_gamma = sum g xhat (fp64, the product formed in fp64, the forward's order), rounded to fp32;
+ *     d_v = gamma save_invstd (g - mean(g) - xhat mean(g xhat)), the two means rounded to fp32 first;
+ *     frozen: d_v = gamma save_invstd g.
+ *   d_v and d_res must not overlap g_y, y or v.
+ *   workspace (both): pnr_batchnorm2d_*_workspace_bytes(N, C, H, W) bytes, 8-byte aligned, required.
+ * pnr_conv2d_backward_data:  d_x[n,ci,iy,ix] = sum_{co,ky,kx} d_y[n,co,oy,ox] w[co,ci,ky,kx] over the (oy, ox) with
+ *   oy s - p + ky = iy, ox s - p + kx = ix: a gather.  The K = Cout k k terms are taken in ascending (co, ky, kx), terms that
+ *   do not exist enter as zeros, and K is cut into slices and quarters exactly as pnr_conv2d_affine cuts Cin k k:
+ *   pnr_conv2d_affine_slices(Cout, k) partial sums meet in one element.  d_x == NULL is a no-op (the stem's is wanted only
+ *   when the image requires grad).  Shapes as pnr_conv2d_affine (the forward layer's N, Cin, H, W, Cout, ksize, stride).
+ * pnr_conv2d_backward_weight:  d_w[co,ci,ky,kx] = sum_{n,oy,ox} d_y[n,co,oy,ox] x[n,ci, oy s - p + ky, ox s - p + kx], the
+ *   P = N Ho Wo terms in ascending p = (n Ho + oy) Wo + ox.  P is cut into S slices, S = 1 (P < 1024), 8 (P < 16384), else 64,
+ *   of ceil(P / S) terms rounded up to 64, every slice into four quarters; quarters and slices are added as in the forward.
+ *   pnr_conv2d_backward_weight_slices(P) = 4 S.  A function of P alone.  N >= 1.
+ * pnr_maxpool2d_3x3s2_backward:  x (N,C,H,W) the pool's input, g_y (N,C,Ho,Wo) -> d_x (N,C,H,W).  A gather: an input pixel
+ *   adds the gradients of the <= 4 windows that hold it and whose FIRST maximum in (ky, kx) scan order it is (the forward's
+ *   rule and torch's: it decides the ties at 0 behind a ReLU), in ascending (oy, ox).  Equals torch's CPU result bit for bit.
+ *   Needs no workspace.
+ * PNR_E_INVALID, before any HIP call, the message prefixed with the entry's name: a null or misaligned pointer (the nullable
+ *   ones excepted), a bad size or (ksize, stride), channel counts outside pnr_conv2d_affine's rule, N H W or N Ho Wo >= 2^31,
+ *   M < 2 in batch mode, a workspace that is too small.  N = 0 is a no-op (refused by pnr_conv2d_backward_weight). */
+size_t pnr_batchnorm2d_train_forward_workspace_bytes(int N, int C, int H, int W);
+size_t pnr_batchnorm2d_backward_workspace_bytes(int N, int C, int H, int W);
+int pnr_batchnorm2d_train_forward(const float *v, int N, int C, int H, int W, const float *gamma, const float *beta,
+                                  float *running_mean /*nullable*/, float *running_var /*nullable*/, double eps,
+                                  double momentum, int frozen, const float *res /*nullable*/, int relu, float *y,
+                                  float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+int pnr_batchnorm2d_backward(const float *g_y, const float *y /*nullable*/, const float *v, const float *save_mean,
+                             const float *save_invstd, const float *gamma, int N, int C, int H, int W, int frozen,
+                             float *d_v, float *d_gamma, float *d_beta, float *d_res /*nullable*/, void *workspace,
+                             size_t workspace_bytes, void *stream);
+size_t pnr_conv2d_backward_data_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ksize, int stride);
+int pnr_conv2d_backward_data(const float *d_y, const float *w, int N, int Cin, int H, int W, int Cout, int ksize,
+                             int stride, float *d_x /*nullable*/, void *workspace, size_t workspace_bytes, void *stream);
+int pnr_conv2d_backward_weight_slices(long long P);
+size_t pnr_conv2d_backward_weight_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ksize, int stride);
+int pnr_conv2d_backward_weight(const float *d_y, const float *x, int N, int Cin, int H, int W, int Cout, int ksize,
+                               int stride, float *d_w, void *workspace, size_t workspace_bytes, void *stream);
+int pnr_maxpool2d_3x3s2_backward(const float *x, const float *g_y, int N, int C, int H, int W, float *d_x, void *stream);
+
+/* One convolution of the trunk with its batch norm, for training (host struct of device pointers). */
+typedef struct PnrConvTrainRecord {
+    const float *w;        /* (cout, cin, ksize, ksize) */
+    const float *gamma;    /* (cout) */
+    const float *beta;     /* (cout) */
+    float *running_mean;   /* (cout); nullable together with running_var unless frozen */
+    float *running_var;
+    float *d_w;            /* backward only: where the three gradients go, every element written */
+    float *d_gamma;
+    float *d_beta;
+    double eps, momentum;
+    int32_t cin, cout, ksize, stride;
+} PnrConvTrainRecord;
+
+/* The whole trunk forward and backward as host loops over the entries above and pnr_conv2d_affine (scale 1, shift 0: the raw
+ * convolution) / pnr_maxpool2d_3x3s2; arguments as pnr_encoder_trunk_forward, the records in the same order.  The library owns
+ * no memory: `saved` (pnr_encoder_trunk_train_saved_bytes, 8-byte aligned) receives in the forward what the backward reads --
+ * every raw convolution, every layer output that is not a level, the pooled stem, every (mean, invstd) -- and must reach the
+ * backward unchanged together with images and levels.  workspace: pnr_encoder_trunk_train_workspace_bytes, 8-byte aligned,
+ * serves both calls and carries nothing between them.  frozen as in pnr_batchnorm2d_train_forward, for every batch norm.
+ * Backward: d_levels (HOST array of n_levels device pointers, all required) are the gradients of the levels; a level's own
+ * gradient is added last, (d_conv1 + d_identity) + d_level; d_images (NV,3,H,W) is nullable.  The forward updates the running
+ * statistics of every record that has them (batch mode); num_batches_tracked is the caller's.
+ * The bytes are those of the per-layer entries chained by hand.  Refusals as pnr_encoder_trunk_forward, plus M < 2 for any
+ * batch norm in batch mode.  NV = 0 is a no-op. */
+size_t pnr_encoder_trunk_train_saved_bytes(const int *blocks /*host*/, int n_levels, int use_first_pool, int NV, int H, int W);
+size_t pnr_encoder_trunk_train_workspace_bytes(const int *blocks /*host*/, int n_levels, int use_first_pool, int NV, int H, int W);
+int pnr_encoder_trunk_train_forward(const PnrConvTrainRecord *convs /*host*/, int n_convs, const int *blocks /*host*/,
+                                    int n_levels, int use_first_pool, int frozen, const float *images, int NV, int H, int W,
+                                    float *const *levels /*host*/, void *saved, size_t saved_bytes, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+int pnr_encoder_trunk_backward(const PnrConvTrainRecord *convs /*host*/, int n_convs, const int *blocks /*host*/,
+                               int n_levels, int use_first_pool, int frozen, const float *images, int NV, int H, int W,
+                               const float *const *levels /*host*/, const float *const *d_levels /*host*/, const void *saved,
+                               size_t saved_bytes, float *d_images /*nullable*/, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
 /* ---- next-row helpers: eval epilogue on device ----------------------
  * eval/eval.py:283-290,327-329 and util.psnr (src/util/util.py:474-481): rgb (n_views,pixels,3) ->
  * clamp to [0,1] [-> uint8 = trunc(x*255)]; depth -> (d - z_near)/(z_far - z_near); per-view sum

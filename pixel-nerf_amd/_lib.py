@@ -15,8 +15,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # experiment switch is compiled with -DPNR_VARIANT and reports a NEGATIVE ABI revision: load() refuses it unless the
 # process says PIXELNERF_ALLOW_VARIANT=1 (the A/B tools do) -- a stray -D can no longer yield a library that passes for the product
 LIB_PATH = os.environ.get("PIXELNERF_HIP_LIB") or os.path.join(CSRC, "libpixelnerf_hip.so")
-SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_bwd_split.hip", "pnr_scatter.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip", "pnr_mesh.hip", "pnr_occupancy.hip", "pnr_meshfinish.hip", "pnr_baked.hip", "pnr_baked_grad.hip", "pnr_baked_scene.hip", "pnr_baked_tv.hip", "pnr_baked_visibility.hip", "pnr_baked_resample.hip", "pnr_conv.hip"]
-HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_geom.h", "pnr_wave.h", "pnr_raysrc.h", "pnr_internal.h", "pnr_entry.h", "pnr_split_ops.h", "pnr_scatter_plan.h", "pnr_occgrid.h", "pnr_baked.h", "pnr_baked_grad.h", "pnr_mc_tables.inc", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
+SOURCES = ["pnr_api.hip", "pnr_pack.hip", "pnr_render.hip", "pnr_mlp.hip", "pnr_split.hip", "pnr_bwd.hip", "pnr_bwd_split.hip", "pnr_scatter.hip", "pnr_f32.hip", "pnr_encode.hip", "pnr_camera.hip", "pnr_mesh.hip", "pnr_occupancy.hip", "pnr_meshfinish.hip", "pnr_baked.hip", "pnr_baked_grad.hip", "pnr_baked_scene.hip", "pnr_baked_tv.hip", "pnr_baked_visibility.hip", "pnr_baked_resample.hip", "pnr_conv.hip", "pnr_conv_bwd.hip"]
+HEADERS = ["pnr_common.h", "pnr_layout.h", "pnr_device.h", "pnr_geom.h", "pnr_wave.h", "pnr_raysrc.h", "pnr_internal.h", "pnr_entry.h", "pnr_split_ops.h", "pnr_scatter_plan.h", "pnr_occgrid.h", "pnr_baked.h", "pnr_baked_grad.h", "pnr_conv.h", "pnr_mc_tables.inc", os.path.join("..", "..", "include", "pixelnerf_hip.h")]
 
 ABI_VERSION = 12  # PNR_ABI_VERSION of the include/pixelnerf_hip.h this binding (struct layouts, argtypes below) was written against
 PREC_F16, PREC_BF16, PREC_F32, PREC_F16X3 = 0, 1, 2, 3
@@ -81,6 +81,14 @@ class PnrConvRecord(ctypes.Structure):
                 ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("ksize", ctypes.c_int32), ("stride", ctypes.c_int32)]
 
 
+class PnrConvTrainRecord(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
+                ("d_w", ctypes.c_void_p), ("d_gamma", ctypes.c_void_p), ("d_beta", ctypes.c_void_p),
+                ("eps", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("ksize", ctypes.c_int32), ("stride", ctypes.c_int32)]
+
+
 BAKED_SCENE_MAX_OBJECTS = 8  # PNR_BAKED_SCENE_MAX_OBJECTS
 
 
@@ -128,6 +136,23 @@ PROTOTYPES = {
     "pnr_encoder_trunk_workspace_bytes": (_SZ, [ctypes.POINTER(_I), _I, _I, _I, _I, _I]),
     "pnr_encoder_trunk_forward": (_I, [ctypes.POINTER(PnrConvRecord), _I, ctypes.POINTER(_I), _I, _I, _P, _I, _I, _I,
                                        ctypes.POINTER(ctypes.c_void_p), _P, _SZ, _P]),
+    "pnr_batchnorm2d_train_forward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "pnr_batchnorm2d_backward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "pnr_batchnorm2d_train_forward": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _I, _P, _I, _P, _P, _P,
+                                           _P, _SZ, _P]),
+    "pnr_batchnorm2d_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "pnr_conv2d_backward_data_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
+    "pnr_conv2d_backward_data": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "pnr_conv2d_backward_weight_slices": (_I, [ctypes.c_longlong]),
+    "pnr_conv2d_backward_weight_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
+    "pnr_conv2d_backward_weight": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "pnr_maxpool2d_3x3s2_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "pnr_encoder_trunk_train_saved_bytes": (_SZ, [ctypes.POINTER(_I), _I, _I, _I, _I, _I]),
+    "pnr_encoder_trunk_train_workspace_bytes": (_SZ, [ctypes.POINTER(_I), _I, _I, _I, _I, _I]),
+    "pnr_encoder_trunk_train_forward": (_I, [ctypes.POINTER(PnrConvTrainRecord), _I, ctypes.POINTER(_I), _I, _I, _I, _P, _I, _I, _I,
+                                             ctypes.POINTER(ctypes.c_void_p), _P, _SZ, _P, _SZ, _P]),
+    "pnr_encoder_trunk_backward": (_I, [ctypes.POINTER(PnrConvTrainRecord), _I, ctypes.POINTER(_I), _I, _I, _I, _P, _I, _I, _I,
+                                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _P, _SZ, _P, _P, _SZ, _P]),
     "pnr_grid_index": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "pnr_grid_index_backward": (_I, [_P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P, _P]),
     "pnr_positional_encoding": (_I, [_P, ctypes.c_longlong, _I, _I, _P, _P, _I, _P, _P]),

@@ -483,6 +483,40 @@ def pyramid_to_latent_autograd(levels):
     return _PyramidFunction.apply(*levels)
 
 
+class _EncoderTrunkFunction(torch.autograd.Function):
+    """The encoder's ResNet trunk as ONE autograd node: forward = pnr_encoder_trunk_train_forward (batch norm in batch mode, or
+    the frozen form), backward = pnr_encoder_trunk_backward.  Inputs: the image and, per convolution in the order the layers
+    run, (weight, gamma, beta); outputs: the pyramid levels.  The running statistics are updated in place by the forward."""
+
+    @staticmethod
+    def forward(ctx, cfg, image, *params):
+        stats, blocks, n_levels, pool, frozen = cfg
+        convs = [(params[3 * i].detach(), params[3 * i + 1].detach(), params[3 * i + 2].detach()) + tuple(stats[i]) for i in range(len(stats))]
+        records, keep = ops.encoder_trunk_train_records(convs)
+        image = image.detach().contiguous()
+        levels, saved = ops.encoder_trunk_train_forward(image, records, blocks, n_levels, pool, frozen)
+        ctx.cfg, ctx.records, ctx.keep = (blocks, n_levels, pool, frozen), records, keep
+        ctx.save_for_backward(image, saved, *levels)
+        return tuple(levels)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *d_levels):
+        blocks, n_levels, pool, frozen = ctx.cfg
+        image, saved, *levels = ctx.saved_tensors
+        d_levels = [g.float().contiguous() for g in d_levels]
+        grads, d_image = ops.encoder_trunk_backward(image, ctx.records, blocks, n_levels, pool, frozen, levels, d_levels, saved,
+                                                    want_images=ctx.needs_input_grad[1])
+        flat = [g if need else None for g, need in zip((g for t in grads for g in t), ctx.needs_input_grad[2:])]
+        return (None, d_image, *flat)
+
+
+def encoder_trunk_autograd(image, params, stats, blocks, n_levels, use_first_pool, frozen):
+    """params: [weight, gamma, beta] * n_convs, flat; stats: [(running_mean, running_var, eps, momentum, stride)] per convolution
+    -> the list of pyramid levels with the HIP backward behind them"""
+    return list(_EncoderTrunkFunction.apply((stats, tuple(blocks), n_levels, use_first_pool, frozen), image, *params))
+
+
 def _channel_last_grad(net, latent):
     """may the grid gradient of this call stay channel-last memory?  Only for the latent the encoder's own HIP node made."""
     enc = getattr(net, "encoder", None)

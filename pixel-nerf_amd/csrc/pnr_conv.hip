@@ -15,24 +15,9 @@
 // quarter of that per wave and four times the workgroups.
 #include <cstdio>
 
-#include "pnr_common.h"
+#include "pnr_conv.h"  // the tile and slice constants, the shape rules: shared with the training entries (pnr_conv_bwd.hip)
 
 namespace pnr {
-
-constexpr int CV_BM = 32;   // output channels per workgroup
-constexpr int CV_BN = 32;   // output pixels per workgroup (pixels of the whole batch, flattened: n, oy, ox)
-constexpr int CV_BK = 16;   // reduction terms a wave stages per chunk
-constexpr int CV_LD = 36;   // LDS row stride in floats: 16-byte aligned rows, 4 floats of padding
-constexpr int CV_WAVES = 4; // quarters of a slice = waves of a workgroup
-constexpr int CV_SLICE = 576;  // a reduction of >= 2 CV_SLICE terms is cut into slices of about that length ...
-constexpr int CV_MAX_SLICES = 8;  // ... at most this many
-
-inline int conv_slices(long long K) { return K >= 2 * CV_SLICE ? (int)(K / CV_SLICE < CV_MAX_SLICES ? K / CV_SLICE : CV_MAX_SLICES) : 1; }
-inline int conv_slice_len(long long K) {
-    const int n = conv_slices(K);
-    const long long per = (K + n - 1) / n;
-    return (int)((per + 63) / 64 * 64);  // a quarter is a whole number of chunks
-}
 
 struct ConvParams {
     const float *x, *w, *scale, *shift, *res;
@@ -180,18 +165,8 @@ __global__ __launch_bounds__(256) void maxpool_3x3s2_kernel(const float *x, floa
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int conv_fail(const char *entry, const char *what) {
-    char msg[256];
-    std::snprintf(msg, sizeof(msg), "%s: %s", entry, what);
-    return pnr_fail(PNR_E_INVALID, msg);
-}
-
-inline int conv_pad(int ksize) { return ksize / 2; }
-inline int conv_out(int n, int ksize, int stride) { return (n + 2 * conv_pad(ksize) - ksize) / stride + 1; }
-inline bool misaligned(const void *p) { return ((size_t)p & 3) != 0; }
-
 // what is wrong with a layer's shape (nullptr: nothing)
-static const char *conv_shape_defect(int N, int Cin, int H, int W, int Cout, int ksize, int stride) {
+const char *conv_shape_defect(int N, int Cin, int H, int W, int Cout, int ksize, int stride) {
     if (N < 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return "bad sizes (N >= 0; Cin, H, W, Cout > 0)";
     if (!((ksize == 7 && stride == 2) || (ksize == 3 && stride == 1) || (ksize == 3 && stride == 2) || (ksize == 1 && stride == 2)))
         return "(ksize, stride) must be one of (7,2), (3,1), (3,2), (1,2)";
@@ -205,7 +180,7 @@ static const char *conv_shape_defect(int N, int Cin, int H, int W, int Cout, int
     return nullptr;
 }
 
-static size_t conv_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ksize, int stride) {
+size_t conv_workspace_bytes(int N, int Cin, int H, int W, int Cout, int ksize, int stride) {
     const int n_sl = conv_slices((long long)Cin * ksize * ksize);
     if (n_sl == 1) return 0;
     return (size_t)n_sl * N * Cout * conv_out(H, ksize, stride) * conv_out(W, ksize, stride) * sizeof(float);
@@ -226,8 +201,8 @@ static int conv_check(const char *entry, const float *x, int N, int Cin, int H, 
 }
 
 // launches of one checked layer
-static void conv_launch(const float *x, int N, int Cin, int H, int W, const float *w, const float *scale, const float *shift, int Cout,
-                        int ksize, int stride, const float *res, int relu, float *y, void *workspace, hipStream_t stream) {
+void conv_launch(const float *x, int N, int Cin, int H, int W, const float *w, const float *scale, const float *shift, int Cout,
+                 int ksize, int stride, const float *res, int relu, float *y, void *workspace, hipStream_t stream) {
     ConvParams q = {};
     q.x = x; q.w = w; q.scale = scale; q.shift = shift; q.res = res; q.y = y; q.part = (float *)workspace;
     q.N = N; q.Cin = Cin; q.H = H; q.W = W; q.Cout = Cout; q.stride = stride; q.pad = conv_pad(ksize);
@@ -249,15 +224,13 @@ static const char *pool_defect(const float *x, int N, int C, int H, int W, const
     return nullptr;
 }
 
-static void pool_launch(const float *x, int N, int C, int H, int W, float *y, hipStream_t stream) {
+void pool_launch(const float *x, int N, int C, int H, int W, float *y, hipStream_t stream) {
     const int Ho = conv_out(H, 3, 2), Wo = conv_out(W, 3, 2);
     const long long total = (long long)N * C * Ho * Wo;
     hipLaunchKernelGGL(maxpool_3x3s2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, y, H, W, Ho, Wo, total);
 }
 
 // ---- the whole trunk: one walk that either sizes the scratch (run == false) or launches
-constexpr size_t TRUNK_ALIGN = 256;
-inline size_t align_up(size_t b) { return (b + TRUNK_ALIGN - 1) / TRUNK_ALIGN * TRUNK_ALIGN; }
 
 struct TrunkShape {
     int h[5], w[5];      // level sizes

@@ -135,6 +135,10 @@ class SpatialEncoder(nn.Module):
     # process, and per image whatever the batch.  The batch norms are folded into per-channel (scale, shift) in fp64 once
     # per set of weights (`_hip_trunk`, rebuilt when a parameter or BN buffer is replaced or written in place).  Inference
     # only: a module in training mode, a call with grad enabled or a non-fp32 / non-HIP input raises (no fallback).
+    # "hip_train": under no_grad in eval mode exactly what "hip" runs (the same bytes); with grad enabled or in training mode the
+    # trunk is ONE autograd node over pnr_encoder_trunk_train_forward / pnr_encoder_trunk_backward (csrc/pnr_conv_bwd.hip): batch
+    # norm with batch statistics (a module in eval() with grad enabled: the frozen form, running statistics), every gradient in
+    # an order fixed by the layer's shape -- a training step through the encoder gives equal bytes from run to run.
     trunk = "torch"
     _TRANSIENT = ("_graphs", "latents", "_nhwc", "_scaling_cache", "_hip_latent", "_hip_trunk")  # per-process caches: rebuilt on demand, never part of a copy / checkpoint
 
@@ -154,7 +158,7 @@ class SpatialEncoder(nn.Module):
 
     def _storage_fingerprint(self):
         fp = tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
-        if self.trunk == "hip":
+        if self.trunk in ("hip", "hip_train"):
             # a capture of the HIP trunk points at the FOLDED (scale, shift), which follow an in-place write only through a rebuild
             self._hip_trunk_records()
             fp += ("hip", self._hip_trunk[0])
@@ -201,6 +205,59 @@ class SpatialEncoder(nn.Module):
                                "torch.no_grad() with a float32 HIP image, or set encoder.trunk = 'torch'")
         blocks = [len(s) for s in (self.model.layer1, self.model.layer2, self.model.layer3, self.model.layer4)]
         return ops.encoder_trunk(x, self._hip_trunk_records(), blocks, self.num_layers, self.use_first_pool)
+
+    def _stages_hip_train(self, x):
+        """the trunk under autograd through HIP (trunk = "hip_train"), or, under no_grad in eval mode, `_stages_hip`"""
+        if not self.training and not torch.is_grad_enabled():
+            if not x.is_cuda or x.dtype != torch.float32:
+                raise RuntimeError(f"SpatialEncoder.trunk = 'hip_train' runs float32 images on a HIP device, the input is {x.dtype} on "
+                                   f"{x.device}: move / convert the image, or set encoder.trunk = 'torch'")
+            return self._stages_hip(x)
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise RuntimeError(f"SpatialEncoder.trunk = 'hip_train' runs float32 images on a HIP device, the input is {x.dtype} on "
+                               f"{x.device}: move / convert the image (no autocast), or set encoder.trunk = 'torch'")
+        pairs = self._trunk_convs()
+        frozen = not self.training
+        for _, bn in pairs:
+            if bn.running_mean is None or bn.running_var is None or bn.momentum is None:
+                raise RuntimeError("SpatialEncoder.trunk = 'hip_train' needs batch norms with running statistics and a fixed momentum "
+                                   "(track_running_stats=True, momentum is not None): rebuild the module with nn.BatchNorm2d's defaults, "
+                                   "or set encoder.trunk = 'torch'")
+        if not frozen:
+            for (conv, _), (h, w) in zip(pairs, self._trunk_out_sizes(x.shape[-2], x.shape[-1])):
+                if x.shape[0] * h * w < 2:
+                    raise RuntimeError(f"SpatialEncoder.trunk = 'hip_train': a batch norm of this trunk would see {x.shape[0] * h * w} value "
+                                       f"per channel for a {tuple(x.shape)} input, batch statistics need at least 2: send a larger image "
+                                       "or more views, or call net.eval() (the frozen form)")
+        params, stats = [], []
+        for conv, bn in pairs:
+            params += [conv.weight, bn.weight, bn.bias]
+            stats.append((bn.running_mean, bn.running_var, bn.eps, bn.momentum, conv.stride[0]))
+        blocks = [len(s) for s in (self.model.layer1, self.model.layer2, self.model.layer3, self.model.layer4)]
+        levels = autograd.encoder_trunk_autograd(x, params, stats, blocks, self.num_layers, self.use_first_pool, frozen)
+        if not frozen:
+            with torch.no_grad():
+                for _, bn in pairs:
+                    bn.num_batches_tracked.add_(1)
+                    # the kernels wrote the running statistics behind torch's back: say so, so that whatever is cached on their
+                    # version (the folded records of an inference encode, its captured graphs) is rebuilt
+                    torch.autograd.graph.increment_version(bn.running_mean)
+                    torch.autograd.graph.increment_version(bn.running_var)
+        return levels
+
+    def _trunk_out_sizes(self, H, W):
+        """(h, w) of every convolution's output in `_trunk_convs` order"""
+        out = lambda n, k, s: (n + 2 * (k // 2) - k) // s + 1
+        h, w = out(H, 7, 2), out(W, 7, 2)
+        sizes = [(h, w)]
+        if self.use_first_pool and self.num_layers > 1:
+            h, w = out(h, 3, 2), out(w, 3, 2)
+        for depth, stage in enumerate((self.model.layer1, self.model.layer2, self.model.layer3, self.model.layer4)[: self.num_layers - 1]):
+            for j, blk in enumerate(stage):
+                if j == 0 and depth > 0:
+                    h, w = out(h, 3, 2), out(w, 3, 2)
+                sizes += [(h, w)] * (3 if blk.downsample is not None else 2)
+        return sizes
 
     def _graphable(self, x):
         return (self.use_graph and not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
@@ -266,8 +323,10 @@ class SpatialEncoder(nn.Module):
         """the stem and the first num_layers - 1 residual stages of the trunk; every stage's output is one pyramid level"""
         if self.trunk == "hip":
             return self._stages_hip(x)
+        if self.trunk == "hip_train":
+            return self._stages_hip_train(x)
         if self.trunk != "torch":
-            raise ValueError(f"SpatialEncoder.trunk must be 'torch' or 'hip', got {self.trunk!r}")
+            raise ValueError(f"SpatialEncoder.trunk must be 'torch', 'hip' or 'hip_train', got {self.trunk!r}")
         trunk = self.model
         levels = [trunk.relu(trunk.bn1(trunk.conv1(x)))]
         for depth, stage in enumerate((trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4)[: self.num_layers - 1]):
@@ -368,8 +427,8 @@ class SpatialEncoder(nn.Module):
                   feature_scale=conf.get_float("feature_scale", 1.0),
                   use_first_pool=conf.get_bool("use_first_pool", True))
         trunk = conf.get_string("trunk", "torch")
-        if trunk not in ("torch", "hip"):
-            raise ValueError(f"encoder.trunk must be 'torch' or 'hip', got {trunk!r}")
+        if trunk not in ("torch", "hip", "hip_train"):
+            raise ValueError(f"encoder.trunk must be 'torch', 'hip' or 'hip_train', got {trunk!r}")
         if trunk != "torch":
             enc.trunk = trunk
         return enc

@@ -1060,6 +1060,201 @@ def encoder_trunk(images, records, blocks, n_levels, use_first_pool=True):
     return levels
 
 
+def _workspace8(nbytes, dev):
+    """caller-owned device scratch for entries that keep fp64 sums in it (torch's allocator aligns far beyond 8 bytes)"""
+    return torch.empty(((max(nbytes, 8) + 7) // 8,), dtype=torch.float64, device=dev)
+
+
+def batchnorm2d_train_forward(v, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, frozen=False,
+                              residual=None, relu=False):
+    """pnr_batchnorm2d_train_forward: nn.BatchNorm2d in training mode (batch statistics in fp64, a fixed order) + residual + ReLU
+    on v (N,C,H,W) fp32 HIP; running_mean / running_var (C) are updated IN PLACE when given.  frozen: the statistics are the
+    running ones, nothing is updated.  -> (y, save_mean (C), save_invstd (C))"""
+    lib = _lib.load()
+    v = _f32(v, "v", (None, None, None, None))
+    N, C, H, W = v.shape
+    gamma, beta = _f32(gamma, "gamma", (C,)), _f32(beta, "beta", (C,))
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together or not at all")
+    if running_mean is not None:
+        for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+            if _f32(t, name, (C,)) is not t:
+                raise ValueError(f"{name}: must be contiguous (it is updated in place)")
+    if residual is not None:
+        residual = _f32(residual, "residual", (N, C, H, W))
+    dev = v.device
+    y = torch.empty_like(v)
+    mean, invstd = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+    nbytes = lib.pnr_batchnorm2d_train_forward_workspace_bytes(N, C, H, W)
+    ws = _workspace8(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_batchnorm2d_train_forward(_p(v), N, C, H, W, _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps),
+                                                     float(momentum), 1 if frozen else 0, _p(residual), 1 if relu else 0, _p(y), _p(mean),
+                                                     _p(invstd), _p(ws), ws.numel() * 8, _stream()), "pnr_batchnorm2d_train_forward")
+    return y, mean, invstd
+
+
+def batchnorm2d_backward(g_y, y, v, save_mean, save_invstd, gamma, frozen=False, want_res=False):
+    """pnr_batchnorm2d_backward: g_y the gradient of the layer's output, y that output when the layer had a ReLU (else None),
+    v the batch norm's input.  -> (d_v, d_gamma, d_beta, d_res | None); d_res is the gradient behind the ReLU mask."""
+    lib = _lib.load()
+    v = _f32(v, "v", (None, None, None, None))
+    N, C, H, W = v.shape
+    g_y = _f32(g_y, "g_y", (N, C, H, W))
+    if y is not None:
+        y = _f32(y, "y", (N, C, H, W))
+    save_mean, save_invstd, gamma = _f32(save_mean, "save_mean", (C,)), _f32(save_invstd, "save_invstd", (C,)), _f32(gamma, "gamma", (C,))
+    dev = v.device
+    d_v = torch.empty_like(v)
+    d_gamma, d_beta = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+    d_res = torch.empty_like(v) if want_res else None
+    ws = _workspace8(lib.pnr_batchnorm2d_backward_workspace_bytes(N, C, H, W), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_batchnorm2d_backward(_p(g_y), _p(y), _p(v), _p(save_mean), _p(save_invstd), _p(gamma), N, C, H, W,
+                                                1 if frozen else 0, _p(d_v), _p(d_gamma), _p(d_beta), _p(d_res), _p(ws), ws.numel() * 8,
+                                                _stream()), "pnr_batchnorm2d_backward")
+    return d_v, d_gamma, d_beta, d_res
+
+
+def conv2d_backward_data(d_y, weight, x_shape, stride=1):
+    """pnr_conv2d_backward_data: the gradient of conv2d_affine's input.  d_y (N,Cout,Ho,Wo), weight (Cout,Cin,k,k),
+    x_shape = (N,Cin,H,W) of the forward's input.  -> d_x (N,Cin,H,W)"""
+    lib = _lib.load()
+    N, Cin, H, W = (int(s) for s in x_shape)
+    weight = _f32(weight, "weight", (None, Cin, None, None))
+    Cout, _, k, k2 = weight.shape
+    if k != k2:
+        raise ValueError(f"weight: expected a square kernel, got {tuple(weight.shape)}")
+    stride = int(stride)
+    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+    d_y = _f32(d_y, "d_y", (N, Cout, Ho, Wo))
+    dev = d_y.device
+    d_x = torch.empty((N, Cin, H, W), dtype=torch.float32, device=dev)
+    nbytes = lib.pnr_conv2d_backward_data_workspace_bytes(N, Cin, H, W, Cout, k, stride)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_conv2d_backward_data(_p(d_y), _p(weight), N, Cin, H, W, Cout, k, stride, _p(d_x), _p(ws), nbytes, _stream()),
+                   "pnr_conv2d_backward_data")
+    return d_x
+
+
+def conv2d_backward_weight(d_y, x, ksize, stride=1):
+    """pnr_conv2d_backward_weight: the gradient of conv2d_affine's weight.  d_y (N,Cout,Ho,Wo), x (N,Cin,H,W) the forward's
+    input.  -> d_w (Cout,Cin,k,k)"""
+    lib = _lib.load()
+    x = _f32(x, "x", (None, None, None, None))
+    N, Cin, H, W = x.shape
+    k, stride = int(ksize), int(stride)
+    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+    d_y = _f32(d_y, "d_y", (N, None, Ho, Wo))
+    Cout = d_y.shape[1]
+    dev = x.device
+    d_w = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=dev)
+    nbytes = lib.pnr_conv2d_backward_weight_workspace_bytes(N, Cin, H, W, Cout, k, stride)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_conv2d_backward_weight(_p(d_y), _p(x), N, Cin, H, W, Cout, k, stride, _p(d_w), _p(ws), nbytes, _stream()),
+                   "pnr_conv2d_backward_weight")
+    return d_w
+
+
+def maxpool2d_3x3s2_backward(x, g_y):
+    """pnr_maxpool2d_3x3s2_backward: x (N,C,H,W) the pool's input, g_y (N,C,Ho,Wo) -> d_x, bit for bit torch's CPU result"""
+    lib = _lib.load()
+    x = _f32(x, "x", (None, None, None, None))
+    N, C, H, W = x.shape
+    g_y = _f32(g_y, "g_y", (N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1))
+    d_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pnr_maxpool2d_3x3s2_backward(_p(x), _p(g_y), N, C, H, W, _p(d_x), _stream()), "pnr_maxpool2d_3x3s2_backward")
+    return d_x
+
+
+def encoder_trunk_train_records(convs):
+    """convs: [(weight, gamma, beta, running_mean | None, running_var | None, eps, momentum, stride)] in the order the layers run
+    -> (the host array of PnrConvTrainRecord, the tensors it points into: keep both alive together).  The gradient pointers are
+    set by encoder_trunk_backward."""
+    keep, recs = [], (_lib.PnrConvTrainRecord * len(convs))()
+    for i, (weight, gamma, beta, rm, rv, eps, momentum, stride) in enumerate(convs):
+        weight = _f32(weight, f"convs[{i}].weight", (None, None, None, None))
+        Cout, Cin, k, _ = weight.shape
+        gamma, beta = _f32(gamma, f"convs[{i}].gamma", (Cout,)), _f32(beta, f"convs[{i}].beta", (Cout,))
+        for name, t in (("running_mean", rm), ("running_var", rv)):
+            if t is not None and _f32(t, f"convs[{i}].{name}", (Cout,)) is not t:
+                raise ValueError(f"convs[{i}].{name}: must be contiguous (it is updated in place)")
+        keep += [weight, gamma, beta, rm, rv]
+        r = recs[i]
+        r.w, r.gamma, r.beta = weight.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+        r.running_mean = None if rm is None else rm.data_ptr()
+        r.running_var = None if rv is None else rv.data_ptr()
+        r.eps, r.momentum = float(eps), float(momentum)
+        r.cin, r.cout, r.ksize, r.stride = Cin, Cout, k, int(stride)
+    return recs, keep
+
+
+def _trunk_args(images, blocks, n_levels, use_first_pool):
+    images = _f32(images, "images", (None, 3, None, None))
+    if len(blocks) != 4:
+        raise ValueError("blocks: the BasicBlock counts of the four residual stages, e.g. (3, 4, 6, 3)")
+    n_levels = int(n_levels)
+    if not 1 <= n_levels <= 5:
+        raise ValueError(f"n_levels must be in [1, 5], got {n_levels}")
+    return images, (ctypes.c_int * 4)(*[int(b) for b in blocks]), n_levels, 1 if use_first_pool else 0
+
+
+def encoder_trunk_train_forward(images, records, blocks, n_levels, use_first_pool=True, frozen=False):
+    """pnr_encoder_trunk_train_forward: the trunk with batch norm in batch mode (frozen: the running statistics), updating the
+    records' running statistics in place.  -> (levels, saved): saved goes to encoder_trunk_backward unchanged."""
+    lib = _lib.load()
+    images, blk, n_levels, pool = _trunk_args(images, blocks, n_levels, use_first_pool)
+    NV, _, H, W = images.shape
+    dev = images.device
+    levels = []
+    for i in range(n_levels):
+        h, w = encoder_level_shape(H, W, i, use_first_pool)
+        levels.append(torch.empty((NV, (64, 64, 128, 256, 512)[i], h, w), dtype=torch.float32, device=dev))
+    saved = _workspace8(lib.pnr_encoder_trunk_train_saved_bytes(blk, n_levels, pool, NV, H, W), dev)
+    if NV == 0:
+        return levels, saved
+    ptrs = (ctypes.c_void_p * n_levels)(*[t.data_ptr() for t in levels])
+    ws = _workspace8(lib.pnr_encoder_trunk_train_workspace_bytes(blk, n_levels, pool, NV, H, W), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_encoder_trunk_train_forward(records, len(records), blk, n_levels, pool, 1 if frozen else 0, _p(images), NV, H, W,
+                                                       ptrs, _p(saved), saved.numel() * 8, _p(ws), ws.numel() * 8, _stream()),
+                   "pnr_encoder_trunk_train_forward")
+    return levels, saved
+
+
+def encoder_trunk_backward(images, records, blocks, n_levels, use_first_pool, frozen, levels, d_levels, saved, want_images=False):
+    """pnr_encoder_trunk_backward: d_levels the gradients of the levels -> ([(d_w, d_gamma, d_beta)] per record, d_images | None)"""
+    lib = _lib.load()
+    images, blk, n_levels, pool = _trunk_args(images, blocks, n_levels, use_first_pool)
+    NV, _, H, W = images.shape
+    dev = images.device
+    levels = [_f32(t, f"levels[{i}]") for i, t in enumerate(levels)]
+    d_levels = [_f32(g, f"d_levels[{i}]", tuple(t.shape)) for i, (g, t) in enumerate(zip(d_levels, levels))]
+    grads = []
+    for r in records:
+        d_w = torch.empty((r.cout, r.cin, r.ksize, r.ksize), dtype=torch.float32, device=dev)
+        d_g, d_b = torch.empty(r.cout, dtype=torch.float32, device=dev), torch.empty(r.cout, dtype=torch.float32, device=dev)
+        r.d_w, r.d_gamma, r.d_beta = d_w.data_ptr(), d_g.data_ptr(), d_b.data_ptr()
+        grads.append((d_w, d_g, d_b))
+    d_images = torch.empty_like(images) if want_images else None
+    if NV == 0:
+        for t in grads:
+            for g in t:
+                g.zero_()
+        return grads, d_images
+    lp = (ctypes.c_void_p * n_levels)(*[t.data_ptr() for t in levels])
+    gp = (ctypes.c_void_p * n_levels)(*[t.data_ptr() for t in d_levels])
+    ws = _workspace8(lib.pnr_encoder_trunk_train_workspace_bytes(blk, n_levels, pool, NV, H, W), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_encoder_trunk_backward(records, len(records), blk, n_levels, pool, 1 if frozen else 0, _p(images), NV, H, W, lp, gp,
+                                                  _p(saved), saved.numel() * 8, _p(d_images), _p(ws), ws.numel() * 8, _stream()),
+                   "pnr_encoder_trunk_backward")
+    return grads, d_images
+
+
 def sample_training_rays(poses, images, focal, z_near, z_far, ids, c=None, bboxes=None, ux=None, uy=None):
     """train/train.py:143-182 on device.  poses (SB,NV,4,4), images (SB,NV,3,H,W) in [-1,1], focal (SB,2),
     c (SB,2)|None; ids (SB,B) int64: view ids (with bboxes (SB,NV,4) + ux, uy (SB,B)) or flat pixel indices.
